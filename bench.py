@@ -319,6 +319,30 @@ def run_configs(eng, torch, device):
     return out
 
 
+DUMP_SAMPLES = 1 << 20  # entries sampled from each of T and Z (all of them when the factors have fewer)
+
+
+def dump_outputs(path, lam, T, Z, cplx):
+    """The arrays the last timed step handed its caller, as float64 .npy files under `path`: eigenvalues.npy (n x 2: real,
+    imaginary part), and T_sample.npy / Z_sample.npy, the same seeded sample of entries of the packed [p][n][n]
+    column-major blocks of T and Z (ComplexF64: each entry as a (real, imaginary) pair).  At most 16 MB (Float64) or
+    32 MB (ComplexF64) of factor samples."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "eigenvalues.npy"), np.stack([lam.real, lam.imag], axis=1).astype(np.float64))
+    numel = T.numel()
+    if numel <= DUMP_SAMPLES:
+        idx = np.arange(numel, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(20240611).integers(0, numel, size=DUMP_SAMPLES, dtype=np.int64))
+    didx = torch.from_numpy(idx).to(T.device)
+    for name, buf in (("T_sample", T), ("Z_sample", Z)):
+        flat = torch.view_as_real(buf).reshape(-1, 2) if cplx else buf.reshape(-1)
+        np.save(os.path.join(path, name + ".npy"), flat.index_select(0, didx).cpu().numpy().astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -335,6 +359,9 @@ def main():
                     help="c128: BASELINE configs[2] (pschur! of ComplexF64 factors) as the timed workload, e.g. period-sharded: "
                          "--gpus N --dtype c128")
     ap.add_argument("--no-configs", action="store_true", help="skip the one-shot runs of BASELINE configs[1]..[4] behind the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0) as float64 .npy files under DIR: eigenvalues, and a "
+                         "fixed, seeded sample of the Schur factors T and the Schur vectors Z")
     args = ap.parse_args()
 
     import numpy as np
@@ -466,6 +493,8 @@ def main():
         thresh = 100 * np.sqrt(n / 32)
         ok, err, orth, tri = device_gate(lam)
         gate_ok = bool(bool(ok) and float(lam_err) <= 1e-10 and shard_gate_ok)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, lam, bufs[-1], zbufs[-1], cplx)
 
         nwin = sum(s.nwindows for (_, _, s, _) in results)
         nlaunch = sum(s.nlaunch_step for (_, _, s, _) in results)

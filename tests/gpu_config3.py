@@ -1,6 +1,6 @@
 """One full-size run of BASELINE config 3 (pschur! n=1024 p=64 ComplexF64) on one GPU: timing + accuracy gate."""
 import json, sys, time
-sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/tests')
+import os; _T = os.path.dirname(os.path.abspath(__file__)); sys.path.insert(0, os.path.dirname(_T)); sys.path.insert(0, _T)
 import numpy as np
 import torch; torch.cuda.init()
 import psd_amd, psdtest as pt

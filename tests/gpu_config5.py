@@ -1,7 +1,7 @@
 """BASELINE config 5 at full size: pschur!(A,:L) n=1024 p=16 Float64, then ordschur! moving the n/4 eigenvalues of
 largest modulus (conjugates closed) to the top.  Timing + invariants."""
 import json, sys, time
-sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/tests')
+import os; _T = os.path.dirname(os.path.abspath(__file__)); sys.path.insert(0, os.path.dirname(_T)); sys.path.insert(0, _T)
 import numpy as np
 import torch; torch.cuda.init()
 import psd_amd, psdtest as pt

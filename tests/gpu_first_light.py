@@ -1,5 +1,5 @@
 import sys, time
-sys.path.insert(0,'/root/repo'); sys.path.insert(0,'/root/repo/tests')
+import os; _T = os.path.dirname(os.path.abspath(__file__)); sys.path.insert(0, os.path.dirname(_T)); sys.path.insert(0, _T)
 import numpy as np
 import psd_amd, psdtest as pt
 eng = psd_amd.Engine()

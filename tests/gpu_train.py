@@ -1,12 +1,10 @@
 """Experimental multishift trains (psd_set_train) against the default iteration at cfg2 on one GPU: wall time, ticks,
-sweeps, invariants.  usage: gpu_train.py [n] [p] [bulges ...]   (PSD_ELTYPE=c128: ComplexF64; GPU_MAX_HW_QUEUES is raised before HIP starts: every
-cursor needs its own hardware queue to run beside the others)"""
+sweeps, invariants.  usage: gpu_train.py [n] [p] [bulges ...]   (PSD_ELTYPE=c128: ComplexF64)"""
 import json
 import os
 import sys
 import time
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))

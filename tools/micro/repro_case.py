@@ -1,5 +1,6 @@
 import os, sys
-sys.path.insert(0, "/root/repo/tests"); sys.path.insert(0, "/root/repo")
+_R = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.join(_R, "tests")); sys.path.insert(0, _R)
 import numpy as np, torch
 torch.cuda.init()
 import psd_amd, psdtest as pt
