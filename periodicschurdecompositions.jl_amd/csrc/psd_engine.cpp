@@ -46,10 +46,9 @@ psd_simctx psd_sim;
 //  * psd_env(): selectors between code paths that ALL return a correct decomposition (the tests use them to reach every
 //    path of the product library).
 //  * psd_env_diag(): diagnostics, timing experiments and tuning knobs, some of which void the results (the Hessenberg chain
-//    without its panel updates, the panel kernel run on finished matrices, a hand-over that never validates).  They exist
-//    only in a build with -DPSD_DIAG: libpsd_mi355x_diag.so, built beside the product library for tools/ and the
-//    fault-injection test, and the test-only serial simulation.  In the product library a stray environment variable
-//    cannot change what a call returns.
+//    without its panel updates, a hand-over that never validates).  They exist only in a build with -DPSD_DIAG:
+//    libpsd_mi355x_diag.so, built beside the product library for tools/ and the fault-injection test, and the test-only
+//    serial simulation.  In the product library a stray environment variable cannot change what a call returns.
 #define PSD_SL_MAXG_API 8  // (= PSD_SL_MAXG of psd_slice3.h, which the serial simulation does not see)
 static inline const char* psd_env(const char* k) { return getenv(k); }
 #ifdef PSD_DIAG
@@ -290,7 +289,7 @@ struct psd_ctx {
 #ifndef PSD_HOSTSIM
     hipStream_t stream2 = nullptr;  // the far parts of the bulk updates (beside the next tick's chases)
     hipStream_t stream3 = nullptr;  // the panel updates of the Hessenberg reduction (beside its chain)
-    hipStream_t stream4 = nullptr;  // every other chain launch of the Hessenberg reduction in pipe mode (hessenberg2_pipe)
+    hipStream_t stream4 = nullptr;  // the second chain stream of the Hessenberg reduction in pipe mode (h2_chain)
     int hess_pipe_depth = 3;        // chain launches in flight in the pipe form (real reduction): 3 with stream2 — idle during the reduction — as the
                                     // third chain stream, or 2 (PSD_H2_DEPTH).  Measured at n = 1024, p = 64: 409 -> 399 ms
     int hess_pipe = 1;              // PSD_H2_PIPE=0: chain launches back to back on one stream; 2: pipe form also beside other contexts
@@ -689,291 +688,285 @@ static inline bool psd_pipe_form(const psd_ctx* c) {
 }
 
 #ifndef PSD_HOSTSIM
-// look-ahead form (psd_hess2.h): one launch per chain link, the panel updates ride one launch behind the chain
-template <int NK, int CR>
-int hessenberg2_launches(psd_ctx* c, int n, int p, const psd_hess2_args& ha) {
-    const int nC = ((ha.xcd && CR < 16) ? (((n + CR - 1) / CR + 128 / CR - 1) / (128 / CR)) * (128 / CR) : (n + CR - 1) / CR) + 1, nT = (n + PSD_H2_ROWS - 1) / PSD_H2_ROWS, nB = (n + 3) / 4;
-    const size_t lds = ((size_t)n + 8 + 2 * PSD_H2_NT + 64) * sizeof(double);
-    int gridx = nC + nT + nB;
-    auto link = [&](int i, int j) {
-        hipLaunchKernelGGL((psd_hess2_link<NK, CR>), dim3(gridx), dim3(PSD_H2_NT), lds, c->stream, ha, n, i, j, nC, nT);
-    };
+// Look-ahead Hessenberg reduction (psd_hess2.h, psd_zhess2.h): one host path for both element types.
+
+// Diagnostic hooks of the real kernels (diagnostic build): PSD_H2_FAULT, the hand-over to this link never validates (test
+// hook); PSD_H2_TRACE[=<links>], per-link stamps of one chain block, summarised on stderr when the reduction is done.
+struct h2_diag {
+    psd_ctx* c;
+    long long* t = nullptr;
+    static constexpr size_t words = 1024 * 8 + 1024 * 4;
+    h2_diag(psd_ctx* c_, psd_hess2_args& ha) : c(c_) {
+        ha.fault = -1;
+        if (const char* e = psd_env_diag("PSD_H2_FAULT")) ha.fault = atoi(e);
+        ha.trace = nullptr;
+        ha.trace_hi = 0x7fffffff;
+        const char* e = psd_env_diag("PSD_H2_TRACE");
+        if (!e) return;
+        if (atoi(e) > 1) ha.trace_hi = atoi(e);
+        if (psd_rt_malloc((void**)&t, words * sizeof(long long)) != 0) t = nullptr;
+        else if (psd_rt_memset(t, 0, words * sizeof(long long), c->stream) == 0) ha.trace = t;
+    }
+    ~h2_diag() {
+        if (!t) return;
+        std::vector<long long> h(words);
+        (void)psd_rt_sync(c->stream);
+        (void)hipMemcpy(h.data(), t, sizeof(long long) * h.size(), hipMemcpyDeviceToHost);
+        double acc[8] = {0};
+        int cnt = 0;
+        double per = 0;
+        for (int q = 1; q < 1023; ++q) {
+            const long long* a = &h[(size_t)q * 8];
+            const long long* pr = &h[(size_t)(q - 1) * 8];
+            if (a[0] == 0 || a[6] == 0 || pr[0] == 0 || a[0] < pr[0]) continue;
+            for (int k = 1; k <= 6; ++k) acc[k] += (double)(a[k] - a[k - 1]);
+            per += (double)(a[0] - pr[0]);
+            ++cnt;
+        }
+        if (cnt) fprintf(stderr, "psd hess2 trace (last %d links, block 2, us): link period %.2f | ring loads %.2f | norm reduce %.2f | larfg %.2f | v to LDS + publish %.2f | gemv %.2f | finish %.2f\n", cnt, per / cnt / 100.0, acc[1] / cnt / 100.0, acc[2] / cnt / 100.0, acc[3] / cnt / 100.0, acc[4] / cnt / 100.0, acc[5] / cnt / 100.0, acc[6] / cnt / 100.0);
+        const long long* bk = &h[1024 * 8];
+        long long t0 = 0;
+        for (int q = 0; q < 1024; ++q)
+            if (bk[4 * q] && (!t0 || bk[4 * q] < t0)) t0 = bk[4 * q];
+        if (t0) {
+            fprintf(stderr, "psd hess2 trace, one link, per block (start, end in us after the first start):");
+            for (int q = 0; q < 1024; ++q)
+                if (bk[4 * q] && (q < 12 || q % 16 == 0)) fprintf(stderr, " b%d %.2f-%.2f", q, (bk[4 * q] - t0) / 100.0, (bk[4 * q + 1] - t0) / 100.0);
+            double lastend = 0, maxstart = 0;
+            for (int q = 0; q < 1024; ++q)
+                if (bk[4 * q]) {
+                    if ((bk[4 * q + 1] - t0) / 100.0 > lastend) lastend = (bk[4 * q + 1] - t0) / 100.0;
+                    if ((bk[4 * q] - t0) / 100.0 > maxstart) maxstart = (bk[4 * q] - t0) / 100.0;
+                }
+            fprintf(stderr, " | last start %.2f last end %.2f\n", maxstart, lastend);
+        }
+        psd_rt_free(t);
+    }
+};
+struct h2_no_diag {
+    h2_no_diag(psd_ctx*, psd_zhess2_args&) {}
+};
+
+// What the drivers need of an element type: its kernels and argument struct, its ring, and the choices measured per type.
+template <typename T> struct h2_type;
+template <> struct h2_type<double> {
+    typedef psd_hess2_args args;
+    typedef h2_diag diag;
+    static constexpr int NT = PSD_H2_NT, ROWS = PSD_H2_ROWS;
+    static constexpr int CR_LARGE = 8;      // chain rows per block of the 32-column kernel (n > 1024)
+    static constexpr int PIPE_NMAX = 2048;  // (every order of the look-ahead form: hessenberg_dev)
+    template <int NK, int CR>
+    static void link(int grid, size_t lds, hipStream_t s, const args& ha, int n, int i, int j, int nC, int nT) {
+        hipLaunchKernelGGL((psd_hess2_link<NK, CR>), dim3(grid), dim3(NT), lds, s, ha, n, i, j, nC, nT);
+    }
+    template <int NK>
+    static void bulk(int K, size_t lds, hipStream_t s, const args& ha, int n, int idx0, int nT) {
+        hipLaunchKernelGGL((psd_hess2_bulk<NK>), dim3(nT + (n + 3) / 4, K), dim3(NT), lds, s, ha, n, idx0, nT);
+    }
+    static double*& ring(psd_ctx* c) { return c->h2ring; }
+    static int& ring_n(psd_ctx* c) { return c->h2ring_n; }
+    static size_t slot_doubles(int n) { return psd_h2_slot_doubles(n); }
+    // the pipe form's settings; returns its chain streams
+    static int pipe(const psd_ctx* c, int n, args& ha) {
+        ha.pipe = 2;  // (every poll round reads the whole column; 1: a watch round on one record per strip first — one more round trip per link, 477 against 442 ms)
+        if (n > 512 && n <= 1024) ha.xcd = 0;  // (8-row strips: two per line, the mapping no longer pays: 482 -> 474 ms)
+        // 3 with the iteration's second stream (idle here) as the third (c->hess_pipe_depth), only while three launches fit
+        // the chip beside each other with room to spare — n <= 1024: 3 x 129 workgroups of the 16-column kernel, four to a
+        // CU.  The 32-column kernel of larger orders runs two workgroups per CU: a third launch would take slots the second
+        // still needs, and the first could wait for ever — measured: n = 2048 ran into the bounded wait, n = 1536 took
+        // 1.67 s instead of 1.41 s
+        return (c->hess_pipe_depth >= 3 && c->stream2 && n <= 1024) ? 3 : 2;
+    }
+};
+template <> struct h2_type<psd_z> {
+    typedef psd_zhess2_args args;
+    typedef h2_no_diag diag;
+    static constexpr int NT = PSD_ZH2_NT, ROWS = PSD_ZH2_ROWS;
+    static constexpr int CR_LARGE = 4;
+    static constexpr int PIPE_NMAX = 1024;
+    template <int NK, int CR>
+    static void link(int grid, size_t lds, hipStream_t s, const args& ha, int n, int i, int j, int nC, int nT) {
+        hipLaunchKernelGGL((psd_zhess2_link<NK, CR>), dim3(grid), dim3(NT), lds, s, ha, n, i, j, nC, nT);
+    }
+    template <int NK>
+    static void bulk(int K, size_t lds, hipStream_t s, const args& ha, int n, int idx0, int nT) {
+        hipLaunchKernelGGL((psd_zhess2_bulk<NK>), dim3(nT + (n + 3) / 4, K), dim3(NT), lds, s, ha, n, idx0, nT);
+    }
+    static double*& ring(psd_ctx* c) { return c->zh2ring; }
+    static int& ring_n(psd_ctx* c) { return c->zh2ring_n; }
+    static size_t slot_doubles(int n) { return psd_zh2_slot_doubles(n); }
+    static int pipe(const psd_ctx*, int, args& ha) {
+        ha.pipe = 1;
+        return 2;
+    }
+};
+
+// Launch geometry: chain blocks of CR rows (+ 1); strips of ROWS rows above the left reflector and 4-column groups for the
+// panel part.  With xcd, the chain blocks whose strips share a 128-byte line (RPL rows) run on one XCD: their count is
+// rounded up to 8 lines' worth of blocks.
+template <typename T> size_t h2_lds(int n) { return ((size_t)n + 8 + 2 * h2_type<T>::NT + 64) * sizeof(T); }
+template <typename T, int CR> struct h2_grid {
+    static constexpr int RPL = 128 / (int)sizeof(T), G = 8 * RPL / CR;
+    int nC, nT;
+    h2_grid(int n, int xcd) {
+        const int nc = (n + CR - 1) / CR;
+        nC = ((xcd && CR < RPL) ? (nc + G - 1) / G * G : nc) + 1;
+        nT = (n + h2_type<T>::ROWS - 1) / h2_type<T>::ROWS;
+    }
+};
+
+// The events of the multi-stream forms: [3][8] chain-end rings, [8] panel-update ring, start, join.  All or none: when a
+// creation fails, the events made before it are destroyed and the context keeps what it had.
+constexpr size_t PSD_H2_EVENTS = 34;
+int h2_events(psd_ctx* c) {
+    std::vector<hipEvent_t> made;
+    for (size_t q = c->h2ev.size(); q < PSD_H2_EVENTS; ++q) {
+        hipEvent_t e = nullptr;
+        const int rc = (int)hipEventCreateWithFlags(&e, hipEventDisableTiming);
+        if (rc != 0) {
+            for (hipEvent_t m : made) (void)hipEventDestroy(m);
+            return PSD_INFO_RUNTIME + (rc & 0xffff);
+        }
+        made.push_back(e);
+    }
+    c->h2ev.insert(c->h2ev.end(), made.begin(), made.end());
+    return 0;
+}
+
+// One-stream form: one launch per chain link, the panel updates ride one launch behind the chain
+template <typename T, int NK, int CR>
+int h2_launches(psd_ctx* c, int n, int p, const typename h2_type<T>::args& ha) {
+    const h2_grid<T, CR> g(n, ha.xcd);
+    const int grid = g.nC + g.nT + (n + 3) / 4;
+    const size_t lds = h2_lds<T>(n);
+    auto link = [&](int i, int j) { h2_type<T>::template link<NK, CR>(grid, lds, c->stream, ha, n, i, j, g.nC, g.nT); };
     link(0, 1);  // the position before link (1, p): stages column 1 of A_p
     for (int i = 1; i <= n - 1; ++i)
         for (int j = p; j >= 1; --j) link(i, j);
-    link(n, p);      // drain: the panel updates of the last two links
+    link(n, p);  // drain: the panel updates of the last two links
     link(n, p - 1);
     return 0;
 }
-// Two-stream form: the chain launches carry no bulk part; the panel updates of K consecutive links (K distinct
-// matrices) are ONE launch on the CU-masked second stream, up to p - K links behind the chain.  What the chain needs of a
-// matrix — its update by the previous link on it, p links earlier — is awaited by event before the launch that reads it.
-template <int NK, int CR>
-int hessenberg2_async(psd_ctx* c, int n, int p, const psd_hess2_args& ha, int K) {
+
+// Multi-stream forms: the chain launches carry no bulk part; the panel updates of K consecutive links (K distinct matrices)
+// are ONE launch on the CU-masked stream3, up to p - K links behind the chain.  What the chain needs of a matrix — its
+// update by the previous link on it, p links earlier — is awaited by event before the launch that reads it.  The chain
+// launches alternate over NS streams: NS = 1 keeps them on the main stream; NS = 2, 3 is the pipe form (ha.pipe), where the
+// launch of link q + 1 is resident and has requested its strip of the next matrix while the launch of link q still runs;
+// it then polls the staged column, which travels as self-validating records (psd_h2_tag).  At most NS chain launches are
+// in flight (a stream runs its own launches in order), a waiting launch holds one workgroup slot of four per CU, and every
+// wait is bounded.  A batch of panel updates waits for EVERY chain stream (a launch can end before its predecessor's
+// block 0 has stored v and tau), and what the chain needs of a batch is awaited on every chain stream.
+template <typename T, int NK, int CR>
+int h2_chain(psd_ctx* c, int n, int p, const typename h2_type<T>::args& ha, int K, int NS) {
+    typedef h2_type<T> Tr;
     // Every way out (a failed runtime call in the middle of the launch sequence included) first waits for the side streams:
     // their launches read and write the caller's factors and this context's ring.
     struct SideStreams {
         psd_ctx* c;
         ~SideStreams() {
-            if (c->stream3) (void)hipStreamSynchronize(c->stream3);
-            if (c->stream4) (void)hipStreamSynchronize(c->stream4);
+            for (hipStream_t s : {c->stream3, c->stream4, c->stream2})
+                if (s) (void)hipStreamSynchronize(s);
         }
     } side_streams{c};
+    PSD_CHECK(h2_events(c));
 
-    const int nC = ((ha.xcd && CR < 16) ? (((n + CR - 1) / CR + 128 / CR - 1) / (128 / CR)) * (128 / CR) : (n + CR - 1) / CR) + 1, nT = (n + PSD_H2_ROWS - 1) / PSD_H2_ROWS, nB = (n + 3) / 4;
-    const size_t lds = ((size_t)n + 8 + 2 * PSD_H2_NT + 64) * sizeof(double);
-    const int Q = (n - 1) * p;
-    const int nbatch = Q / K + 1;  // link indices 0 .. Q (Q: the drain position)
-    if ((int)c->h2ev.size() < 16) {
-        c->h2ev.resize(16, nullptr);
-        for (auto& e : c->h2ev) PSD_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
+    const h2_grid<T, CR> g(n, ha.xcd);
+    const size_t lds = h2_lds<T>(n);
+    const int nbatch = (n - 1) * p / K + 1;  // link indices 0 .. (n - 1) p, the drain position
     // (an event is re-recorded 8 batches later; the chain awaits batch b while at most (p - K) / K < 8 later ones exist)
-    hipEvent_t* evA = c->h2ev.data();      // [8]: chain reached the end of a batch
-    hipEvent_t* evB = c->h2ev.data() + 8;  // [8]: a batch of panel updates is done
-    // order against whatever ran on the main stream before
-    PSD_CHECK(hipEventRecord(evA[0], c->stream));
-    PSD_CHECK(hipStreamWaitEvent(c->stream3, evA[0], 0));
-    hipLaunchKernelGGL((psd_hess2_link<NK, CR>), dim3(nC), dim3(PSD_H2_NT), lds, c->stream, ha, n, 0, 1, nC, 0);  // staging
-    const int lag = 0;  // (launching a batch later than it could be — so that the chain finds its matrix in the Infinity Cache — was measured in rounds 2 and 3: no gain)
-    int nextb = 0;  // next batch to launch
-    const bool nobulk = psd_env_diag("PSD_H2_NOBULK") != nullptr;  // (timing experiment: the chain alone; results are wrong)
-    auto batch = [&](int b) -> int {
-        PSD_CHECK(hipEventRecord(evA[b & 7], c->stream));
-        PSD_CHECK(hipStreamWaitEvent(c->stream3, evA[b & 7], 0));
-        if (!nobulk) hipLaunchKernelGGL((psd_hess2_bulk<NK>), dim3(nT + nB, K), dim3(PSD_H2_NT), lds, c->stream3, ha, n, b * K, nT);
-        PSD_CHECK(hipEventRecord(evB[b & 7], c->stream3));
-        return 0;
-    };
-    int idx = 0;
-    for (int i = 1; i <= n - 1; ++i)
-        for (int j = p; j >= 1; --j, ++idx) {
-            // chain#idx reads the matrix of link idx + 1, last updated by B(idx + 1 - p): batch (idx + 1 - p) / K
-            const int need = idx + 1 - p;
-            if (need >= 0 && need % K == 0) PSD_CHECK(hipStreamWaitEvent(c->stream, evB[(need / K) & 7], 0));
-            hipLaunchKernelGGL((psd_hess2_link<NK, CR>), dim3(nC), dim3(PSD_H2_NT), lds, c->stream, ha, n, i, j, nC, 0);
-            // links nextb K .. nextb K + K - 1 have their reflectors once the chain has passed the last of them
-            if (idx >= nextb * K + K - 1 + lag) {
-                PSD_CHECK(batch(nextb));
-                ++nextb;
-            }
-        }
-    for (; nextb < nbatch; ++nextb) PSD_CHECK(batch(nextb));  // the rest, up to the drain position Q
-    PSD_CHECK(hipStreamWaitEvent(c->stream, evB[(nbatch - 1) & 7], 0));
-    return 0;
-}
-// Pipe form of the two-stream reduction: the chain launches alternate between two streams, so that the launch of link
-// q + 1 is resident and has requested its strip of the next matrix while the launch of link q still runs; it then polls the
-// staged column, which travels as self-validating records (psd_h2_tag).  At most two chain launches are in flight (a
-// stream runs its own launches in order), a waiting launch holds one workgroup slot of four per CU, and every wait is
-// bounded.  A batch of panel updates waits for BOTH chain streams (a launch can end before its predecessor's block 0 has
-// stored v and tau), and what the chain needs of a batch is awaited on both streams.
-template <int NK, int CR>
-int hessenberg2_pipe(psd_ctx* c, int n, int p, const psd_hess2_args& ha, int K) {
-    // Every way out (a failed runtime call in the middle of the launch sequence included) first waits for the side streams:
-    // their launches read and write the caller's factors and this context's ring.
-    struct SideStreams {
-        psd_ctx* c;
-        ~SideStreams() {
-            if (c->stream3) (void)hipStreamSynchronize(c->stream3);
-            if (c->stream4) (void)hipStreamSynchronize(c->stream4);
-            if (c->stream2) (void)hipStreamSynchronize(c->stream2);
-        }
-    } side_streams{c};
-
-    const int nC = ((ha.xcd && CR < 16) ? (((n + CR - 1) / CR + 128 / CR - 1) / (128 / CR)) * (128 / CR) : (n + CR - 1) / CR) + 1, nT = (n + PSD_H2_ROWS - 1) / PSD_H2_ROWS, nB = (n + 3) / 4;
-    const size_t lds = ((size_t)n + 8 + 2 * PSD_H2_NT + 64) * sizeof(double);
-    const int Q = (n - 1) * p;
-    const int nbatch = Q / K + 1;
-    if ((int)c->h2ev.size() < 34) {
-        const size_t old = c->h2ev.size();
-        c->h2ev.resize(34, nullptr);
-        for (size_t q = old; q < c->h2ev.size(); ++q) PSD_CHECK(hipEventCreateWithFlags(&c->h2ev[q], hipEventDisableTiming));
-    }
-    hipEvent_t* evA = c->h2ev.data();       // [8]: chain stream 0 reached the end of a batch
-    hipEvent_t* evB = c->h2ev.data() + 8;   // [8]: a batch of panel updates is done
-    hipEvent_t* evC = c->h2ev.data() + 16;  // [8]: chain stream 1 reached the end of a batch
-    hipEvent_t evJ = c->h2ev[24], evK = c->h2ev[25];
-    hipEvent_t* evD = c->h2ev.data() + 26;  // [8]: chain stream 2 reached the end of a batch (three-deep form)
-    // NS chain streams: 2, or 3 with the iteration's second stream (idle here) as the third (c->hess_pipe_depth)
-    // (three only while three launches fit the chip beside each other with room to spare — n <= 1024: 3 x 129 workgroups of
-    //  the 16-column kernel, four to a CU.  The 32-column kernel of larger orders runs two workgroups per CU: a third launch
-    //  would take slots the second still needs, and the first could wait for ever — measured: n = 2048 ran into the bounded
-    //  wait, n = 1536 took 1.67 s instead of 1.41 s)
-    const int NS = (c->hess_pipe_depth >= 3 && c->stream2 && n <= 1024) ? 3 : 2;
+    hipEvent_t* evE = c->h2ev.data();       // [NS][8]: chain stream k reached the end of a batch
+    hipEvent_t* evB = c->h2ev.data() + 24;  // [8]: a batch of panel updates is done
+    hipEvent_t evS = c->h2ev[32], evJ = c->h2ev[33];
     hipStream_t S[3] = {c->stream, c->stream4, c->stream2};
-    PSD_CHECK(hipEventRecord(evJ, c->stream));  // (whatever ran on the main stream before: the memsets, the caller's work)
-    PSD_CHECK(hipStreamWaitEvent(c->stream3, evJ, 0));
-    PSD_CHECK(hipStreamWaitEvent(c->stream4, evJ, 0));
-    if (NS == 3) PSD_CHECK(hipStreamWaitEvent(c->stream2, evJ, 0));
-    hipLaunchKernelGGL((psd_hess2_link<NK, CR>), dim3(nC), dim3(PSD_H2_NT), lds, S[0], ha, n, 0, 1, nC, 0);  // staging
-    int nextb = 0;
+    PSD_CHECK(hipEventRecord(evS, c->stream));  // (whatever ran on the main stream before: the memsets, the caller's work)
+    PSD_CHECK(hipStreamWaitEvent(c->stream3, evS, 0));
+    for (int k = 1; k < NS; ++k) PSD_CHECK(hipStreamWaitEvent(S[k], evS, 0));
+    Tr::template link<NK, CR>(g.nC, lds, S[0], ha, n, 0, 1, g.nC, 0);  // staging
     const bool nobulk = psd_env_diag("PSD_H2_NOBULK") != nullptr;  // (timing experiment: the chain alone; results are wrong)
     auto batch = [&](int b) -> int {
-        PSD_CHECK(hipEventRecord(evA[b & 7], S[0]));
-        PSD_CHECK(hipEventRecord(evC[b & 7], S[1]));
-        PSD_CHECK(hipStreamWaitEvent(c->stream3, evA[b & 7], 0));
-        PSD_CHECK(hipStreamWaitEvent(c->stream3, evC[b & 7], 0));
-        if (NS == 3) {
-            PSD_CHECK(hipEventRecord(evD[b & 7], S[2]));
-            PSD_CHECK(hipStreamWaitEvent(c->stream3, evD[b & 7], 0));
+        for (int k = 0; k < NS; ++k) {
+            PSD_CHECK(hipEventRecord(evE[8 * k + (b & 7)], S[k]));
+            PSD_CHECK(hipStreamWaitEvent(c->stream3, evE[8 * k + (b & 7)], 0));
         }
-        if (!nobulk) hipLaunchKernelGGL((psd_hess2_bulk<NK>), dim3(nT + nB, K), dim3(PSD_H2_NT), lds, c->stream3, ha, n, b * K, nT);
+        if (!nobulk) Tr::template bulk<NK>(K, lds, c->stream3, ha, n, b * K, g.nT);
         PSD_CHECK(hipEventRecord(evB[b & 7], c->stream3));
         return 0;
     };
-    int idx = 0;
+    int idx = 0, nextb = 0;
     for (int i = 1; i <= n - 1; ++i)
         for (int j = p; j >= 1; --j, ++idx) {
             hipStream_t s = S[(idx + 1) % NS];
-            // chain#idx reads the matrix of link idx + 1, last updated by B(idx + 1 - p): batch (idx + 1 - p) / K; the launch
-            // behind it, on the other stream, reads a matrix of the same batch
+            // chain#idx reads the matrix of link idx + 1, last updated by B(idx + 1 - p): batch (idx + 1 - p) / K; the NS - 1
+            // launches behind it, on the other chain streams, read matrices of the same batch
             const int need = idx + 1 - p;
-            if (need >= 0 && need % K == 0) PSD_CHECK(hipStreamWaitEvent(s, evB[(need / K) & 7], 0));
-            if (need >= 1 && (need - 1) % K == 0) PSD_CHECK(hipStreamWaitEvent(s, evB[((need - 1) / K) & 7], 0));
-            if (NS == 3 && need >= 2 && (need - 2) % K == 0) PSD_CHECK(hipStreamWaitEvent(s, evB[((need - 2) / K) & 7], 0));
-            hipLaunchKernelGGL((psd_hess2_link<NK, CR>), dim3(nC), dim3(PSD_H2_NT), lds, s, ha, n, i, j, nC, 0);
-            if (idx >= nextb * K + K - 1) {
-                PSD_CHECK(batch(nextb));
-                ++nextb;
-            }
+            for (int d = 0; d < NS; ++d)
+                if (need >= d && (need - d) % K == 0) PSD_CHECK(hipStreamWaitEvent(s, evB[((need - d) / K) & 7], 0));
+            Tr::template link<NK, CR>(g.nC, lds, s, ha, n, i, j, g.nC, 0);
+            // links nextb K .. nextb K + K - 1 have their reflectors once the chain has passed the last of them
+            if (idx >= nextb * K + K - 1) PSD_CHECK(batch(nextb++));
         }
-    for (; nextb < nbatch; ++nextb) PSD_CHECK(batch(nextb));
-    PSD_CHECK(hipEventRecord(evK, S[1]));
-    PSD_CHECK(hipStreamWaitEvent(c->stream, evK, 0));
-    if (NS == 3) {
-        PSD_CHECK(hipEventRecord(evJ, S[2]));
+    for (; nextb < nbatch; ++nextb) PSD_CHECK(batch(nextb));  // the rest, up to the drain position
+    for (int k = 1; k < NS; ++k) {
+        PSD_CHECK(hipEventRecord(evJ, S[k]));
         PSD_CHECK(hipStreamWaitEvent(c->stream, evJ, 0));
     }
     PSD_CHECK(hipStreamWaitEvent(c->stream, evB[(nbatch - 1) & 7], 0));
-    if (psd_env_diag("PSD_H2_BULKBENCH")) {
-        // diagnostics: the panel kernel ALONE on the finished matrices (the transformations it applies are the ring's
-        // leftovers: results void), the first 100 batches back to back on the panel stream
-        PSD_CHECK(hipDeviceSynchronize());
-        hipEvent_t e0, e1;
-        PSD_CHECK(hipEventCreate(&e0));
-        PSD_CHECK(hipEventCreate(&e1));
-        const int nb = nbatch < 100 ? nbatch : 100;
-        for (int which = 0; which < 2; ++which) {
-            hipStream_t st = which ? c->stream : c->stream3;
-            PSD_CHECK(hipEventRecord(e0, st));
-            for (int b = 0; b < nb; ++b)
-                hipLaunchKernelGGL((psd_hess2_bulk<NK>), dim3(nT + nB, K), dim3(PSD_H2_NT), lds, st, ha, n, b * K, nT);
-            PSD_CHECK(hipEventRecord(e1, st));
-            PSD_CHECK(hipStreamSynchronize(st));
-            float ms = 0;
-            PSD_CHECK(hipEventElapsedTime(&ms, e0, e1));
-            double by = 0;
-            for (int idx2 = 0; idx2 < nb * K; ++idx2) by += 16.0 * n * (n - (idx2 / p + 1));
-            fprintf(stderr, "psd hess2 bulk alone (%s stream): %d batches of %d links in %.3f ms = %.1f us per batch, %.0f GB/s algorithmic (read + write)\n",
-                    which ? "unmasked" : "panel", nb, K, ms, 1e3 * ms / nb, by / ms / 1e6);
-        }
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-    }
     return 0;
 }
-int hessenberg2_dev(psd_ctx* c, int n, int p, double* dH, double* dtau) {
-    if (!c->h2ring || c->h2ring_n < n) {
-        if (c->h2ring) psd_rt_free(c->h2ring);
-        c->h2ring = nullptr;
-        PSD_CHECK(psd_rt_malloc((void**)&c->h2ring, PSD_H2_RING * psd_h2_slot_doubles(n) * sizeof(double) + 64));
-        c->h2ring_n = n;
+
+// NS: chain streams of the multi-stream forms, 0 for the one-stream form
+template <typename T, int NK, int CR>
+int h2_form(psd_ctx* c, int n, int p, const typename h2_type<T>::args& ha, int K, int NS) {
+    return NS ? h2_chain<T, NK, CR>(c, n, p, ha, K, NS) : h2_launches<T, NK, CR>(c, n, p, ha);
+}
+
+template <typename T>
+int hessenberg2_dev(psd_ctx* c, int n, int p, T* dH, T* dtau) {
+    typedef h2_type<T> Tr;
+    if (h2_lds<T>(n) > 64 * 1024) return PSD_INFO_NOTIMPL;
+    const size_t slot = Tr::slot_doubles(n);
+    const size_t ringbytes = PSD_H2_RING * slot * sizeof(double) + 64;  // (+ the pipe form's error word)
+    double*& ring = Tr::ring(c);
+    if (!ring || Tr::ring_n(c) < n) {
+        if (ring) psd_rt_free(ring);
+        ring = nullptr;
+        PSD_CHECK(psd_rt_malloc((void**)&ring, ringbytes));
+        Tr::ring_n(c) = n;
     }
-    PSD_CHECK(psd_rt_memset(c->h2ring, 0, PSD_H2_RING * psd_h2_slot_doubles(c->h2ring_n) * sizeof(double) + 64, c->stream));
-    psd_hess2_args ha;
+    PSD_CHECK(psd_rt_memset(ring, 0, ringbytes, c->stream));
+    typename Tr::args ha{};
     ha.H = dH;
     ha.tau = dtau;
-    ha.ring = c->h2ring;
+    ha.ring = ring;
     ha.p = p;
     ha.ringmask = 3;
     ha.xcd = c->hess_xcd;
-    ha.trace = nullptr;
-    ha.trace_hi = 0x7fffffff;
-    ha.pipe = 0;
-    ha.fault = -1;
-    if (const char* e = psd_env_diag("PSD_H2_FAULT")) ha.fault = atoi(e);  // (test hook: the hand-over to this link never validates)
-    ha.err = (int*)(c->h2ring + PSD_H2_RING * psd_h2_slot_doubles(c->h2ring_n));
-    if (const char* e = psd_env_diag("PSD_H2_TRACE")) { if (atoi(e) > 1) ha.trace_hi = atoi(e); }
-    long long* h2trace = nullptr;
-    if (psd_env_diag("PSD_H2_TRACE") && psd_rt_malloc((void**)&h2trace, (1024 * 8 + 1024 * 4) * sizeof(long long)) == 0) {
-        PSD_CHECK(psd_rt_memset(h2trace, 0, (1024 * 8 + 1024 * 4) * sizeof(long long), c->stream));
-        ha.trace = h2trace;
-    }
-    struct H2TraceDump {
-        psd_ctx* c;
-        long long* t;
-        ~H2TraceDump() {
-            if (!t) return;
-            std::vector<long long> h(1024 * 8 + 1024 * 4);
-            (void)psd_rt_sync(c->stream);
-            (void)hipMemcpy(h.data(), t, sizeof(long long) * h.size(), hipMemcpyDeviceToHost);
-            double acc[8] = {0};
-            int cnt = 0;
-            double per = 0;
-            for (int q = 1; q < 1023; ++q) {
-                const long long* a = &h[(size_t)q * 8];
-                const long long* pr = &h[(size_t)(q - 1) * 8];
-                if (a[0] == 0 || a[6] == 0 || pr[0] == 0 || a[0] < pr[0]) continue;
-                for (int k = 1; k <= 6; ++k) acc[k] += (double)(a[k] - a[k - 1]);
-                per += (double)(a[0] - pr[0]);
-                ++cnt;
-            }
-            if (cnt) fprintf(stderr, "psd hess2 trace (last %d links, block 2, us): link period %.2f | ring loads %.2f | norm reduce %.2f | larfg %.2f | v to LDS + publish %.2f | gemv %.2f | finish %.2f\n", cnt, per / cnt / 100.0, acc[1] / cnt / 100.0, acc[2] / cnt / 100.0, acc[3] / cnt / 100.0, acc[4] / cnt / 100.0, acc[5] / cnt / 100.0, acc[6] / cnt / 100.0);
-            {
-                const long long* bk = &h[1024 * 8];
-                long long t0 = 0;
-                for (int q = 0; q < 1024; ++q)
-                    if (bk[4 * q] && (!t0 || bk[4 * q] < t0)) t0 = bk[4 * q];
-                if (t0) {
-                    fprintf(stderr, "psd hess2 trace, one link, per block (start, end in us after the first start):");
-                    for (int q = 0; q < 1024; ++q)
-                        if (bk[4 * q] && (q < 12 || q % 16 == 0)) fprintf(stderr, " b%d %.2f-%.2f", q, (bk[4 * q] - t0) / 100.0, (bk[4 * q + 1] - t0) / 100.0);
-                    double lastend = 0, maxstart = 0;
-                    for (int q = 0; q < 1024; ++q)
-                        if (bk[4 * q]) {
-                            if ((bk[4 * q + 1] - t0) / 100.0 > lastend) lastend = (bk[4 * q + 1] - t0) / 100.0;
-                            if ((bk[4 * q] - t0) / 100.0 > maxstart) maxstart = (bk[4 * q] - t0) / 100.0;
-                        }
-                    fprintf(stderr, " | last start %.2f last end %.2f\n", maxstart, lastend);
-                }
-            }
-            psd_rt_free(t);
-        }
-    } h2dump{c, h2trace};
-    // two-stream form: K links per panel-update launch; the chain may run p - K links ahead of the updates and the ring
+    ha.err = (int*)(ring + PSD_H2_RING * slot);
+    typename Tr::diag diag(c, ha);
+    // multi-stream forms: K links per panel-update launch; the chain may run p - K links ahead of the updates and the ring
     // keeps every link the pending updates still read (p + K + 2 <= PSD_H2_RING)
     int K = c->hess_async;
-    if (K < 0) K = (p >= 32 && n >= 512) ? ((p >= 48 && c->hess_pipe && c->stream4) ? 24 : 16) : 0;  // (measured at p = 64: 16 / 24 / 32 links per batch 548 / 529 / 540 ms)
+    if (K < 0) K = (p >= 32 && n >= 512) ? ((p >= 48 && c->hess_pipe && c->stream4 && n <= Tr::PIPE_NMAX) ? 24 : 16) : 0;  // (measured at p = 64: 16 / 24 / 32 links per batch 548 / 529 / 540 ms real, 633 / 604 / 621 ms complex)
     if (K > 0 && p >= 9 * K) K = (p + 7) / 8;
+    int NS = 0;
     if (K > 0 && p >= 2 * K && p + K + 2 <= PSD_H2_RING && c->stream3) {
         ha.ringmask = PSD_H2_RING - 1;
-        if (c->stream4 && psd_pipe_form(c)) {  // (PSD_H2_PIPE=2: also beside other contexts)
-            ha.pipe = 2;  // (every poll round reads the whole column; 1: a watch round on one record per strip first — one more round trip per link, 477 against 442 ms)
-            if (n > 512 && n <= 1024) ha.xcd = 0;  // (8-row strips: two per line, the mapping no longer pays: 482 -> 474 ms)
-            int rc;
-            if (n <= 256) rc = hessenberg2_pipe<4, 8>(c, n, p, ha, K);
-            else if (n <= 512) rc = hessenberg2_pipe<8, 8>(c, n, p, ha, K);
-            // (strips of 8 rows here, 4 in the one-stream forms: with the strip requested before the wait the GEMV no longer
-            //  needs every CU's memory pipeline, and half as many workgroups poll; measured 4 / 8 / 16 / 32 rows: 519 / 483 / 542 / 570 ms)
-            else if (n <= 1024) rc = hessenberg2_pipe<16, 8>(c, n, p, ha, K);
-            else rc = hessenberg2_pipe<32, 8>(c, n, p, ha, K);
-            if (rc != 0) return rc;
-            // (a launch that gave up waiting left void results: say so.  One word, read when the reduction is done)
-            int herr = 0;
-            PSD_CHECK(psd_rt_d2h(&herr, ha.err, sizeof(int), c->stream));
-            PSD_CHECK(psd_rt_sync(c->stream));
-            return herr ? PSD_INFO_RUNTIME + 0xfffb : 0;
-        }
-        if (n <= 256) return hessenberg2_async<4, 8>(c, n, p, ha, K);
-        if (n <= 512) return hessenberg2_async<8, 8>(c, n, p, ha, K);
-        if (n <= 1024) return hessenberg2_async<16, 4>(c, n, p, ha, K);
-        return hessenberg2_async<32, 8>(c, n, p, ha, K);
+        NS = (n <= Tr::PIPE_NMAX && psd_pipe_form(c)) ? Tr::pipe(c, n, ha) : 1;  // (PSD_H2_PIPE=2: also beside other contexts)
     }
-    if (n <= 256) return hessenberg2_launches<4, 8>(c, n, p, ha);
-    if (n <= 512) return hessenberg2_launches<8, 8>(c, n, p, ha);
-    if (n <= 1024) return hessenberg2_launches<16, 4>(c, n, p, ha);
-    return hessenberg2_launches<32, 8>(c, n, p, ha);
+    int rc;
+    if (n <= 256) rc = h2_form<T, 4, 8>(c, n, p, ha, K, NS);
+    else if (n <= 512) rc = h2_form<T, 8, 8>(c, n, p, ha, K, NS);
+    // (strips of 8 rows in the pipe form, 4 in the others: with the strip requested before the wait the GEMV no longer needs
+    //  every CU's memory pipeline, and half as many workgroups poll; measured 4 / 8 / 16 / 32 rows: 519 / 483 / 542 / 570 ms)
+    else if (n <= 1024) rc = NS >= 2 ? h2_form<T, 16, 8>(c, n, p, ha, K, NS) : h2_form<T, 16, 4>(c, n, p, ha, K, NS);
+    else rc = h2_form<T, 32, Tr::CR_LARGE>(c, n, p, ha, K, NS);
+    if (rc != 0 || NS < 2) return rc;
+    // (a pipe launch that gave up waiting left void results: say so.  One word, read when the reduction is done)
+    int herr = 0;
+    PSD_CHECK(psd_rt_d2h(&herr, ha.err, sizeof(int), c->stream));
+    PSD_CHECK(psd_rt_sync(c->stream));
+    return herr ? PSD_INFO_RUNTIME + 0xfffb : 0;
 }
 #endif
 
@@ -1693,7 +1686,7 @@ int psd_create(psd_ctx** ctx, int device) {
         }
         // the same for the panel updates of the Hessenberg reduction: its chain launches are HBM-latency chains that
         // slow down under the panel traffic; half of the chip for the panels measured best (PSD_HESS_CUS)
-        int keeph = 64;  // (128 until the chain launches overlapped: hessenberg2_pipe)
+        int keeph = 64;  // (128 until the chain launches overlapped: the pipe form of h2_chain)
         if (const char* e = psd_env_diag("PSD_HESS_CUS")) keeph = atoi(e);
         rc = hipErrorInvalidValue;
         if (ncu > keeph + 32 && keeph > 0 && ncu <= 1024) {
@@ -2010,189 +2003,12 @@ int psd_d_pschur_hess(psd_ctx* c, int n, int p, double* const* H, double* const*
 // complex path
 namespace {
 
-#ifndef PSD_HOSTSIM
-// look-ahead form (psd_zhess2.h), the complex counterparts of hessenberg2_launches / hessenberg2_async
-template <int NK, int CR>
-int zhessenberg2_launches(psd_ctx* c, int n, int p, const psd_zhess2_args& ha) {
-    constexpr int LG = 64 / CR;  // chain blocks per group of 8 lines (16-byte elements: 8 rows per 128-byte line)
-    const int nC = ((ha.xcd && CR < 8) ? (((n + CR - 1) / CR + LG - 1) / LG) * LG : (n + CR - 1) / CR) + 1, nT = (n + PSD_ZH2_ROWS - 1) / PSD_ZH2_ROWS, nB = (n + 3) / 4;
-    const size_t lds = ((size_t)n + 8 + 2 * PSD_ZH2_NT + 64) * sizeof(psd_z);
-    const int gridx = nC + nT + nB;
-    auto link = [&](int i, int j) {
-        hipLaunchKernelGGL((psd_zhess2_link<NK, CR>), dim3(gridx), dim3(PSD_ZH2_NT), lds, c->stream, ha, n, i, j, nC, nT);
-    };
-    link(0, 1);
-    for (int i = 1; i <= n - 1; ++i)
-        for (int j = p; j >= 1; --j) link(i, j);
-    link(n, p);
-    link(n, p - 1);
-    return 0;
-}
-template <int NK, int CR>
-int zhessenberg2_async(psd_ctx* c, int n, int p, const psd_zhess2_args& ha, int K) {
-    // Every way out (a failed runtime call in the middle of the launch sequence included) first waits for the side streams:
-    // their launches read and write the caller's factors and this context's ring.
-    struct SideStreams {
-        psd_ctx* c;
-        ~SideStreams() {
-            if (c->stream3) (void)hipStreamSynchronize(c->stream3);
-            if (c->stream4) (void)hipStreamSynchronize(c->stream4);
-        }
-    } side_streams{c};
-
-    constexpr int LG = 64 / CR;
-    const int nC = ((ha.xcd && CR < 8) ? (((n + CR - 1) / CR + LG - 1) / LG) * LG : (n + CR - 1) / CR) + 1, nT = (n + PSD_ZH2_ROWS - 1) / PSD_ZH2_ROWS, nB = (n + 3) / 4;
-    const size_t lds = ((size_t)n + 8 + 2 * PSD_ZH2_NT + 64) * sizeof(psd_z);
-    const int Q = (n - 1) * p;
-    const int nbatch = Q / K + 1;
-    if ((int)c->h2ev.size() < 16) {
-        c->h2ev.resize(16, nullptr);
-        for (auto& e : c->h2ev) PSD_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    hipEvent_t* evA = c->h2ev.data();
-    hipEvent_t* evB = c->h2ev.data() + 8;
-    PSD_CHECK(hipEventRecord(evA[0], c->stream));
-    PSD_CHECK(hipStreamWaitEvent(c->stream3, evA[0], 0));
-    hipLaunchKernelGGL((psd_zhess2_link<NK, CR>), dim3(nC), dim3(PSD_ZH2_NT), lds, c->stream, ha, n, 0, 1, nC, 0);
-    int nextb = 0;
-    auto batch = [&](int b) -> int {
-        PSD_CHECK(hipEventRecord(evA[b & 7], c->stream));
-        PSD_CHECK(hipStreamWaitEvent(c->stream3, evA[b & 7], 0));
-        hipLaunchKernelGGL((psd_zhess2_bulk<NK>), dim3(nT + nB, K), dim3(PSD_ZH2_NT), lds, c->stream3, ha, n, b * K, nT);
-        PSD_CHECK(hipEventRecord(evB[b & 7], c->stream3));
-        return 0;
-    };
-    int idx = 0;
-    for (int i = 1; i <= n - 1; ++i)
-        for (int j = p; j >= 1; --j, ++idx) {
-            const int need = idx + 1 - p;
-            if (need >= 0 && need % K == 0) PSD_CHECK(hipStreamWaitEvent(c->stream, evB[(need / K) & 7], 0));
-            hipLaunchKernelGGL((psd_zhess2_link<NK, CR>), dim3(nC), dim3(PSD_ZH2_NT), lds, c->stream, ha, n, i, j, nC, 0);
-            if (idx >= nextb * K + K - 1) {
-                PSD_CHECK(batch(nextb));
-                ++nextb;
-            }
-        }
-    for (; nextb < nbatch; ++nextb) PSD_CHECK(batch(nextb));
-    PSD_CHECK(hipStreamWaitEvent(c->stream, evB[(nbatch - 1) & 7], 0));
-    return 0;
-}
-// pipe form for ComplexF64 (see hessenberg2_pipe)
-template <int NK, int CR>
-int zhessenberg2_pipe(psd_ctx* c, int n, int p, const psd_zhess2_args& ha, int K) {
-    // Every way out (a failed runtime call in the middle of the launch sequence included) first waits for the side streams:
-    // their launches read and write the caller's factors and this context's ring.
-    struct SideStreams {
-        psd_ctx* c;
-        ~SideStreams() {
-            if (c->stream3) (void)hipStreamSynchronize(c->stream3);
-            if (c->stream4) (void)hipStreamSynchronize(c->stream4);
-        }
-    } side_streams{c};
-
-    constexpr int LG = 64 / CR;
-    const int nC = ((ha.xcd && CR < 8) ? (((n + CR - 1) / CR + LG - 1) / LG) * LG : (n + CR - 1) / CR) + 1, nT = (n + PSD_ZH2_ROWS - 1) / PSD_ZH2_ROWS, nB = (n + 3) / 4;
-    const size_t lds = ((size_t)n + 8 + 2 * PSD_ZH2_NT + 64) * sizeof(psd_z);
-    const int Q = (n - 1) * p;
-    const int nbatch = Q / K + 1;
-    if ((int)c->h2ev.size() < 26) {
-        const size_t old = c->h2ev.size();
-        c->h2ev.resize(26, nullptr);
-        for (size_t q = old; q < c->h2ev.size(); ++q) PSD_CHECK(hipEventCreateWithFlags(&c->h2ev[q], hipEventDisableTiming));
-    }
-    hipEvent_t* evA = c->h2ev.data();
-    hipEvent_t* evB = c->h2ev.data() + 8;
-    hipEvent_t* evC = c->h2ev.data() + 16;
-    hipEvent_t evJ = c->h2ev[24], evK = c->h2ev[25];
-    hipStream_t S[2] = {c->stream, c->stream4};
-    PSD_CHECK(hipEventRecord(evJ, c->stream));
-    PSD_CHECK(hipStreamWaitEvent(c->stream3, evJ, 0));
-    PSD_CHECK(hipStreamWaitEvent(c->stream4, evJ, 0));
-    hipLaunchKernelGGL((psd_zhess2_link<NK, CR>), dim3(nC), dim3(PSD_ZH2_NT), lds, S[0], ha, n, 0, 1, nC, 0);
-    int nextb = 0;
-    auto batch = [&](int b) -> int {
-        PSD_CHECK(hipEventRecord(evA[b & 7], S[0]));
-        PSD_CHECK(hipEventRecord(evC[b & 7], S[1]));
-        PSD_CHECK(hipStreamWaitEvent(c->stream3, evA[b & 7], 0));
-        PSD_CHECK(hipStreamWaitEvent(c->stream3, evC[b & 7], 0));
-        hipLaunchKernelGGL((psd_zhess2_bulk<NK>), dim3(nT + nB, K), dim3(PSD_ZH2_NT), lds, c->stream3, ha, n, b * K, nT);
-        PSD_CHECK(hipEventRecord(evB[b & 7], c->stream3));
-        return 0;
-    };
-    int idx = 0;
-    for (int i = 1; i <= n - 1; ++i)
-        for (int j = p; j >= 1; --j, ++idx) {
-            hipStream_t s = S[(idx + 1) & 1];
-            const int need = idx + 1 - p;
-            if (need >= 0 && need % K == 0) PSD_CHECK(hipStreamWaitEvent(s, evB[(need / K) & 7], 0));
-            if (need >= 1 && (need - 1) % K == 0) PSD_CHECK(hipStreamWaitEvent(s, evB[((need - 1) / K) & 7], 0));
-            hipLaunchKernelGGL((psd_zhess2_link<NK, CR>), dim3(nC), dim3(PSD_ZH2_NT), lds, s, ha, n, i, j, nC, 0);
-            if (idx >= nextb * K + K - 1) {
-                PSD_CHECK(batch(nextb));
-                ++nextb;
-            }
-        }
-    for (; nextb < nbatch; ++nextb) PSD_CHECK(batch(nextb));
-    PSD_CHECK(hipEventRecord(evK, S[1]));
-    PSD_CHECK(hipStreamWaitEvent(c->stream, evK, 0));
-    PSD_CHECK(hipStreamWaitEvent(c->stream, evB[(nbatch - 1) & 7], 0));
-    return 0;
-}
-int zhessenberg2_dev(psd_ctx* c, int n, int p, psd_z* dH, psd_z* dtau) {
-    const size_t ringbytes = PSD_H2_RING * psd_zh2_slot_doubles(n) * sizeof(double) + 64;  // (+ the pipe form's error word)
-    if (!c->zh2ring || c->zh2ring_n < n) {
-        if (c->zh2ring) psd_rt_free(c->zh2ring);
-        c->zh2ring = nullptr;
-        PSD_CHECK(psd_rt_malloc((void**)&c->zh2ring, ringbytes));
-        c->zh2ring_n = n;
-    }
-    PSD_CHECK(psd_rt_memset(c->zh2ring, 0, ringbytes, c->stream));
-    psd_zhess2_args ha;
-    ha.H = dH;
-    ha.tau = dtau;
-    ha.ring = c->zh2ring;
-    ha.p = p;
-    ha.ringmask = 3;
-    ha.xcd = c->hess_xcd;
-    ha.pipe = 0;
-    ha.err = (int*)(c->zh2ring + PSD_H2_RING * psd_zh2_slot_doubles(n));
-    const size_t lds = ((size_t)n + 8 + 2 * PSD_ZH2_NT + 64) * sizeof(psd_z);
-    if (lds > 64 * 1024) return PSD_INFO_NOTIMPL;
-    int K = c->hess_async;
-    if (K < 0) K = (p >= 32 && n >= 512) ? ((p >= 48 && c->hess_pipe && c->stream4 && n <= 1024) ? 24 : 16) : 0;  // (as hessenberg2_dev: 16 / 24 / 32 links per batch 633 / 604 / 621 ms at p = 64)
-    if (K > 0 && p >= 9 * K) K = (p + 7) / 8;
-    if (K > 0 && p >= 2 * K && p + K + 2 <= PSD_H2_RING && c->stream3) {
-        ha.ringmask = PSD_H2_RING - 1;
-        if (c->stream4 && n <= 1024 && psd_pipe_form(c)) {
-            ha.pipe = 1;
-            int rc;
-            if (n <= 256) rc = zhessenberg2_pipe<4, 8>(c, n, p, ha, K);
-            else if (n <= 512) rc = zhessenberg2_pipe<8, 8>(c, n, p, ha, K);
-            else rc = zhessenberg2_pipe<16, 8>(c, n, p, ha, K);
-            if (rc != 0) return rc;
-            int herr = 0;
-            PSD_CHECK(psd_rt_d2h(&herr, ha.err, sizeof(int), c->stream));
-            PSD_CHECK(psd_rt_sync(c->stream));
-            return herr ? PSD_INFO_RUNTIME + 0xfffb : 0;
-        }
-        if (n <= 256) return zhessenberg2_async<4, 8>(c, n, p, ha, K);
-        if (n <= 512) return zhessenberg2_async<8, 8>(c, n, p, ha, K);
-        if (n <= 1024) return zhessenberg2_async<16, 4>(c, n, p, ha, K);
-        return zhessenberg2_async<32, 4>(c, n, p, ha, K);
-    }
-    if (n <= 256) return zhessenberg2_launches<4, 8>(c, n, p, ha);
-    if (n <= 512) return zhessenberg2_launches<8, 8>(c, n, p, ha);
-    if (n <= 1024) return zhessenberg2_launches<16, 4>(c, n, p, ha);
-    return zhessenberg2_launches<32, 4>(c, n, p, ha);
-}
-#endif
-
 int zhessenberg_dev(psd_ctx* c, int n, int p, psd_z* dH, psd_z* dtau) {
     const size_t nn = (size_t)n * n;
     PSD_CHECK(psd_rt_memset(dtau, 0, sizeof(psd_z) * (size_t)n * p, c->stream));
     if (n < 2) return 0;
 #ifndef PSD_HOSTSIM
-    if (p >= 3 && n <= 2048 && c->hess_lookahead) return zhessenberg2_dev(c, n, p, dH, dtau);
+    if (p >= 3 && n <= 2048 && c->hess_lookahead) return hessenberg2_dev(c, n, p, dH, dtau);
 #endif
     const size_t lds_refl = PSD_HESS_NT * 8;
     const size_t lds_apply = (PSD_HESS_NT + (size_t)n + 8) * sizeof(psd_z);

@@ -201,7 +201,7 @@ PSD_D void psd_h2_larfg(double alpha, double xnorm, double& tau, double& beta, d
 // (w of the right reflector, v of the left one: 16 + 16 doubles per lane) stay in registers for all of the wave's columns,
 // and the next column is requested before the current one is reduced.  One column per wave read both vectors again for
 // every column (two thirds of its load instructions, all L2 traffic) and had one column's loads in flight per wave:
-// the panel kernel alone ran at 2.3 TB/s on its 192 CUs (PSD_H2_BULKBENCH).
+// the panel kernel alone ran at 2.3 TB/s on its 192 CUs (round-3 measurement).
 template <int NKC>
 PSD_D void psd_h2_col_load(const double* M, int n, int R0, int mL, int c, int lane, double (&a0)[NKC], double (&a1)[NKC]) {
 #pragma unroll

@@ -248,11 +248,12 @@ def test_formq_blocked(monkeypatch):
     ec.case_formq_blocked(make, [(64, 3, "R"), (97, 2, "L"), (130, 1, "R"), (257, 5, "R"), (512, 4, "L")])
 
 
-@pytest.mark.parametrize("pipe", ["2", "0"])
+@pytest.mark.parametrize("pipe,depth", [("2", None), ("0", None), ("2", "2")], ids=["2", "0", "2-depth2"])
 @pytest.mark.parametrize("n,p,K", [(33, 8, 4), (130, 9, 4), (257, 16, 8), (300, 40, 16), (64, 70, 16), (96, 150, 16)])
-def test_phessenberg_two_stream_vs_oracle(monkeypatch, n, p, K, pipe):
-    """The multi-stream forms of the look-ahead reduction — pipe "2": consecutive chain launches overlap on two streams
-    and hand the staged column over as self-validating records; "0": back to back on one stream.
+def test_phessenberg_two_stream_vs_oracle(monkeypatch, n, p, K, pipe, depth):
+    """The multi-stream forms of the look-ahead reduction — pipe "2": consecutive chain launches overlap on three streams
+    (two with PSD_H2_DEPTH=2) and hand the staged column over as self-validating records; "0":
+    back to back on one stream.
     The two-stream form of the look-ahead reduction (chain launches alone on the main stream, the panel updates of K
     consecutive links as one launch on the second stream, awaited by event p - 1 links later; by itself only for
     p >= 32, n >= 512) forced on small problems: periods that are not multiples of K, a last batch that is only the
@@ -264,6 +265,8 @@ def test_phessenberg_two_stream_vs_oracle(monkeypatch, n, p, K, pipe):
 
     monkeypatch.setenv("PSD_HESS_ASYNC", str(K))
     monkeypatch.setenv("PSD_H2_PIPE", pipe)  # ("2": overlapping chain launches although the session's engine is alive too)
+    if depth:
+        monkeypatch.setenv("PSD_H2_DEPTH", depth)
     eng = psd_amd.Engine(device=0)
     A = pt.bench_factors(n, p, seed=170 + n + p)
     W = [a.copy(order="F") for a in A]
