@@ -264,6 +264,73 @@ int psd_d_checkpsd_dev(psd_ctx* ctx, int n, int p, const double* dT, const doubl
                        const uint8_t* S, char orient, int schurindex, double thresh, int strict, double* err,
                        double* orth, double* tri, int* ok, int* info);
 
+/* ---- partial_pschur: periodic Krylov-Schur for dense factors — src/krylov.jl:446-798 (D. Kressner, Numer. Math. 2006) --
+ * A `nev`-order partial periodic Schur decomposition of the product A_p ... A_2 A_1 in the LEFT orientation of the
+ * reference (krylov.jl:87-139):  A_l Z_l = Z_{l+1} T_l (l < p),  A_p Z_p = Z_1 T_p,  Z_l n x nconv orthonormal, T_p the
+ * quasi-triangular factor (schurindex = p), T_1..T_{p-1} upper triangular.  The factors stay resident on the device; one
+ * Krylov step is p matrix-vector products and the orthogonalisation of each result, with the decisions of the
+ * Gram-Schmidt rule (re-orthogonalise once when ||w|| < ||r|| / sqrt(2), in span when that still fails) taken on the
+ * device and read back once per step.  The projected problems (order <= maxdim) go through the engine's own
+ * psd_?_pschur_hess, psd_?_ordschur and psd_?_rphessenberg on the same context.
+ *
+ * Arguments are the reference's keywords: which = 'M' (LM, largest magnitude), 'R' (LR), 'r' (SR), 'I' (LI), 'i' (SI);
+ * mindim / maxdim the kept and the maximal subspace order; tol the convergence tolerance (reference default sqrt(eps));
+ * tol1 the null-vector threshold of the start (100 eps); restarts the restart limit (100); purgebuffer (2).  u1 (host, n
+ * elements, may be NULL): start vector; without it the start comes from a counter-based generator seeded by `seed` (the
+ * reference's `vrand!` cannot cross the ABI), so that a run can be repeated bit for bit.
+ *
+ * Outputs: *nconv converged Schur vectors (History.nconverged); T: p host buffers of maxdim * maxdim elements, T[l] the
+ * nconv x nconv factor T_{l+1} (ld nconv); Z: p buffers of n * maxdim elements, Z[l] the n x nconv block Z_{l+1} (ld n);
+ * wr / wi: maxdim entries, the first nconv the eigenvalues (P.values); stats (may be NULL): History and counters.
+ *
+ * info: 0 (also when not converged: stats->converged = 0, as History.converged); <0 argument -k invalid, checked before
+ * the device is touched:
+ *   -1 ctx NULL; -2 n < 1; -3 p < 1; -4 A NULL;  -5 nev < 1 (krylov.jl:462); -6 which not one of M R r I i;
+ *   -7 not nev <= mindim <= maxdim <= p n (krylov.jl:465-466); -8 maxdim above PSD_KRYLOV_MAXDIM;
+ *   -9 u1 zero or not finite; -11 tol not > 0; -12 tol1 < 0; -13 restarts < 0; -14 purgebuffer < 0;
+ *   -15 nconv NULL; -16 T NULL; -17 Z NULL; -18 wr or wi NULL;
+ * PSD_INFO_PKSFAIL: PKSFailure("Arnoldi reinitialization failed") (krylov.jl:182); PSD_INFO_ILLCOND + j: reordering of
+ * the locked Ritz values failed (IllConditionedException(j), which the reference does not catch there, :625);
+ * PSD_INFO_RUNTIME + k: HIP runtime failure.
+ * ComplexF64 (psd_z_*): A, T, Z, u1 interleaved (re, im); wr / wi still the real and imaginary parts of P.values. */
+#define PSD_INFO_PKSFAIL 5000
+#define PSD_KRYLOV_MAXDIM 2048
+
+typedef struct psd_krylov_stats {
+    int64_t nprods;      /* History.mvproducts: matrix-vector products (p per Krylov step)                    */
+    int32_t nconverged;  /* History.nconverged                                                                 */
+    int32_t converged;   /* History.converged (nconv >= nev)                                                   */
+    int32_t nev;         /* History.nev                                                                        */
+    int32_t restarts;    /* restart iterations run                                                             */
+    int32_t nreorth;     /* second Gram-Schmidt passes                                                         */
+    int32_t nreinit;     /* re-initialised basis vectors (_reinitialize!, krylov.jl:152-182)                   */
+    int32_t ndeflate;    /* deflations for a singular factor (_deflate!, krylov.jl:184-226)                    */
+    int32_t suspect;     /* 1: the Arnoldi process gave up (> 5 singularities): results suspect (krylov.jl:781)  */
+    double ms_arnoldi;   /* Arnoldi extensions: matvecs, orthogonalisation, host reads (host clock)            */
+    double ms_proj;      /* projected problems: pschur!, ordschur!, residuals, _rphessenberg! (host clock)      */
+    double ms_basis;     /* basis updates V_l <- V_l Q_l (host clock around a synchronise)                     */
+    double ms_total;     /* whole call (host entry: including the copies of A and the results)                 */
+} psd_krylov_stats;
+
+int psd_d_partial_pschur(psd_ctx* ctx, int n, int p, const double* const* A, int nev, char which, int mindim,
+                         int maxdim, const double* u1, uint64_t seed, double tol, double tol1, int restarts,
+                         int purgebuffer, int* nconv, double* const* T, double* const* Z, double* wr, double* wi,
+                         psd_krylov_stats* stats, int* info);
+int psd_z_partial_pschur(psd_ctx* ctx, int n, int p, const double* const* A, int nev, char which, int mindim,
+                         int maxdim, const double* u1, uint64_t seed, double tol, double tol1, int restarts,
+                         int purgebuffer, int* nconv, double* const* T, double* const* Z, double* wr, double* wi,
+                         psd_krylov_stats* stats, int* info);
+/* Device-resident variants: dA a device [p][n][n] block (factor-major, not modified), dZ a device [p][n][maxdim] block
+ * (Z_{l+1} in the first n * nconv elements of block l, ld n); T, wr, wi, u1 host buffers as above. */
+int psd_d_partial_pschur_dev(psd_ctx* ctx, int n, int p, const double* dA, int nev, char which, int mindim, int maxdim,
+                             const double* u1, uint64_t seed, double tol, double tol1, int restarts, int purgebuffer,
+                             int* nconv, double* const* T, double* dZ, double* wr, double* wi, psd_krylov_stats* stats,
+                             int* info);
+int psd_z_partial_pschur_dev(psd_ctx* ctx, int n, int p, const double* dA, int nev, char which, int mindim, int maxdim,
+                             const double* u1, uint64_t seed, double tol, double tol1, int restarts, int purgebuffer,
+                             int* nconv, double* const* T, double* dZ, double* wr, double* wi, psd_krylov_stats* stats,
+                             int* info);
+
 #ifdef __cplusplus
 }
 #endif

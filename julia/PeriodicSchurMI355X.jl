@@ -1,9 +1,10 @@
 # PeriodicSchurMI355X.jl — reference-side binding of libpsd_mi355x.so (include/psd_mi355x.h).
 #
 # Loaded next to RalphAS/PeriodicSchurDecompositions.jl v0.1.6, this module re-points the package's hot path
-# (pschur!/pschur, phessenberg!, gpschur, both ordschur! families, checkpsd) at the MI355X engine for Float64 and
-# ComplexF64 operands; everything else of the package (Krylov driver, eigvecs, generic element types) keeps running the
-# Julia code, which now reaches the engine through these methods wherever it calls them.
+# (pschur!/pschur, phessenberg!, gpschur, both ordschur! families, checkpsd, partial_pschur on dense factors) at the MI355X
+# engine for Float64 and ComplexF64 operands; everything else of the package (the Krylov driver on linear maps, eigvecs,
+# generic element types) keeps running the Julia code, which now reaches the engine through these methods wherever it
+# calls them.
 #
 #     using PeriodicSchurDecompositions, LinearAlgebra
 #     include("julia/PeriodicSchurMI355X.jl"); using .PeriodicSchurMI355X
@@ -20,6 +21,7 @@ import PeriodicSchurDecompositions
 import PeriodicSchurDecompositions: pschur!, pschur, phessenberg!, gpschur, PeriodicSchur, GeneralizedPeriodicSchur,
                                     checkpsd
 const PSD = PeriodicSchurDecompositions
+using ArnoldiMethod: ArnoldiMethod
 
 export set_train!, engine_version
 
@@ -406,6 +408,65 @@ function checkpsd(P::PSD.AbstractPeriodicSchur{T}, Hs::AbstractVector{<:Abstract
         end
     end
     return ok[] != 0, err
+end
+
+# ---------------------------------------------------------------------------------------------------------------------
+# partial_pschur(As, nev, which; ...) — krylov.jl:446-487, for dense Float64 / ComplexF64 factors: the Krylov steps run on
+# the device (psd_d_partial_pschur / psd_z_partial_pschur).  Operators given as linear maps keep the reference's CPU
+# driver (this method only matches Vector{Matrix{T}}).  The reference's `vrand!` keyword is NOT honoured on the device:
+# without `u1` the start vector comes from the library's counter-based generator, seeded by `seed`.
+const _KTARGET = Dict(ArnoldiMethod.LM => 'M', ArnoldiMethod.LR => 'R', ArnoldiMethod.SR => 'r',
+                      ArnoldiMethod.LI => 'I', ArnoldiMethod.SI => 'i')
+const INFO_PKSFAIL = 5000
+
+function PSD.partial_pschur(As::Vector{Matrix{T}}, nev::Integer, which::ArnoldiMethod.Target = ArnoldiMethod.LM();
+                            mindim::Integer = min(max(10, nev), size(As[1], 1)),
+                            maxdim::Integer = min(max(20, 2nev), size(As[1], 1)),
+                            u1 = nothing, tol = sqrt(eps(Float64)), tol1 = 100 * eps(Float64),
+                            restarts = 100, purgebuffer = 2, seed::Integer = 0) where {T <: BlasElt}
+    p = length(As); n = size(As[1], 1)
+    for l in 1:p
+        checksquare(As[l]) == n || throw(ArgumentError("all As must have the same (square) size"))     # krylov.jl:457-461
+    end
+    nev < 1 && throw(ArgumentError("nev cannot be less than 1"))                                         # :462-464
+    nev ≤ mindim ≤ maxdim ≤ p * n ||
+        throw(ArgumentError("nev ≤ mindim ≤ maxdim does not hold, got $nev ≤ $mindim ≤ $maxdim"))        # :465-466
+    u = u1 === nothing ? nothing : Vector{T}(u1)
+    u === nothing || length(u) == n || throw(ArgumentError("u1 must have length matching first matrix/operator"))
+    Ts = [Matrix{T}(undef, maxdim, maxdim) for _ in 1:p]
+    Zs = [Matrix{T}(undef, n, maxdim) for _ in 1:p]
+    wr = zeros(maxdim); wi = zeros(maxdim)
+    nconv = Ref{Cint}(0); info = Ref{Cint}(0)
+    st = zeros(UInt8, 96)  # psd_krylov_stats: nprods Int64, nconverged Int32, converged Int32, nev Int32, ...
+    Ap = _ptrs(As); Tp = _ptrs(Ts); Zp = _ptrs(Zs)
+    fn = T <: Real ? :psd_d_partial_pschur : :psd_z_partial_pschur
+    GC.@preserve As Ts Zs u wr wi st begin
+        up = u === nothing ? Ptr{Float64}(C_NULL) : Ptr{Float64}(pointer(u))
+        args = (ctx().ptr, n, p, Ap, nev, _KTARGET[typeof(which)], mindim, maxdim, up, UInt64(seed), Float64(tol),
+                Float64(tol1), restarts, purgebuffer, nconv, Tp, Zp, wr, wi, pointer(st), info)
+        if T <: Real
+            ccall((:psd_d_partial_pschur, libpsd), Cint,
+                  (Ptr{Cvoid}, Cint, Cint, Ptr{Ptr{Float64}}, Cint, Cchar, Cint, Cint, Ptr{Float64}, UInt64, Cdouble,
+                   Cdouble, Cint, Cint, Ref{Cint}, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ptr{Float64}, Ptr{Float64},
+                   Ptr{UInt8}, Ref{Cint}), args...)
+        else
+            ccall((:psd_z_partial_pschur, libpsd), Cint,
+                  (Ptr{Cvoid}, Cint, Cint, Ptr{Ptr{Float64}}, Cint, Cchar, Cint, Cint, Ptr{Float64}, UInt64, Cdouble,
+                   Cdouble, Cint, Cint, Ref{Cint}, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ptr{Float64}, Ptr{Float64},
+                   Ptr{UInt8}, Ref{Cint}), args...)
+        end
+    end
+    info[] == INFO_PKSFAIL && throw(PSD.PKSFailure("Arnoldi reinitialization failed"))                  # krylov.jl:182
+    2000 <= info[] < 3000 && throw(PSD.IllConditionedException(info[] - 2000))
+    _throw(info[])
+    k = Int(nconv[])
+    # T[l] holds the k x k factor with leading dimension k in its first k^2 elements
+    Tk = [copy(reshape(view(vec(Ts[l]), 1:(k * k)), k, k)) for l in 1:p]
+    Zk = [Zs[l][:, 1:k] for l in 1:p]
+    λ = complex.(wr[1:k], wi[1:k])
+    nprods = Int(reinterpret(Int64, st[1:8])[1])
+    ps = PSD.PartialPeriodicSchur(Tk[p], Tk[1:(p - 1)], Zk, λ)                                         # krylov.jl:796
+    return ps, ArnoldiMethod.History(nprods, k, k ≥ nev, nev)
 end
 
 end # module

@@ -112,6 +112,46 @@ class GeneralizedPeriodicSchur(PeriodicSchur):
         self.alpha, self.beta, self.alphascale = alpha, beta, alphascale
 
 
+class KrylovStats(C.Structure):
+    """psd_krylov_stats (include/psd_mi355x.h): History fields and counters of one partial_pschur call."""
+    _fields_ = [
+        ("nprods", C.c_int64), ("nconverged", C.c_int32), ("converged", C.c_int32), ("nev", C.c_int32),
+        ("restarts", C.c_int32), ("nreorth", C.c_int32), ("nreinit", C.c_int32), ("ndeflate", C.c_int32),
+        ("suspect", C.c_int32), ("ms_arnoldi", C.c_double), ("ms_proj", C.c_double), ("ms_basis", C.c_double),
+        ("ms_total", C.c_double),
+    ]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class PKSFailure(Exception):
+    """PKSFailure (src/krylov.jl:21-23): the Arnoldi re-initialisation failed."""
+
+
+class PartialPeriodicSchur(PeriodicSchur):
+    """Mirror of `PartialPeriodicSchur` (src/krylov.jl:87-139): k Schur vectors of length n per factor, left
+    orientation, A_l Z_l = Z_{l+1} T_l (l < p) and A_p Z_p = Z_1 T_p; `T1` = T_p (schurindex = p)."""
+
+    def __init__(self, Ts, Z, values, stats=None):
+        super().__init__(Ts, Z, values, "L", len(Ts), stats)
+
+
+class History:
+    """Mirror of `ArnoldiMethod.History`: matrix-vector products, converged count, converged flag, nev."""
+
+    def __init__(self, mvproducts, nconverged, converged, nev):
+        self.mvproducts, self.nconverged, self.converged, self.nev = mvproducts, nconverged, converged, nev
+
+    def __repr__(self):
+        return (f"History(mvproducts={self.mvproducts}, nconverged={self.nconverged}, converged={self.converged}, "
+                f"nev={self.nev})")
+
+
+# partial_pschur targets (ArnoldiMethod's LM / LR / SR / LI / SI) as the ABI's char codes
+KRYLOV_TARGETS = {"LM": "M", "LR": "R", "SR": "r", "LI": "I", "SI": "i"}
+
+
 def char_lr(lr):
     """src/PeriodicSchurDecompositions.jl:155-163,175-177."""
     if lr in ("R", ":R"):
@@ -192,6 +232,11 @@ class Engine:
                                                 dp, dp, ip, C.POINTER(Stats), ip]
         lib.psd_set_shard.argtypes = [C.c_void_p, C.c_int, C.c_int]
         lib.psd_shard_owned.argtypes = [C.c_void_p, C.c_int, C.c_char, u8p]
+        for nm, dev in (("psd_d_partial_pschur", False), ("psd_z_partial_pschur", False),
+                        ("psd_d_partial_pschur_dev", True), ("psd_z_partial_pschur_dev", True)):
+            getattr(lib, nm).argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p if dev else dpp, C.c_int, C.c_char,
+                                         C.c_int, C.c_int, dp, C.c_uint64, C.c_double, C.c_double, C.c_int, C.c_int,
+                                         ip, dpp, C.c_void_p if dev else dpp, dp, dp, C.POINTER(KrylovStats), ip]
         self.ctx = C.c_void_p()
         rc = lib.psd_create(C.byref(self.ctx), device)
         if rc != 0:
@@ -781,6 +826,8 @@ class Engine:
         mu^p = lambda_k (left orientation)."""
         import copy
 
+        if isinstance(ps0, PartialPeriodicSchur):
+            return self._partial_eigvecs(ps0, select, shifted)
         if len(ps0.Z) == 0 or ps0.Z[0].shape[0] == 0:
             raise ValueError("eigvecs requires Schur vectors in the PSD")  # vectors.jl:30-32
         n, m = ps0.Z[0].shape
@@ -847,6 +894,118 @@ class Engine:
             k += nl
             sel = sel[nl:] + sel[:nl]  # circshift!(sel, -nl)
         return Vs
+
+    def _partial_eigvecs(self, ps0, select, shifted):
+        """eigvecs(ps::PartialPeriodicSchur, select; shifted) — src/krylov.jl:996-1022: the eigenvectors of the k x k
+        problem (identity Schur vectors), then Z_l times them."""
+        p = ps0.period
+        k = ps0.Z[0].shape[1]
+        real = not np.iscomplexobj(ps0.Ts[0])
+        dt = np.float64 if real else np.complex128
+        small = PeriodicSchur([np.array(t, dtype=dt, order="F") for t in ps0.Ts],
+                              [np.asfortranarray(np.eye(k, dtype=dt)) for _ in range(p)],
+                              np.array(ps0.values, dtype=complex), ps0.orientation, ps0.schurindex)
+        V0 = self.eigvecs(small, select, shifted=shifted)
+        out = []
+        for l, v in enumerate(V0):
+            z = ps0.Z[l]
+            if not isinstance(z, np.ndarray):  # device-resident Schur vectors (torch): the product stays there
+                import torch
+
+                out.append(z.to(torch.complex128) @ torch.as_tensor(v, device=z.device))
+            else:
+                out.append(np.asarray(z) @ v)
+        return out
+
+    def partial_pschur(self, As, nev=None, which="LM", *, mindim=None, maxdim=None, u1=None, tol=None, tol1=None,
+                       restarts=100, purgebuffer=2, seed=0):
+        """partial_pschur(As, nev, which; mindim, maxdim, u1, tol, tol1, restarts, purgebuffer) — src/krylov.jl:446-487,
+        for dense factors on the device.  `As`: a list of p numpy n x n matrices (host entry) or of torch device tensors
+        / one torch [p, n, n] device tensor (device-resident entry: the Schur vectors come back as torch tensors on the
+        same device).  `which`: "LM", "LR", "SR", "LI" or "SI".  `seed` replaces the reference's `vrand!`: without `u1`
+        the start vector comes from a counter-based generator seeded by it.  Returns (PartialPeriodicSchur, History);
+        the counters of the call are in `P.stats` (KrylovStats)."""
+        if which not in KRYLOV_TARGETS:
+            raise ValueError(f"unknown target {which!r}: one of LM, LR, SR, LI, SI")
+        dev = not (isinstance(As, (list, tuple)) and all(isinstance(a, np.ndarray) for a in As))
+        if dev:
+            import torch
+
+            dA = As if isinstance(As, torch.Tensor) else torch.stack(list(As))
+            if dA.dim() != 3 or dA.shape[1] != dA.shape[2]:
+                raise DimensionMismatch("all As must have the same (square) size")
+            if not dA.is_cuda:
+                raise TypeError("device-resident partial_pschur needs GPU tensors (use numpy arrays for host input)")
+            cplx = dA.is_complex()
+            # factor-major [p][n][n] blocks of column-major matrices: the transpose of each factor, contiguous
+            dA = dA.to(torch.complex128 if cplx else torch.float64).transpose(1, 2).contiguous()
+            p, n = dA.shape[0], dA.shape[1]
+        else:
+            n = _check_square(As)
+            p = len(As)
+            cplx = self._is_complex(As)
+        if p < 1:
+            raise DimensionMismatch("empty sequence")
+        dt = np.complex128 if cplx else np.float64
+        if nev is None:
+            nev = min(6, n)
+        if mindim is None:
+            mindim = min(max(10, nev), n)
+        if maxdim is None:
+            maxdim = min(max(20, 2 * nev), n)
+        if tol is None:
+            tol = float(np.sqrt(np.finfo(np.float64).eps))
+        if tol1 is None:
+            tol1 = 100 * float(np.finfo(np.float64).eps)
+        if nev < 1:
+            raise ValueError("nev cannot be less than 1")  # krylov.jl:462
+        if not (nev <= mindim <= maxdim <= p * n):
+            raise ValueError(f"nev ≤ mindim ≤ maxdim does not hold, got {nev} ≤ {mindim} ≤ {maxdim}")  # :465-466
+        uarr = None
+        if u1 is not None:
+            if hasattr(u1, "detach"):
+                u1 = u1.detach().cpu().numpy()
+            uarr = np.ascontiguousarray(np.asarray(u1, dtype=dt).reshape(-1))
+            if uarr.shape[0] != n:
+                raise ValueError("u1 must have length matching first matrix/operator")  # krylov.jl:538-540
+        kmax = maxdim
+        Ts = [np.zeros(kmax * kmax, dtype=dt) for _ in range(p)]  # (nconv x nconv, ld nconv: reshaped below)
+        wr, wi = np.zeros(kmax), np.zeros(kmax)
+        nconv, info = C.c_int(0), C.c_int(0)
+        st = KrylovStats()
+        dp = C.POINTER(C.c_double)
+        up = uarr.view(np.float64).ctypes.data_as(dp) if uarr is not None else None
+        common = (int(nev), KRYLOV_TARGETS[which].encode(), int(mindim), int(maxdim), up, int(seed) & (2 ** 64 - 1),
+                  float(tol), float(tol1), int(restarts), int(purgebuffer), C.byref(nconv), self._ptrs(Ts))
+        if dev:
+            import torch
+
+            dZ = torch.zeros((p, kmax, n), dtype=dA.dtype, device=dA.device)  # block l: n x kmax column-major
+            fn = self.lib.psd_z_partial_pschur_dev if cplx else self.lib.psd_d_partial_pschur_dev
+            torch.cuda.synchronize(dA.device)
+            fn(self.ctx, n, p, C.c_void_p(dA.data_ptr()), *common, C.c_void_p(dZ.data_ptr()), wr.ctypes.data_as(dp),
+               wi.ctypes.data_as(dp), C.byref(st), C.byref(info))
+        else:
+            Aw = [np.asfortranarray(a, dtype=dt) for a in As]
+            Zs = [np.zeros((n, kmax), dtype=dt, order="F") for _ in range(p)]
+            fn = self.lib.psd_z_partial_pschur if cplx else self.lib.psd_d_partial_pschur
+            fn(self.ctx, n, p, self._ptrs(Aw), *common, self._ptrs(Zs), wr.ctypes.data_as(dp), wi.ctypes.data_as(dp),
+               C.byref(st), C.byref(info))
+        iv = info.value
+        if iv == 5000:
+            raise PKSFailure("Arnoldi reinitialization failed")
+        if 2000 <= iv < 3000:
+            raise IllConditionedException(iv - 2000)
+        self._raise(iv)
+        k = nconv.value
+        Tk = [np.asfortranarray(t[: k * k].reshape(k, k, order="F")) for t in Ts]
+        if dev:
+            Zk = [dZ[l, :k, :].transpose(0, 1) for l in range(p)]
+        else:
+            Zk = [np.asfortranarray(z[:, :k]) for z in Zs]
+        lam = (wr + 1j * wi)[:k]
+        P = PartialPeriodicSchur(Tk, Zk, lam, st)
+        return P, History(int(st.nprods), int(st.nconverged), bool(st.converged), int(st.nev))
 
     def checkpsd(self, P, As, thresh=100, strict=True, S=None, details=False):
         """checkpsd(P, As; thresh, strict) — src/diagnostics.jl:190-263 — evaluated on the device (matrix cores).
@@ -965,3 +1124,7 @@ def pschur_(A, lr="R", **kw):
 
 def phessenberg_(A):
     return default_engine().phessenberg_(A)
+
+
+def partial_pschur(As, nev=None, which="LM", **kw):
+    return default_engine().partial_pschur(As, nev, which, **kw)

@@ -18,6 +18,7 @@
 #include "psd_grord.h"
 #include "psd_rhessx.h"
 #include "psd_check.h"
+#include "psd_krylov.h"
 
 #include "../../include/psd_mi355x.h"
 
@@ -4064,3 +4065,4 @@ extern "C" int psd_dbg_apply_bench(psd_ctx* c, int n, int p, int nwin, int W, in
 }
 
 #include "psd_check_host.inl"
+#include "psd_krylov_host.inl"
