@@ -331,6 +331,56 @@ int psd_z_partial_pschur_dev(psd_ctx* ctx, int n, int p, const double* dA, int n
                              int* nconv, double* const* T, double* dZ, double* wr, double* wi, psd_krylov_stats* stats,
                              int* info);
 
+/* ---- eigvecs(ps, select; shifted) by periodic back-substitution — vectors.jl:25-138 without the reordering ----------
+ * The selected right eigenvectors of the product and of its circular shifts, from a periodic Schur decomposition, by
+ * the periodic form of LAPACK's xTREVC: the triangular factors are solved bottom up (a cyclic recurrence round the period
+ * per row block; the updates from the rows below are matrix-core products over panels of columns), then V_l = Z_l X_l on
+ * the matrix cores.  The factors are not modified.  Result: A_l v_l = mu v_{l+1} (left orientation; right:
+ * A_l v_{l+1} = mu v_l), mu = lambda^(1/p) the principal root of the caller's eigenvalue, ||V_1(:, j)||_2 = 1, the
+ * largest-modulus entry of V_1(:, j) real and positive (lowest row on a tie), the same factor applied to every V_l(:, j);
+ * for a conjugate pair of a real decomposition the second column is the conjugate of the first.
+ *
+ * T, Z: p pointers to n x n matrices, the user order of the decomposition (T[schurindex-1] the quasi-triangular factor),
+ * any schurindex, orient 'L' or 'R'.  Eigenvalues: wr / wi (Float64, psd_d_*) or alpha / beta / ascale (ComplexF64,
+ * psd_z_*: alpha[k] / beta[k] * 2^ascale[k], ascale may be NULL) — the P.values the decomposition reports.  S: NULL or
+ * the signature (a signed S: PSD_INFO_NOTIMPL).  select: nsel = n flags, completed to whole conjugate pairs in place
+ * (vectors.jl:42-62).  Columns come in the order of the selected eigenvalues from top to bottom.  shifted: V holds p
+ * matrices (V_1 .. V_p), else one (V_1, bit-identical to V_1 of the shifted call).  V: p (or 1) pointers to n x maxvec
+ * complex interleaved buffers, column-major, ld n; V = NULL: a size query (select completed, stats->nvec set, nothing
+ * computed).  An eigenvalue zero (mu = 0) gives a column of NaNs (the reference's formula divides by mu as well) and is
+ * counted in stats->nzero.  Near-equal eigenvalues: a pivot below max(eps, tiny) (relative) is replaced by it
+ * (stats->nperturbed), so repeated eigenvalues return finite vectors.
+ * info: 0; -1 ctx NULL; -2 n < 1; -3 p < 1; -4 T NULL; -5 Z NULL (no Schur vectors, vectors.jl:30-32); -6 eigenvalues
+ * NULL; -7 orient; -8 schurindex not in 1..p; -9 select NULL or nsel != n (vectors.jl:34-36); -10 maxvec below the
+ * number of columns; PSD_INFO_NOTIMPL signed S; PSD_INFO_RUNTIME + k. */
+typedef struct psd_evec_stats {
+    int32_t nvec;           /* columns returned (conjugate partners included)                                  */
+    int32_t nperturbed;     /* pivots replaced by smin (near-equal eigenvalues)                                */
+    int32_t nrescaled;      /* columns scaled by a power of two against overflow                               */
+    int32_t nzero;          /* zero-eigenvalue columns (NaN)                                                   */
+    double ms_solve;        /* back-substitution: updates and cyclic solves (device events)                   */
+    double ms_backtransform;/* V_l = Z_l X_l and the normalisation (device events)                            */
+    double ms_kernels;      /* the two together                                                               */
+} psd_evec_stats;
+
+int psd_d_eigvecs(psd_ctx* ctx, int n, int p, double* const* T, double* const* Z, const double* wr, const double* wi,
+                  const uint8_t* S, char orient, int schurindex, uint8_t* select, int nsel, int shifted,
+                  double* const* V, int maxvec, psd_evec_stats* stats, int* info);
+int psd_z_eigvecs(psd_ctx* ctx, int n, int p, double* const* T, double* const* Z, const double* alpha,
+                  const double* beta, const int32_t* ascale, const uint8_t* S, char orient, int schurindex,
+                  uint8_t* select, int nsel, int shifted, double* const* V, int maxvec, psd_evec_stats* stats,
+                  int* info);
+/* Device-resident variants: dT, dZ device [p][n][n] blocks as psd_?_pschur_dev leaves them (user order), dV a device
+ * block of (shifted ? p : 1) matrices n x nvec (complex interleaved, column-major, ld n; block l at 2 l n nvec doubles,
+ * nvec = stats->nvec of a size query with dV = NULL).  Eigenvalues, S and select are host arrays. */
+int psd_d_eigvecs_dev(psd_ctx* ctx, int n, int p, const double* dT, const double* dZ, const double* wr,
+                      const double* wi, const uint8_t* S, char orient, int schurindex, uint8_t* select, int nsel,
+                      int shifted, double* dV, int maxvec, psd_evec_stats* stats, int* info);
+int psd_z_eigvecs_dev(psd_ctx* ctx, int n, int p, const double* dT, const double* dZ, const double* alpha,
+                      const double* beta, const int32_t* ascale, const uint8_t* S, char orient, int schurindex,
+                      uint8_t* select, int nsel, int shifted, double* dV, int maxvec, psd_evec_stats* stats,
+                      int* info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -469,4 +469,48 @@ function PSD.partial_pschur(As::Vector{Matrix{T}}, nev::Integer, which::ArnoldiM
     return ps, ArnoldiMethod.History(nprods, k, k ≥ nev, nev)
 end
 
+
+# ---------------------------------------------------------------------------------------------------------------------
+# eigvecs_device(ps, select; shifted) — eigvecs (vectors.jl:25-138) by periodic back-substitution on the device
+# (psd_d_eigvecs / psd_z_eigvecs): no reordering, one call for all selected vectors.  `select` is completed to whole
+# conjugate pairs; the columns come in the order of the selected eigenvalues from top to bottom; ‖V_1[:, j]‖ = 1 with its
+# largest entry real and positive.  A zero eigenvalue gives a column of NaNs.  (Signed generalized decompositions are
+# not covered: the C ABI returns PSD_INFO_NOTIMPL for them.)
+function eigvecs_device(ps::PeriodicSchur{T}, select::AbstractVector{Bool}; shifted::Bool = true) where {T <: BlasElt}
+    isempty(ps.Z) && throw(ArgumentError("eigvecs requires Schur vectors in the PSD"))                 # vectors.jl:30-32
+    p = ps.period; n = size(ps.T1, 1)
+    length(select) == n ||
+        throw(ArgumentError("length of `select` must correspond to rank of Schur (sub-)space"))       # vectors.jl:34-36
+    Ts = _userT(ps); Zs = ps.Z
+    sel = UInt8.(select); info = Ref{Cint}(0); st = zeros(UInt8, 40)  # psd_evec_stats: nvec Int32 first
+    Tp = _ptrs(Ts); Zp = _ptrs(Zs)
+    wr = Float64.(real.(ps.values)); wi = Float64.(imag.(ps.values))
+    α = ComplexF64.(ps.values); β = ones(n); sc = zeros(Int32, n)
+    call(Vp, maxvec) = GC.@preserve Ts Zs sel wr wi α β sc st begin
+        if T <: Real
+            ccall((:psd_d_eigvecs, libpsd), Cint,
+                  (Ptr{Cvoid}, Cint, Cint, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8},
+                   Cchar, Cint, Ptr{UInt8}, Cint, Cint, Ptr{Ptr{Float64}}, Cint, Ptr{UInt8}, Ref{Cint}),
+                  ctx().ptr, n, p, Tp, Zp, wr, wi, C_NULL, ps.orientation, ps.schurindex, sel, n, shifted, Vp, maxvec,
+                  pointer(st), info)
+        else
+            ccall((:psd_z_eigvecs, libpsd), Cint,
+                  (Ptr{Cvoid}, Cint, Cint, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ptr{ComplexF64}, Ptr{Float64},
+                   Ptr{Int32}, Ptr{UInt8}, Cchar, Cint, Ptr{UInt8}, Cint, Cint, Ptr{Ptr{Float64}}, Cint, Ptr{UInt8},
+                   Ref{Cint}),
+                  ctx().ptr, n, p, Tp, Zp, α, β, sc, C_NULL, ps.orientation, ps.schurindex, sel, n, shifted, Vp,
+                  maxvec, pointer(st), info)
+        end
+    end
+    call(Ptr{Ptr{Float64}}(C_NULL), 0)                                                       # size query: completes select
+    _throw(info[])
+    nvec = Int(reinterpret(Int32, st[1:4])[1])
+    Vs = [Matrix{ComplexF64}(undef, n, nvec) for _ in 1:(shifted ? p : 1)]
+    GC.@preserve Vs begin
+        call(_ptrs(Vs), nvec)
+    end
+    _throw(info[])
+    return shifted ? Vs : Vs[1]
+end
+
 end # module

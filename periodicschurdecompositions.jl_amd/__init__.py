@@ -125,6 +125,17 @@ class KrylovStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class EvecStats(C.Structure):
+    """psd_evec_stats (include/psd_mi355x.h): counters and device times of one eigvecs call by back-substitution."""
+    _fields_ = [
+        ("nvec", C.c_int32), ("nperturbed", C.c_int32), ("nrescaled", C.c_int32), ("nzero", C.c_int32),
+        ("ms_solve", C.c_double), ("ms_backtransform", C.c_double), ("ms_kernels", C.c_double),
+    ]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class PKSFailure(Exception):
     """PKSFailure (src/krylov.jl:21-23): the Arnoldi re-initialisation failed."""
 
@@ -237,6 +248,14 @@ class Engine:
             getattr(lib, nm).argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p if dev else dpp, C.c_int, C.c_char,
                                          C.c_int, C.c_int, dp, C.c_uint64, C.c_double, C.c_double, C.c_int, C.c_int,
                                          ip, dpp, C.c_void_p if dev else dpp, dp, dp, C.POINTER(KrylovStats), ip]
+        i32p = C.POINTER(C.c_int32)
+        for nm, dev, cplx in (("psd_d_eigvecs", False, False), ("psd_z_eigvecs", False, True),
+                              ("psd_d_eigvecs_dev", True, False), ("psd_z_eigvecs_dev", True, True)):
+            mats = C.c_void_p if dev else dpp
+            vals = [dp, dp, i32p] if cplx else [dp, dp]
+            getattr(lib, nm).argtypes = ([C.c_void_p, C.c_int, C.c_int, mats, mats] + vals +
+                                         [u8p, C.c_char, C.c_int, u8p, C.c_int, C.c_int, mats, C.c_int,
+                                          C.POINTER(EvecStats), ip])
         self.ctx = C.c_void_p()
         rc = lib.psd_create(C.byref(self.ctx), device)
         if rc != 0:
@@ -816,16 +835,23 @@ class Engine:
         P.stats = st
         return P
 
-    def eigvecs(self, ps0, select, shifted=True):
+    def eigvecs(self, ps0, select, shifted=True, method="ordschur"):
         """LinearAlgebra.eigvecs(ps::PeriodicSchur, select; shifted) — src/vectors.jl:25-138: selected right
         eigenvectors of the product (and of its circular shifts).  A loop of `ordschur!` calls (on the device) that
         brings one selected eigenvalue (or conjugate pair) after the other to the top, where its vector is read off
         the leading Schur vectors; for a pair the 2x2 cyclic problem is solved (babd.jl, here a dense 2p x 2p solve).
         `select` is completed to conjugate pairs for a real decomposition (vectors.jl:42-62); `ps0` is not modified.
         Returns a list of p (shifted) or one complex n x nvec matrices, normalised so that A_l v_l = mu v_{l+1},
-        mu^p = lambda_k (left orientation)."""
+        mu^p = lambda_k (left orientation).
+
+        method="backsub": periodic back-substitution on the device instead (psd_?_eigvecs: no reordering, one call for
+        all selected vectors; see `_eigvecs_backsub`).  The counters of that call are left in `self.eigvecs_stats`."""
         import copy
 
+        if method == "backsub":
+            return self._eigvecs_backsub(ps0, select, shifted)
+        if method != "ordschur":
+            raise ValueError(f"unknown method {method!r}: 'ordschur' or 'backsub'")
         if isinstance(ps0, PartialPeriodicSchur):
             return self._partial_eigvecs(ps0, select, shifted)
         if len(ps0.Z) == 0 or ps0.Z[0].shape[0] == 0:
@@ -895,7 +921,101 @@ class Engine:
             sel = sel[nl:] + sel[:nl]  # circshift!(sel, -nl)
         return Vs
 
-    def _partial_eigvecs(self, ps0, select, shifted):
+    @staticmethod
+    def _evec_values(ps, cplx):
+        """The eigenvalue arguments of psd_?_eigvecs: (wr, wi) or (alpha, beta, ascale)."""
+        if not cplx:
+            v = np.asarray(ps.values, dtype=np.complex128)
+            return [np.ascontiguousarray(v.real), np.ascontiguousarray(v.imag)]
+        if isinstance(ps, GeneralizedPeriodicSchur):
+            return [np.ascontiguousarray(ps.alpha, dtype=np.complex128), np.ascontiguousarray(ps.beta, dtype=np.float64),
+                    np.ascontiguousarray(ps.alphascale, dtype=np.int32)]
+        v = np.ascontiguousarray(ps.values, dtype=np.complex128)
+        return [v, np.ones(len(v)), np.zeros(len(v), dtype=np.int32)]
+
+    @staticmethod
+    def _evec_ptrs(vals):
+        dp, i32p = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        return [v.ctypes.data_as(i32p if v.dtype == np.int32 else dp) for v in vals]
+
+    def _eigvecs_backsub(self, ps0, select, shifted):
+        """eigvecs(ps, select; shifted) by periodic back-substitution (psd_d_eigvecs / psd_z_eigvecs): the triangular
+        factors are solved bottom up on the device and V_l = Z_l X_l is formed on the matrix cores.  Same result contract
+        as the default method (src/vectors.jl:25-138), plus: ||V_1[:, j]|| = 1 with its largest-modulus entry real and
+        positive; a zero eigenvalue gives a column of NaNs (counted in eigvecs_stats.nzero).  PartialPeriodicSchur: the
+        projected k x k problem, then Z_l times its vectors.  A signed GeneralizedPeriodicSchur: NotImplementedPSD."""
+        if isinstance(ps0, PartialPeriodicSchur):
+            return self._partial_eigvecs(ps0, select, shifted, "backsub")
+        if isinstance(ps0, GeneralizedPeriodicSchur) and not all(ps0.S):
+            raise NotImplementedPSD("eigenvectors of a signed GeneralizedPeriodicSchur")
+        if len(ps0.Z) == 0 or ps0.Z[0].shape[0] == 0:
+            raise ValueError("eigvecs requires Schur vectors in the PSD")  # vectors.jl:30-32
+        n, m = ps0.Z[0].shape
+        if len(select) != m:
+            raise ValueError("length of `select` must correspond to rank of Schur (sub-)space")  # vectors.jl:34-36
+        cplx = np.iscomplexobj(ps0.Ts[0])
+        if any(np.iscomplexobj(t) != cplx for t in ps0.Ts) or any(np.iscomplexobj(z) != cplx for z in ps0.Z):
+            # (a real quasi-triangular factor sent through the complex path would lose its 2x2 row blocks)
+            raise TypeError("eigvecs: the factors T and the Schur vectors Z must be all real or all complex")
+        dt = np.complex128 if cplx else np.float64
+        Ts = [np.asfortranarray(t, dtype=dt) for t in ps0.Ts]  # (read only: ps0 is never written)
+        Zs = [np.asfortranarray(z, dtype=dt) for z in ps0.Z]
+        p = len(Ts)
+        vals = self._evec_values(ps0, cplx)
+        sel = (C.c_uint8 * m)(*[1 if x else 0 for x in select])
+        st = EvecStats()
+        info = C.c_int(0)
+        fn = self.lib.psd_z_eigvecs if cplx else self.lib.psd_d_eigvecs
+        args = [self.ctx, n, p, self._ptrs(Ts), self._ptrs(Zs)] + self._evec_ptrs(vals) + [None,
+                ps0.orientation.encode(), ps0.schurindex, sel, m, int(bool(shifted))]
+        fn(*args, None, 0, C.byref(st), C.byref(info))  # size query: select completed, st.nvec
+        self._raise(info.value)
+        nvec = st.nvec
+        Vs = [np.zeros((n, nvec), dtype=np.complex128, order="F") for _ in range(p if shifted else 1)]
+        fn(*args, self._ptrs(Vs), nvec, C.byref(st), C.byref(info))
+        self._raise(info.value)
+        self.eigvecs_stats = st
+        return Vs
+
+    def eigvecs_dev(self, dT, dZ, values, select, lr="R", schurindex=1, shifted=True, S=None):
+        """Device-resident eigvecs by back-substitution (psd_d_eigvecs_dev / psd_z_eigvecs_dev), mirroring pschur_dev:
+        dT, dZ are torch device tensors holding the [p][n][n] column-major blocks pschur_dev / zpschur_dev leave (float64
+        or complex128, user order, T[schurindex-1] quasi-triangular); `values` the eigenvalues they returned.  Returns a
+        list of (p if shifted else 1) torch device tensors n x nvec (complex128) and leaves the counters in
+        `self.eigvecs_stats`."""
+        import torch
+
+        p, n = dT.shape[0], dT.shape[1]
+        if dZ is None:
+            raise ValueError("eigvecs requires Schur vectors in the PSD")
+        if S is not None and not all(S):
+            raise NotImplementedPSD("eigenvectors of a signed GeneralizedPeriodicSchur")
+        cplx = dT.is_complex()
+        if dZ.dtype != dT.dtype:
+            raise TypeError("eigvecs_dev: dT and dZ must have the same dtype (float64 or complex128)")
+        if len(select) != n:
+            raise ValueError("length of `select` must correspond to rank of Schur (sub-)space")
+        v = np.asarray(values, dtype=np.complex128)
+        vals = ([v, np.ones(n), np.zeros(n, dtype=np.int32)] if cplx
+                else [np.ascontiguousarray(v.real), np.ascontiguousarray(v.imag)])
+        sel = (C.c_uint8 * n)(*[1 if x else 0 for x in select])
+        st = EvecStats()
+        info = C.c_int(0)
+        fn = self.lib.psd_z_eigvecs_dev if cplx else self.lib.psd_d_eigvecs_dev
+        args = [self.ctx, n, p, C.c_void_p(dT.data_ptr()), C.c_void_p(dZ.data_ptr())] + self._evec_ptrs(vals) + [
+            None, char_lr(lr).encode(), int(schurindex), sel, n, int(bool(shifted))]
+        fn(*args, None, 0, C.byref(st), C.byref(info))
+        self._raise(info.value)
+        nvec = st.nvec
+        nmat = p if shifted else 1
+        dV = torch.empty((nmat, max(nvec, 1), n), dtype=torch.complex128, device=dT.device)
+        torch.cuda.synchronize(dT.device)
+        fn(*args, C.c_void_p(dV.data_ptr()), nvec, C.byref(st), C.byref(info))
+        self._raise(info.value)
+        self.eigvecs_stats = st
+        return [dV[l, :nvec, :].transpose(0, 1) for l in range(nmat)]
+
+    def _partial_eigvecs(self, ps0, select, shifted, method="ordschur"):
         """eigvecs(ps::PartialPeriodicSchur, select; shifted) — src/krylov.jl:996-1022: the eigenvectors of the k x k
         problem (identity Schur vectors), then Z_l times them."""
         p = ps0.period
@@ -905,7 +1025,7 @@ class Engine:
         small = PeriodicSchur([np.array(t, dtype=dt, order="F") for t in ps0.Ts],
                               [np.asfortranarray(np.eye(k, dtype=dt)) for _ in range(p)],
                               np.array(ps0.values, dtype=complex), ps0.orientation, ps0.schurindex)
-        V0 = self.eigvecs(small, select, shifted=shifted)
+        V0 = self.eigvecs(small, select, shifted=shifted, method=method)
         out = []
         for l, v in enumerate(V0):
             z = ps0.Z[l]

@@ -19,6 +19,7 @@
 #include "psd_rhessx.h"
 #include "psd_check.h"
 #include "psd_krylov.h"
+#include "psd_evec.h"
 
 #include "../../include/psd_mi355x.h"
 
@@ -4066,3 +4067,4 @@ extern "C" int psd_dbg_apply_bench(psd_ctx* c, int n, int p, int nwin, int W, in
 
 #include "psd_check_host.inl"
 #include "psd_krylov_host.inl"
+#include "psd_evec_host.inl"
