@@ -381,6 +381,41 @@ int psd_z_eigvecs_dev(psd_ctx* ctx, int n, int p, const double* dT, const double
                       uint8_t* select, int nsel, int shifted, double* dV, int maxvec, psd_evec_stats* stats,
                       int* info);
 
+/* ---- geigvecs: eigenvectors of signed and singular periodic products (the periodic form of xTGEVC) --------------------
+ * The selected right eigenvectors of a (generalized) periodic Schur decomposition with signature S, zero and infinite
+ * eigenvalues included, by the back-substitution of psd_?_eigvecs with homogeneous recurrences.  For every column j the
+ * vectors v_1 .. v_p (V_l(:, j)) and complex scalars a_1 .. a_p (a[l + p j]) satisfy, l + 1 cyclic,
+ *     orient 'L':  S[l] true: A_l v_l = a_l v_{l+1};    S[l] false: A_l v_{l+1} = a_l v_l
+ *     orient 'R':  S[l] true: A_l v_{l+1} = a_l v_l;    S[l] false: A_l v_l = a_l v_{l+1}
+ * with A_l the factors the decomposition represents.  a_l = T_l(k, k), the diagonal at the eigenvalue's own row k (so a
+ * zero a_l is a zero eigenvalue if S[l], an infinite one if not; nothing divides by the eigenvalue).  A conjugate pair
+ * of a real decomposition (2x2 block at rows k, k+1): a_l = sqrt|det B_l|, times e^(+-i arg lambda_k) at schurindex (sign
+ * from S there), where
+ * B_l is the factors' 2x2 block and lambda_k the member with positive imaginary part; the partner column and its scalars
+ * are the conjugates.  For finite non-zero eigenvalues the product of a_l^(+-1) (sign from S) is lambda_k.
+ * Normalisation, select completion, shifted and V as psd_?_eigvecs.  A cyclic pivot below
+ * smin = max(eps max(|A|, |C|), tiny) is replaced by smin (stats->nperturbed): the vectors are always finite.
+ *
+ * T, Z: p pointers to n x n matrices in user order (T[schurindex-1] quasi-triangular), orient 'L' or 'R', any
+ * schurindex.  S: NULL (all true) or p flags.  No eigenvalue arguments: everything comes from T.  a: host, p x maxvec
+ * complex interleaved, column-major with ld p, may be NULL.  V = NULL: a size query.  stats: psd_evec_stats, with nzero
+ * the number of columns whose eigenvalue is zero or infinite (a zero a_l; these columns are computed).
+ * info: 0; -1 ctx NULL; -2 n < 1; -3 p < 1; -4 T NULL; -5 Z NULL; -7 orient; -8 schurindex not in 1..p; -9 select
+ * NULL or nsel != n; -13 maxvec below the number of columns; PSD_INFO_RUNTIME + k. */
+int psd_d_geigvecs(psd_ctx* ctx, int n, int p, double* const* T, double* const* Z, const uint8_t* S, char orient,
+                   int schurindex, uint8_t* select, int nsel, int shifted, double* const* V, int maxvec, double* a,
+                   psd_evec_stats* stats, int* info);
+int psd_z_geigvecs(psd_ctx* ctx, int n, int p, double* const* T, double* const* Z, const uint8_t* S, char orient,
+                   int schurindex, uint8_t* select, int nsel, int shifted, double* const* V, int maxvec, double* a,
+                   psd_evec_stats* stats, int* info);
+/* Device-resident variants: dT, dZ, dV as psd_?_eigvecs_dev; S, select and a are host arrays. */
+int psd_d_geigvecs_dev(psd_ctx* ctx, int n, int p, const double* dT, const double* dZ, const uint8_t* S, char orient,
+                       int schurindex, uint8_t* select, int nsel, int shifted, double* dV, int maxvec, double* a,
+                       psd_evec_stats* stats, int* info);
+int psd_z_geigvecs_dev(psd_ctx* ctx, int n, int p, const double* dT, const double* dZ, const uint8_t* S, char orient,
+                       int schurindex, uint8_t* select, int nsel, int shifted, double* dV, int maxvec, double* a,
+                       psd_evec_stats* stats, int* info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -513,4 +513,50 @@ function eigvecs_device(ps::PeriodicSchur{T}, select::AbstractVector{Bool}; shif
     return shifted ? Vs : Vs[1]
 end
 
+# ---------------------------------------------------------------------------------------------------------------------
+# geigvecs_device(P, select; shifted) — eigenvectors of signed and singular periodic products (psd_d_geigvecs /
+# psd_z_geigvecs), the periodic form of xTGEVC.  Returns (Vs, a): for every column, l + 1 cyclic,
+#   'L': A_l v_l = a_l v_{l+1} if S[l], else A_l v_{l+1} = a_l v_l;  'R': the mirror.
+# a_l = T_l[k, k] at the eigenvalue's own row (zero and infinite eigenvalues give valid vectors); a conjugate pair of a
+# real decomposition takes sqrt|det B_l|, times exp(±im arg λ_k) at schurindex.  `select` is completed to whole pairs;
+# ‖V_1[:, j]‖ = 1 with its largest entry real and positive.
+function geigvecs_device(P::Union{PeriodicSchur{T}, GeneralizedPeriodicSchur{T}}, select::AbstractVector{Bool};
+                         shifted::Bool = true) where {T <: BlasElt}
+    isempty(P.Z) && throw(ArgumentError("geigvecs requires Schur vectors in the PSD"))
+    p = P.period; n = size(P.T1, 1)
+    length(select) == n ||
+        throw(ArgumentError("length of `select` must correspond to rank of Schur (sub-)space"))
+    Ts = _userT(P); Zs = P.Z
+    S = P isa GeneralizedPeriodicSchur ? UInt8.(P.S) : UInt8[]
+    length(S) in (0, p) || throw(DimensionMismatch("length of S must match the period"))
+    Sp = isempty(S) ? Ptr{UInt8}(C_NULL) : pointer(S)
+    sel = UInt8.(select); info = Ref{Cint}(0); st = zeros(UInt8, 40)  # psd_evec_stats: nvec Int32 first
+    Tp = _ptrs(Ts); Zp = _ptrs(Zs)
+    call(Vp, maxvec, ap) = GC.@preserve Ts Zs S sel st begin
+        if T <: Real
+            ccall((:psd_d_geigvecs, libpsd), Cint,
+                  (Ptr{Cvoid}, Cint, Cint, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ptr{UInt8}, Cchar, Cint, Ptr{UInt8},
+                   Cint, Cint, Ptr{Ptr{Float64}}, Cint, Ptr{ComplexF64}, Ptr{UInt8}, Ref{Cint}),
+                  ctx().ptr, n, p, Tp, Zp, Sp, P.orientation, P.schurindex, sel, n, shifted, Vp, maxvec, ap,
+                  pointer(st), info)
+        else
+            ccall((:psd_z_geigvecs, libpsd), Cint,
+                  (Ptr{Cvoid}, Cint, Cint, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ptr{UInt8}, Cchar, Cint, Ptr{UInt8},
+                   Cint, Cint, Ptr{Ptr{Float64}}, Cint, Ptr{ComplexF64}, Ptr{UInt8}, Ref{Cint}),
+                  ctx().ptr, n, p, Tp, Zp, Sp, P.orientation, P.schurindex, sel, n, shifted, Vp, maxvec, ap,
+                  pointer(st), info)
+        end
+    end
+    call(Ptr{Ptr{Float64}}(C_NULL), 0, Ptr{ComplexF64}(C_NULL))                      # size query: completes select
+    _throw(info[])
+    nvec = Int(reinterpret(Int32, st[1:4])[1])
+    Vs = [Matrix{ComplexF64}(undef, n, nvec) for _ in 1:(shifted ? p : 1)]
+    a = Matrix{ComplexF64}(undef, p, max(nvec, 1))                                  # column-major, ld p: as the ABI
+    GC.@preserve Vs a begin
+        call(_ptrs(Vs), nvec, pointer(a))
+    end
+    _throw(info[])
+    return (shifted ? Vs : Vs[1]), a[:, 1:nvec]
+end
+
 end # module

@@ -256,6 +256,11 @@ class Engine:
             getattr(lib, nm).argtypes = ([C.c_void_p, C.c_int, C.c_int, mats, mats] + vals +
                                          [u8p, C.c_char, C.c_int, u8p, C.c_int, C.c_int, mats, C.c_int,
                                           C.POINTER(EvecStats), ip])
+        for nm, dev in (("psd_d_geigvecs", False), ("psd_z_geigvecs", False), ("psd_d_geigvecs_dev", True),
+                        ("psd_z_geigvecs_dev", True)):
+            mats = C.c_void_p if dev else dpp
+            getattr(lib, nm).argtypes = [C.c_void_p, C.c_int, C.c_int, mats, mats, u8p, C.c_char, C.c_int, u8p, C.c_int,
+                                         C.c_int, mats, C.c_int, dp, C.POINTER(EvecStats), ip]
         self.ctx = C.c_void_p()
         rc = lib.psd_create(C.byref(self.ctx), device)
         if rc != 0:
@@ -854,6 +859,9 @@ class Engine:
             raise ValueError(f"unknown method {method!r}: 'ordschur' or 'backsub'")
         if isinstance(ps0, PartialPeriodicSchur):
             return self._partial_eigvecs(ps0, select, shifted)
+        if isinstance(ps0, GeneralizedPeriodicSchur) and not all(ps0.S):
+            # (the reordering below applies every factor forwards: its vectors would be wrong)
+            raise NotImplementedPSD("eigvecs of a signed GeneralizedPeriodicSchur: use Engine.geigvecs")
         if len(ps0.Z) == 0 or ps0.Z[0].shape[0] == 0:
             raise ValueError("eigvecs requires Schur vectors in the PSD")  # vectors.jl:30-32
         n, m = ps0.Z[0].shape
@@ -1014,6 +1022,89 @@ class Engine:
         self._raise(info.value)
         self.eigvecs_stats = st
         return [dV[l, :nvec, :].transpose(0, 1) for l in range(nmat)]
+
+    def geigvecs(self, P, select, shifted=True):
+        """Eigenvectors of a signed or singular periodic product (psd_d_geigvecs / psd_z_geigvecs): periodic
+        back-substitution with homogeneous recurrences, the periodic form of xTGEVC.  P: a PeriodicSchur or a
+        GeneralizedPeriodicSchur (its signature S honoured).  Returns (Vs, a): Vs a list of p (shifted) or one complex
+        n x nvec matrices, a a complex p x nvec array, such that for every column, l + 1 cyclic,
+            'L': A_l v_l = a_l v_{l+1} if S[l], else A_l v_{l+1} = a_l v_l;
+            'R': A_l v_{l+1} = a_l v_l if S[l], else A_l v_l = a_l v_{l+1}.
+        a_l = T_l[k, k] at the eigenvalue's own row k (a zero a_l: a zero or infinite eigenvalue, still a valid vector);
+        a conjugate pair of a real decomposition takes sqrt|det B_l|, times e^(i arg lambda_k) at schurindex.  select is
+        completed to whole pairs; the normalisation is that of eigvecs(method="backsub").  The counters go to
+        self.eigvecs_stats (nzero: columns with a zero or infinite eigenvalue)."""
+        if isinstance(P, PartialPeriodicSchur):
+            raise TypeError("geigvecs: a PartialPeriodicSchur is not supported")
+        if len(P.Z) == 0 or P.Z[0].shape[0] == 0:
+            raise ValueError("geigvecs requires Schur vectors in the PSD")
+        n, m = P.Z[0].shape
+        if len(select) != m:
+            raise ValueError("length of `select` must correspond to rank of Schur (sub-)space")
+        p = len(P.Ts)
+        S = P.S if isinstance(P, GeneralizedPeriodicSchur) else None
+        if S is not None and len(S) != p:
+            raise DimensionMismatch("length of S must match the period")
+        cplx = np.iscomplexobj(P.Ts[0])
+        if any(np.iscomplexobj(t) != cplx for t in P.Ts) or any(np.iscomplexobj(z) != cplx for z in P.Z):
+            raise TypeError("geigvecs: the factors T and the Schur vectors Z must be all real or all complex")
+        dt = np.complex128 if cplx else np.float64
+        Ts = [np.asfortranarray(t, dtype=dt) for t in P.Ts]  # (read only)
+        Zs = [np.asfortranarray(z, dtype=dt) for z in P.Z]
+        Sarr = None if S is None else (C.c_uint8 * p)(*[1 if x else 0 for x in S])
+        sel = (C.c_uint8 * m)(*[1 if x else 0 for x in select])
+        st = EvecStats()
+        info = C.c_int(0)
+        fn = self.lib.psd_z_geigvecs if cplx else self.lib.psd_d_geigvecs
+        args = [self.ctx, n, p, self._ptrs(Ts), self._ptrs(Zs), Sarr, P.orientation.encode(), P.schurindex, sel, m,
+                int(bool(shifted))]
+        fn(*args, None, 0, None, C.byref(st), C.byref(info))  # size query: select completed, st.nvec
+        self._raise(info.value)
+        nvec = st.nvec
+        Vs = [np.zeros((n, nvec), dtype=np.complex128, order="F") for _ in range(p if shifted else 1)]
+        abuf = np.zeros(2 * p * max(nvec, 1))  # (p x nvec complex, column-major)
+        fn(*args, self._ptrs(Vs), nvec, abuf.ctypes.data_as(C.POINTER(C.c_double)), C.byref(st), C.byref(info))
+        self._raise(info.value)
+        self.eigvecs_stats = st
+        return Vs, abuf.view(np.complex128)[:p * nvec].reshape((p, nvec), order="F")
+
+    def geigvecs_dev(self, dT, dZ, select, lr, schurindex, S=None, shifted=True):
+        """Device-resident geigvecs (psd_d_geigvecs_dev / psd_z_geigvecs_dev): dT, dZ torch device tensors holding the
+        [p][n][n] column-major blocks of the factors in user order (float64 or complex128), S the signature (None: all
+        true).  Returns (Vs, a): (p if shifted else 1) torch device tensors n x nvec (complex128) and a complex p x nvec
+        numpy array; the counters go to self.eigvecs_stats."""
+        import torch
+
+        if dZ is None:
+            raise ValueError("geigvecs requires Schur vectors in the PSD")
+        p, n = dT.shape[0], dT.shape[1]
+        if S is not None and len(S) != p:
+            raise DimensionMismatch("length of S must match the period")
+        cplx = dT.is_complex()
+        if dZ.dtype != dT.dtype:
+            raise TypeError("geigvecs_dev: dT and dZ must have the same dtype (float64 or complex128)")
+        if len(select) != n:
+            raise ValueError("length of `select` must correspond to rank of Schur (sub-)space")
+        Sarr = None if S is None else (C.c_uint8 * p)(*[1 if x else 0 for x in S])
+        sel = (C.c_uint8 * n)(*[1 if x else 0 for x in select])
+        st = EvecStats()
+        info = C.c_int(0)
+        fn = self.lib.psd_z_geigvecs_dev if cplx else self.lib.psd_d_geigvecs_dev
+        args = [self.ctx, n, p, C.c_void_p(dT.data_ptr()), C.c_void_p(dZ.data_ptr()), Sarr, char_lr(lr).encode(),
+                int(schurindex), sel, n, int(bool(shifted))]
+        fn(*args, None, 0, None, C.byref(st), C.byref(info))
+        self._raise(info.value)
+        nvec = st.nvec
+        nmat = p if shifted else 1
+        dV = torch.empty((nmat, max(nvec, 1), n), dtype=torch.complex128, device=dT.device)
+        abuf = np.zeros(2 * p * max(nvec, 1))
+        torch.cuda.synchronize(dT.device)
+        fn(*args, C.c_void_p(dV.data_ptr()), nvec, abuf.ctypes.data_as(C.POINTER(C.c_double)), C.byref(st),
+           C.byref(info))
+        self._raise(info.value)
+        self.eigvecs_stats = st
+        a = abuf.view(np.complex128)[:p * nvec].reshape((p, nvec), order="F")
+        return [dV[l, :nvec, :].transpose(0, 1) for l in range(nmat)], a
 
     def _partial_eigvecs(self, ps0, select, shifted, method="ordschur"):
         """eigvecs(ps::PartialPeriodicSchur, select; shifted) — src/krylov.jl:996-1022: the eigenvectors of the k x k

@@ -20,6 +20,7 @@
 #include "psd_check.h"
 #include "psd_krylov.h"
 #include "psd_evec.h"
+#include "psd_gevec.h"
 
 #include "../../include/psd_mi355x.h"
 
@@ -4068,3 +4069,4 @@ extern "C" int psd_dbg_apply_bench(psd_ctx* c, int n, int p, int nwin, int W, in
 #include "psd_check_host.inl"
 #include "psd_krylov_host.inl"
 #include "psd_evec_host.inl"
+#include "psd_gevec_host.inl"
