@@ -8,11 +8,14 @@ BASELINE.json quotes its target on, n=1024, p=64, Float64 (0.5 GiB of factors + 
 256 MiB Infinity Cache); `--n 512 --p 16` gives BASELINE configs[1] as a secondary line.  N>1: see DESIGN.md
 "Multi-GPU"; value = all sweeps of all ranks / max-over-ranks time.
 
-The accuracy gate (device checkpsd + eigenvalues against LAPACK on the explicit product) runs outside the timed
-region; a failed gate makes the exit status non-zero.
-
-After the headline, N = 1 runs BASELINE configs[1]..[4] once each (`configs` in the JSON line: time, sweeps or swaps,
-algorithmic GB/s, fraction of the HBM peak, accuracy gate; `--no-configs` skips them) and the CPU baseline.
+A plain run does only what the headline needs: it builds the input, warms up, times the steps, writes the dumps of
+`--dump-outputs` and prints the line, with the per-step figures (phases, sweeps, roofline) that the timed steps' own
+statistics give.  `--full` adds everything that costs runs or checks of its own, all outside the timed region:
+- the accuracy gate on the last timed step (device checkpsd + eigenvalues against LAPACK on the explicit product;
+  every rank's result in the sharded mode); a failed gate makes the exit status non-zero;
+- N > 1, sharded: the same steps once more as independent replicas (`replicas`);
+- N = 1, Float64: BASELINE configs[1]..[4] once each (`configs`: time, sweeps or swaps, algorithmic GB/s, fraction of
+  the HBM peak, accuracy gate; `--no-configs` skips them) and the CPU baseline (`--no-cpu-baseline` skips it).
 
 Prints ONE JSON line on rank 0.
 """
@@ -350,7 +353,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--n", "--order", dest="n", type=int, default=1024)
     ap.add_argument("--p", "--period", dest="p", type=int, default=64)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the accuracy gate, the replicas line (N > 1, sharded), BASELINE configs[1]..[4] and the "
+                         "CPU baseline (N = 1) after the timed steps")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--mode", choices=["sharded", "replicas"], default="sharded",
                     help="N > 1: 'sharded' = ONE problem, Schur vectors split by period over the ranks (strong scaling); "
                          "'replicas' = one independent problem per rank (weak scaling)")
@@ -358,7 +364,8 @@ def main():
     ap.add_argument("--dtype", choices=["f64", "c128"], default="f64",
                     help="c128: BASELINE configs[2] (pschur! of ComplexF64 factors) as the timed workload, e.g. period-sharded: "
                          "--gpus N --dtype c128")
-    ap.add_argument("--no-configs", action="store_true", help="skip the one-shot runs of BASELINE configs[1]..[4] behind the headline")
+    ap.add_argument("--no-configs", action="store_true",
+                    help="with --full: skip the one-shot runs of BASELINE configs[1]..[4] behind the headline")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step returned (rank 0) as float64 .npy files under DIR: eigenvalues, and a "
                          "fixed, seeded sample of the Schur factors T and the Schur vectors Z")
@@ -407,10 +414,11 @@ def main():
     cplx = args.dtype == "c128"
     if cplx:
         seed = 1234 + 3  # BASELINE config index 3 (configs[2])
-    As = pt.bench_factors(n, p, seed, dtype=np.complex128) if cplx else pt.bench_factors(n, p, seed)
+    As = pt.bench_factors(n, p, seed, dtype=np.complex128 if cplx else np.float64, workers=min(16, os.cpu_count() or 1))
     host = torch.from_numpy(pt.pack(As, np.complex128 if cplx else np.float64))
     total = args.steps + args.warmup
-    bufs = [host.to(device) for _ in range(total)]
+    bufs = [host.to(device)]  # (one host-to-device copy; every other step's operand is a device copy of it)
+    bufs += [bufs[0].clone() for _ in range(total - 1)]
     zbufs = [torch.zeros_like(bufs[0]) for _ in range(total)]
     torch.cuda.synchronize()
 
@@ -440,9 +448,9 @@ def main():
     if sharded:
         sweeps_all = sweeps  # ONE problem: every rank ran the same (replicated) chain, its sweeps count once
     # Beside the sharded line: the same K steps as N independent replicas (one problem per rank, no collective) — the
-    # throughput mode of a path whose chains do not shard.  Reported as an extra object.
+    # throughput mode of a path whose chains do not shard.  Reported as an extra object (--full).
     replicas = None
-    if sharded:
+    if sharded and args.full:
         eng.set_shard(0, 1)
         rb = [host.to(device) for _ in range(args.steps)]
         rz = [torch.zeros_like(rb[0]) for _ in range(args.steps)]
@@ -477,7 +485,7 @@ def main():
     # In the sharded mode every rank checks the decomposition it holds (its own T, the gathered Z) against the input and
     # the verdicts are combined: a rank whose chains had taken another path than the others' would fail here.
     shard_gate_ok = True
-    if sharded:
+    if sharded and args.full:
         okr, _, _, _ = device_gate(results[-1][0])
         flag = torch.tensor([1.0 if okr else 0.0], dtype=torch.float64, device=None if backend != "nccl" else device)
         dist.all_reduce(flag, op=dist.ReduceOp.MIN)
@@ -485,14 +493,20 @@ def main():
     if rank == 0:
         st = results[-1][2]
         lam = results[-1][0]
-        # accuracy gate on the last timed step (outside the timed region): eigenvalues against LAPACK on the explicit
-        # product, and the reference's checkpsd (diagnostics.jl:190-263) evaluated on the device
-        P = pt.product(As)
-        lam_ref = np.linalg.eigvals(P)
-        lam_err = pt.match_eigs(lam_ref, lam) / np.linalg.norm(P, 2)
-        thresh = 100 * np.sqrt(n / 32)
-        ok, err, orth, tri = device_gate(lam)
-        gate_ok = bool(bool(ok) and float(lam_err) <= 1e-10 and shard_gate_ok)
+        gate_ok = True
+        accuracy = None
+        if args.full:
+            # accuracy gate on the last timed step (outside the timed region): eigenvalues against LAPACK on the explicit
+            # product, and the reference's checkpsd (diagnostics.jl:190-263) evaluated on the device
+            P = pt.product(As)
+            lam_ref = np.linalg.eigvals(P)
+            lam_err = pt.match_eigs(lam_ref, lam) / np.linalg.norm(P, 2)
+            thresh = 100 * np.sqrt(n / 32)
+            ok, err, orth, tri = device_gate(lam)
+            gate_ok = bool(bool(ok) and float(lam_err) <= 1e-10 and shard_gate_ok)
+            accuracy = {"gate_ok": gate_ok, "eig_rel_err_vs_numpy_prod": float(lam_err), "eig_tol": 1e-10,
+                        "checkpsd_ok": bool(ok), "checkpsd_max_err_eps": float(err.max()), "checkpsd_thresh_eps": thresh,
+                        "orth_max_over_eps_n": float(orth.max() / (pt.EPS * n)), "evaluated": "device (psd_d_checkpsd_dev)"}
         if args.dump_outputs:
             dump_outputs(args.dump_outputs, lam, bufs[-1], zbufs[-1], cplx)
 
@@ -582,20 +596,19 @@ def main():
                                  "hessenberg": st.bytes_hess / (st.ms_hess * 1e-3) / 1e9 if st.ms_hess else None,
                                  "whole_call": (bytes_sw / args.steps + st.bytes_hess + st.bytes_formq) * args.steps / elapsed / 1e9},
             "time_to_solution_s": elapsed_max / args.steps,
-            "accuracy": {"gate_ok": gate_ok, "eig_rel_err_vs_numpy_prod": float(lam_err), "eig_tol": 1e-10, "checkpsd_ok": bool(ok),
-                         "checkpsd_max_err_eps": float(err.max()), "checkpsd_thresh_eps": thresh,
-                         "orth_max_over_eps_n": float(orth.max() / (pt.EPS * n)), "evaluated": "device (psd_d_checkpsd_dev)"},
             "roofline": roof,
         }
+        if accuracy is not None:
+            out["accuracy"] = accuracy
         if replicas is not None:
             out["replicas"] = replicas
-        if world == 1 and not args.no_configs and not cplx:
+        if args.full and world == 1 and not args.no_configs and not cplx:
             del bufs, zbufs
             torch.cuda.empty_cache()
             out["configs"] = run_configs(eng, torch, device)
             if not all(c["gate_ok"] for c in out["configs"].values()):
                 gate_ok = False
-        if world == 1 and not args.no_cpu_baseline and not cplx:
+        if args.full and world == 1 and not args.no_cpu_baseline and not cplx:
             positions = sum(int((lg[lg[:, 0] == 0][:, 2] - lg[lg[:, 0] == 0][:, 1] + 1).sum()) for (_, _, _, lg) in results)
             out["sweep_positions_per_step"] = positions / args.steps
             out["cpu_baseline"] = cpu_baseline(n, p, seed, eng, positions / args.steps)

@@ -41,21 +41,28 @@ def randn_counter(seed, stream, count):
     return np.sqrt(-2.0 * np.log(f1)) * np.cos(2.0 * np.pi * f2)
 
 
-def synth_factors(n, p, seed, dtype=np.float64):
+def synth_factors(n, p, seed, dtype=np.float64, workers=1):
     """p factors n x n with i.i.d. N(0, 1/n) entries (complex: re, im ~ N(0, 1/(2n))): spectral radius ~ 1
-    per factor, so the period-p product neither overflows nor underflows."""
-    out = []
-    for j in range(p):
+    per factor, so the period-p product neither overflows nor underflows.  `workers` > 1 draws
+    the factors on that many threads (numpy's loops release the GIL; every factor is its own stream, so the
+    result does not depend on it)."""
+    def one(j):
         if np.issubdtype(dtype, np.complexfloating):
             g = randn_counter(seed, j, 2 * n * n)
             a = (g[: n * n] + 1j * g[n * n:]) / np.sqrt(2.0 * n)
         else:
             a = randn_counter(seed, j, n * n) / np.sqrt(float(n))
-        out.append(np.asfortranarray(a.reshape(n, n).astype(dtype)))
-    return out
+        return np.asfortranarray(a.reshape(n, n).astype(dtype))
+
+    if workers > 1 and p > 1:
+        from concurrent.futures import ThreadPoolExecutor
+
+        with ThreadPoolExecutor(min(workers, p)) as ex:
+            return list(ex.map(one, range(p)))
+    return [one(j) for j in range(p)]
 
 
-def bench_factors(n, p, seed, dtype=np.float64, eps=0.5):
+def bench_factors(n, p, seed, dtype=np.float64, eps=0.5, workers=1):
     """Benchmark / parity ensemble: A_j = I + eps * G_j / sqrt(n), G_j i.i.d. standard normal.
 
     SURVEY.md §8(d) proposed plain N(0, 1/n) factors, but the period-p product of those has real eigenvalue
@@ -64,7 +71,7 @@ def bench_factors(n, p, seed, dtype=np.float64, eps=0.5):
     sub-diagonal of 1e-11..1e-6 in T1 that is then zeroed (:1066-1073): the reference algorithm fails its own
     `checkpsd` there (measured with the oracle; DESIGN.md "Inputs").  Shifting by I keeps every factor well
     conditioned, so the reference's invariants hold and can be demanded of the GPU path."""
-    return [np.asfortranarray(np.eye(n, dtype=dtype) + eps * a) for a in synth_factors(n, p, seed, dtype)]
+    return [np.asfortranarray(np.eye(n, dtype=dtype) + eps * a) for a in synth_factors(n, p, seed, dtype, workers)]
 
 
 def rand_uniform_factors(n, p, seed):

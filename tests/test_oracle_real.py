@@ -117,6 +117,18 @@ def test_medium_bench_ensemble(built):
     assert pt.match_eigs(lam, ps.values) < 1e-10 * np.linalg.norm(pt.product(As), 2)
 
 
+@pytest.mark.parametrize("dtype", [np.float64, np.complex128])
+def test_bench_factors_threaded_draw_is_identical(dtype):
+    """bench.py draws its input on several threads (psdtest.bench_factors(workers=...)): the factors must be the
+    serial draw's, bit for bit and in the same order."""
+    serial = pt.bench_factors(48, 7, seed=1236, dtype=dtype)
+    threaded = pt.bench_factors(48, 7, seed=1236, dtype=dtype, workers=4)
+    assert len(threaded) == len(serial)
+    for a, b in zip(serial, threaded):
+        assert b.dtype == a.dtype and b.flags.f_contiguous
+        assert np.array_equal(a, b)
+
+
 def test_input_ensemble_claim_plain_gaussian_breaks_reference_checkpsd():
     """DESIGN.md section 6 / psdtest.bench_factors: SURVEY.md 8(d) proposed plain N(0, 1/n) factors, but on their
     period-32 products the REFERENCE algorithm (the oracle restates it) fails its own checkpsd — the 2x2

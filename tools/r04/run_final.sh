@@ -3,8 +3,8 @@
 set -o pipefail
 O=gpurun_out/r04y; mkdir -p $O
 R=$GRAFT_REPO_ROOT
-python bench.py > $O/bench_default.json 2> $O/bench_default.err; tail -c 300 $O/bench_default.err
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_command.json 2> $O/bench_driver.err; tail -c 300 $O/bench_driver.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; tail -c 300 $O/bench_default.err
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_command.json 2> $O/bench_driver.err; tail -c 300 $O/bench_driver.err
 python - <<'PY'
 import json
 for f in ("bench_default", "bench_driver_command"):
@@ -13,8 +13,8 @@ for f in ("bench_default", "bench_driver_command"):
     if "configs" in d:
         for k, v in d["configs"].items(): print("  ", k, "%.1f ms" % v["ms"], v.get("phase_ms"), v["gate_ok"], "%.0f eps" % v["checkpsd_max_err_eps"], v.get("swaps"), v.get("residual_over_oracle"))
 PY
-python bench.py --dtype c128 --steps 1 --warmup 1 --no-cpu-baseline --no-configs > $O/bench_c128_1024x64.json 2>> $O/bench_default.err
-for n in 512 1536 2048; do python bench.py --order $n --period 64 --steps 1 --warmup 1 --no-cpu-baseline --no-configs > $O/bench_${n}x64.json 2>> $O/bench_default.err; done
+python bench.py --full --dtype c128 --steps 1 --warmup 1 --no-cpu-baseline --no-configs > $O/bench_c128_1024x64.json 2>> $O/bench_default.err
+for n in 512 1536 2048; do python bench.py --full --order $n --period 64 --steps 1 --warmup 1 --no-cpu-baseline --no-configs > $O/bench_${n}x64.json 2>> $O/bench_default.err; done
 python - <<'PY'
 import json
 for f in ("bench_c128_1024x64", "bench_512x64", "bench_1536x64", "bench_2048x64"):

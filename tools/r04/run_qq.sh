@@ -1,8 +1,8 @@
 #!/bin/bash
 set -o pipefail
 O=gpurun_out/r04y; mkdir -p $O
-python bench.py > $O/bench_default.json 2> $O/bench_default.err; tail -c 200 $O/bench_default.err
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_command.json 2> $O/bench_driver.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; tail -c 200 $O/bench_default.err
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_command.json 2> $O/bench_driver.err
 python - <<'PY'
 import json
 for f in ("bench_default", "bench_driver_command"):

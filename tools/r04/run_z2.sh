@@ -1,7 +1,7 @@
 #!/bin/bash
 set -o pipefail
 O=gpurun_out/r04y; mkdir -p $O
-for n in 1536 2048; do python bench.py --order $n --period 64 --steps 1 --warmup 1 --no-cpu-baseline --no-configs > $O/bench_${n}x64.json 2>> $O/bench_default.err; done
+for n in 1536 2048; do python bench.py --full --order $n --period 64 --steps 1 --warmup 1 --no-cpu-baseline --no-configs > $O/bench_${n}x64.json 2>> $O/bench_default.err; done
 python - <<'PY'
 import json
 for f in ("bench_1536x64", "bench_2048x64"):
