@@ -331,6 +331,54 @@ int psd_z_partial_pschur_dev(psd_ctx* ctx, int n, int p, const double* dA, int n
                              int* nconv, double* const* T, double* dZ, double* wr, double* wi, psd_krylov_stats* stats,
                              int* info);
 
+/* ---- partial_pschur for sparse factors (CSR) — the reference takes "matrices or any linear maps that implement mul!"
+ * (krylov.jl:416-487); the sparse Jacobians of a discretised periodic problem are the linear maps that matter in practice.
+ * Factor l is a CSR triple: rowptr[l] (n + 1 entries, int64), colind[l] (rowptr[l][n] entries, int32), both 0-based, and
+ * val[l] (as many elements, Float64, or ComplexF64 as interleaved (re, im); the product is plain, not conjugated).  The
+ * columns of a row may come in any order and may repeat (repeats add up).  Only the matrix-vector product differs from
+ * the dense driver: a device SpMV without floating-point atomics, whose summation order depends on the matrix and on a
+ * group width G alone (a row is summed by G consecutive lanes: lane g takes the entries start + g, start + g + G, ... in
+ * that order, then a fixed tree runs over the lanes).  G is the smallest power of two >= nnz / n in [1, 64], chosen from
+ * n and nnz only, so a run repeats bit for bit on any machine.  A row is never split, so a few very long rows in a very
+ * sparse matrix are correct but not fast.  All other arguments, the outputs and the algorithmic info values are those of
+ * psd_d_partial_pschur.
+ *
+ * Argument codes as psd_d_partial_pschur, with: -4 also for a NULL rowptr / colind / val array or a NULL element of one;
+ *   -19 rowptr invalid (rowptr[0] != 0, decreasing, or rowptr[n] negative or above 2^40);
+ *   -20 a column index outside [0, n).
+ * The host entries check the structure on the host before anything is copied.  The `_dev` entries take the same three
+ * host arrays, of p DEVICE pointers, and dZ as psd_d_partial_pschur_dev; they read rowptr[n] of every factor and run a
+ * structure-check kernel (which reads rowptr and colind and gathers through neither) before any Krylov work, so -19 and
+ * -20 come back before an index is ever used as an address. */
+int psd_d_partial_pschur_csr(psd_ctx* ctx, int n, int p, const int64_t* const* rowptr, const int32_t* const* colind,
+                             const double* const* val, int nev, char which, int mindim, int maxdim, const double* u1,
+                             uint64_t seed, double tol, double tol1, int restarts, int purgebuffer, int* nconv,
+                             double* const* T, double* const* Z, double* wr, double* wi, psd_krylov_stats* stats,
+                             int* info);
+int psd_z_partial_pschur_csr(psd_ctx* ctx, int n, int p, const int64_t* const* rowptr, const int32_t* const* colind,
+                             const double* const* val, int nev, char which, int mindim, int maxdim, const double* u1,
+                             uint64_t seed, double tol, double tol1, int restarts, int purgebuffer, int* nconv,
+                             double* const* T, double* const* Z, double* wr, double* wi, psd_krylov_stats* stats,
+                             int* info);
+int psd_d_partial_pschur_csr_dev(psd_ctx* ctx, int n, int p, const int64_t* const* rowptr, const int32_t* const* colind,
+                                 const double* const* val, int nev, char which, int mindim, int maxdim, const double* u1,
+                                 uint64_t seed, double tol, double tol1, int restarts, int purgebuffer, int* nconv,
+                                 double* const* T, double* dZ, double* wr, double* wi, psd_krylov_stats* stats,
+                                 int* info);
+int psd_z_partial_pschur_csr_dev(psd_ctx* ctx, int n, int p, const int64_t* const* rowptr, const int32_t* const* colind,
+                                 const double* const* val, int nev, char which, int mindim, int maxdim, const double* u1,
+                                 uint64_t seed, double tol, double tol1, int restarts, int purgebuffer, int* nconv,
+                                 double* const* T, double* dZ, double* wr, double* wi, psd_krylov_stats* stats,
+                                 int* info);
+/* y = A x for one CSR factor through the driver's own kernel, once: host buffers (x, y: n elements); group = G as above,
+ * 0 for the automatic width.  The result has the driver's rounding, so it pins the kernel at a chosen G.
+ * info: -1 ctx NULL; -2 n < 1; -4 rowptr, colind or val NULL; -8 group not 0 and not a power of two <= 64; -9 x NULL;
+ * -17 y NULL; -19 / -20 as above; PSD_INFO_RUNTIME + k. */
+int psd_d_csr_matvec(psd_ctx* ctx, int n, const int64_t* rowptr, const int32_t* colind, const double* val,
+                     const double* x, double* y, int group, int* info);
+int psd_z_csr_matvec(psd_ctx* ctx, int n, const int64_t* rowptr, const int32_t* colind, const double* val,
+                     const double* x, double* y, int group, int* info);
+
 /* ---- eigvecs(ps, select; shifted) by periodic back-substitution — vectors.jl:25-138 without the reordering ----------
  * The selected right eigenvectors of the product and of its circular shifts, from a periodic Schur decomposition, by
  * the periodic form of LAPACK's xTREVC: the triangular factors are solved bottom up (a cyclic recurrence round the period

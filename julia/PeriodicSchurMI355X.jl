@@ -1,8 +1,8 @@
 # PeriodicSchurMI355X.jl — reference-side binding of libpsd_mi355x.so (include/psd_mi355x.h).
 #
 # Loaded next to RalphAS/PeriodicSchurDecompositions.jl v0.1.6, this module re-points the package's hot path
-# (pschur!/pschur, phessenberg!, gpschur, both ordschur! families, checkpsd, partial_pschur on dense factors) at the MI355X
-# engine for Float64 and ComplexF64 operands; everything else of the package (the Krylov driver on linear maps, eigvecs,
+# (pschur!/pschur, phessenberg!, gpschur, both ordschur! families, checkpsd, partial_pschur on dense and on sparse
+# factors) at the MI355X engine for Float64 and ComplexF64 operands; everything else of the package (the Krylov driver on linear maps, eigvecs,
 # generic element types) keeps running the Julia code, which now reaches the engine through these methods wherever it
 # calls them.
 #
@@ -17,6 +17,7 @@ module PeriodicSchurMI355X
 
 using LinearAlgebra
 using LinearAlgebra: checksquare
+using SparseArrays: SparseMatrixCSC, sparse, getcolptr, rowvals, nonzeros
 import PeriodicSchurDecompositions
 import PeriodicSchurDecompositions: pschur!, pschur, phessenberg!, gpschur, PeriodicSchur, GeneralizedPeriodicSchur,
                                     checkpsd
@@ -412,8 +413,9 @@ end
 
 # ---------------------------------------------------------------------------------------------------------------------
 # partial_pschur(As, nev, which; ...) — krylov.jl:446-487, for dense Float64 / ComplexF64 factors: the Krylov steps run on
-# the device (psd_d_partial_pschur / psd_z_partial_pschur).  Operators given as linear maps keep the reference's CPU
-# driver (this method only matches Vector{Matrix{T}}).  The reference's `vrand!` keyword is NOT honoured on the device:
+# the device (psd_d_partial_pschur / psd_z_partial_pschur); sparse factors have the method further down.  Operators given
+# as other linear maps keep the reference's CPU driver (these methods only match Vector{Matrix{T}} and
+# Vector{SparseMatrixCSC{T,Int}}).  The reference's `vrand!` keyword is NOT honoured on the device:
 # without `u1` the start vector comes from the library's counter-based generator, seeded by `seed`.
 const _KTARGET = Dict(ArnoldiMethod.LM => 'M', ArnoldiMethod.LR => 'R', ArnoldiMethod.SR => 'r',
                       ArnoldiMethod.LI => 'I', ArnoldiMethod.SI => 'i')
@@ -456,10 +458,17 @@ function PSD.partial_pschur(As::Vector{Matrix{T}}, nev::Integer, which::ArnoldiM
                    Ptr{UInt8}, Ref{Cint}), args...)
         end
     end
-    info[] == INFO_PKSFAIL && throw(PSD.PKSFailure("Arnoldi reinitialization failed"))                  # krylov.jl:182
-    2000 <= info[] < 3000 && throw(PSD.IllConditionedException(info[] - 2000))
-    _throw(info[])
-    k = Int(nconv[])
+    return _partial_result(info[], Int(nconv[]), Ts, Zs, wr, wi, st, nev)
+end
+
+# error mapping and result construction of the partial_pschur methods
+function _partial_result(info::Integer, k::Int, Ts, Zs, wr, wi, st, nev)
+    p = length(Ts)
+    info == INFO_PKSFAIL && throw(PSD.PKSFailure("Arnoldi reinitialization failed"))                    # krylov.jl:182
+    2000 <= info < 3000 && throw(PSD.IllConditionedException(info - 2000))
+    info == -19 && throw(ArgumentError("invalid CSR row pointers"))
+    info == -20 && throw(ArgumentError("CSR column index outside [0, n)"))
+    _throw(info)
     # T[l] holds the k x k factor with leading dimension k in its first k^2 elements
     Tk = [copy(reshape(view(vec(Ts[l]), 1:(k * k)), k, k)) for l in 1:p]
     Zk = [Zs[l][:, 1:k] for l in 1:p]
@@ -467,6 +476,58 @@ function PSD.partial_pschur(As::Vector{Matrix{T}}, nev::Integer, which::ArnoldiM
     nprods = Int(reinterpret(Int64, st[1:8])[1])
     ps = PSD.PartialPeriodicSchur(Tk[p], Tk[1:(p - 1)], Zk, λ)                                         # krylov.jl:796
     return ps, ArnoldiMethod.History(nprods, k, k ≥ nev, nev)
+end
+
+# partial_pschur for sparse factors (psd_d_partial_pschur_csr / psd_z_partial_pschur_csr): the products run through the
+# device SpMV.  The library takes CSR; the CSR of A is the CSC of transpose(A) (plain transpose, for ComplexF64 too: the
+# values are not conjugated), shifted to 0-based, with the row pointers as Int64 and the column indices as Int32.  Other
+# linear maps (anything that only implements `mul!`) and lists that mix dense and sparse factors keep the reference's CPU
+# driver.
+function PSD.partial_pschur(As::Vector{SparseMatrixCSC{T, Int}}, nev::Integer,
+                            which::ArnoldiMethod.Target = ArnoldiMethod.LM();
+                            mindim::Integer = min(max(10, nev), size(As[1], 1)),
+                            maxdim::Integer = min(max(20, 2nev), size(As[1], 1)),
+                            u1 = nothing, tol = sqrt(eps(Float64)), tol1 = 100 * eps(Float64),
+                            restarts = 100, purgebuffer = 2, seed::Integer = 0) where {T <: BlasElt}
+    p = length(As); n = size(As[1], 1)
+    for l in 1:p
+        checksquare(As[l]) == n || throw(ArgumentError("all As must have the same (square) size"))     # krylov.jl:457-461
+    end
+    nev < 1 && throw(ArgumentError("nev cannot be less than 1"))                                         # :462-464
+    nev ≤ mindim ≤ maxdim ≤ p * n ||
+        throw(ArgumentError("nev ≤ mindim ≤ maxdim does not hold, got $nev ≤ $mindim ≤ $maxdim"))        # :465-466
+    u = u1 === nothing ? nothing : Vector{T}(u1)
+    u === nothing || length(u) == n || throw(ArgumentError("u1 must have length matching first matrix/operator"))
+    At = [sparse(transpose(A)) for A in As]
+    rowptr = [Int64.(getcolptr(A) .- 1) for A in At]
+    colind = [Int32.(rowvals(A) .- 1) for A in At]
+    vals = [Vector{T}(nonzeros(A)) for A in At]
+    Ts = [Matrix{T}(undef, maxdim, maxdim) for _ in 1:p]
+    Zs = [Matrix{T}(undef, n, maxdim) for _ in 1:p]
+    wr = zeros(maxdim); wi = zeros(maxdim)
+    nconv = Ref{Cint}(0); info = Ref{Cint}(0)
+    st = zeros(UInt8, 96)
+    Tp = _ptrs(Ts); Zp = _ptrs(Zs)
+    GC.@preserve rowptr colind vals Ts Zs u wr wi st begin
+        Rp = Ptr{Int64}[pointer(r) for r in rowptr]
+        Cp = Ptr{Int32}[pointer(c) for c in colind]
+        Vp = Ptr{Float64}[Ptr{Float64}(pointer(v)) for v in vals]
+        up = u === nothing ? Ptr{Float64}(C_NULL) : Ptr{Float64}(pointer(u))
+        args = (ctx().ptr, n, p, Rp, Cp, Vp, nev, _KTARGET[typeof(which)], mindim, maxdim, up, UInt64(seed),
+                Float64(tol), Float64(tol1), restarts, purgebuffer, nconv, Tp, Zp, wr, wi, pointer(st), info)
+        if T <: Real
+            ccall((:psd_d_partial_pschur_csr, libpsd), Cint,
+                  (Ptr{Cvoid}, Cint, Cint, Ptr{Ptr{Int64}}, Ptr{Ptr{Int32}}, Ptr{Ptr{Float64}}, Cint, Cchar, Cint, Cint,
+                   Ptr{Float64}, UInt64, Cdouble, Cdouble, Cint, Cint, Ref{Cint}, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}},
+                   Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Ref{Cint}), args...)
+        else
+            ccall((:psd_z_partial_pschur_csr, libpsd), Cint,
+                  (Ptr{Cvoid}, Cint, Cint, Ptr{Ptr{Int64}}, Ptr{Ptr{Int32}}, Ptr{Ptr{Float64}}, Cint, Cchar, Cint, Cint,
+                   Ptr{Float64}, UInt64, Cdouble, Cdouble, Cint, Cint, Ref{Cint}, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}},
+                   Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Ref{Cint}), args...)
+        end
+    end
+    return _partial_result(info[], Int(nconv[]), Ts, Zs, wr, wi, st, nev)
 end
 
 

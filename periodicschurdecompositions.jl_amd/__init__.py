@@ -10,6 +10,7 @@ INTEGRATION.md.
 All numerical work happens in the HIP library.  There is no CPU fallback: if the library is
 missing or no GPU is visible, `Engine()` raises.
 """
+import collections
 import ctypes as C
 import os
 
@@ -163,6 +164,54 @@ class History:
 KRYLOV_TARGETS = {"LM": "M", "LR": "R", "SR": "r", "LI": "I", "SI": "i"}
 
 
+# One sparse factor of partial_pschur in CSR form: order n, row pointers (n + 1), column indices and values (0-based).
+CSR = collections.namedtuple("CSR", "n indptr indices data")
+
+
+def _is_torch_csr(a):
+    return type(a).__module__.split(".")[0] == "torch" and str(getattr(a, "layout", "")) == "torch.sparse_csr"
+
+
+def _host_csr(a):
+    """A sparse factor given on the host as a CSR tuple, or None: a `CSR` (or any (n, indptr, indices, data)), a bare
+    (indptr, indices, data) of a square matrix, or an object with .indptr / .indices / .data / .shape and
+    format == "csr" (scipy's csr_matrix / csr_array, by duck typing); other scipy formats through their own .tocsr()."""
+    if isinstance(a, tuple) and len(a) == 4:
+        return CSR(int(a[0]), *a[1:])
+    if isinstance(a, tuple) and len(a) == 3:
+        return CSR(len(a[0]) - 1, *a)
+    fmt = getattr(a, "format", None)
+    if isinstance(fmt, str) and fmt != "csr" and hasattr(a, "tocsr"):
+        a = a.tocsr()
+        fmt = getattr(a, "format", None)
+    if fmt == "csr" and all(hasattr(a, k) for k in ("indptr", "indices", "data", "shape")):
+        if len(a.shape) != 2 or a.shape[0] != a.shape[1]:
+            raise DimensionMismatch("all As must have the same (square) size")  # krylov.jl:460-464
+        return CSR(int(a.shape[0]), a.indptr, a.indices, a.data)
+    return None
+
+
+def _csr_arrays(a, dt):
+    """(indptr int64, indices int32, data dt) of a host CSR factor, contiguous.  Column indices that int32 cannot hold
+    are clamped to -1 / n, which the library reports as out of range."""
+    if a.n < 1:
+        raise DimensionMismatch("all As must have the same (square) size")
+    indptr = np.ascontiguousarray(np.asarray(a.indptr).reshape(-1), dtype=np.int64)
+    ind = np.asarray(a.indices).reshape(-1)
+    if ind.dtype != np.int32:
+        ind = np.clip(ind.astype(np.int64), -1, a.n).astype(np.int32)
+    data = np.ascontiguousarray(np.asarray(a.data).reshape(-1), dtype=dt)
+    if indptr.shape[0] != a.n + 1:
+        raise DimensionMismatch("all As must have the same (square) size")
+    if ind.shape[0] != data.shape[0] or indptr[-1] > ind.shape[0]:
+        raise ValueError("invalid CSR row pointers (indptr): the last entry exceeds the stored entries")
+    return indptr, np.ascontiguousarray(ind), data
+
+
+_CSR_ERRORS = {-19: "invalid CSR row pointers (indptr): they must start at 0, not decrease and end at the entry count",
+               -20: "CSR column index outside [0, n)"}
+
+
 def char_lr(lr):
     """src/PeriodicSchurDecompositions.jl:155-163,175-177."""
     if lr in ("R", ":R"):
@@ -248,6 +297,13 @@ class Engine:
             getattr(lib, nm).argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p if dev else dpp, C.c_int, C.c_char,
                                          C.c_int, C.c_int, dp, C.c_uint64, C.c_double, C.c_double, C.c_int, C.c_int,
                                          ip, dpp, C.c_void_p if dev else dpp, dp, dp, C.POINTER(KrylovStats), ip]
+        for nm, dev in (("psd_d_partial_pschur_csr", False), ("psd_z_partial_pschur_csr", False),
+                        ("psd_d_partial_pschur_csr_dev", True), ("psd_z_partial_pschur_csr_dev", True)):
+            getattr(lib, nm).argtypes = [C.c_void_p, C.c_int, C.c_int, dpp, dpp, dpp, C.c_int, C.c_char, C.c_int, C.c_int,
+                                         dp, C.c_uint64, C.c_double, C.c_double, C.c_int, C.c_int, ip, dpp,
+                                         C.c_void_p if dev else dpp, dp, dp, C.POINTER(KrylovStats), ip]
+        lib.psd_d_csr_matvec.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, dp, dp, C.c_int, ip]
+        lib.psd_z_csr_matvec.argtypes = lib.psd_d_csr_matvec.argtypes
         i32p = C.POINTER(C.c_int32)
         for nm, dev, cplx in (("psd_d_eigvecs", False, False), ("psd_z_eigvecs", False, True),
                               ("psd_d_eigvecs_dev", True, False), ("psd_z_eigvecs_dev", True, True)):
@@ -1128,18 +1184,84 @@ class Engine:
                 out.append(np.asarray(z) @ v)
         return out
 
+    @staticmethod
+    def _csr_factors(As):
+        """The sparse forms of partial_pschur's `As`: None when no factor is sparse, else (dev, n, p, cplx, (indptr list,
+        indices list, data list)) as the CSR entry points take them — numpy arrays (host entry) or torch device tensors
+        (device-resident entry), int64 / int32 / Float64 or ComplexF64."""
+        if not isinstance(As, (list, tuple)) or isinstance(As, CSR):
+            return None
+        tor = [_is_torch_csr(a) for a in As]
+        host = [None if t or isinstance(a, np.ndarray) else _host_csr(a) for a, t in zip(As, tor)]
+        nsp = sum(tor) + sum(h is not None for h in host)
+        if nsp == 0:
+            return None
+        if nsp != len(As) or (any(tor) and not all(tor)):
+            raise TypeError("partial_pschur takes dense factors or sparse factors of one kind, not a mix")
+        if all(tor):
+            import torch
+
+            if not all(a.is_cuda for a in As):
+                raise TypeError("device-resident partial_pschur needs GPU tensors (use CSR tuples for host input)")
+            n = As[0].shape[0]
+            if any(a.dim() != 2 or tuple(a.shape) != (n, n) for a in As):
+                raise DimensionMismatch("all As must have the same (square) size")  # krylov.jl:460-464
+            cplx = any(a.is_complex() for a in As)
+            vt = torch.complex128 if cplx else torch.float64
+            # (column indices int32 cannot hold go to -1 / n: the structure check reports them)
+            parts = ([a.crow_indices().to(torch.int64).contiguous() for a in As],
+                     [a.col_indices().clamp(-1, n).to(torch.int32).contiguous() for a in As],
+                     [a.values().to(vt).contiguous() for a in As])
+            return True, n, len(As), cplx, parts
+        n = host[0].n
+        if any(h.n != n for h in host):
+            raise DimensionMismatch("all As must have the same (square) size")  # krylov.jl:460-464
+        cplx = any(np.iscomplexobj(h.data) for h in host)
+        arrs = [_csr_arrays(h, np.complex128 if cplx else np.float64) for h in host]
+        return False, n, len(As), cplx, tuple([a[i] for a in arrs] for i in range(3))
+
+    def csr_matvec(self, A, x, group=0):
+        """y = A x for one sparse factor (a host form of partial_pschur's) through the driver's own SpMV kernel, run
+        once: `group` pins the lanes per row (a power of two <= 64; 0: the automatic width), so the result has the
+        rounding of the driver's products."""
+        h = _host_csr(A)
+        if h is None:
+            raise TypeError("csr_matvec needs a CSR tuple or a scipy sparse matrix")
+        cplx = np.iscomplexobj(h.data) or np.iscomplexobj(x)
+        dt = np.complex128 if cplx else np.float64
+        indptr, ind, data = _csr_arrays(h, dt)
+        xa = np.ascontiguousarray(np.asarray(x, dtype=dt).reshape(-1))
+        if xa.shape[0] != h.n:
+            raise DimensionMismatch("x must have length matching the matrix")
+        y = np.zeros(h.n, dtype=dt)
+        info = C.c_int(0)
+        dp = C.POINTER(C.c_double)
+        fn = self.lib.psd_z_csr_matvec if cplx else self.lib.psd_d_csr_matvec
+        fn(self.ctx, h.n, indptr.ctypes.data, ind.ctypes.data, data.ctypes.data, xa.view(np.float64).ctypes.data_as(dp),
+           y.view(np.float64).ctypes.data_as(dp), int(group), C.byref(info))
+        if info.value in _CSR_ERRORS:
+            raise ValueError(_CSR_ERRORS[info.value])
+        if info.value == -8:
+            raise ValueError(f"group must be 0 or a power of two <= 64, got {group}")
+        self._raise(info.value)
+        return y
+
     def partial_pschur(self, As, nev=None, which="LM", *, mindim=None, maxdim=None, u1=None, tol=None, tol1=None,
                        restarts=100, purgebuffer=2, seed=0):
         """partial_pschur(As, nev, which; mindim, maxdim, u1, tol, tol1, restarts, purgebuffer) — src/krylov.jl:446-487,
-        for dense factors on the device.  `As`: a list of p numpy n x n matrices (host entry) or of torch device tensors
-        / one torch [p, n, n] device tensor (device-resident entry: the Schur vectors come back as torch tensors on the
-        same device).  `which`: "LM", "LR", "SR", "LI" or "SI".  `seed` replaces the reference's `vrand!`: without `u1`
+        for dense or sparse factors on the device.  `As`: a list of p numpy n x n matrices (host entry) or of torch device
+        tensors / one torch [p, n, n] device tensor (device-resident entry: the Schur vectors come back as torch tensors
+        on the same device); or a list of p sparse factors, all `CSR` tuples / scipy sparse matrices (host entry) or all
+        torch sparse-CSR device tensors (device-resident entry).  Dense and sparse factors do not mix.  `which`: "LM", "LR", "SR", "LI" or "SI".  `seed` replaces the reference's `vrand!`: without `u1`
         the start vector comes from a counter-based generator seeded by it.  Returns (PartialPeriodicSchur, History);
         the counters of the call are in `P.stats` (KrylovStats)."""
         if which not in KRYLOV_TARGETS:
             raise ValueError(f"unknown target {which!r}: one of LM, LR, SR, LI, SI")
+        sparse = self._csr_factors(As)
         dev = not (isinstance(As, (list, tuple)) and all(isinstance(a, np.ndarray) for a in As))
-        if dev:
+        if sparse:
+            dev, n, p, cplx, csr = sparse
+        elif dev:
             import torch
 
             dA = As if isinstance(As, torch.Tensor) else torch.stack(list(As))
@@ -1188,7 +1310,26 @@ class Engine:
         up = uarr.view(np.float64).ctypes.data_as(dp) if uarr is not None else None
         common = (int(nev), KRYLOV_TARGETS[which].encode(), int(mindim), int(maxdim), up, int(seed) & (2 ** 64 - 1),
                   float(tol), float(tol1), int(restarts), int(purgebuffer), C.byref(nconv), self._ptrs(Ts))
-        if dev:
+        if sparse:
+            sfx = "_csr_dev" if dev else "_csr"
+            fn = getattr(self.lib, ("psd_z_partial_pschur" if cplx else "psd_d_partial_pschur") + sfx)
+            if dev:
+                import torch
+
+                vals = csr[2]
+                dZ = torch.zeros((p, kmax, n), dtype=vals[0].dtype, device=vals[0].device)
+                torch.cuda.synchronize(vals[0].device)
+                ptrs = [(C.c_void_p * p)(*[t.data_ptr() for t in part]) for part in csr]
+                zarg = C.c_void_p(dZ.data_ptr())
+            else:
+                Zs = [np.zeros((n, kmax), dtype=dt, order="F") for _ in range(p)]
+                ptrs = [self._ptrs(part) for part in csr]
+                zarg = self._ptrs(Zs)
+            fn(self.ctx, n, p, *ptrs, *common, zarg, wr.ctypes.data_as(dp), wi.ctypes.data_as(dp), C.byref(st),
+               C.byref(info))
+            if info.value in _CSR_ERRORS:
+                raise ValueError(_CSR_ERRORS[info.value])
+        elif dev:
             import torch
 
             dZ = torch.zeros((p, kmax, n), dtype=dA.dtype, device=dA.device)  # block l: n x kmax column-major

@@ -367,3 +367,6 @@ PSD_KERNEL_B(64) psd_kr_reset(int* st) {
         st[PSD_KR_ST_KIND] = 0;
     }
 }
+
+// CSR operators (sparse factors): the matvec that writes v directly, and the structure check
+#include "psd_csr.h"

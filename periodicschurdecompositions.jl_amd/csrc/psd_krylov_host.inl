@@ -5,11 +5,22 @@
 // owns (never the context's dH / dZ: the projected pschur_hess / ordschur calls reserve those at their own order).  The
 // projected problems are solved through the engine's own entry points on the same context, on host copies of order
 // <= maxdim.  Indices below follow the reference: 1-based where a line of krylov.jl is restated.
+//
+// The factors are dense ([p][n][n], read through psd_kr_mv) or sparse (p CSR triples, read through psd_kr_csr_mv, which
+// writes the work vector directly); everything behind the product sees them only through that vector.
 #include <algorithm>
 #include <complex>
 #include <type_traits>
 
 namespace {
+
+// p sparse factors on the device: host arrays of p device pointers, and log2 of the group width of each factor
+struct KrylovCsr {
+    const int64_t* const* rowptr;
+    const int32_t* const* colind;
+    const double* const* val;
+    const int* lg;
+};
 
 template <bool Z>
 struct KrylovRun {
@@ -21,7 +32,8 @@ struct KrylovRun {
     double tol, tol1;
     uint64_t seed, draw = 0;
     psd_krylov_stats* st;
-    const double* dA;  // [p][n][n]
+    const double* dA = nullptr;     // dense factors [p][n][n], or
+    const KrylovCsr* csr = nullptr;  // sparse factors
     // device
     psd_devbuf bV, bpart, bv, bpA, bpB, bw1, bw2, bh, bH, bQ, bst;
     int nchunk = 1, ccols = 1, nblk = 1, ldp = 1;
@@ -48,7 +60,7 @@ struct KrylovRun {
         nchunk = (n + ccols - 1) / ccols;
         const size_t e = sizeof(double) * ES;
         PSD_CHECK(bV.alloc((size_t)p * vstride * e));
-        PSD_CHECK(bpart.alloc((size_t)nchunk * n * e));
+        if (!csr) PSD_CHECK(bpart.alloc((size_t)nchunk * n * e));  // (a CSR product has no partial sums)
         PSD_CHECK(bv.alloc((size_t)n * e));
         PSD_CHECK(bpA.alloc((size_t)nblk * ldp * e));
         PSD_CHECK(bpB.alloc((size_t)nblk * ldp * e));
@@ -99,15 +111,22 @@ struct KrylovRun {
     }
     // factor l (0-based) of Krylov step j (1-based), krylov.jl:262-333 / :335-371
     void factor(int l, int j) {
-        const double* Al = dA + (size_t)l * n * n * ES;
         const double* u = V(l) + (size_t)(j - 1) * n * ES;
+        const int lo = (l + 1) % p;
+        const int ncols = (l < p - 1) ? j - 1 : j;
+        double* Hcol = bH.d() + ((size_t)l * hstride + (size_t)(j - 1) * ldh) * ES;
+        if (csr) {
+            const int rows = PSD_KR_NT >> csr->lg[l];
+            PSD_LAUNCH(psd_kr_csr_mv<Z>, psd_dim3((n + rows - 1) / rows), PSD_KR_NT, PSD_KR_NT * sizeof(double) * ES,
+                       c->stream, csr->rowptr[l], csr->colind[l], csr->val[l], u, bv.d(), n, csr->lg[l], dst());
+            stage(args(V(lo), ncols, Hcol, l), 0);
+            return;
+        }
+        const double* Al = dA + (size_t)l * n * n * ES;
         const int rp = (!Z && n % 2 == 0) ? 2 : 1;
         const int tiles = (n + PSD_KR_NT * rp - 1) / (PSD_KR_NT * rp);
         if (rp == 2) PSD_LAUNCH((psd_kr_mv<Z, 2>), psd_dim3(tiles, nchunk), PSD_KR_NT, 0, c->stream, Al, u, bpart.d(), n, ccols, dst());
         else PSD_LAUNCH((psd_kr_mv<Z, 1>), psd_dim3(tiles, nchunk), PSD_KR_NT, 0, c->stream, Al, u, bpart.d(), n, ccols, dst());
-        const int lo = (l + 1) % p;
-        const int ncols = (l < p - 1) ? j - 1 : j;
-        double* Hcol = bH.d() + ((size_t)l * hstride + (size_t)(j - 1) * ldh) * ES;
         stage(args(V(lo), ncols, Hcol, l), nchunk);
     }
     int read_state(int* s) {
@@ -381,12 +400,13 @@ inline bool kr_before(char which, std::complex<double> a, std::complex<double> b
     }
 }
 
-// _partial_pschur!, krylov.jl:500-798.  dA device [p][n][n]; results: T host (p x maxdim^2), Z device or host.
+// _partial_pschur!, krylov.jl:500-798.  dA device [p][n][n], or csr (then dA is not read); results: T host
+// (p x maxdim^2), Z device or host.
 template <bool Z>
 int partial_pschur_run(psd_ctx* c, int n, int p, const double* dA, int nev, char which, int kmin, int kmax,
                        const double* u1, uint64_t seed, double tol, double tol1, int restarts, int purgebuffer,
                        int* nconv_out, double* const* Tout, double* const* Zhost, double* dZout, double* wr, double* wi,
-                       psd_krylov_stats* st, int* info) {
+                       psd_krylov_stats* st, int* info, const KrylovCsr* csr = nullptr) {
     typedef typename KrylovRun<Z>::T T;
     typedef std::complex<double> C;
     constexpr int ES = Z ? 2 : 1;
@@ -404,6 +424,7 @@ int partial_pschur_run(psd_ctx* c, int n, int p, const double* dA, int nev, char
     K.seed = seed;
     K.st = st;
     K.dA = dA;
+    K.csr = csr;
     if (int rc = K.alloc()) return *info = rc;
     // start vector, krylov.jl:534-544: u1 or a draw of the generator, normalised into V_1[:, 1]
     if (u1) {
@@ -779,6 +800,181 @@ int partial_pschur_devapi(psd_ctx* c, int n, int p, const double* dA, int nev, c
     return *info = rc;
 }
 
+// ---- sparse (CSR) factors --------------------------------------------------------------------------------------------
+// The checks of psd_kr_csr_check on a host copy (host entries, before anything is copied): 0, -19 or -20.
+inline int csr_check_host(int n, const int64_t* rp, const int32_t* ci) {
+    if (rp[0] != 0) return -19;
+    for (int i = 0; i < n; ++i)
+        if (rp[i + 1] < rp[i]) return -19;
+    if (rp[n] > PSD_KR_CSR_MAXNNZ) return -19;
+    for (int64_t k = 0; k < rp[n]; ++k)
+        if (ci[k] < 0 || ci[k] >= n) return -20;
+    return 0;
+}
+
+inline int csr_log2(int G) {
+    int lg = 0;
+    while ((1 << lg) < G) ++lg;
+    return lg;
+}
+
+// Structure check of p device-resident factors, before any of them is gathered through: the counts come from rowptr[n]
+// (bounded here), the rest from psd_kr_csr_check, whose flag words are read once.  code: 0, -19 or -20; lg: log2 of the
+// automatic group width of every factor.
+inline int csr_validate_dev(psd_ctx* c, int n, int p, const int64_t* const* rowptr, const int32_t* const* colind, int* lg,
+                            int* code) {
+    *code = 0;
+    std::vector<int64_t> nnz(p);
+    for (int l = 0; l < p; ++l) PSD_CHECK(psd_rt_d2h(&nnz[l], rowptr[l] + n, sizeof(int64_t), c->stream));
+    PSD_CHECK(psd_rt_sync(c->stream));
+    for (int l = 0; l < p; ++l)
+        if (nnz[l] < 0 || nnz[l] > PSD_KR_CSR_MAXNNZ) {
+            *code = -19;
+            return 0;
+        }
+    psd_devbuf bf;
+    PSD_CHECK(bf.alloc(sizeof(int) * PSD_KR_CSR_FLAGS));
+    PSD_CHECK(psd_rt_memset(bf.p, 0, sizeof(int) * PSD_KR_CSR_FLAGS, c->stream));
+    for (int l = 0; l < p; ++l) {
+        const int64_t total = std::max<int64_t>(nnz[l], (int64_t)n + 1);
+        const int nb = (int)std::min<int64_t>((total + PSD_KR_NT - 1) / PSD_KR_NT, 4096);
+        PSD_LAUNCH(psd_kr_csr_check, psd_dim3(nb), PSD_KR_NT, 0, c->stream, rowptr[l], colind[l], n, nnz[l], (int*)bf.p);
+        lg[l] = csr_log2(psd_kr_csr_group(n, nnz[l]));
+    }
+    int f[PSD_KR_CSR_FLAGS];
+    PSD_CHECK(psd_rt_d2h(f, bf.p, sizeof(f), c->stream));
+    PSD_CHECK(psd_rt_sync(c->stream));
+    PSD_CHECK(psd_rt_last_error());
+    if (f[PSD_KR_CSR_BAD_ROWPTR]) *code = -19;
+    else if (f[PSD_KR_CSR_BAD_COLIND]) *code = -20;
+    return 0;
+}
+
+// the array arguments of a CSR entry: NULL arrays and NULL elements are argument 4
+inline bool csr_null(int p, const int64_t* const* rowptr, const int32_t* const* colind, const double* const* val) {
+    if (!rowptr || !colind || !val) return true;
+    for (int l = 0; l < p; ++l)
+        if (!rowptr[l] || !colind[l] || !val[l]) return true;
+    return false;
+}
+
+// p factors already on the device: structure check, then the driver.  Zhost or dZ as in partial_pschur_run.
+template <bool Z>
+int partial_pschur_csr_dev(psd_ctx* c, int n, int p, const int64_t* const* rowptr, const int32_t* const* colind,
+                           const double* const* val, int nev, char which, int mindim, int maxdim, const double* u1,
+                           uint64_t seed, double tol, double tol1, int restarts, int purgebuffer, int* nconv,
+                           double* const* T, double* const* Zhost, double* dZ, double* wr, double* wi,
+                           psd_krylov_stats* st, int* info) {
+    std::vector<int> lg(p);
+    int code = 0;
+    if (int rc = csr_validate_dev(c, n, p, rowptr, colind, lg.data(), &code)) return *info = rc;
+    if (code) return *info = code;
+    const KrylovCsr op = {rowptr, colind, val, lg.data()};
+    return partial_pschur_run<Z>(c, n, p, nullptr, nev, which, mindim, maxdim, u1, seed, tol, tol1, restarts, purgebuffer,
+                                 nconv, T, Zhost, dZ, wr, wi, st, info, &op);
+}
+
+template <bool Z>
+int partial_pschur_csr_host(psd_ctx* c, int n, int p, const int64_t* const* rowptr, const int32_t* const* colind,
+                            const double* const* val, int nev, char which, int mindim, int maxdim, const double* u1,
+                            uint64_t seed, double tol, double tol1, int restarts, int purgebuffer, int* nconv,
+                            double* const* T, double* const* Zo, double* wr, double* wi, psd_krylov_stats* st,
+                            int* info) {
+    int dummy;
+    if (!info) info = &dummy;
+    if (st) memset(st, 0, sizeof(*st));
+    const void* A = (rowptr && colind && val) ? (const void*)rowptr : nullptr;
+    if ((*info = partial_pschur_args<Z>(c, n, p, A, nev, which, mindim, maxdim, u1, tol, tol1, restarts, purgebuffer,
+                                        nconv, T, Zo, wr, wi)) != 0)
+        return *info;
+    if (csr_null(p, rowptr, colind, val)) return *info = -4;
+    for (int l = 0; l < p; ++l)
+        if (!T[l] || !Zo[l]) return *info = !T[l] ? -16 : -17;
+    for (int l = 0; l < p; ++l)
+        if (int rc = csr_check_host(n, rowptr[l], colind[l])) return *info = rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    constexpr int ES = Z ? 2 : 1;
+    std::vector<psd_devbuf> buf(3 * (size_t)p);
+    std::vector<const int64_t*> drp(p);
+    std::vector<const int32_t*> dci(p);
+    std::vector<const double*> dvl(p);
+    for (int l = 0; l < p; ++l) {
+        const size_t nnz = (size_t)rowptr[l][n];
+        psd_devbuf &b0 = buf[3 * l], &b1 = buf[3 * l + 1], &b2 = buf[3 * l + 2];
+        PSD_CHECK(b0.alloc(sizeof(int64_t) * ((size_t)n + 1)));
+        PSD_CHECK(b1.alloc(sizeof(int32_t) * nnz));
+        PSD_CHECK(b2.alloc(sizeof(double) * ES * nnz));
+        PSD_CHECK(psd_rt_h2d(b0.p, rowptr[l], sizeof(int64_t) * ((size_t)n + 1), c->stream));
+        PSD_CHECK(psd_rt_h2d(b1.p, colind[l], sizeof(int32_t) * nnz, c->stream));
+        PSD_CHECK(psd_rt_h2d(b2.p, val[l], sizeof(double) * ES * nnz, c->stream));
+        drp[l] = (const int64_t*)b0.p;
+        dci[l] = (const int32_t*)b1.p;
+        dvl[l] = b2.d();
+    }
+    PSD_CHECK(psd_rt_sync(c->stream));
+    int rc = partial_pschur_csr_dev<Z>(c, n, p, drp.data(), dci.data(), dvl.data(), nev, which, mindim, maxdim, u1, seed,
+                                       tol, tol1, restarts, purgebuffer, nconv, T, Zo, nullptr, wr, wi, st, info);
+    if (st) st->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return *info = rc;
+}
+
+template <bool Z>
+int partial_pschur_csr_devapi(psd_ctx* c, int n, int p, const int64_t* const* rowptr, const int32_t* const* colind,
+                              const double* const* val, int nev, char which, int mindim, int maxdim, const double* u1,
+                              uint64_t seed, double tol, double tol1, int restarts, int purgebuffer, int* nconv,
+                              double* const* T, double* dZ, double* wr, double* wi, psd_krylov_stats* st, int* info) {
+    int dummy;
+    if (!info) info = &dummy;
+    if (st) memset(st, 0, sizeof(*st));
+    const void* A = (rowptr && colind && val) ? (const void*)rowptr : nullptr;
+    if ((*info = partial_pschur_args<Z>(c, n, p, A, nev, which, mindim, maxdim, u1, tol, tol1, restarts, purgebuffer,
+                                        nconv, T, dZ, wr, wi)) != 0)
+        return *info;
+    if (csr_null(p, rowptr, colind, val)) return *info = -4;
+    for (int l = 0; l < p; ++l)
+        if (!T[l]) return *info = -16;
+    const auto t0 = std::chrono::steady_clock::now();
+    int rc = partial_pschur_csr_dev<Z>(c, n, p, rowptr, colind, val, nev, which, mindim, maxdim, u1, seed, tol, tol1,
+                                       restarts, purgebuffer, nconv, T, nullptr, dZ, wr, wi, st, info);
+    if (st) st->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return *info = rc;
+}
+
+// y = A x through the driver's kernel, once, on host buffers (group 0: the automatic width)
+template <bool Z>
+int csr_matvec_host(psd_ctx* c, int n, const int64_t* rowptr, const int32_t* colind, const double* val, const double* x,
+                    double* y, int group, int* info) {
+    int dummy;
+    if (!info) info = &dummy;
+    if (!c) return *info = -1;
+    if (n < 1) return *info = -2;
+    if (!rowptr || !colind || !val) return *info = -4;
+    if (group < 0 || group > 64 || (group & (group - 1)) != 0) return *info = -8;
+    if (!x) return *info = -9;
+    if (!y) return *info = -17;
+    if (int rc = csr_check_host(n, rowptr, colind)) return *info = rc;
+    constexpr int ES = Z ? 2 : 1;
+    const size_t nnz = (size_t)rowptr[n], e = sizeof(double) * ES;
+    const int lg = csr_log2(group ? group : psd_kr_csr_group(n, (int64_t)nnz));
+    psd_devbuf b0, b1, b2, bx, by;
+    PSD_CHECK(b0.alloc(sizeof(int64_t) * ((size_t)n + 1)));
+    PSD_CHECK(b1.alloc(sizeof(int32_t) * nnz));
+    PSD_CHECK(b2.alloc(e * nnz));
+    PSD_CHECK(bx.alloc(e * n));
+    PSD_CHECK(by.alloc(e * n));
+    PSD_CHECK(psd_rt_h2d(b0.p, rowptr, sizeof(int64_t) * ((size_t)n + 1), c->stream));
+    PSD_CHECK(psd_rt_h2d(b1.p, colind, sizeof(int32_t) * nnz, c->stream));
+    PSD_CHECK(psd_rt_h2d(b2.p, val, e * nnz, c->stream));
+    PSD_CHECK(psd_rt_h2d(bx.p, x, e * n, c->stream));
+    const int rows = PSD_KR_NT >> lg;
+    PSD_LAUNCH(psd_kr_csr_mv<Z>, psd_dim3((n + rows - 1) / rows), PSD_KR_NT, PSD_KR_NT * e, c->stream,
+               (const int64_t*)b0.p, (const int32_t*)b1.p, b2.d(), bx.d(), by.d(), n, lg, (const int*)nullptr);
+    PSD_CHECK(psd_rt_d2h(y, by.p, e * n, c->stream));
+    PSD_CHECK(psd_rt_sync(c->stream));
+    PSD_CHECK(psd_rt_last_error());
+    return *info = 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -809,5 +1005,33 @@ int psd_z_partial_pschur_dev(psd_ctx* c, int n, int p, const double* dA, int nev
                              int* info) {
     return partial_pschur_devapi<true>(c, n, p, dA, nev, which, mindim, maxdim, u1, seed, tol, tol1, restarts,
                                        purgebuffer, nconv, T, dZ, wr, wi, st, info);
+}
+#define PSD_KR_CSR_ARGS                                                                                                  \
+    psd_ctx *c, int n, int p, const int64_t *const *rowptr, const int32_t *const *colind, const double *const *val,     \
+        int nev, char which, int mindim, int maxdim, const double *u1, uint64_t seed, double tol, double tol1,         \
+        int restarts, int purgebuffer, int *nconv, double *const *T
+#define PSD_KR_CSR_PASS \
+    c, n, p, rowptr, colind, val, nev, which, mindim, maxdim, u1, seed, tol, tol1, restarts, purgebuffer, nconv, T
+int psd_d_partial_pschur_csr(PSD_KR_CSR_ARGS, double* const* Z, double* wr, double* wi, psd_krylov_stats* st, int* info) {
+    return partial_pschur_csr_host<false>(PSD_KR_CSR_PASS, Z, wr, wi, st, info);
+}
+int psd_z_partial_pschur_csr(PSD_KR_CSR_ARGS, double* const* Z, double* wr, double* wi, psd_krylov_stats* st, int* info) {
+    return partial_pschur_csr_host<true>(PSD_KR_CSR_PASS, Z, wr, wi, st, info);
+}
+int psd_d_partial_pschur_csr_dev(PSD_KR_CSR_ARGS, double* dZ, double* wr, double* wi, psd_krylov_stats* st, int* info) {
+    return partial_pschur_csr_devapi<false>(PSD_KR_CSR_PASS, dZ, wr, wi, st, info);
+}
+int psd_z_partial_pschur_csr_dev(PSD_KR_CSR_ARGS, double* dZ, double* wr, double* wi, psd_krylov_stats* st, int* info) {
+    return partial_pschur_csr_devapi<true>(PSD_KR_CSR_PASS, dZ, wr, wi, st, info);
+}
+#undef PSD_KR_CSR_ARGS
+#undef PSD_KR_CSR_PASS
+int psd_d_csr_matvec(psd_ctx* c, int n, const int64_t* rowptr, const int32_t* colind, const double* val, const double* x,
+                     double* y, int group, int* info) {
+    return csr_matvec_host<false>(c, n, rowptr, colind, val, x, y, group, info);
+}
+int psd_z_csr_matvec(psd_ctx* c, int n, const int64_t* rowptr, const int32_t* colind, const double* val, const double* x,
+                     double* y, int group, int* info) {
+    return csr_matvec_host<true>(c, n, rowptr, colind, val, x, y, group, info);
 }
 }  // extern "C"
