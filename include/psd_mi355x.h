@@ -150,6 +150,33 @@ int psd_d_pschur_hess(psd_ctx* ctx, int n, int p, double* const* H, double* cons
 int psd_d_pschur_hess_batch(psd_ctx* ctx, int nb, int n, int p, double* const* H, double* const* Q, int wantT, int wantZ,
                             int maxitfac, double* wr, double* wi, int* infos, psd_stats* stats, int* info);
 
+/* nb GENERAL (unreduced) problems of the same shape (n, p) in ONE call, Float64, all-true signature: parameter sweeps and
+ * multiple-shooting orbits of order 8 ... 64 issue hundreds of them, and one such problem leaves the device launch-bound.
+ * phessenberg!(A) (PeriodicSchurDecompositions.jl:213-259) for each: A: nb * p pointers, problem q's factor j at
+ * [q * p + j], overwritten LAPACK-style like psd_d_phessenberg; tau is [nb][p][n].  One workgroup reduces one problem, the
+ * whole batch in one launch (orders above 128 fall back to the single-problem reduction, problem by problem): H and tau
+ * equal, bit for bit, what psd_d_phessenberg's one-launch-per-link form gives.  Any nb >= 1; a batch larger than the
+ * device memory is worked through in groups. */
+int psd_d_phessenberg_batch(psd_ctx* ctx, int nb, int n, int p, double* const* A, double* tau, psd_stats* stats,
+                            int* info);
+
+/* pschur!(A, lr; wantZ, wantT, maxitfac) (PeriodicSchurDecompositions.jl:120-152) for each of nb problems.  A / Z: nb * p
+ * pointers in user order, problem q's factor s at [q * p + s]; on exit as psd_d_pschur leaves them (Z may be NULL when
+ * !wantZ).  wr / wi: nb * n eigenvalues, problem by problem.  schurindex: 1 for 'R', p for 'L', the same for every
+ * problem.  infos[nb] (may be NULL): per-problem info — a problem that exhausts its sweep budget ends alone, the others
+ * are complete; the return value is the first non-zero one.  Argument errors and PSD_INFO_RUNTIME codes end the call.
+ * The reduction and the Q formation run over the whole batch, the iteration in chunks of 32 problems side by side on the
+ * slot scheduler.  stats: the times are sums over the call, the counters sums over the problems. */
+int psd_d_pschur_batch(psd_ctx* ctx, int nb, int n, int p, double* const* A, char orient, int wantT, int wantZ,
+                       int maxitfac, double* const* Z, double* wr, double* wi, int* infos, int* schurindex,
+                       psd_stats* stats, int* info);
+
+/* Device-resident variant of psd_d_pschur_batch: dA, dZ are device pointers to [nb][p][n][n] column-major blocks in
+ * user order (dZ may be NULL when !wantZ).  wr / wi / infos are host buffers. */
+int psd_d_pschur_batch_dev(psd_ctx* ctx, int nb, int n, int p, double* dA, char orient, int wantT, int wantZ,
+                           int maxitfac, double* dZ, double* wr, double* wi, int* infos, int* schurindex,
+                           psd_stats* stats, int* info);
+
 /* Device-resident variant of psd_d_pschur: dA, dZ are device pointers to [p][n][n] blocks in user
  * order (dZ may be NULL when !wantZ).  wr/wi/sweeplog are host buffers. */
 int psd_d_pschur_dev(psd_ctx* ctx, int n, int p, double* dA, char orient, int wantT, int wantZ, int maxitfac,

@@ -24,7 +24,7 @@ import PeriodicSchurDecompositions: pschur!, pschur, phessenberg!, gpschur, Peri
 const PSD = PeriodicSchurDecompositions
 using ArnoldiMethod: ArnoldiMethod
 
-export set_train!, engine_version
+export set_train!, engine_version, pschur_batch!, pschur_batch
 
 const libpsd = get(ENV, "LIBPSD_MI355X", joinpath(@__DIR__, "..", "periodicschurdecompositions.jl_amd", "libpsd_mi355x.so"))
 
@@ -137,6 +137,48 @@ function pschur!(A::Vector{Matrix{Float64}}, lr::Symbol = :R; wantZ::Bool = true
     wantZ || (Z = [similar(T1, 0, 0)])                   # PSD.jl:1074-1076
     PeriodicSchur(T1, T, Z, complex.(wr, wi), orient, js)
 end
+
+# pschur_batch!(problems, lr; wantZ, wantT, maxitfac, infos) — no reference equivalent: pschur!(A, lr; ...) (PSD.jl:120-152)
+# for many small Float64 problems of equal order and period in ONE call (psd_d_pschur_batch; parameter sweeps, the orbits
+# of a multiple-shooting run).  Works in place like pschur!; returns a Vector{PeriodicSchur}.  A problem that does not
+# converge throws like pschur! after all have run; with `infos` (a Vector{Cint} of length(problems)) the per-problem
+# codes are stored there instead and nothing is thrown for a failed problem.
+function pschur_batch!(problems::Vector{Vector{Matrix{Float64}}}, lr::Symbol = :R; wantZ::Bool = true, wantT::Bool = true,
+                       maxitfac = 30, infos::Union{Nothing, Vector{Cint}} = nothing)
+    orient = PSD.char_lr(lr)                                                                      # PSD.jl:155-177
+    nb = length(problems)
+    nb == 0 && return PeriodicSchur[]
+    p = length(problems[1]); n = _check(problems[1])
+    for A in problems
+        (length(A) == p && _check(A) == n) || throw(DimensionMismatch("the problems of a batch must have equal order and period"))
+    end
+    flat = reduce(vcat, problems)
+    Z = wantZ ? [Matrix{Float64}(undef, n, n) for _ in 1:(nb * p)] : Matrix{Float64}[]
+    wr = Matrix{Float64}(undef, n, nb); wi = similar(wr)
+    codes = infos === nothing ? Vector{Cint}(undef, nb) : infos
+    length(codes) == nb || throw(DimensionMismatch("infos must have one entry per problem"))
+    si = Ref{Cint}(0); info = Ref{Cint}(0)
+    Ap = _ptrs(flat); Zp = _ptrs(Z)
+    GC.@preserve flat Z wr wi codes begin
+        ccall((:psd_d_pschur_batch, libpsd), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Ptr{Float64}}, Cchar, Cint, Cint, Cint,
+               Ptr{Ptr{Float64}}, Ptr{Float64}, Ptr{Float64}, Ptr{Cint}, Ref{Cint}, Ptr{Cvoid}, Ref{Cint}),
+              ctx().ptr, nb, n, p, Ap, orient, wantT, wantZ, maxitfac,
+              wantZ ? Zp : C_NULL, wr, wi, codes, si, C_NULL, info)
+    end
+    (info[] < 0 || info[] >= INFO_NOTIMPL) && _throw(info[])                 # argument / runtime codes end the call
+    js = Int(si[])
+    out = map(1:nb) do q
+        A = problems[q]
+        T1 = A[js]; T = [A[j] for j in 1:p if j != js]
+        Zq = wantZ ? Z[((q - 1) * p + 1):(q * p)] : [similar(T1, 0, 0)]
+        PeriodicSchur(T1, T, Zq, complex.(wr[:, q], wi[:, q]), orient, js)
+    end
+    infos === nothing && foreach(_throw, codes)
+    out
+end
+pschur_batch(problems::AbstractVector, lr::Symbol = :R; kwargs...) =
+    pschur_batch!([Matrix{Float64}[Matrix{Float64}(a) for a in A] for A in problems], lr; kwargs...)
 
 # pschur!(A, lr; ...), ComplexF64 — PSD.jl:1106-1111 (the all-true signature of generalized.jl:108-137)
 function pschur!(A::Vector{Matrix{ComplexF64}}, lr::Symbol = :R; wantZ::Bool = true, wantT::Bool = true, maxitfac = 30)

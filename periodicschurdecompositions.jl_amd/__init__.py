@@ -290,6 +290,11 @@ class Engine:
                                            C.c_char, C.c_int, C.c_double, C.c_int, dp, dp, dp, ip, ip]
         lib.psd_d_pschur_hess_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, dpp, dpp, C.c_int, C.c_int, C.c_int,
                                                 dp, dp, ip, C.POINTER(Stats), ip]
+        lib.psd_d_phessenberg_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, dpp, dp, C.POINTER(Stats), ip]
+        lib.psd_d_pschur_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, dpp, C.c_char, C.c_int, C.c_int, C.c_int,
+                                           dpp, dp, dp, ip, ip, C.POINTER(Stats), ip]
+        lib.psd_d_pschur_batch_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_char, C.c_int,
+                                               C.c_int, C.c_int, C.c_void_p, dp, dp, ip, ip, C.POINTER(Stats), ip]
         lib.psd_set_shard.argtypes = [C.c_void_p, C.c_int, C.c_int]
         lib.psd_shard_owned.argtypes = [C.c_void_p, C.c_int, C.c_char, u8p]
         for nm, dev in (("psd_d_partial_pschur", False), ("psd_z_partial_pschur", False),
@@ -776,6 +781,144 @@ class Engine:
         for q in range(nb):
             self._raise(infos[q])
         return out
+
+    def _batch_shape(self, problems):
+        """(n, p, flat list of factors) of a batch of general problems; DimensionMismatch unless all have one shape."""
+        n = p = None
+        flat = []
+        for A in problems:
+            A = list(A)
+            if len(A) < 1:
+                raise DimensionMismatch("empty sequence")
+            if self._is_complex(A):
+                raise NotImplementedPSD("pschur_batch: Float64 only (ComplexF64 has no batched iteration)")
+            nq = _check_square(A)
+            if n is None:
+                n, p = nq, len(A)
+            if nq != n or len(A) != p:
+                raise DimensionMismatch("the problems of a batch must have equal order and period")
+            flat += A
+        return n, p, flat
+
+    def phessenberg_batch_(self, problems):
+        """phessenberg!(A) (src/PeriodicSchurDecompositions.jl:213-259) for a list of problems of equal shape in ONE call
+        (psd_d_phessenberg_batch).  `problems`: list of lists of p writable Fortran-ordered matrices, overwritten
+        LAPACK-style.  Returns a list of (H list, tau[p][n]) like phessenberg_, and the Stats of the call."""
+        nb = len(problems)
+        if nb == 0:
+            return [], Stats()
+        n, p, flat = self._batch_shape(problems)
+        self._as_work(flat)
+        tau = np.zeros((nb, p, n))
+        st = Stats()
+        info = C.c_int(0)
+        self.lib.psd_d_phessenberg_batch(self.ctx, nb, n, p, self._ptrs(flat), tau.ctypes.data_as(C.POINTER(C.c_double)),
+                                         C.byref(st), C.byref(info))
+        self._raise(info.value)
+        out = []
+        for q in range(nb):
+            A = flat[q * p:(q + 1) * p]
+            out.append(([np.triu(a, -1 if j == 0 else 0) for j, a in enumerate(A)], tau[q]))
+        return out, st
+
+    def pschur_batch_(self, problems, lr="R", wantZ=True, wantT=True, maxitfac=30, infos_out=None):
+        """pschur!(A, lr; wantZ, wantT, maxitfac) (src/PeriodicSchurDecompositions.jl:120-152) for many small problems of
+        equal shape in ONE call (psd_d_pschur_batch): the reduction and the Q formation run over the whole batch, the
+        iteration 32 problems at a time side by side.  Float64, all-true signature.
+
+        `problems`: a list of lists of p writable Fortran-ordered n x n matrices, overwritten with the T factors; returns
+        a list of PeriodicSchur.  Or one torch [nb, p, n, n] device tensor (device-resident entry,
+        psd_d_pschur_batch_dev; the input is not modified): returns (T, Z, values, stats) with T, Z torch tensors
+        [nb, p, n, n] on the same device (Z None when not wantZ), values a complex [nb, n] array; orientation and
+        schurindex (1 for "R", p for "L") are those of the call.
+
+        A problem that fails to converge raises like the single call, after all have run — the others are complete
+        then.  `infos_out`: a list that receives the per-problem info codes instead (nothing is raised for a failed
+        problem then)."""
+        orient = char_lr(lr)
+        if hasattr(problems, "data_ptr"):
+            return self._pschur_batch_dev(problems, orient, wantZ, wantT, maxitfac, infos_out)
+        nb = len(problems)
+        if nb == 0:
+            if infos_out is not None:
+                infos_out[:] = []
+            return []
+        n, p, flat = self._batch_shape(problems)
+        self._as_work(flat)
+        Zall = [np.zeros((n, n), order="F") for _ in range(nb * p)] if wantZ else []
+        wr = np.zeros((nb, n))
+        wi = np.zeros((nb, n))
+        infos = (C.c_int * nb)()
+        si = C.c_int(0)
+        st = Stats()
+        info = C.c_int(0)
+        dp = C.POINTER(C.c_double)
+        self.lib.psd_d_pschur_batch(self.ctx, nb, n, p, self._ptrs(flat), orient.encode(), int(wantT), int(wantZ),
+                                    int(maxitfac), self._ptrs(Zall) if wantZ else None, wr.ctypes.data_as(dp),
+                                    wi.ctypes.data_as(dp), infos, C.byref(si), C.byref(st), C.byref(info))
+        if info.value < 0 or info.value >= INFO_NOTIMPL:
+            self._raise(info.value)
+        out = []
+        for q in range(nb):
+            Z = Zall[q * p:(q + 1) * p] if wantZ else []
+            out.append(PeriodicSchur(flat[q * p:(q + 1) * p], Z, wr[q] + 1j * wi[q], orient, si.value, st))
+        if infos_out is not None:
+            infos_out[:] = [int(infos[q]) for q in range(nb)]
+            return out
+        for q in range(nb):
+            self._raise(infos[q])
+        return out
+
+    def pschur_batch(self, problems, lr="R", **kw):
+        """Copying form of pschur_batch_: the factors are left untouched."""
+        if hasattr(problems, "data_ptr"):
+            return self.pschur_batch_(problems, lr, **kw)
+        for A in problems:
+            if self._is_complex(list(A)):
+                raise NotImplementedPSD("pschur_batch: Float64 only (ComplexF64 has no batched iteration)")
+        work = [[np.array(a, dtype=np.float64, order="F", copy=True) for a in A] for A in problems]
+        return self.pschur_batch_(work, lr, **kw)
+
+    def _pschur_batch_dev(self, dA, orient, wantZ, wantT, maxitfac, infos_out):
+        import torch
+
+        if dA.dim() != 4 or dA.shape[2] != dA.shape[3]:
+            raise DimensionMismatch("a device batch is one [nb, p, n, n] tensor of square factors")
+        if dA.is_complex():
+            raise NotImplementedPSD("pschur_batch: Float64 only (ComplexF64 has no batched iteration)")
+        if not dA.is_cuda:
+            raise TypeError("device-resident pschur_batch needs a GPU tensor (use lists of numpy arrays for host input)")
+        nb, p, n = dA.shape[0], dA.shape[1], dA.shape[2]
+        if nb == 0:
+            if infos_out is not None:
+                infos_out[:] = []
+            return dA.clone(), (dA.clone() if wantZ else None), np.zeros((0, n), dtype=complex), Stats()
+        # [nb][p][n][n] blocks of column-major matrices: the transpose of each factor, contiguous (as partial_pschur);
+        # always a copy, the caller's tensor stays as it is
+        dT = dA.to(torch.float64).transpose(2, 3).contiguous()
+        if dT.data_ptr() == dA.data_ptr():
+            dT = dT.clone()
+        dZ = torch.zeros_like(dT) if wantZ else None
+        wr = np.zeros((nb, n))
+        wi = np.zeros((nb, n))
+        infos = (C.c_int * nb)()
+        si = C.c_int(0)
+        st = Stats()
+        info = C.c_int(0)
+        dp = C.POINTER(C.c_double)
+        torch.cuda.synchronize(dA.device)
+        self.lib.psd_d_pschur_batch_dev(self.ctx, nb, n, p, C.c_void_p(dT.data_ptr()), orient.encode(), int(wantT),
+                                        int(wantZ), int(maxitfac), C.c_void_p(dZ.data_ptr()) if wantZ else None,
+                                        wr.ctypes.data_as(dp), wi.ctypes.data_as(dp), infos, C.byref(si), C.byref(st),
+                                        C.byref(info))
+        if info.value < 0 or info.value >= INFO_NOTIMPL:
+            self._raise(info.value)
+        if infos_out is not None:
+            infos_out[:] = [int(infos[q]) for q in range(nb)]
+        else:
+            for q in range(nb):
+                self._raise(infos[q])
+        return dT.transpose(2, 3), (dZ.transpose(2, 3) if wantZ else None), wr + 1j * wi, st
 
     def ordschur_(self, P, select, wantZ=True, Z=None):
         """LinearAlgebra.ordschur!(P, select; wantZ, Z) — src/ordschur.jl:11-73 (ComplexF64).  Mutates and returns P.

@@ -3,6 +3,7 @@
 // serial simulation for the CPU-only test tier; the package never loads that build.
 #include <atomic>
 #include "psd_hess.h"
+#include "psd_bhess.h"
 #include "psd_hess2.h"
 #include "psd_formq2.h"
 #include "psd_real_qr.h"
@@ -262,6 +263,8 @@ struct psd_ctx {
 #endif
     // period sharding (psd_set_shard): this context holds the Schur vectors Z_j of a contiguous slice of the period
     int shard_rank = 0, shard_world = 1;
+    int batch_group = 0;  // PSD_BATCH_GROUP: most problems a host batch entry takes to the device at once (0: what fits)
+    int bh_nmax = PSD_BH_NMAX;  // largest order of the one-workgroup-per-problem reduction (diagnostic build: PSD_BH_NMAX in the environment, for the sweep that sets the constant)
     void slice(int p, int& lo, int& hi) const {  // [lo, hi), 0-based internal factor index
         const int base = p / shard_world, rem = p % shard_world;
         lo = shard_rank * base + (shard_rank < rem ? shard_rank : rem);
@@ -1723,6 +1726,8 @@ int psd_create(psd_ctx** ctx, int device) {
     if (const char* e = psd_env("PSD_CDEFER_EDGE")) c->cedge = atoi(e);
     if (const char* e = psd_env("PSD_ORD_PIPE")) c->ord_pipe = atoi(e);
     if (const char* e = psd_env("PSD_FORMQ_BLOCKED")) c->formq_blocked = atoi(e);
+    if (const char* e = psd_env("PSD_BATCH_GROUP")) c->batch_group = atoi(e) > 0 ? atoi(e) : 0;
+    if (const char* e = psd_env_diag("PSD_BH_NMAX")) c->bh_nmax = (atoi(e) >= 1 && atoi(e) <= 2048) ? atoi(e) : PSD_BH_NMAX;
     if (const char* e = psd_env("PSD_BAND_HELPER")) c->band_helper = atoi(e);
     if (const char* e = psd_env_diag("PSD_TRAIN_LONG")) c->train_long = atoi(e);
     if (const char* e = psd_env_diag("PSD_TRAIN_STOP")) c->train_stop = atoi(e);
@@ -4070,3 +4075,4 @@ extern "C" int psd_dbg_apply_bench(psd_ctx* c, int n, int p, int nwin, int W, in
 #include "psd_krylov_host.inl"
 #include "psd_evec_host.inl"
 #include "psd_gevec_host.inl"
+#include "psd_batch_host.inl"

@@ -259,11 +259,11 @@ PSD_KERNEL psd_set_identity(double* Q, int n) {
 // One step (reflector index i) of the backward accumulation Q_j = H_{j,1} ... H_{j,n-1}, all
 // factors at once (what Matrix(H.Q) / Matrix(QR.Q) produce, PSD.jl:136-143).  grid = (tiles, p).
 // (j0: first factor of the slice this launch forms, 0-based: a period-sharded context forms the Q_j it owns)
-PSD_KERNEL psd_formq_step(const double* Hp, const double* tau, double* Q, int n, int i, int j0) {
+// (body: j = factor, 1-based; tile = the 4-column group of Q_j — the batched Q formation of psd_bhess.h loops over them)
+PSD_D void psd_formq_step_body(const double* Hp, const double* tau, double* Q, int n, int i, int j, int tile) {
     PSD_LDS_DECL;
     double* red = (double*)psd_lds;
     const int NT = PSD_NTHREADS;
-    const int j = j0 + PSD_BLOCK_Y + 1;
     const int r0 = i + ((j == 1) ? 1 : 0);
     const int m = n - r0 + 1;
     if (m < 2) return;
@@ -271,7 +271,7 @@ PSD_KERNEL psd_formq_step(const double* Hp, const double* tau, double* Q, int n,
     if (tj == 0.0) return;
     const psd_mat<double> V = psd_mat<double>{const_cast<double*>(Hp) + (size_t)(j - 1) * n * n, n};
     const psd_mat<double> M = psd_mat<double>{Q + (size_t)(j - 1) * n * n, n};
-    const int cbase = r0 + 4 * PSD_BLOCK_X;
+    const int cbase = r0 + 4 * tile;
     if (cbase > n) return;
     PSD_PAR_FOR(t, NT) {
         const int wv = t >> 6, lane = t & 63;
@@ -296,6 +296,9 @@ PSD_KERNEL psd_formq_step(const double* Hp, const double* tau, double* Q, int n,
             for (int q = lane; q < m; q += 64) M(r0 + q, c) -= w * ((q == 0) ? 1.0 : V(r0 + q, i));
         }
     }
+}
+PSD_KERNEL psd_formq_step(const double* Hp, const double* tau, double* Q, int n, int i, int j0) {
+    psd_formq_step_body(Hp, tau, Q, n, i, j0 + PSD_BLOCK_Y + 1, PSD_BLOCK_X);
 }
 
 // PSD.jl:147,149: keep R_j (j >= 2) / triu(H_1, -1): zero the reflector storage.  grid = (n, p)

@@ -1,0 +1,122 @@
+#!/usr/bin/env python3
+"""Timing of the batched entries on the MI355X (profiles/batch/README.md).
+
+  call   (default)  Engine.pschur_batch_ against a loop of Engine.pschur_ over the same problems on the same engine:
+                    wall time around the call(s) and the device times of the stats (hess / formq / iterate / copy), the
+                    second of two runs of each.
+  --loop-only       the loop alone: what a commit without the batched entries can run (the baseline of record).
+  --sweep           the batched reduction (phessenberg_batch_) against nb single reductions (phessenberg_) over the order,
+                    nb = 64, p = 8: the measurement PSD_BH_NMAX is set from.  Runs on the diagnostic library with the cap
+                    lifted (PSD_BH_NMAX in the environment), so that every order takes the batched kernel.
+
+One JSON line per shape on stdout; --json FILE collects them."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def parse_shapes(text):
+    return [tuple(int(x) for x in s.split("x")) for s in text.split(",") if s]
+
+
+def factors(nb, n, p):
+    import psdtest as pt
+
+    return [pt.bench_factors(n, p, seed=9000 + q) for q in range(nb)]
+
+
+def copies(probs):
+    return [[a.copy(order="F") for a in A] for A in probs]
+
+
+def time_loop(eng, probs, lr):
+    best = None
+    for _ in range(2):
+        Ws = copies(probs)
+        dev = dict(hess=0.0, formq=0.0, iter=0.0, copy=0.0, total=0.0)
+        t0 = time.perf_counter()
+        for W in Ws:
+            st = eng.pschur_(W, lr).stats
+            dev["hess"] += st.ms_hess
+            dev["formq"] += st.ms_formq
+            dev["iter"] += st.ms_iter
+            dev["copy"] += st.ms_copy
+            dev["total"] += st.ms_total
+        best = dict(wall_ms=1e3 * (time.perf_counter() - t0), **{"ms_" + k: v for k, v in dev.items()})
+    return best
+
+
+def time_batch(eng, probs, lr):
+    best = None
+    for _ in range(2):
+        Ws = copies(probs)
+        t0 = time.perf_counter()
+        out = eng.pschur_batch_(Ws, lr)
+        wall = 1e3 * (time.perf_counter() - t0)
+        st = out[0].stats
+        best = dict(wall_ms=wall, ms_hess=st.ms_hess, ms_formq=st.ms_formq, ms_iter=st.ms_iter, ms_copy=st.ms_copy,
+                    ms_total=st.ms_total, nsweeps=int(st.nsweeps), ticks=int(st.nlaunch_step))
+    return best
+
+
+def time_sweep(eng, nb, n, p):
+    probs = factors(nb, n, p)
+    for _ in range(2):
+        Ws = copies(probs)
+        single = 0.0
+        for W in Ws:
+            single += eng.phessenberg_(W)[2].ms_hess
+        Ws = copies(probs)
+        batch = eng.phessenberg_batch_(Ws)[1].ms_hess
+    return dict(nb=nb, n=n, p=p, ms_hess_single_sum=single, ms_hess_batch=batch, ratio=single / batch if batch else None)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--shapes", default="256x32x16,256x16x64,64x64x16,1024x8x32", help="nb x n x p, comma separated")
+    ap.add_argument("--lr", default="R")
+    ap.add_argument("--loop-only", action="store_true")
+    ap.add_argument("--sweep", action="store_true")
+    ap.add_argument("--sweep-orders", default="32,64,96,128,192,256")
+    ap.add_argument("--lib", default=None, help="library to load instead of the package's (a build of another commit)")
+    ap.add_argument("--json", default=None)
+    args = ap.parse_args()
+
+    import torch
+
+    torch.cuda.init()
+    import psd_amd
+
+    if args.sweep:
+        os.environ["PSD_BH_NMAX"] = "2048"
+        eng = psd_amd.Engine(0, libpath=psd_amd.DIAG_LIB_PATH)
+    else:
+        eng = psd_amd.Engine(0, libpath=args.lib)
+    rows = []
+    if args.sweep:
+        for n in [int(x) for x in args.sweep_orders.split(",") if x]:
+            rows.append(time_sweep(eng, 64, n, 8))
+            print(json.dumps(rows[-1]), flush=True)
+    else:
+        for (nb, n, p) in parse_shapes(args.shapes):
+            probs = factors(nb, n, p)
+            row = dict(nb=nb, n=n, p=p, lr=args.lr, loop=time_loop(eng, probs, args.lr))
+            if not args.loop_only:
+                row["batch"] = time_batch(eng, probs, args.lr)
+                row["wall_ratio"] = row["loop"]["wall_ms"] / row["batch"]["wall_ms"]
+                row["device_ratio"] = row["loop"]["ms_total"] / row["batch"]["ms_total"]
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    if args.json:
+        with open(args.json, "w") as fh:
+            json.dump(dict(engine=eng.version(), rows=rows), fh, indent=1)
+
+
+if __name__ == "__main__":
+    main()
