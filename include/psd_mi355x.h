@@ -491,6 +491,51 @@ int psd_z_geigvecs_dev(psd_ctx* ctx, int n, int p, const double* dT, const doubl
                        int schurindex, uint8_t* select, int nsel, int shifted, double* dV, int maxvec, double* a,
                        psd_evec_stats* stats, int* info);
 
+/* ---- eigvecs_batch: eigenvectors of many small periodic Schur forms in one call -------------------------------------
+ * psd_?_eigvecs (back-substitution) for nb decompositions of one shape (n, p), as psd_d_pschur_batch leaves them:
+ * Float64, all-true signature, one orient and schurindex for the whole batch.  Per problem the result contract is that
+ * of psd_d_eigvecs: select completed to whole conjugate pairs, columns top to bottom, ||V_1(:, j)|| = 1 with the
+ * largest-modulus entry real and positive, the partner of a pair the exact conjugate, a zero eigenvalue a NaN column
+ * (counted), small pivots replaced by smin (counted), columns past 2^500 rescaled by a power of two (counted).  A
+ * problem's vectors do not depend on its place in the batch or on the grouping (bit for bit).  Up to order 128 the
+ * whole back-substitution of a group is one launch (several columns per wavefront for p <= 32) and the call makes the
+ * same number of launches whatever nb and n are (stats->nlaunch); above, psd_d_eigvecs_dev runs problem by problem on
+ * the slices of the batch buffers.  A batch whose workspace exceeds the free device memory is worked through in groups
+ * (PSD_BATCH_GROUP in the environment lowers the group size).
+ *
+ * T, Z: nb * p pointers to n x n matrices (problem-major, user order).  wr, wi: host [nb][n].  select: host [nb][n],
+ * completed in place.  A problem whose row of select is all false costs nothing and gets nvec = 0: that is how a caller
+ * skips the problems whose psd_d_pschur_batch info was non-zero.  V: nb * nmat pointers (nmat = shifted ? p : 1) to
+ * n x maxvec complex interleaved column-major blocks; the columns at and beyond nvec[q] are written as zeros.  V = NULL:
+ * a size query (select completed, nvec filled, nothing computed).  nvec: host [nb], out.  pcnt: host [nb][3] or NULL:
+ * perturbed pivots, rescaled columns, zero eigenvalues per problem.
+ * info: 0; -1 ctx NULL; -2 n < 1; -3 p < 1; -4 T NULL; -5 Z NULL; -6 wr or wi NULL; -7 orient; -8 schurindex not in
+ * 1..p; -9 select NULL; -10 maxvec below the largest nvec; -11 nb < 0; -12 nvec NULL; PSD_INFO_NOTIMPL on a
+ * period-sharded context; PSD_INFO_RUNTIME + k.  nb == 0 returns 0 and touches nothing. */
+typedef struct psd_bevec_stats {
+    int32_t nb;             /* problems of the call                                                            */
+    int32_t nvec_total;     /* columns returned over all problems                                              */
+    int32_t nperturbed;     /* as psd_evec_stats, summed over the batch                                        */
+    int32_t nrescaled;
+    int32_t nzero;
+    int32_t nlaunch;        /* kernel launches of the call                                                     */
+    int32_t ngroups;        /* groups the batch was worked through in                                          */
+    int32_t reserved;
+    double ms_solve;        /* device events, summed over the groups                                           */
+    double ms_backtransform;
+    double ms_kernels;
+} psd_bevec_stats;
+
+int psd_d_eigvecs_batch(psd_ctx* ctx, int nb, int n, int p, double* const* T, double* const* Z, const double* wr,
+                        const double* wi, char orient, int schurindex, uint8_t* select, int shifted, double* const* V,
+                        int maxvec, int* nvec, int32_t* pcnt, psd_bevec_stats* stats, int* info);
+/* Device-resident variant: dT, dZ device [nb][p][n][n] column-major blocks in user order (what psd_d_pschur_batch_dev
+ * leaves), dV a device block [nb][nmat][maxvec][n] of interleaved complex values (each block column-major n x maxvec).
+ * wr, wi, select, nvec and pcnt are host arrays.  One kernel and one read-back define the 2x2 row blocks. */
+int psd_d_eigvecs_batch_dev(psd_ctx* ctx, int nb, int n, int p, const double* dT, const double* dZ, const double* wr,
+                            const double* wi, char orient, int schurindex, uint8_t* select, int shifted, double* dV,
+                            int maxvec, int* nvec, int32_t* pcnt, psd_bevec_stats* stats, int* info);
+
 #ifdef __cplusplus
 }
 #endif

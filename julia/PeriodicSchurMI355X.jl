@@ -24,7 +24,7 @@ import PeriodicSchurDecompositions: pschur!, pschur, phessenberg!, gpschur, Peri
 const PSD = PeriodicSchurDecompositions
 using ArnoldiMethod: ArnoldiMethod
 
-export set_train!, engine_version, pschur_batch!, pschur_batch
+export set_train!, engine_version, pschur_batch!, pschur_batch, eigvecs_batch_device
 
 const libpsd = get(ENV, "LIBPSD_MI355X", joinpath(@__DIR__, "..", "periodicschurdecompositions.jl_amd", "libpsd_mi355x.so"))
 
@@ -179,6 +179,51 @@ function pschur_batch!(problems::Vector{Vector{Matrix{Float64}}}, lr::Symbol = :
 end
 pschur_batch(problems::AbstractVector, lr::Symbol = :R; kwargs...) =
     pschur_batch!([Matrix{Float64}[Matrix{Float64}(a) for a in A] for A in problems], lr; kwargs...)
+
+# eigvecs_batch_device(problems, select; shifted) — no reference equivalent: eigvecs(ps, select; shifted) (vectors.jl:25-138)
+# by periodic back-substitution for many small Float64 decompositions of equal order, period, orientation and schurindex in
+# ONE call (psd_d_eigvecs_batch), the follow-up of pschur_batch!.  `select`: a Vector{Bool} used for every problem or one per
+# problem; completed to conjugate pairs.  A problem whose flags are all false costs nothing and gets n x 0 matrices (skip
+# the problems whose pschur_batch! code was non-zero that way).  Returns, per problem, the p (shifted) or 1 matrices of
+# eigvecs_device.
+function eigvecs_batch_device(problems::Vector{<:PeriodicSchur{Float64}}, select::AbstractVector; shifted::Bool = true)
+    nb = length(problems)
+    nb == 0 && return Vector{Matrix{ComplexF64}}[]
+    ps1 = problems[1]
+    p = ps1.period; n = size(ps1.T1, 1); js = ps1.schurindex; orient = ps1.orientation
+    (isempty(ps1.Z) || size(ps1.Z[1], 1) == 0) && throw(ArgumentError("eigvecs requires Schur vectors in the PSD"))
+    sel = zeros(UInt8, n, nb)
+    for (q, ps) in enumerate(problems)
+        (ps.period == p && size(ps.T1, 1) == n && ps.schurindex == js && ps.orientation == orient) ||
+            throw(DimensionMismatch("the problems of a batch must have equal order, period, orientation and schurindex"))
+        sq = select[1] isa Bool ? select : select[q]
+        length(sq) == n || throw(ArgumentError("length of `select` must correspond to rank of Schur (sub-)space"))
+        sel[:, q] .= UInt8.(sq)
+    end
+    # user order: T1 at schurindex, the others around it
+    T = reduce(vcat, [[j == js ? ps.T1 : ps.T[j < js ? j : j - 1] for j in 1:p] for ps in problems])
+    Z = reduce(vcat, [ps.Z for ps in problems])
+    wr = [real(ps.values[i]) for i in 1:n, ps in problems]; wi = [imag(ps.values[i]) for i in 1:n, ps in problems]
+    nvec = zeros(Cint, nb); info = Ref{Cint}(0)
+    Tp = _ptrs(T); Zp = _ptrs(Z)
+    nmat = shifted ? p : 1
+    call(Vp, maxvec) = ccall((:psd_d_eigvecs_batch, libpsd), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ptr{Float64}, Ptr{Float64}, Cchar, Cint,
+         Ptr{UInt8}, Cint, Ptr{Ptr{ComplexF64}}, Cint, Ptr{Cint}, Ptr{Int32}, Ptr{Cvoid}, Ref{Cint}),
+        ctx().ptr, nb, n, p, Tp, Zp, wr, wi, orient, js, sel, shifted, Vp, maxvec, nvec, C_NULL, C_NULL, info)
+    GC.@preserve T Z wr wi sel nvec begin
+        call(C_NULL, 0)                                   # size query: select completed, nvec
+        info[] != 0 && _throw(info[])
+        maxvec = Int(maximum(nvec))
+        V = [zeros(ComplexF64, n, maxvec) for _ in 1:(nb * nmat)]
+        Vp = [pointer(v) for v in V]
+        GC.@preserve V Vp begin
+            call(Vp, maxvec)
+        end
+        info[] != 0 && _throw(info[])
+        return [[V[(q - 1) * nmat + l][:, 1:nvec[q]] for l in 1:nmat] for q in 1:nb]
+    end
+end
 
 # pschur!(A, lr; ...), ComplexF64 — PSD.jl:1106-1111 (the all-true signature of generalized.jl:108-137)
 function pschur!(A::Vector{Matrix{ComplexF64}}, lr::Symbol = :R; wantZ::Bool = true, wantT::Bool = true, maxitfac = 30)

@@ -137,6 +137,18 @@ class EvecStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class BevecStats(C.Structure):
+    """psd_bevec_stats (include/psd_mi355x.h): counters, launches and device times of one eigvecs_batch call."""
+    _fields_ = [
+        ("nb", C.c_int32), ("nvec_total", C.c_int32), ("nperturbed", C.c_int32), ("nrescaled", C.c_int32),
+        ("nzero", C.c_int32), ("nlaunch", C.c_int32), ("ngroups", C.c_int32), ("reserved", C.c_int32),
+        ("ms_solve", C.c_double), ("ms_backtransform", C.c_double), ("ms_kernels", C.c_double),
+    ]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class PKSFailure(Exception):
     """PKSFailure (src/krylov.jl:21-23): the Arnoldi re-initialisation failed."""
 
@@ -322,6 +334,10 @@ class Engine:
             mats = C.c_void_p if dev else dpp
             getattr(lib, nm).argtypes = [C.c_void_p, C.c_int, C.c_int, mats, mats, u8p, C.c_char, C.c_int, u8p, C.c_int,
                                          C.c_int, mats, C.c_int, dp, C.POINTER(EvecStats), ip]
+        for nm, dev in (("psd_d_eigvecs_batch", False), ("psd_d_eigvecs_batch_dev", True)):
+            mats = C.c_void_p if dev else dpp
+            getattr(lib, nm).argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, mats, mats, dp, dp, C.c_char, C.c_int,
+                                         u8p, C.c_int, mats, C.c_int, ip, i32p, C.POINTER(BevecStats), ip]
         self.ctx = C.c_void_p()
         rc = lib.psd_create(C.byref(self.ctx), device)
         if rc != 0:
@@ -1221,6 +1237,136 @@ class Engine:
         self._raise(info.value)
         self.eigvecs_stats = st
         return [dV[l, :nvec, :].transpose(0, 1) for l in range(nmat)]
+
+    def eigvecs_batch(self, problems, *args, shifted=True, lr="R", schurindex=1):
+        """eigvecs(ps, select; shifted) by periodic back-substitution for MANY small decompositions of one shape in ONE
+        call (psd_d_eigvecs_batch): the follow-up of pschur_batch.  Float64, all-true signature.  Per problem the result
+        contract is that of `_eigvecs_backsub`; a problem's vectors do not depend on its place in the batch.
+
+        eigvecs_batch(problems, select, shifted=True): `problems` a list of PeriodicSchur of equal order, period,
+        orientation and schurindex; returns a list of what eigvecs(ps, select, method="backsub") returns for each.
+        eigvecs_batch(T, Z, values, select, lr=..., schurindex=..., shifted=True): the torch outputs of the
+        device-resident pschur_batch_ ([nb, p, n, n] tensors, values [nb, n]); returns (V, nvec) with V a complex128
+        device tensor viewed as [nb, nmat, n, maxvec] (nmat = p if shifted else 1, maxvec = max(nvec); the columns of
+        problem q at and beyond nvec[q] are zero) and nvec an int array [nb].
+
+        `select`: [nb][n] flags, or one [n] row used for every problem; completed to conjugate pairs per problem.  A
+        problem whose row is all false costs nothing and gets no columns: that is how to skip the problems whose
+        pschur_batch info was non-zero.  The stats of the call are left in `self.eigvecs_batch_stats` (BevecStats), the
+        per-problem counters (perturbed pivots, rescaled columns, zero eigenvalues) in `self.eigvecs_batch_counts`
+        ([nb, 3])."""
+        if hasattr(problems, "data_ptr"):
+            if len(args) != 3:
+                raise TypeError("eigvecs_batch(T, Z, values, select, lr=..., schurindex=...)")
+            return self._eigvecs_batch_dev(problems, args[0], args[1], args[2], lr, schurindex, shifted)
+        if len(args) != 1:
+            raise TypeError("eigvecs_batch(problems, select, shifted=True)")
+        problems = list(problems)
+        nb = len(problems)
+        if nb == 0:
+            self.eigvecs_batch_stats = BevecStats()
+            self.eigvecs_batch_counts = np.zeros((0, 3), dtype=np.int32)
+            return []
+        n = p = None
+        Ts, Zs = [], []
+        for ps in problems:
+            if isinstance(ps, GeneralizedPeriodicSchur) and not all(ps.S):
+                raise NotImplementedPSD("eigvecs_batch: signed GeneralizedPeriodicSchur (use geigvecs per problem)")
+            if len(ps.Z) == 0 or ps.Z[0].shape[0] == 0:
+                raise ValueError("eigvecs requires Schur vectors in the PSD")  # vectors.jl:30-32
+            if any(np.iscomplexobj(t) for t in ps.Ts):
+                raise NotImplementedPSD("eigvecs_batch: Float64 only (use eigvecs per problem for ComplexF64)")
+            if any(np.iscomplexobj(z) for z in ps.Z):
+                raise TypeError("eigvecs: the factors T and the Schur vectors Z must be all real or all complex")
+            nq = ps.Ts[0].shape[0]
+            if n is None:
+                n, p, orient, si = nq, len(ps.Ts), ps.orientation, ps.schurindex
+            if (nq != n or len(ps.Ts) != p or len(ps.Z) != p or ps.orientation != orient or ps.schurindex != si
+                    or any(t.shape != (n, n) for t in ps.Ts) or any(z.shape != (n, n) for z in ps.Z)):
+                raise DimensionMismatch("the problems of a batch must have equal order, period, orientation and schurindex")
+            Ts += [np.asfortranarray(t, dtype=np.float64) for t in ps.Ts]  # (read only: the problems are never written)
+            Zs += [np.asfortranarray(z, dtype=np.float64) for z in ps.Z]
+        sel = self._batch_select(args[0], nb, n)
+        vals = np.array([np.asarray(ps.values, dtype=np.complex128) for ps in problems])
+        wr, wi = np.ascontiguousarray(vals.real), np.ascontiguousarray(vals.imag)
+        dp, u8p = C.POINTER(C.c_double), C.POINTER(C.c_uint8)
+        nvec = (C.c_int * nb)()
+        cnts = np.zeros((nb, 3), dtype=np.int32)
+        st = BevecStats()
+        info = C.c_int(0)
+        head = [self.ctx, nb, n, p, self._ptrs(Ts), self._ptrs(Zs), wr.ctypes.data_as(dp), wi.ctypes.data_as(dp),
+                orient.encode(), int(si), sel.ctypes.data_as(u8p), int(bool(shifted))]
+        tail = [nvec, cnts.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(st), C.byref(info)]
+        self.lib.psd_d_eigvecs_batch(*head, None, 0, *tail)  # size query: select completed, nvec
+        self._raise(info.value)
+        maxvec = max(nvec)
+        nmat = p if shifted else 1
+        Vs = [np.zeros((n, maxvec), dtype=np.complex128, order="F") for _ in range(nb * nmat)]
+        self.lib.psd_d_eigvecs_batch(*head, self._ptrs(Vs), maxvec, *tail)
+        self._raise(info.value)
+        self.eigvecs_batch_stats = st
+        self.eigvecs_batch_counts = cnts
+        return [[np.asfortranarray(Vs[q * nmat + l][:, :nvec[q]]) for l in range(nmat)] for q in range(nb)]
+
+    @staticmethod
+    def _batch_select(select, nb, n):
+        """[nb][n] flags (uint8, contiguous, a copy) from [nb][n] or one [n] row for every problem."""
+        sel = np.asarray(select)
+        if sel.ndim == 1 and sel.shape[0] == n:
+            sel = np.broadcast_to(sel, (nb, n))
+        if sel.shape != (nb, n):
+            raise ValueError("argument 9 invalid: `select` must be [nb][n] flags or one row of n "
+                             "(its length must correspond to the rank of the Schur space)")  # vectors.jl:34-36
+        return np.ascontiguousarray(sel.astype(bool), dtype=np.uint8)
+
+    def _eigvecs_batch_dev(self, T, Z, values, select, lr, schurindex, shifted):
+        import torch
+
+        if Z is None:
+            raise ValueError("eigvecs requires Schur vectors in the PSD")
+        if T.dim() != 4 or T.shape[2] != T.shape[3] or Z.shape != T.shape:
+            raise DimensionMismatch("a device batch is [nb, p, n, n] tensors T and Z of square factors")
+        if T.is_complex() or Z.is_complex():
+            raise NotImplementedPSD("eigvecs_batch: Float64 only (use eigvecs_dev per problem for ComplexF64)")
+        if not (T.is_cuda and Z.is_cuda):
+            raise TypeError("device-resident eigvecs_batch needs GPU tensors (use a list of PeriodicSchur for host input)")
+        nb, p, n = T.shape[0], T.shape[1], T.shape[2]
+        orient = char_lr(lr)
+        nmat = p if shifted else 1
+        if nb == 0:
+            self.eigvecs_batch_stats = BevecStats()
+            self.eigvecs_batch_counts = np.zeros((0, 3), dtype=np.int32)
+            return torch.zeros((0, nmat, n, 0), dtype=torch.complex128, device=T.device), np.zeros(0, dtype=np.int32)
+        sel = self._batch_select(select, nb, n)
+        vals = np.asarray(values, dtype=np.complex128)
+        if vals.shape != (nb, n):
+            raise DimensionMismatch("values must be [nb, n]")
+        wr, wi = np.ascontiguousarray(vals.real), np.ascontiguousarray(vals.imag)
+        # [nb][p][n][n] blocks of column-major matrices: the transpose of each factor, contiguous (what pschur_batch_
+        # returns a view of: no copy then)
+        dT = T.to(torch.float64).transpose(2, 3).contiguous()
+        dZ = Z.to(torch.float64).transpose(2, 3).contiguous()
+        dp, u8p = C.POINTER(C.c_double), C.POINTER(C.c_uint8)
+        nvec = (C.c_int * nb)()
+        cnts = np.zeros((nb, 3), dtype=np.int32)
+        st = BevecStats()
+        info = C.c_int(0)
+        head = [self.ctx, nb, n, p, C.c_void_p(dT.data_ptr()), C.c_void_p(dZ.data_ptr()), wr.ctypes.data_as(dp),
+                wi.ctypes.data_as(dp), orient.encode(), int(schurindex), sel.ctypes.data_as(u8p), int(bool(shifted))]
+        tail = [nvec, cnts.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(st), C.byref(info)]
+        torch.cuda.synchronize(T.device)
+        self.lib.psd_d_eigvecs_batch_dev(*head, None, 0, *tail)  # size query
+        self._raise(info.value)
+        maxvec = max(nvec)
+        dV = torch.empty((nb, nmat, max(maxvec, 1), n), dtype=torch.complex128, device=T.device)
+        if maxvec == 0:
+            dV.zero_()
+        torch.cuda.synchronize(T.device)
+        self.lib.psd_d_eigvecs_batch_dev(*head, C.c_void_p(dV.data_ptr()), max(maxvec, 1), *tail)
+        self._raise(info.value)
+        self.eigvecs_batch_stats = st
+        self.eigvecs_batch_counts = cnts
+        return dV[:, :, :maxvec, :].transpose(2, 3), np.array(list(nvec), dtype=np.int32)
 
     def geigvecs(self, P, select, shifted=True):
         """Eigenvectors of a signed or singular periodic product (psd_d_geigvecs / psd_z_geigvecs): periodic

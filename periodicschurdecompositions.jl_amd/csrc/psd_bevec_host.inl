@@ -1,0 +1,324 @@
+// Host driver of psd_d_eigvecs_batch / psd_d_eigvecs_batch_dev (psd_bevec.h): eigenvectors by back-substitution for nb
+// periodic Schur decompositions of one shape, as psd_d_pschur_batch leaves them.  Included at the end of psd_engine.cpp
+// behind psd_evec_host.inl (eigvecs_dev, psd_ev_root) and psd_batch_host.inl (psd_batchbuf, batch_group, batch_upload).
+//
+// Per group of problems: the tables (row-block map, solve columns, roots, eigenvalues, the list of units) are built on
+// the host and uploaded once; then psd_bev_solve, psd_bev_backtransform for V_1, psd_bev_norm, psd_bev_backtransform for
+// the other factors — four launches whatever nb and n are — and one read-back of the counters.  Orders above
+// PSD_BEV_NMAX run eigvecs_dev problem by problem on the slices of the batch buffers.
+
+namespace {
+
+// the 2x2 row blocks of every problem from the sub-diagonals sub [nb][n] of the quasi-triangular factors; completes select
+// to whole conjugate pairs and counts the columns
+void bevec_blocks(int nb, int n, const double* sub, uint8_t* select, std::vector<int>& bsz, int* nvec) {
+    bsz.assign((size_t)nb * n, 1);
+    for (int q = 0; q < nb; ++q) {
+        int* b = bsz.data() + (size_t)q * n;
+        uint8_t* s = select + (size_t)q * n;
+        for (int i = 0; i + 1 < n; ++i)
+            if (b[i] == 1 && sub && sub[(size_t)q * n + i] != 0.0) {
+                b[i] = 2;
+                b[i + 1] = 0;
+            }
+        int nv = 0;
+        for (int i = 0; i < n; i += b[i]) {
+            if (b[i] == 2 && (s[i] || s[i + 1])) s[i] = s[i + 1] = 1;
+            if (s[i]) nv += b[i];
+        }
+        nvec[q] = nv;
+    }
+}
+
+struct bevec_call {
+    psd_ctx* c;
+    int n, p, six, schurindex, shifted, maxvec;
+    bool left;
+    char orient;
+};
+
+// gc problems resident on the device (dT, dZ [gc][p][n][n], dV [gc][nmat][maxvec][n] complex), their eigenvalues, completed
+// selections and row blocks; cnt3 [gc][3] receives the counters per problem
+int bevec_group(const bevec_call& k, int gc, const double* dT, const double* dZ, const double* wr, const double* wi,
+                const uint8_t* select, const int* bsz, double* dV, int32_t* cnt3, psd_bevec_stats* st) {
+    psd_ctx* c = k.c;
+    const int n = k.n, p = k.p, nmat = k.shifted ? p : 1;
+    const int IS = psd_bev_istride(n), IH = psd_bev_ihead(p), DS = psd_bev_dstride(n);
+    std::vector<int> itab((size_t)IH + (size_t)gc * IS, 0), units;
+    std::vector<double> dtab((size_t)gc * DS, 0.0);
+    for (int j = 0; j < p; ++j) {  // working form (left orientation), as eigvecs_dev
+        itab[j] = k.left ? j : p - 1 - j;
+        itab[p + j] = k.left ? j : (p - j) % p;
+    }
+    int nsm = 0;
+    for (int q = 0; q < gc; ++q) {
+        int* tab = itab.data() + IH + (size_t)q * IS;
+        double* dt = dtab.data() + (size_t)q * DS;
+        const int* b = bsz + (size_t)q * n;
+        const uint8_t* s = select + (size_t)q * n;
+        int ns = 0, nvec = 0, nblk = 0;
+        for (int i = 0; i < n; i += b[i]) {
+            ++nblk;
+            if (!s[i]) continue;
+            const std::complex<double> l(wr[(size_t)q * n + i], wi[(size_t)q * n + i]), u = psd_ev_root(l, p);
+            tab[n + ns] = i;
+            tab[2 * n + ns] = b[i];
+            tab[3 * n + ns] = i + b[i];
+            tab[4 * n + ns] = nvec;
+            tab[5 * n + ns] = b[i] == 2;
+            tab[6 * n + ns] = nblk;
+            dt[2 * ns] = u.real();
+            dt[2 * ns + 1] = u.imag();
+            dt[2 * n + 2 * ns] = l.real();
+            dt[2 * n + 2 * ns + 1] = l.imag();
+            units.push_back(q);
+            units.push_back(ns);
+            nvec += b[i];
+            ++ns;
+        }
+        for (int i = 0; i < n; ++i) {
+            tab[i] = b[i];
+            dt[4 * n + 2 * i] = wr[(size_t)q * n + i];
+            dt[4 * n + 2 * i + 1] = wi[(size_t)q * n + i];
+        }
+        tab[7 * n] = ns;
+        nsm = ns > nsm ? ns : nsm;
+    }
+    const int nunits = (int)(units.size() / 2);
+    PSD_CHECK(psd_rt_memset(dV, 0, sizeof(double) * 2 * (size_t)gc * nmat * n * k.maxvec, c->stream));
+    if (nunits == 0) {
+        PSD_CHECK(psd_rt_sync(c->stream));
+        return 0;
+    }
+    itab.insert(itab.end(), units.begin(), units.end());
+    const size_t ncnt = 3 * (size_t)gc * n;
+    psd_batchbuf bI, bD, bX, bR, bS, bC;
+    PSD_CHECK(bI.alloc(sizeof(int) * itab.size()));
+    PSD_CHECK(bD.alloc(sizeof(double) * dtab.size()));
+    PSD_CHECK(bX.alloc(sizeof(double) * 2 * (size_t)gc * p * n * nsm));
+    if (p > 64) PSD_CHECK(bR.alloc(sizeof(double) * 4 * (size_t)nunits * p));
+    PSD_CHECK(bS.alloc(sizeof(double) * 2 * (size_t)gc * n));
+    PSD_CHECK(bC.alloc(sizeof(int) * ncnt));
+    PSD_CHECK(psd_rt_h2d(bI.ptr, itab.data(), sizeof(int) * itab.size(), c->stream));
+    PSD_CHECK(psd_rt_h2d(bD.ptr, dtab.data(), sizeof(double) * dtab.size(), c->stream));
+    PSD_CHECK(psd_rt_memset(bC.ptr, 0, sizeof(int) * ncnt, c->stream));
+    Timer tsolve, tback;
+    tsolve.start(c->stream);
+    psd_bev_args a;
+    a.T = dT; a.itab = (const int*)bI.ptr; a.dtab = bD.d(); a.X = bX.d(); a.R = bR.d(); a.cnt = (int*)bC.ptr;
+    a.n = n; a.p = p; a.nsm = nsm; a.nunits = nunits; a.gc = gc; a.six = k.six;
+    const int C = 64 / psd_bev_lw(p);
+    PSD_LAUNCH(psd_bev_solve, psd_dim3((nunits + C - 1) / C), 64, PSD_BEV_LDS, c->stream, a);
+    st->nlaunch += 1;
+    st->ms_solve += tsolve.stop(c->stream);
+    // V_l = Z_l x_l: V_1 first, its norms and phases, then the other factors with the column factors
+    tback.start(c->stream);
+    psd_bev_bt_args g;
+    g.Z = dZ; g.X = bX.d(); g.itab = (const int*)bI.ptr; g.S = nullptr; g.cnt = (const int*)bC.ptr; g.V = dV;
+    g.n = n; g.p = p; g.nsm = nsm; g.nmat = nmat; g.maxvec = k.maxvec; g.z0 = 0; g.nz = 1;
+    const int tiles = (int)(((size_t)nsm * n + PSD_BEV_NT - 1) / PSD_BEV_NT);
+    PSD_LAUNCH(psd_bev_backtransform, psd_dim3(gc, tiles), PSD_BEV_NT, 0, c->stream, g);
+    PSD_LAUNCH(psd_bev_norm, psd_dim3((int)(((size_t)gc * n + PSD_BEV_NT - 1) / PSD_BEV_NT)), PSD_BEV_NT, 0, c->stream, dV,
+               (const int*)bI.ptr, (const int*)bC.ptr, bS.d(), n, p, gc, nmat, k.maxvec);
+    st->nlaunch += 2;
+    if (nmat > 1) {
+        g.S = bS.d(); g.z0 = 1; g.nz = nmat - 1;
+        PSD_LAUNCH(psd_bev_backtransform, psd_dim3(gc * (nmat - 1), tiles), PSD_BEV_NT, 0, c->stream, g);
+        st->nlaunch += 1;
+    }
+    st->ms_backtransform += tback.stop(c->stream);
+    std::vector<int> cnt(ncnt);
+    PSD_CHECK(psd_rt_d2h(cnt.data(), bC.ptr, sizeof(int) * ncnt, c->stream));
+    PSD_CHECK(psd_rt_sync(c->stream));
+    PSD_CHECK(psd_rt_last_error());
+    for (int q = 0; q < gc; ++q)
+        for (int j = 0; j < n; ++j) {
+            const int* e = cnt.data() + 3 * ((size_t)q * n + j);
+            cnt3[3 * q] += e[0];
+            cnt3[3 * q + 1] += e[1] > 0;
+            cnt3[3 * q + 2] += e[2];
+        }
+    return 0;
+}
+
+// above PSD_BEV_NMAX: the single path on the slices of the batch buffers (its V blocks are n x nvec: through a staging
+// block into the n x maxvec blocks of the batch)
+int bevec_single(const bevec_call& k, int gc, const double* dT, const double* dZ, const double* wr, const double* wi,
+                 uint8_t* select, const int* nvec, double* dV, int32_t* cnt3, psd_bevec_stats* st) {
+    psd_ctx* c = k.c;
+    const int n = k.n, p = k.p, nmat = k.shifted ? p : 1;
+    const size_t nn = (size_t)n * n, vb = 2 * (size_t)n * k.maxvec;
+    PSD_CHECK(psd_rt_memset(dV, 0, sizeof(double) * vb * nmat * gc, c->stream));
+    psd_batchbuf stage;
+    PSD_CHECK(stage.alloc(sizeof(double) * vb * nmat));
+    for (int q = 0; q < gc; ++q) {
+        if (nvec[q] == 0) continue;
+        std::vector<std::complex<double>> lam(n);
+        for (int i = 0; i < n; ++i) lam[i] = std::complex<double>(wr[(size_t)q * n + i], wi[(size_t)q * n + i]);
+        psd_evec_stats es;
+        memset(&es, 0, sizeof(es));
+        const int rc = eigvecs_dev<false>(c, n, p, dT + (size_t)q * p * nn, dZ + (size_t)q * p * nn, lam.data(), k.orient,
+                                          k.schurindex, select + (size_t)q * n, k.shifted, stage.d(), nvec[q], &es);
+        if (rc != 0) return rc;
+        for (int l = 0; l < nmat; ++l)
+            PSD_CHECK(psd_rt_d2d(dV + ((size_t)q * nmat + l) * vb, stage.d() + 2 * (size_t)l * n * nvec[q],
+                                 sizeof(double) * 2 * n * nvec[q], c->stream));
+        PSD_CHECK(psd_rt_sync(c->stream));
+        cnt3[3 * q] += es.nperturbed;
+        cnt3[3 * q + 1] += es.nrescaled;
+        cnt3[3 * q + 2] += es.nzero;
+        st->ms_solve += es.ms_solve;
+        st->ms_backtransform += es.ms_backtransform;
+        st->nlaunch += 3 + 2 * ((n + PSD_EV_CH - 1) / PSD_EV_CH);  // (an upper bound: a launch pair per chunk)
+    }
+    return 0;
+}
+
+int bevec_run(const bevec_call& k, int gc, const double* dT, const double* dZ, const double* wr, const double* wi,
+              uint8_t* select, const int* bsz, const int* nvec, double* dV, int32_t* cnt3, psd_bevec_stats* st) {
+    st->ngroups += 1;
+    if (k.n > k.c->bev_nmax) return bevec_single(k, gc, dT, dZ, wr, wi, select, nvec, dV, cnt3, st);
+    return bevec_group(k, gc, dT, dZ, wr, wi, select, bsz, dV, cnt3, st);
+}
+
+int bevec_checked(psd_ctx* c, int nb, int n, int p, const void* T, const void* Z, const double* wr, const double* wi,
+                  char orient, int schurindex, const uint8_t* select, int* nvec, psd_bevec_stats* st) {
+    if (!c) return -1;
+    if (n < 1) return -2;
+    if (p < 1) return -3;
+    if (nb < 0) return -11;
+    if (nb == 0) return 0;
+    if (!T) return -4;
+    if (!Z) return -5;
+    if (!wr || !wi) return -6;
+    if (orient != 'L' && orient != 'R') return -7;
+    if (schurindex < 1 || schurindex > p) return -8;
+    if (!select) return -9;
+    if (!nvec) return -12;
+    if (c->shard_world > 1) return PSD_INFO_NOTIMPL;  // (a period-sharded context keeps a slice of Z: single problems only)
+    (void)st;
+    return 0;
+}
+
+void bevec_finish(int nb, const int* nvec, const int32_t* cnt3, int32_t* pcnt, psd_bevec_stats* st) {
+    st->nb = nb;
+    for (int q = 0; q < nb; ++q) {
+        st->nvec_total += nvec[q];
+        st->nperturbed += cnt3[3 * q];
+        st->nrescaled += cnt3[3 * q + 1];
+        st->nzero += cnt3[3 * q + 2];
+    }
+    st->ms_kernels = st->ms_solve + st->ms_backtransform;
+    if (pcnt) memcpy(pcnt, cnt3, sizeof(int32_t) * 3 * (size_t)nb);
+}
+
+}  // namespace
+
+extern "C" {
+
+int psd_d_eigvecs_batch_dev(psd_ctx* c, int nb, int n, int p, const double* dT, const double* dZ, const double* wr,
+                            const double* wi, char orient, int schurindex, uint8_t* select, int shifted, double* dV,
+                            int maxvec, int* nvec, int32_t* pcnt, psd_bevec_stats* stats, int* info) {
+    int dummy;
+    if (!info) info = &dummy;
+    psd_bevec_stats local;
+    psd_bevec_stats* st = stats ? stats : &local;
+    memset(st, 0, sizeof(*st));
+    if ((*info = bevec_checked(c, nb, n, p, dT, dZ, wr, wi, orient, schurindex, select, nvec, st)) != 0 || nb == 0)
+        return *info;
+    const size_t nn = (size_t)n * n, tot = (size_t)nb * n;
+    const bool left = orient == 'L';
+    bool any = false;
+    for (size_t e = 0; e < tot && !any; ++e) any = select[e] != 0;
+    std::vector<double> sub;
+    if (any && n > 1) {  // one kernel and one read-back define the 2x2 row blocks of the whole batch
+        psd_batchbuf bsub;
+        PSD_CHECK(bsub.alloc(sizeof(double) * tot));
+        PSD_LAUNCH(psd_bev_subdiag, psd_dim3((int)((tot + PSD_BEV_NT - 1) / PSD_BEV_NT)), PSD_BEV_NT, 0, c->stream, dT, n, p,
+                   schurindex - 1, nb, bsub.d());
+        st->nlaunch += 1;
+        sub.resize(tot);
+        PSD_CHECK(psd_rt_d2h(sub.data(), bsub.d(), sizeof(double) * tot, c->stream));
+        PSD_CHECK(psd_rt_sync(c->stream));
+    }
+    std::vector<int> bsz;
+    bevec_blocks(nb, n, sub.empty() ? nullptr : sub.data(), select, bsz, nvec);
+    int mv = 0;
+    for (int q = 0; q < nb; ++q) mv = nvec[q] > mv ? nvec[q] : mv;
+    if (!dV) return *info = 0;
+    if (mv > maxvec) return *info = -10;
+    std::vector<int32_t> cnt3(3 * (size_t)nb, 0);
+    if (any) {
+        const bevec_call k{c, n, p, left ? schurindex - 1 : p - schurindex, schurindex, shifted, maxvec, left, orient};
+        const int nmat = shifted ? p : 1;
+        const int g = batch_group(c, nb, sizeof(double) * 2 * (size_t)p * n * (mv > 0 ? mv : 1));
+        for (int q0 = 0; q0 < nb; q0 += g) {
+            const int gc = nb - q0 < g ? nb - q0 : g;
+            *info = bevec_run(k, gc, dT + (size_t)q0 * p * nn, dZ + (size_t)q0 * p * nn, wr + (size_t)q0 * n,
+                              wi + (size_t)q0 * n, select + (size_t)q0 * n, bsz.data() + (size_t)q0 * n, nvec + q0,
+                              dV + 2 * (size_t)q0 * nmat * n * maxvec, cnt3.data() + 3 * (size_t)q0, st);
+            if (*info != 0) return *info;
+        }
+    } else {
+        PSD_CHECK(psd_rt_memset(dV, 0, sizeof(double) * 2 * (size_t)nb * (shifted ? p : 1) * n * maxvec, c->stream));
+        PSD_CHECK(psd_rt_sync(c->stream));
+    }
+    bevec_finish(nb, nvec, cnt3.data(), pcnt, st);
+    return *info = 0;
+}
+
+int psd_d_eigvecs_batch(psd_ctx* c, int nb, int n, int p, double* const* T, double* const* Z, const double* wr,
+                        const double* wi, char orient, int schurindex, uint8_t* select, int shifted, double* const* V,
+                        int maxvec, int* nvec, int32_t* pcnt, psd_bevec_stats* stats, int* info) {
+    int dummy;
+    if (!info) info = &dummy;
+    psd_bevec_stats local;
+    psd_bevec_stats* st = stats ? stats : &local;
+    memset(st, 0, sizeof(*st));
+    if ((*info = bevec_checked(c, nb, n, p, T, Z, wr, wi, orient, schurindex, select, nvec, st)) != 0 || nb == 0)
+        return *info;
+    const size_t nn = (size_t)n * n, tot = (size_t)nb * n;
+    const bool left = orient == 'L';
+    bool any = false;
+    for (size_t e = 0; e < tot && !any; ++e) any = select[e] != 0;
+    std::vector<double> sub(tot, 0.0);  // (the factors are on the host: no kernel)
+    for (int q = 0; q < nb; ++q) {
+        const double* t = T[(size_t)q * p + schurindex - 1];
+        for (int i = 0; i + 1 < n; ++i) sub[(size_t)q * n + i] = t[(size_t)i * n + i + 1];
+    }
+    std::vector<int> bsz;
+    bevec_blocks(nb, n, sub.data(), select, bsz, nvec);
+    int mv = 0;
+    for (int q = 0; q < nb; ++q) mv = nvec[q] > mv ? nvec[q] : mv;
+    if (!V) return *info = 0;
+    if (mv > maxvec) return *info = -10;
+    const int nmat = shifted ? p : 1;
+    const size_t vb = 2 * (size_t)n * maxvec;
+    std::vector<int32_t> cnt3(3 * (size_t)nb, 0);
+    if (!any || maxvec == 0) {
+        for (size_t e = 0; e < (size_t)nb * nmat; ++e) memset(V[e], 0, sizeof(double) * vb);
+        bevec_finish(nb, nvec, cnt3.data(), pcnt, st);
+        return *info = 0;
+    }
+    const bevec_call k{c, n, p, left ? schurindex - 1 : p - schurindex, schurindex, shifted, maxvec, left, orient};
+    int g = batch_group(c, nb, sizeof(double) * (2 * nn * p + vb * nmat + 2 * (size_t)p * n * mv));
+    psd_batchbuf dbuf[2], dV;
+    psd_hostbuf hst, hv;
+    if ((*info = batch_buffers(g, nn * p, 2, dbuf, hst)) != 0) return *info;
+    PSD_CHECK(dV.alloc(sizeof(double) * vb * nmat * g));
+    if (!hv.alloc(sizeof(double) * vb * nmat * g)) return *info = PSD_INFO_RUNTIME + 3;
+    for (int q0 = 0; q0 < nb; q0 += g) {
+        const int gc = nb - q0 < g ? nb - q0 : g;
+        if ((*info = batch_upload(c, T, q0, gc, p, nn, hst.d(), dbuf[0].d())) != 0) return *info;
+        if ((*info = batch_upload(c, Z, q0, gc, p, nn, hst.d(), dbuf[1].d())) != 0) return *info;
+        *info = bevec_run(k, gc, dbuf[0].d(), dbuf[1].d(), wr + (size_t)q0 * n, wi + (size_t)q0 * n,
+                          select + (size_t)q0 * n, bsz.data() + (size_t)q0 * n, nvec + q0, dV.d(),
+                          cnt3.data() + 3 * (size_t)q0, st);
+        if (*info != 0) return *info;
+        if ((*info = batch_download(c, V, q0, gc, nmat, vb, hv.d(), dV.d())) != 0) return *info;
+    }
+    bevec_finish(nb, nvec, cnt3.data(), pcnt, st);
+    return *info = 0;
+}
+
+}  // extern "C"

@@ -22,6 +22,7 @@
 #include "psd_krylov.h"
 #include "psd_evec.h"
 #include "psd_gevec.h"
+#include "psd_bevec.h"
 
 #include "../../include/psd_mi355x.h"
 
@@ -265,6 +266,7 @@ struct psd_ctx {
     int shard_rank = 0, shard_world = 1;
     int batch_group = 0;  // PSD_BATCH_GROUP: most problems a host batch entry takes to the device at once (0: what fits)
     int bh_nmax = PSD_BH_NMAX;  // largest order of the one-workgroup-per-problem reduction (diagnostic build: PSD_BH_NMAX in the environment, for the sweep that sets the constant)
+    int bev_nmax = PSD_BEV_NMAX;  // largest order of the batched eigenvector kernels (diagnostic build: PSD_BEV_NMAX in the environment, for the sweep that sets the constant)
     void slice(int p, int& lo, int& hi) const {  // [lo, hi), 0-based internal factor index
         const int base = p / shard_world, rem = p % shard_world;
         lo = shard_rank * base + (shard_rank < rem ? shard_rank : rem);
@@ -1728,6 +1730,7 @@ int psd_create(psd_ctx** ctx, int device) {
     if (const char* e = psd_env("PSD_FORMQ_BLOCKED")) c->formq_blocked = atoi(e);
     if (const char* e = psd_env("PSD_BATCH_GROUP")) c->batch_group = atoi(e) > 0 ? atoi(e) : 0;
     if (const char* e = psd_env_diag("PSD_BH_NMAX")) c->bh_nmax = (atoi(e) >= 1 && atoi(e) <= 2048) ? atoi(e) : PSD_BH_NMAX;
+    if (const char* e = psd_env_diag("PSD_BEV_NMAX")) c->bev_nmax = (atoi(e) >= 1 && atoi(e) <= 2048) ? atoi(e) : PSD_BEV_NMAX;
     if (const char* e = psd_env("PSD_BAND_HELPER")) c->band_helper = atoi(e);
     if (const char* e = psd_env_diag("PSD_TRAIN_LONG")) c->train_long = atoi(e);
     if (const char* e = psd_env_diag("PSD_TRAIN_STOP")) c->train_stop = atoi(e);
@@ -4076,3 +4079,4 @@ extern "C" int psd_dbg_apply_bench(psd_ctx* c, int n, int p, int nwin, int W, in
 #include "psd_evec_host.inl"
 #include "psd_gevec_host.inl"
 #include "psd_batch_host.inl"
+#include "psd_bevec_host.inl"

@@ -365,6 +365,53 @@ PSD_HD void psd_ev_seg(int t, int p, int& lo, int& hi) {
     hi = lo + L < p ? lo + L : p;
 }
 
+// y_0(I) of one row block from the total map round the period, y_0 = G y_0 + c with G = 2^S A, c = 2^S c: the own block's
+// null vector (b == 2) or unit (b == 1), else the solve with the pivot rule above.  y: b entries, e0 its exponent; returns
+// the number of perturbed pivots.  ev: the eigenvalues of the rows (re, im), lam the column's.
+PSD_HD int psd_ev_y0(const psd_ev_map& tot, bool isown, int b, int i, psd_z lam, const double* ev, psd_z y[2], int& e0) {
+    y[0] = zmk(1.0, 0.0);
+    y[1] = zmk(0.0, 0.0);
+    e0 = 0;
+    int npert = 0;
+    const double eps = PSD_DBL_EPS, tiny = PSD_DBL_MIN;
+    const double sI = tot.s > 0 ? ldexp(1.0, -tot.s) : 1.0, sG = tot.s > 0 ? 1.0 : ldexp(1.0, tot.s);
+    if (isown && b == 2) {  // the null vector of G - I, up to the power of two: (N01, -N00) or (N11, -N10)
+        psd_z N[2][2];
+        for (int q = 0; q < 2; ++q)
+            for (int k = 0; k < 2; ++k) N[q][k] = zsub(zscal(sG, tot.A[q][k]), zmk(q == k ? sI : 0.0, 0.0));
+        const bool first = zabs2(N[0][1]) + zabs2(N[0][0]) >= zabs2(N[1][1]) + zabs2(N[1][0]);
+        y[0] = first ? N[0][1] : N[1][1];
+        y[1] = first ? zneg(N[0][0]) : zneg(N[1][0]);
+        if (ziszero(y[0]) && ziszero(y[1])) y[0] = zmk(1.0, 0.0);
+    } else if (!isown && b == 1) {
+        const psd_z li = zmk(ev[2 * i], ev[2 * i + 1]);
+        psd_z d1 = zdiv(zsub(lam, li), lam);  // 1 - G = (lambda - lambda_i) / lambda
+        const double smin = fmax(eps * fmax(1.0, zabs(d1)), tiny);
+        if (!(zabs(d1) >= smin)) {
+            d1 = zmk(smin, 0.0);
+            ++npert;
+        }
+        y[0] = zdiv(tot.c[0], d1);
+        e0 = tot.s;
+    } else if (!isown) {  // 2^S > 1: (2^-S I - A) y = c; else (I - 2^S A) y = c and y_0 = 2^S y
+        psd_z M[2][2], cc[2];
+        double mx = 0.0;
+        for (int q = 0; q < 2; ++q) {
+            for (int k = 0; k < 2; ++k) {
+                M[q][k] = zsub(zmk(q == k ? sI : 0.0, 0.0), zscal(sG, tot.A[q][k]));
+                mx = fmax(mx, zabs(M[q][k]));
+            }
+            cc[q] = tot.c[q];
+        }
+        npert += psd_ev_solve2(M, cc, fmax(eps * fmax(sI, mx), tiny), y);
+        e0 = tot.s > 0 ? 0 : tot.s;
+    }
+    return npert;
+}
+
+// the power of two a column is scaled down by once its largest entry reaches 2^big
+PSD_HD int psd_ev_shift(int big) { return big > PSD_EV_BIG ? big - 200 : 0; }
+
 #define PSD_EV_LDS (2 * 64 * sizeof(psd_ev_map) + 64 * sizeof(int))
 
 // One workgroup (one wavefront) per column of [jlo, ns): the rows of the chunk [r0, r1), bottom up.  Every factor l is
@@ -431,41 +478,9 @@ PSD_D void psd_ev_solve_body(const psd_ev_args& a) {
         psd_ev_map* inc = buf + 64 * cur;
         // y_0(I): round the period, y_0 = G y_0 + c with G = 2^S A, c = 2^S c of the total map
         const psd_ev_map tot = inc[63];
-        psd_z y[2] = {zmk(1.0, 0.0), zmk(0.0, 0.0)};
-        int e0 = 0, npert = 0;
-        const double eps = PSD_DBL_EPS, tiny = PSD_DBL_MIN;
-        const double sI = tot.s > 0 ? ldexp(1.0, -tot.s) : 1.0, sG = tot.s > 0 ? 1.0 : ldexp(1.0, tot.s);
-        if (isown && b == 2) {  // the null vector of G - I, up to the power of two: (N01, -N00) or (N11, -N10)
-            psd_z N[2][2];
-            for (int q = 0; q < 2; ++q)
-                for (int k = 0; k < 2; ++k) N[q][k] = zsub(zscal(sG, tot.A[q][k]), zmk(q == k ? sI : 0.0, 0.0));
-            const bool first = zabs2(N[0][1]) + zabs2(N[0][0]) >= zabs2(N[1][1]) + zabs2(N[1][0]);
-            y[0] = first ? N[0][1] : N[1][1];
-            y[1] = first ? zneg(N[0][0]) : zneg(N[1][0]);
-            if (ziszero(y[0]) && ziszero(y[1])) y[0] = zmk(1.0, 0.0);
-        } else if (!isown && b == 1) {
-            const psd_z li = zmk(a.ev[2 * i], a.ev[2 * i + 1]);
-            psd_z d1 = zdiv(zsub(lam, li), lam);  // 1 - G = (lambda - lambda_i) / lambda
-            const double smin = fmax(eps * fmax(1.0, zabs(d1)), tiny);
-            if (!(zabs(d1) >= smin)) {
-                d1 = zmk(smin, 0.0);
-                ++npert;
-            }
-            y[0] = zdiv(tot.c[0], d1);
-            e0 = tot.s;
-        } else if (!isown) {  // 2^S > 1: (2^-S I - A) y = c; else (I - 2^S A) y = c and y_0 = 2^S y
-            psd_z M[2][2], cc[2];
-            double mx = 0.0;
-            for (int q = 0; q < 2; ++q) {
-                for (int k = 0; k < 2; ++k) {
-                    M[q][k] = zsub(zmk(q == k ? sI : 0.0, 0.0), zscal(sG, tot.A[q][k]));
-                    mx = fmax(mx, zabs(M[q][k]));
-                }
-                cc[q] = tot.c[q];
-            }
-            npert += psd_ev_solve2(M, cc, fmax(eps * fmax(sI, mx), tiny), y);
-            e0 = tot.s > 0 ? 0 : tot.s;
-        }
+        psd_z y[2];
+        int e0;
+        const int npert = psd_ev_y0(tot, isown, b, i, lam, a.ev, y, e0);
         PSD_ONE {
             if (npert) a.cnt[3 * j] += npert;
         }
@@ -494,7 +509,7 @@ PSD_D void psd_ev_solve_body(const psd_ev_args& a) {
         PSD_SYNC();
         int big = -100000;
         for (int t = 0; t < 64; ++t) big = red[t] > big ? red[t] : big;
-        const int shift = big > PSD_EV_BIG ? big - 200 : 0;
+        const int shift = psd_ev_shift(big);
         if (shift) PSD_ONE { a.cnt[3 * j + 1] += 1; }
         // store y_l(I) scaled by 2^-shift, as the rows below and the pending R rows of the chunk are (the maps stay in
         // the old scale: only the stored values move)
@@ -531,6 +546,41 @@ PSD_KERNEL psd_ev_subdiag(const double* T, int n, double* out) {
     }
 }
 
+// one solve column of psd_ev_norm: v its n entries (interleaved; the partner's n behind them), zero: a zero eigenvalue
+PSD_HD void psd_ev_norm_col(double* v, int n, bool pair, bool zero, double& sr, double& si) {
+    if (zero) {  // (the other factors follow from s = NaN)
+        for (int i = 0; i < (pair ? 2 * n : n); ++i) v[2 * i] = v[2 * i + 1] = NAN;
+        sr = si = NAN;
+    } else {
+        double big = 0.0;
+        int imax = 0;
+        for (int i = 0; i < n; ++i) big = fmax(big, zabs1(zmk(v[2 * i], v[2 * i + 1])));
+        double ss = 0.0, amax = -1.0;
+        for (int i = 0; i < n; ++i) {  // (scaled by the largest component: no overflow in the sum of squares)
+            const double a2 = zabs2(zscal(1.0 / big, zmk(v[2 * i], v[2 * i + 1])));
+            ss += a2;
+            if (a2 > amax) {
+                amax = a2;
+                imax = i;
+            }
+        }
+        const double nrm = big * sqrt(ss), am = big * sqrt(amax);
+        const psd_z s = zscal(1.0 / (am * nrm), zconj(zmk(v[2 * imax], v[2 * imax + 1])));
+        for (int i = 0; i < n; ++i) {
+            psd_z u = zmul(s, zmk(v[2 * i], v[2 * i + 1]));
+            if (i == imax) u = zmk(am / nrm, 0.0);
+            v[2 * i] = u.re;
+            v[2 * i + 1] = u.im;
+            if (pair) {
+                v[2 * ((size_t)n + i)] = u.re;
+                v[2 * ((size_t)n + i) + 1] = -u.im;
+            }
+        }
+        sr = s.re;
+        si = s.im;
+    }
+}
+
 // ||V_1(:, c)||_2 and the phase: the largest-modulus entry (lowest row on a tie) becomes real and positive.  One lane
 // per solve column; s = conj(v_max) / (|v_max| ||v||) goes to sr/si for the other factors; V_1 is scaled here (and the
 // conjugate partner rewritten).  A zero-eigenvalue column is set to NaN.
@@ -539,38 +589,7 @@ PSD_KERNEL psd_ev_norm(double* V, int n, int ns, const int* ocol, const int* pai
     PSD_PAR_FOR(t, PSD_NTHREADS) {
         const int j = PSD_BLOCK_X * PSD_NTHREADS + t;
         if (j < ns) {
-            double* v = V + 2 * (size_t)ocol[j] * n;
-            if (cnt[3 * j + 2]) {  // (the other factors follow from s = NaN)
-                for (int i = 0; i < (pair[j] ? 2 * n : n); ++i) v[2 * i] = v[2 * i + 1] = NAN;
-                sr[j] = si[j] = NAN;
-            } else {
-                double big = 0.0;
-                int imax = 0;
-                for (int i = 0; i < n; ++i) big = fmax(big, zabs1(zmk(v[2 * i], v[2 * i + 1])));
-                double ss = 0.0, amax = -1.0;
-                for (int i = 0; i < n; ++i) {  // (scaled by the largest component: no overflow in the sum of squares)
-                    const double a2 = zabs2(zscal(1.0 / big, zmk(v[2 * i], v[2 * i + 1])));
-                    ss += a2;
-                    if (a2 > amax) {
-                        amax = a2;
-                        imax = i;
-                    }
-                }
-                const double nrm = big * sqrt(ss), am = big * sqrt(amax);
-                const psd_z s = zscal(1.0 / (am * nrm), zconj(zmk(v[2 * imax], v[2 * imax + 1])));
-                for (int i = 0; i < n; ++i) {
-                    psd_z u = zmul(s, zmk(v[2 * i], v[2 * i + 1]));
-                    if (i == imax) u = zmk(am / nrm, 0.0);
-                    v[2 * i] = u.re;
-                    v[2 * i + 1] = u.im;
-                    if (pair[j]) {
-                        v[2 * ((size_t)n + i)] = u.re;
-                        v[2 * ((size_t)n + i) + 1] = -u.im;
-                    }
-                }
-                sr[j] = s.re;
-                si[j] = s.im;
-            }
+            psd_ev_norm_col(V + 2 * (size_t)ocol[j] * n, n, pair[j] != 0, cnt[3 * j + 2] != 0, sr[j], si[j]);
         }
     }
 }

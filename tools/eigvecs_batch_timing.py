@@ -1,0 +1,129 @@
+#!/usr/bin/env python3
+"""Timing of Engine.eigvecs_batch on the MI355X (profiles/batch/README.md).
+
+For every shape nb x n x p: random factors A_j = I + 0.5 G_j / sqrt(n) are made on the device, decomposed by the
+device-resident pschur_batch_, and with T, Z left on the device all eigenvectors are computed
+  batch   by one Engine.eigvecs_batch call (psd_d_eigvecs_batch_dev), and
+  loop    by Engine.eigvecs_dev problem by problem on the same engine: the code that existed before, the baseline.
+The second of two runs of each is reported: wall time around the call(s) with the device idle before and after, the
+device times and the launches of the stats, and the largest difference between the two results.
+
+  (default)  n in {8, 16, 32, 64, 128}, p in {2, 4, 16}, nb in {32, 1024}
+  --sweep    n across the cap PSD_BEV_NMAX at nb = 64, p = 4, on the diagnostic library with the cap lifted
+             (PSD_BEV_NMAX in the environment), so that every order takes the batched kernels
+
+Every shape runs in a process of its own under `timeout`; the tool stops at the first one that fails.  One JSON line per
+shape on stdout; --json FILE collects them."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def parse_shapes(text):
+    return [tuple(int(x) for x in s.split("x")) for s in text.split(",") if s]
+
+
+def default_shapes():
+    return [(nb, n, p) for nb in (32, 1024) for n in (8, 16, 32, 64, 128) for p in (2, 4, 16)]
+
+
+def run_one(nb, n, p, lr, sweep):
+    import numpy as np
+    import torch
+
+    torch.cuda.init()
+    import psd_amd
+
+    if sweep:
+        os.environ["PSD_BEV_NMAX"] = "2048"
+        eng = psd_amd.Engine(0, libpath=psd_amd.DIAG_LIB_PATH)
+    else:
+        eng = psd_amd.Engine(0)
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(9000 + n + 1000 * p)
+    A = torch.eye(n, dtype=torch.float64, device="cuda") + 0.5 * torch.randn(
+        (nb, p, n, n), dtype=torch.float64, device="cuda", generator=gen) / np.sqrt(n)
+    infos = []
+    T, Z, values, _ = eng.pschur_batch_(A, lr, infos_out=infos)
+    si = p if lr == "L" else 1
+    select = np.ones((nb, n), dtype=bool)
+    select[[q for q in range(nb) if infos[q] != 0]] = False  # (a problem that did not converge is skipped)
+    Tc, Zc = T.transpose(2, 3), Z.transpose(2, 3)  # the [nb][p][n][n] column-major blocks, contiguous
+    assert Tc.is_contiguous() and Zc.is_contiguous()
+    row = dict(nb=nb, n=n, p=p, lr=lr, nfailed=int(sum(1 for i in infos if i != 0)), sweep=bool(sweep))
+    for _ in range(2):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        V, nvec = eng.eigvecs_batch(T, Z, values, select, lr=lr, schurindex=si)
+        torch.cuda.synchronize()
+        st = eng.eigvecs_batch_stats
+        row["batch"] = dict(wall_ms=1e3 * (time.perf_counter() - t0), ms_solve=st.ms_solve,
+                            ms_backtransform=st.ms_backtransform, nlaunch=int(st.nlaunch), ngroups=int(st.ngroups),
+                            nvec=int(st.nvec_total))
+    for _ in range(2):
+        torch.cuda.synchronize()
+        ms, singles = 0.0, []
+        t0 = time.perf_counter()
+        for q in range(nb):
+            if not select[q, 0]:
+                singles.append(None)
+                continue
+            singles.append(eng.eigvecs_dev(Tc[q], Zc[q], values[q], select[q], lr=lr, schurindex=si))
+            ms += eng.eigvecs_stats.ms_kernels
+        torch.cuda.synchronize()
+        row["loop"] = dict(wall_ms=1e3 * (time.perf_counter() - t0), ms_kernels=ms)
+    diff = 0.0
+    for q in range(0, nb, max(1, nb // 8)):
+        if singles[q] is not None:
+            for l in range(p):
+                d = (V[q, l][:, :nvec[q]] - singles[q][l]).abs().max().item()
+                diff = max(diff, d if d == d else 0.0)  # (NaN columns of zero eigenvalues aside)
+    row["max_abs_diff"] = diff
+    row["wall_ratio"] = row["loop"]["wall_ms"] / row["batch"]["wall_ms"]
+    print(json.dumps(row), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--shapes", default=None, help="nb x n x p, comma separated (default: the grid above)")
+    ap.add_argument("--lr", default="R")
+    ap.add_argument("--sweep", action="store_true")
+    ap.add_argument("--sweep-orders", default="64,96,128,160,192,256")
+    ap.add_argument("--timeout", type=int, default=240, help="seconds per shape")
+    ap.add_argument("--json", default=None)
+    ap.add_argument("--one", default=None, help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.one:
+        run_one(*parse_shapes(args.one)[0], args.lr, args.sweep)
+        return 0
+    if args.shapes:
+        shapes = parse_shapes(args.shapes)
+    elif args.sweep:
+        shapes = [(64, int(x), 4) for x in args.sweep_orders.split(",") if x]
+    else:
+        shapes = default_shapes()
+    rows = []
+    for s in shapes:
+        cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--one",
+               "%dx%dx%d" % s, "--lr", args.lr] + (["--sweep"] if args.sweep else [])
+        pr = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
+        sys.stdout.write(pr.stdout)
+        sys.stdout.flush()
+        if pr.returncode != 0:  # a failure, a fault or a time limit: nothing more is started on the device
+            print(json.dumps(dict(shape=s, failed=pr.returncode)), flush=True)
+            break
+        rows += [json.loads(ln) for ln in pr.stdout.splitlines() if ln.startswith("{")]
+    if args.json:
+        with open(args.json, "w") as fh:
+            json.dump(dict(rows=rows), fh, indent=1)
+    return 0 if len(rows) == len(shapes) else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
