@@ -536,6 +536,41 @@ int psd_d_eigvecs_batch_dev(psd_ctx* ctx, int nb, int n, int p, const double* dT
                             const double* wi, char orient, int schurindex, uint8_t* select, int shifted, double* dV,
                             int maxvec, int* nvec, int32_t* pcnt, psd_bevec_stats* stats, int* info);
 
+/* ---- ordschur_batch: reorder many small periodic Schur forms in one call ------------------------------------------
+ * psd_d_ordschur (rordschur.jl:3-132) for nb decompositions of one shape (n, p), as psd_d_pschur_batch leaves them:
+ * Float64, all-true signature, one orient and schurindex (1 or p) for the whole batch.  Per problem the result contract
+ * is that of psd_d_ordschur: the selected eigenvalues lead, selecting one member of a conjugate pair takes its partner
+ * along, the order inside both groups is kept.  Up to order 128 one wavefront carries one problem through its whole
+ * reordering and a group is ONE launch of the swap kernel whatever nb is (stats->nlaunch_step counts them); above, or
+ * for a period whose narrowest window does not fit the LDS, the single-problem driver runs problem by problem on the
+ * slices of the batch buffers.  A problem's result does not depend on its place in the batch or on the grouping (bit
+ * for bit).  A batch that does not fit the free device memory is worked through in groups (PSD_BATCH_GROUP in the
+ * environment lowers the group size; PSD_BORD_W narrows the window, PSD_BORD_NMAX lowers the order limit).
+ *
+ * T, Z: nb * p pointers to n x n matrices (problem-major, user order), reordered in place; Z may be NULL when !wantZ.
+ * select: host [nb][n].  wr, wi: host [nb][n], the eigenvalues in their new order; the rows of a failed problem are not
+ * written.  infos: host [nb] or NULL, per problem 0, 3000 (singular periodic Sylvester system) or 2000 + row (swap
+ * rejected: ill-conditioned), the codes of psd_d_ordschur; a rejected swap ends its problem alone and leaves it a
+ * consistent decomposition (the swaps made so far).  nswaps: host [nb] or NULL, the adjacent swaps of every problem.
+ * stats: nsweeps = swaps and nwindows = windows over all problems, window = W (at most 25 rows: the longest window whose
+ * transform lists cannot overflow), nlaunch_step = launches of the swap
+ * kernel (one per group), ms_iter = ms_total = device time of the kernels, ms_copy (host entry) the copies.
+ * Returns the first non-zero per-problem code, or a call-wide one: -1 ctx NULL; -2 n < 1; -3 p < 1; -4 T NULL;
+ * -5 Z NULL with wantZ; -6 orient; -7 schurindex strictly inside the period; -8 select NULL; -9 wr or wi NULL;
+ * -11 nb < 0; PSD_INFO_NOTIMPL on a period-sharded context; PSD_INFO_RUNTIME + k.  nb == 0 returns 0 and touches
+ * nothing. */
+int psd_d_ordschur_batch(psd_ctx* ctx, int nb, int n, int p, double* const* T, double* const* Z, char orient,
+                         int schurindex, const uint8_t* select, int wantZ, double* wr, double* wi, int* infos,
+                         int* nswaps, psd_stats* stats, int* info);
+/* Device-resident variant: dT, dZ device [nb][p][n][n] column-major blocks in user order (what psd_d_pschur_batch_dev
+ * leaves), reordered in place; select, wr, wi, infos and nswaps are host arrays.  The blocks are brought to the order
+ * the swap kernels work on and back on the device: nothing for 'R' with schurindex 1, block reversals in place for 'L'
+ * with schurindex p, a group of problems at a time through a temporary for the two shifted alignments (a group that
+ * fits the free device memory, as above). */
+int psd_d_ordschur_batch_dev(psd_ctx* ctx, int nb, int n, int p, void* dT, void* dZ, char orient, int schurindex,
+                             const uint8_t* select, int wantZ, double* wr, double* wi, int* infos, int* nswaps,
+                             psd_stats* stats, int* info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,7 +24,7 @@ import PeriodicSchurDecompositions: pschur!, pschur, phessenberg!, gpschur, Peri
 const PSD = PeriodicSchurDecompositions
 using ArnoldiMethod: ArnoldiMethod
 
-export set_train!, engine_version, pschur_batch!, pschur_batch, eigvecs_batch_device
+export set_train!, engine_version, pschur_batch!, pschur_batch, eigvecs_batch_device, ordschur_batch!
 
 const libpsd = get(ENV, "LIBPSD_MI355X", joinpath(@__DIR__, "..", "periodicschurdecompositions.jl_amd", "libpsd_mi355x.so"))
 
@@ -179,6 +179,51 @@ function pschur_batch!(problems::Vector{Vector{Matrix{Float64}}}, lr::Symbol = :
 end
 pschur_batch(problems::AbstractVector, lr::Symbol = :R; kwargs...) =
     pschur_batch!([Matrix{Float64}[Matrix{Float64}(a) for a in A] for A in problems], lr; kwargs...)
+
+# ordschur_batch!(problems, select; wantZ, infos) — no reference equivalent: ordschur!(P, select; wantZ) (rordschur.jl:3-132)
+# for many small Float64 decompositions of equal order, period, orientation and schurindex (1 or p) in ONE call
+# (psd_d_ordschur_batch), the follow-up of pschur_batch!.  `select`: a Vector{Bool} used for every problem or one per
+# problem; one member of a conjugate pair takes its partner along.  Works in place like ordschur! and returns the
+# problems with their values in the new order.  A problem whose swap is rejected ends alone, a consistent decomposition
+# with its old values: it throws like ordschur! after all have run, or with `infos` (a Vector{Cint} of length(problems))
+# the per-problem codes are stored there instead and nothing is thrown for it.
+function ordschur_batch!(problems::Vector{<:PeriodicSchur{Float64}}, select::AbstractVector; wantZ::Bool = true,
+                         infos::Union{Nothing, Vector{Cint}} = nothing)
+    nb = length(problems)
+    nb == 0 && return problems
+    ps1 = problems[1]
+    p = ps1.period; n = size(ps1.T1, 1); js = ps1.schurindex; orient = ps1.orientation
+    (js == 1 || js == p) || throw(ArgumentError("only implemented for schurindex in (1,p)"))     # rordschur.jl:25
+    wantZ = wantZ && all(ps -> !isempty(ps.Z) && size(ps.Z[1], 1) == n, problems)
+    sel = zeros(UInt8, n, nb)
+    for (q, ps) in enumerate(problems)
+        (ps.period == p && size(ps.T1, 1) == n && ps.schurindex == js && ps.orientation == orient) ||
+            throw(DimensionMismatch("the problems of a batch must have equal order, period, orientation and schurindex"))
+        sq = select[1] isa Bool ? select : select[q]
+        length(sq) == n || throw(DimensionMismatch("select must have one entry per eigenvalue"))
+        sel[:, q] .= UInt8.(sq)
+    end
+    # user order: T1 at schurindex, the others around it
+    T = reduce(vcat, [[j == js ? ps.T1 : ps.T[j < js ? j : j - 1] for j in 1:p] for ps in problems])
+    Z = wantZ ? reduce(vcat, [ps.Z for ps in problems]) : Matrix{Float64}[]
+    wr = zeros(n, nb); wi = zeros(n, nb)
+    codes = infos === nothing ? Vector{Cint}(undef, nb) : infos
+    length(codes) == nb || throw(DimensionMismatch("infos must have one entry per problem"))
+    info = Ref{Cint}(0)
+    Tp = _ptrs(T); Zp = _ptrs(Z)
+    GC.@preserve T Z sel wr wi codes begin
+        ccall((:psd_d_ordschur_batch, libpsd), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Cchar, Cint, Ptr{UInt8}, Cint,
+               Ptr{Float64}, Ptr{Float64}, Ptr{Cint}, Ptr{Cint}, Ptr{Cvoid}, Ref{Cint}),
+              ctx().ptr, nb, n, p, Tp, wantZ ? Zp : C_NULL, orient, js, sel, wantZ, wr, wi, codes, C_NULL, C_NULL, info)
+    end
+    (info[] < 0 || info[] >= INFO_NOTIMPL) && _throw(info[])                 # argument / runtime codes end the call
+    for (q, ps) in enumerate(problems)
+        codes[q] == 0 && (ps.values .= complex.(wr[:, q], wi[:, q]))
+    end
+    infos === nothing && foreach(_throw_ord, codes)
+    problems
+end
 
 # eigvecs_batch_device(problems, select; shifted) — no reference equivalent: eigvecs(ps, select; shifted) (vectors.jl:25-138)
 # by periodic back-substitution for many small Float64 decompositions of equal order, period, orientation and schurindex in

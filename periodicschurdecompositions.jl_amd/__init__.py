@@ -11,6 +11,7 @@ All numerical work happens in the HIP library.  There is no CPU fallback: if the
 missing or no GPU is visible, `Engine()` raises.
 """
 import collections
+import copy
 import ctypes as C
 import os
 
@@ -307,6 +308,10 @@ class Engine:
                                            dpp, dp, dp, ip, ip, C.POINTER(Stats), ip]
         lib.psd_d_pschur_batch_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_char, C.c_int,
                                                C.c_int, C.c_int, C.c_void_p, dp, dp, ip, ip, C.POINTER(Stats), ip]
+        for nm, mats in (("psd_d_ordschur_batch", dpp), ("psd_d_ordschur_batch_dev", C.c_void_p)):
+            if hasattr(lib, nm):  # (tools load builds of earlier commits to time their single calls)
+                getattr(lib, nm).argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, mats, mats, C.c_char, C.c_int,
+                                             C.POINTER(C.c_uint8), C.c_int, dp, dp, ip, ip, C.POINTER(Stats), ip]
         lib.psd_set_shard.argtypes = [C.c_void_p, C.c_int, C.c_int]
         lib.psd_shard_owned.argtypes = [C.c_void_p, C.c_int, C.c_char, u8p]
         for nm, dev in (("psd_d_partial_pschur", False), ("psd_z_partial_pschur", False),
@@ -1054,6 +1059,176 @@ class Engine:
         P.values = wr + 1j * wi
         P.stats = st
         return P
+
+    @staticmethod
+    def _raise_ord(iv):
+        """The per-problem codes of ordschur!: 3000 singular, 2000 + row ill-conditioned."""
+        if iv == 3000:
+            raise SingularException()
+        if 2000 <= iv < 3000:
+            raise IllConditionedException(iv - 2000)
+        Engine._raise(iv)
+
+    def _ord_batch_select(self, select, nb, n):
+        try:
+            return self._batch_select(select, nb, n)
+        except ValueError:
+            raise DimensionMismatch("select must be [nb][n] flags or one row of n: one entry per eigenvalue") from None
+
+    def ordschur_batch_(self, problems, *args, wantZ=True, infos_out=None, lr="R", schurindex=1):
+        """LinearAlgebra.ordschur!(P, select; wantZ) (src/rordschur.jl:3-132) for MANY small decompositions of one shape
+        in ONE call (psd_d_ordschur_batch): the follow-up of pschur_batch.  Float64, all-true signature.  Per problem
+        the result contract is that of `ordschur_`; a problem's result does not depend on its place in the batch.
+
+        ordschur_batch_(problems, select, wantZ=True, infos_out=None): `problems` a list of PeriodicSchur of equal order,
+        period, orientation and schurindex (1 or p) with writable Fortran-ordered factors; each is mutated (Ts, Z, values,
+        stats) and the list returned.  The `stats` of a problem are the call's, with `nsweeps` its own swap count; the
+        call's own are left in `self.ordschur_batch_stats` (nsweeps: all swaps, nlaunch_step: launches of the swap
+        kernel, one per group), the swap counts in `self.ordschur_batch_nswaps` ([nb]).
+        ordschur_batch_(T, Z, select, lr=..., schurindex=..., wantZ=True, infos_out=None): the torch outputs of the
+        device-resident pschur_batch_ ([nb, p, n, n] tensors; Z may be None with wantZ=False); returns (T, Z, values,
+        stats).  Tensors in the layout pschur_batch_ returns — a transposed view of contiguous column-major blocks,
+        float64 — are reordered IN PLACE without a copy, and the returned tensors share their storage; any other layout
+        is copied first and the inputs stay as they were.  With wantZ=False the Z that was passed (a tensor or None) is
+        returned as it is.  The `values` row of a failed problem is NaN.
+
+        `select`: [nb][n] flags, or one [n] row used for every problem; selecting one member of a conjugate pair takes
+        its partner along, per problem.  A problem whose swap is rejected (equal eigenvalues: SingularException, an
+        ill-conditioned swap: IllConditionedException) ends alone, a consistent decomposition with its old `values`;
+        the exception of the first such problem is raised after all have run — the others are complete then.
+        `infos_out`: a list that receives the per-problem codes instead (nothing is raised for a failed problem)."""
+        if hasattr(problems, "data_ptr"):
+            if len(args) != 2:
+                raise TypeError("ordschur_batch_(T, Z, select, lr=..., schurindex=...)")
+            return self._ordschur_batch_dev(problems, args[0], args[1], lr, schurindex, wantZ, infos_out)
+        if len(args) != 1:
+            raise TypeError("ordschur_batch_(problems, select, wantZ=True)")
+        problems = list(problems)
+        nb = len(problems)
+        if nb == 0:
+            if infos_out is not None:
+                infos_out[:] = []
+            self.ordschur_batch_stats = Stats()
+            self.ordschur_batch_nswaps = np.zeros(0, dtype=np.int32)
+            return []
+        n = p = None
+        Ts, Zs = [], []
+        for ps in problems:
+            if isinstance(ps, GeneralizedPeriodicSchur) and not all(ps.S):
+                raise NotImplementedPSD("ordschur_batch: signed GeneralizedPeriodicSchur (use ordschur_ per problem)")
+            if any(np.iscomplexobj(t) for t in ps.Ts) or any(np.iscomplexobj(z) for z in ps.Z):
+                raise NotImplementedPSD("ordschur_batch: Float64 only (use ordschur_ per problem for ComplexF64)")
+            nq = _check_square(ps.Ts)
+            if n is None:
+                n, p, orient, si = nq, len(ps.Ts), ps.orientation, ps.schurindex
+            if (nq != n or len(ps.Ts) != p or ps.orientation != orient or ps.schurindex != si
+                    or any(z.shape != (n, n) for z in ps.Z)):
+                raise DimensionMismatch("the problems of a batch must have equal order, period, orientation and schurindex")
+            Ts += list(ps.Ts)
+        if si not in (1, p):
+            raise ValueError("only implemented for schurindex in (1,p)")  # src/rordschur.jl:25
+        wantZ = bool(wantZ) and all(len(ps.Z) > 0 for ps in problems)
+        if wantZ:
+            for ps in problems:
+                if len(ps.Z) != p:
+                    raise DimensionMismatch("one Z per factor")
+                Zs += list(ps.Z)
+        sel = self._ord_batch_select(args[0], nb, n)
+        self._as_work(Ts)
+        self._as_work(Zs)
+        wr, wi = np.zeros((nb, n)), np.zeros((nb, n))
+        infos = (C.c_int * nb)()
+        nsw = (C.c_int * nb)()
+        st = Stats()
+        info = C.c_int(0)
+        dp = C.POINTER(C.c_double)
+        self.lib.psd_d_ordschur_batch(self.ctx, nb, n, p, self._ptrs(Ts), self._ptrs(Zs) if wantZ else None,
+                                      char_lr(orient).encode(), int(si), sel.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                      int(wantZ), wr.ctypes.data_as(dp), wi.ctypes.data_as(dp), infos, nsw, C.byref(st),
+                                      C.byref(info))
+        if info.value < 0 or info.value >= INFO_NOTIMPL:
+            self._raise(info.value)
+        self.ordschur_batch_stats = st
+        self.ordschur_batch_nswaps = np.array(list(nsw), dtype=np.int32)
+        for q, ps in enumerate(problems):
+            if infos[q] == 0:
+                ps.values = wr[q] + 1j * wi[q]
+            ps.stats = Stats.from_buffer_copy(st)
+            ps.stats.nsweeps = nsw[q]
+        if infos_out is not None:
+            infos_out[:] = [int(infos[q]) for q in range(nb)]
+            return problems
+        for q in range(nb):
+            self._raise_ord(infos[q])
+        return problems
+
+    def ordschur_batch(self, problems, *args, **kw):
+        """Copying form of ordschur_batch_: the decompositions are left untouched (device tensors are copied too)."""
+        if hasattr(problems, "data_ptr"):
+            Z = args[0] if len(args) > 0 else None
+            return self.ordschur_batch_(problems.clone(), Z.clone() if Z is not None else None, *args[1:], **kw)
+        work = []
+        for ps in problems:
+            if any(np.iscomplexobj(t) for t in ps.Ts):
+                raise NotImplementedPSD("ordschur_batch: Float64 only (use ordschur_ per problem for ComplexF64)")
+            cp = copy.copy(ps)
+            cp.Ts = [np.array(t, dtype=np.float64, order="F", copy=True) for t in ps.Ts]
+            cp.Z = [np.array(z, dtype=np.float64, order="F", copy=True) for z in ps.Z]
+            cp.values = np.array(ps.values, copy=True)
+            work.append(cp)
+        return self.ordschur_batch_(work, *args, **kw)
+
+    def _ordschur_batch_dev(self, T, Z, select, lr, schurindex, wantZ, infos_out):
+        import torch
+
+        wantZ = bool(wantZ) and Z is not None
+        if T.dim() != 4 or T.shape[2] != T.shape[3] or (Z is not None and Z.shape != T.shape):
+            raise DimensionMismatch("a device batch is [nb, p, n, n] tensors T and Z of square factors")
+        if T.is_complex() or (Z is not None and Z.is_complex()):
+            raise NotImplementedPSD("ordschur_batch: Float64 only (use ordschur_ per problem for ComplexF64)")
+        if not (T.is_cuda and (Z is None or Z.is_cuda)):
+            raise TypeError("device-resident ordschur_batch needs GPU tensors (use a list of PeriodicSchur for host input)")
+        nb, p, n = T.shape[0], T.shape[1], T.shape[2]
+        orient = char_lr(lr)
+        if schurindex not in (1, p):
+            raise ValueError("only implemented for schurindex in (1,p)")  # src/rordschur.jl:25
+        if nb == 0:
+            if infos_out is not None:
+                infos_out[:] = []
+            return T, Z, np.zeros((0, n), dtype=complex), Stats()
+        sel = self._ord_batch_select(select, nb, n)
+
+        def blocks(X):
+            # [nb][p][n][n] blocks of column-major matrices: the transpose of each factor, contiguous.  What
+            # pschur_batch_ returns is a view of exactly that: used as it is, in place
+            Xt = X.transpose(2, 3)
+            if X.dtype == torch.float64 and Xt.is_contiguous():
+                return Xt
+            return X.to(torch.float64).transpose(2, 3).contiguous()
+
+        dT = blocks(T)
+        dZ = blocks(Z) if wantZ else None
+        wr, wi = np.full((nb, n), np.nan), np.zeros((nb, n))
+        infos = (C.c_int * nb)()
+        nsw = (C.c_int * nb)()
+        st = Stats()
+        info = C.c_int(0)
+        dp = C.POINTER(C.c_double)
+        torch.cuda.synchronize(T.device)
+        self.lib.psd_d_ordschur_batch_dev(self.ctx, nb, n, p, C.c_void_p(dT.data_ptr()),
+                                          C.c_void_p(dZ.data_ptr()) if wantZ else None, orient.encode(), int(schurindex),
+                                          sel.ctypes.data_as(C.POINTER(C.c_uint8)), int(wantZ), wr.ctypes.data_as(dp),
+                                          wi.ctypes.data_as(dp), infos, nsw, C.byref(st), C.byref(info))
+        if info.value < 0 or info.value >= INFO_NOTIMPL:
+            self._raise(info.value)
+        self.ordschur_batch_stats = st
+        self.ordschur_batch_nswaps = np.array(list(nsw), dtype=np.int32)
+        if infos_out is not None:
+            infos_out[:] = [int(infos[q]) for q in range(nb)]
+        else:
+            for q in range(nb):
+                self._raise_ord(infos[q])
+        return dT.transpose(2, 3), (dZ.transpose(2, 3) if wantZ else Z), wr + 1j * wi, st
 
     def eigvecs(self, ps0, select, shifted=True, method="ordschur"):
         """LinearAlgebra.eigvecs(ps::PeriodicSchur, select; shifted) — src/vectors.jl:25-138: selected right

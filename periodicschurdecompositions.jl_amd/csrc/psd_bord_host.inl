@@ -1,0 +1,328 @@
+// Host drivers of psd_d_ordschur_batch / psd_d_ordschur_batch_dev (psd_bord.h): ordschur!(P, select) for nb periodic Schur
+// forms of one shape, as psd_d_pschur_batch leaves them.  Included at the end of psd_engine.cpp behind psd_batch_host.inl
+// (psd_batchbuf, batch_group, batch_buffers).
+//
+// Per group of problems: the selections go up once, then psd_bord — every problem's whole reordering in one launch —,
+// psd_bord_values and psd_bord_cleanup, and one read-back of the per-problem states, codes and eigenvalues.  Orders above
+// PSD_BORD_NMAX, and periods whose narrowest window does not fit the LDS, run rordschur_dev problem by problem on the
+// slices of the batch buffers.
+
+namespace {
+
+// Window of the batched kernel: the smallest candidate of choose_window_rord's list that holds the whole problem if its
+// LDS fits, otherwise the widest that fits (0: none), and no wider than the longest span psd_bord gives a window
+// (PSD_BORD_SPAN1: the LDS of rows that no window reaches would only keep other problems off the CU); PSD_BORD_W
+// narrows it
+int bord_window(const psd_ctx* c, int n, int p) {
+    const int cand[] = {32, 24, 20, 16, 12, 10, 8, 6};
+    int W = 0;
+    for (int w : cand) {
+        if (rord_lds_bytes(p, w) > 155 * 1024) continue;
+        if (W == 0) W = w;              // the widest that fits
+        if (w >= n) W = w;              // ... or a narrower one that still holds the problem
+    }
+    if (W > PSD_BORD_SPAN1) W = PSD_BORD_SPAN1;
+    if (W != 0 && c->bord_w >= 6 && c->bord_w < W) W = c->bord_w;
+    return W;
+}
+
+// device workspace of one problem besides its factors
+size_t bord_ws_bytes(int n, int p) {
+    return sizeof(psd_rostate) + sizeof(psd_apply_desc) + sizeof(psd_tq) * (size_t)p * PSD_RORD_CAP + sizeof(int) * (size_t)(p + 1) +
+           (size_t)n + sizeof(double) * (2 * (size_t)n + 8 * (size_t)n * p);
+}
+
+struct bord_ws {
+    psd_batchbuf st, desc, tq, cnt, sel, wr, wi, xscr, infos;
+    int alloc(int g, int n, int p) {
+        PSD_CHECK(st.alloc(sizeof(psd_rostate) * (size_t)g));
+        PSD_CHECK(desc.alloc(sizeof(psd_apply_desc) * (size_t)g));
+        PSD_CHECK(tq.alloc(sizeof(psd_tq) * (size_t)g * p * PSD_RORD_CAP));
+        PSD_CHECK(cnt.alloc(sizeof(int) * (size_t)g * p));
+        PSD_CHECK(sel.alloc((size_t)g * n));
+        PSD_CHECK(wr.alloc(sizeof(double) * (size_t)g * n));
+        PSD_CHECK(wi.alloc(sizeof(double) * (size_t)g * n));
+        PSD_CHECK(xscr.alloc(sizeof(double) * 8 * (size_t)g * n * p));
+        PSD_CHECK(infos.alloc(sizeof(int) * (size_t)g));
+        return 0;
+    }
+};
+
+bool bord_fallback(const psd_ctx* c, int n, int p) { return n > c->bord_nmax || bord_window(c, n, p) == 0; }
+
+// gc problems resident on the device in the internal order (dH, dZ [gc][p][n][n]); select, wr, wi, infos, nswaps: the
+// host rows of these problems.  wr / wi of a problem whose code is non-zero are not written.  Adds to s.
+int bord_group(psd_ctx* c, int gc, int n, int p, double* dH, double* dZ, const uint8_t* select, int wantZ, double* wr,
+               double* wi, int* infos, int* nswaps, psd_stats* s, bord_ws& ws) {
+    const size_t nn = (size_t)n * n;
+    if (bord_fallback(c, n, p)) {
+        int rc = c->reserve(n, p, false, 16);
+        if (rc != 0) return rc;
+        std::vector<double> lr(n), li(n);
+        for (int q = 0; q < gc; ++q) {
+            psd_stats ps;
+            memset(&ps, 0, sizeof(ps));
+            int pinfo = 0;
+            rc = rordschur_dev(c, n, p, dH + (size_t)q * p * nn, wantZ ? dZ + (size_t)q * p * nn : nullptr,
+                               select + (size_t)q * n, wantZ, lr.data(), li.data(), &ps, &pinfo);
+            if (batch_fatal(rc)) return rc;
+            infos[q] = rc;
+            if (nswaps) nswaps[q] = ps.nsweeps;
+            if (rc == 0) {
+                memcpy(wr + (size_t)q * n, lr.data(), sizeof(double) * n);
+                memcpy(wi + (size_t)q * n, li.data(), sizeof(double) * n);
+            }
+            s->nsweeps += ps.nsweeps;
+            s->nwindows += ps.nwindows;
+            s->nlaunch_step += ps.nlaunch_step;
+            s->window = ps.window;
+            s->ms_iter += ps.ms_iter;
+            s->ms_total += ps.ms_total;
+        }
+        return 0;
+    }
+    const int W = bord_window(c, n, p);
+    const size_t lds = rord_lds_bytes(p, W);
+#ifndef PSD_HOSTSIM
+    if (lds > c->bord_lds_set) {
+        PSD_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(psd_bord), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)lds));
+        c->bord_lds_set = lds;
+    }
+#endif
+    PSD_CHECK(psd_rt_h2d(ws.sel.ptr, select, (size_t)gc * n, c->stream));
+    psd_bord_args a;
+    a.H = dH;
+    a.Z = wantZ ? dZ : nullptr;
+    a.st = (psd_rostate*)ws.st.ptr;
+    a.desc = (psd_apply_desc*)ws.desc.ptr;
+    a.tq = (psd_tq*)ws.tq.ptr;
+    a.cnt = (int*)ws.cnt.ptr;
+    a.select = (const unsigned char*)ws.sel.ptr;
+    a.wr = ws.wr.d();
+    a.wi = ws.wi.d();
+    a.xscr = ws.xscr.d();
+    a.infos = (int*)ws.infos.ptr;
+    a.n = n; a.p = p; a.wantZ = wantZ; a.W = W;
+    a.maxwin = 2 * n * (n + 2) + 1024;  // (a block moves up by a row or more per window, and at most n blocks move)
+    Timer t;
+    t.start(c->stream);
+    PSD_LAUNCH(psd_bord, psd_dim3(gc), PSD_STEP_NT, lds, c->stream, a);
+    PSD_LAUNCH(psd_bord_values, psd_dim3((n + 63) / 64, gc), 64, 0, c->stream, a);
+    PSD_LAUNCH(psd_bord_cleanup, psd_dim3(n, gc), 64, 0, c->stream, a);
+    const double ms = t.stop(c->stream);
+    std::vector<psd_rostate> hst(gc);
+    std::vector<double> hw(2 * (size_t)gc * n);
+    PSD_CHECK(psd_rt_d2h(hst.data(), ws.st.ptr, sizeof(psd_rostate) * (size_t)gc, c->stream));
+    PSD_CHECK(psd_rt_d2h(hw.data(), ws.wr.ptr, sizeof(double) * (size_t)gc * n, c->stream));
+    PSD_CHECK(psd_rt_d2h(hw.data() + (size_t)gc * n, ws.wi.ptr, sizeof(double) * (size_t)gc * n, c->stream));
+    PSD_CHECK(psd_rt_sync(c->stream));
+    PSD_CHECK(psd_rt_last_error());
+    for (int q = 0; q < gc; ++q) {
+        if (hst[q].info == PSD_LIST_OVERFLOW) return PSD_INFO_RUNTIME + 77;
+        infos[q] = hst[q].info;  // 0, 2000 + row (IllConditionedException), 3000 (SingularException)
+        if (nswaps) nswaps[q] = hst[q].nswaps;
+        if (hst[q].info == 0) {
+            memcpy(wr + (size_t)q * n, hw.data() + (size_t)q * n, sizeof(double) * n);
+            memcpy(wi + (size_t)q * n, hw.data() + ((size_t)gc + q) * n, sizeof(double) * n);
+        }
+        s->nsweeps += hst[q].nswaps;
+        s->nwindows += hst[q].nwindows;
+    }
+    s->nlaunch_step += 1;
+    s->window = W;
+    s->ms_iter += ms;
+    s->ms_total += ms;
+    return 0;
+}
+
+int bord_checked(psd_ctx* c, int nb, int n, int p, const void* T, const void* Z, char orient, int schurindex,
+                 const uint8_t* select, int wantZ, const double* wr, const double* wi, std::vector<int>& slotA,
+                 std::vector<int>& slotZ) {
+    if (!c) return -1;
+    if (n < 1) return -2;
+    if (p < 1) return -3;
+    if (nb < 0) return -11;
+    if (nb == 0) return 0;
+    if (!T) return -4;
+    if (wantZ && !Z) return -5;
+    if (orient != 'R' && orient != 'L') return -6;
+    if (!ord_slots(orient, schurindex, p, slotA, slotZ)) return -7;  // rordschur.jl:25
+    if (!select) return -8;
+    if (!wr || !wi) return -9;
+    if (c->shard_world > 1) return PSD_INFO_NOTIMPL;  // (a period-sharded context keeps a slice of Z: single problems only)
+    return 0;
+}
+
+bool bord_identity(const std::vector<int>& slot) {
+    for (size_t j = 0; j < slot.size(); ++j)
+        if (slot[j] != (int)j) return false;
+    return true;
+}
+// slot is the reversal of the cnt blocks from `first` on and the identity before them
+bool bord_reversal(const std::vector<int>& slot, int first) {
+    const int p = (int)slot.size();
+    for (int j = 0; j < p; ++j)
+        if (slot[j] != (j < first ? j : p - 1 - (j - first))) return false;
+    return true;
+}
+
+// The [nb][p] blocks of X between the user order and the internal order, in place where the permutation is its own
+// inverse (the reversals of psd_d_pschur_batch's 'L' results: psd_breverse_blocks), otherwise gt problems at a time
+// through tmp [gt][p][nn] (gt == 0: not allocated yet; a group that fits the free memory, halved until it does)
+int bord_permute_dev(psd_ctx* c, int nb, int p, size_t nn, double* X, const std::vector<int>& slot, int first, bool to_internal,
+                     psd_batchbuf& tmp, int& gt, psd_batchbuf& dslot) {
+    if (bord_identity(slot)) return 0;
+    if (bord_reversal(slot, first)) {
+        const int cnt = p - first;
+        if (cnt >= 2) PSD_LAUNCH(psd_breverse_blocks, psd_dim3(nb * (cnt / 2)), PSD_HESS_NT, 0, c->stream, X, nn, p, first, cnt);
+        return 0;
+    }
+    const size_t per = sizeof(double) * nn * p;
+    if (gt == 0) {
+        gt = batch_group(c, nb, per);
+        for (;;) {
+            const int rc = tmp.alloc(per * gt);
+            if (rc == 0) break;
+            (void)psd_rt_last_error();
+            if (gt == 1) {
+                gt = 0;
+                return rc;
+            }
+            gt = (gt + 1) / 2;
+        }
+    }
+    PSD_CHECK(dslot.alloc(sizeof(int) * (size_t)p));
+    PSD_CHECK(psd_rt_h2d(dslot.ptr, slot.data(), sizeof(int) * (size_t)p, c->stream));
+    for (int q0 = 0; q0 < nb; q0 += gt) {
+        const int gc = (nb - q0 < gt) ? (nb - q0) : gt;
+        double* Xg = X + (size_t)q0 * p * nn;
+        PSD_LAUNCH(psd_bord_permute, psd_dim3(gc * p), PSD_HESS_NT, 0, c->stream, tmp.d(), (const double*)Xg,
+                   (const int*)dslot.ptr, nn, p, to_internal ? 1 : 0);
+        PSD_CHECK(psd_rt_d2d(Xg, tmp.d(), per * gc, c->stream));
+    }
+    PSD_CHECK(psd_rt_sync(c->stream));  // (dslot is reused)
+    return 0;
+}
+
+int bord_first_code(int nb, const int* infos) {
+    for (int q = 0; q < nb; ++q)
+        if (infos[q] != 0) return infos[q];
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int psd_d_ordschur_batch_dev(psd_ctx* c, int nb, int n, int p, void* dT, void* dZ, char orient, int schurindex,
+                             const uint8_t* select, int wantZ, double* wr, double* wi, int* infos, int* nswaps,
+                             psd_stats* stats, int* info) {
+    int dummy;
+    if (!info) info = &dummy;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    std::vector<int> slotA, slotZ;
+    if ((*info = bord_checked(c, nb, n, p, dT, dZ, orient, schurindex, select, wantZ, wr, wi, slotA, slotZ)) != 0 || nb == 0)
+        return *info;
+    const size_t nn = (size_t)n * n;
+    psd_stats local;
+    memset(&local, 0, sizeof(local));
+    psd_stats* s = stats ? stats : &local;
+    std::vector<int> linfo(infos ? 0 : nb, 0);
+    int* pinfos = infos ? infos : linfo.data();
+    double* H = (double*)dT;
+    double* Z = wantZ ? (double*)dZ : nullptr;
+    // the workspace of a group; the factors stay where they are
+    int g = batch_group(c, nb, bord_ws_bytes(n, p));
+    bord_ws ws;
+    if (!bord_fallback(c, n, p)) {
+        for (;;) {
+            const int rc = ws.alloc(g, n, p);
+            if (rc == 0) break;
+            (void)psd_rt_last_error();
+            if (g == 1) return *info = rc;
+            g = (g + 1) / 2;
+        }
+    }
+    psd_batchbuf tmp, dslot;
+    int gt = 0;
+    const int firstZ = (slotZ[0] == 0) ? 1 : 0;
+    if ((*info = bord_permute_dev(c, nb, p, nn, H, slotA, 0, true, tmp, gt, dslot)) != 0) return *info;
+    if (Z && (*info = bord_permute_dev(c, nb, p, nn, Z, slotZ, firstZ, true, tmp, gt, dslot)) != 0) return *info;
+    int fatal = 0;
+    for (int q0 = 0; q0 < nb && fatal == 0; q0 += g) {
+        const int gc = (nb - q0 < g) ? (nb - q0) : g;
+        fatal = bord_group(c, gc, n, p, H + (size_t)q0 * p * nn, Z ? Z + (size_t)q0 * p * nn : nullptr,
+                           select + (size_t)q0 * n, wantZ, wr + (size_t)q0 * n, wi + (size_t)q0 * n, pinfos + q0,
+                           nswaps ? nswaps + q0 : nullptr, s, ws);
+    }
+    // back to the user order, also behind a runtime failure: the caller's blocks keep their places
+    int rc = bord_permute_dev(c, nb, p, nn, H, slotA, 0, false, tmp, gt, dslot);
+    if (rc == 0 && Z) rc = bord_permute_dev(c, nb, p, nn, Z, slotZ, firstZ, false, tmp, gt, dslot);
+    if (rc == 0) rc = psd_rt_sync(c->stream) != 0 ? PSD_INFO_RUNTIME + 1 : 0;
+    if (fatal != 0) return *info = fatal;
+    if (rc != 0) return *info = rc;
+    return *info = bord_first_code(nb, pinfos);
+}
+
+int psd_d_ordschur_batch(psd_ctx* c, int nb, int n, int p, double* const* T, double* const* Z, char orient, int schurindex,
+                         const uint8_t* select, int wantZ, double* wr, double* wi, int* infos, int* nswaps, psd_stats* stats,
+                         int* info) {
+    int dummy;
+    if (!info) info = &dummy;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    std::vector<int> slotA, slotZ;
+    if ((*info = bord_checked(c, nb, n, p, T, Z, orient, schurindex, select, wantZ, wr, wi, slotA, slotZ)) != 0 || nb == 0)
+        return *info;
+    const size_t nn = (size_t)n * n;
+    const int nz = wantZ ? 2 : 1;
+    int g = batch_group(c, nb, sizeof(double) * nz * nn * p + bord_ws_bytes(n, p));
+    psd_batchbuf dbuf[2];
+    psd_hostbuf hst;
+    if ((*info = batch_buffers(g, nn * p, nz, dbuf, hst)) != 0) return *info;
+    bord_ws ws;
+    if (!bord_fallback(c, n, p) && (*info = ws.alloc(g, n, p)) != 0) return *info;
+    psd_stats local;
+    memset(&local, 0, sizeof(local));
+    psd_stats* s = stats ? stats : &local;
+    std::vector<int> linfo(infos ? 0 : nb, 0);
+    int* pinfos = infos ? infos : linfo.data();
+    Timer tc;
+    // user slot <-> internal slot on the way through the staging buffer, as psd_d_ordschur copies
+    auto copy = [&](double* const* M, const std::vector<int>& slot, int q0, int gc, double* dev, bool up) -> int {
+        if (!up) {
+            PSD_CHECK(psd_rt_d2h(hst.d(), dev, sizeof(double) * nn * p * gc, c->stream));
+            PSD_CHECK(psd_rt_sync(c->stream));
+        }
+        for (int q = 0; q < gc; ++q)
+            for (int j = 0; j < p; ++j) {
+                double* h = hst.d() + ((size_t)q * p + j) * nn;
+                double* u = M[(size_t)(q0 + q) * p + slot[j]];
+                if (up) memcpy(h, u, nn * sizeof(double));
+                else memcpy(u, h, nn * sizeof(double));
+            }
+        if (up) {
+            PSD_CHECK(psd_rt_h2d(dev, hst.d(), sizeof(double) * nn * p * gc, c->stream));
+            PSD_CHECK(psd_rt_sync(c->stream));  // (the staging buffer is reused)
+        }
+        return 0;
+    };
+    for (int q0 = 0; q0 < nb; q0 += g) {
+        const int gc = (nb - q0 < g) ? (nb - q0) : g;
+        tc.start(c->stream);
+        if ((*info = copy(T, slotA, q0, gc, dbuf[0].d(), true)) != 0) return *info;
+        if (wantZ && (*info = copy(Z, slotZ, q0, gc, dbuf[1].d(), true)) != 0) return *info;
+        double ms_copy = tc.stop(c->stream);
+        *info = bord_group(c, gc, n, p, dbuf[0].d(), wantZ ? dbuf[1].d() : nullptr, select + (size_t)q0 * n, wantZ,
+                           wr + (size_t)q0 * n, wi + (size_t)q0 * n, pinfos + q0, nswaps ? nswaps + q0 : nullptr, s, ws);
+        if (*info != 0) return *info;
+        tc.start(c->stream);
+        if ((*info = copy(T, slotA, q0, gc, dbuf[0].d(), false)) != 0) return *info;
+        if (wantZ && (*info = copy(Z, slotZ, q0, gc, dbuf[1].d(), false)) != 0) return *info;
+        ms_copy += tc.stop(c->stream);
+        s->ms_copy += ms_copy;
+    }
+    return *info = bord_first_code(nb, pinfos);
+}
+
+}  // extern "C"

@@ -1196,26 +1196,12 @@ PSD_D void psd_rord_move(const psd_roparams& P, psd_rostate& st, double* ldsd, d
     }
 }
 
-PSD_KERNEL_B(PSD_STEP_NT) psd_rord_step(psd_roparams P) {
-    PSD_LDS_DECL;
-    psd_rostate st = *P.st;
-    PSD_ONE { P.desc->active = 0; }
-    if (st.phase == PSD_ROPH_DONE) return;
-    const int n = st.n, p = st.p;
-    long long cyc[6] = {0, 0, 0, 0, 0, 0};
-    const long long tk0 = psd_clock(), tw0 = psd_wallclock();
+// The driver scan (rordschur.jl:77-110) from row st.j + 1 on: runs until the next selected block that has to move is found
+// (st.phase becomes PSD_ROPH_MOVE with the _moveblock! prologue done) or the rows are exhausted (PSD_ROPH_DONE).  Every
+// lane runs it on its own copy of the state.  Shared by psd_rord_step and the batched psd_bord (psd_bord.h).
+PSD_D void psd_rord_scan(const psd_roparams& P, psd_rostate& st) {
+    const int n = st.n;
     const psd_mat<double> A1 = psd_mat<double>{P.H, n};
-    double* ldsd = (double*)psd_lds;
-    const size_t winb = (size_t)p * st.W * (st.W + 1);
-    double* scr = ldsd + winb;
-    double* wk = scr + (size_t)p * PSD_RORD_SCR;
-    double* flagbuf = wk + (size_t)p * 52;
-    double* ws = flagbuf + 4;
-    int* lcnt = (int*)(ws + 192 + psd_rord_tree_doubles(p));
-    unsigned char* SL = (unsigned char*)(lcnt + p);  // signature of the left-oriented sequence X_l = T_{sigma(l)}
-    PSD_PAR_FOR(t, p) { SL[t] = psd_rosig(P, psd_ord_sigma(p, t + 1)) ? 1 : 0; }
-    PSD_SYNC();
-    // driver scan: rordschur.jl:77-110
     while (st.phase == PSD_ROPH_SCAN) {
         st.j += 1;
         if (st.j > n) {
@@ -1257,6 +1243,27 @@ PSD_KERNEL_B(PSD_STEP_NT) psd_rord_step(psd_roparams P) {
             }
         }
     }
+}
+
+PSD_KERNEL_B(PSD_STEP_NT) psd_rord_step(psd_roparams P) {
+    PSD_LDS_DECL;
+    psd_rostate st = *P.st;
+    PSD_ONE { P.desc->active = 0; }
+    if (st.phase == PSD_ROPH_DONE) return;
+    const int p = st.p;
+    long long cyc[6] = {0, 0, 0, 0, 0, 0};
+    const long long tk0 = psd_clock(), tw0 = psd_wallclock();
+    double* ldsd = (double*)psd_lds;
+    const size_t winb = (size_t)p * st.W * (st.W + 1);
+    double* scr = ldsd + winb;
+    double* wk = scr + (size_t)p * PSD_RORD_SCR;
+    double* flagbuf = wk + (size_t)p * 52;
+    double* ws = flagbuf + 4;
+    int* lcnt = (int*)(ws + 192 + psd_rord_tree_doubles(p));
+    unsigned char* SL = (unsigned char*)(lcnt + p);  // signature of the left-oriented sequence X_l = T_{sigma(l)}
+    PSD_PAR_FOR(t, p) { SL[t] = psd_rosig(P, psd_ord_sigma(p, t + 1)) ? 1 : 0; }
+    PSD_SYNC();
+    psd_rord_scan(P, st);
     if (st.phase == PSD_ROPH_MOVE) psd_rord_move(P, st, ldsd, scr, wk, flagbuf, ws, lcnt, SL, cyc);
     cyc[0] = psd_clock() - tk0;
     cyc[5] = psd_wallclock() - tw0;
@@ -1821,41 +1828,44 @@ PSD_D void psd_rord_eigpair(const psd_roparams& P, int n, int p, int j, psd_z* X
     l2i = alpha[1].im * exp2(scal[1]);
 }
 
-// ordschur.jl:122-204 _updateλ! (real): one thread per position j
-PSD_KERNEL psd_rord_values(psd_roparams P, int n, int p) {
-    const int NT = PSD_NTHREADS;
+// ordschur.jl:122-204 _updateλ! (real) for position j of one problem (shared with psd_bord_values, psd_bord.h)
+PSD_D void psd_rord_value_at(const psd_roparams& P, int n, int p, int j) {
     const psd_mat<double> A1 = psd_mat<double>{P.H, n};
-    PSD_PAR_FOR(t, NT) {
-        const int j = 1 + PSD_BLOCK_X * NT + t;
-        if (j <= n) {
-            const bool second = (j > 1) && (A1(j, j - 1) != 0);
-            const bool first = (j < n) && (A1(j + 1, j) != 0);
-            if (first && !second) {
-                double a, b, c, d;
-                psd_rord_eigpair(P, n, p, j, (psd_z*)(P.xscr + (size_t)(j - 1) * p * 8), a, b, c, d);
-                P.wr[j - 1] = a; P.wi[j - 1] = b;
-                P.wr[j] = c; P.wi[j] = d;
-            } else if (!second) {
-                double v = A1(j, j);
-                int sc = 0;
-                for (int l = 2; l <= p; ++l) {
-                    v *= P.H[(size_t)(l - 1) * n * n + (size_t)(j - 1) * n + (j - 1)];
-                    if (v != 0) {
-                        int e;
-                        v = frexp(v, &e);
-                        sc += e;
-                    }
-                }
-                P.wr[j - 1] = ldexp(v, sc);
-                P.wi[j - 1] = 0.0;
+    const bool second = (j > 1) && (A1(j, j - 1) != 0);
+    const bool first = (j < n) && (A1(j + 1, j) != 0);
+    if (first && !second) {
+        double a, b, c, d;
+        psd_rord_eigpair(P, n, p, j, (psd_z*)(P.xscr + (size_t)(j - 1) * p * 8), a, b, c, d);
+        P.wr[j - 1] = a; P.wi[j - 1] = b;
+        P.wr[j] = c; P.wi[j] = d;
+    } else if (!second) {
+        double v = A1(j, j);
+        int sc = 0;
+        for (int l = 2; l <= p; ++l) {
+            v *= P.H[(size_t)(l - 1) * n * n + (size_t)(j - 1) * n + (j - 1)];
+            if (v != 0) {
+                int e;
+                v = frexp(v, &e);
+                sc += e;
             }
         }
+        P.wr[j - 1] = ldexp(v, sc);
+        P.wi[j - 1] = 0.0;
     }
 }
 
-// rordschur.jl:117-130: zero everything below the (1x1 / 2x2) diagonal blocks of T_1.  grid over columns.
-PSD_KERNEL psd_rord_cleanup(psd_roparams P, int n) {
-    const int c = PSD_BLOCK_X + 1;
+// one thread per position j
+PSD_KERNEL psd_rord_values(psd_roparams P, int n, int p) {
+    const int NT = PSD_NTHREADS;
+    PSD_PAR_FOR(t, NT) {
+        const int j = 1 + PSD_BLOCK_X * NT + t;
+        if (j <= n) psd_rord_value_at(P, n, p, j);
+    }
+}
+
+// rordschur.jl:117-130: zero everything below the (1x1 / 2x2) diagonal blocks of T_1, column c of one problem (shared
+// with psd_bord_cleanup, psd_bord.h)
+PSD_D void psd_rord_cleanup_col(const psd_roparams& P, int n, int c) {
     const psd_mat<double> A1 = psd_mat<double>{P.H, n};
     // the pair's first eigenvalue has positive imaginary part (rpschur2x2.jl:263-266), the second negative
     const int j0 = (P.wi[c - 1] > 0.0) ? (c + 2) : (c + 1);
@@ -1864,3 +1874,6 @@ PSD_KERNEL psd_rord_cleanup(psd_roparams P, int n) {
         if (r <= n) A1(r, c) = 0.0;
     }
 }
+
+// grid over columns
+PSD_KERNEL psd_rord_cleanup(psd_roparams P, int n) { psd_rord_cleanup_col(P, n, PSD_BLOCK_X + 1); }
