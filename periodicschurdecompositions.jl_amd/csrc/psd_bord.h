@@ -18,6 +18,8 @@
 // a 1x1 or intact 2x2 block crosses at most W - 1 neighbours, the halves of a split pair two swaps per neighbour over
 // at most W - 2 rows.  These spans keep every window of the batched kernel inside the lists (psd_rord_move reads the
 // span from st.W; the LDS stays laid out for the launch's W, which the host keeps at or below PSD_BORD_SPAN1).
+// psd_rord_move bounds its span the same way for every caller (PSD_RORD_SPAN1 / PSD_RORD_SPAN2, psd_rord.h); the spans
+// here are at or below those, so the batched kernel's windows are what they were.
 #define PSD_BORD_SPAN1 (PSD_RORD_CAP + 1)
 #define PSD_BORD_SPAN2 (PSD_RORD_CAP / 2 + 2)
 

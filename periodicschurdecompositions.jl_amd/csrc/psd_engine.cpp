@@ -3205,7 +3205,8 @@ int rordschur_dev(psd_ctx* c, int n, int p, double* dH, double* dZ, const uint8_
         stats->nlaunch_step = (int32_t)launched;
         stats->window = W;
     }
-    return *info = hst.info;
+    // (a window that overran its transform lists — psd_rord_move lets none — is a runtime failure, as in the QR drivers)
+    return *info = (hst.info == PSD_LIST_OVERFLOW) ? (PSD_INFO_RUNTIME + 77) : hst.info;
 }
 
 }  // namespace

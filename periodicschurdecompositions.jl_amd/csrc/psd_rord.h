@@ -19,7 +19,14 @@
 #include "psd_zord.h"
 
 #define PSD_RORD_SCR 96    // doubles of per-factor swap scratch
-#define PSD_RORD_CAP 24    // block transforms per owner and window
+// Block transforms per owner and window.  Every swap records one transform per owner, so a window may make at most
+// PSD_RORD_CAP swaps.  psd_rord_move bounds that itself: its window spans PSD_RORD_SPAN1 rows while the travelling block
+// is whole (a 1x1 or an intact pair crosses at most span - 1 neighbours, one swap each) and PSD_RORD_SPAN2 rows once a
+// pair has split (its halves make at most two swaps per row crossed); a pair that splits inside a window ends it as
+// soon as the next block could not be crossed within the lists.  psd_list_overflow behind every window is the guard.
+#define PSD_RORD_CAP 24
+#define PSD_RORD_SPAN1 (PSD_RORD_CAP + 1)
+#define PSD_RORD_SPAN2 (PSD_RORD_CAP / 2 + 2)
 
 struct psd_tq {  // dense orthogonal block transform acting on indices pos..pos+m-1
     int pos, m;
@@ -1063,6 +1070,9 @@ PSD_D int psd_rord_swap(const psd_roparams& P, const psd_rostate& st, const psd_
         const double* Q = scr + (l - 1) * PSD_RORD_SCR + 64;
         psd_rord_win_apply(w, sg, own, i1, m, Q, psd_rosig(P, sg), psd_rosig(P, own));
         {
+            // psd_rord_move starts no swap that the lists do not hold.  Should a change of a span or of the capacity
+            // break that, the record stays inside the list (as psd_record's) and the count goes on: the guard behind
+            // the window (psd_list_overflow) then ends the call with PSD_LIST_OVERFLOW and nothing of the window is kept.
             const int q = lcnt[own - 1];
             PSD_SYNC();
             if (q < PSD_RORD_CAP) {
@@ -1100,14 +1110,17 @@ PSD_D void psd_rord_move(const psd_roparams& P, psd_rostate& st, double* ldsd, d
                          double* ws, int* lcnt, const unsigned char* SL, long long* cyc) {
     const int n = st.n, p = st.p;
     // window: bottom = end of the travelling block(s); top as high as the LDS window allows
+    // (the LDS is laid out for st.W; the rows the window spans are bounded by what its transform lists hold, PSD_RORD_CAP)
     const int width = st.splitsrc ? 2 : st.nbsrc;
+    const int span0 = st.splitsrc ? PSD_RORD_SPAN2 : PSD_RORD_SPAN1;
+    const int span = (st.W < span0) ? st.W : span0;
     psd_win w;
     w.b = ldsd;
     w.W = st.W;
     w.ld = st.W + 1;
     w.bsz = st.W * (st.W + 1);
     w.be = st.here + width - 1;
-    w.bs = (w.be - st.W + 1 > st.jtarget) ? (w.be - st.W + 1) : st.jtarget;
+    w.bs = (w.be - span + 1 > st.jtarget) ? (w.be - span + 1) : st.jtarget;
     PSD_PAR_FOR(m, p) { lcnt[m] = 0; }
     const long long tl0 = psd_clock();
     psd_win_load(P_as_r(P), w, n, p);
@@ -1115,6 +1128,7 @@ PSD_D void psd_rord_move(const psd_roparams& P, psd_rostate& st, double* ldsd, d
     int fail = 0;
     int here = st.here;
     const int top0 = here;
+    const int nsw0 = st.nswaps;  // (every swap records one transform per owner: st.nswaps - nsw0 is the length of the lists)
     // rordschur.jl:181-247 restricted to the blocks that fit the window
     while (here > st.jtarget && !fail) {
         if (st.pend1x1) {  // second 1x1 of a split pair follows its partner (rordschur.jl:207-215)
@@ -1132,6 +1146,12 @@ PSD_D void psd_rord_move(const psd_roparams& P, psd_rostate& st, double* ldsd, d
             break;  // the next block may start above the window (row jtarget itself is a block start)
         }
         if (here - nbnext < w.bs) break;
+        {   // swaps the next block may take: one under a whole block; under the halves of a split pair two for a 1x1
+            // and up to three for a pair (which may split under the first half).  A pair that split inside this window
+            // may stand in a span of PSD_RORD_SPAN1 rows: the window ends where the lists would not hold the next block.
+            const int need = !st.splitsrc ? 1 : ((nbnext == 1) ? 2 : 3);
+            if (st.nswaps - nsw0 + need > PSD_RORD_CAP) break;
+        }
         if (!st.splitsrc) {
             fail = psd_rord_swap(P, st, w, scr, wk, ws, flagbuf, lcnt, here - nbnext, nbnext, st.nbsrc, cyc, SL);
             if (fail) break;
@@ -1163,8 +1183,12 @@ PSD_D void psd_rord_move(const psd_roparams& P, psd_rostate& st, double* ldsd, d
             }
         }
     }
+    PSD_SYNC();
     if (fail) {
         st.info = (fail == 2) ? PSD_INFO_SINGULAR : (PSD_INFO_ILLCOND_BASE + st.jsrc0);
+        st.phase = PSD_ROPH_DONE;
+    } else if (psd_list_overflow(lcnt, p, PSD_RORD_CAP)) {  // never apply truncated lists: nothing of this window is stored
+        st.info = PSD_LIST_OVERFLOW;
         st.phase = PSD_ROPH_DONE;
     } else {
         const long long tl1 = psd_clock();
@@ -1293,7 +1317,7 @@ PSD_KERNEL_B(PSD_APPLY_NT) psd_rord_apply(psd_roparams P, int n, int p) {
     if (!d.active) return;
     const int m = PSD_BLOCK_Y + 1;
     const int role = PSD_BLOCK_Z;
-    const int cnt = P.cnt[m - 1] < PSD_RORD_CAP ? P.cnt[m - 1] : PSD_RORD_CAP;
+    const int cnt = P.cnt[m - 1];  // (<= PSD_RORD_CAP: a window that overran its lists leaves no active descriptor)
     if (cnt <= 0) return;
     const int T = PSD_APPLY_NT;
     const int S = d.phi - d.plo + 1;
@@ -1620,7 +1644,7 @@ PSD_KERNEL_B(PSD_APPLY_NT) psd_rord_apply_mb(psd_roparams P, int n, int p, int p
     const bool inpass0 = left || role == 2;
     if ((pass == 0) != inpass0) return;
     const int* pcnt = P.cnt + (size_t)slot * p;
-    const int cnt = pcnt[m - 1] < PSD_RORD_CAP ? pcnt[m - 1] : PSD_RORD_CAP;
+    const int cnt = pcnt[m - 1];  // (<= PSD_RORD_CAP, as in psd_rord_apply)
     if (cnt <= 0) return;
     const psd_tq* gtq = P.tq + ((size_t)slot * p + (m - 1)) * PSD_RORD_CAP;
     const int T = PSD_APPLY_NT;

@@ -1548,3 +1548,250 @@ def case_formq_blocked(make_engine, sizes):
             assert d < 50 * pt.EPS * np.sqrt(n), (n, p, j, d)
             orth = np.linalg.norm(pb.Z[j].T @ pb.Z[j] - np.eye(n))
             assert orth < 10 * pt.EPS * n, (n, p, j, orth)
+
+
+# ------------------------------------------------------------------------------------------------
+# ordschur! (real): a chosen block at a chosen distance from its target.  The window kernel (psd_rord_move) records one
+# block transform per owner and swap in lists of PSD_RORD_CAP = 24 entries, so the cases put 23, 24, 25, W - 2 .. W + 1
+# and 2 W - 1 rows between a selected block and the top, for every window width W the LDS formula (choose_window_rord)
+# returns up to p = 70.  The inputs are hand-built Schur forms (no pschur!): milliseconds each.
+# Not covered, and why.  (a) A target that is the second row of a pair (the `jd -= 1` prologue of _moveblock!): the driver
+# scan hands out targets that are one row behind the selected blocks already in place, always a block start, so no
+# selection reaches it; case_rordschur_span_targets has the nearest layouts.  (b) A travelling pair that splits (the
+# splitsrc / pend1x1 branches): a pair splits when a swap leaves an exact zero below its diagonal.  The family
+# rord_form(n, p, [r], tiny={r: c}) with (p, n, r) in (3, 20, 16), (16, 20, 16), (34, 18, 14), c in 1e-6, 1e-9, 1e-12,
+# 1e-15, 1e-17, 1e-300 and seeds 0..15 — 288 forms, the pair selected — gave none on the simulation (nsweeps == r every time).
+RORD_CAP = 24
+# p -> W = stats.window, one period per width (asserted by every case: a change of the LDS formula must not empty a case)
+RORD_P_W = [(3, 32), (16, 24), (26, 20), (34, 16), (44, 12), (52, 10), (60, 8), (70, 6)]
+
+
+def rord_form(n, p, pairs=(), lr="R", seed=1, tiny=None):
+    """A Float64 periodic Schur form built by hand and the factors it decomposes (Z = I, so A_k = T_k):
+    T_k = 0.3 triu(U(-1, 1)) with the diagonal 1 + 0.05 j (j = 0-based row) in every factor, so that the real eigenvalues
+    (1 + 0.05 j)^p are well separated.  `pairs`: 0-based first rows of conjugate pairs, shaped as pt.mkrps shapes them:
+    a standardised 2x2 in the quasi-triangular factor (equal diagonal d, off-diagonals -d c above and d c below), d I in
+    the others — eigenvalues d^p (1 +- i c), c = 1 (or `tiny[row]`: a pair a rounding error away from two real ones).
+    lr = "R": schurindex 1; "L": schurindex p (the alignments of pschur!)."""
+    import psd_amd
+
+    U = pt.rand_uniform_factors(n, p, 7700 + 13 * seed + n + 100 * p)
+    T = [np.asfortranarray(0.3 * np.triu(2.0 * u - 1.0)) for u in U]
+    lam = np.zeros(n, dtype=complex)
+    d = 1.0 + 0.05 * np.arange(n)
+    for k in range(p):
+        T[k][np.diag_indices(n)] = d
+    lam[:] = d ** p
+    for r in pairs:
+        c = 1.0 if tiny is None else tiny.get(r, 1.0)
+        for k in range(p):
+            T[k][r + 1, r + 1] = d[r]
+            T[k][r, r + 1] = 0.0
+        T[0][r, r + 1] = -d[r] * c
+        T[0][r + 1, r] = d[r] * c
+        lam[r] = d[r] ** p * (1 + 1j * c)
+        lam[r + 1] = d[r] ** p * (1 - 1j * c)
+    if lr == "L":  # the quasi-triangular factor last in the list, as pschur!(A, :L) and pt.mkrps leave it
+        Ts, si = T[1:] + [T[0]], p
+    else:
+        Ts, si = T, 1
+    A = [t.copy(order="F") for t in Ts]
+    for a in A:
+        a.setflags(write=False)
+    Z = [np.asfortranarray(np.eye(n)) for _ in range(p)]
+    return psd_amd.PeriodicSchur([t.copy(order="F") for t in Ts], Z, lam, lr, si), A
+
+
+def _rord_layout(kind, dist):
+    """(n, pairs, selected rows) of a layout in which the selected block has `dist` rows above it, all unselected:
+    kind[0]: the travelling block ("1" a 1x1, "2" an intact pair), kind[1]: its neighbours ("1": 1x1 blocks, "2": a run
+    of pairs, "s": the same run one row lower — a 1x1 at the top and, for the widths W with W - dist even, the window's
+    top row inside a neighbouring pair)."""
+    width = 2 if kind[0] == "2" else 1
+    n = dist + width
+    pairs = []
+    if kind[1] in "2s":
+        r = 1 if kind[1] == "s" else 0
+        while r + 1 < dist:
+            pairs.append(r)
+            r += 2
+    sel = [dist] + ([dist + 1] if width == 2 else [])
+    if width == 2:
+        pairs.append(dist)
+    return n, pairs, sel
+
+
+def rord_check(ps0, A, ps1, select, n, p, W):
+    """The assertions of a window-edge case, all against something other than the code under test."""
+    assert ps1.stats.window == W, (p, ps1.stats.window, W)
+    ok, err = pt.checkpsd(ps1, A, thresh=100 * np.sqrt(max(n / 32, 1)))
+    assert ok, (n, p, err.max())
+    lam0 = ps0.values
+    closed = np.array(select, dtype=bool).copy()  # (the selection is closed under conjugation)
+    for i in range(n - 1):
+        if lam0[i].imag > 0 and (closed[i] or closed[i + 1]):
+            closed[i] = closed[i + 1] = True
+    m = int(closed.sum())
+    sc = abs(lam0).max()
+    assert pt.match_eigs(lam0[closed], ps1.values[:m]) < 1e-8 * sc
+    assert pt.match_eigs(lam0[~closed], ps1.values[m:]) < 1e-8 * sc
+    for i in range(n - 1):  # structure: sub-diagonal entries only inside conjugate pairs
+        if ps1.values[i].imag == 0 or ps1.values[i].imag < 0:
+            assert ps1.T1[i + 1, i] == 0
+    po = pt.oracle_ordschur(pt.PSD(ps0.Ts, ps0.Z, lam0, ps0.orientation, ps0.schurindex), select)
+    assert po.info == 0 and ps1.stats.nsweeps == po.nswaps, (ps1.stats.nsweeps, po.nswaps)
+    if not np.any(lam0.imag != 0):  # all real: the order inside each group is the oracle's
+        assert np.allclose(ps1.values[:m], po.values[:m], rtol=1e-8, atol=0)
+        assert np.allclose(ps1.values[m:], po.values[m:], rtol=1e-8, atol=0)
+    return po
+
+
+def rord_distances(W, width=1, nmax=48):
+    return sorted({d for d in (RORD_CAP - 1, RORD_CAP, RORD_CAP + 1, W - 2, W - 1, W, W + 1, 2 * W - 1)
+                   if 1 <= d <= nmax - width})
+
+
+def case_rordschur_span(eng, p, W, kind, lr="R"):
+    """One block travels `dist` rows to the top, for every distance of rord_distances(W); wantZ = false gives the same T
+    and leaves Z alone at the longest of them."""
+    width = 2 if kind[0] == "2" else 1
+    dists = rord_distances(W, width)
+    for dist in dists:
+        n, pairs, sel = _rord_layout(kind, dist)
+        ps0, A = rord_form(n, p, pairs, lr)
+        select = np.zeros(n, dtype=bool)
+        select[sel] = True
+        ps1 = eng.ordschur_(_clone(ps0), select)
+        rord_check(ps0, A, ps1, select, n, p, W)
+        if dist == dists[-1]:
+            ps2 = eng.ordschur_(_clone(ps0), select, wantZ=False)
+            assert all(np.array_equal(a, b) for a, b in zip(ps2.Z, ps0.Z))
+            assert max(np.abs(a - b).max() for a, b in zip(ps2.Ts, ps1.Ts)) < 1e-12 * max(1.0, abs(ps0.values).max())
+
+
+def case_rordschur_span_targets(eng, p, W):
+    """Targets below the top: a selected pair already in place at rows 1:2 (the target of the next block is the row
+    behind a pair; the `jd -= 1` prologue of _moveblock! reads the sub-diagonal there), and an unselected pair at the
+    top with the target inside the window's first rows."""
+    for dist in rord_distances(W, 1, nmax=44):
+        for toppair_selected in (True, False):
+            n = dist + 4
+            pairs = [0, 3] if toppair_selected else [0]
+            ps0, A = rord_form(n, p, pairs, "R", seed=2)
+            select = np.zeros(n, dtype=bool)
+            select[n - 1] = True
+            if toppair_selected:
+                select[0] = True  # (one member: the partner comes along)
+            ps1 = eng.ordschur_(_clone(ps0), select)
+            rord_check(ps0, A, ps1, select, n, p, W)
+
+
+def case_rordschur_span_pipelined(make_engine, cases):
+    """Two and three selected blocks a few rows apart, each a full window or more from its target: the pipelined driver
+    has several slots under way.  Against the serial driver (equal swap counts, factors to the tolerance of
+    case_rordschur_pipelined) and the checks of rord_check."""
+    e_pipe = make_engine({"PSD_ORD_PIPE": "1"})
+    e_ser = make_engine({"PSD_ORD_PIPE": "0"})
+    for (p, W, n, pairs, sel, lr) in cases:
+        ps0, A = rord_form(n, p, pairs, lr, seed=3)
+        select = np.zeros(n, dtype=bool)
+        select[list(sel)] = True
+        ps1 = e_pipe.ordschur_(_clone(ps0), select)
+        ps2 = e_ser.ordschur_(_clone(ps0), select)
+        assert ps1.stats.nsweeps == ps2.stats.nsweeps > 0
+        for ps in (ps1, ps2):
+            rord_check(ps0, A, ps, select, n, p, W)
+        sc = abs(ps0.values).max()
+        assert pt.match_eigs(ps2.values, ps1.values) < 1e-9 * sc
+        assert np.allclose(ps1.values, ps2.values, rtol=1e-6, atol=1e-8 * sc)
+
+
+RORD_PIPE_CASES = [
+    # (p, W, n, pairs, selected rows, orientation)
+    (3, 32, 48, (), (40, 44), "R"),
+    (3, 32, 48, (), (33, 40, 47), "L"),
+    (3, 32, 48, (10, 20, 36, 44), (36, 40, 44), "R"),
+    (16, 24, 48, (), (30, 38, 46), "R"),
+    (16, 24, 46, (5, 12, 40), (33, 40, 45), "L"),
+    (34, 16, 40, (), (25, 32, 39), "R"),
+]
+
+
+# The other entry points of the same driver, on the shape that overran the lists: p = 3 (W = 32), n = 40, a 1x1 block
+# that crosses 31 rows in one window (and 25, one more than the lists hold).
+def case_gordschur_span(eng):
+    """Signed real reordering (psd_d_gordschur -> rordschur_dev with a signature): S = (+, -, +) and (+, +, -) in the
+    right orientation, hand-built as rord_form; residuals by pt.rgpschur_check, swaps and values against the oracle.
+    A conjugate pair in the last two rows (not moved) takes the call to the real driver: an all-real signed form goes
+    through the complex one."""
+    import psd_amd
+
+    n, p = 40, 3
+    for S in ([True, False, True], [True, True, False]):
+        for row in (25, 31):
+            ps, A = rord_form(n, p, (n - 2,), "R", seed=4)
+            lam = np.ones(n)
+            for l in range(p):
+                lam = lam * (np.diag(A[l]) if S[l] else 1.0 / np.diag(A[l]))
+            lam = lam.astype(complex)
+            lam[n - 2:] *= [1 + 1j, 1 - 1j]
+            mk = lambda cls: cls(S, [t.copy(order="F") for t in ps.Ts], [z.copy(order="F") for z in ps.Z], lam.copy(),
+                                 np.ones(n), np.zeros(n, dtype=np.int32), "R", 1)
+            select = np.zeros(n, dtype=bool)
+            select[row] = True
+            ps1 = eng.ordschur_(mk(psd_amd.GeneralizedPeriodicSchur), select)
+            assert ps1.stats.window == 32 and ps1.stats.nsweeps == row
+            pt.rgpschur_check(A, S, ps1, tol=100 * np.sqrt(n / 32), qtol=10)
+            assert np.isclose(ps1.values[0], lam[row], rtol=1e-8)
+            assert np.allclose(ps1.values[1:row + 1], lam[:row], rtol=1e-8) and np.allclose(ps1.values[row + 1:], lam[row + 1:], rtol=1e-8)
+            po = pt.oracle_gordschur(mk(pt.GPSD), select)
+            assert po.info == 0 and po.nswaps == ps1.stats.nsweeps
+            assert pt.match_eigs(po.values, ps1.values) < 1e-9 * abs(po.values).max()
+
+
+def case_ordschur_batch_span(eng):
+    """psd_d_ordschur_batch on the same move.  n = 32 inside the batched kernel: its windows span PSD_BORD_SPAN1 = 25
+    rows, so the 31 rows take two windows; n = 130 (just above PSD_BORD_NMAX = 128) takes the single driver problem by
+    problem, at W = 32."""
+    p = 3
+    for (n, rows, window, nwin) in ((32, (31, 25), RORD_CAP + 1, (2, 2)), (130, (31, 56), 32, None)):
+        made = [rord_form(n, p, (), "R", seed=5 + q) for q in range(len(rows))]
+        sels = np.zeros((len(rows), n), dtype=bool)
+        for q, r in enumerate(rows):
+            sels[q, r] = True
+        out = eng.ordschur_batch_([_clone(ps0) for ps0, _ in made], sels)
+        st = eng.ordschur_batch_stats
+        assert st.window == window, st.window
+        if nwin is not None:
+            assert st.nlaunch_step == 1 and st.nwindows == sum(nwin)
+        else:
+            assert st.nlaunch_step > 1  # the single driver's launches
+        for q, (ps0, A) in enumerate(made):
+            assert out[q].stats.nsweeps == rows[q]
+            out[q].stats.window = window  # (a problem carries the call's stats)
+            rord_check(ps0, A, out[q], sels[q], n, p, window)
+
+
+def case_rordschur_span_capi(eng):
+    """One call of psd_d_ordschur through the C ABI on the same move: info and return value 0, swap count, factors."""
+    import ctypes as C
+
+    import psd_amd
+
+    n, p, row = 40, 3, 31
+    ps0, A = rord_form(n, p, (), "R", seed=6)
+    w = _clone(ps0)
+    sel = (C.c_uint8 * n)(*[1 if j == row else 0 for j in range(n)])
+    wr, wi = np.zeros(n), np.zeros(n)
+    st = psd_amd.Stats()
+    info = C.c_int(-99)
+    dp = C.POINTER(C.c_double)
+    rc = eng.lib.psd_d_ordschur(eng.ctx, n, p, eng._ptrs(w.Ts), eng._ptrs(w.Z), b"R", 1, sel, 1, wr.ctypes.data_as(dp),
+                                wi.ctypes.data_as(dp), C.byref(st), C.byref(info))
+    assert rc == 0 and info.value == 0
+    assert st.nsweeps == row and st.nwindows == 2 and st.window == 32
+    w.values = wr + 1j * wi
+    w.stats = st
+    select = np.zeros(n, dtype=bool)
+    select[row] = True
+    rord_check(ps0, A, w, select, n, p, 32)

@@ -166,6 +166,38 @@ def test_rordschur_pipelined(monkeypatch):
     ec.case_rordschur_pipelined(make, [(140, 2, "R", 0.5), (160, 5, "L", 0.25), (300, 8, "R", 0.3), (256, 40, "L", 0.5)])
 
 
+@pytest.mark.parametrize("kind,lr", [("11", "R"), ("21", "R"), ("12", "R"), ("22", "R"), ("1s", "R"), ("2s", "R"),
+                                     ("11", "L"), ("2s", "L")])
+@pytest.mark.parametrize("p,W", ec.RORD_P_W)
+def test_rordschur_span(gpu_engine, p, W, kind, lr):
+    """a chosen block at 23 .. 2 W - 1 rows from its target, every window width (engine_cases.case_rordschur_span)"""
+    ec.case_rordschur_span(gpu_engine, p, W, kind, lr)
+
+
+@pytest.mark.parametrize("p,W", ec.RORD_P_W)
+def test_rordschur_span_targets(gpu_engine, p, W):
+    ec.case_rordschur_span_targets(gpu_engine, p, W)
+
+
+def test_rordschur_span_pipelined(monkeypatch):
+    import psd_amd
+
+    def make(env):
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        return psd_amd.Engine()
+
+    ec.case_rordschur_span_pipelined(make, ec.RORD_PIPE_CASES)
+
+
+def test_rordschur_span_entry_points(gpu_engine):
+    """the same move through the signed real reordering, psd_d_ordschur_batch (inside the batched kernel and above its
+    largest order) and one raw call of psd_d_ordschur"""
+    ec.case_gordschur_span(gpu_engine)
+    ec.case_ordschur_batch_span(gpu_engine)
+    ec.case_rordschur_span_capi(gpu_engine)
+
+
 def test_rphessenberg(gpu_engine):
     ec.case_rphessenberg(gpu_engine)
 

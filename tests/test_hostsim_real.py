@@ -87,6 +87,39 @@ def test_rordschur_pipelined(built, monkeypatch):
     ec.case_rordschur_pipelined(make, [(140, 2, "R", 0.5), (160, 5, "L", 0.25), (90, 3, "R", 0.6)])
 
 
+@pytest.mark.parametrize("kind,lr", [("11", "R"), ("21", "R"), ("12", "R"), ("22", "R"), ("1s", "R"), ("2s", "R"),
+                                     ("11", "L"), ("2s", "L")])
+@pytest.mark.parametrize("p,W", ec.RORD_P_W)
+def test_rordschur_span(sim_engine, p, W, kind, lr):
+    ec.case_rordschur_span(sim_engine, p, W, kind, lr)
+
+
+@pytest.mark.parametrize("p,W", ec.RORD_P_W)
+def test_rordschur_span_targets(sim_engine, p, W):
+    ec.case_rordschur_span_targets(sim_engine, p, W)
+
+
+def test_rordschur_span_pipelined(built, monkeypatch):
+    import os
+
+    import psd_amd
+
+    lib = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostsim", "_build", "libpsd_hostsim.so")
+
+    def make(env):
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        return psd_amd.Engine(libpath=lib)
+
+    ec.case_rordschur_span_pipelined(make, ec.RORD_PIPE_CASES)
+
+
+def test_rordschur_span_entry_points(sim_engine):
+    ec.case_gordschur_span(sim_engine)
+    ec.case_ordschur_batch_span(sim_engine)
+    ec.case_rordschur_span_capi(sim_engine)
+
+
 def test_zordschur_pipelined(built, monkeypatch):
     import os
 
