@@ -348,7 +348,10 @@ int psd_z_partial_pschur(psd_ctx* ctx, int n, int p, const double* const* A, int
                          int purgebuffer, int* nconv, double* const* T, double* const* Z, double* wr, double* wi,
                          psd_krylov_stats* stats, int* info);
 /* Device-resident variants: dA a device [p][n][n] block (factor-major, not modified), dZ a device [p][n][maxdim] block
- * (Z_{l+1} in the first n * nconv elements of block l, ld n); T, wr, wi, u1 host buffers as above. */
+ * (Z_{l+1} in the first n * nconv elements of block l, ld n); T, wr, wi, u1 host buffers as above.
+ * Alignment: dA may be any 8-byte aligned pointer (a view into a larger allocation at any element offset).  The Float64
+ * product reads two rows per lane through 16-byte loads only when n is even AND dA is 16-byte aligned; otherwise it takes
+ * the one-row body.  The body decides the column chunking, so the bits of a result depend on n and on that alignment. */
 int psd_d_partial_pschur_dev(psd_ctx* ctx, int n, int p, const double* dA, int nev, char which, int mindim, int maxdim,
                              const double* u1, uint64_t seed, double tol, double tol1, int restarts, int purgebuffer,
                              int* nconv, double* const* T, double* dZ, double* wr, double* wi, psd_krylov_stats* stats,
@@ -405,6 +408,54 @@ int psd_d_csr_matvec(psd_ctx* ctx, int n, const int64_t* rowptr, const int32_t* 
                      const double* x, double* y, int group, int* info);
 int psd_z_csr_matvec(psd_ctx* ctx, int n, const int64_t* rowptr, const int32_t* colind, const double* val,
                      const double* x, double* y, int group, int* info);
+
+/* ---- diagnostic entries of the dense Krylov kernels -------------------------------------------------------------------
+ * TEST PLUMBING, not part of the product's interface and without a Julia binding: each runs kernels of the dense driver
+ * once, on host buffers, through the driver's own launch code and launch geometry, so that a test can compare one kernel
+ * with a high-precision reference at a chosen shape.  Elements are Float64 (psd_d_*) or ComplexF64 as interleaved (re, im)
+ * pairs (psd_z_*); matrices are column-major.  info: <0 argument -k invalid (listed per entry); PSD_INFO_RUNTIME + k.
+ *
+ * The launch geometry of the driver at order n and subspace order maxdim:
+ *   rp      rows per lane of the matvec: 2 for Float64 with n even and a 16-byte aligned factor pointer, else 1;
+ *   tiles   = ceil(n / (256 rp)) row tiles of the matvec;
+ *   nchunk, ccols: column chunks of the matvec and their width: nchunk0 = max(1, min(ceil(1024 / tiles), ceil(n / 32))),
+ *           ccols = ceil(n / nchunk0), nchunk = ceil(n / ccols) (the last chunk holds n - (nchunk - 1) ccols columns);
+ *   nblk    = ceil(n / 256) workgroups of the row kernels;  ldp = maxdim + 2, the pitch of their partial sums. */
+typedef struct psd_krylov_geom {
+    int32_t rp, tiles, nchunk, ccols, nblk, ldp;
+} psd_krylov_geom;
+
+/* y = A x as the driver forms it: the chunked product (psd_kr_mv), then the in-order sum of the chunks (psd_kr_dots).
+ * A: n x n; a_dev = 0: a host buffer, copied to a fresh (16-byte aligned) device allocation; a_dev = 1: a device pointer,
+ * read in place under the alignment rule of psd_d_partial_pschur_dev.  x, y: host, n elements.  geom (may be NULL)
+ * receives the geometry used (ldp as for maxdim = 0).
+ * info: -1 ctx NULL; -2 n < 1; -4 A NULL; -8 a_dev not 0 or 1; -9 x NULL; -17 y NULL. */
+int psd_d_dense_matvec(psd_ctx* ctx, int n, const double* A, int a_dev, const double* x, double* y,
+                       psd_krylov_geom* geom, int* info);
+int psd_z_dense_matvec(psd_ctx* ctx, int n, const double* A, int a_dev, const double* x, double* y,
+                       psd_krylov_geom* geom, int* info);
+/* One orthogonalise-normalise-store stage of the driver (geometry of maxdim = ncols, null-vector threshold 100 eps):
+ * v against the ncols columns of U (n x ncols, orthonormal), classical Gram-Schmidt with the conditional second pass.
+ * h (ncols elements) and *hjj receive the column of the projected factor (its last entry is 0 when the stage stopped);
+ * unew (n elements) is uploaded as column ncols of the basis and read back after the stage, and U is read back as well,
+ * so a caller sees what the stage wrote and what it left alone.  state[0] = 1 when the stage stopped the step,
+ * state[1] = its kind (1: v in the span of U; 2: null vector, ncols = 0 only), state[2] = 1 when the second pass ran,
+ * state[3] = nblk.
+ * info: -1 ctx NULL; -2 n < 1; -3 ncols < 0 or > PSD_KRYLOV_MAXDIM; -4 U NULL with ncols > 0; -5 v NULL; -6 h NULL with
+ * ncols > 0; -7 hjj NULL; -8 unew NULL; -9 state NULL. */
+int psd_d_kr_orth(psd_ctx* ctx, int n, int ncols, double* U, const double* v, double* h, double* hjj, double* unew,
+                  int32_t* state, int* info);
+int psd_z_kr_orth(psd_ctx* ctx, int n, int ncols, double* U, const double* v, double* h, double* hjj, double* unew,
+                  int32_t* state, int* info);
+/* The in-place basis update V_l[:, a0:a0+m) <- V_l[:, a0:a0+m) Q_l for l = 0..p-1 in one launch.  V: [p][n][ldv_cols]
+ * (ld n), Q: [p][m][m].  *R (may be NULL) receives the rows per workgroup: the tile of R x m elements is staged in LDS,
+ * R = max(1, min(64, 65536 / (m * element bytes))).
+ * info: -1 ctx NULL; -2 n < 1; -3 p < 1; -4 ldv_cols < 1; -5 a0 < 0; -6 m < 1, m > PSD_KRYLOV_MAXDIM or
+ * a0 + m > ldv_cols; -7 V NULL; -8 Q NULL. */
+int psd_d_kr_basis(psd_ctx* ctx, int n, int p, int ldv_cols, int a0, int m, double* V, const double* Q, int32_t* R,
+                   int* info);
+int psd_z_kr_basis(psd_ctx* ctx, int n, int p, int ldv_cols, int a0, int m, double* V, const double* Q, int32_t* R,
+                   int* info);
 
 /* ---- eigvecs(ps, select; shifted) by periodic back-substitution — vectors.jl:25-138 without the reordering ----------
  * The selected right eigenvectors of the product and of its circular shifts, from a periodic Schur decomposition, by

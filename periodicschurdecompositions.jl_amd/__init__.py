@@ -127,6 +127,15 @@ class KrylovStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class KrylovGeom(C.Structure):
+    """psd_krylov_geom (include/psd_mi355x.h): launch geometry of the dense Krylov kernels."""
+    _fields_ = [("rp", C.c_int32), ("tiles", C.c_int32), ("nchunk", C.c_int32), ("ccols", C.c_int32),
+                ("nblk", C.c_int32), ("ldp", C.c_int32)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class EvecStats(C.Structure):
     """psd_evec_stats (include/psd_mi355x.h): counters and device times of one eigvecs call by back-substitution."""
     _fields_ = [
@@ -326,6 +335,14 @@ class Engine:
                                          C.c_void_p if dev else dpp, dp, dp, C.POINTER(KrylovStats), ip]
         lib.psd_d_csr_matvec.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, dp, dp, C.c_int, ip]
         lib.psd_z_csr_matvec.argtypes = lib.psd_d_csr_matvec.argtypes
+        if hasattr(lib, "psd_d_dense_matvec"):  # (tools load builds of earlier commits)
+            lib.psd_d_dense_matvec.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, dp, dp, C.POINTER(KrylovGeom), ip]
+            lib.psd_z_dense_matvec.argtypes = lib.psd_d_dense_matvec.argtypes
+            lib.psd_d_kr_orth.argtypes = [C.c_void_p, C.c_int, C.c_int, dp, dp, dp, dp, dp, C.POINTER(C.c_int32), ip]
+            lib.psd_z_kr_orth.argtypes = lib.psd_d_kr_orth.argtypes
+            lib.psd_d_kr_basis.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp,
+                                           C.POINTER(C.c_int32), ip]
+            lib.psd_z_kr_basis.argtypes = lib.psd_d_kr_basis.argtypes
         i32p = C.POINTER(C.c_int32)
         for nm, dev, cplx in (("psd_d_eigvecs", False, False), ("psd_z_eigvecs", False, True),
                               ("psd_d_eigvecs_dev", True, False), ("psd_z_eigvecs_dev", True, True)):
@@ -1709,6 +1726,104 @@ class Engine:
             raise ValueError(f"group must be 0 or a power of two <= 64, got {group}")
         self._raise(info.value)
         return y
+
+    # ---- diagnostic entries of the dense Krylov kernels (test plumbing, include/psd_mi355x.h) ----
+    def dense_matvec(self, A, x, in_place=False):
+        """y = A x through the dense driver's own matvec kernels, run once.  `A`: a numpy n x n matrix (copied to the
+        device), or a torch device tensor holding the matrix column-major (`A.t()` contiguous), which the kernel reads in
+        place at whatever address the view has.  in_place: hand the memory of a column-major numpy array to the kernel as
+        it is (meaningful only where host memory is device memory: the serial simulation).  Returns (y, geom): geom the
+        launch geometry used, a dict with rp, tiles, nchunk, ccols, nblk, ldp."""
+        keep = None
+        if hasattr(A, "data_ptr"):
+            if A.dim() != 2 or A.shape[0] != A.shape[1] or not A.t().is_contiguous() or not A.is_cuda:
+                raise TypeError("dense_matvec needs a column-major square device tensor (A.t() contiguous)")
+            cplx = A.is_complex()
+            if A.element_size() != (16 if cplx else 8):
+                raise TypeError("dense_matvec needs float64 or complex128")
+            import torch
+
+            torch.cuda.synchronize(A.device)
+            n, aptr, a_dev = A.shape[0], A.data_ptr(), 1
+            cplx = cplx or np.iscomplexobj(x)
+            if cplx and not A.is_complex():
+                raise TypeError("a complex x needs a complex A")
+        else:
+            A = np.asarray(A)
+            n = _check_square([A])
+            cplx = np.iscomplexobj(A) or np.iscomplexobj(x)
+            if in_place:
+                if not A.flags.f_contiguous or A.dtype != (np.complex128 if cplx else np.float64):
+                    raise TypeError("in_place needs a column-major array of the element type")
+                keep = A
+            else:
+                keep = np.asfortranarray(A, dtype=np.complex128 if cplx else np.float64)
+            aptr, a_dev = keep.ctypes.data, 1 if in_place else 0
+        dt = np.complex128 if cplx else np.float64
+        xa = np.ascontiguousarray(np.asarray(x, dtype=dt).reshape(-1))
+        if xa.shape[0] != n:
+            raise DimensionMismatch("x must have length matching the matrix")
+        y = np.zeros(n, dtype=dt)
+        geom, info = KrylovGeom(), C.c_int(0)
+        dp = C.POINTER(C.c_double)
+        fn = self.lib.psd_z_dense_matvec if cplx else self.lib.psd_d_dense_matvec
+        fn(self.ctx, n, C.c_void_p(aptr), a_dev, xa.view(np.float64).ctypes.data_as(dp),
+           y.view(np.float64).ctypes.data_as(dp), C.byref(geom), C.byref(info))
+        self._raise(info.value)
+        return y, geom.asdict()
+
+    def kr_orth(self, U, v, unew=None):
+        """One orthogonalisation stage of the dense driver: v against the orthonormal columns of U (n x ncols).  Returns
+        (h, hjj, unew, state, U_after): the coefficients, the norm, column ncols of the basis after the stage (`unew` on
+        entry: what the column holds before, zeros by default), state = dict(stop, kind, reorth, nblk), and the first
+        ncols columns as the stage left them."""
+        U = np.asarray(U)
+        v = np.asarray(v).reshape(-1)
+        n, ncols = v.shape[0], (U.shape[1] if U.ndim == 2 else 0)
+        if ncols and U.shape[0] != n:
+            raise DimensionMismatch("U must have as many rows as v has elements")
+        cplx = np.iscomplexobj(U) or np.iscomplexobj(v)
+        dt = np.complex128 if cplx else np.float64
+        Ua = np.array(U.reshape(n, ncols), dtype=dt, order="F")
+        va = np.ascontiguousarray(v, dtype=dt)
+        un = np.zeros(n, dtype=dt) if unew is None else np.array(np.asarray(unew).reshape(-1), dtype=dt)
+        if un.shape[0] != n:
+            raise DimensionMismatch("unew must have as many elements as v")
+        h = np.zeros(ncols, dtype=dt)
+        hjj, info = C.c_double(0.0), C.c_int(0)
+        st = (C.c_int32 * 4)()
+        dp = C.POINTER(C.c_double)
+
+        def ptr(a):
+            return a.ctypes.data_as(dp) if a.size else None
+
+        fn = self.lib.psd_z_kr_orth if cplx else self.lib.psd_d_kr_orth
+        fn(self.ctx, n, ncols, ptr(Ua), ptr(va), ptr(h), C.byref(hjj), ptr(un), st, C.byref(info))
+        self._raise(info.value)
+        state = dict(stop=int(st[0]), kind=int(st[1]), reorth=int(st[2]), nblk=int(st[3]))
+        return h, float(hjj.value), un, state, Ua
+
+    def kr_basis(self, V, Q, a0):
+        """The dense driver's in-place basis update V_l[:, a0:a0+m) <- V_l[:, a0:a0+m) Q_l.  V: p matrices n x ncols,
+        Q: p matrices m x m.  Returns (list of the updated matrices, R): R the rows per workgroup the launch chose."""
+        p = len(V)
+        if p < 1 or len(Q) != p:
+            raise DimensionMismatch("V and Q must hold the same number (>= 1) of matrices")
+        cplx = any(np.iscomplexobj(a) for a in list(V) + list(Q))
+        dt = np.complex128 if cplx else np.float64
+        n, cols = np.asarray(V[0]).shape
+        m = np.asarray(Q[0]).shape[0]
+        if any(np.asarray(a).shape != (n, cols) for a in V) or any(np.asarray(q).shape != (m, m) for q in Q):
+            raise DimensionMismatch("all V_l must be n x ncols and all Q_l m x m")
+        Va = np.stack([np.asarray(a, dtype=dt).T for a in V]).copy()  # [p][cols][n]: block l column-major n x cols
+        Qa = np.stack([np.asarray(q, dtype=dt).T for q in Q]).copy()
+        R, info = C.c_int32(0), C.c_int(0)
+        dp = C.POINTER(C.c_double)
+        fn = self.lib.psd_z_kr_basis if cplx else self.lib.psd_d_kr_basis
+        fn(self.ctx, n, p, cols, int(a0), m, Va.view(np.float64).ctypes.data_as(dp),
+           Qa.view(np.float64).ctypes.data_as(dp), C.byref(R), C.byref(info))
+        self._raise(info.value)
+        return [np.asfortranarray(Va[l].T) for l in range(p)], int(R.value)
 
     def partial_pschur(self, As, nev=None, which="LM", *, mindim=None, maxdim=None, u1=None, tol=None, tol1=None,
                        restarts=100, purgebuffer=2, seed=0):

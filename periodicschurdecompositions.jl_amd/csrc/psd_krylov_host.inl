@@ -22,6 +22,86 @@ struct KrylovCsr {
     const int* lg;
 };
 
+// ---- launch geometry and launches, shared by the driver and by the diagnostic entries (psd_?_dense_matvec,
+// psd_?_kr_orth, psd_?_kr_basis) so that the two cannot drift apart ---------------------------------------------------
+// Geometry at order n and subspace order kmax; dA: the dense factors (nullptr: none, counts as aligned).  The two-row
+// body of the Float64 matvec needs an even n (a pair never straddles a column) and a 16-byte aligned base (its loads).
+template <bool Z>
+psd_krylov_geom kr_geometry(int n, int kmax, const double* dA) {
+    psd_krylov_geom g;
+    g.rp = (!Z && n % 2 == 0 && ((uintptr_t)dA & 15) == 0) ? 2 : 1;
+    g.tiles = (n + PSD_KR_NT * g.rp - 1) / (PSD_KR_NT * g.rp);
+    // about 1024 workgroups (4 per compute unit) of at least 32 columns each
+    g.nchunk = std::max(1, std::min((1024 + g.tiles - 1) / g.tiles, (n + 31) / 32));
+    g.ccols = (n + g.nchunk - 1) / g.nchunk;
+    g.nchunk = (n + g.ccols - 1) / g.ccols;
+    g.nblk = (n + PSD_KR_NT - 1) / PSD_KR_NT;
+    g.ldp = kmax + 2;
+    return g;
+}
+// part[chunk][r] = the partial products of A u (A: one n x n factor on the device)
+template <bool Z>
+void kr_launch_mv(psd_ctx* c, const psd_krylov_geom& g, const double* A, const double* u, double* part, int n,
+                  const int* st) {
+    if (g.rp == 2) PSD_LAUNCH((psd_kr_mv<Z, 2>), psd_dim3(g.tiles, g.nchunk), PSD_KR_NT, 0, c->stream, A, u, part, n, g.ccols, st);
+    else PSD_LAUNCH((psd_kr_mv<Z, 1>), psd_dim3(g.tiles, g.nchunk), PSD_KR_NT, 0, c->stream, A, u, part, n, g.ccols, st);
+}
+template <bool Z>
+void kr_launch_dots(psd_ctx* c, const psd_kr_args& a, const double* part, int nch, int gate) {
+    const size_t e = sizeof(double) * (Z ? 2 : 1);
+    PSD_LAUNCH(psd_kr_dots<Z>, psd_dim3(a.nblk), PSD_KR_NT, 2 * PSD_KR_NT * e, c->stream, a, part, nch, gate);
+}
+// orthogonalise v (summed from the matvec partials when nch > 0) against U[:, 0:ncols), store into U[:, ncols)
+template <bool Z>
+void kr_launch_stage(psd_ctx* c, const psd_kr_args& a, const double* part, int nch) {
+    const size_t e = sizeof(double) * (Z ? 2 : 1);
+    kr_launch_dots<Z>(c, a, part, nch, 0);
+    if (a.ncols > 0) {
+        const size_t lx = (PSD_KR_NT + (size_t)a.ncols) * e;
+        PSD_LAUNCH(psd_kr_axpy<Z>, psd_dim3(a.nblk), PSD_KR_NT, lx, c->stream, a, 1);
+        kr_launch_dots<Z>(c, a, part, 0, 1);
+        PSD_LAUNCH(psd_kr_axpy<Z>, psd_dim3(a.nblk), PSD_KR_NT, lx, c->stream, a, 2);
+    }
+    PSD_LAUNCH(psd_kr_store<Z>, psd_dim3(a.nblk), PSD_KR_NT, 0, c->stream, a);
+}
+// rows per workgroup of the basis update: the R x m tile fits the LDS budget
+template <bool Z>
+int kr_basis_rows(int m) {
+    const size_t e = sizeof(double) * (Z ? 2 : 1);
+    const int R = (int)std::min<size_t>(64, PSD_KR_BASIS_LDS / ((size_t)m * e));
+    return R < 1 ? 1 : R;
+}
+// V_l[:, a0:a0+m) <- V_l[:, a0:a0+m) Q_l for every l (V: p blocks vstride elements apart, ld n; Q: [p][m][m]); returns R
+template <bool Z>
+int kr_launch_basis(psd_ctx* c, double* V, size_t vstride, const double* Q, int n, int p, int a0, int m) {
+    const size_t e = sizeof(double) * (Z ? 2 : 1);
+    const int R = kr_basis_rows<Z>(m);
+    PSD_LAUNCH(psd_kr_basis<Z>, psd_dim3((n + R - 1) / R, p), PSD_KR_NT, (size_t)R * m * e, c->stream, V, vstride, Q, n,
+               a0, m, R);
+    return R;
+}
+inline psd_kr_args kr_args(const psd_krylov_geom& g, int n, int ncols, int lfac, double tol1, double* U, double* v,
+                           double* pA, double* pB, double* w1, double* w2, double* h, double* Hcol, int* st) {
+    psd_kr_args a;
+    a.n = n;
+    a.ncols = ncols;
+    a.nblk = g.nblk;
+    a.ldp = g.ldp;
+    a.lfac = lfac;
+    a.eta = 1.0 / sqrt(2.0);
+    a.tol1 = tol1;
+    a.U = U;
+    a.v = v;
+    a.pA = pA;
+    a.pB = pB;
+    a.w1 = w1;
+    a.w2 = w2;
+    a.h = h;
+    a.Hcol = Hcol;
+    a.st = st;
+    return a;
+}
+
 template <bool Z>
 struct KrylovRun {
     typedef typename std::conditional<Z, std::complex<double>, double>::type T;
@@ -36,7 +116,7 @@ struct KrylovRun {
     const KrylovCsr* csr = nullptr;  // sparse factors
     // device
     psd_devbuf bV, bpart, bv, bpA, bpB, bw1, bw2, bh, bH, bQ, bst;
-    int nchunk = 1, ccols = 1, nblk = 1, ldp = 1;
+    psd_krylov_geom g;
     size_t vstride = 0, hstride = 0;
     int ldh = 0;
     // host copy of the projected factors: H_l ((kmax + 1) x kmax, ld kmax + 1), l = 1..p; H_p holds the footer row
@@ -50,14 +130,8 @@ struct KrylovRun {
         vstride = (size_t)n * (kmax + 1);
         ldh = kmax + 1;
         hstride = (size_t)ldh * kmax;
-        nblk = (n + PSD_KR_NT - 1) / PSD_KR_NT;
-        ldp = kmax + 2;
-        const int rp = (!Z && n % 2 == 0) ? 2 : 1;
-        const int tiles = (n + PSD_KR_NT * rp - 1) / (PSD_KR_NT * rp);
-        // about 1024 workgroups (4 per compute unit) of at least 32 columns each
-        nchunk = std::max(1, std::min((1024 + tiles - 1) / tiles, (n + 31) / 32));
-        ccols = (n + nchunk - 1) / nchunk;
-        nchunk = (n + ccols - 1) / ccols;
+        g = kr_geometry<Z>(n, kmax, dA);
+        const int nchunk = g.nchunk, nblk = g.nblk, ldp = g.ldp;
         const size_t e = sizeof(double) * ES;
         PSD_CHECK(bV.alloc((size_t)p * vstride * e));
         if (!csr) PSD_CHECK(bpart.alloc((size_t)nchunk * n * e));  // (a CSR product has no partial sums)
@@ -78,37 +152,9 @@ struct KrylovRun {
     int* dst() const { return (int*)bst.p; }
 
     psd_kr_args args(double* U, int ncols, double* Hcol, int lfac) {
-        psd_kr_args a;
-        a.n = n;
-        a.ncols = ncols;
-        a.nblk = nblk;
-        a.ldp = ldp;
-        a.lfac = lfac;
-        a.eta = 1.0 / sqrt(2.0);
-        a.tol1 = tol1;
-        a.U = U;
-        a.v = bv.d();
-        a.pA = bpA.d();
-        a.pB = bpB.d();
-        a.w1 = bw1.d();
-        a.w2 = bw2.d();
-        a.h = bh.d();
-        a.Hcol = Hcol;
-        a.st = dst();
-        return a;
+        return kr_args(g, n, ncols, lfac, tol1, U, bv.d(), bpA.d(), bpB.d(), bw1.d(), bw2.d(), bh.d(), Hcol, dst());
     }
-    // orthogonalise v (summed from the matvec partials when nchunk > 0) against U[:, 0:ncols), store into U[:, ncols)
-    void stage(const psd_kr_args& a, int nch) {
-        const size_t e = sizeof(double) * ES;
-        PSD_LAUNCH(psd_kr_dots<Z>, psd_dim3(nblk), PSD_KR_NT, 2 * PSD_KR_NT * e, c->stream, a, bpart.d(), nch, 0);
-        if (a.ncols > 0) {
-            const size_t lx = (PSD_KR_NT + (size_t)a.ncols) * e;
-            PSD_LAUNCH(psd_kr_axpy<Z>, psd_dim3(nblk), PSD_KR_NT, lx, c->stream, a, 1);
-            PSD_LAUNCH(psd_kr_dots<Z>, psd_dim3(nblk), PSD_KR_NT, 2 * PSD_KR_NT * e, c->stream, a, bpart.d(), 0, 1);
-            PSD_LAUNCH(psd_kr_axpy<Z>, psd_dim3(nblk), PSD_KR_NT, lx, c->stream, a, 2);
-        }
-        PSD_LAUNCH(psd_kr_store<Z>, psd_dim3(nblk), PSD_KR_NT, 0, c->stream, a);
-    }
+    void stage(const psd_kr_args& a, int nch) { kr_launch_stage<Z>(c, a, bpart.d(), nch); }
     // factor l (0-based) of Krylov step j (1-based), krylov.jl:262-333 / :335-371
     void factor(int l, int j) {
         const double* u = V(l) + (size_t)(j - 1) * n * ES;
@@ -123,11 +169,8 @@ struct KrylovRun {
             return;
         }
         const double* Al = dA + (size_t)l * n * n * ES;
-        const int rp = (!Z && n % 2 == 0) ? 2 : 1;
-        const int tiles = (n + PSD_KR_NT * rp - 1) / (PSD_KR_NT * rp);
-        if (rp == 2) PSD_LAUNCH((psd_kr_mv<Z, 2>), psd_dim3(tiles, nchunk), PSD_KR_NT, 0, c->stream, Al, u, bpart.d(), n, ccols, dst());
-        else PSD_LAUNCH((psd_kr_mv<Z, 1>), psd_dim3(tiles, nchunk), PSD_KR_NT, 0, c->stream, Al, u, bpart.d(), n, ccols, dst());
-        stage(args(V(lo), ncols, Hcol, l), nchunk);
+        kr_launch_mv<Z>(c, g, Al, u, bpart.d(), n, dst());
+        stage(args(V(lo), ncols, Hcol, l), g.nchunk);
     }
     int read_state(int* s) {
         PSD_CHECK(psd_rt_d2h(s, bst.p, sizeof(int) * PSD_KR_ST_WORDS, c->stream));
@@ -166,11 +209,7 @@ struct KrylovRun {
         std::vector<T> q((size_t)p * m * m);
         for (int l = 0; l < p; ++l) std::copy(Q[l].begin(), Q[l].end(), q.begin() + (size_t)l * m * m);
         PSD_CHECK(psd_rt_h2d(bQ.p, q.data(), q.size() * sizeof(T), c->stream));
-        const size_t e = sizeof(double) * ES;
-        int R = (int)std::min<size_t>(64, PSD_KR_BASIS_LDS / ((size_t)m * e));
-        if (R < 1) R = 1;
-        PSD_LAUNCH(psd_kr_basis<Z>, psd_dim3((n + R - 1) / R, p), PSD_KR_NT, (size_t)R * m * e, c->stream, bV.d(),
-                   vstride, bQ.d(), n, a0, m, R);
+        kr_launch_basis<Z>(c, bV.d(), vstride, bQ.d(), n, p, a0, m);
         PSD_CHECK(psd_rt_sync(c->stream));
         PSD_CHECK(psd_rt_last_error());
         if (st) st->ms_basis += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -975,6 +1014,127 @@ int csr_matvec_host(psd_ctx* c, int n, const int64_t* rowptr, const int32_t* col
     return *info = 0;
 }
 
+// ---- diagnostic entries of the dense kernels (test plumbing; include/psd_mi355x.h) -----------------------------------
+// y = A x: psd_kr_mv, then the chunk sum of psd_kr_dots (ncols = 0), on host buffers; A in place when a_dev
+template <bool Z>
+int dense_matvec_host(psd_ctx* c, int n, const double* A, int a_dev, const double* x, double* y, psd_krylov_geom* geom,
+                      int* info) {
+    int dummy;
+    if (!info) info = &dummy;
+    if (!c) return *info = -1;
+    if (n < 1) return *info = -2;
+    if (!A) return *info = -4;
+    if (a_dev != 0 && a_dev != 1) return *info = -8;
+    if (!x) return *info = -9;
+    if (!y) return *info = -17;
+    const size_t e = sizeof(double) * (Z ? 2 : 1);
+    psd_devbuf bA, bx, bv, bpart, bpA;
+    const double* dA = A;
+    if (!a_dev) {
+        PSD_CHECK(bA.alloc(e * n * n));
+        PSD_CHECK(psd_rt_h2d(bA.p, A, e * n * n, c->stream));
+        dA = bA.d();
+    }
+    const psd_krylov_geom g = kr_geometry<Z>(n, 0, dA);
+    if (geom) *geom = g;
+    PSD_CHECK(bx.alloc(e * n));
+    PSD_CHECK(bv.alloc(e * n));
+    PSD_CHECK(bpart.alloc(e * n * g.nchunk));
+    PSD_CHECK(bpA.alloc(e * g.nblk * g.ldp));
+    PSD_CHECK(psd_rt_h2d(bx.p, x, e * n, c->stream));
+    kr_launch_mv<Z>(c, g, dA, bx.d(), bpart.d(), n, nullptr);
+    const psd_kr_args a = kr_args(g, n, 0, 0, 0.0, nullptr, bv.d(), bpA.d(), nullptr, nullptr, nullptr, nullptr, nullptr,
+                                  nullptr);
+    kr_launch_dots<Z>(c, a, bpart.d(), g.nchunk, 0);
+    PSD_CHECK(psd_rt_d2h(y, bv.p, e * n, c->stream));
+    PSD_CHECK(psd_rt_sync(c->stream));
+    PSD_CHECK(psd_rt_last_error());
+    return *info = 0;
+}
+
+// one stage of the driver on host buffers
+template <bool Z>
+int kr_orth_host(psd_ctx* c, int n, int ncols, double* U, const double* v, double* h, double* hjj, double* unew,
+                 int32_t* state, int* info) {
+    int dummy;
+    if (!info) info = &dummy;
+    if (!c) return *info = -1;
+    if (n < 1) return *info = -2;
+    if (ncols < 0 || ncols > PSD_KRYLOV_MAXDIM) return *info = -3;
+    if (!U && ncols > 0) return *info = -4;
+    if (!v) return *info = -5;
+    if (!h && ncols > 0) return *info = -6;
+    if (!hjj) return *info = -7;
+    if (!unew) return *info = -8;
+    if (!state) return *info = -9;
+    constexpr int ES = Z ? 2 : 1;
+    const size_t e = sizeof(double) * ES;
+    const psd_krylov_geom g = kr_geometry<Z>(n, ncols, nullptr);
+    psd_devbuf bU, bv, bpA, bpB, bw1, bw2, bh, bHc, bst;
+    PSD_CHECK(bU.alloc(e * n * ((size_t)ncols + 1)));
+    PSD_CHECK(bv.alloc(e * n));
+    PSD_CHECK(bpA.alloc(e * g.nblk * g.ldp));
+    PSD_CHECK(bpB.alloc(e * g.nblk * g.ldp));
+    PSD_CHECK(bw1.alloc(sizeof(double) * g.nblk));
+    PSD_CHECK(bw2.alloc(sizeof(double) * g.nblk));
+    PSD_CHECK(bh.alloc(e * g.ldp));
+    PSD_CHECK(bHc.alloc(e * ((size_t)ncols + 1)));
+    PSD_CHECK(bst.alloc(sizeof(int) * PSD_KR_ST_WORDS));
+    PSD_CHECK(psd_rt_memset(bst.p, 0, sizeof(int) * PSD_KR_ST_WORDS, c->stream));
+    PSD_CHECK(psd_rt_memset(bHc.p, 0, e * ((size_t)ncols + 1), c->stream));
+    if (ncols > 0) PSD_CHECK(psd_rt_h2d(bU.p, U, e * n * ncols, c->stream));
+    double* dnew = bU.d() + (size_t)ncols * n * ES;
+    PSD_CHECK(psd_rt_h2d(dnew, unew, e * n, c->stream));
+    PSD_CHECK(psd_rt_h2d(bv.p, v, e * n, c->stream));
+    const psd_kr_args a = kr_args(g, n, ncols, 0, 100 * 2.220446049250313e-16, bU.d(), bv.d(), bpA.d(), bpB.d(),
+                                  bw1.d(), bw2.d(), bh.d(), bHc.d(), (int*)bst.p);
+    kr_launch_stage<Z>(c, a, nullptr, 0);
+    std::vector<double> hc(((size_t)ncols + 1) * ES);
+    int s[PSD_KR_ST_WORDS];
+    if (ncols > 0) PSD_CHECK(psd_rt_d2h(U, bU.p, e * n * ncols, c->stream));
+    PSD_CHECK(psd_rt_d2h(unew, dnew, e * n, c->stream));
+    PSD_CHECK(psd_rt_d2h(hc.data(), bHc.p, e * ((size_t)ncols + 1), c->stream));
+    PSD_CHECK(psd_rt_d2h(s, bst.p, sizeof(s), c->stream));
+    PSD_CHECK(psd_rt_sync(c->stream));
+    PSD_CHECK(psd_rt_last_error());
+    for (size_t i = 0; i < (size_t)ncols * ES; ++i) h[i] = hc[i];
+    *hjj = hc[(size_t)ncols * ES];
+    state[0] = s[PSD_KR_ST_STOP];
+    state[1] = s[PSD_KR_ST_KIND];
+    state[2] = s[PSD_KR_ST_NREORTH];
+    state[3] = g.nblk;
+    return *info = 0;
+}
+
+// the basis update on host buffers
+template <bool Z>
+int kr_basis_host(psd_ctx* c, int n, int p, int ldv_cols, int a0, int m, double* V, const double* Q, int32_t* R,
+                  int* info) {
+    int dummy;
+    if (!info) info = &dummy;
+    if (!c) return *info = -1;
+    if (n < 1) return *info = -2;
+    if (p < 1) return *info = -3;
+    if (ldv_cols < 1) return *info = -4;
+    if (a0 < 0) return *info = -5;
+    if (m < 1 || m > PSD_KRYLOV_MAXDIM || (int64_t)a0 + m > ldv_cols) return *info = -6;
+    if (!V) return *info = -7;
+    if (!Q) return *info = -8;
+    const size_t e = sizeof(double) * (Z ? 2 : 1);
+    const size_t vstride = (size_t)n * ldv_cols;
+    psd_devbuf bV, bQ;
+    PSD_CHECK(bV.alloc(e * vstride * p));
+    PSD_CHECK(bQ.alloc(e * m * m * p));
+    PSD_CHECK(psd_rt_h2d(bV.p, V, e * vstride * p, c->stream));
+    PSD_CHECK(psd_rt_h2d(bQ.p, Q, e * m * m * p, c->stream));
+    const int rows = kr_launch_basis<Z>(c, bV.d(), vstride, bQ.d(), n, p, a0, m);
+    if (R) *R = rows;
+    PSD_CHECK(psd_rt_d2h(V, bV.p, e * vstride * p, c->stream));
+    PSD_CHECK(psd_rt_sync(c->stream));
+    PSD_CHECK(psd_rt_last_error());
+    return *info = 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1033,5 +1193,29 @@ int psd_d_csr_matvec(psd_ctx* c, int n, const int64_t* rowptr, const int32_t* co
 int psd_z_csr_matvec(psd_ctx* c, int n, const int64_t* rowptr, const int32_t* colind, const double* val, const double* x,
                      double* y, int group, int* info) {
     return csr_matvec_host<true>(c, n, rowptr, colind, val, x, y, group, info);
+}
+int psd_d_dense_matvec(psd_ctx* c, int n, const double* A, int a_dev, const double* x, double* y, psd_krylov_geom* geom,
+                       int* info) {
+    return dense_matvec_host<false>(c, n, A, a_dev, x, y, geom, info);
+}
+int psd_z_dense_matvec(psd_ctx* c, int n, const double* A, int a_dev, const double* x, double* y, psd_krylov_geom* geom,
+                       int* info) {
+    return dense_matvec_host<true>(c, n, A, a_dev, x, y, geom, info);
+}
+int psd_d_kr_orth(psd_ctx* c, int n, int ncols, double* U, const double* v, double* h, double* hjj, double* unew,
+                  int32_t* state, int* info) {
+    return kr_orth_host<false>(c, n, ncols, U, v, h, hjj, unew, state, info);
+}
+int psd_z_kr_orth(psd_ctx* c, int n, int ncols, double* U, const double* v, double* h, double* hjj, double* unew,
+                  int32_t* state, int* info) {
+    return kr_orth_host<true>(c, n, ncols, U, v, h, hjj, unew, state, info);
+}
+int psd_d_kr_basis(psd_ctx* c, int n, int p, int ldv_cols, int a0, int m, double* V, const double* Q, int32_t* R,
+                   int* info) {
+    return kr_basis_host<false>(c, n, p, ldv_cols, a0, m, V, Q, R, info);
+}
+int psd_z_kr_basis(psd_ctx* c, int n, int p, int ldv_cols, int a0, int m, double* V, const double* Q, int32_t* R,
+                   int* info) {
+    return kr_basis_host<true>(c, n, p, ldv_cols, a0, m, V, Q, R, info);
 }
 }  // extern "C"

@@ -94,16 +94,21 @@ def check(P, As, tol=1e-10):
     return worst_rel, worst_orth
 
 
-def check_values(P, vfull, which, nev, rtol=1e-5):
+def check_values(P, vfull, which, nev, rtol=1e-5, among=None, found=0):
+    """Every returned value is one of the `among` leading values of the full spectrum in the order of the target
+    (default 2 nev; a wide subspace locks many more than nev values, then len(P.values) + nev is the count to pass), and
+    the `found` leading values of the full spectrum are each returned to 1e-6 |lambda|."""
     key, desc = BYES[which]
     order = np.argsort(key(vfull), kind="stable")
     if desc:
         order = order[::-1]
-    best = vfull[order[: 2 * nev]]
+    best = vfull[order[: 2 * nev if among is None else among]]
     if not np.iscomplexobj(P.Ts[0]):  # (a real spectrum: the cut may separate a conjugate pair)
         best = np.concatenate([best, np.conj(best)])
     for lam in P.values:
         assert np.any(np.abs(best - lam) <= rtol * np.abs(best)), (lam, best)
+    for lam in vfull[order[:found]]:
+        assert np.min(np.abs(P.values - lam)) <= 1e-6 * abs(lam), (lam, P.values)
 
 
 def ev_check(eng, P, As):
@@ -143,6 +148,28 @@ def pkstest(eng, As, which, vfull=None, nev=4, k0=6, tol=1e-10, restarts=60, **k
     if vfull is not None:
         check_values(P, vfull, which, nev)
     ev_check(eng, P, As)
+    return P, hist
+
+
+# A subspace wider than a workgroup of the row kernels (ncols > 256: the strided loops of psd_kr_axpy / psd_kr_store take
+# a second trip, psd_kr_basis tiles fewer than 64 rows): dominant(600, 2) with these keywords
+WIDE_N, WIDE_P, WIDE_NEV = 600, 2, 6
+WIDE_KW = dict(mindim=150, maxdim=300, tol=1e-10, restarts=100, seed=1)
+
+
+def wide_subspace(eng, cplx):
+    """dominant(600, 2), nev = 6, mindim = 150, maxdim = 300, tol = 1e-10: converges in the first restart iteration
+    (restarts = 1 observed on the serial simulation, real and complex, with well over nev values locked), so the values
+    are matched against len(P.values) + nev leading values of the full spectrum, and the nev / 2 dominant ones must be
+    found.  The full spectrum comes from numpy's eigvals of the explicit product A_2 A_1: the factors of dominant() are
+    well conditioned (it agrees with the oracle's periodic QR to 2e-13 |lambda| on the 40 leading values, in a second
+    where the complex oracle takes half a minute at this order)."""
+    As = dominant(WIDE_N, WIDE_P, cplx=cplx, seed=51 + int(cplx))
+    P, hist = eng.partial_pschur(As, WIDE_NEV, "LM", **WIDE_KW)
+    assert hist.nconverged >= WIDE_NEV and hist.converged, hist.__dict__
+    assert hist.nconverged == P.Z[0].shape[1] == len(P.values)
+    check(P, As, WIDE_KW["tol"])
+    check_values(P, np.linalg.eigvals(As[1] @ As[0]), "LM", WIDE_NEV, among=len(P.values) + WIDE_NEV, found=WIDE_NEV // 2)
     return P, hist
 
 

@@ -103,3 +103,24 @@ def test_real_8192x8_device_resident(gpu_engine):
         assert res <= bound, (l, res, bound)
         orth = torch.linalg.matrix_norm(Zl.T @ Zl - torch.eye(k, device="cuda", dtype=torch.float64)).item()
         assert orth < 100 * n * eps, (l, orth)
+
+
+@pytest.mark.parametrize("n,p,kw", [(31, 3, {}), (257, 2, dict(xpnd=1.05, unit=True)), (513, 2, dict(xpnd=1.02, unit=True))])
+def test_odd_real_orders(gpu_engine, n, p, kw):
+    """Odd orders take the one-row body psd_kr_mv<false, 1> of the Float64 matvec through the whole driver (one row
+    either side of a tile at 257 and 513)."""
+    As = kc.mkmats1(n, p, **kw)
+    kc.pkstest(gpu_engine, As, "LM", kc.full_values(As))
+
+
+@pytest.mark.parametrize("cplx", [False, True])
+def test_wide_subspace(gpu_engine, cplx):
+    """maxdim = 300 > 256: see krylov_cases.wide_subspace."""
+    P, h = kc.wide_subspace(gpu_engine, cplx)
+    assert P.stats.restarts >= 1
+
+
+def test_bit_identical_runs_odd_order(gpu_engine):
+    As = kc.mkmats1(257, 2, xpnd=1.05, seed=23, unit=True)
+    kw = dict(mindim=6, maxdim=12, tol=1e-10, restarts=60, seed=9)
+    kc.same_bits(*gpu_engine.partial_pschur(As, 4, "LM", **kw), *gpu_engine.partial_pschur(As, 4, "LM", **kw))

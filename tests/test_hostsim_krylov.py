@@ -143,3 +143,24 @@ def test_rank_deficient_reinitialises(sim_engine):
     scale = np.max(np.abs(vfull))
     for lam in P.values:  # (the zero eigenvalues of the singular product are valid answers too)
         assert np.min(np.abs(vfull - lam)) <= 1e-5 * scale
+
+
+@pytest.mark.parametrize("n,p,kw", [(31, 3, {}), (257, 2, dict(xpnd=1.05, unit=True)), (513, 2, dict(xpnd=1.02, unit=True))])
+def test_odd_real_orders(sim_engine, n, p, kw):
+    """Odd orders take the one-row body psd_kr_mv<false, 1> of the Float64 matvec through the whole driver (one row
+    either side of a tile at 257 and 513)."""
+    As = kc.mkmats1(n, p, **kw)
+    kc.pkstest(sim_engine, As, "LM", kc.full_values(As))
+
+
+@pytest.mark.parametrize("cplx", [False, True])
+def test_wide_subspace(sim_engine, cplx):
+    """maxdim = 300 > 256: see krylov_cases.wide_subspace."""
+    P, h = kc.wide_subspace(sim_engine, cplx)
+    assert P.stats.restarts >= 1
+
+
+def test_bit_identical_runs_odd_order(sim_engine):
+    As = kc.mkmats1(257, 2, xpnd=1.05, seed=23, unit=True)
+    kw = dict(mindim=6, maxdim=12, tol=1e-10, restarts=60, seed=9)
+    kc.same_bits(*sim_engine.partial_pschur(As, 4, "LM", **kw), *sim_engine.partial_pschur(As, 4, "LM", **kw))
