@@ -218,17 +218,24 @@ int batch_buffers(int& g, size_t per_doubles, int nbufs, psd_batchbuf* dev, psd_
     }
 }
 
-// the factors of problems [q0, q0 + g) between the caller's matrices and one device buffer, through one staging buffer
-int batch_upload(psd_ctx* c, double* const* M, int q0, int g, int p, size_t nn, double* host, double* dev) {
-    for (size_t k = 0; k < (size_t)g * p; ++k) memcpy(host + k * nn, M[(size_t)q0 * p + k], nn * sizeof(double));
+// the factors of problems [q0, q0 + g) between the caller's matrices and one device buffer, through one staging buffer;
+// slot (0-based, as ord_slots returns it; null: the identity): the caller's factor slot[j] of a problem is its device block j
+int batch_upload(psd_ctx* c, double* const* M, int q0, int g, int p, size_t nn, double* host, double* dev,
+                 const int* slot = nullptr) {
+    for (size_t q = 0; q < (size_t)g; ++q)
+        for (int j = 0; j < p; ++j)
+            memcpy(host + (q * p + j) * nn, M[(q0 + q) * p + (slot ? slot[j] : j)], nn * sizeof(double));
     PSD_CHECK(psd_rt_h2d(dev, host, sizeof(double) * nn * p * g, c->stream));
     PSD_CHECK(psd_rt_sync(c->stream));  // (the staging buffer is reused)
     return 0;
 }
-int batch_download(psd_ctx* c, double* const* M, int q0, int g, int p, size_t nn, double* host, const double* dev) {
+int batch_download(psd_ctx* c, double* const* M, int q0, int g, int p, size_t nn, double* host, const double* dev,
+                   const int* slot = nullptr) {
     PSD_CHECK(psd_rt_d2h(host, dev, sizeof(double) * nn * p * g, c->stream));
     PSD_CHECK(psd_rt_sync(c->stream));
-    for (size_t k = 0; k < (size_t)g * p; ++k) memcpy(M[(size_t)q0 * p + k], host + k * nn, nn * sizeof(double));
+    for (size_t q = 0; q < (size_t)g; ++q)
+        for (int j = 0; j < p; ++j)
+            memcpy(M[(q0 + q) * p + (slot ? slot[j] : j)], host + (q * p + j) * nn, nn * sizeof(double));
     return 0;
 }
 

@@ -14,13 +14,7 @@ namespace {
 // (PSD_BORD_SPAN1: the LDS of rows that no window reaches would only keep other problems off the CU); PSD_BORD_W
 // narrows it
 int bord_window(const psd_ctx* c, int n, int p) {
-    const int cand[] = {32, 24, 20, 16, 12, 10, 8, 6};
-    int W = 0;
-    for (int w : cand) {
-        if (rord_lds_bytes(p, w) > 155 * 1024) continue;
-        if (W == 0) W = w;              // the widest that fits
-        if (w >= n) W = w;              // ... or a narrower one that still holds the problem
-    }
+    int W = choose_window_rord(p, n);
     if (W > PSD_BORD_SPAN1) W = PSD_BORD_SPAN1;
     if (W != 0 && c->bord_w >= 6 && c->bord_w < W) W = c->bord_w;
     return W;
@@ -83,13 +77,7 @@ int bord_group(psd_ctx* c, int gc, int n, int p, double* dH, double* dZ, const u
     }
     const int W = bord_window(c, n, p);
     const size_t lds = rord_lds_bytes(p, W);
-#ifndef PSD_HOSTSIM
-    if (lds > c->bord_lds_set) {
-        PSD_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(psd_bord), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)lds));
-        c->bord_lds_set = lds;
-    }
-#endif
+    PSD_CHECK(c->lds_limit(reinterpret_cast<const void*>(psd_bord), lds));
     PSD_CHECK(psd_rt_h2d(ws.sel.ptr, select, (size_t)gc * n, c->stream));
     psd_bord_args a;
     a.H = dH;
@@ -288,37 +276,19 @@ int psd_d_ordschur_batch(psd_ctx* c, int nb, int n, int p, double* const* T, dou
     std::vector<int> linfo(infos ? 0 : nb, 0);
     int* pinfos = infos ? infos : linfo.data();
     Timer tc;
-    // user slot <-> internal slot on the way through the staging buffer, as psd_d_ordschur copies
-    auto copy = [&](double* const* M, const std::vector<int>& slot, int q0, int gc, double* dev, bool up) -> int {
-        if (!up) {
-            PSD_CHECK(psd_rt_d2h(hst.d(), dev, sizeof(double) * nn * p * gc, c->stream));
-            PSD_CHECK(psd_rt_sync(c->stream));
-        }
-        for (int q = 0; q < gc; ++q)
-            for (int j = 0; j < p; ++j) {
-                double* h = hst.d() + ((size_t)q * p + j) * nn;
-                double* u = M[(size_t)(q0 + q) * p + slot[j]];
-                if (up) memcpy(h, u, nn * sizeof(double));
-                else memcpy(u, h, nn * sizeof(double));
-            }
-        if (up) {
-            PSD_CHECK(psd_rt_h2d(dev, hst.d(), sizeof(double) * nn * p * gc, c->stream));
-            PSD_CHECK(psd_rt_sync(c->stream));  // (the staging buffer is reused)
-        }
-        return 0;
-    };
     for (int q0 = 0; q0 < nb; q0 += g) {
         const int gc = (nb - q0 < g) ? (nb - q0) : g;
         tc.start(c->stream);
-        if ((*info = copy(T, slotA, q0, gc, dbuf[0].d(), true)) != 0) return *info;
-        if (wantZ && (*info = copy(Z, slotZ, q0, gc, dbuf[1].d(), true)) != 0) return *info;
+        // user slot <-> internal slot on the way through the staging buffer, as psd_d_ordschur copies
+        if ((*info = batch_upload(c, T, q0, gc, p, nn, hst.d(), dbuf[0].d(), slotA.data())) != 0) return *info;
+        if (wantZ && (*info = batch_upload(c, Z, q0, gc, p, nn, hst.d(), dbuf[1].d(), slotZ.data())) != 0) return *info;
         double ms_copy = tc.stop(c->stream);
         *info = bord_group(c, gc, n, p, dbuf[0].d(), wantZ ? dbuf[1].d() : nullptr, select + (size_t)q0 * n, wantZ,
                            wr + (size_t)q0 * n, wi + (size_t)q0 * n, pinfos + q0, nswaps ? nswaps + q0 : nullptr, s, ws);
         if (*info != 0) return *info;
         tc.start(c->stream);
-        if ((*info = copy(T, slotA, q0, gc, dbuf[0].d(), false)) != 0) return *info;
-        if (wantZ && (*info = copy(Z, slotZ, q0, gc, dbuf[1].d(), false)) != 0) return *info;
+        if ((*info = batch_download(c, T, q0, gc, p, nn, hst.d(), dbuf[0].d(), slotA.data())) != 0) return *info;
+        if (wantZ && (*info = batch_download(c, Z, q0, gc, p, nn, hst.d(), dbuf[1].d(), slotZ.data())) != 0) return *info;
         ms_copy += tc.stop(c->stream);
         s->ms_copy += ms_copy;
     }

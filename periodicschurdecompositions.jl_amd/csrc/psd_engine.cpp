@@ -28,6 +28,8 @@
 #include "../../include/psd_mi355x.h"
 
 #include <chrono>
+#include <climits>
+#include <initializer_list>
 #include <new>
 #include <vector>
 
@@ -172,7 +174,24 @@ struct psd_ctx {
     int* cnt = nullptr;
     int* log = nullptr;
     int logcap = 0;
-    size_t step_lds_set = 0, zstep_lds_set = 0, rostep_lds_set = 0;
+    // Dynamic-LDS limits raised so far, per kernel (the runtime's own code of a failed call; nothing to do in the serial
+    // simulation).  The attribute is an upper limit and every launch passes its own dynamic size, so it only ever needs
+    // raising: a smaller request leaves it alone.
+    std::vector<std::pair<const void*, size_t>> lds_set;
+    int lds_limit(const void* kernel, size_t bytes) {
+#ifndef PSD_HOSTSIM
+        auto it = lds_set.begin();
+        while (it != lds_set.end() && it->first != kernel) ++it;
+        if (it == lds_set.end()) it = lds_set.insert(it, {kernel, (size_t)0});
+        if (bytes <= it->second) return 0;
+        if (int e = (int)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes)) return e;
+        it->second = bytes;
+#else
+        (void)kernel;
+        (void)bytes;
+#endif
+        return 0;
+    }
     psd_hess_args* hargs = nullptr;  // device argument block of the graph-replayed Hessenberg reduction
     // multishift trains: bulges per train (0/1 = off), per-cursor state / descriptor / lists
     int ztrain_m = 48;  // complex single-shift engine (shifts from a block of order <= PSD_ZHQR_MAX, reused by longer trains) (psd_set_train sets both; psd_set_train_z / PSD_TRAIN_Z this one)
@@ -270,7 +289,6 @@ struct psd_ctx {
     int bev_nmax = PSD_BEV_NMAX;  // largest order of the batched eigenvector kernels (diagnostic build: PSD_BEV_NMAX in the environment, for the sweep that sets the constant)
     int bord_nmax = PSD_BORD_NMAX;  // largest order of the batched reordering kernel (PSD_BORD_NMAX in the environment lowers it: the tests reach the fallback with it)
     int bord_w = 0;                 // PSD_BORD_W: a narrower window of the batched reordering kernel (0: bord_window's own choice)
-    size_t bord_lds_set = 0;
     void slice(int p, int& lo, int& hi) const {  // [lo, hi), 0-based internal factor index
         const int base = p / shard_world, rem = p % shard_world;
         lo = shard_rank * base + (shard_rank < rem ? shard_rank : rem);
@@ -321,7 +339,6 @@ struct psd_ctx {
     int chase2 = 1;           // two-wave chase of the real periodic QR sweep (psd_c2_run; PSD_C2=0: one wavefront per bulge)
     int apply_wl2 = 1;        // register-line form of the work-list bulk apply (psd_apply2.h) where it is the faster one; PSD_APPLY_WL2=0: never, 2: always
     int apply_wl2_grid = 1024;  // its grid of four-wave workgroups (PSD_APPLY_WL2_GRID)
-    size_t wl2_lds_set[3] = {0, 0, 0};
     psd_rostate* rost = nullptr;
     psd_tq* rotq = nullptr;
     unsigned char* rosel = nullptr;
@@ -334,7 +351,6 @@ struct psd_ctx {
     int* rocnt_mb = nullptr;
     psd_apply_desc* rodesc_mb = nullptr;
     int ord_pipe = 1;  // PSD_ORD_PIPE=0: one selected block at a time (psd_rord_step)
-    size_t rostep_mb_lds_set = 0;
     int rocap_n = 0, rocap_p = 0;
     // complex path
     int zcap_n = 0, zcap_p = 0, zlogcap = 0;
@@ -350,9 +366,7 @@ struct psd_ctx {
     psd_ostate* ombst = nullptr;
     psd_oslot* oslots = nullptr;
     psd_omb* omb = nullptr;
-    size_t ostep_mb_lds_set = 0, zgostep_mb_lds_set = 0;
     unsigned char* osel = nullptr;
-    size_t ostep_lds_set = 0;
     // real generalized path
     int gcap_n = 0, gcap_p = 0, glogcap = 0;
     psd_gstate* gst = nullptr;
@@ -362,7 +376,6 @@ struct psd_ctx {
     psd_z* galpha = nullptr;
     double *gbeta = nullptr, *gxscr = nullptr;
     int *gascale = nullptr, *gcnt = nullptr, *glog = nullptr;
-    size_t gstep_lds_set = 0, ghess_lds_set = 0;
     // multishift trains of the real signed engine (psd_set_train sets all engines; psd_set_train_g / PSD_TRAIN_G this one)
     int gtrain_m = 48, gtcap_p = 0;  // (real signed engine: 48 bulges W positions apart; the complex signed one caps at 16)
     psd_gstate* gtcst = nullptr;
@@ -395,7 +408,6 @@ struct psd_ctx {
     psd_ztr *zgtr = nullptr, *zgdG = nullptr;
     unsigned char* zgS = nullptr;
     int* zgcnt = nullptr;
-    size_t zgstep_lds_set = 0, zgostep_lds_set = 0, zghess_lds_set = 0;
     // multishift trains of the complex signed engine (width: gtrain_m, as the real signed engine)
     int zgtcap_p = 0;
     psd_zgstate* zgtcst = nullptr;
@@ -1109,10 +1121,7 @@ int launch_apply_wl(psd_ctx* c, psd_stream_t stream, const psd_rparams& Pq, int 
             kern = psd_rq_apply_wl2<32, 2>;
             slot = 2;
         }
-        if (lb > c->wl2_lds_set[slot]) {
-            PSD_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb));
-            c->wl2_lds_set[slot] = lb;
-        }
+        PSD_CHECK(c->lds_limit(reinterpret_cast<const void*>(kern), lb));
         hipLaunchKernelGGL(kern, dim3(g), dim3(PSD_WL2_NT), lb, stream, Pq, n, p, p + 8, pass, NSL, zlo1, zhi1, mode);
         return 0;
     }
@@ -1160,13 +1169,7 @@ int iterate_dev(psd_ctx* c, int n, int p, double* dH, double* dZ, int wantT, int
     P.wi = c->wi;
     P.log = c->log;
     const size_t lds_step = step_lds_bytes(p, W, 8, true);
-#ifndef PSD_HOSTSIM
-    if (lds_step > c->step_lds_set) {
-        PSD_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(psd_rq_step),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_step));
-        c->step_lds_set = lds_step;
-    }
-#endif
+    PSD_CHECK(c->lds_limit(reinterpret_cast<const void*>(psd_rq_step), lds_step));
     // multishift trains (default: up to 32 bulges; psd_set_train / PSD_TRAIN): M cursors, each with its own state,
     // descriptor and lists; cursor 0 is the ordinary state machine
     const int M = (c->train_m >= 2) ? ((c->train_m > PSD_TRAIN_MAX) ? PSD_TRAIN_MAX : c->train_m) : 1;
@@ -1286,12 +1289,8 @@ int iterate_dev(psd_ctx* c, int n, int p, double* dH, double* dZ, int wantT, int
             if (c->train_stop) P.ccancel = c->tslotw + 6 * PSD_SLOTS;
             P.plan = c->tslotw + 8 * PSD_SLOTS;
         }
-#ifndef PSD_HOSTSIM
-        PSD_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(psd_rq_step_train),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_step));
-        PSD_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(psd_rq_step_mb),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_step));
-#endif
+        PSD_CHECK(c->lds_limit(reinterpret_cast<const void*>(psd_rq_step_train), lds_step));
+        PSD_CHECK(c->lds_limit(reinterpret_cast<const void*>(psd_rq_step_mb), lds_step));
     }
     int train_oc = 104;
     if (const char* e = psd_env_diag("PSD_TRAIN_OC")) train_oc = atoi(e);  // (tuning hook)
@@ -1639,6 +1638,23 @@ int check_dims(int n, int p) {
     return 0;
 }
 
+// Staging of the host entry points: p blocks of `bytes` each between the caller's matrices and a contiguous device buffer,
+// one asynchronous copy per block on c->stream, straight from / into the caller's memory, blocks in the order 0 .. p-1.
+// slot (0-based, as ord_slots returns it; null: the identity): M[slot[j]] is the caller's matrix of device block j.
+// They return the runtime's code of the first copy that fails; the caller waits for the stream where it needs the data.
+template <class T>
+int stage_in(psd_ctx* c, void* dev, T* const* M, int p, size_t bytes, const int* slot = nullptr) {
+    for (int j = 0; j < p; ++j)
+        if (int e = psd_rt_h2d((char*)dev + j * bytes, M[slot ? slot[j] : j], bytes, c->stream)) return e;
+    return 0;
+}
+template <class T>
+int stage_out(psd_ctx* c, T* const* M, const void* dev, int p, size_t bytes, const int* slot = nullptr) {
+    for (int j = 0; j < p; ++j)
+        if (int e = psd_rt_d2h(M[slot ? slot[j] : j], (const char*)dev + j * bytes, bytes, c->stream)) return e;
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1876,13 +1892,13 @@ int psd_d_phessenberg(psd_ctx* c, int n, int p, double* const* A, double* tau, p
     const size_t nn = (size_t)n * n;
     Timer tc, tk;
     tc.start(c->stream);
-    for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_h2d(c->dH + j * nn, A[j], nn * 8, c->stream));
+    PSD_CHECK(stage_in(c, c->dH, A, p, nn * 8));
     double ms_copy = tc.stop(c->stream);
     tk.start(c->stream);
     if ((*info = hessenberg_dev(c, n, p, c->dH, c->tau)) != 0) return *info;
     double ms = tk.stop(c->stream);
     tc.start(c->stream);
-    for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_d2h(A[j], c->dH + j * nn, nn * 8, c->stream));
+    PSD_CHECK(stage_out(c, A, c->dH, p, nn * 8));
     PSD_CHECK(psd_rt_d2h(tau, c->tau, sizeof(double) * (size_t)n * p, c->stream));
     PSD_CHECK(psd_rt_sync(c->stream));
     ms_copy += tc.stop(c->stream);
@@ -1965,7 +1981,7 @@ int psd_d_pschur(psd_ctx* c, int n, int p, double* const* A, const uint8_t* S, c
     const size_t nn = (size_t)n * n;
     Timer tc;
     tc.start(c->stream);
-    for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_h2d(c->dH + j * nn, A[j], nn * 8, c->stream));
+    PSD_CHECK(stage_in(c, c->dH, A, p, nn * 8));
     double ms_copy = tc.stop(c->stream);
     psd_stats local;
     psd_stats* s = stats ? stats : &local;
@@ -1973,9 +1989,8 @@ int psd_d_pschur(psd_ctx* c, int n, int p, double* const* A, const uint8_t* S, c
                               schurindex, s, sweeplog, maxlog, info);
     if (rc < 0 || rc >= PSD_INFO_NOTIMPL) return rc;
     tc.start(c->stream);
-    for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_d2h(A[j], c->dH + j * nn, nn * 8, c->stream));
-    if (wantZ)
-        for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_d2h(Z[j], c->dZ + j * nn, nn * 8, c->stream));
+    PSD_CHECK(stage_out(c, A, c->dH, p, nn * 8));
+    if (wantZ) PSD_CHECK(stage_out(c, Z, c->dZ, p, nn * 8));
     PSD_CHECK(psd_rt_sync(c->stream));
     ms_copy += tc.stop(c->stream);
     s->ms_copy = ms_copy;
@@ -1995,9 +2010,8 @@ int psd_d_pschur_hess(psd_ctx* c, int n, int p, double* const* H, double* const*
     const int mlog = 2 * maxitfac * n + n + 16;
     if ((*info = c->reserve(n, p, true, mlog)) != 0) return *info;
     const size_t nn = (size_t)n * n;
-    for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_h2d(c->dH + j * nn, H[j], nn * 8, c->stream));
-    if (wantZ)
-        for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_h2d(c->dZ + j * nn, Q[j], nn * 8, c->stream));
+    PSD_CHECK(stage_in(c, c->dH, H, p, nn * 8));
+    if (wantZ) PSD_CHECK(stage_in(c, c->dZ, Q, p, nn * 8));
     psd_stats local;
     memset(&local, 0, sizeof(local));
     psd_stats* s = stats ? stats : &local;
@@ -2007,9 +2021,8 @@ int psd_d_pschur_hess(psd_ctx* c, int n, int p, double* const* H, double* const*
                            info);
     s->ms_iter = s->ms_total = t.stop(c->stream);
     if (rc < 0 || rc >= PSD_INFO_NOTIMPL) return rc;
-    for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_d2h(H[j], c->dH + j * nn, nn * 8, c->stream));
-    if (wantZ)
-        for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_d2h(Q[j], c->dZ + j * nn, nn * 8, c->stream));
+    PSD_CHECK(stage_out(c, H, c->dH, p, nn * 8));
+    if (wantZ) PSD_CHECK(stage_out(c, Q, c->dZ, p, nn * 8));
     PSD_CHECK(psd_rt_sync(c->stream));
     return rc;
 }
@@ -2124,13 +2137,7 @@ int ziterate_dev(psd_ctx* c, int n, int p, psd_z* dH, psd_z* dZ, int wantT, int 
     P.zslG = 1;
     P.zslmem = nullptr;
     P.zslerr = nullptr;
-#ifndef PSD_HOSTSIM
-    if (lds_step > c->zstep_lds_set) {
-        PSD_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(psd_zq_step),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_step));
-        c->zstep_lds_set = lds_step;
-    }
-#endif
+    PSD_CHECK(c->lds_limit(reinterpret_cast<const void*>(psd_zq_step), lds_step));
     // multishift trains (see iterate_dev): cursor 0 = slot 0 of the cursor arrays
     const int M = (c->ztrain_m >= 2) ? ((c->ztrain_m > PSD_TRAIN_MAX) ? PSD_TRAIN_MAX : c->ztrain_m) : 1;
     P.cst = nullptr;
@@ -2147,10 +2154,7 @@ int ziterate_dev(psd_ctx* c, int n, int p, psd_z* dH, psd_z* dZ, int wantT, int 
         P.desc = c->ztdesc;
         P.cnt = c->ztcnt;
         P.tr = c->zttr;
-#ifndef PSD_HOSTSIM
-        PSD_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(psd_zq_step_train),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_step));
-#endif
+        PSD_CHECK(c->lds_limit(reinterpret_cast<const void*>(psd_zq_step_train), lds_step));
     }
     // factor-sliced sweep windows (psd_set_slices; psd_zslice3.h): G workgroups per cursor slot; needs the scan chase,
     // the train kernel and at least two factors per slice
@@ -2428,13 +2432,7 @@ int zgiterate_dev(psd_ctx* c, int n, int p, psd_z* dH, psd_z* dZ, const uint8_t*
     P.ascale = c->zascale;
     P.log = c->zlog;
     const size_t lds_step = step_lds_bytes(p, W, 16);
-#ifndef PSD_HOSTSIM
-    if (lds_step > c->zgstep_lds_set) {
-        PSD_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(psd_zgq_step),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_step));
-        c->zgstep_lds_set = lds_step;
-    }
-#endif
+    PSD_CHECK(c->lds_limit(reinterpret_cast<const void*>(psd_zgq_step), lds_step));
     // stage 2 of the signed Hessenberg reduction: pipeline over the factors (see giterate_dev)
     const size_t lds_hess = psd_zghess_lds_bytes(p, W);
     const int hess_links = psd_ghess_links(p), hess_waves = psd_ghess_waves(p);
@@ -2444,13 +2442,7 @@ int zgiterate_dev(psd_ctx* c, int n, int p, psd_z* dH, psd_z* dZ, const uint8_t*
     int hess_scan = 1;
     if (const char* e = psd_env("PSD_HESS_SCAN")) hess_scan = atoi(e);
     (void)hess_scan;
-#ifndef PSD_HOSTSIM
-    if (hess_pipe && lds_hess > c->zghess_lds_set) {
-        PSD_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(psd_zgq_hess_step),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_hess));
-        c->zghess_lds_set = lds_hess;
-    }
-#endif
+    if (hess_pipe) PSD_CHECK(c->lds_limit(reinterpret_cast<const void*>(psd_zgq_hess_step), lds_hess));
     // multishift trains (as giterate_dev)
     const int tw = hessmode ? 0 : c->gtrain_m;
     const int Mcap = (PSD_ZHQR_MAX < PSD_TRAIN_MAX) ? PSD_ZHQR_MAX : PSD_TRAIN_MAX;
@@ -2470,10 +2462,7 @@ int zgiterate_dev(psd_ctx* c, int n, int p, psd_z* dH, psd_z* dZ, const uint8_t*
             P.desc = c->zgtdesc;
             P.cnt = c->zgtcnt;
             P.tr = c->zgttr;
-#ifndef PSD_HOSTSIM
-            PSD_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(psd_zgq_step_train),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_step));
-#endif
+            PSD_CHECK(c->lds_limit(reinterpret_cast<const void*>(psd_zgq_step_train), lds_step));
         }
     }
     int train_oc = 50;
@@ -2629,16 +2618,16 @@ int zsigned_pschur_host(psd_ctx* c, int n, int p, double* const* A, const uint8_
                         psd_stats* stats, int* info) {
     if (maxitfac < 1) return *info = -9;
     const bool left = orient == 'L';
-    auto slotA = [&](int j) { return left ? (p + 1 - j) : j; };
-    auto slotZ = [&](int j) { return (!left || j == 1) ? j : (p + 2 - j); };  // generalized.jl:910-927
+    std::vector<int> sA, sZ;  // the reversal of generalized.jl:910-927 for 'L' (schurindex p), the identity for 'R'
+    ord_slots(orient, left ? p : 1, p, sA, sZ);
     std::vector<uint8_t> Sarg(p, 1);
-    for (int j = 1; j <= p; ++j) Sarg[j - 1] = S[slotA(j) - 1] ? 1 : 0;
+    for (int j = 0; j < p; ++j) Sarg[j] = S[sA[j]] ? 1 : 0;
     if (!Sarg[0]) return *info = -5;  // generalized.jl:140
     const int mlog = 2 * maxitfac * n + n + 16;
     if ((*info = c->zreserve(n, p, true, mlog)) != 0) return *info;
     if ((*info = c->zgreserve(n, p)) != 0) return *info;
     const size_t nn = (size_t)n * n;
-    for (int j = 1; j <= p; ++j) PSD_CHECK(psd_rt_h2d(c->zH + (size_t)(j - 1) * nn, A[slotA(j) - 1], nn * 16, c->stream));
+    PSD_CHECK(stage_in(c, c->zH, A, p, nn * 16, sA.data()));
     psd_stats local;
     memset(&local, 0, sizeof(local));
     psd_stats* s = stats ? stats : &local;
@@ -2657,10 +2646,8 @@ int zsigned_pschur_host(psd_ctx* c, int n, int p, double* const* A, const uint8_
     s->ms_total = tt.stop(c->stream);
     if (schurindex) *schurindex = left ? p : 1;
     if (rc < 0 || rc >= PSD_INFO_NOTIMPL) return rc;
-    for (int j = 1; j <= p; ++j) PSD_CHECK(psd_rt_d2h(A[slotA(j) - 1], c->zH + (size_t)(j - 1) * nn, nn * 16, c->stream));
-    if (wantZ)
-        for (int j = 1; j <= p; ++j)
-            PSD_CHECK(psd_rt_d2h(Z[slotZ(j) - 1], c->zZ + (size_t)(j - 1) * nn, nn * 16, c->stream));
+    PSD_CHECK(stage_out(c, A, c->zH, p, nn * 16, sA.data()));
+    if (wantZ) PSD_CHECK(stage_out(c, Z, c->zZ, p, nn * 16, sZ.data()));
     PSD_CHECK(psd_rt_sync(c->stream));
     return rc;
 }
@@ -2672,9 +2659,8 @@ int zsigned_hess_host(psd_ctx* c, int n, int p, double* const* H, const uint8_t*
     if ((*info = c->zreserve(n, p, true, mlog)) != 0) return *info;
     if ((*info = c->zgreserve(n, p)) != 0) return *info;
     const size_t nn = (size_t)n * n;
-    for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_h2d(c->zH + j * nn, H[j], nn * 16, c->stream));
-    if (wantZ)
-        for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_h2d(c->zZ + j * nn, Q[j], nn * 16, c->stream));
+    PSD_CHECK(stage_in(c, c->zH, H, p, nn * 16));
+    if (wantZ) PSD_CHECK(stage_in(c, c->zZ, Q, p, nn * 16));
     psd_stats local;
     memset(&local, 0, sizeof(local));
     psd_stats* s = stats ? stats : &local;
@@ -2684,9 +2670,8 @@ int zsigned_hess_host(psd_ctx* c, int n, int p, double* const* H, const uint8_t*
                              info);
     s->ms_iter = s->ms_total = t.stop(c->stream);
     if (rc < 0 || rc >= PSD_INFO_NOTIMPL) return rc;
-    for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_d2h(H[j], c->zH + j * nn, nn * 16, c->stream));
-    if (wantZ)
-        for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_d2h(Q[j], c->zZ + j * nn, nn * 16, c->stream));
+    PSD_CHECK(stage_out(c, H, c->zH, p, nn * 16));
+    if (wantZ) PSD_CHECK(stage_out(c, Q, c->zZ, p, nn * 16));
     PSD_CHECK(psd_rt_sync(c->stream));
     return rc;
 }
@@ -2708,12 +2693,11 @@ int psd_z_gphessenberg(psd_ctx* c, int n, int p, double* const* A, const uint8_t
     if ((*info = c->zreserve(n, p, true, 16)) != 0) return *info;
     if ((*info = c->zgreserve(n, p)) != 0) return *info;
     const size_t nn = (size_t)n * n;
-    for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_h2d(c->zH + j * nn, A[j], nn * 16, c->stream));
+    PSD_CHECK(stage_in(c, c->zH, A, p, nn * 16));
     *info = zsghess_dev(c, n, p, c->zH, Q ? c->zZ : nullptr, S, stats);
     if (*info != 0) return *info;
-    for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_d2h(A[j], c->zH + j * nn, nn * 16, c->stream));
-    if (Q)
-        for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_d2h(Q[j], c->zZ + j * nn, nn * 16, c->stream));
+    PSD_CHECK(stage_out(c, A, c->zH, p, nn * 16));
+    if (Q) PSD_CHECK(stage_out(c, Q, c->zZ, p, nn * 16));
     PSD_CHECK(psd_rt_sync(c->stream));
     return 0;
 }
@@ -2727,12 +2711,12 @@ int psd_z_phessenberg(psd_ctx* c, int n, int p, double* const* A, double* tau, p
     if (!A || !tau) return *info = -4;
     if ((*info = c->zreserve(n, p, true, 16)) != 0) return *info;
     const size_t nn = (size_t)n * n;
-    for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_h2d(c->zH + j * nn, A[j], nn * 16, c->stream));
+    PSD_CHECK(stage_in(c, c->zH, A, p, nn * 16));
     Timer tk;
     tk.start(c->stream);
     if ((*info = zhessenberg_dev(c, n, p, c->zH, c->ztau)) != 0) return *info;
     const double ms = tk.stop(c->stream);
-    for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_d2h(A[j], c->zH + j * nn, nn * 16, c->stream));
+    PSD_CHECK(stage_out(c, A, c->zH, p, nn * 16));
     PSD_CHECK(psd_rt_d2h(tau, c->ztau, sizeof(psd_z) * (size_t)n * p, c->stream));
     PSD_CHECK(psd_rt_sync(c->stream));
     PSD_CHECK(psd_rt_last_error());
@@ -2815,7 +2799,7 @@ int psd_z_pschur(psd_ctx* c, int n, int p, double* const* A, const uint8_t* S, c
     const size_t nn = (size_t)n * n;
     Timer tc;
     tc.start(c->stream);
-    for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_h2d(c->zH + j * nn, A[j], nn * 16, c->stream));
+    PSD_CHECK(stage_in(c, c->zH, A, p, nn * 16));
     double ms_copy = tc.stop(c->stream);
     psd_stats local;
     psd_stats* s = stats ? stats : &local;
@@ -2824,9 +2808,8 @@ int psd_z_pschur(psd_ctx* c, int n, int p, double* const* A, const uint8_t* S, c
                               sweeplog, maxlog, info);
     if (rc < 0 || rc >= PSD_INFO_NOTIMPL) return rc;
     tc.start(c->stream);
-    for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_d2h(A[j], c->zH + j * nn, nn * 16, c->stream));
-    if (wantZ)
-        for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_d2h(Z[j], c->zZ + j * nn, nn * 16, c->stream));
+    PSD_CHECK(stage_out(c, A, c->zH, p, nn * 16));
+    if (wantZ) PSD_CHECK(stage_out(c, Z, c->zZ, p, nn * 16));
     PSD_CHECK(psd_rt_sync(c->stream));
     ms_copy += tc.stop(c->stream);
     s->ms_copy = ms_copy;
@@ -2853,9 +2836,8 @@ int psd_z_pschur_hess(psd_ctx* c, int n, int p, double* const* H, const uint8_t*
     const int mlog = 2 * maxitfac * n + n + 16;
     if ((*info = c->zreserve(n, p, true, mlog)) != 0) return *info;
     const size_t nn = (size_t)n * n;
-    for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_h2d(c->zH + j * nn, H[j], nn * 16, c->stream));
-    if (wantZ)
-        for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_h2d(c->zZ + j * nn, Q[j], nn * 16, c->stream));
+    PSD_CHECK(stage_in(c, c->zH, H, p, nn * 16));
+    if (wantZ) PSD_CHECK(stage_in(c, c->zZ, Q, p, nn * 16));
     psd_stats local;
     memset(&local, 0, sizeof(local));
     psd_stats* s = stats ? stats : &local;
@@ -2865,14 +2847,133 @@ int psd_z_pschur_hess(psd_ctx* c, int n, int p, double* const* H, const uint8_t*
                             sweeplog, maxlog, info);
     s->ms_iter = s->ms_total = t.stop(c->stream);
     if (rc < 0 || rc >= PSD_INFO_NOTIMPL) return rc;
-    for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_d2h(H[j], c->zH + j * nn, nn * 16, c->stream));
-    if (wantZ)
-        for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_d2h(Q[j], c->zZ + j * nn, nn * 16, c->stream));
+    PSD_CHECK(stage_out(c, H, c->zH, p, nn * 16));
+    if (wantZ) PSD_CHECK(stage_out(c, Q, c->zZ, p, nn * 16));
     PSD_CHECK(psd_rt_sync(c->stream));
     return rc;
 }
 
 }  // extern "C"
+
+// =================================================================================================
+// ordschur!: what the three reordering drivers (complex, real, complex signed) share
+namespace {
+
+// Window of a reordering step kernel: the widest of `cand` (descending) whose LDS, by the engine's formula, fits — or a
+// narrower one that fits and still holds `hold` rows (psd_bord: a whole small problem).  0: none fits.
+template <class F>
+int choose_window_lds(std::initializer_list<int> cand, F lds_bytes, int hold = INT_MAX) {
+    int W = 0;
+    for (int w : cand) {
+        if (lds_bytes(w) > (size_t)155 * 1024) continue;
+        if (W == 0 || w >= hold) W = w;
+    }
+    return W;
+}
+
+// The selection goes up and the window is settled.  Pipelined drivers (psd_oslot / psd_roslot): the selected blocks
+// travel one window apart.  The tick lasts as long as its longest window, so with many blocks to move shorter windows
+// (more blocks under way) are the faster schedule.
+int ord_begin(psd_ctx* c, int n, const uint8_t* select, unsigned char* dsel, int& W) {
+    if (c->ord_pipe != 0) {
+        int nsel = 0;
+        for (int q = 0; q < n; ++q) nsel += select[q] ? 1 : 0;
+        if (nsel >= 8 && n >= 128 && W > 16) W = 16;
+    }
+    return psd_rt_h2d(dsel, select, (size_t)n, c->stream);
+}
+
+// Where an engine's states live on the device: the one state of the serial form (one selected block at a time,
+// PSD_ORD_PIPE=0), the scheduler state and the slots of the pipelined form; the phase that ends a run and the runtime
+// code of a run that does not end.
+template <class State, class Sched, class Slot>
+struct ord_dev {
+    const State* st;
+    const Sched* mb;
+    const Slot* slots;
+    int nslots, done, cap_code;
+};
+
+template <class State, class Slot>
+void ord_sum(State& s, const Slot& q) {
+    s.nswaps += q.nswaps;
+    s.nwindows += q.nwindows;
+}
+
+// (the real engine's slots also carry its cycle counters)
+void ord_sum(psd_rostate& s, const psd_roslot& q) {
+    ord_sum<psd_rostate, psd_roslot>(s, q);
+    for (int e = 0; e < 6; ++e) s.cyc[e] += q.cyc[e];
+}
+
+// One run of a reordering engine.  init(): the pipelined form's limits and the init kernel; tick(): the launches of one
+// tick; values(): the eigenvalue epilogue of a run that ended with info 0 (both return a code as PSD_CHECK makes it).
+// The host polls drained, every 32 ticks in the serial form and every 16 in the pipelined one, and gives up after `cap`
+// ticks.  hst: the final state (pipelined: info of the scheduler, counts summed over the slots).  Returns a runtime
+// code or 0; the engine maps hst.info.
+template <class State, class Sched, class Slot, class Init, class Tick, class Values>
+int ord_drive(psd_ctx* c, int W, long long cap, ord_dev<State, Sched, Slot> d, Init init, Tick tick, Values values,
+              State& hst, psd_stats* stats, int* info) {
+    const bool pipe = c->ord_pipe != 0;
+    memset(&hst, 0, sizeof(hst));
+    long long launched = 0;
+    Timer t;
+    t.start(c->stream);
+    if (int e = init()) return e;
+    Sched hg;
+    memset(&hg, 0, sizeof(hg));
+    for (;;) {
+        for (int b = 0; b < (pipe ? 16 : 32); ++b) {
+            tick();
+            ++launched;
+        }
+        if (pipe) PSD_CHECK(psd_rt_d2h(&hg, d.mb, sizeof(hg), c->stream));
+        else PSD_CHECK(psd_rt_d2h(&hst, d.st, sizeof(hst), c->stream));
+        PSD_CHECK(psd_rt_sync(c->stream));
+        if ((pipe ? hg.phase : hst.phase) == d.done) break;
+        if (launched > cap) return *info = PSD_INFO_RUNTIME + d.cap_code;
+    }
+    if (pipe) {
+        std::vector<Slot> hs(d.nslots);
+        PSD_CHECK(psd_rt_d2h(hs.data(), d.slots, sizeof(Slot) * d.nslots, c->stream));
+        PSD_CHECK(psd_rt_sync(c->stream));
+        hst.phase = d.done;
+        hst.info = hg.info;
+        for (const Slot& q : hs) ord_sum(hst, q);
+    }
+    if (hst.info == 0)
+        if (int e = values()) return e;
+    const double ms = t.stop(c->stream);
+    PSD_CHECK(psd_rt_last_error());
+    if (stats) {
+        stats->ms_iter = stats->ms_total = ms;
+        stats->nsweeps = hst.nswaps;  // adjacent swaps performed
+        stats->nwindows = hst.nwindows;
+        stats->nlaunch_step = (int32_t)launched;
+        stats->window = W;
+    }
+    return 0;
+}
+
+// the scaled eigenvalues of the complex and the signed engines come down (ascale through a host array of int)
+int ord_scaled_values(psd_ctx* c, int n, const psd_z* dalpha, const double* dbeta, const int* dascale, double* alpha,
+                      double* beta, int32_t* ascale) {
+    PSD_CHECK(psd_rt_d2h(alpha, dalpha, sizeof(psd_z) * n, c->stream));
+    PSD_CHECK(psd_rt_d2h(beta, dbeta, sizeof(double) * n, c->stream));
+    std::vector<int> hsc(n, 0);
+    PSD_CHECK(psd_rt_d2h(hsc.data(), dascale, sizeof(int) * n, c->stream));
+    PSD_CHECK(psd_rt_sync(c->stream));
+    for (int q = 0; q < n; ++q) ascale[q] = hsc[q];
+    return 0;
+}
+
+// what the complex standard and the complex signed engine have in common: the cap and the states of psd_ord1_plan
+long long zord_cap(int n, int W) { return (long long)n * ((long long)n / (W > 1 ? W - 1 : 1) + 2) + 1024; }
+ord_dev<psd_ostate, psd_omb, psd_ostate> zord_states(const psd_ctx* c, int cap_code) {
+    return {c->ost, c->omb, c->ombst, PSD_O_SLOTS, PSD_OPH_DONE, cap_code};
+}
+
+}  // namespace
 
 // =================================================================================================
 // ordschur! (complex)
@@ -2882,28 +2983,15 @@ size_t ord_lds_bytes(int p, int W) {
     size_t b = (size_t)p * W * (W + 1) * 16 + (size_t)13 * p * 16 + ((size_t)p + 2) * 8 + (size_t)p * 4 + 64;
     return (b + 15) & ~(size_t)15;
 }
-int choose_window_ord(int p) {
-    const int cand[] = {32, 24, 20, 16, 12, 10, 8, 6, 4};
-    for (int W : cand)
-        if (ord_lds_bytes(p, W) <= 155 * 1024) return W;
-    return 0;
-}
 
 // device arrays in internal right order; select on host
 int zordschur_dev(psd_ctx* c, int n, int p, psd_z* dH, psd_z* dZ, const uint8_t* select, int wantZ, double* alpha,
                   double* beta, int32_t* ascale, psd_stats* stats, int* info) {
-    int W = choose_window_ord(p);
+    int W = choose_window_lds({32, 24, 20, 16, 12, 10, 8, 6, 4}, [&](int w) { return ord_lds_bytes(p, w); });
     if (W == 0) return *info = PSD_INFO_NOTIMPL;
-    // pipelined driver (psd_oslot): the selected eigenvalues travel a window apart; with many of them shorter windows
-    // (the tick lasts as long as its longest window) are the faster schedule
     const bool pipe = c->ord_pipe != 0;
-    if (pipe) {
-        int nsel = 0;
-        for (int q = 0; q < n; ++q) nsel += select[q] ? 1 : 0;
-        if (nsel >= 8 && n >= 128 && W > 16) W = 16;
-        PSD_CHECK(c->ztreserve(p));
-    }
-    PSD_CHECK(psd_rt_h2d(c->osel, select, (size_t)n, c->stream));
+    if (pipe) PSD_CHECK(c->ztreserve(p));
+    PSD_CHECK(ord_begin(c, n, select, c->osel, W));
     psd_oparams O;
     O.z.H = dH;
     O.z.zlo = 1;  // (ordschur! is not sharded: every Z_m is this context's)
@@ -2915,108 +3003,55 @@ int zordschur_dev(psd_ctx* c, int n, int p, psd_z* dH, psd_z* dZ, const uint8_t*
     O.z.zslerr = nullptr;
     O.z.Z = wantZ ? dZ : nullptr;
     O.z.st = c->zst;
-    O.z.desc = c->zdesc;
-    O.z.tr = c->ztr;
-    O.z.cnt = c->zcnt;
+    O.z.desc = pipe ? c->ztdesc : c->zdesc;
+    O.z.tr = pipe ? c->zttr : c->ztr;
+    O.z.cnt = pipe ? c->ztcnt : c->zcnt;
     O.z.dG = c->zdG;
     O.z.alpha = c->zalpha;
     O.z.beta = c->zbeta;
     O.z.ascale = c->zascale;
     O.z.log = c->zlog;
-    O.st = c->ost;
+    O.st = pipe ? c->ombst : c->ost;
     O.select = c->osel;
     const size_t lds_step = ord_lds_bytes(p, W);
-#ifndef PSD_HOSTSIM
-    if (lds_step > c->ostep_lds_set) {
-        PSD_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(psd_zord_step),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_step));
-        c->ostep_lds_set = lds_step;
-    }
-#endif
+    PSD_CHECK(c->lds_limit(reinterpret_cast<const void*>(psd_zord_step), lds_step));
     const size_t lds_apply = PSD_ZTR_LDS_BYTES + (size_t)32 * (PSD_ZAPPLY_NT + 1) * sizeof(psd_z);
     const int tiles = (n + PSD_ZAPPLY_NT - 1) / PSD_ZAPPLY_NT;
-    psd_ostate hst;
-    memset(&hst, 0, sizeof(hst));
-    long long launched = 0;
-    const long long cap = (long long)n * ((long long)n / (W > 1 ? W - 1 : 1) + 2) + 1024;
-    Timer t;
-    t.start(c->stream);
-    if (pipe) {
-        O.st = c->ombst;
-        O.z.desc = c->ztdesc;
-        O.z.cnt = c->ztcnt;
-        O.z.tr = c->zttr;
 #ifndef PSD_HOSTSIM
-        if (lds_step > c->ostep_mb_lds_set) {
-            PSD_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(psd_zord_step_mb),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_step));
-            c->ostep_mb_lds_set = lds_step;
-        }
-        const int wl_grid = 2048;
+    const int wl_grid = 2048;
 #else
-        const int wl_grid = 6;
+    const int wl_grid = 6;
 #endif
-        const size_t lds_wl = lds_apply + sizeof(int) * 2 * (PSD_TRAIN_MAX + 2);
-        PSD_CHECK(psd_rt_memset(c->ztdesc, 0, sizeof(psd_zapply_desc) * PSD_TRAIN_MAX, c->stream));
-        PSD_LAUNCH(psd_ord1_init_mb, psd_dim3(1), 64, 0, c->stream, c->ombst, c->oslots, c->omb, n, p, wantZ, W);
-        psd_omb hg;
-        memset(&hg, 0, sizeof(hg));
-        for (;;) {
-            for (int b = 0; b < 16; ++b) {
-                PSD_LAUNCH(psd_ord1_plan, psd_dim3(1), 64, 0, c->stream, c->ombst, c->oslots, c->omb, c->osel);
-                PSD_LAUNCH(psd_zord_step_mb, psd_dim3(PSD_O_SLOTS), PSD_STEP_NT, lds_step, c->stream, O, p, p + 8);
-                // rows of every window, then columns (a row operation of one window meets a column operation of another in
-                // off-diagonal blocks), then the Schur vectors: the work-list form of the trains
-                for (int pass : {2, 1, 3})
-                    PSD_LAUNCH(psd_zq_apply_wl, psd_dim3(wl_grid), PSD_ZAPPLY_NT, lds_wl, c->stream, O.z, n, p, p + 8, pass, PSD_O_SLOTS, (int)lds_apply);
-                ++launched;
-            }
-            PSD_CHECK(psd_rt_d2h(&hg, c->omb, sizeof(hg), c->stream));
-            PSD_CHECK(psd_rt_sync(c->stream));
-            if (hg.phase == PSD_OPH_DONE) break;
-            if (launched > cap) return *info = PSD_INFO_RUNTIME + 0xfffd;
+    const size_t lds_wl = lds_apply + sizeof(int) * 2 * (PSD_TRAIN_MAX + 2);
+    auto init = [&]() -> int {
+        if (pipe) {
+            PSD_CHECK(c->lds_limit(reinterpret_cast<const void*>(psd_zord_step_mb), lds_step));
+            PSD_CHECK(psd_rt_memset(c->ztdesc, 0, sizeof(psd_zapply_desc) * PSD_TRAIN_MAX, c->stream));
+            PSD_LAUNCH(psd_ord1_init_mb, psd_dim3(1), 64, 0, c->stream, c->ombst, c->oslots, c->omb, n, p, wantZ, W);
+        } else {
+            PSD_LAUNCH(psd_zord_init, psd_dim3(1), 64, 0, c->stream, O, n, p, wantZ, W);
         }
-        std::vector<psd_ostate> hs(PSD_O_SLOTS);
-        PSD_CHECK(psd_rt_d2h(hs.data(), c->ombst, sizeof(psd_ostate) * PSD_O_SLOTS, c->stream));
-        PSD_CHECK(psd_rt_sync(c->stream));
-        hst.phase = PSD_OPH_DONE;
-        hst.info = hg.info;
-        for (const psd_ostate& q : hs) {
-            hst.nswaps += q.nswaps;
-            hst.nwindows += q.nwindows;
-        }
-    } else {
-    PSD_LAUNCH(psd_zord_init, psd_dim3(1), 64, 0, c->stream, O, n, p, wantZ, W);
-    for (;;) {
-        for (int b = 0; b < 32; ++b) {
+        return 0;
+    };
+    auto tick = [&]() {
+        if (pipe) {
+            PSD_LAUNCH(psd_ord1_plan, psd_dim3(1), 64, 0, c->stream, c->ombst, c->oslots, c->omb, c->osel);
+            PSD_LAUNCH(psd_zord_step_mb, psd_dim3(PSD_O_SLOTS), PSD_STEP_NT, lds_step, c->stream, O, p, p + 8);
+            // rows of every window, then columns (a row operation of one window meets a column operation of another in
+            // off-diagonal blocks), then the Schur vectors: the work-list form of the trains
+            for (int pass : {2, 1, 3})
+                PSD_LAUNCH(psd_zq_apply_wl, psd_dim3(wl_grid), PSD_ZAPPLY_NT, lds_wl, c->stream, O.z, n, p, p + 8, pass, PSD_O_SLOTS, (int)lds_apply);
+        } else {
             PSD_LAUNCH(psd_zord_step, psd_dim3(1), PSD_STEP_NT, lds_step, c->stream, O);
             PSD_LAUNCH(psd_zq_apply, psd_dim3(tiles, p, 3), PSD_ZAPPLY_NT, lds_apply, c->stream, O.z, n, p);
-            ++launched;
         }
-        PSD_CHECK(psd_rt_d2h(&hst, c->ost, sizeof(hst), c->stream));
-        PSD_CHECK(psd_rt_sync(c->stream));
-        if (hst.phase == PSD_OPH_DONE) break;
-        if (launched > cap) return *info = PSD_INFO_RUNTIME + 0xfffd;
-    }
-    }
-    if (hst.info == 0) {
+    };
+    auto values = [&]() -> int {
         PSD_LAUNCH(psd_zord_values, psd_dim3((n + 255) / 256), 256, 0, c->stream, O.z, n, p);
-        PSD_CHECK(psd_rt_d2h(alpha, c->zalpha, sizeof(psd_z) * n, c->stream));
-        PSD_CHECK(psd_rt_d2h(beta, c->zbeta, sizeof(double) * n, c->stream));
-        std::vector<int> hsc(n, 0);
-        PSD_CHECK(psd_rt_d2h(hsc.data(), c->zascale, sizeof(int) * n, c->stream));
-        PSD_CHECK(psd_rt_sync(c->stream));
-        for (int q = 0; q < n; ++q) ascale[q] = hsc[q];
-    }
-    const double ms = t.stop(c->stream);
-    PSD_CHECK(psd_rt_last_error());
-    if (stats) {
-        stats->ms_iter = stats->ms_total = ms;
-        stats->nsweeps = hst.nswaps;  // adjacent swaps performed
-        stats->nwindows = hst.nwindows;
-        stats->nlaunch_step = (int32_t)launched;
-        stats->window = W;
-    }
+        return ord_scaled_values(c, n, c->zalpha, c->zbeta, c->zascale, alpha, beta, ascale);
+    };
+    psd_ostate hst;
+    if (int rc = ord_drive(c, W, zord_cap(n, W), zord_states(c, 0xfffd), init, tick, values, hst, stats, info)) return rc;
     return *info = hst.info;  // 0, 2000+j (IllConditionedException(j)), 3000 (SingularException)
 }
 
@@ -3040,14 +3075,12 @@ int psd_z_ordschur(psd_ctx* c, int n, int p, double* const* T, double* const* Z,
     if (!ord_slots(orient, schurindex, p, slotA, slotZ)) return *info = -7;  // ArgumentError, ordschur.jl:32
     if ((*info = c->zreserve(n, p, true, 16)) != 0) return *info;
     const size_t nn = (size_t)n * n;
-    for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_h2d(c->zH + j * nn, T[slotA[j]], nn * 16, c->stream));
-    if (wantZ)
-        for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_h2d(c->zZ + j * nn, Z[slotZ[j]], nn * 16, c->stream));
+    PSD_CHECK(stage_in(c, c->zH, T, p, nn * 16, slotA.data()));
+    if (wantZ) PSD_CHECK(stage_in(c, c->zZ, Z, p, nn * 16, slotZ.data()));
     int rc = zordschur_dev(c, n, p, c->zH, c->zZ, select, wantZ, alpha, beta, ascale, stats, info);
     if (rc < 0 || rc >= PSD_INFO_NOTIMPL) return rc;
-    for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_d2h(T[slotA[j]], c->zH + j * nn, nn * 16, c->stream));
-    if (wantZ)
-        for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_d2h(Z[slotZ[j]], c->zZ + j * nn, nn * 16, c->stream));
+    PSD_CHECK(stage_out(c, T, c->zH, p, nn * 16, slotA.data()));
+    if (wantZ) PSD_CHECK(stage_out(c, Z, c->zZ, p, nn * 16, slotZ.data()));
     PSD_CHECK(psd_rt_sync(c->stream));
     return rc;
 }
@@ -3063,11 +3096,9 @@ size_t rord_lds_bytes(int p, int W) {
                (size_t)p * 5 + 80;
     return (b + 15) & ~(size_t)15;
 }
-int choose_window_rord(int p) {
-    const int cand[] = {32, 24, 20, 16, 12, 10, 8, 6};
-    for (int W : cand)
-        if (rord_lds_bytes(p, W) <= 155 * 1024) return W;
-    return 0;
+// (no window of 4: a 2x2 block and its target need more)
+int choose_window_rord(int p, int hold = INT_MAX) {
+    return choose_window_lds({32, 24, 20, 16, 12, 10, 8, 6}, [&](int w) { return rord_lds_bytes(p, w); }, hold);
 }
 
 // Sint != nullptr: GeneralizedPeriodicSchur (signed swaps), eigenvalues returned in the scaled form (alpha complex)
@@ -3077,14 +3108,7 @@ int rordschur_dev(psd_ctx* c, int n, int p, double* dH, double* dZ, const uint8_
     int W = choose_window_rord(p);
     if (W == 0) return *info = PSD_INFO_NOTIMPL;
     if ((*info = c->roreserve(n, p)) != 0) return *info;
-    // Pipelined driver (psd_roslot): the selected blocks travel one window apart.  The tick lasts as long as its longest
-    // window, so with many blocks to move shorter windows (more blocks under way) are the faster schedule.
     const bool pipe = c->ord_pipe != 0;
-    if (pipe) {
-        int nsel = 0;
-        for (int q = 0; q < n; ++q) nsel += select[q] ? 1 : 0;
-        if (nsel >= 8 && n >= 128 && W > 16) W = 16;
-    }
     if (Sint) {
         if ((*info = c->greserve(n, p, 16)) != 0) return *info;
         std::vector<unsigned char> hS(p, 1);
@@ -3092,16 +3116,16 @@ int rordschur_dev(psd_ctx* c, int n, int p, double* dH, double* dZ, const uint8_
         PSD_CHECK(psd_rt_h2d(c->gS, hS.data(), (size_t)p, c->stream));
         PSD_CHECK(psd_rt_sync(c->stream));
     }
-    PSD_CHECK(psd_rt_h2d(c->rosel, select, (size_t)n, c->stream));
+    PSD_CHECK(ord_begin(c, n, select, c->rosel, W));
     psd_roparams P;
-    P.mb = nullptr;
-    P.slots = nullptr;
+    P.mb = pipe ? c->romb : nullptr;
+    P.slots = pipe ? c->roslots : nullptr;
     P.H = dH;
     P.Z = wantZ ? dZ : nullptr;
     P.st = c->rost;
-    P.desc = c->desc;
-    P.tq = c->rotq;
-    P.cnt = c->cnt;
+    P.desc = pipe ? c->rodesc_mb : c->desc;
+    P.tq = pipe ? c->rotq_mb : c->rotq;
+    P.cnt = pipe ? c->rocnt_mb : c->cnt;
     P.select = c->rosel;
     P.wr = c->wr;
     P.wi = c->wi;
@@ -3111,100 +3135,48 @@ int rordschur_dev(psd_ctx* c, int n, int p, double* dH, double* dZ, const uint8_
     P.beta = Sint ? c->gbeta : nullptr;
     P.ascale = Sint ? c->gascale : nullptr;
     const size_t lds_step = rord_lds_bytes(p, W);
-#ifndef PSD_HOSTSIM
-    if (lds_step > c->rostep_lds_set) {
-        PSD_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(psd_rord_step),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_step));
-        c->rostep_lds_set = lds_step;
-    }
-#endif
+    PSD_CHECK(c->lds_limit(reinterpret_cast<const void*>(psd_rord_step), lds_step));
     const size_t lds_apply = sizeof(psd_tq) * PSD_RORD_CAP + (size_t)32 * (PSD_APPLY_NT + 1) * 8;
     const int tiles = (n + PSD_APPLY_NT - 1) / PSD_APPLY_NT;
-    psd_rostate hst;
-    memset(&hst, 0, sizeof(hst));
-    long long launched = 0;
     const long long cap = 2LL * n * ((long long)n / (W > 4 ? W - 4 : 1) + 2) + 1024;
-    Timer t;
-    t.start(c->stream);
-    if (pipe) {
-        P.mb = c->romb;
-        P.slots = c->roslots;
-        P.tq = c->rotq_mb;
-        P.cnt = c->rocnt_mb;
-        P.desc = c->rodesc_mb;
-#ifndef PSD_HOSTSIM
-        if (lds_step > c->rostep_mb_lds_set) {
-            PSD_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(psd_rord_step_mb),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_step));
-            c->rostep_mb_lds_set = lds_step;
+    auto init = [&]() -> int {
+        if (pipe) {
+            PSD_CHECK(c->lds_limit(reinterpret_cast<const void*>(psd_rord_step_mb), lds_step));
+            PSD_LAUNCH(psd_rord_init_mb, psd_dim3(1), 64, 0, c->stream, P, n, p, wantZ, W);
+        } else {
+            PSD_LAUNCH(psd_rord_init, psd_dim3(1), 64, 0, c->stream, P, n, p, wantZ, W);
         }
-#endif
-        PSD_LAUNCH(psd_rord_init_mb, psd_dim3(1), 64, 0, c->stream, P, n, p, wantZ, W);
-        psd_romb hg;
-        memset(&hg, 0, sizeof(hg));
-        for (;;) {
-            for (int b = 0; b < 16; ++b) {
-                PSD_LAUNCH(psd_rord_plan, psd_dim3(1), 64, 0, c->stream, P);
-                PSD_LAUNCH(psd_rord_step_mb, psd_dim3(PSD_RO_SLOTS), PSD_STEP_NT, lds_step, c->stream, P);
-                PSD_LAUNCH(psd_rord_apply_mb, psd_dim3(tiles, p, 3 * PSD_RO_SLOTS), PSD_APPLY_NT, lds_apply, c->stream, P, n, p, 0);
-                PSD_LAUNCH(psd_rord_apply_mb, psd_dim3(tiles, p, 3 * PSD_RO_SLOTS), PSD_APPLY_NT, lds_apply, c->stream, P, n, p, 1);
-                ++launched;
-            }
-            PSD_CHECK(psd_rt_d2h(&hg, c->romb, sizeof(hg), c->stream));
-            PSD_CHECK(psd_rt_sync(c->stream));
-            if (hg.phase == PSD_ROPH_DONE) break;
-            if (launched > cap) return *info = PSD_INFO_RUNTIME + 0xfffc;
-        }
-        std::vector<psd_roslot> hs(PSD_RO_SLOTS);
-        PSD_CHECK(psd_rt_d2h(hs.data(), c->roslots, sizeof(psd_roslot) * PSD_RO_SLOTS, c->stream));
-        PSD_CHECK(psd_rt_sync(c->stream));
-        hst.phase = PSD_ROPH_DONE;
-        hst.info = hg.info;
-        for (const psd_roslot& q : hs) {
-            hst.nswaps += q.nswaps;
-            hst.nwindows += q.nwindows;
-            for (int e = 0; e < 6; ++e) hst.cyc[e] += q.cyc[e];
-        }
-    } else {
-    PSD_LAUNCH(psd_rord_init, psd_dim3(1), 64, 0, c->stream, P, n, p, wantZ, W);
-    for (;;) {
-        for (int b = 0; b < 32; ++b) {
+        return 0;
+    };
+    auto tick = [&]() {
+        if (pipe) {
+            PSD_LAUNCH(psd_rord_plan, psd_dim3(1), 64, 0, c->stream, P);
+            PSD_LAUNCH(psd_rord_step_mb, psd_dim3(PSD_RO_SLOTS), PSD_STEP_NT, lds_step, c->stream, P);
+            PSD_LAUNCH(psd_rord_apply_mb, psd_dim3(tiles, p, 3 * PSD_RO_SLOTS), PSD_APPLY_NT, lds_apply, c->stream, P, n, p, 0);
+            PSD_LAUNCH(psd_rord_apply_mb, psd_dim3(tiles, p, 3 * PSD_RO_SLOTS), PSD_APPLY_NT, lds_apply, c->stream, P, n, p, 1);
+        } else {
             PSD_LAUNCH(psd_rord_step, psd_dim3(1), PSD_STEP_NT, lds_step, c->stream, P);
             PSD_LAUNCH(psd_rord_apply, psd_dim3(tiles, p, 3), PSD_APPLY_NT, lds_apply, c->stream, P, n, p);
-            ++launched;
         }
-        PSD_CHECK(psd_rt_d2h(&hst, c->rost, sizeof(hst), c->stream));
-        PSD_CHECK(psd_rt_sync(c->stream));
-        if (hst.phase == PSD_ROPH_DONE) break;
-        if (launched > cap) return *info = PSD_INFO_RUNTIME + 0xfffc;
-    }
-    }
-    if (hst.info == 0 && Sint) {
-        PSD_LAUNCH(psd_grord_values, psd_dim3((n + 63) / 64), 64, 0, c->stream, P, n, p);
-        PSD_LAUNCH(psd_grord_cleanup, psd_dim3(n), 64, 0, c->stream, P, n);
-        PSD_CHECK(psd_rt_d2h(alpha, c->galpha, sizeof(psd_z) * n, c->stream));
-        PSD_CHECK(psd_rt_d2h(beta, c->gbeta, sizeof(double) * n, c->stream));
-        std::vector<int> hsc(n, 0);
-        PSD_CHECK(psd_rt_d2h(hsc.data(), c->gascale, sizeof(int) * n, c->stream));
-        PSD_CHECK(psd_rt_sync(c->stream));
-        for (int q = 0; q < n; ++q) ascale[q] = hsc[q];
-    } else if (hst.info == 0) {
+    };
+    auto values = [&]() -> int {
+        if (Sint) {
+            PSD_LAUNCH(psd_grord_values, psd_dim3((n + 63) / 64), 64, 0, c->stream, P, n, p);
+            PSD_LAUNCH(psd_grord_cleanup, psd_dim3(n), 64, 0, c->stream, P, n);
+            return ord_scaled_values(c, n, c->galpha, c->gbeta, c->gascale, alpha, beta, ascale);
+        }
         PSD_LAUNCH(psd_rord_values, psd_dim3((n + 63) / 64), 64, 0, c->stream, P, n, p);
         PSD_LAUNCH(psd_rord_cleanup, psd_dim3(n), 64, 0, c->stream, P, n);
         PSD_CHECK(psd_rt_d2h(wr, c->wr, sizeof(double) * n, c->stream));
         PSD_CHECK(psd_rt_d2h(wi, c->wi, sizeof(double) * n, c->stream));
         PSD_CHECK(psd_rt_sync(c->stream));
-    }
-    const double ms = t.stop(c->stream);
-    PSD_CHECK(psd_rt_last_error());
-    if (stats) {
-        stats->ms_iter = stats->ms_total = ms;
-        stats->nsweeps = hst.nswaps;
-        stats->nwindows = hst.nwindows;
+        return 0;
+    };
+    const ord_dev<psd_rostate, psd_romb, psd_roslot> dev = {c->rost, c->romb, c->roslots, PSD_RO_SLOTS, PSD_ROPH_DONE, 0xfffc};
+    psd_rostate hst;
+    if (int rc = ord_drive(c, W, cap, dev, init, tick, values, hst, stats, info)) return rc;
+    if (stats)
         for (int q = 0; q < 6; ++q) stats->step_cycles[q] = hst.cyc[q];
-        stats->nlaunch_step = (int32_t)launched;
-        stats->window = W;
-    }
     // (a window that overran its transform lists — psd_rord_move lets none — is a runtime failure, as in the QR drivers)
     return *info = (hst.info == PSD_LIST_OVERFLOW) ? (PSD_INFO_RUNTIME + 77) : hst.info;
 }
@@ -3228,14 +3200,12 @@ int psd_d_ordschur(psd_ctx* c, int n, int p, double* const* T, double* const* Z,
     if (!ord_slots(orient, schurindex, p, slotA, slotZ)) return *info = -7;  // rordschur.jl:25
     if ((*info = c->reserve(n, p, true, 16)) != 0) return *info;
     const size_t nn = (size_t)n * n;
-    for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_h2d(c->dH + j * nn, T[slotA[j]], nn * 8, c->stream));
-    if (wantZ)
-        for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_h2d(c->dZ + j * nn, Z[slotZ[j]], nn * 8, c->stream));
+    PSD_CHECK(stage_in(c, c->dH, T, p, nn * 8, slotA.data()));
+    if (wantZ) PSD_CHECK(stage_in(c, c->dZ, Z, p, nn * 8, slotZ.data()));
     int rc = rordschur_dev(c, n, p, c->dH, c->dZ, select, wantZ, wr, wi, stats, info);
     if (rc < 0 || rc >= PSD_INFO_NOTIMPL) return rc;
-    for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_d2h(T[slotA[j]], c->dH + j * nn, nn * 8, c->stream));
-    if (wantZ)
-        for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_d2h(Z[slotZ[j]], c->dZ + j * nn, nn * 8, c->stream));
+    PSD_CHECK(stage_out(c, T, c->dH, p, nn * 8, slotA.data()));
+    if (wantZ) PSD_CHECK(stage_out(c, Z, c->dZ, p, nn * 8, slotZ.data()));
     PSD_CHECK(psd_rt_sync(c->stream));
     return rc;
 }
@@ -3296,13 +3266,7 @@ int giterate_dev(psd_ctx* c, int n, int p, double* dH, double* dZ, const uint8_t
 #endif
         }
     }
-#ifndef PSD_HOSTSIM
-    if (lds_step > c->gstep_lds_set) {
-        PSD_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(psd_gq_step),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_step));
-        c->gstep_lds_set = lds_step;
-    }
-#endif
+    PSD_CHECK(c->lds_limit(reinterpret_cast<const void*>(psd_gq_step), lds_step));
     // stage 2 of the signed Hessenberg reduction runs as a pipeline over the factors (psd_gq_hess_step) when its LDS
     // (window + mailboxes) fits; PSD_HESS_SERIAL=1 (test hook) keeps the single-wave chase
     const size_t lds_hess = psd_ghess_lds_bytes(p, W);
@@ -3312,15 +3276,10 @@ int giterate_dev(psd_ctx* c, int n, int p, double* dH, double* dZ, const uint8_t
     // (scan form of the stage-2 kernel, the default; PSD_HESS_SCAN=0: the pipeline of beats over the factors of round 2)
     int hess_scan = 1;
     if (const char* e = psd_env("PSD_HESS_SCAN")) hess_scan = atoi(e);
-#ifndef PSD_HOSTSIM
-    if (hess_pipe && lds_hess > c->ghess_lds_set) {
-        PSD_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(psd_gq_hess_step),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_hess));
-        PSD_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(psd_gq_hess_step_scan),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_hess));
-        c->ghess_lds_set = lds_hess;
+    if (hess_pipe) {
+        PSD_CHECK(c->lds_limit(reinterpret_cast<const void*>(psd_gq_hess_step), lds_hess));
+        PSD_CHECK(c->lds_limit(reinterpret_cast<const void*>(psd_gq_hess_step_scan), lds_hess));
     }
-#endif
     // multishift trains (as iterate_dev): M cursors, cursor 0 is the ordinary state machine
     const int tw = hessmode ? 0 : c->gtrain_m;
     const int M = (tw >= 2) ? ((tw > PSD_TRAIN_MAX) ? PSD_TRAIN_MAX : tw) : 1;
@@ -3339,10 +3298,7 @@ int giterate_dev(psd_ctx* c, int n, int p, double* dH, double* dZ, const uint8_t
             P.desc = c->gtdesc;
             P.cnt = c->gtcnt;
             P.tr = c->gttr;
-#ifndef PSD_HOSTSIM
-            PSD_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(psd_gq_step_train),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_step));
-#endif
+            PSD_CHECK(c->lds_limit(reinterpret_cast<const void*>(psd_gq_step_train), lds_step));
         }
     }
     int train_oc = 50;  // (a position of a signed factor costs about 1 us, a tick's overhead about 50 us)
@@ -3559,12 +3515,11 @@ int psd_d_gphessenberg(psd_ctx* c, int n, int p, double* const* A, const uint8_t
     if (S && !S[0]) return *info = -5;  // generalized.jl:990
     if ((*info = c->reserve(n, p, true, 16)) != 0) return *info;
     const size_t nn = (size_t)n * n;
-    for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_h2d(c->dH + j * nn, A[j], nn * 8, c->stream));
+    PSD_CHECK(stage_in(c, c->dH, A, p, nn * 8));
     *info = sghess_dev(c, n, p, c->dH, Q ? c->dZ : nullptr, S, stats);
     if (*info != 0) return *info;
-    for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_d2h(A[j], c->dH + j * nn, nn * 8, c->stream));
-    if (Q)
-        for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_d2h(Q[j], c->dZ + j * nn, nn * 8, c->stream));
+    PSD_CHECK(stage_out(c, A, c->dH, p, nn * 8));
+    if (Q) PSD_CHECK(stage_out(c, Q, c->dZ, p, nn * 8));
     PSD_CHECK(psd_rt_sync(c->stream));
     return 0;
 }
@@ -3583,20 +3538,20 @@ int psd_d_gpschur(psd_ctx* c, int n, int p, double* const* A, const uint8_t* S, 
     if (wantZ && !Z) return *info = -10;
     if (maxitfac < 1) return *info = -9;
     const bool left = orient == 'L';
-    auto slotA = [&](int j) { return left ? (p + 1 - j) : j; };               // internal j <- user slot (1-based)
-    auto slotZ = [&](int j) { return (!left || j == 1) ? j : (p + 2 - j); };  // rgeneralized.jl:1062-1071
+    std::vector<int> sA, sZ;  // internal j <- user slot: the reversal of rgeneralized.jl:1062-1071 for 'L' (schurindex p)
+    ord_slots(orient, left ? p : 1, p, sA, sZ);
     std::vector<uint8_t> Sarg(p, 1);
     bool alltrue = true;
-    for (int j = 1; j <= p; ++j) {
-        Sarg[j - 1] = (!S || S[slotA(j) - 1]) ? 1 : 0;
-        alltrue = alltrue && Sarg[j - 1];
+    for (int j = 0; j < p; ++j) {
+        Sarg[j] = (!S || S[sA[j]]) ? 1 : 0;
+        alltrue = alltrue && Sarg[j];
     }
     if (!Sarg[0]) return *info = -5;  // rgeneralized.jl:37
     if ((*info = c->reserve(n, p, true, 16)) != 0) return *info;
     const size_t nn = (size_t)n * n;
     Timer tc;
     tc.start(c->stream);
-    for (int j = 1; j <= p; ++j) PSD_CHECK(psd_rt_h2d(c->dH + (size_t)(j - 1) * nn, A[slotA(j) - 1], nn * 8, c->stream));
+    PSD_CHECK(stage_in(c, c->dH, A, p, nn * 8, sA.data()));
     double ms_copy = tc.stop(c->stream);
     psd_stats local;
     memset(&local, 0, sizeof(local));
@@ -3630,10 +3585,8 @@ int psd_d_gpschur(psd_ctx* c, int n, int p, double* const* A, const uint8_t* S, 
     if (schurindex) *schurindex = left ? p : 1;
     if (rc < 0 || rc >= PSD_INFO_NOTIMPL) return rc;
     tc.start(c->stream);
-    for (int j = 1; j <= p; ++j) PSD_CHECK(psd_rt_d2h(A[slotA(j) - 1], c->dH + (size_t)(j - 1) * nn, nn * 8, c->stream));
-    if (wantZ)
-        for (int j = 1; j <= p; ++j)
-            PSD_CHECK(psd_rt_d2h(Z[slotZ(j) - 1], c->dZ + (size_t)(j - 1) * nn, nn * 8, c->stream));
+    PSD_CHECK(stage_out(c, A, c->dH, p, nn * 8, sA.data()));
+    if (wantZ) PSD_CHECK(stage_out(c, Z, c->dZ, p, nn * 8, sZ.data()));
     PSD_CHECK(psd_rt_sync(c->stream));
     s->ms_copy = ms_copy + tc.stop(c->stream);
     return rc;
@@ -3653,9 +3606,8 @@ int psd_d_gpschur_hess(psd_ctx* c, int n, int p, double* const* H, const uint8_t
     if (maxitfac < 1) return *info = -9;
     if ((*info = c->reserve(n, p, true, 16)) != 0) return *info;
     const size_t nn = (size_t)n * n;
-    for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_h2d(c->dH + j * nn, H[j], nn * 8, c->stream));
-    if (wantZ)
-        for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_h2d(c->dZ + j * nn, Q[j], nn * 8, c->stream));
+    PSD_CHECK(stage_in(c, c->dH, H, p, nn * 8));
+    if (wantZ) PSD_CHECK(stage_in(c, c->dZ, Q, p, nn * 8));
     psd_stats local;
     memset(&local, 0, sizeof(local));
     psd_stats* s = stats ? stats : &local;
@@ -3665,9 +3617,8 @@ int psd_d_gpschur_hess(psd_ctx* c, int n, int p, double* const* H, const uint8_t
                             sweeplog, maxlog, info);
     s->ms_iter = s->ms_total = t.stop(c->stream);
     if (rc < 0 || rc >= PSD_INFO_NOTIMPL) return rc;
-    for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_d2h(H[j], c->dH + j * nn, nn * 8, c->stream));
-    if (wantZ)
-        for (int j = 0; j < p; ++j) PSD_CHECK(psd_rt_d2h(Q[j], c->dZ + j * nn, nn * 8, c->stream));
+    PSD_CHECK(stage_out(c, H, c->dH, p, nn * 8));
+    if (wantZ) PSD_CHECK(stage_out(c, Q, c->dZ, p, nn * 8));
     PSD_CHECK(psd_rt_sync(c->stream));
     return rc;
 }
@@ -3687,24 +3638,11 @@ size_t zgord_lds_bytes(int p, int W) {
 // dH/dZ in the internal right order, S internal signature
 int zgordschur_dev(psd_ctx* c, int n, int p, psd_z* dH, psd_z* dZ, const uint8_t* S, const uint8_t* select, int wantZ,
                    double* alpha, double* beta, int32_t* ascale, psd_stats* stats, int* info) {
-    int W = 0;
-    {
-        const int cand[] = {32, 24, 20, 16, 12, 10, 8, 6, 4};
-        for (int Wc : cand)
-            if (zgord_lds_bytes(p, Wc) <= 155 * 1024) {
-                W = Wc;
-                break;
-            }
-    }
+    int W = choose_window_lds({32, 24, 20, 16, 12, 10, 8, 6, 4}, [&](int w) { return zgord_lds_bytes(p, w); });
     if (W == 0) return *info = PSD_INFO_NOTIMPL;
     const bool pipe = c->ord_pipe != 0;  // pipelined driver (psd_oslot), as zordschur_dev
-    if (pipe) {
-        int nsel = 0;
-        for (int q = 0; q < n; ++q) nsel += select[q] ? 1 : 0;
-        if (nsel >= 8 && n >= 128 && W > 16) W = 16;
-        PSD_CHECK(c->zgtreserve(p));
-    }
-    PSD_CHECK(psd_rt_h2d(c->osel, select, (size_t)n, c->stream));
+    if (pipe) PSD_CHECK(c->zgtreserve(p));
+    PSD_CHECK(ord_begin(c, n, select, c->osel, W));
     std::vector<unsigned char> hS(p, 1);
     for (int l = 0; l < p; ++l) hS[l] = S[l] ? 1 : 0;
     PSD_CHECK(psd_rt_h2d(c->zgS, hS.data(), (size_t)p, c->stream));
@@ -3716,131 +3654,68 @@ int zgordschur_dev(psd_ctx* c, int n, int p, psd_z* dH, psd_z* dZ, const uint8_t
     O.z.Z = wantZ ? dZ : nullptr;
     O.z.S = c->zgS;
     O.z.st = c->zgst;
-    O.z.desc = c->zgdesc;
-    O.z.tr = c->zgtr;
-    O.z.cnt = c->zgcnt;
+    O.z.desc = pipe ? c->zgtdesc : c->zgdesc;
+    O.z.tr = pipe ? c->zgttr : c->zgtr;
+    O.z.cnt = pipe ? c->zgtcnt : c->zgcnt;
     O.z.dG = c->zgdG;
     O.z.alpha = c->zalpha;
     O.z.beta = c->zbeta;
     O.z.ascale = c->zascale;
     O.z.log = c->zlog;
-    O.st = c->ost;
+    O.st = pipe ? c->ombst : c->ost;
     O.select = c->osel;
     const size_t lds_step = zgord_lds_bytes(p, W);
-#ifndef PSD_HOSTSIM
-    if (lds_step > c->zgostep_lds_set) {
-        PSD_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(psd_zgord_step),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_step));
-        c->zgostep_lds_set = lds_step;
-    }
-#endif
+    PSD_CHECK(c->lds_limit(reinterpret_cast<const void*>(psd_zgord_step), lds_step));
     const size_t lds_apply = sizeof(psd_ztr) * PSD_GTR_CAP + (size_t)32 * (PSD_ZAPPLY_NT + 1) * sizeof(psd_z);
     const int tiles = (n + PSD_ZAPPLY_NT - 1) / PSD_ZAPPLY_NT;
-    psd_ostate hst;
-    memset(&hst, 0, sizeof(hst));
-    long long launched = 0;
-    const long long cap = (long long)n * ((long long)n / (W > 1 ? W - 1 : 1) + 2) + 1024;
-    Timer t;
-    t.start(c->stream);
-    if (pipe) {
-        O.st = c->ombst;
-        O.z.desc = c->zgtdesc;
-        O.z.cnt = c->zgtcnt;
-        O.z.tr = c->zgttr;
-#ifndef PSD_HOSTSIM
-        if (lds_step > c->zgostep_mb_lds_set) {
-            PSD_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(psd_zgord_step_mb),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_step));
-            c->zgostep_mb_lds_set = lds_step;
+    auto init = [&]() -> int {
+        if (pipe) {
+            PSD_CHECK(c->lds_limit(reinterpret_cast<const void*>(psd_zgord_step_mb), lds_step));
+            PSD_CHECK(psd_rt_memset(c->zgtdesc, 0, sizeof(psd_gapply_desc) * PSD_TRAIN_MAX, c->stream));
+            PSD_LAUNCH(psd_ord1_init_mb, psd_dim3(1), 64, 0, c->stream, c->ombst, c->oslots, c->omb, n, p, wantZ, W);
+        } else {
+            PSD_LAUNCH(psd_zgord_init, psd_dim3(1), 64, 0, c->stream, O, n, p, wantZ, W);
         }
-#endif
-        PSD_CHECK(psd_rt_memset(c->zgtdesc, 0, sizeof(psd_gapply_desc) * PSD_TRAIN_MAX, c->stream));
-        PSD_LAUNCH(psd_ord1_init_mb, psd_dim3(1), 64, 0, c->stream, c->ombst, c->oslots, c->omb, n, p, wantZ, W);
-        psd_omb hg;
-        memset(&hg, 0, sizeof(hg));
-        for (;;) {
-            for (int b = 0; b < 16; ++b) {
-                PSD_LAUNCH(psd_ord1_plan, psd_dim3(1), 64, 0, c->stream, c->ombst, c->oslots, c->omb, c->osel);
-                PSD_LAUNCH(psd_zgord_step_mb, psd_dim3(PSD_O_SLOTS), PSD_STEP_NT, lds_step, c->stream, O, p, p + 8);
-                PSD_LAUNCH(psd_zgq_apply_train, psd_dim3(tiles, p, 2 * PSD_O_SLOTS), PSD_ZAPPLY_NT, lds_apply, c->stream, O.z, n, p, p + 8, 0);
-                PSD_LAUNCH(psd_zgq_apply_train, psd_dim3(tiles, p, PSD_O_SLOTS), PSD_ZAPPLY_NT, lds_apply, c->stream, O.z, n, p, p + 8, 1);
-                ++launched;
-            }
-            PSD_CHECK(psd_rt_d2h(&hg, c->omb, sizeof(hg), c->stream));
-            PSD_CHECK(psd_rt_sync(c->stream));
-            if (hg.phase == PSD_OPH_DONE) break;
-            if (launched > cap) return *info = PSD_INFO_RUNTIME + 0xfffb;
-        }
-        std::vector<psd_ostate> hs(PSD_O_SLOTS);
-        PSD_CHECK(psd_rt_d2h(hs.data(), c->ombst, sizeof(psd_ostate) * PSD_O_SLOTS, c->stream));
-        PSD_CHECK(psd_rt_sync(c->stream));
-        hst.phase = PSD_OPH_DONE;
-        hst.info = hg.info;
-        for (const psd_ostate& q : hs) {
-            hst.nswaps += q.nswaps;
-            hst.nwindows += q.nwindows;
-        }
-    } else {
-    PSD_LAUNCH(psd_zgord_init, psd_dim3(1), 64, 0, c->stream, O, n, p, wantZ, W);
-    for (;;) {
-        for (int b = 0; b < 32; ++b) {
+        return 0;
+    };
+    auto tick = [&]() {
+        if (pipe) {
+            PSD_LAUNCH(psd_ord1_plan, psd_dim3(1), 64, 0, c->stream, c->ombst, c->oslots, c->omb, c->osel);
+            PSD_LAUNCH(psd_zgord_step_mb, psd_dim3(PSD_O_SLOTS), PSD_STEP_NT, lds_step, c->stream, O, p, p + 8);
+            PSD_LAUNCH(psd_zgq_apply_train, psd_dim3(tiles, p, 2 * PSD_O_SLOTS), PSD_ZAPPLY_NT, lds_apply, c->stream, O.z, n, p, p + 8, 0);
+            PSD_LAUNCH(psd_zgq_apply_train, psd_dim3(tiles, p, PSD_O_SLOTS), PSD_ZAPPLY_NT, lds_apply, c->stream, O.z, n, p, p + 8, 1);
+        } else {
             PSD_LAUNCH(psd_zgord_step, psd_dim3(1), PSD_STEP_NT, lds_step, c->stream, O);
             PSD_LAUNCH(psd_zgq_apply, psd_dim3(tiles, p, 3), PSD_ZAPPLY_NT, lds_apply, c->stream, O.z, n, p);
-            ++launched;
         }
-        PSD_CHECK(psd_rt_d2h(&hst, c->ost, sizeof(hst), c->stream));
-        PSD_CHECK(psd_rt_sync(c->stream));
-        if (hst.phase == PSD_OPH_DONE) break;
-        if (launched > cap) return *info = PSD_INFO_RUNTIME + 0xfffb;
-    }
-    }
-    if (hst.info == 0) {
+    };
+    auto values = [&]() -> int {
         PSD_LAUNCH(psd_zgord_values, psd_dim3((n + 255) / 256), 256, 0, c->stream, O.z, n, p);
-        PSD_CHECK(psd_rt_d2h(alpha, c->zalpha, sizeof(psd_z) * n, c->stream));
-        PSD_CHECK(psd_rt_d2h(beta, c->zbeta, sizeof(double) * n, c->stream));
-        std::vector<int> hsc(n, 0);
-        PSD_CHECK(psd_rt_d2h(hsc.data(), c->zascale, sizeof(int) * n, c->stream));
-        PSD_CHECK(psd_rt_sync(c->stream));
-        for (int q = 0; q < n; ++q) ascale[q] = hsc[q];
-    }
-    const double ms = t.stop(c->stream);
-    PSD_CHECK(psd_rt_last_error());
-    if (stats) {
-        stats->ms_iter = stats->ms_total = ms;
-        stats->nsweeps = hst.nswaps;
-        stats->nwindows = hst.nwindows;
-        stats->nlaunch_step = (int32_t)launched;
-        stats->window = W;
-    }
+        return ord_scaled_values(c, n, c->zalpha, c->zbeta, c->zascale, alpha, beta, ascale);
+    };
+    psd_ostate hst;
+    if (int rc = ord_drive(c, W, zord_cap(n, W), zord_states(c, 0xfffb), init, tick, values, hst, stats, info)) return rc;
     return *info = hst.info;
 }
 
-// host entry shared by the complex and the (promoted) real case; Tz/Zz: p host matrices of n*n complex
-int gordschur_host(psd_ctx* c, int n, int p, std::vector<std::vector<psd_z>>& Tz, std::vector<std::vector<psd_z>>& Zz,
-                   const uint8_t* S, char orient, int schurindex, const uint8_t* select, int wantZ, double* alpha,
-                   double* beta, int32_t* ascale, psd_stats* stats, int* info) {
-    std::vector<int> sA, sZ;
+// host entry shared by the complex and the (promoted) real case; T/Z: p host matrices of n*n complex
+int gordschur_host(psd_ctx* c, int n, int p, double* const* T, double* const* Z, const uint8_t* S, char orient,
+                   int schurindex, const uint8_t* select, int wantZ, double* alpha, double* beta, int32_t* ascale,
+                   psd_stats* stats, int* info) {
+    std::vector<int> sA, sZ;  // internal j <- user slot
     if (!ord_slots(orient, schurindex, p, sA, sZ)) return *info = -7;  // ArgumentError, ordschur.jl:32
     if ((*info = c->zreserve(n, p, true, 16)) != 0) return *info;
     if ((*info = c->zgreserve(n, p)) != 0) return *info;
     const size_t nn = (size_t)n * n;
-    auto slotA = [&](int j) { return sA[j - 1] + 1; };  // internal j <- user slot (1-based)
-    auto slotZ = [&](int j) { return sZ[j - 1] + 1; };
     std::vector<uint8_t> Sint(p, 1);
-    for (int j = 1; j <= p; ++j) Sint[j - 1] = S[slotA(j) - 1] ? 1 : 0;
+    for (int j = 0; j < p; ++j) Sint[j] = S[sA[j]] ? 1 : 0;
     if (!Sint[0]) return *info = -5;
-    for (int j = 1; j <= p; ++j)
-        PSD_CHECK(psd_rt_h2d(c->zH + (size_t)(j - 1) * nn, Tz[slotA(j) - 1].data(), nn * 16, c->stream));
-    if (wantZ)
-        for (int j = 1; j <= p; ++j)
-            PSD_CHECK(psd_rt_h2d(c->zZ + (size_t)(j - 1) * nn, Zz[slotZ(j) - 1].data(), nn * 16, c->stream));
+    PSD_CHECK(stage_in(c, c->zH, T, p, nn * 16, sA.data()));
+    if (wantZ) PSD_CHECK(stage_in(c, c->zZ, Z, p, nn * 16, sZ.data()));
     int rc = zgordschur_dev(c, n, p, c->zH, c->zZ, Sint.data(), select, wantZ, alpha, beta, ascale, stats, info);
     if (rc < 0 || rc >= PSD_INFO_NOTIMPL) return rc;
-    for (int j = 1; j <= p; ++j)
-        PSD_CHECK(psd_rt_d2h(Tz[slotA(j) - 1].data(), c->zH + (size_t)(j - 1) * nn, nn * 16, c->stream));
-    if (wantZ)
-        for (int j = 1; j <= p; ++j)
-            PSD_CHECK(psd_rt_d2h(Zz[slotZ(j) - 1].data(), c->zZ + (size_t)(j - 1) * nn, nn * 16, c->stream));
+    PSD_CHECK(stage_out(c, T, c->zH, p, nn * 16, sA.data()));
+    if (wantZ) PSD_CHECK(stage_out(c, Z, c->zZ, p, nn * 16, sZ.data()));
     PSD_CHECK(psd_rt_sync(c->stream));
     return rc;
 }
@@ -3868,23 +3743,7 @@ int psd_z_gordschur(psd_ctx* c, int n, int p, double* const* T, double* const* Z
     if (!info) info = &dummy;
     if (stats) memset(stats, 0, sizeof(*stats));
     if (gord_check_args(c, n, p, T, Z, S, orient, select, wantZ, info) != 0) return *info;
-    const size_t nn = (size_t)n * n;
-    std::vector<std::vector<psd_z>> Tz(p), Zz(wantZ ? p : 0);
-    for (int j = 0; j < p; ++j) {
-        Tz[j].resize(nn);
-        memcpy(Tz[j].data(), T[j], nn * 16);
-        if (wantZ) {
-            Zz[j].resize(nn);
-            memcpy(Zz[j].data(), Z[j], nn * 16);
-        }
-    }
-    int rc = gordschur_host(c, n, p, Tz, Zz, S, orient, schurindex, select, wantZ, alpha, beta, ascale, stats, info);
-    if (rc < 0 || rc >= PSD_INFO_NOTIMPL) return rc;
-    for (int j = 0; j < p; ++j) {
-        memcpy(T[j], Tz[j].data(), nn * 16);
-        if (wantZ) memcpy(Z[j], Zz[j].data(), nn * 16);
-    }
-    return rc;
+    return gordschur_host(c, n, p, T, Z, S, orient, schurindex, select, wantZ, alpha, beta, ascale, stats, info);
 }
 
 // Float64 with a real spectrum (T1 triangular): promoted to the complex kernel, whose rotations stay real on real data.
@@ -3908,35 +3767,34 @@ int psd_d_gordschur(psd_ctx* c, int n, int p, double* const* T, double* const* Z
         std::vector<int> sA, sZ;
         if (!ord_slots(orient, schurindex, p, sA, sZ)) return *info = -7;
         if ((*info = c->reserve(n, p, true, 16)) != 0) return *info;
-        auto slotA = [&](int j) { return sA[j - 1] + 1; };
-        auto slotZ = [&](int j) { return sZ[j - 1] + 1; };
         std::vector<uint8_t> Sint(p, 1);
-        for (int j = 1; j <= p; ++j) Sint[j - 1] = S[slotA(j) - 1] ? 1 : 0;
+        for (int j = 0; j < p; ++j) Sint[j] = S[sA[j]] ? 1 : 0;
         if (!Sint[0]) return *info = -5;
-        for (int j = 1; j <= p; ++j) PSD_CHECK(psd_rt_h2d(c->dH + (size_t)(j - 1) * nn, T[slotA(j) - 1], nn * 8, c->stream));
-        if (wantZ)
-            for (int j = 1; j <= p; ++j)
-                PSD_CHECK(psd_rt_h2d(c->dZ + (size_t)(j - 1) * nn, Z[slotZ(j) - 1], nn * 8, c->stream));
+        PSD_CHECK(stage_in(c, c->dH, T, p, nn * 8, sA.data()));
+        if (wantZ) PSD_CHECK(stage_in(c, c->dZ, Z, p, nn * 8, sZ.data()));
         int rc = rordschur_dev(c, n, p, c->dH, c->dZ, select, wantZ, nullptr, nullptr, stats, info, Sint.data(), alpha, beta,
                                ascale);
         if (rc < 0 || rc >= PSD_INFO_NOTIMPL) return rc;
-        for (int j = 1; j <= p; ++j) PSD_CHECK(psd_rt_d2h(T[slotA(j) - 1], c->dH + (size_t)(j - 1) * nn, nn * 8, c->stream));
-        if (wantZ)
-            for (int j = 1; j <= p; ++j)
-                PSD_CHECK(psd_rt_d2h(Z[slotZ(j) - 1], c->dZ + (size_t)(j - 1) * nn, nn * 8, c->stream));
+        PSD_CHECK(stage_out(c, T, c->dH, p, nn * 8, sA.data()));
+        if (wantZ) PSD_CHECK(stage_out(c, Z, c->dZ, p, nn * 8, sZ.data()));
         PSD_CHECK(psd_rt_sync(c->stream));
         return rc;
     }
+    // (only the promotion needs host copies: gordschur_host stages from and into them)
     std::vector<std::vector<psd_z>> Tz(p), Zz(wantZ ? p : 0);
+    std::vector<double*> Tp(p), Zp(wantZ ? p : 0);
     for (int j = 0; j < p; ++j) {
         Tz[j].resize(nn);
         for (size_t q = 0; q < nn; ++q) Tz[j][q] = zmk(T[j][q], 0.0);
+        Tp[j] = reinterpret_cast<double*>(Tz[j].data());
         if (wantZ) {
             Zz[j].resize(nn);
             for (size_t q = 0; q < nn; ++q) Zz[j][q] = zmk(Z[j][q], 0.0);
+            Zp[j] = reinterpret_cast<double*>(Zz[j].data());
         }
     }
-    int rc = gordschur_host(c, n, p, Tz, Zz, S, orient, schurindex, select, wantZ, alpha, beta, ascale, stats, info);
+    int rc = gordschur_host(c, n, p, Tp.data(), Zp.data(), S, orient, schurindex, select, wantZ, alpha, beta, ascale, stats,
+                            info);
     if (rc < 0 || rc >= PSD_INFO_NOTIMPL) return rc;
     for (int j = 0; j < p; ++j) {
         for (size_t q = 0; q < nn; ++q) T[j][q] = Tz[j][q].re;
@@ -3969,15 +3827,13 @@ int rphessenberg_host(psd_ctx* c, int m, int n, int p, double* Ap, double* const
     PSD_CHECK(psd_rt_malloc((void**)&dA, (p > 1 ? (size_t)(p - 1) * nn : 1) * ES));
     if (Q) PSD_CHECK(psd_rt_malloc((void**)&dQ, (size_t)p * nqq * ES));
     PSD_CHECK(psd_rt_h2d(dAp, Ap, nap * ES, c->stream));
-    for (int l = 0; l + 1 < p; ++l) PSD_CHECK(psd_rt_h2d(dA + (size_t)l * nn, A[l], nn * ES, c->stream));
-    if (Q)
-        for (int l = 0; l < p; ++l) PSD_CHECK(psd_rt_h2d(dQ + (size_t)l * nqq, Q[l], nqq * ES, c->stream));
+    PSD_CHECK(stage_in(c, dA, A, p - 1, nn * ES));
+    if (Q) PSD_CHECK(stage_in(c, dQ, Q, p, nqq * ES));
     const size_t lds = sizeof(double) * PSD_RH_NT + (size_t)(n + 2) * ES;
     PSD_LAUNCH(psd_rphess_kernel<O>, psd_dim3(1), PSD_RH_NT, lds, c->stream, dAp, dA, dQ, m, n, p, nq, nqc);
     PSD_CHECK(psd_rt_d2h(Ap, dAp, nap * ES, c->stream));
-    for (int l = 0; l + 1 < p; ++l) PSD_CHECK(psd_rt_d2h(A[l], dA + (size_t)l * nn, nn * ES, c->stream));
-    if (Q)
-        for (int l = 0; l < p; ++l) PSD_CHECK(psd_rt_d2h(Q[l], dQ + (size_t)l * nqq, nqq * ES, c->stream));
+    PSD_CHECK(stage_out(c, A, dA, p - 1, nn * ES));
+    if (Q) PSD_CHECK(stage_out(c, Q, dQ, p, nqq * ES));
     PSD_CHECK(psd_rt_sync(c->stream));
     PSD_CHECK(psd_rt_last_error());
     psd_rt_free(dAp);

@@ -1795,3 +1795,58 @@ def case_rordschur_span_capi(eng):
     select = np.zeros(n, dtype=bool)
     select[row] = True
     rord_check(ps0, A, w, select, n, p, 32)
+
+
+def case_ordschur_abi_codes(eng):
+    """Argument codes of the four single-problem reordering entries (psd_{d,z}_ordschur, psd_{d,z}_gordschur) through
+    the raw C ABI: the Python wrapper validates before it calls, so only this reaches them.  n = 4, p = 3, triangular T
+    and identity Z; every call returns before a kernel runs.  The codes are those documented in psd_mi355x.h; a check
+    earlier in the list wins (a null selection is reported even when schurindex is bad as well)."""
+    import ctypes as C
+
+    n, p = 4, 3
+    dp = C.POINTER(C.c_double)
+    i32p = C.POINTER(C.c_int32)
+
+    def call(cplx, signed, ctx="ok", n=n, p=p, T="ok", Z="ok", wantZ=1, orient=b"R", schurindex=1, select="ok",
+             S=(1, 1, 1)):
+        dt = np.complex128 if cplx else np.float64
+        Ts = [np.asfortranarray(np.triu(np.arange(1.0, n * n + 1).reshape(n, n) / (j + 2)).astype(dt)) for j in range(p)]
+        Zs = [np.asfortranarray(np.eye(n, dtype=dt)) for _ in range(p)]
+        sel = (C.c_uint8 * max(n, 1))(*([1] + [0] * (max(n, 1) - 1)))
+        a, b = np.zeros(2 * max(n, 1)), np.zeros(max(n, 1))
+        sc = np.zeros(max(n, 1), dtype=np.int32)
+        info = C.c_int(-99)
+        head = [eng.ctx if ctx == "ok" else None, n, p, eng._ptrs(Ts) if T == "ok" else None,
+                eng._ptrs(Zs) if Z == "ok" else None]
+        tail = [orient, schurindex, sel if select == "ok" else None, wantZ]
+        if signed:
+            Sarr = None if S is None else (C.c_uint8 * len(S))(*S)
+            fn = eng.lib.psd_z_gordschur if cplx else eng.lib.psd_d_gordschur
+            rc = fn(*head, Sarr, *tail, a.ctypes.data_as(dp), b.ctypes.data_as(dp), sc.ctypes.data_as(i32p), None,
+                    C.byref(info))
+        elif cplx:
+            rc = eng.lib.psd_z_ordschur(*head, *tail, a.ctypes.data_as(dp), b.ctypes.data_as(dp),
+                                        sc.ctypes.data_as(i32p), None, C.byref(info))
+        else:
+            rc = eng.lib.psd_d_ordschur(*head, *tail, a.ctypes.data_as(dp), b.ctypes.data_as(dp), None, C.byref(info))
+        assert rc == info.value
+        return rc
+
+    for cplx in (False, True):
+        for signed in (False, True):
+            kw = dict(cplx=cplx, signed=signed)
+            assert call(ctx=None, **kw) == -1
+            assert call(n=0, **kw) == -2
+            assert call(p=0, **kw) == -3
+            assert call(T=None, **kw) == -4
+            assert call(Z=None, wantZ=1, **kw) == -5
+            assert call(orient=b"X", **kw) == -6
+            assert call(select=None, schurindex=2, **kw) == -8
+            assert call(schurindex=2, **kw) == -7
+            assert call(schurindex=0, **kw) == -7  # (psd_d_gordschur: before it reads T[schurindex - 1])
+            assert call(schurindex=p + 1, **kw) == -7
+            assert call(orient=b"L", schurindex=2, **kw) == -7
+            if signed:
+                assert call(S=None, **kw) == -5
+                assert call(S=(0, 1, 1), **kw) == -5  # (generalized.jl:182: the internal first factor enters directly)

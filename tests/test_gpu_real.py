@@ -198,6 +198,10 @@ def test_rordschur_span_entry_points(gpu_engine):
     ec.case_rordschur_span_capi(gpu_engine)
 
 
+def test_ordschur_abi_argument_codes(gpu_engine):
+    ec.case_ordschur_abi_codes(gpu_engine)
+
+
 def test_rphessenberg(gpu_engine):
     ec.case_rphessenberg(gpu_engine)
 

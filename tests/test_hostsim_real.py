@@ -120,6 +120,10 @@ def test_rordschur_span_entry_points(sim_engine):
     ec.case_rordschur_span_capi(sim_engine)
 
 
+def test_ordschur_abi_argument_codes(sim_engine):
+    ec.case_ordschur_abi_codes(sim_engine)
+
+
 def test_zordschur_pipelined(built, monkeypatch):
     import os
 
