@@ -177,6 +177,38 @@ int psd_d_pschur_batch_dev(psd_ctx* ctx, int nb, int n, int p, double* dA, char 
                            int maxitfac, double* dZ, double* wr, double* wi, int* infos, int* schurindex,
                            psd_stats* stats, int* info);
 
+/* ---- the same batch entries for ComplexF64, all signatures +1 -----------------------------------------------------
+ * Matrices and tau are interleaved (re, im) pairs, column-major; eigenvalues come in the scaled form of psd_z_pschur:
+ * alpha (nb * n pairs), beta and ascale (nb * n), problem by problem, lambda = alpha / beta * 2^ascale.  One workgroup
+ * reduces one problem and forms one Q_j (as the real entries); the iteration — the single-shift periodic QZ of
+ * generalized.jl:166-931 — runs ONE WAVEFRONT PER PROBLEM from the first deflation test to the phase normalisation in a
+ * single launch per group, so a problem's result does not depend on its place in the batch.  Orders above 128 run the
+ * single call's reduction, Q formation and iteration problem by problem on the batch buffer.  Any nb >= 1; a batch larger
+ * than the device memory is worked through in groups.  infos[nb] (may be NULL): per-problem info — PSD_INFO_NOCONV +
+ * level for a problem that exhausts its sweep budget, PSD_INFO_RUNTIME + k for one whose in-kernel loop hit its bound;
+ * the others are complete.  The return value is the first non-zero per-problem code, or a call-wide code.
+ *
+ * psd_z_phessenberg_batch: as psd_d_phessenberg_batch; H and tau equal, bit for bit, what psd_z_phessenberg's
+ * one-launch-per-link form gives.  info: -1 ctx; -2 nb < 1; -3 n; -4 p; -5 A NULL; -6 tau NULL. */
+int psd_z_phessenberg_batch(psd_ctx* ctx, int nb, int n, int p, double* const* A, double* tau, psd_stats* stats,
+                            int* info);
+/* pschur!(A::Vector{Matrix{ComplexF64}}, lr) for each of nb problems, as psd_d_pschur_batch.  info: -1 ctx; -2 nb < 1;
+ * -3 n; -4 p; -5 A NULL; -6 orient; -9 maxitfac < 1; -10 wantZ without Z; -11 alpha, beta or ascale NULL. */
+int psd_z_pschur_batch(psd_ctx* ctx, int nb, int n, int p, double* const* A, char orient, int wantT, int wantZ,
+                       int maxitfac, double* const* Z, double* alpha, double* beta, int32_t* ascale, int* infos,
+                       int* schurindex, psd_stats* stats, int* info);
+/* Device-resident variant: dA, dZ device [nb][p][n][n] column-major complex blocks in user order (dZ may be NULL when
+ * !wantZ), overwritten; alpha / beta / ascale / infos are host buffers.  Argument codes as psd_z_pschur_batch. */
+int psd_z_pschur_batch_dev(psd_ctx* ctx, int nb, int n, int p, double* dA, char orient, int wantT, int wantZ,
+                           int maxitfac, double* dZ, double* alpha, double* beta, int32_t* ascale, int* infos,
+                           int* schurindex, psd_stats* stats, int* info);
+/* nb Hessenberg-triangular ComplexF64 problems (pschur!(H1, Hs, S; wantT, wantZ, Q, maxitfac) with S all true): H / Q
+ * as psd_d_pschur_hess_batch (Q may be NULL when !wantZ, otherwise Q_j on entry and Z_j on exit), any nb >= 1.
+ * info: -1 ctx; -2 nb < 1; -3 n; -4 p; -5 H NULL; -6 wantZ without Q; -9 maxitfac < 1; -10 alpha, beta or ascale NULL. */
+int psd_z_pschur_hess_batch(psd_ctx* ctx, int nb, int n, int p, double* const* H, double* const* Q, int wantT, int wantZ,
+                            int maxitfac, double* alpha, double* beta, int32_t* ascale, int* infos, psd_stats* stats,
+                            int* info);
+
 /* Device-resident variant of psd_d_pschur: dA, dZ are device pointers to [p][n][n] blocks in user
  * order (dZ may be NULL when !wantZ).  wr/wi/sweeplog are host buffers. */
 int psd_d_pschur_dev(psd_ctx* ctx, int n, int p, double* dA, char orient, int wantT, int wantZ, int maxitfac,

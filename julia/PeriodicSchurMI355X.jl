@@ -138,11 +138,13 @@ function pschur!(A::Vector{Matrix{Float64}}, lr::Symbol = :R; wantZ::Bool = true
     PeriodicSchur(T1, T, Z, complex.(wr, wi), orient, js)
 end
 
-# pschur_batch!(problems, lr; wantZ, wantT, maxitfac, infos) — no reference equivalent: pschur!(A, lr; ...) (PSD.jl:120-152)
-# for many small Float64 problems of equal order and period in ONE call (psd_d_pschur_batch; parameter sweeps, the orbits
-# of a multiple-shooting run).  Works in place like pschur!; returns a Vector{PeriodicSchur}.  A problem that does not
-# converge throws like pschur! after all have run; with `infos` (a Vector{Cint} of length(problems)) the per-problem
-# codes are stored there instead and nothing is thrown for a failed problem.
+# pschur_batch!(problems, lr; wantZ, wantT, maxitfac, infos) — no reference equivalent: pschur!(A, lr; ...) (PSD.jl:120-152,
+# 1106-1111) for many small problems of equal order and period in ONE call (parameter sweeps, the orbits of a
+# multiple-shooting run).  Two methods: Float64 problems (psd_d_pschur_batch) and ComplexF64 problems (psd_z_pschur_batch,
+# all signatures +1: one wavefront carries one problem through the whole iteration).  Works in place like pschur!; returns
+# a Vector{PeriodicSchur}.  A problem that does not converge throws like pschur! after all have run; with `infos` (a
+# Vector{Cint} of length(problems)) the per-problem codes are stored there instead and nothing is thrown for a failed
+# problem.
 function pschur_batch!(problems::Vector{Vector{Matrix{Float64}}}, lr::Symbol = :R; wantZ::Bool = true, wantT::Bool = true,
                        maxitfac = 30, infos::Union{Nothing, Vector{Cint}} = nothing)
     orient = PSD.char_lr(lr)                                                                      # PSD.jl:155-177
@@ -177,7 +179,45 @@ function pschur_batch!(problems::Vector{Vector{Matrix{Float64}}}, lr::Symbol = :
     infos === nothing && foreach(_throw, codes)
     out
 end
+function pschur_batch!(problems::Vector{Vector{Matrix{ComplexF64}}}, lr::Symbol = :R; wantZ::Bool = true,
+                       wantT::Bool = true, maxitfac = 30, infos::Union{Nothing, Vector{Cint}} = nothing)
+    orient = PSD.char_lr(lr)
+    nb = length(problems)
+    nb == 0 && return PeriodicSchur[]
+    p = length(problems[1]); n = _check(problems[1])
+    for A in problems
+        (length(A) == p && _check(A) == n) || throw(DimensionMismatch("the problems of a batch must have equal order and period"))
+    end
+    flat = reduce(vcat, problems)
+    Z = wantZ ? [Matrix{ComplexF64}(undef, n, n) for _ in 1:(nb * p)] : Matrix{ComplexF64}[]
+    α = zeros(ComplexF64, n, nb); β = zeros(Float64, n, nb); sc = zeros(Int32, n, nb)
+    codes = infos === nothing ? Vector{Cint}(undef, nb) : infos
+    length(codes) == nb || throw(DimensionMismatch("infos must have one entry per problem"))
+    si = Ref{Cint}(0); info = Ref{Cint}(0)
+    Ap = _ptrs(flat); Zp = _ptrs(Z)
+    GC.@preserve flat Z α β sc codes begin
+        ccall((:psd_z_pschur_batch, libpsd), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Ptr{Float64}}, Cchar, Cint, Cint, Cint,
+               Ptr{Ptr{Float64}}, Ptr{ComplexF64}, Ptr{Float64}, Ptr{Int32}, Ptr{Cint}, Ref{Cint}, Ptr{Cvoid}, Ref{Cint}),
+              ctx().ptr, nb, n, p, Ap, orient, wantT, wantZ, maxitfac,
+              wantZ ? Zp : C_NULL, α, β, sc, codes, si, C_NULL, info)
+    end
+    # argument codes and call-wide runtime codes end the call (a per-problem code is also the return value: not those)
+    (info[] < 0 || (info[] >= INFO_NOTIMPL && !(info[] in codes))) && _throw(info[])
+    js = Int(si[])
+    out = map(1:nb) do q
+        A = problems[q]
+        T1 = A[js]; T = [A[j] for j in 1:p if j != js]
+        Zq = wantZ ? Z[((q - 1) * p + 1):(q * p)] : [similar(T1, 0, 0)]
+        vals = α[:, q] ./ β[:, q] .* 2.0 .^ sc[:, q]                                                 # generalized.jl:74-76
+        PeriodicSchur(T1, T, Zq, vals, orient, js)
+    end
+    infos === nothing && foreach(_throw, codes)
+    out
+end
 pschur_batch(problems::AbstractVector, lr::Symbol = :R; kwargs...) =
+    any(A -> any(a -> eltype(a) <: Complex, A), problems) ?
+    pschur_batch!([Matrix{ComplexF64}[Matrix{ComplexF64}(a) for a in A] for A in problems], lr; kwargs...) :
     pschur_batch!([Matrix{Float64}[Matrix{Float64}(a) for a in A] for A in problems], lr; kwargs...)
 
 # ordschur_batch!(problems, select; wantZ, infos) — no reference equivalent: ordschur!(P, select; wantZ) (rordschur.jl:3-132)

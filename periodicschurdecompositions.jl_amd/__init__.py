@@ -317,6 +317,13 @@ class Engine:
                                            dpp, dp, dp, ip, ip, C.POINTER(Stats), ip]
         lib.psd_d_pschur_batch_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_char, C.c_int,
                                                C.c_int, C.c_int, C.c_void_p, dp, dp, ip, ip, C.POINTER(Stats), ip]
+        if hasattr(lib, "psd_z_pschur_batch"):  # (tools load builds of earlier commits to time their single calls)
+            lib.psd_z_phessenberg_batch.argtypes = lib.psd_d_phessenberg_batch.argtypes
+            for nm, mats in (("psd_z_pschur_batch", dpp), ("psd_z_pschur_batch_dev", C.c_void_p)):
+                getattr(lib, nm).argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, mats, C.c_char, C.c_int, C.c_int,
+                                             C.c_int, mats, dp, dp, i32p, ip, ip, C.POINTER(Stats), ip]
+            lib.psd_z_pschur_hess_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, dpp, dpp, C.c_int, C.c_int,
+                                                    C.c_int, dp, dp, i32p, ip, C.POINTER(Stats), ip]
         for nm, mats in (("psd_d_ordschur_batch", dpp), ("psd_d_ordschur_batch_dev", C.c_void_p)):
             if hasattr(lib, nm):  # (tools load builds of earlier commits to time their single calls)
                 getattr(lib, nm).argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, mats, mats, C.c_char, C.c_int,
@@ -829,7 +836,7 @@ class Engine:
             if len(A) < 1:
                 raise DimensionMismatch("empty sequence")
             if self._is_complex(A):
-                raise NotImplementedPSD("pschur_batch: Float64 only (ComplexF64 has no batched iteration)")
+                raise NotImplementedPSD("pschur_batch: Float64 only (ComplexF64 problems: zpschur_batch)")
             nq = _check_square(A)
             if n is None:
                 n, p = nq, len(A)
@@ -913,9 +920,200 @@ class Engine:
             return self.pschur_batch_(problems, lr, **kw)
         for A in problems:
             if self._is_complex(list(A)):
-                raise NotImplementedPSD("pschur_batch: Float64 only (ComplexF64 has no batched iteration)")
+                raise NotImplementedPSD("pschur_batch: Float64 only (ComplexF64 problems: zpschur_batch)")
         work = [[np.array(a, dtype=np.float64, order="F", copy=True) for a in A] for A in problems]
         return self.pschur_batch_(work, lr, **kw)
+
+    # ---- ComplexF64 batch family (psd_z_*_batch): one wavefront per problem in the iteration
+    def _zbatch_shape(self, problems):
+        """(n, p, flat list of factors) of a batch of complex problems; DimensionMismatch unless all have one shape,
+        TypeError for a problem without a complex factor (the Float64 family is pschur_batch)."""
+        n = p = None
+        flat = []
+        for A in problems:
+            A = list(A)
+            if len(A) < 1:
+                raise DimensionMismatch("empty sequence")
+            if not self._is_complex(A):
+                raise TypeError("zpschur_batch: ComplexF64 only (use pschur_batch for Float64 problems)")
+            nq = _check_square(A)
+            if n is None:
+                n, p = nq, len(A)
+            if nq != n or len(A) != p:
+                raise DimensionMismatch("the problems of a batch must have equal order and period")
+            flat += A
+        return n, p, flat
+
+    def _zbatch_finish(self, nb, n, p, Tall, Zall, alpha, beta, sc, infos, orient, si, st, info, infos_out,
+                       general=False):
+        if info.value < 0 or info.value >= INFO_NOTIMPL:
+            if not any(int(infos[q]) == info.value for q in range(nb)):  # (a call-wide code: nothing is complete)
+                self._raise(info.value)
+        out = []
+        for q in range(nb):
+            g = GeneralizedPeriodicSchur([True] * p, Tall[q * p:(q + 1) * p], Zall[q * p:(q + 1) * p] if Zall else [],
+                                         alpha[q], beta[q], sc[q], orient, si, st)
+            out.append(g if general else PeriodicSchur(g.Ts, g.Z, g.values, orient, si, st))
+        if infos_out is not None:
+            infos_out[:] = [int(infos[q]) for q in range(nb)]
+            return out
+        for q in range(nb):
+            self._raise(infos[q])
+        return out
+
+    def zphessenberg_batch_(self, problems):
+        """phessenberg!(A) for a list of ComplexF64 problems of equal shape in ONE call (psd_z_phessenberg_batch): one
+        workgroup reduces one problem.  `problems`: list of lists of p writable Fortran-ordered complex128 matrices,
+        overwritten LAPACK-style.  Returns a list of (H list, tau[p][n]) like phessenberg_, and the Stats of the call."""
+        nb = len(problems)
+        if nb == 0:
+            return [], Stats()
+        n, p, flat = self._zbatch_shape(problems)
+        self._as_work(flat, np.complex128)
+        tau = np.zeros((nb, p, n), dtype=np.complex128)
+        st = Stats()
+        info = C.c_int(0)
+        self.lib.psd_z_phessenberg_batch(self.ctx, nb, n, p, self._ptrs(flat),
+                                         tau.view(np.float64).ctypes.data_as(C.POINTER(C.c_double)), C.byref(st),
+                                         C.byref(info))
+        self._raise(info.value)
+        out = []
+        for q in range(nb):
+            A = flat[q * p:(q + 1) * p]
+            out.append(([np.triu(a, -1 if j == 0 else 0) for j, a in enumerate(A)], tau[q]))
+        return out, st
+
+    def zpschur_batch_(self, problems, lr="R", wantZ=True, wantT=True, maxitfac=30, infos_out=None):
+        """pschur!(A::Vector{Matrix{ComplexF64}}, lr; wantZ, wantT, maxitfac) for many small problems of equal shape in
+        ONE call (psd_z_pschur_batch): the reduction and the Q formation one workgroup per problem (and factor), the
+        iteration one wavefront per problem in a single launch.  All signatures +1.
+
+        `problems`: a list of lists of p writable Fortran-ordered complex128 n x n matrices, overwritten with the T
+        factors; returns a list of PeriodicSchur.  Or one torch complex128 [nb, p, n, n] device tensor (device-resident
+        entry, psd_z_pschur_batch_dev; the input is not modified): returns (T, Z, values, stats) as pschur_batch_ does.
+
+        A problem that fails to converge raises like the single call, after all have run — the others are complete
+        then.  `infos_out`: a list that receives the per-problem info codes instead (nothing is raised for a failed
+        problem then)."""
+        orient = char_lr(lr)
+        if hasattr(problems, "data_ptr"):
+            return self._zpschur_batch_dev(problems, orient, wantZ, wantT, maxitfac, infos_out)
+        nb = len(problems)
+        if nb == 0:
+            if infos_out is not None:
+                infos_out[:] = []
+            return []
+        n, p, flat = self._zbatch_shape(problems)
+        self._as_work(flat, np.complex128)
+        Zall = [np.zeros((n, n), dtype=np.complex128, order="F") for _ in range(nb * p)] if wantZ else []
+        alpha = np.zeros((nb, n), dtype=np.complex128)
+        beta = np.zeros((nb, n))
+        sc = np.zeros((nb, n), dtype=np.int32)
+        infos = (C.c_int * nb)()
+        si = C.c_int(0)
+        st = Stats()
+        info = C.c_int(0)
+        dp = C.POINTER(C.c_double)
+        self.lib.psd_z_pschur_batch(self.ctx, nb, n, p, self._ptrs(flat), orient.encode(), int(wantT), int(wantZ),
+                                    int(maxitfac), self._ptrs(Zall) if wantZ else None,
+                                    alpha.view(np.float64).ctypes.data_as(dp), beta.ctypes.data_as(dp),
+                                    sc.ctypes.data_as(C.POINTER(C.c_int32)), infos, C.byref(si), C.byref(st),
+                                    C.byref(info))
+        return self._zbatch_finish(nb, n, p, flat, Zall, alpha, beta, sc, infos, orient, si.value, st, info, infos_out)
+
+    def zpschur_batch(self, problems, lr="R", **kw):
+        """Copying form of zpschur_batch_: the factors are left untouched."""
+        if hasattr(problems, "data_ptr"):
+            return self.zpschur_batch_(problems, lr, **kw)
+        for A in problems:
+            if not self._is_complex(list(A)):
+                raise TypeError("zpschur_batch: ComplexF64 only (use pschur_batch for Float64 problems)")
+        work = [[np.array(a, dtype=np.complex128, order="F", copy=True) for a in A] for A in problems]
+        return self.zpschur_batch_(work, lr, **kw)
+
+    def zpschur_hess_batch_(self, problems, wantT=True, wantZ=True, maxitfac=30, infos_out=None):
+        """pschur!(H1, Hs, S; wantT, wantZ, Q, maxitfac) for ComplexF64 with S all true (src/generalized.jl:166-175) for a
+        list of Hessenberg-triangular problems of equal shape in ONE call (psd_z_pschur_hess_batch).  `problems`: list
+        of (H1, Hs) or (H1, Hs, Q); matrices are overwritten.  Returns a list of GeneralizedPeriodicSchur, as zpschur_hess_
+        does; failures and `infos_out` as zpschur_batch_."""
+        nb = len(problems)
+        if nb == 0:
+            if infos_out is not None:
+                infos_out[:] = []
+            return []
+        Hall, Qall = [], []
+        n = problems[0][0].shape[0]
+        p = len(problems[0][1]) + 1
+        for pr in problems:
+            H = [pr[0]] + list(pr[1])
+            if len(H) != p or _check_square(H) != n:
+                raise DimensionMismatch("the problems of a batch must have equal order and period")
+            if not self._is_complex(H):
+                raise TypeError("zpschur_hess_batch_: ComplexF64 only (use pschur_hess_batch_ for Float64 problems)")
+            self._as_work(H, np.complex128)
+            Hall += H
+            if wantZ:
+                Q = (list(pr[2]) if len(pr) > 2 and pr[2] is not None
+                     else [np.asfortranarray(np.eye(n, dtype=np.complex128)) for _ in range(p)])
+                self._as_work(Q, np.complex128)
+                Qall += Q
+        alpha = np.zeros((nb, n), dtype=np.complex128)
+        beta = np.zeros((nb, n))
+        sc = np.zeros((nb, n), dtype=np.int32)
+        infos = (C.c_int * nb)()
+        st = Stats()
+        info = C.c_int(0)
+        dp = C.POINTER(C.c_double)
+        self.lib.psd_z_pschur_hess_batch(self.ctx, nb, n, p, self._ptrs(Hall), self._ptrs(Qall) if wantZ else None,
+                                         int(wantT), int(wantZ), int(maxitfac),
+                                         alpha.view(np.float64).ctypes.data_as(dp), beta.ctypes.data_as(dp),
+                                         sc.ctypes.data_as(C.POINTER(C.c_int32)), infos, C.byref(st), C.byref(info))
+        return self._zbatch_finish(nb, n, p, Hall, Qall, alpha, beta, sc, infos, "R", 1, st, info, infos_out, general=True)
+
+    def _zpschur_batch_dev(self, dA, orient, wantZ, wantT, maxitfac, infos_out):
+        import torch
+
+        if dA.dim() != 4 or dA.shape[2] != dA.shape[3]:
+            raise DimensionMismatch("a device batch is one [nb, p, n, n] tensor of square factors")
+        if not dA.is_complex():
+            raise TypeError("zpschur_batch: ComplexF64 only (use pschur_batch for Float64 problems)")
+        if not dA.is_cuda:
+            raise TypeError("device-resident zpschur_batch needs a GPU tensor (use lists of numpy arrays for host input)")
+        nb, p, n = dA.shape[0], dA.shape[1], dA.shape[2]
+        if nb == 0:
+            if infos_out is not None:
+                infos_out[:] = []
+            return dA.clone(), (dA.clone() if wantZ else None), np.zeros((0, n), dtype=complex), Stats()
+        # [nb][p][n][n] blocks of column-major matrices: the transpose of each factor, contiguous; always a copy
+        dT = dA.to(torch.complex128).transpose(2, 3).contiguous()
+        if dT.data_ptr() == dA.data_ptr():
+            dT = dT.clone()
+        dZ = torch.zeros_like(dT) if wantZ else None
+        alpha = np.zeros((nb, n), dtype=np.complex128)
+        beta = np.zeros((nb, n))
+        sc = np.zeros((nb, n), dtype=np.int32)
+        infos = (C.c_int * nb)()
+        si = C.c_int(0)
+        st = Stats()
+        info = C.c_int(0)
+        dp = C.POINTER(C.c_double)
+        torch.cuda.synchronize(dA.device)
+        self.lib.psd_z_pschur_batch_dev(self.ctx, nb, n, p, C.c_void_p(dT.data_ptr()), orient.encode(), int(wantT),
+                                        int(wantZ), int(maxitfac), C.c_void_p(dZ.data_ptr()) if wantZ else None,
+                                        alpha.view(np.float64).ctypes.data_as(dp), beta.ctypes.data_as(dp),
+                                        sc.ctypes.data_as(C.POINTER(C.c_int32)), infos, C.byref(si), C.byref(st),
+                                        C.byref(info))
+        if info.value < 0 or info.value >= INFO_NOTIMPL:
+            if not any(int(infos[q]) == info.value for q in range(nb)):
+                self._raise(info.value)
+        if infos_out is not None:
+            infos_out[:] = [int(infos[q]) for q in range(nb)]
+        else:
+            for q in range(nb):
+                self._raise(infos[q])
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            values = alpha / beta * np.exp2(sc.astype(np.float64))  # (as GeneralizedPeriodicSchur)
+        return dT.transpose(2, 3), (dZ.transpose(2, 3) if wantZ else None), values, st
 
     def _pschur_batch_dev(self, dA, orient, wantZ, wantT, maxitfac, infos_out):
         import torch
@@ -923,7 +1121,7 @@ class Engine:
         if dA.dim() != 4 or dA.shape[2] != dA.shape[3]:
             raise DimensionMismatch("a device batch is one [nb, p, n, n] tensor of square factors")
         if dA.is_complex():
-            raise NotImplementedPSD("pschur_batch: Float64 only (ComplexF64 has no batched iteration)")
+            raise NotImplementedPSD("pschur_batch: Float64 only (ComplexF64 problems: zpschur_batch)")
         if not dA.is_cuda:
             raise TypeError("device-resident pschur_batch needs a GPU tensor (use lists of numpy arrays for host input)")
         nb, p, n = dA.shape[0], dA.shape[1], dA.shape[2]

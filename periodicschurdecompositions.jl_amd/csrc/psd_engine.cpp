@@ -24,6 +24,7 @@
 #include "psd_gevec.h"
 #include "psd_bevec.h"
 #include "psd_bord.h"
+#include "psd_zbqz.h"
 
 #include "../../include/psd_mi355x.h"
 
@@ -286,6 +287,7 @@ struct psd_ctx {
     int shard_rank = 0, shard_world = 1;
     int batch_group = 0;  // PSD_BATCH_GROUP: most problems a host batch entry takes to the device at once (0: what fits)
     int bh_nmax = PSD_BH_NMAX;  // largest order of the one-workgroup-per-problem reduction (diagnostic build: PSD_BH_NMAX in the environment, for the sweep that sets the constant)
+    int zb_nmax = PSD_ZB_NMAX;  // largest order of the complex one-workgroup / one-wavefront-per-problem kernels (diagnostic build: PSD_ZB_NMAX in the environment, for the sweep that sets the constant)
     int bev_nmax = PSD_BEV_NMAX;  // largest order of the batched eigenvector kernels (diagnostic build: PSD_BEV_NMAX in the environment, for the sweep that sets the constant)
     int bord_nmax = PSD_BORD_NMAX;  // largest order of the batched reordering kernel (PSD_BORD_NMAX in the environment lowers it: the tests reach the fallback with it)
     int bord_w = 0;                 // PSD_BORD_W: a narrower window of the batched reordering kernel (0: bord_window's own choice)
@@ -1750,6 +1752,7 @@ int psd_create(psd_ctx** ctx, int device) {
     if (const char* e = psd_env("PSD_FORMQ_BLOCKED")) c->formq_blocked = atoi(e);
     if (const char* e = psd_env("PSD_BATCH_GROUP")) c->batch_group = atoi(e) > 0 ? atoi(e) : 0;
     if (const char* e = psd_env_diag("PSD_BH_NMAX")) c->bh_nmax = (atoi(e) >= 1 && atoi(e) <= 2048) ? atoi(e) : PSD_BH_NMAX;
+    if (const char* e = psd_env_diag("PSD_ZB_NMAX")) c->zb_nmax = (atoi(e) >= 1 && atoi(e) <= 2048) ? atoi(e) : PSD_ZB_NMAX;
     if (const char* e = psd_env_diag("PSD_BEV_NMAX")) c->bev_nmax = (atoi(e) >= 1 && atoi(e) <= 2048) ? atoi(e) : PSD_BEV_NMAX;
     if (const char* e = psd_env("PSD_BORD_NMAX")) c->bord_nmax = (atoi(e) >= 1 && atoi(e) < PSD_BORD_NMAX) ? atoi(e) : PSD_BORD_NMAX;
     if (const char* e = psd_env("PSD_BORD_W")) c->bord_w = (atoi(e) >= 6 && atoi(e) <= 32) ? atoi(e) : 0;
@@ -3942,5 +3945,6 @@ extern "C" int psd_dbg_apply_bench(psd_ctx* c, int n, int p, int nwin, int W, in
 #include "psd_evec_host.inl"
 #include "psd_gevec_host.inl"
 #include "psd_batch_host.inl"
+#include "psd_zbatch_host.inl"
 #include "psd_bevec_host.inl"
 #include "psd_bord_host.inl"

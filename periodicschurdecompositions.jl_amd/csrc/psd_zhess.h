@@ -182,11 +182,11 @@ PSD_KERNEL psd_zset_identity(psd_z* Q, int n) {
 }
 
 // backward accumulation step of Q_j = H_{j,1} ... H_{j,n-1}: lmul!(H, Q), householder.jl:190-205
-PSD_KERNEL psd_zformq_step(const psd_z* Hp, const psd_z* tau, psd_z* Q, int n, int i, int j0) {
+// (bx: the tile of four columns, j: the factor, 1-based — the block indices of psd_zformq_step; psd_zbformq loops over them)
+PSD_D void psd_zformq_step_body(const psd_z* Hp, const psd_z* tau, psd_z* Q, int n, int i, int j, int bx) {
     PSD_LDS_DECL;
     psd_z* red = (psd_z*)psd_lds;
     const int NT = PSD_NTHREADS;
-    const int j = j0 + PSD_BLOCK_Y + 1;  // (j0: first factor of a period-sharded context's slice, 0-based)
     const int r0 = i + ((j == 1) ? 1 : 0);
     const int m = n - r0 + 1;
     if (m < 1) return;
@@ -194,7 +194,7 @@ PSD_KERNEL psd_zformq_step(const psd_z* Hp, const psd_z* tau, psd_z* Q, int n, i
     if (ziszero(tj)) return;
     const psd_mat<psd_z> V = psd_mat<psd_z>{const_cast<psd_z*>(Hp) + (size_t)(j - 1) * n * n, n};
     const psd_mat<psd_z> M = psd_mat<psd_z>{Q + (size_t)(j - 1) * n * n, n};
-    const int cbase = r0 + 4 * PSD_BLOCK_X;
+    const int cbase = r0 + 4 * bx;
     if (cbase > n) return;
     PSD_PAR_FOR(t, NT) {
         const int wv = t >> 6, lane = t & 63;
@@ -225,6 +225,10 @@ PSD_KERNEL psd_zformq_step(const psd_z* Hp, const psd_z* tau, psd_z* Q, int n, i
             }
         }
     }
+}
+PSD_KERNEL psd_zformq_step(const psd_z* Hp, const psd_z* tau, psd_z* Q, int n, int i, int j0) {
+    // (j0: first factor of a period-sharded context's slice, 0-based)
+    psd_zformq_step_body(Hp, tau, Q, n, i, j0 + PSD_BLOCK_Y + 1, PSD_BLOCK_X);
 }
 
 #ifndef PSD_HOSTSIM

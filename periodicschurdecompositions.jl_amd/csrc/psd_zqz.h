@@ -1500,13 +1500,14 @@ PSD_KERNEL_B(PSD_ZAPPLY_NT) psd_zq_apply_wl(psd_zparams P, int n, int p, int cst
 
 // Deferred right side of H_1 after a zero-shift pass (generalized.jl:436-444):
 // for j = djlo..djhi: rmul!(view(H1, drow0:(j+1), :), G_j').  One thread per row.
-PSD_KERNEL psd_zq_defer(psd_zparams P, int n) {
+// (bx: the tile of PSD_NTHREADS rows / columns — the block index of psd_zq_defer; psd_zbqz loops over it)
+PSD_D void psd_zq_defer_body(const psd_zparams& P, int n, int bx) {
     const psd_zapply_desc d = *P.desc;
     if (!d.active || !d.defer_run) return;
     const psd_mat<psd_z> H1 = psd_mat<psd_z>{P.H, n};
     const int NT = PSD_NTHREADS;
     if (d.defer_run == 1) {
-        const int rbase = d.drow0 + PSD_BLOCK_X * NT;
+        const int rbase = d.drow0 + bx * NT;
         PSD_PAR_FOR(t, NT) {
             const int r = rbase + t;
             if (r <= d.djhi + 1 && d.djhi >= d.djlo) {
@@ -1525,7 +1526,7 @@ PSD_KERNEL psd_zq_defer(psd_zparams P, int n) {
     } else {
         // generalized.jl:561-564: for j = djhi:-1:djlo  lmul!(G_j, view(H1, :, (j-1):ilastm)), rows (j-1, j);
         // one thread per column c (>= djlo-1), rotations j <= c+1, streamed up the column
-        const int cbase = (d.djlo - 1) + PSD_BLOCK_X * NT;
+        const int cbase = (d.djlo - 1) + bx * NT;
         PSD_PAR_FOR(t, NT) {
             const int c = cbase + t;
             if (c <= d.lc1 && d.djhi >= d.djlo) {
@@ -1546,8 +1547,10 @@ PSD_KERNEL psd_zq_defer(psd_zparams P, int n) {
     }
 }
 
-PSD_KERNEL psd_zq_init(psd_zparams P, int n, int p, int wantT, int wantZ, int W, int maxitfac, int maxlog,
-                       int train_want, int train_oc) {
+PSD_KERNEL psd_zq_defer(psd_zparams P, int n) { psd_zq_defer_body(P, n, PSD_BLOCK_X); }
+
+PSD_D void psd_zq_init_body(const psd_zparams& P, int n, int p, int wantT, int wantZ, int W, int maxitfac, int maxlog,
+                            int train_want, int train_oc) {
     const psd_mat<psd_z> H1 = psd_mat<psd_z>{P.H, n};
     PSD_PAR_FOR(c, n) {
         for (int r = c + 3; r <= n; ++r) H1(r, c + 1) = zmk(0.0, 0.0);  // _gethess!
@@ -1576,13 +1579,17 @@ PSD_KERNEL psd_zq_init(psd_zparams P, int n, int p, int wantT, int wantZ, int W,
         P.desc->defer_run = 0;
     }
 }
+PSD_KERNEL psd_zq_init(psd_zparams P, int n, int p, int wantT, int wantZ, int W, int maxitfac, int maxlog,
+                       int train_want, int train_oc) {
+    psd_zq_init_body(P, n, p, wantT, wantZ, W, maxitfac, maxlog, train_want, train_oc);
+}
 
 // generalized.jl:860-908 for factor l (S all true): diag(T_l) real >= 0, phases folded into row j of
 // T_l, column j of Z_l and column j of T_{l-1}.  grid = n blocks (one per j); launched for l = p..2.
-PSD_KERNEL psd_zq_phase(psd_zparams P, int n, int l, int wantZ) {
+// (j: the diagonal position, 1-based — block index + 1 of psd_zq_phase; psd_zbqz loops over it)
+PSD_D void psd_zq_phase_body(const psd_zparams& P, int n, int l, int wantZ, int j) {
     PSD_LDS_DECL;
     psd_z* zs = (psd_z*)psd_lds;
-    const int j = PSD_BLOCK_X + 1;
     const psd_mat<psd_z> Hl = psd_mat<psd_z>{P.H + (size_t)(l - 1) * n * n, n};
     const psd_mat<psd_z> Hm = psd_mat<psd_z>{P.H + (size_t)(l - 2) * n * n, n};
     PSD_ONE {
@@ -1606,3 +1613,4 @@ PSD_KERNEL psd_zq_phase(psd_zparams P, int n, int l, int wantZ) {
     }
     PSD_PAR_FOR(r, j) { Hm(r + 1, j) = zmul(Hm(r + 1, j), zc); }
 }
+PSD_KERNEL psd_zq_phase(psd_zparams P, int n, int l, int wantZ) { psd_zq_phase_body(P, n, l, wantZ, PSD_BLOCK_X + 1); }

@@ -9,6 +9,10 @@
                     nb = 64, p = 8: the measurement PSD_BH_NMAX is set from.  Runs on the diagnostic library with the cap
                     lifted (PSD_BH_NMAX in the environment), so that every order takes the batched kernel.
 
+  --complex         the ComplexF64 family: Engine.zpschur_batch_ against the loop of Engine.pschur_ over the same complex
+                    problems, in the same process and run, nb = 256, p = 8 over the orders of --complex-orders: the
+                    measurement PSD_ZB_NMAX is set from (the largest order at which the batched call still wins).
+
 One JSON line per shape on stdout; --json FILE collects them."""
 import argparse
 import json
@@ -25,10 +29,11 @@ def parse_shapes(text):
     return [tuple(int(x) for x in s.split("x")) for s in text.split(",") if s]
 
 
-def factors(nb, n, p):
+def factors(nb, n, p, dtype=None):
+    import numpy as np
     import psdtest as pt
 
-    return [pt.bench_factors(n, p, seed=9000 + q) for q in range(nb)]
+    return [pt.bench_factors(n, p, seed=9000 + q, dtype=dtype or np.float64) for q in range(nb)]
 
 
 def copies(probs):
@@ -52,12 +57,12 @@ def time_loop(eng, probs, lr):
     return best
 
 
-def time_batch(eng, probs, lr):
+def time_batch(eng, probs, lr, cplx=False):
     best = None
     for _ in range(2):
         Ws = copies(probs)
         t0 = time.perf_counter()
-        out = eng.pschur_batch_(Ws, lr)
+        out = eng.zpschur_batch_(Ws, lr) if cplx else eng.pschur_batch_(Ws, lr)
         wall = 1e3 * (time.perf_counter() - t0)
         st = out[0].stats
         best = dict(wall_ms=wall, ms_hess=st.ms_hess, ms_formq=st.ms_formq, ms_iter=st.ms_iter, ms_copy=st.ms_copy,
@@ -84,6 +89,9 @@ def main():
     ap.add_argument("--loop-only", action="store_true")
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--sweep-orders", default="32,64,96,128,192,256")
+    ap.add_argument("--complex", dest="cplx", action="store_true")
+    ap.add_argument("--complex-orders", default="8,16,32,64,96,128")
+    ap.add_argument("--complex-nb", type=int, default=256)
     ap.add_argument("--lib", default=None, help="library to load instead of the package's (a build of another commit)")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
@@ -103,6 +111,18 @@ def main():
         for n in [int(x) for x in args.sweep_orders.split(",") if x]:
             rows.append(time_sweep(eng, 64, n, 8))
             print(json.dumps(rows[-1]), flush=True)
+    elif args.cplx:
+        import numpy as np
+
+        for n in [int(x) for x in args.complex_orders.split(",") if x]:
+            nb, p = args.complex_nb, 8
+            probs = factors(nb, n, p, np.complex128)
+            row = dict(nb=nb, n=n, p=p, lr=args.lr, dtype="complex128", loop=time_loop(eng, probs, args.lr),
+                       batch=time_batch(eng, probs, args.lr, cplx=True))
+            row["wall_ratio"] = row["loop"]["wall_ms"] / row["batch"]["wall_ms"]
+            row["device_ratio"] = row["loop"]["ms_total"] / row["batch"]["ms_total"]
+            rows.append(row)
+            print(json.dumps(row), flush=True)
     else:
         for (nb, n, p) in parse_shapes(args.shapes):
             probs = factors(nb, n, p)
