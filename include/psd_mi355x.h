@@ -489,6 +489,37 @@ int psd_d_kr_basis(psd_ctx* ctx, int n, int p, int ldv_cols, int a0, int m, doub
 int psd_z_kr_basis(psd_ctx* ctx, int n, int p, int ldv_cols, int a0, int m, double* V, const double* Q, int32_t* R,
                    int* info);
 
+/* ---- diagnostic entry of the scalar device routines -------------------------------------------------------------------
+ * TEST PLUMBING, not part of the product's interface and without a Julia binding: one kernel runs once, lane t of
+ * workgroup t / 64 evaluates case t by calling the routine the engine's chains call (reflectors, Givens rotations, the
+ * reflector scalars of the look-ahead Hessenberg reduction, the power-of-two rescaling of the scan chase, and the
+ * reciprocal / root forms under them), so that a test can compare each with exact arithmetic one call at a time.
+ * in, out: host, ncases rows of 8 doubles; slots an op does not name are ignored on input and zero on output.  The raw
+ * forms promise their accuracy only for the arguments their callers' range guards admit; NaN and Inf inputs are outside
+ * every routine's contract.  Complex values are (re, im) in consecutive slots.
+ * info: -1 ctx NULL; -2 unknown op; -3 ncases < 1; -4 in NULL; -5 out NULL; PSD_INFO_RUNTIME + k. */
+typedef enum psd_diag_scalar_op {
+    PSD_DS_RCP = 0,              /* psd_rcp_fast:        (x)                  -> (1/x) */
+    PSD_DS_SQRT_PAIR = 1,        /* psd_sqrt_pair_fast:  (s)                  -> (sqrt s, 1/sqrt s) */
+    PSD_DS_RSQRT2 = 2,           /* psd_rsqrt2_fast:     (a, b)               -> (1/sqrt a, 1/sqrt b) */
+    PSD_DS_REFL2 = 3,            /* psd_refl2:           (x0, x1)             -> (beta, v1, tau) */
+    PSD_DS_REFL3 = 4,            /* psd_refl3:           (x0, x1, x2)         -> (beta, v1, v2, tau) */
+    PSD_DS_REFL2_LEAN = 5,       /* psd_refl2_lean:      as PSD_DS_REFL2 */
+    PSD_DS_REFL3_LEAN = 6,       /* psd_refl3_lean:      as PSD_DS_REFL3 */
+    PSD_DS_REFL32_PAIR = 7,      /* psd_refl32_pair:     (x0, x1, x2, y0, y1) -> (beta, v1, v2, tau, beta', w1, tau') */
+    PSD_DS_REFLECTOR_SMALL = 8,  /* psd_reflector_small: (n, x0, x1, x2), n = 3, anything else runs n = 2
+                                                                               -> (beta, v1, v2, tau), v2 = 0 for n = 2 */
+    PSD_DS_H2_LARFG = 9,         /* psd_h2_larfg:        (alpha, xnorm)       -> (tau, beta, mult) */
+    PSD_DS_ZH2_LARFG = 10,       /* psd_zh2_larfg:       (alpha, xnorm), alpha complex -> (tau, beta, mult), tau and mult complex */
+    PSD_DS_GIVENS = 11,          /* psd_givens:          (f, g)               -> (cs, sn, r) */
+    PSD_DS_ZGIVENS = 12,         /* psd_zgivens:         (f, g) complex       -> (cs, sn, r), sn and r complex */
+    PSD_DS_ZGIVENS_LEAN = 13,    /* psd_zgivens_lean:    as PSD_DS_ZGIVENS */
+    PSD_DS_C3_SCALE = 14,        /* (m, x, e, bz, bin), e an integer in [-4096, 4096]
+                                    -> (psd_c3_expo(m), psd_c3_ldexp(x, e), psd_c3_beta(bz, bin, e)) */
+    PSD_DS_NOPS = 15
+} psd_diag_scalar_op;
+int psd_diag_scalar(psd_ctx* ctx, int op, int ncases, const double* in, double* out, int* info);
+
 /* ---- eigvecs(ps, select; shifted) by periodic back-substitution — vectors.jl:25-138 without the reordering ----------
  * The selected right eigenvectors of the product and of its circular shifts, from a periodic Schur decomposition, by
  * the periodic form of LAPACK's xTREVC: the triangular factors are solved bottom up (a cyclic recurrence round the period

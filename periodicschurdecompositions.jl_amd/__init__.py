@@ -185,6 +185,11 @@ class History:
 # partial_pschur targets (ArnoldiMethod's LM / LR / SR / LI / SI) as the ABI's char codes
 KRYLOV_TARGETS = {"LM": "M", "LR": "R", "SR": "r", "LI": "I", "SI": "i"}
 
+# psd_diag_scalar_op (include/psd_mi355x.h): the ops of the scalar diagnostic entry, by name
+DIAG_SCALAR_OPS = {nm: k for k, nm in enumerate(
+    ("rcp", "sqrt_pair", "rsqrt2", "refl2", "refl3", "refl2_lean", "refl3_lean", "refl32_pair", "reflector_small",
+     "h2_larfg", "zh2_larfg", "givens", "zgivens", "zgivens_lean", "c3_scale"))}
+
 
 # One sparse factor of partial_pschur in CSR form: order n, row pointers (n + 1), column indices and values (0-based).
 CSR = collections.namedtuple("CSR", "n indptr indices data")
@@ -350,6 +355,8 @@ class Engine:
             lib.psd_d_kr_basis.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp,
                                            C.POINTER(C.c_int32), ip]
             lib.psd_z_kr_basis.argtypes = lib.psd_d_kr_basis.argtypes
+        if hasattr(lib, "psd_diag_scalar"):
+            lib.psd_diag_scalar.argtypes = [C.c_void_p, C.c_int, C.c_int, dp, dp, ip]
         i32p = C.POINTER(C.c_int32)
         for nm, dev, cplx in (("psd_d_eigvecs", False, False), ("psd_z_eigvecs", False, True),
                               ("psd_d_eigvecs_dev", True, False), ("psd_z_eigvecs_dev", True, True)):
@@ -2022,6 +2029,25 @@ class Engine:
            Qa.view(np.float64).ctypes.data_as(dp), C.byref(R), C.byref(info))
         self._raise(info.value)
         return [np.asfortranarray(Va[l].T) for l in range(p)], int(R.value)
+
+    def diag_scalar(self, op_name, X):
+        """The scalar device routine `op_name` (a key of DIAG_SCALAR_OPS) on every row of X, one lane per row, in one
+        launch (test plumbing, include/psd_mi355x.h).  X: ncases x k operands, k <= 8 in the slot order of
+        psd_diag_scalar_op.  Returns the ncases x 8 output rows."""
+        if op_name not in DIAG_SCALAR_OPS:
+            raise ValueError(f"unknown op {op_name!r}: one of " + ", ".join(DIAG_SCALAR_OPS))
+        X = np.asarray(X, dtype=np.float64)
+        if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] > 8:
+            raise DimensionMismatch("X must be ncases x k with ncases >= 1 and k <= 8")
+        xin = np.zeros((X.shape[0], 8))
+        xin[:, :X.shape[1]] = X
+        out = np.full((X.shape[0], 8), np.nan)
+        info = C.c_int(0)
+        dp = C.POINTER(C.c_double)
+        self.lib.psd_diag_scalar(self.ctx, DIAG_SCALAR_OPS[op_name], X.shape[0], xin.ctypes.data_as(dp),
+                                 out.ctypes.data_as(dp), C.byref(info))
+        self._raise(info.value)
+        return out
 
     def partial_pschur(self, As, nev=None, which="LM", *, mindim=None, maxdim=None, u1=None, tol=None, tol1=None,
                        restarts=100, purgebuffer=2, seed=0):

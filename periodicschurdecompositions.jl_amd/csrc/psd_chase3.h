@@ -35,7 +35,7 @@
 #define PSD_C3_WAVES 4    // wavefronts of a chase workgroup under the scan chase (one per SIMD)
 #define PSD_C3_FPL 4      // links of the factor chain per lane of the scan (16 lanes x 4 >= 63)
 
-// exponent e with m 2^-e in [0.5, 1) for finite m > 0, else 0
+// exponent e with m 2^-e in [0.5, 1) for 0 < m < 1.7e308 (subnormals included), else 0: no rescaling
 PSD_D int psd_c3_expo(double m) {
     if (!(m > 0.0) || !(m < 1.7e308)) return 0;
 #ifdef PSD_HOSTSIM

@@ -137,9 +137,12 @@ PSD_D void psd_zgivens_lean(psd_z f, psd_z g, double& cs, psd_z& sn, psd_z& r) {
     double c0 = f2 * k;
     psd_z r0 = zscal(n2 * k, f);
     psd_z s0 = zscal(k, fg);
-    // (magnitudes between 1e-146 and 1e145 as in psd_zgivens: then n2 < 1e291, and f2 is normal)
-    const double scale = fmax(zabs1(f), zabs1(g));
-    const bool ok = (scale < 9.989595361011175e+145) & (scale > 1.0010415475915505e-146) & (f2 > fmax(g2, 1.0) * PSD_DBL_MIN);
+    // (magnitudes between 1e-146 and 1e145 as in psd_zgivens: then n2 < 1e291, and f2 is normal.  f conj(g) is formed
+    //  BEFORE it is scaled, so it must not underflow either: f = 6e-124, g = 5e-238 has sn = 8e-115, but f conj(g) = 3e-361
+    //  is zero in double.  |f| |g| >= fm gm, and at 1e-290 a product keeps all its bits; a zero g gives sn = 0 exactly.)
+    const double fm = zabs1(f), gm = zabs1(g), scale = fmax(fm, gm);
+    const bool ok = (scale < 9.989595361011175e+145) & (scale > 1.0010415475915505e-146) & (f2 > fmax(g2, 1.0) * PSD_DBL_MIN) &
+                    ((fm * gm > 1e-290) | ziszero(g));
     if (!ok) {
         const psd_zgiv_out o = psd_zgivens_slow(f, g);
         c0 = o.cs;

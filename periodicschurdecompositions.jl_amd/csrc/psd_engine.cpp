@@ -3948,3 +3948,4 @@ extern "C" int psd_dbg_apply_bench(psd_ctx* c, int n, int p, int nwin, int W, in
 #include "psd_zbatch_host.inl"
 #include "psd_bevec_host.inl"
 #include "psd_bord_host.inl"
+#include "psd_diag_scalar.inl"

@@ -145,6 +145,9 @@ PSD_D double psd_h2_wave_max(double x) {
     return x;
 }
 
+#endif  // PSD_HOSTSIM
+
+// (the serial simulation sees this one routine of the file: psd_diag_scalar runs it there)
 // (tau, beta, mult) of the reflector of x = (alpha; tail) from the tail's scaled norm (householder.jl:77-105, dlarfg);
 // tau = 0: H = I (householder.jl:74-76)
 PSD_D void psd_h2_larfg(double alpha, double xnorm, double& tau, double& beta, double& mult) {
@@ -196,6 +199,8 @@ PSD_D void psd_h2_larfg(double alpha, double xnorm, double& tau, double& beta, d
     mult = acc * (1.0 / (alpha - beta));
     for (int q = 0; q < kount; ++q) beta *= sfmin;
 }
+
+#ifndef PSD_HOSTSIM
 
 // Bottom part of a panel update with CPW columns per wavefront (two-stream forms, NK <= 16): the two vectors of the link
 // (w of the right reflector, v of the left one: 16 + 16 doubles per lane) stay in registers for all of the wave's columns,

@@ -74,6 +74,9 @@ PSD_D void psd_zh2_st2(psd_z* M, int n, int r, int c, bool ok0, bool ok1, psd_z 
     if (ok1) q[1] = x1;
 }
 
+#endif  // PSD_HOSTSIM
+
+// (the serial simulation sees this one routine of the file: psd_diag_scalar runs it there)
 // householder.jl:110-156 from the tail's norm: tau (complex), beta (real), mult = 1 / (alpha - beta); tau = 0: H = I
 PSD_D void psd_zh2_larfg(psd_z alpha, double xnorm, psd_z& tau, double& beta, psd_z& mult) {
     double ar = alpha.re, ai = alpha.im;
@@ -107,6 +110,8 @@ PSD_D void psd_zh2_larfg(psd_z alpha, double xnorm, psd_z& tau, double& beta, ps
     mult = zscal(acc, zdiv(zmk(1.0, 0.0), zmk(ar - beta, ai)));
     for (int q = 0; q < kount; ++q) beta *= sfmin;
 }
+
+#ifndef PSD_HOSTSIM
 
 // The deferred update of the matrix of link Lb: M <- H(v_Lb)^H (M H(v_La)) (see psd_h2_bulk_body)
 template <int NK>
