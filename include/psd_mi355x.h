@@ -685,6 +685,35 @@ int psd_d_ordschur_batch_dev(psd_ctx* ctx, int nb, int n, int p, void* dT, void*
                              const uint8_t* select, int wantZ, double* wr, double* wi, int* infos, int* nswaps,
                              psd_stats* stats, int* info);
 
+/* ---- zordschur_batch: reorder many small ComplexF64 periodic Schur forms in one call -------------------------------
+ * psd_z_ordschur (ordschur.jl:11-73) for nb decompositions of one shape (n, p), as psd_z_pschur_batch leaves them:
+ * ComplexF64, all-true signature, one orient and schurindex (1 or p) for the whole batch; the conventions of
+ * psd_d_ordschur_batch with interleaved complex matrices.  Up to order 128 one wavefront carries one problem through its
+ * whole reordering — the step and apply bodies of the single driver's serial form, the same windows and the same
+ * arithmetic — and a group is ONE launch of the swap kernel (psd_zbord) whatever nb is; above, or for a period whose
+ * narrowest window does not fit the LDS, psd_z_ordschur's driver runs problem by problem on the slices of the batch
+ * buffers.  A problem's result does not depend on its place in the batch or on the grouping (bit for bit).
+ * PSD_BATCH_GROUP, PSD_BORD_W (here from 4) and PSD_BORD_NMAX act as for the real entry.
+ *
+ * T, Z: nb * p pointers to n x n interleaved complex matrices (problem-major, user order), reordered in place; Z may be
+ * NULL when !wantZ.  select: host [nb][n], used as given (there are no conjugate pairs to complete).  alpha: host
+ * [nb][n] complex pairs, beta, ascale: host [nb][n] — the eigenvalues alpha / beta * 2^ascale in their new order; the
+ * rows of a failed problem are not written.  infos, nswaps, stats and the per-problem codes (0, 3000, 2000 + row) as
+ * for psd_d_ordschur_batch; stats->window = W (at most 32).
+ * Returns the first non-zero per-problem code, or a call-wide one: -1 ctx NULL; -2 n < 1; -3 p < 1; -4 T NULL;
+ * -5 Z NULL with wantZ; -6 orient; -7 schurindex strictly inside the period; -8 select NULL; -9 alpha, beta or ascale
+ * NULL; -11 nb < 0; PSD_INFO_NOTIMPL on a period-sharded context; PSD_INFO_RUNTIME + k.  nb == 0 returns 0 and touches
+ * nothing. */
+int psd_z_ordschur_batch(psd_ctx* ctx, int nb, int n, int p, double* const* T, double* const* Z, char orient,
+                         int schurindex, const uint8_t* select, int wantZ, double* alpha, double* beta, int32_t* ascale,
+                         int* infos, int* nswaps, psd_stats* stats, int* info);
+/* Device-resident variant: dT, dZ device [nb][p][n][n] column-major interleaved complex blocks in user order (what
+ * psd_z_pschur_batch_dev leaves), reordered in place; the other arrays are host arrays.  The blocks are brought to the
+ * internal order and back on the device, as psd_d_ordschur_batch_dev does. */
+int psd_z_ordschur_batch_dev(psd_ctx* ctx, int nb, int n, int p, void* dT, void* dZ, char orient, int schurindex,
+                             const uint8_t* select, int wantZ, double* alpha, double* beta, int32_t* ascale, int* infos,
+                             int* nswaps, psd_stats* stats, int* info);
+
 #ifdef __cplusplus
 }
 #endif

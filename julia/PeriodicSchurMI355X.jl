@@ -265,6 +265,50 @@ function ordschur_batch!(problems::Vector{<:PeriodicSchur{Float64}}, select::Abs
     problems
 end
 
+# ordschur_batch!(problems, select; wantZ, infos) for ComplexF64 — ordschur!(P, select; wantZ) (ordschur.jl:11-73) for many
+# small complex decompositions of equal order, period, orientation and schurindex (1 or p) in ONE call
+# (psd_z_ordschur_batch), the follow-up of pschur_batch! on complex problems.  `select` is used as given (there are no
+# conjugate pairs to complete); everything else as the Float64 method above.
+# NOT YET RUN: this method has not been executed.  It follows the Float64 method above and the complex branch of
+# ordschur! line by line; the C entry it calls is tested through the Python binding.
+function ordschur_batch!(problems::Vector{<:PeriodicSchur{ComplexF64}}, select::AbstractVector; wantZ::Bool = true,
+                         infos::Union{Nothing, Vector{Cint}} = nothing)
+    nb = length(problems)
+    nb == 0 && return problems
+    ps1 = problems[1]
+    p = ps1.period; n = size(ps1.T1, 1); js = ps1.schurindex; orient = ps1.orientation
+    (js == 1 || js == p) || throw(ArgumentError("only implemented for schurindex in (1,p)"))     # ordschur.jl:32
+    wantZ = wantZ && all(ps -> !isempty(ps.Z) && size(ps.Z[1], 1) == n, problems)
+    sel = zeros(UInt8, n, nb)
+    for (q, ps) in enumerate(problems)
+        (ps.period == p && size(ps.T1, 1) == n && ps.schurindex == js && ps.orientation == orient) ||
+            throw(DimensionMismatch("the problems of a batch must have equal order, period, orientation and schurindex"))
+        sq = select[1] isa Bool ? select : select[q]
+        length(sq) == n || throw(DimensionMismatch("select must have one entry per eigenvalue"))
+        sel[:, q] .= UInt8.(sq)
+    end
+    # user order: T1 at schurindex, the others around it
+    T = reduce(vcat, [[j == js ? ps.T1 : ps.T[j < js ? j : j - 1] for j in 1:p] for ps in problems])
+    Z = wantZ ? reduce(vcat, [ps.Z for ps in problems]) : Matrix{ComplexF64}[]
+    α = zeros(ComplexF64, n, nb); β = zeros(n, nb); sc = zeros(Int32, n, nb)
+    codes = infos === nothing ? Vector{Cint}(undef, nb) : infos
+    length(codes) == nb || throw(DimensionMismatch("infos must have one entry per problem"))
+    info = Ref{Cint}(0)
+    Tp = _ptrs(T); Zp = _ptrs(Z)
+    GC.@preserve T Z sel α β sc codes begin
+        ccall((:psd_z_ordschur_batch, libpsd), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Cchar, Cint, Ptr{UInt8}, Cint,
+               Ptr{ComplexF64}, Ptr{Float64}, Ptr{Int32}, Ptr{Cint}, Ptr{Cint}, Ptr{Cvoid}, Ref{Cint}),
+              ctx().ptr, nb, n, p, Tp, wantZ ? Zp : C_NULL, orient, js, sel, wantZ, α, β, sc, codes, C_NULL, C_NULL, info)
+    end
+    (info[] < 0 || info[] >= INFO_NOTIMPL) && _throw(info[])                 # argument / runtime codes end the call
+    for (q, ps) in enumerate(problems)
+        codes[q] == 0 && (ps.values .= _values(α[:, q], β[:, q], sc[:, q]))                       # ordschur.jl:118
+    end
+    infos === nothing && foreach(_throw_ord, codes)
+    problems
+end
+
 # eigvecs_batch_device(problems, select; shifted) — no reference equivalent: eigvecs(ps, select; shifted) (vectors.jl:25-138)
 # by periodic back-substitution for many small Float64 decompositions of equal order, period, orientation and schurindex in
 # ONE call (psd_d_eigvecs_batch), the follow-up of pschur_batch!.  `select`: a Vector{Bool} used for every problem or one per

@@ -333,6 +333,10 @@ class Engine:
             if hasattr(lib, nm):  # (tools load builds of earlier commits to time their single calls)
                 getattr(lib, nm).argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, mats, mats, C.c_char, C.c_int,
                                              C.POINTER(C.c_uint8), C.c_int, dp, dp, ip, ip, C.POINTER(Stats), ip]
+        for nm, mats in (("psd_z_ordschur_batch", dpp), ("psd_z_ordschur_batch_dev", C.c_void_p)):
+            if hasattr(lib, nm):  # (as above)
+                getattr(lib, nm).argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, mats, mats, C.c_char, C.c_int,
+                                             C.POINTER(C.c_uint8), C.c_int, dp, dp, i32p, ip, ip, C.POINTER(Stats), ip]
         lib.psd_set_shard.argtypes = [C.c_void_p, C.c_int, C.c_int]
         lib.psd_shard_owned.argtypes = [C.c_void_p, C.c_int, C.c_char, u8p]
         for nm, dev in (("psd_d_partial_pschur", False), ("psd_z_partial_pschur", False),
@@ -1451,6 +1455,174 @@ class Engine:
             for q in range(nb):
                 self._raise_ord(infos[q])
         return dT.transpose(2, 3), (dZ.transpose(2, 3) if wantZ else Z), wr + 1j * wi, st
+
+    def zordschur_batch_(self, problems, *args, wantZ=True, infos_out=None, lr="R", schurindex=1):
+        """LinearAlgebra.ordschur!(P, select; wantZ) (src/ordschur.jl:11-73) for MANY small ComplexF64 decompositions of
+        one shape in ONE call (psd_z_ordschur_batch): the follow-up of zpschur_batch, the complex counterpart of
+        ordschur_batch_.  All-true signature.  Per problem the result contract is that of `ordschur_`; a problem's
+        result does not depend on its place in the batch.
+
+        zordschur_batch_(problems, select, wantZ=True, infos_out=None): `problems` a list of complex PeriodicSchur (or
+        GeneralizedPeriodicSchur with S all true) of equal order, period, orientation and schurindex (1 or p) with
+        writable Fortran-ordered complex128 factors; each is mutated (Ts, Z, values, stats) and the list returned.  The
+        `stats` of a problem are the call's, with `nsweeps` its own swap count; the call's own are left in
+        `self.zordschur_batch_stats` (nsweeps: all swaps, nlaunch_step: launches of the swap kernel, one per group),
+        the swap counts in `self.zordschur_batch_nswaps` ([nb]).
+        zordschur_batch_(T, Z, select, lr=..., schurindex=..., wantZ=True, infos_out=None): the torch outputs of the
+        device-resident zpschur_batch_ ([nb, p, n, n] complex128 tensors; Z may be None with wantZ=False); returns
+        (T, Z, values, stats).  Tensors in the layout zpschur_batch_ returns — a transposed view of contiguous
+        column-major blocks — are reordered IN PLACE without a copy, and the returned tensors share their storage; any
+        other layout is copied first and the inputs stay as they were.  The `values` row of a failed problem is NaN.
+
+        `select`: [nb][n] flags, or one [n] row used for every problem, used as given.  A problem whose swap is
+        rejected (equal eigenvalues: SingularException, an ill-conditioned swap: IllConditionedException) ends alone, a
+        consistent decomposition with its old `values`; the exception of the first such problem is raised after all
+        have run — the others are complete then.  `infos_out`: a list that receives the per-problem codes instead
+        (nothing is raised for a failed problem)."""
+        if hasattr(problems, "data_ptr"):
+            if len(args) != 2:
+                raise TypeError("zordschur_batch_(T, Z, select, lr=..., schurindex=...)")
+            return self._zordschur_batch_dev(problems, args[0], args[1], lr, schurindex, wantZ, infos_out)
+        if len(args) != 1:
+            raise TypeError("zordschur_batch_(problems, select, wantZ=True)")
+        problems = list(problems)
+        nb = len(problems)
+        if nb == 0:
+            if infos_out is not None:
+                infos_out[:] = []
+            self.zordschur_batch_stats = Stats()
+            self.zordschur_batch_nswaps = np.zeros(0, dtype=np.int32)
+            return []
+        n = p = None
+        Ts, Zs = [], []
+        for ps in problems:
+            if isinstance(ps, GeneralizedPeriodicSchur) and not all(ps.S):
+                raise NotImplementedPSD("zordschur_batch: signed GeneralizedPeriodicSchur (use ordschur_ per problem)")
+            if not all(np.iscomplexobj(t) for t in ps.Ts):
+                raise NotImplementedPSD("zordschur_batch: ComplexF64 only (Float64 problems: ordschur_batch)")
+            nq = _check_square(ps.Ts)
+            if n is None:
+                n, p, orient, si = nq, len(ps.Ts), ps.orientation, ps.schurindex
+            if (nq != n or len(ps.Ts) != p or ps.orientation != orient or ps.schurindex != si
+                    or any(z.shape != (n, n) for z in ps.Z)):
+                raise DimensionMismatch("the problems of a batch must have equal order, period, orientation and schurindex")
+            Ts += list(ps.Ts)
+        if si not in (1, p):
+            raise ValueError("only implemented for schurindex in (1,p)")  # src/ordschur.jl:32
+        wantZ = bool(wantZ) and all(len(ps.Z) > 0 for ps in problems)
+        if wantZ:
+            for ps in problems:
+                if len(ps.Z) != p:
+                    raise DimensionMismatch("one Z per factor")
+                Zs += list(ps.Z)
+        sel = self._ord_batch_select(args[0], nb, n)
+        self._as_work(Ts, np.complex128)
+        self._as_work(Zs, np.complex128)
+        alpha = np.zeros((nb, n), dtype=np.complex128)
+        beta = np.zeros((nb, n))
+        sc = np.zeros((nb, n), dtype=np.int32)
+        infos = (C.c_int * nb)()
+        nsw = (C.c_int * nb)()
+        st = Stats()
+        info = C.c_int(0)
+        dp = C.POINTER(C.c_double)
+        self.lib.psd_z_ordschur_batch(self.ctx, nb, n, p, self._ptrs(Ts), self._ptrs(Zs) if wantZ else None,
+                                      char_lr(orient).encode(), int(si), sel.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                      int(wantZ), alpha.view(np.float64).ctypes.data_as(dp), beta.ctypes.data_as(dp),
+                                      sc.ctypes.data_as(C.POINTER(C.c_int32)), infos, nsw, C.byref(st), C.byref(info))
+        if info.value < 0 or info.value >= INFO_NOTIMPL:
+            self._raise(info.value)
+        self.zordschur_batch_stats = st
+        self.zordschur_batch_nswaps = np.array(list(nsw), dtype=np.int32)
+        for q, ps in enumerate(problems):
+            if infos[q] == 0:
+                with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+                    ps.values = alpha[q] / beta[q] * np.exp2(sc[q].astype(np.float64))
+                if isinstance(ps, GeneralizedPeriodicSchur):
+                    ps.alpha, ps.beta, ps.alphascale = alpha[q].copy(), beta[q].copy(), sc[q].copy()
+            ps.stats = Stats.from_buffer_copy(st)
+            ps.stats.nsweeps = nsw[q]
+        if infos_out is not None:
+            infos_out[:] = [int(infos[q]) for q in range(nb)]
+            return problems
+        for q in range(nb):
+            self._raise_ord(infos[q])
+        return problems
+
+    def zordschur_batch(self, problems, *args, **kw):
+        """Copying form of zordschur_batch_: the decompositions are left untouched (device tensors are copied too)."""
+        if hasattr(problems, "data_ptr"):
+            Z = args[0] if len(args) > 0 else None
+            return self.zordschur_batch_(problems.clone(), Z.clone() if Z is not None else None, *args[1:], **kw)
+        work = []
+        for ps in problems:
+            if not all(np.iscomplexobj(t) for t in ps.Ts):
+                raise NotImplementedPSD("zordschur_batch: ComplexF64 only (Float64 problems: ordschur_batch)")
+            cp = copy.copy(ps)
+            cp.Ts = [np.array(t, dtype=np.complex128, order="F", copy=True) for t in ps.Ts]
+            cp.Z = [np.array(z, dtype=np.complex128, order="F", copy=True) for z in ps.Z]
+            cp.values = np.array(ps.values, copy=True)
+            work.append(cp)
+        return self.zordschur_batch_(work, *args, **kw)
+
+    def _zordschur_batch_dev(self, T, Z, select, lr, schurindex, wantZ, infos_out):
+        import torch
+
+        wantZ = bool(wantZ) and Z is not None
+        if T.dim() != 4 or T.shape[2] != T.shape[3] or (Z is not None and Z.shape != T.shape):
+            raise DimensionMismatch("a device batch is [nb, p, n, n] tensors T and Z of square factors")
+        if not T.is_complex() or (Z is not None and not Z.is_complex()):
+            raise NotImplementedPSD("zordschur_batch: ComplexF64 only (Float64 problems: ordschur_batch)")
+        if not (T.is_cuda and (Z is None or Z.is_cuda)):
+            raise TypeError("device-resident zordschur_batch needs GPU tensors (use a list of PeriodicSchur for host input)")
+        nb, p, n = T.shape[0], T.shape[1], T.shape[2]
+        orient = char_lr(lr)
+        if schurindex not in (1, p):
+            raise ValueError("only implemented for schurindex in (1,p)")  # src/ordschur.jl:32
+        if nb == 0:
+            if infos_out is not None:
+                infos_out[:] = []
+            self.zordschur_batch_stats = Stats()
+            self.zordschur_batch_nswaps = np.zeros(0, dtype=np.int32)
+            return T, Z, np.zeros((0, n), dtype=complex), self.zordschur_batch_stats
+        sel = self._ord_batch_select(select, nb, n)
+
+        def blocks(X):
+            # [nb][p][n][n] blocks of column-major matrices: the transpose of each factor, contiguous.  What
+            # zpschur_batch_ returns is a view of exactly that: used as it is, in place
+            Xt = X.transpose(2, 3)
+            if X.dtype == torch.complex128 and Xt.is_contiguous():
+                return Xt
+            return X.to(torch.complex128).transpose(2, 3).contiguous()
+
+        dT = blocks(T)
+        dZ = blocks(Z) if wantZ else None
+        alpha = np.full((nb, n), np.nan, dtype=np.complex128)
+        beta = np.ones((nb, n))
+        sc = np.zeros((nb, n), dtype=np.int32)
+        infos = (C.c_int * nb)()
+        nsw = (C.c_int * nb)()
+        st = Stats()
+        info = C.c_int(0)
+        dp = C.POINTER(C.c_double)
+        torch.cuda.synchronize(T.device)
+        self.lib.psd_z_ordschur_batch_dev(self.ctx, nb, n, p, C.c_void_p(dT.data_ptr()),
+                                          C.c_void_p(dZ.data_ptr()) if wantZ else None, orient.encode(), int(schurindex),
+                                          sel.ctypes.data_as(C.POINTER(C.c_uint8)), int(wantZ),
+                                          alpha.view(np.float64).ctypes.data_as(dp), beta.ctypes.data_as(dp),
+                                          sc.ctypes.data_as(C.POINTER(C.c_int32)), infos, nsw, C.byref(st), C.byref(info))
+        if info.value < 0 or info.value >= INFO_NOTIMPL:
+            self._raise(info.value)
+        self.zordschur_batch_stats = st
+        self.zordschur_batch_nswaps = np.array(list(nsw), dtype=np.int32)
+        if infos_out is not None:
+            infos_out[:] = [int(infos[q]) for q in range(nb)]
+        else:
+            for q in range(nb):
+                self._raise_ord(infos[q])
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            values = alpha / beta * np.exp2(sc.astype(np.float64))
+        return dT.transpose(2, 3), (dZ.transpose(2, 3) if wantZ else Z), values, st
 
     def eigvecs(self, ps0, select, shifted=True, method="ordschur"):
         """LinearAlgebra.eigvecs(ps::PeriodicSchur, select; shifted) — src/vectors.jl:25-138: selected right

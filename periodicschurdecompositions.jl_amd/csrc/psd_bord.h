@@ -12,6 +12,7 @@
 #pragma once
 #include "psd_rord.h"
 
+#define PSD_BORD_WMIN 6    // least window PSD_BORD_W may ask of psd_bord (a 2x2 block and its target need more than 4 rows)
 #define PSD_BORD_NMAX 128  // largest order of the batched kernel (above: rordschur_dev problem by problem); profiles/batch/README.md
 
 // The transform lists of a window hold PSD_RORD_CAP records per owner.  A window of psd_rord_move records one per swap:

@@ -16,7 +16,7 @@ namespace {
 int bord_window(const psd_ctx* c, int n, int p) {
     int W = choose_window_rord(p, n);
     if (W > PSD_BORD_SPAN1) W = PSD_BORD_SPAN1;
-    if (W != 0 && c->bord_w >= 6 && c->bord_w < W) W = c->bord_w;
+    if (W != 0 && c->bord_w >= PSD_BORD_WMIN && c->bord_w < W) W = c->bord_w;
     return W;
 }
 

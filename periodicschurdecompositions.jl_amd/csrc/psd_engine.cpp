@@ -25,6 +25,7 @@
 #include "psd_bevec.h"
 #include "psd_bord.h"
 #include "psd_zbqz.h"
+#include "psd_zbord.h"
 
 #include "../../include/psd_mi355x.h"
 
@@ -1755,7 +1756,7 @@ int psd_create(psd_ctx** ctx, int device) {
     if (const char* e = psd_env_diag("PSD_ZB_NMAX")) c->zb_nmax = (atoi(e) >= 1 && atoi(e) <= 2048) ? atoi(e) : PSD_ZB_NMAX;
     if (const char* e = psd_env_diag("PSD_BEV_NMAX")) c->bev_nmax = (atoi(e) >= 1 && atoi(e) <= 2048) ? atoi(e) : PSD_BEV_NMAX;
     if (const char* e = psd_env("PSD_BORD_NMAX")) c->bord_nmax = (atoi(e) >= 1 && atoi(e) < PSD_BORD_NMAX) ? atoi(e) : PSD_BORD_NMAX;
-    if (const char* e = psd_env("PSD_BORD_W")) c->bord_w = (atoi(e) >= 6 && atoi(e) <= 32) ? atoi(e) : 0;
+    if (const char* e = psd_env("PSD_BORD_W")) c->bord_w = (atoi(e) >= 1 && atoi(e) <= 32) ? atoi(e) : 0;  // (each kernel has its own least window: PSD_BORD_WMIN, PSD_ZBORD_WMIN)
     if (const char* e = psd_env("PSD_BAND_HELPER")) c->band_helper = atoi(e);
     if (const char* e = psd_env_diag("PSD_TRAIN_LONG")) c->train_long = atoi(e);
     if (const char* e = psd_env_diag("PSD_TRAIN_STOP")) c->train_stop = atoi(e);
@@ -3948,4 +3949,5 @@ extern "C" int psd_dbg_apply_bench(psd_ctx* c, int n, int p, int nwin, int W, in
 #include "psd_zbatch_host.inl"
 #include "psd_bevec_host.inl"
 #include "psd_bord_host.inl"
+#include "psd_zbord_host.inl"
 #include "psd_diag_scalar.inl"

@@ -445,36 +445,39 @@ PSD_KERNEL psd_zord_init(psd_oparams O, int n, int p, int wantZ, int W) {
     }
 }
 
-// ordschur.jl:97-120 _updateλ!: eigenvalue j from the diagonals (T_1 first), scaled form.  grid over j.
+// ordschur.jl:97-120 _updateλ!: eigenvalue j from the diagonals (T_1 first), scaled form
+PSD_D void psd_zord_value_at(const psd_zparams& P, int n, int p, int j) {
+    psd_z alpha = zmk(1.0, 0.0);
+    int scale = 0;
+    for (int l = 1; l <= p; ++l) {
+        alpha = zmul(alpha, psd_zfac(P, n, l)(j, j));
+        if (zabs(alpha) == 0) {
+            alpha = zmk(0.0, 0.0);
+            scale = 0;
+        } else {
+            int guard = 0;
+            while (zabs(alpha) < 1.0 && guard < 2200) {
+                alpha = zscal(2.0, alpha);
+                scale -= 1;
+                ++guard;
+            }
+            while (zabs(alpha) >= 2.0 && guard < 4400) {
+                alpha = zscal(0.5, alpha);
+                scale += 1;
+                ++guard;
+            }
+        }
+    }
+    P.alpha[j - 1] = alpha;
+    P.beta[j - 1] = 1.0;
+    P.ascale[j - 1] = scale;
+}
+
+// grid over j
 PSD_KERNEL psd_zord_values(psd_zparams P, int n, int p) {
     const int NT = PSD_NTHREADS;
     PSD_PAR_FOR(t, NT) {
         const int j = 1 + PSD_BLOCK_X * NT + t;
-        if (j <= n) {
-            psd_z alpha = zmk(1.0, 0.0);
-            int scale = 0;
-            for (int l = 1; l <= p; ++l) {
-                alpha = zmul(alpha, psd_zfac(P, n, l)(j, j));
-                if (zabs(alpha) == 0) {
-                    alpha = zmk(0.0, 0.0);
-                    scale = 0;
-                } else {
-                    int guard = 0;
-                    while (zabs(alpha) < 1.0 && guard < 2200) {
-                        alpha = zscal(2.0, alpha);
-                        scale -= 1;
-                        ++guard;
-                    }
-                    while (zabs(alpha) >= 2.0 && guard < 4400) {
-                        alpha = zscal(0.5, alpha);
-                        scale += 1;
-                        ++guard;
-                    }
-                }
-            }
-            P.alpha[j - 1] = alpha;
-            P.beta[j - 1] = 1.0;
-            P.ascale[j - 1] = scale;
-        }
+        if (j <= n) psd_zord_value_at(P, n, p, j);
     }
 }

@@ -8,7 +8,11 @@ median modulus are selected per problem (the stable half of a Floquet spectrum),
                     the loop of Engine.ordschur_ calls over the same problems on the same engine, and the device-resident
                     entry on torch tensors (wall time without any host copy of a matrix);
   --loop-only       the loop alone: what a commit without the batched entry can run (the baseline of record; --lib names
-                    its library).
+                    its library);
+  --complex         the ComplexF64 family on the same shapes: Engine.zpschur_batch decomposes complex bench_factors, one
+                    Engine.zordschur_batch_ call (psd_z_ordschur_batch) against the loop of Engine.ordschur_
+                    (psd_z_ordschur) over the same problems, both host entries with their copies, and the device-resident
+                    entry.
 
 The second of two runs of each is reported.  One JSON line per shape on stdout; --json FILE collects them."""
 import argparse
@@ -47,20 +51,20 @@ def time_loop(eng, pss, sels):
     return best
 
 
-def time_batch(eng, pss, sels):
+def time_batch(eng, pss, sels, cplx=False):
     best = None
     for _ in range(2):
         work = clones(pss)
         t0 = time.perf_counter()
-        eng.ordschur_batch_(work, sels)
+        (eng.zordschur_batch_ if cplx else eng.ordschur_batch_)(work, sels)
         wall = 1e3 * (time.perf_counter() - t0)
-        st = eng.ordschur_batch_stats
+        st = eng.zordschur_batch_stats if cplx else eng.ordschur_batch_stats
         best = dict(wall_ms=wall, ms_total=st.ms_total, ms_copy=st.ms_copy, nswaps=int(st.nsweeps), nwindows=int(st.nwindows),
                     window=int(st.window), launches=int(st.nlaunch_step))
     return best
 
 
-def time_dev(eng, pss, sels, lr):
+def time_dev(eng, pss, sels, lr, cplx=False):
     import numpy as np
     import torch
 
@@ -71,9 +75,10 @@ def time_dev(eng, pss, sels, lr):
         T, Z = T0.clone(), Z0.clone()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        eng.ordschur_batch_(T, Z, sels, lr=lr, schurindex=pss[0].schurindex)
+        (eng.zordschur_batch_ if cplx else eng.ordschur_batch_)(T, Z, sels, lr=lr, schurindex=pss[0].schurindex)
         torch.cuda.synchronize()
-        best = dict(wall_ms=1e3 * (time.perf_counter() - t0), ms_total=eng.ordschur_batch_stats.ms_total)
+        st = eng.zordschur_batch_stats if cplx else eng.ordschur_batch_stats
+        best = dict(wall_ms=1e3 * (time.perf_counter() - t0), ms_total=st.ms_total)
     return best
 
 
@@ -83,6 +88,7 @@ def main():
                     help="nb x n x p, comma separated")
     ap.add_argument("--lr", default="R")
     ap.add_argument("--loop-only", action="store_true")
+    ap.add_argument("--complex", dest="cplx", action="store_true")
     ap.add_argument("--lib", default=None, help="library to load instead of the package's (a build of another commit)")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
@@ -97,12 +103,16 @@ def main():
     eng = psd_amd.Engine(0, libpath=args.lib)
     rows = []
     for (nb, n, p) in parse_shapes(args.shapes):
-        pss = eng.pschur_batch([pt.bench_factors(n, p, seed=9000 + q) for q in range(nb)], args.lr)
+        if args.cplx:
+            pss = eng.zpschur_batch([pt.bench_factors(n, p, seed=9000 + q, dtype=np.complex128) for q in range(nb)], args.lr)
+        else:
+            pss = eng.pschur_batch([pt.bench_factors(n, p, seed=9000 + q) for q in range(nb)], args.lr)
         sels = np.array([np.abs(ps.values) <= np.sort(np.abs(ps.values))[n // 2] for ps in pss])
-        row = dict(nb=nb, n=n, p=p, lr=args.lr, loop=time_loop(eng, pss, sels))
+        row = dict(nb=nb, n=n, p=p, lr=args.lr, dtype="complex128" if args.cplx else "float64",
+                   loop=time_loop(eng, pss, sels))
         if not args.loop_only:
-            row["batch"] = time_batch(eng, pss, sels)
-            row["dev"] = time_dev(eng, pss, sels, args.lr)
+            row["batch"] = time_batch(eng, pss, sels, args.cplx)
+            row["dev"] = time_dev(eng, pss, sels, args.lr, args.cplx)
             row["wall_ratio"] = row["loop"]["wall_ms"] / row["batch"]["wall_ms"]
             row["device_ratio"] = row["loop"]["ms_total"] / row["batch"]["ms_total"] if row["batch"]["ms_total"] else None
             row["swaps_per_s"] = 1e3 * row["batch"]["nswaps"] / row["batch"]["wall_ms"]
