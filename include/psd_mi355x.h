@@ -650,6 +650,38 @@ int psd_d_eigvecs_batch_dev(psd_ctx* ctx, int nb, int n, int p, const double* dT
                             const double* wi, char orient, int schurindex, uint8_t* select, int shifted, double* dV,
                             int maxvec, int* nvec, int32_t* pcnt, psd_bevec_stats* stats, int* info);
 
+/* ---- zeigvecs_batch: eigenvectors of many small ComplexF64 periodic Schur forms in one call -------------------------
+ * psd_z_eigvecs (back-substitution) for nb decompositions of one shape (n, p), as psd_z_pschur_batch leaves them:
+ * ComplexF64, all-true signature, one orient and schurindex for the whole batch; the conventions of psd_d_eigvecs_batch
+ * with interleaved complex matrices.  Per problem the result contract is that of psd_z_eigvecs: one column per selected
+ * row, top to bottom, ||V_1(:, j)|| = 1 with the largest-modulus entry real and positive, a zero eigenvalue a NaN column
+ * (counted), small pivots replaced by smin (counted), columns past 2^500 rescaled by a power of two (counted).  A
+ * problem's vectors do not depend on its place in the batch or on the grouping (bit for bit).  Up to order 128 the whole
+ * back-substitution of a group is one launch and the call makes four launches with shifted and p > 1, three otherwise,
+ * none when nothing is selected (stats->nlaunch); nothing is read back before the solve, a complex form being triangular
+ * in every factor.  Above, psd_z_eigvecs_dev's driver runs problem by problem on the slices of the batch buffers.
+ * PSD_BATCH_GROUP acts as for the real entry.
+ *
+ * T, Z: nb * p pointers to n x n interleaved complex matrices (problem-major, user order).  alpha: host [nb][n] complex
+ * pairs, beta: host [nb][n], ascale: host [nb][n] or NULL (zeros) — the eigenvalues alpha / beta * 2^ascale, converted
+ * as psd_z_eigvecs converts them.  select: host [nb][n], used as given (there are no conjugate pairs to complete);
+ * nvec[q] is the count of its row q, and a problem whose row is all false costs nothing.  V, maxvec, nvec, pcnt, stats
+ * and V = NULL (a size query) as for psd_d_eigvecs_batch.
+ * info: 0; -1 ctx NULL; -2 n < 1; -3 p < 1; -4 T NULL; -5 Z NULL; -6 alpha or beta NULL; -7 orient; -8 schurindex not in
+ * 1..p; -9 select NULL; -10 maxvec below the largest nvec; -11 nb < 0; -12 nvec NULL; PSD_INFO_NOTIMPL on a
+ * period-sharded context; PSD_INFO_RUNTIME + k.  nb == 0 returns 0 and touches nothing. */
+int psd_z_eigvecs_batch(psd_ctx* ctx, int nb, int n, int p, double* const* T, double* const* Z, const double* alpha,
+                        const double* beta, const int32_t* ascale, char orient, int schurindex, const uint8_t* select,
+                        int shifted, double* const* V, int maxvec, int* nvec, int32_t* pcnt, psd_bevec_stats* stats,
+                        int* info);
+/* Device-resident variant: dT, dZ device [nb][p][n][n] interleaved column-major blocks in user order (what
+ * psd_z_pschur_batch_dev leaves), dV a device block [nb][nmat][maxvec][n] of interleaved complex values.  alpha, beta,
+ * ascale, select, nvec and pcnt are host arrays. */
+int psd_z_eigvecs_batch_dev(psd_ctx* ctx, int nb, int n, int p, const double* dT, const double* dZ, const double* alpha,
+                            const double* beta, const int32_t* ascale, char orient, int schurindex,
+                            const uint8_t* select, int shifted, double* dV, int maxvec, int* nvec, int32_t* pcnt,
+                            psd_bevec_stats* stats, int* info);
+
 /* ---- ordschur_batch: reorder many small periodic Schur forms in one call ------------------------------------------
  * psd_d_ordschur (rordschur.jl:3-132) for nb decompositions of one shape (n, p), as psd_d_pschur_batch leaves them:
  * Float64, all-true signature, one orient and schurindex (1 or p) for the whole batch.  Per problem the result contract

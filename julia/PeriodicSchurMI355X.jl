@@ -354,6 +354,48 @@ function eigvecs_batch_device(problems::Vector{<:PeriodicSchur{Float64}}, select
     end
 end
 
+# eigvecs_batch_device for ComplexF64 decompositions (psd_z_eigvecs_batch), the follow-up of the complex pschur_batch!: the
+# contract above, except that `select` is used as given — a complex form has no conjugate pairs to complete.  The
+# eigenvalues go in as alpha = values, beta = 1, ascale = NULL.
+function eigvecs_batch_device(problems::Vector{<:PeriodicSchur{ComplexF64}}, select::AbstractVector; shifted::Bool = true)
+    nb = length(problems)
+    nb == 0 && return Vector{Matrix{ComplexF64}}[]
+    ps1 = problems[1]
+    p = ps1.period; n = size(ps1.T1, 1); js = ps1.schurindex; orient = ps1.orientation
+    (isempty(ps1.Z) || size(ps1.Z[1], 1) == 0) && throw(ArgumentError("eigvecs requires Schur vectors in the PSD"))
+    sel = zeros(UInt8, n, nb)
+    for (q, ps) in enumerate(problems)
+        (ps.period == p && size(ps.T1, 1) == n && ps.schurindex == js && ps.orientation == orient) ||
+            throw(DimensionMismatch("the problems of a batch must have equal order, period, orientation and schurindex"))
+        sq = select[1] isa Bool ? select : select[q]
+        length(sq) == n || throw(ArgumentError("length of `select` must correspond to rank of Schur (sub-)space"))
+        sel[:, q] .= UInt8.(sq)
+    end
+    # user order: T1 at schurindex, the others around it
+    T = reduce(vcat, [[j == js ? ps.T1 : ps.T[j < js ? j : j - 1] for j in 1:p] for ps in problems])
+    Z = reduce(vcat, [ps.Z for ps in problems])
+    α = ComplexF64[ps.values[i] for i in 1:n, ps in problems]; β = ones(Float64, n, nb)
+    nvec = zeros(Cint, nb); info = Ref{Cint}(0)
+    Tp = _ptrs(T); Zp = _ptrs(Z)
+    nmat = shifted ? p : 1
+    call(Vp, maxvec) = ccall((:psd_z_eigvecs_batch, libpsd), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ptr{ComplexF64}, Ptr{Float64}, Ptr{Int32},
+         Cchar, Cint, Ptr{UInt8}, Cint, Ptr{Ptr{ComplexF64}}, Cint, Ptr{Cint}, Ptr{Int32}, Ptr{Cvoid}, Ref{Cint}),
+        ctx().ptr, nb, n, p, Tp, Zp, α, β, C_NULL, orient, js, sel, shifted, Vp, maxvec, nvec, C_NULL, C_NULL, info)
+    GC.@preserve T Z α β sel nvec begin
+        call(C_NULL, 0)                                   # size query: nvec
+        info[] != 0 && _throw(info[])
+        maxvec = Int(maximum(nvec))
+        V = [zeros(ComplexF64, n, maxvec) for _ in 1:(nb * nmat)]
+        Vp = [pointer(v) for v in V]
+        GC.@preserve V Vp begin
+            call(Vp, maxvec)
+        end
+        info[] != 0 && _throw(info[])
+        return [[V[(q - 1) * nmat + l][:, 1:nvec[q]] for l in 1:nmat] for q in 1:nb]
+    end
+end
+
 # pschur!(A, lr; ...), ComplexF64 — PSD.jl:1106-1111 (the all-true signature of generalized.jl:108-137)
 function pschur!(A::Vector{Matrix{ComplexF64}}, lr::Symbol = :R; wantZ::Bool = true, wantT::Bool = true, maxitfac = 30)
     gps = pschur!(A, trues(length(A)), lr; wantZ = wantZ, wantT = wantT, maxitfac = maxitfac)

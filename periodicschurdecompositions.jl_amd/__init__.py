@@ -378,6 +378,11 @@ class Engine:
             mats = C.c_void_p if dev else dpp
             getattr(lib, nm).argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, mats, mats, dp, dp, C.c_char, C.c_int,
                                          u8p, C.c_int, mats, C.c_int, ip, i32p, C.POINTER(BevecStats), ip]
+        for nm, dev in (("psd_z_eigvecs_batch", False), ("psd_z_eigvecs_batch_dev", True)):
+            if hasattr(lib, nm):  # (tools load builds of earlier commits to time their single calls)
+                mats = C.c_void_p if dev else dpp
+                getattr(lib, nm).argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, mats, mats, dp, dp, i32p, C.c_char,
+                                             C.c_int, u8p, C.c_int, mats, C.c_int, ip, i32p, C.POINTER(BevecStats), ip]
         self.ctx = C.c_void_p()
         rc = lib.psd_create(C.byref(self.ctx), device)
         if rc != 0:
@@ -1844,7 +1849,7 @@ class Engine:
             if len(ps.Z) == 0 or ps.Z[0].shape[0] == 0:
                 raise ValueError("eigvecs requires Schur vectors in the PSD")  # vectors.jl:30-32
             if any(np.iscomplexobj(t) for t in ps.Ts):
-                raise NotImplementedPSD("eigvecs_batch: Float64 only (use eigvecs per problem for ComplexF64)")
+                raise NotImplementedPSD("eigvecs_batch: Float64 only (ComplexF64 problems: zeigvecs_batch)")
             if any(np.iscomplexobj(z) for z in ps.Z):
                 raise TypeError("eigvecs: the factors T and the Schur vectors Z must be all real or all complex")
             nq = ps.Ts[0].shape[0]
@@ -1896,7 +1901,7 @@ class Engine:
         if T.dim() != 4 or T.shape[2] != T.shape[3] or Z.shape != T.shape:
             raise DimensionMismatch("a device batch is [nb, p, n, n] tensors T and Z of square factors")
         if T.is_complex() or Z.is_complex():
-            raise NotImplementedPSD("eigvecs_batch: Float64 only (use eigvecs_dev per problem for ComplexF64)")
+            raise NotImplementedPSD("eigvecs_batch: Float64 only (ComplexF64 problems: zeigvecs_batch)")
         if not (T.is_cuda and Z.is_cuda):
             raise TypeError("device-resident eigvecs_batch needs GPU tensors (use a list of PeriodicSchur for host input)")
         nb, p, n = T.shape[0], T.shape[1], T.shape[2]
@@ -1932,6 +1937,124 @@ class Engine:
             dV.zero_()
         torch.cuda.synchronize(T.device)
         self.lib.psd_d_eigvecs_batch_dev(*head, C.c_void_p(dV.data_ptr()), max(maxvec, 1), *tail)
+        self._raise(info.value)
+        self.eigvecs_batch_stats = st
+        self.eigvecs_batch_counts = cnts
+        return dV[:, :, :maxvec, :].transpose(2, 3), np.array(list(nvec), dtype=np.int32)
+
+    def zeigvecs_batch(self, problems, *args, shifted=True, lr="R", schurindex=1):
+        """eigvecs(ps, select; shifted) by periodic back-substitution for MANY small ComplexF64 decompositions of one
+        shape in ONE call (psd_z_eigvecs_batch): the follow-up of zpschur_batch, the complex counterpart of
+        eigvecs_batch.  All-true signature.  Per problem the result contract is that of `_eigvecs_backsub`; a problem's
+        vectors do not depend on its place in the batch.
+
+        zeigvecs_batch(problems, select, shifted=True): `problems` a list of complex PeriodicSchur (or
+        GeneralizedPeriodicSchur with S all true) of equal order, period, orientation and schurindex; returns a list of
+        what eigvecs(ps, select, method="backsub") returns for each.
+        zeigvecs_batch(T, Z, values, select, lr=..., schurindex=..., shifted=True): the torch outputs of the
+        device-resident zpschur_batch_ ([nb, p, n, n] complex128 tensors, values [nb, n]); returns (V, nvec) shaped as
+        eigvecs_batch returns them.
+
+        `select`: [nb][n] flags, or one [n] row used for every problem, used as given.  A problem whose row is all false
+        costs nothing and gets no columns.  Stats and counters are left in `self.eigvecs_batch_stats` and
+        `self.eigvecs_batch_counts`, as by eigvecs_batch."""
+        if hasattr(problems, "data_ptr"):
+            if len(args) != 3:
+                raise TypeError("zeigvecs_batch(T, Z, values, select, lr=..., schurindex=...)")
+            return self._zeigvecs_batch_dev(problems, args[0], args[1], args[2], lr, schurindex, shifted)
+        if len(args) != 1:
+            raise TypeError("zeigvecs_batch(problems, select, shifted=True)")
+        problems = list(problems)
+        nb = len(problems)
+        if nb == 0:
+            self.eigvecs_batch_stats = BevecStats()
+            self.eigvecs_batch_counts = np.zeros((0, 3), dtype=np.int32)
+            return []
+        n = p = None
+        Ts, Zs = [], []
+        for ps in problems:
+            if isinstance(ps, GeneralizedPeriodicSchur) and not all(ps.S):
+                raise NotImplementedPSD("zeigvecs_batch: signed GeneralizedPeriodicSchur (use geigvecs per problem)")
+            if len(ps.Z) == 0 or ps.Z[0].shape[0] == 0:
+                raise ValueError("eigvecs requires Schur vectors in the PSD")  # vectors.jl:30-32
+            cplx = [np.iscomplexobj(a) for a in list(ps.Ts) + list(ps.Z)]
+            if not any(cplx):
+                raise TypeError("zeigvecs_batch: ComplexF64 only (Float64 problems: eigvecs_batch)")
+            if not all(cplx):
+                raise TypeError("eigvecs: the factors T and the Schur vectors Z must be all real or all complex")
+            nq = ps.Ts[0].shape[0]
+            if n is None:
+                n, p, orient, si = nq, len(ps.Ts), ps.orientation, ps.schurindex
+            if (nq != n or len(ps.Ts) != p or len(ps.Z) != p or ps.orientation != orient or ps.schurindex != si
+                    or any(t.shape != (n, n) for t in ps.Ts) or any(z.shape != (n, n) for z in ps.Z)):
+                raise DimensionMismatch("the problems of a batch must have equal order, period, orientation and schurindex")
+            Ts += [np.asfortranarray(t, dtype=np.complex128) for t in ps.Ts]  # (read only: the problems are never written)
+            Zs += [np.asfortranarray(z, dtype=np.complex128) for z in ps.Z]
+        sel = self._batch_select(args[0], nb, n)
+        vals = [self._evec_values(ps, True) for ps in problems]
+        alpha, beta, sc = (np.ascontiguousarray(np.array([v[k] for v in vals])) for k in range(3))
+        nvec = (C.c_int * nb)()
+        cnts = np.zeros((nb, 3), dtype=np.int32)
+        st = BevecStats()
+        info = C.c_int(0)
+        head = [self.ctx, nb, n, p, self._ptrs(Ts), self._ptrs(Zs)] + self._evec_ptrs([alpha, beta, sc]) + [
+            orient.encode(), int(si), sel.ctypes.data_as(C.POINTER(C.c_uint8)), int(bool(shifted))]
+        tail = [nvec, cnts.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(st), C.byref(info)]
+        self.lib.psd_z_eigvecs_batch(*head, None, 0, *tail)  # size query: nvec
+        self._raise(info.value)
+        maxvec = max(nvec)
+        nmat = p if shifted else 1
+        Vs = [np.zeros((n, maxvec), dtype=np.complex128, order="F") for _ in range(nb * nmat)]
+        self.lib.psd_z_eigvecs_batch(*head, self._ptrs(Vs), maxvec, *tail)
+        self._raise(info.value)
+        self.eigvecs_batch_stats = st
+        self.eigvecs_batch_counts = cnts
+        return [[np.asfortranarray(Vs[q * nmat + l][:, :nvec[q]]) for l in range(nmat)] for q in range(nb)]
+
+    def _zeigvecs_batch_dev(self, T, Z, values, select, lr, schurindex, shifted):
+        import torch
+
+        if Z is None:
+            raise ValueError("eigvecs requires Schur vectors in the PSD")
+        if T.dim() != 4 or T.shape[2] != T.shape[3] or Z.shape != T.shape:
+            raise DimensionMismatch("a device batch is [nb, p, n, n] tensors T and Z of square factors")
+        if not T.is_complex() and not Z.is_complex():
+            raise TypeError("zeigvecs_batch: ComplexF64 only (Float64 problems: eigvecs_batch)")
+        if not (T.is_complex() and Z.is_complex()):
+            raise TypeError("eigvecs: the factors T and the Schur vectors Z must be all real or all complex")
+        if not (T.is_cuda and Z.is_cuda):
+            raise TypeError("device-resident zeigvecs_batch needs GPU tensors (use a list of PeriodicSchur for host input)")
+        nb, p, n = T.shape[0], T.shape[1], T.shape[2]
+        orient = char_lr(lr)
+        nmat = p if shifted else 1
+        if nb == 0:
+            self.eigvecs_batch_stats = BevecStats()
+            self.eigvecs_batch_counts = np.zeros((0, 3), dtype=np.int32)
+            return torch.zeros((0, nmat, n, 0), dtype=torch.complex128, device=T.device), np.zeros(0, dtype=np.int32)
+        sel = self._batch_select(select, nb, n)
+        vals = np.ascontiguousarray(values, dtype=np.complex128)
+        if vals.shape != (nb, n):
+            raise DimensionMismatch("values must be [nb, n]")
+        # [nb][p][n][n] blocks of column-major matrices: the transpose of each factor, contiguous (what zpschur_batch_
+        # returns a view of: no copy then)
+        dT = T.to(torch.complex128).transpose(2, 3).contiguous()
+        dZ = Z.to(torch.complex128).transpose(2, 3).contiguous()
+        nvec = (C.c_int * nb)()
+        cnts = np.zeros((nb, 3), dtype=np.int32)
+        st = BevecStats()
+        info = C.c_int(0)
+        ev = [vals, np.ones((nb, n)), np.zeros((nb, n), dtype=np.int32)]  # (as eigvecs_dev passes them)
+        head = [self.ctx, nb, n, p, C.c_void_p(dT.data_ptr()), C.c_void_p(dZ.data_ptr())] + self._evec_ptrs(ev) + [
+            orient.encode(), int(schurindex), sel.ctypes.data_as(C.POINTER(C.c_uint8)), int(bool(shifted))]
+        tail = [nvec, cnts.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(st), C.byref(info)]
+        self.lib.psd_z_eigvecs_batch_dev(*head, None, 0, *tail)  # size query
+        self._raise(info.value)
+        maxvec = max(nvec)
+        dV = torch.empty((nb, nmat, max(maxvec, 1), n), dtype=torch.complex128, device=T.device)
+        if maxvec == 0:
+            dV.zero_()
+        torch.cuda.synchronize(T.device)
+        self.lib.psd_z_eigvecs_batch_dev(*head, C.c_void_p(dV.data_ptr()), max(maxvec, 1), *tail)
         self._raise(info.value)
         self.eigvecs_batch_stats = st
         self.eigvecs_batch_counts = cnts

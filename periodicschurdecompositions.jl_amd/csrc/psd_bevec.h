@@ -3,7 +3,8 @@
 // host driver is psd_bevec_host.inl.  The algebra — the affine maps of the cyclic recurrence, the pivot rule (psd_ev_y0,
 // psd_ev_solve2), the power-of-two rescaling (psd_ev_shift, psd_ev_col::rescale), the epilogue of the back-transform
 // (psd_ev_store) and the normalisation (psd_ev_norm_col) — is that of psd_evec.h, called from here; what is new is how
-// the work is laid out.
+// the work is laid out.  The solve body is a template: its complex instantiation, for the decompositions
+// psd_z_pschur_batch leaves, and the complex back-transform are in psd_zbevec.h (driver psd_zbevec_host.inl).
 //
 // At these orders the single path is launch-bound (a GEMM and a solve launch per 16-row chunk, two host round trips,
 // five allocations, per problem) and its solve kernel gives one lane to each factor, so that at p = 4 sixty of the 64
@@ -69,13 +70,14 @@ struct psd_bev_args {
 
 #define PSD_BEV_LDS (192 * sizeof(psd_ev_map) + 128 * sizeof(psd_z) + 5 * 64 * sizeof(int))
 
-// the single path's view of problem q: psd_ev_col then addresses its factors, X and tables
+// the single path's view of problem q: psd_ev_col then addresses its factors, X and tables (CPLX: T interleaved complex)
+template <bool CPLX>
 PSD_D void psd_bev_colargs(const psd_bev_args& a, int q, psd_ev_args& e) {
     const int n = a.n;
     const size_t xs = (size_t)a.p * n * a.nsm;
     const int* tab = a.itab + psd_bev_ihead(a.p) + (size_t)q * psd_bev_istride(n);
     const double* dt = a.dtab + (size_t)q * psd_bev_dstride(n);
-    e.T = a.T + (size_t)q * a.p * n * n;
+    e.T = a.T + (size_t)q * a.p * n * n * (CPLX ? 2 : 1);
     e.wmap = a.itab;
     e.bsz = tab;
     e.k0 = tab + n;
@@ -100,6 +102,8 @@ struct psd_bev_blk {
     int q, j, i1, i, b, ke;
     bool act, isown;
 };
+// (a complex form has no 2x2 blocks: every block is one row, whatever the table says)
+template <bool CPLX>
 PSD_D psd_bev_blk psd_bev_block(const psd_bev_args& a, const int* cq, const int* cj, const int* ci1, int c) {
     psd_bev_blk k;
     k.q = cq[c];
@@ -112,28 +116,32 @@ PSD_D psd_bev_blk psd_bev_block(const psd_bev_args& a, const int* cq, const int*
         const int* tab = a.itab + psd_bev_ihead(a.p) + (size_t)k.q * psd_bev_istride(a.n);
         k.ke = tab[3 * a.n + k.j];
         k.isown = k.i1 == k.ke;
-        k.b = k.isown ? tab[2 * a.n + k.j] : (tab[k.i1 - 1] == 0 ? 2 : 1);
+        k.b = CPLX ? 1 : (k.isown ? tab[2 * a.n + k.j] : (tab[k.i1 - 1] == 0 ? 2 : 1));
         k.i = k.i1 - k.b;
     }
     return k;
 }
 
 // the map of factor l in the block: y_{l+1}(I) = (D_l y_l(I) + r_l(I)) / mu
-PSD_D psd_ev_map psd_bev_fmap(const psd_ev_col<false>& col, const psd_bev_blk& k, int l, psd_z rmu, const psd_z* r) {
+template <bool CPLX>
+PSD_D psd_ev_map psd_bev_fmap(const psd_ev_col<CPLX>& col, const psd_bev_blk& k, int l, psd_z rmu, const psd_z* r) {
     psd_ev_map m = psd_ev_ident();
     psd_z D[2][2];
-    col.d(l, k.i, k.b, D);
+    const int b = CPLX ? 1 : k.b;  // (complex: D[q][kk] with q, kk > 0 is not loaded)
+    col.d(l, k.i, b, D);
     for (int q = 0; q < 2; ++q)
-        for (int kk = 0; kk < 2; ++kk) m.A[q][kk] = (q < k.b && kk < k.b) ? zmul(D[q][kk], rmu) : zmk(0.0, 0.0);
+        for (int kk = 0; kk < 2; ++kk) m.A[q][kk] = (q < b && kk < b) ? zmul(D[q][kk], rmu) : zmk(0.0, 0.0);
     if (!k.isown)
         for (int q = 0; q < 2; ++q)  // (constant bounds: the maps stay in registers)
-            if (q < k.b) m.c[q] = zmul(r[2 * l + q], rmu);
+            if (q < b) m.c[q] = zmul(r[2 * l + q], rmu);
     psd_ev_mnorm(m);
     return m;
 }
 
-// (one wavefront per workgroup: the launch bound lifts the register cap of the 1024-thread default, so nothing spills)
-PSD_KERNEL_B(64) psd_bev_solve(psd_bev_args a) {
+// The body of psd_bev_solve (real: 1x1 and 2x2 row blocks) and of psd_zbev_solve (psd_zbevec.h; complex: the block width
+// is 1 at compile time, so stage A has C p tasks and the second row of a block is never looked at).
+template <bool CPLX>
+PSD_D void psd_bev_solve_body(const psd_bev_args& a) {
     PSD_LDS_DECL;
     psd_ev_map* buf = (psd_ev_map*)psd_lds;  // [2][64]: the scan
     psd_ev_map* v0s = buf + 128;             // [C]: y_0(I) of a unit
@@ -174,13 +182,13 @@ PSD_KERNEL_B(64) psd_bev_solve(psd_bev_args a) {
         // A: the update products, dealt over the 64 lanes
         PSD_PAR_FOR(t, 64) {
             const int cp = C * p;
-            for (int tau = t; tau < 2 * cp; tau += 64) {
+            for (int tau = t; tau < (CPLX ? 1 : 2) * cp; tau += 64) {
                 const int qr = tau / cp, c = (tau - qr * cp) / p, l = tau - qr * cp - c * p;
-                const psd_bev_blk k = psd_bev_block(a, cq, cj, ci1, c);
+                const psd_bev_blk k = psd_bev_block<CPLX>(a, cq, cj, ci1, c);
                 if (!k.act || k.isown || qr >= k.b) continue;
                 psd_ev_args e;
-                psd_bev_colargs(a, k.q, e);
-                const psd_ev_col<false> col(e, k.j);
+                psd_bev_colargs<CPLX>(a, k.q, e);
+                const psd_ev_col<CPLX> col(e, k.j);
                 psd_z s = zmk(0.0, 0.0);
                 for (int kk = k.i1; kk < k.ke; ++kk) s = zadd(s, zmul(col.w(l, k.i + qr, kk), col.x(l, kk)));
                 (rg ? rg : rl + 2 * LW * c)[2 * l + qr] = s;
@@ -190,12 +198,12 @@ PSD_KERNEL_B(64) psd_bev_solve(psd_bev_args a) {
         // B: the maps of the owned factors, then the segmented scan
         PSD_PAR_FOR(t, 64) {
             const int c = t / LW, li = t - c * LW;
-            const psd_bev_blk k = psd_bev_block(a, cq, cj, ci1, c);
+            const psd_bev_blk k = psd_bev_block<CPLX>(a, cq, cj, ci1, c);
             psd_ev_map seg = psd_ev_ident();
             if (k.act) {
                 psd_ev_args e;
-                psd_bev_colargs(a, k.q, e);
-                const psd_ev_col<false> col(e, k.j);
+                psd_bev_colargs<CPLX>(a, k.q, e);
+                const psd_ev_col<CPLX> col(e, k.j);
                 const psd_z rmu = zdiv(zmk(1.0, 0.0), zmk(e.mu[2 * k.j], e.mu[2 * k.j + 1]));
                 const psd_z* r = rg ? rg : rl + 2 * LW * c;
                 int lo, hi;
@@ -218,12 +226,12 @@ PSD_KERNEL_B(64) psd_bev_solve(psd_bev_args a) {
         // C: y_0(I) round the period, and the largest entry y_l(I) will have
         PSD_PAR_FOR(t, 64) {
             const int c = t / LW, li = t - c * LW;
-            const psd_bev_blk k = psd_bev_block(a, cq, cj, ci1, c);
+            const psd_bev_blk k = psd_bev_block<CPLX>(a, cq, cj, ci1, c);
             int mx = -100000;
             if (k.act) {
                 psd_ev_args e;
-                psd_bev_colargs(a, k.q, e);
-                const psd_ev_col<false> col(e, k.j);
+                psd_bev_colargs<CPLX>(a, k.q, e);
+                const psd_ev_col<CPLX> col(e, k.j);
                 const psd_z rmu = zdiv(zmk(1.0, 0.0), zmk(e.mu[2 * k.j], e.mu[2 * k.j + 1]));
                 const psd_z* r = rg ? rg : rl + 2 * LW * c;
                 psd_z y[2];
@@ -250,11 +258,11 @@ PSD_KERNEL_B(64) psd_bev_solve(psd_bev_args a) {
         // D: a column growing past 2^PSD_EV_BIG is scaled down first; then y_l(I), in the scale of the stored rows
         PSD_PAR_FOR(t, 64) {
             const int c = t / LW, li = t - c * LW;
-            const psd_bev_blk k = psd_bev_block(a, cq, cj, ci1, c);
+            const psd_bev_blk k = psd_bev_block<CPLX>(a, cq, cj, ci1, c);
             if (k.act) {
                 psd_ev_args e;
-                psd_bev_colargs(a, k.q, e);
-                const psd_ev_col<false> col(e, k.j);
+                psd_bev_colargs<CPLX>(a, k.q, e);
+                const psd_ev_col<CPLX> col(e, k.j);
                 const psd_z rmu = zdiv(zmk(1.0, 0.0), zmk(e.mu[2 * k.j], e.mu[2 * k.j + 1]));
                 const psd_z* r = rg ? rg : rl + 2 * LW * c;
                 int big = -100000;
@@ -275,12 +283,15 @@ PSD_KERNEL_B(64) psd_bev_solve(psd_bev_args a) {
         }
         PSD_SYNC();
         PSD_PAR_FOR(t, C) {
-            const psd_bev_blk k = psd_bev_block(a, cq, cj, ci1, t);
+            const psd_bev_blk k = psd_bev_block<CPLX>(a, cq, cj, ci1, t);
             if (k.act) ci1[t] = k.i;
         }
         PSD_SYNC();
     }
 }
+
+// (one wavefront per workgroup: the launch bound lifts the register cap of the 1024-thread default, so nothing spills)
+PSD_KERNEL_B(64) psd_bev_solve(psd_bev_args a) { psd_bev_solve_body<false>(a); }
 
 // the sub-diagonals of the quasi-triangular factors (block `blk` of every problem): out [nb][n]
 PSD_KERNEL psd_bev_subdiag(const double* T, int n, int p, int blk, int nb, double* out) {

@@ -23,6 +23,7 @@
 #include "psd_evec.h"
 #include "psd_gevec.h"
 #include "psd_bevec.h"
+#include "psd_zbevec.h"
 #include "psd_bord.h"
 #include "psd_zbqz.h"
 #include "psd_zbord.h"
@@ -3948,6 +3949,7 @@ extern "C" int psd_dbg_apply_bench(psd_ctx* c, int n, int p, int nwin, int W, in
 #include "psd_batch_host.inl"
 #include "psd_zbatch_host.inl"
 #include "psd_bevec_host.inl"
+#include "psd_zbevec_host.inl"
 #include "psd_bord_host.inl"
 #include "psd_zbord_host.inl"
 #include "psd_diag_scalar.inl"

@@ -11,6 +11,8 @@ device times and the launches of the stats, and the largest difference between t
   (default)  n in {8, 16, 32, 64, 128}, p in {2, 4, 16}, nb in {32, 1024}
   --sweep    n across the cap PSD_BEV_NMAX at nb = 64, p = 4, on the diagnostic library with the cap lifted
              (PSD_BEV_NMAX in the environment), so that every order takes the batched kernels
+  --complex  ComplexF64 factors: zpschur_batch_, then Engine.zeigvecs_batch (psd_z_eigvecs_batch_dev) against the loop
+             of Engine.eigvecs_dev on the complex T, Z
 
 Every shape runs in a process of its own under `timeout`; the tool stops at the first one that fails.  One JSON line per
 shape on stdout; --json FILE collects them."""
@@ -33,7 +35,7 @@ def default_shapes():
     return [(nb, n, p) for nb in (32, 1024) for n in (8, 16, 32, 64, 128) for p in (2, 4, 16)]
 
 
-def run_one(nb, n, p, lr, sweep):
+def run_one(nb, n, p, lr, sweep, cplx=False):
     import numpy as np
     import torch
 
@@ -47,20 +49,22 @@ def run_one(nb, n, p, lr, sweep):
         eng = psd_amd.Engine(0)
     gen = torch.Generator(device="cuda")
     gen.manual_seed(9000 + n + 1000 * p)
-    A = torch.eye(n, dtype=torch.float64, device="cuda") + 0.5 * torch.randn(
-        (nb, p, n, n), dtype=torch.float64, device="cuda", generator=gen) / np.sqrt(n)
+    dt = torch.complex128 if cplx else torch.float64  # (complex: real and imaginary parts N(0, 1/2) each)
+    A = torch.eye(n, dtype=dt, device="cuda") + 0.5 * torch.randn(
+        (nb, p, n, n), dtype=dt, device="cuda", generator=gen) / np.sqrt(n)
     infos = []
-    T, Z, values, _ = eng.pschur_batch_(A, lr, infos_out=infos)
+    T, Z, values, _ = (eng.zpschur_batch_ if cplx else eng.pschur_batch_)(A, lr, infos_out=infos)
+    batched = eng.zeigvecs_batch if cplx else eng.eigvecs_batch
     si = p if lr == "L" else 1
     select = np.ones((nb, n), dtype=bool)
     select[[q for q in range(nb) if infos[q] != 0]] = False  # (a problem that did not converge is skipped)
     Tc, Zc = T.transpose(2, 3), Z.transpose(2, 3)  # the [nb][p][n][n] column-major blocks, contiguous
     assert Tc.is_contiguous() and Zc.is_contiguous()
-    row = dict(nb=nb, n=n, p=p, lr=lr, nfailed=int(sum(1 for i in infos if i != 0)), sweep=bool(sweep))
+    row = dict(nb=nb, n=n, p=p, lr=lr, nfailed=int(sum(1 for i in infos if i != 0)), sweep=bool(sweep), complex=bool(cplx))
     for _ in range(2):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        V, nvec = eng.eigvecs_batch(T, Z, values, select, lr=lr, schurindex=si)
+        V, nvec = batched(T, Z, values, select, lr=lr, schurindex=si)
         torch.cuda.synchronize()
         st = eng.eigvecs_batch_stats
         row["batch"] = dict(wall_ms=1e3 * (time.perf_counter() - t0), ms_solve=st.ms_solve,
@@ -95,12 +99,13 @@ def main():
     ap.add_argument("--lr", default="R")
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--sweep-orders", default="64,96,128,160,192,256")
+    ap.add_argument("--complex", action="store_true", dest="cplx")
     ap.add_argument("--timeout", type=int, default=240, help="seconds per shape")
     ap.add_argument("--json", default=None)
     ap.add_argument("--one", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.one:
-        run_one(*parse_shapes(args.one)[0], args.lr, args.sweep)
+        run_one(*parse_shapes(args.one)[0], args.lr, args.sweep, args.cplx)
         return 0
     if args.shapes:
         shapes = parse_shapes(args.shapes)
@@ -111,7 +116,8 @@ def main():
     rows = []
     for s in shapes:
         cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--one",
-               "%dx%dx%d" % s, "--lr", args.lr] + (["--sweep"] if args.sweep else [])
+               "%dx%dx%d" % s, "--lr", args.lr] + (["--sweep"] if args.sweep else []) + (
+                   ["--complex"] if args.cplx else [])
         pr = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
         sys.stdout.write(pr.stdout)
         sys.stdout.flush()
