@@ -209,6 +209,43 @@ int psd_z_pschur_hess_batch(psd_ctx* ctx, int nb, int n, int p, double* const* H
                             int maxitfac, double* alpha, double* beta, int32_t* ascale, int* infos, psd_stats* stats,
                             int* info);
 
+/* ---- the same batch entries for ComplexF64 with a SIGNED signature ------------------------------------------------
+ * pschur!(A, S, lr) of generalized.jl:108-148 — the path behind gpschur(As, Bs), the generalized periodic eigenproblem
+ * B_p^-1 A_p ... B_1^-1 A_1 (one pair: the QZ problem of a pencil) — for nb problems of one shape (n, p) and ONE
+ * signature S (p bytes, user order, non-zero = +1) per call.  Conventions as the all-true entries above.  One workgroup
+ * runs stage 1 of one problem's signed Hessenberg reduction (generalized.jl:988-1033); stage 2 (:1034-1079) and the
+ * signed periodic QZ iteration run ONE WAVEFRONT PER PROBLEM, one launch each per group, so a problem's result does not
+ * depend on its place in the batch.  Orders above 128 run the single call's reduction and iteration problem by problem
+ * on the batch buffer.  An all-true or NULL S takes the all-true entries' path: the results are then theirs, bit for
+ * bit.  infos[nb] (may be NULL): PSD_INFO_NOCONV + level for a problem that exhausts its sweep budget,
+ * PSD_INFO_RUNTIME + 77 for a rotation list that overflowed, PSD_INFO_RUNTIME + 0xfffe for one whose in-kernel loop hit
+ * its bound; the others are complete.  The return value is the first non-zero per-problem code, or a call-wide code.
+ * stats: the times are sums over the call, the counters sums over the problems (reserved = ncase2 + 1000 * ncase3,
+ * summed as the two counts).
+ * info (all four): -1 ctx; -2 nb < 1; -3 n; -4 p; -5 A / H NULL; -6 orient (psd_z_gpschur_hess_batch: wantZ without Q);
+ * -7 the entry of S that lands leftmost in working order (S[0] for 'R' and the two Hessenberg entries, S[p-1] for 'L')
+ * is false; -9 maxitfac < 1; -10 wantZ without Z; -11 alpha, beta or ascale NULL.
+ *
+ * psd_z_gphessenberg_batch: _phessenberg!(A, S; wantQ) for each problem, as psd_z_gphessenberg: A (nb * p pointers)
+ * overwritten by H_l, Q (nb * p pointers, or NULL) receives Qs[l]. */
+int psd_z_gphessenberg_batch(psd_ctx* ctx, int nb, int n, int p, double* const* A, const uint8_t* S, double* const* Q,
+                             psd_stats* stats, int* info);
+/* pschur!(A::Vector{Matrix{ComplexF64}}, S, lr) for each of nb problems: A / Z nb * p pointers in user order, as
+ * psd_z_pschur_batch; schurindex: 1 for 'R', p for 'L'. */
+int psd_z_gpschur_batch(psd_ctx* ctx, int nb, int n, int p, double* const* A, const uint8_t* S, char orient, int wantT,
+                        int wantZ, int maxitfac, double* const* Z, double* alpha, double* beta, int32_t* ascale, int* infos,
+                        int* schurindex, psd_stats* stats, int* info);
+/* Device-resident variant: dA, dZ device [nb][p][n][n] column-major complex blocks in user order (dZ may be NULL when
+ * !wantZ), overwritten; S, alpha / beta / ascale / infos are host buffers. */
+int psd_z_gpschur_batch_dev(psd_ctx* ctx, int nb, int n, int p, double* dA, const uint8_t* S, char orient, int wantT,
+                            int wantZ, int maxitfac, double* dZ, double* alpha, double* beta, int32_t* ascale, int* infos,
+                            int* schurindex, psd_stats* stats, int* info);
+/* nb Hessenberg-triangular ComplexF64 problems with the signature S (internal order): pschur!(H1, Hs, S; wantT, wantZ,
+ * Q, maxitfac) for each; H / Q as psd_z_pschur_hess_batch. */
+int psd_z_gpschur_hess_batch(psd_ctx* ctx, int nb, int n, int p, double* const* H, const uint8_t* S, double* const* Q,
+                             int wantT, int wantZ, int maxitfac, double* alpha, double* beta, int32_t* ascale, int* infos,
+                             psd_stats* stats, int* info);
+
 /* Device-resident variant of psd_d_pschur: dA, dZ are device pointers to [p][n][n] blocks in user
  * order (dZ may be NULL when !wantZ).  wr/wi/sweeplog are host buffers. */
 int psd_d_pschur_dev(psd_ctx* ctx, int n, int p, double* dA, char orient, int wantT, int wantZ, int maxitfac,

@@ -24,7 +24,7 @@ import PeriodicSchurDecompositions: pschur!, pschur, phessenberg!, gpschur, Peri
 const PSD = PeriodicSchurDecompositions
 using ArnoldiMethod: ArnoldiMethod
 
-export set_train!, engine_version, pschur_batch!, pschur_batch, eigvecs_batch_device, ordschur_batch!
+export set_train!, engine_version, pschur_batch!, pschur_batch, gpschur_batch, eigvecs_batch_device, ordschur_batch!
 
 const libpsd = get(ENV, "LIBPSD_MI355X", joinpath(@__DIR__, "..", "periodicschurdecompositions.jl_amd", "libpsd_mi355x.so"))
 
@@ -219,6 +219,62 @@ pschur_batch(problems::AbstractVector, lr::Symbol = :R; kwargs...) =
     any(A -> any(a -> eltype(a) <: Complex, A), problems) ?
     pschur_batch!([Matrix{ComplexF64}[Matrix{ComplexF64}(a) for a in A] for A in problems], lr; kwargs...) :
     pschur_batch!([Matrix{Float64}[Matrix{Float64}(a) for a in A] for A in problems], lr; kwargs...)
+
+# pschur_batch!(problems, S, lr; wantZ, wantT, maxitfac, infos) — pschur!(A, S, lr) (generalized.jl:108-148) for many small
+# ComplexF64 problems of equal order and period and ONE signature S in ONE call (psd_z_gpschur_batch): the signed
+# Hessenberg reduction and the signed periodic QZ, one workgroup / one wavefront per problem.  Works in place; returns a
+# Vector{GeneralizedPeriodicSchur}.  An all-true S runs the path of pschur_batch!(problems, lr).  Failures and `infos` as
+# pschur_batch!(problems, lr).
+function pschur_batch!(problems::Vector{Vector{Matrix{ComplexF64}}}, S::AbstractVector{Bool}, lr::Symbol = :R;
+                       wantZ::Bool = true, wantT::Bool = true, maxitfac = 30,
+                       infos::Union{Nothing, Vector{Cint}} = nothing)
+    orient = PSD.char_lr(lr)
+    nb = length(problems)
+    nb == 0 && return GeneralizedPeriodicSchur[]
+    p = length(problems[1]); n = _check(problems[1])
+    for A in problems
+        (length(A) == p && _check(A) == n) || throw(DimensionMismatch("the problems of a batch must have equal order and period"))
+    end
+    length(S) == p || throw(DimensionMismatch("one sign per factor"))
+    (orient == 'L' ? S[p] : S[1]) || throw(ArgumentError("The leftmost entry in S must be true"))  # generalized.jl:140
+    flat = reduce(vcat, problems)
+    Z = wantZ ? [Matrix{ComplexF64}(undef, n, n) for _ in 1:(nb * p)] : Matrix{ComplexF64}[]
+    α = zeros(ComplexF64, n, nb); β = zeros(Float64, n, nb); sc = zeros(Int32, n, nb)
+    codes = infos === nothing ? Vector{Cint}(undef, nb) : infos
+    length(codes) == nb || throw(DimensionMismatch("infos must have one entry per problem"))
+    si = Ref{Cint}(0); info = Ref{Cint}(0)
+    Ap = _ptrs(flat); Zp = _ptrs(Z); Sb = UInt8.(S)
+    GC.@preserve flat Z α β sc codes Sb begin
+        ccall((:psd_z_gpschur_batch, libpsd), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Ptr{Float64}}, Ptr{UInt8}, Cchar, Cint, Cint, Cint,
+               Ptr{Ptr{Float64}}, Ptr{ComplexF64}, Ptr{Float64}, Ptr{Int32}, Ptr{Cint}, Ref{Cint}, Ptr{Cvoid}, Ref{Cint}),
+              ctx().ptr, nb, n, p, Ap, Sb, orient, wantT, wantZ, maxitfac,
+              wantZ ? Zp : C_NULL, α, β, sc, codes, si, C_NULL, info)
+    end
+    (info[] < 0 || (info[] >= INFO_NOTIMPL && !(info[] in codes))) && _throw(info[])
+    js = Int(si[])
+    out = map(1:nb) do q
+        A = problems[q]
+        T1 = A[js]; Tv = [A[j] for j in 1:p if j != js]
+        Zq = wantZ ? Z[((q - 1) * p + 1):(q * p)] : [similar(T1, 0, 0)]
+        GeneralizedPeriodicSchur(collect(Bool, S), js, T1, Tv, Zq, α[:, q], complex.(β[:, q]), Int.(sc[:, q]), orient)
+    end
+    infos === nothing && foreach(_throw, codes)
+    out
+end
+pschur_batch(problems::AbstractVector, S::AbstractVector{Bool}, lr::Symbol = :R; kwargs...) =
+    pschur_batch!([Matrix{ComplexF64}[Matrix{ComplexF64}(a) for a in A] for A in problems], S, lr; kwargs...)
+
+# gpschur_batch(Aslist, Bslist) — gpschur(As, Bs) (generalized.jl:1191-1211) for many pairs of series of equal shape in ONE
+# call: the interleaving of gpschur per problem, then pschur_batch! with the common alternating signature
+function gpschur_batch(Aslist::AbstractVector, Bslist::AbstractVector; kwargs...)
+    length(Aslist) == length(Bslist) || throw(DimensionMismatch("one Bs per As"))
+    isempty(Aslist) && return GeneralizedPeriodicSchur[]
+    args = [PSD._mkpsargs(collect(As), Bs) for (As, Bs) in zip(Aslist, Bslist)]
+    Ss = args[1][2]
+    all(a -> a[2] == Ss, args) || throw(DimensionMismatch("the problems of a batch must have equal order and period"))
+    pschur_batch!([Matrix{ComplexF64}[Matrix{ComplexF64}(c) for c in a[1]] for a in args], collect(Bool, Ss); kwargs...)
+end
 
 # ordschur_batch!(problems, select; wantZ, infos) — no reference equivalent: ordschur!(P, select; wantZ) (rordschur.jl:3-132)
 # for many small Float64 decompositions of equal order, period, orientation and schurindex (1 or p) in ONE call

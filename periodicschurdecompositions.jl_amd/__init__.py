@@ -329,6 +329,14 @@ class Engine:
                                              C.c_int, mats, dp, dp, i32p, ip, ip, C.POINTER(Stats), ip]
             lib.psd_z_pschur_hess_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, dpp, dpp, C.c_int, C.c_int,
                                                     C.c_int, dp, dp, i32p, ip, C.POINTER(Stats), ip]
+        if hasattr(lib, "psd_z_gpschur_batch"):  # (as above)
+            lib.psd_z_gphessenberg_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, dpp, C.POINTER(C.c_uint8), dpp,
+                                                     C.POINTER(Stats), ip]
+            for nm, mats in (("psd_z_gpschur_batch", dpp), ("psd_z_gpschur_batch_dev", C.c_void_p)):
+                getattr(lib, nm).argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, mats, C.POINTER(C.c_uint8), C.c_char,
+                                             C.c_int, C.c_int, C.c_int, mats, dp, dp, i32p, ip, ip, C.POINTER(Stats), ip]
+            lib.psd_z_gpschur_hess_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, dpp, C.POINTER(C.c_uint8), dpp,
+                                                     C.c_int, C.c_int, C.c_int, dp, dp, i32p, ip, C.POINTER(Stats), ip]
         for nm, mats in (("psd_d_ordschur_batch", dpp), ("psd_d_ordschur_batch_dev", C.c_void_p)):
             if hasattr(lib, nm):  # (tools load builds of earlier commits to time their single calls)
                 getattr(lib, nm).argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, mats, mats, C.c_char, C.c_int,
@@ -961,13 +969,14 @@ class Engine:
         return n, p, flat
 
     def _zbatch_finish(self, nb, n, p, Tall, Zall, alpha, beta, sc, infos, orient, si, st, info, infos_out,
-                       general=False):
+                       general=False, S=None):
         if info.value < 0 or info.value >= INFO_NOTIMPL:
             if not any(int(infos[q]) == info.value for q in range(nb)):  # (a call-wide code: nothing is complete)
                 self._raise(info.value)
         out = []
         for q in range(nb):
-            g = GeneralizedPeriodicSchur([True] * p, Tall[q * p:(q + 1) * p], Zall[q * p:(q + 1) * p] if Zall else [],
+            g = GeneralizedPeriodicSchur([True] * p if S is None else list(S), Tall[q * p:(q + 1) * p],
+                                         Zall[q * p:(q + 1) * p] if Zall else [],
                                          alpha[q], beta[q], sc[q], orient, si, st)
             out.append(g if general else PeriodicSchur(g.Ts, g.Z, g.values, orient, si, st))
         if infos_out is not None:
@@ -999,10 +1008,11 @@ class Engine:
             out.append(([np.triu(a, -1 if j == 0 else 0) for j, a in enumerate(A)], tau[q]))
         return out, st
 
-    def zpschur_batch_(self, problems, lr="R", wantZ=True, wantT=True, maxitfac=30, infos_out=None):
+    def zpschur_batch_(self, problems, lr="R", wantZ=True, wantT=True, maxitfac=30, infos_out=None, S=None):
         """pschur!(A::Vector{Matrix{ComplexF64}}, lr; wantZ, wantT, maxitfac) for many small problems of equal shape in
         ONE call (psd_z_pschur_batch): the reduction and the Q formation one workgroup per problem (and factor), the
-        iteration one wavefront per problem in a single launch.  All signatures +1.
+        iteration one wavefront per problem in a single launch.  All signatures +1; with `S` (one signature for the
+        batch) the call is zgpschur_batch_(problems, S, lr, ...).
 
         `problems`: a list of lists of p writable Fortran-ordered complex128 n x n matrices, overwritten with the T
         factors; returns a list of PeriodicSchur.  Or one torch complex128 [nb, p, n, n] device tensor (device-resident
@@ -1011,6 +1021,8 @@ class Engine:
         A problem that fails to converge raises like the single call, after all have run — the others are complete
         then.  `infos_out`: a list that receives the per-problem info codes instead (nothing is raised for a failed
         problem then)."""
+        if S is not None:
+            return self.zgpschur_batch_(problems, S, lr, wantZ=wantZ, wantT=wantT, maxitfac=maxitfac, infos_out=infos_out)
         orient = char_lr(lr)
         if hasattr(problems, "data_ptr"):
             return self._zpschur_batch_dev(problems, orient, wantZ, wantT, maxitfac, infos_out)
@@ -1130,6 +1142,202 @@ class Engine:
         with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
             values = alpha / beta * np.exp2(sc.astype(np.float64))  # (as GeneralizedPeriodicSchur)
         return dT.transpose(2, 3), (dZ.transpose(2, 3) if wantZ else None), values, st
+
+    # ---- ComplexF64 batch family with a signed signature (psd_z_gp*_batch): gpschur(As, Bs) for many small problems
+    def _zgbatch_sig(self, S, p, orient):
+        """The signature of a batch as a C array; the checks of pschur!(A, S, lr) (src/generalized.jl:138-141)."""
+        S = [bool(x) for x in S]
+        if len(S) != p:
+            raise DimensionMismatch("length of S must match the period")
+        if not (S[p - 1] if orient == "L" else S[0]):
+            raise ValueError("The leftmost entry in S must be true")  # src/generalized.jl:140
+        return S, (C.c_uint8 * p)(*[1 if x else 0 for x in S])
+
+    def zgphessenberg_batch_(self, problems, S, wantQ=True):
+        """_phessenberg!(A, S; wantQ) for ComplexF64 (src/generalized.jl:988-1082) for a list of problems of equal shape
+        and ONE signature in ONE call (psd_z_gphessenberg_batch): stage 1 one workgroup per problem, stage 2 one
+        wavefront per problem.  `problems`: list of lists of p writable Fortran-ordered complex128 matrices, overwritten
+        with the Hessenberg / triangular factors.  Returns a list of (H list, Q list) like gphessenberg_, and the Stats
+        of the call."""
+        nb = len(problems)
+        if nb == 0:
+            return [], Stats()
+        n, p, flat = self._zbatch_shape(problems)
+        self._as_work(flat, np.complex128)
+        S, Sarr = self._zgbatch_sig(S, p, "R")
+        Qall = [np.zeros((n, n), dtype=np.complex128, order="F") for _ in range(nb * p)] if wantQ else []
+        st = Stats()
+        info = C.c_int(0)
+        self.lib.psd_z_gphessenberg_batch(self.ctx, nb, n, p, self._ptrs(flat), Sarr, self._ptrs(Qall) if wantQ else None,
+                                          C.byref(st), C.byref(info))
+        self._raise(info.value)
+        return [(flat[q * p:(q + 1) * p], Qall[q * p:(q + 1) * p] if wantQ else []) for q in range(nb)], st
+
+    def zgpschur_batch_(self, problems, S, lr="R", wantZ=True, wantT=True, maxitfac=30, infos_out=None):
+        """pschur!(A::Vector{Matrix{ComplexF64}}, S, lr; wantZ, wantT, maxitfac) (src/generalized.jl:108-148) for many
+        small problems of equal shape and ONE signature `S` in ONE call (psd_z_gpschur_batch): the signed Hessenberg
+        reduction and the signed periodic QZ iteration, one workgroup / one wavefront per problem.
+
+        `problems`: a list of lists of p writable Fortran-ordered complex128 n x n matrices, overwritten with the T
+        factors; returns a list of GeneralizedPeriodicSchur.  Or one torch complex128 [nb, p, n, n] device tensor
+        (device-resident entry, psd_z_gpschur_batch_dev; the input is not modified): returns (T, Z, values, stats).
+        An all-true `S` runs the path of zpschur_batch_ (the same bits).  Failures and `infos_out` as zpschur_batch_."""
+        orient = char_lr(lr)
+        if hasattr(problems, "data_ptr"):
+            return self._zgpschur_batch_dev(problems, S, orient, wantZ, wantT, maxitfac, infos_out)
+        nb = len(problems)
+        if nb == 0:
+            if infos_out is not None:
+                infos_out[:] = []
+            return []
+        n, p, flat = self._zbatch_shape(problems)
+        S, Sarr = self._zgbatch_sig(S, p, orient)
+        self._as_work(flat, np.complex128)
+        Zall = [np.zeros((n, n), dtype=np.complex128, order="F") for _ in range(nb * p)] if wantZ else []
+        alpha = np.zeros((nb, n), dtype=np.complex128)
+        beta = np.zeros((nb, n))
+        sc = np.zeros((nb, n), dtype=np.int32)
+        infos = (C.c_int * nb)()
+        si = C.c_int(0)
+        st = Stats()
+        info = C.c_int(0)
+        dp = C.POINTER(C.c_double)
+        self.lib.psd_z_gpschur_batch(self.ctx, nb, n, p, self._ptrs(flat), Sarr, orient.encode(), int(wantT), int(wantZ),
+                                     int(maxitfac), self._ptrs(Zall) if wantZ else None,
+                                     alpha.view(np.float64).ctypes.data_as(dp), beta.ctypes.data_as(dp),
+                                     sc.ctypes.data_as(C.POINTER(C.c_int32)), infos, C.byref(si), C.byref(st),
+                                     C.byref(info))
+        return self._zbatch_finish(nb, n, p, flat, Zall, alpha, beta, sc, infos, orient, si.value, st, info, infos_out,
+                                   general=True, S=S)
+
+    def zgpschur_batch(self, problems, S, lr="R", **kw):
+        """Copying form of zgpschur_batch_: the factors are left untouched."""
+        if hasattr(problems, "data_ptr"):
+            return self.zgpschur_batch_(problems, S, lr, **kw)
+        for A in problems:
+            if not self._is_complex(list(A)):
+                raise TypeError("zgpschur_batch: ComplexF64 only")
+        work = [[np.array(a, dtype=np.complex128, order="F", copy=True) for a in A] for A in problems]
+        return self.zgpschur_batch_(work, S, lr, **kw)
+
+    def zgpschur_hess_batch_(self, problems, S, wantT=True, wantZ=True, maxitfac=30, infos_out=None):
+        """pschur!(H1, Hs, S; wantT, wantZ, Q, maxitfac) for ComplexF64 (src/generalized.jl:166-175) for a list of
+        Hessenberg-triangular problems of equal shape and ONE signature in ONE call (psd_z_gpschur_hess_batch).
+        `problems`: list of (H1, Hs) or (H1, Hs, Q); matrices are overwritten.  Returns a list of
+        GeneralizedPeriodicSchur, as zpschur_hess_ does; failures and `infos_out` as zpschur_batch_."""
+        nb = len(problems)
+        if nb == 0:
+            if infos_out is not None:
+                infos_out[:] = []
+            return []
+        Hall, Qall = [], []
+        n = problems[0][0].shape[0]
+        p = len(problems[0][1]) + 1
+        S = [bool(x) for x in S]
+        if len(S) != p:
+            raise DimensionMismatch("S must have one entry per factor")
+        if not S[0]:
+            raise ValueError("Signature entry S[1] must be true")  # src/generalized.jl:182
+        for pr in problems:
+            H = [pr[0]] + list(pr[1])
+            if len(H) != p or _check_square(H) != n:
+                raise DimensionMismatch("the problems of a batch must have equal order and period")
+            if not self._is_complex(H):
+                raise TypeError("zgpschur_hess_batch_: ComplexF64 only")
+            self._as_work(H, np.complex128)
+            Hall += H
+            if wantZ:
+                Q = (list(pr[2]) if len(pr) > 2 and pr[2] is not None
+                     else [np.asfortranarray(np.eye(n, dtype=np.complex128)) for _ in range(p)])
+                self._as_work(Q, np.complex128)
+                Qall += Q
+        alpha = np.zeros((nb, n), dtype=np.complex128)
+        beta = np.zeros((nb, n))
+        sc = np.zeros((nb, n), dtype=np.int32)
+        infos = (C.c_int * nb)()
+        st = Stats()
+        info = C.c_int(0)
+        dp = C.POINTER(C.c_double)
+        Sarr = (C.c_uint8 * p)(*[1 if x else 0 for x in S])
+        self.lib.psd_z_gpschur_hess_batch(self.ctx, nb, n, p, self._ptrs(Hall), Sarr, self._ptrs(Qall) if wantZ else None,
+                                          int(wantT), int(wantZ), int(maxitfac),
+                                          alpha.view(np.float64).ctypes.data_as(dp), beta.ctypes.data_as(dp),
+                                          sc.ctypes.data_as(C.POINTER(C.c_int32)), infos, C.byref(st), C.byref(info))
+        return self._zbatch_finish(nb, n, p, Hall, Qall, alpha, beta, sc, infos, "R", 1, st, info, infos_out, general=True,
+                                   S=S)
+
+    def _zgpschur_batch_dev(self, dA, S, orient, wantZ, wantT, maxitfac, infos_out):
+        import torch
+
+        if dA.dim() != 4 or dA.shape[2] != dA.shape[3]:
+            raise DimensionMismatch("a device batch is one [nb, p, n, n] tensor of square factors")
+        if not dA.is_complex():
+            raise TypeError("zgpschur_batch: ComplexF64 only")
+        if not dA.is_cuda:
+            raise TypeError("device-resident zgpschur_batch needs a GPU tensor (use lists of numpy arrays for host input)")
+        nb, p, n = dA.shape[0], dA.shape[1], dA.shape[2]
+        S, Sarr = self._zgbatch_sig(S, p, orient)
+        if nb == 0:
+            if infos_out is not None:
+                infos_out[:] = []
+            return dA.clone(), (dA.clone() if wantZ else None), np.zeros((0, n), dtype=complex), Stats()
+        # [nb][p][n][n] blocks of column-major matrices: the transpose of each factor, contiguous; always a copy
+        dT = dA.to(torch.complex128).transpose(2, 3).contiguous()
+        if dT.data_ptr() == dA.data_ptr():
+            dT = dT.clone()
+        dZ = torch.zeros_like(dT) if wantZ else None
+        alpha = np.zeros((nb, n), dtype=np.complex128)
+        beta = np.zeros((nb, n))
+        sc = np.zeros((nb, n), dtype=np.int32)
+        infos = (C.c_int * nb)()
+        si = C.c_int(0)
+        st = Stats()
+        info = C.c_int(0)
+        dp = C.POINTER(C.c_double)
+        torch.cuda.synchronize(dA.device)
+        self.lib.psd_z_gpschur_batch_dev(self.ctx, nb, n, p, C.c_void_p(dT.data_ptr()), Sarr, orient.encode(), int(wantT),
+                                         int(wantZ), int(maxitfac), C.c_void_p(dZ.data_ptr()) if wantZ else None,
+                                         alpha.view(np.float64).ctypes.data_as(dp), beta.ctypes.data_as(dp),
+                                         sc.ctypes.data_as(C.POINTER(C.c_int32)), infos, C.byref(si), C.byref(st),
+                                         C.byref(info))
+        if info.value < 0 or info.value >= INFO_NOTIMPL:
+            if not any(int(infos[q]) == info.value for q in range(nb)):
+                self._raise(info.value)
+        if infos_out is not None:
+            infos_out[:] = [int(infos[q]) for q in range(nb)]
+        else:
+            for q in range(nb):
+                self._raise(infos[q])
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            values = alpha / beta * np.exp2(sc.astype(np.float64))  # (as GeneralizedPeriodicSchur)
+        return dT.transpose(2, 3), (dZ.transpose(2, 3) if wantZ else None), values, st
+
+    def gpschur_batch(self, As_list, Bs_list, **kw):
+        """gpschur(As, Bs) (src/generalized.jl:1191-1211) for many pairs of series of equal shape in ONE call: the
+        interleaving of `gpschur` per problem, then zgpschur_batch_ with the common signature (T, F, T, F, ...).
+        Returns a list of GeneralizedPeriodicSchur."""
+        if len(As_list) != len(Bs_list):
+            raise DimensionMismatch("one Bs per As")
+        cz = lambda m: np.array(m, dtype=np.complex128, order="F", copy=True)  # noqa: E731
+        problems, Ss = [], None
+        for As, Bs in zip(As_list, Bs_list):
+            ph = len(As)
+            if len(Bs) != ph:
+                raise DimensionMismatch("As and Bs must have the same length")
+            ib = 0 if ph == 1 else ph - 2
+            Cs, Sq = [cz(As[ph - 1]), cz(Bs[ib])], [True, False]
+            for j in range(ph - 1, 0, -1):  # j = ph-1 .. 1 (1-based), as gpschur
+                Cs.append(cz(As[j - 1]))
+                jx = ph if j == 1 else j - 1
+                Cs.append(cz(Bs[jx - 1]))
+                Sq += [True, False]
+            if Ss is not None and Sq != Ss:
+                raise DimensionMismatch("the problems of a batch must have equal order and period")
+            Ss = Sq
+            problems.append(Cs)
+        if not problems:
+            return []
+        return self.zgpschur_batch_(problems, Ss, "R", **kw)
 
     def _pschur_batch_dev(self, dA, orient, wantZ, wantT, maxitfac, infos_out):
         import torch

@@ -26,6 +26,7 @@
 #include "psd_zbevec.h"
 #include "psd_bord.h"
 #include "psd_zbqz.h"
+#include "psd_zgbqz.h"
 #include "psd_zbord.h"
 
 #include "../../include/psd_mi355x.h"
@@ -3948,6 +3949,7 @@ extern "C" int psd_dbg_apply_bench(psd_ctx* c, int n, int p, int nwin, int W, in
 #include "psd_gevec_host.inl"
 #include "psd_batch_host.inl"
 #include "psd_zbatch_host.inl"
+#include "psd_zgbatch_host.inl"
 #include "psd_bevec_host.inl"
 #include "psd_zbevec_host.inl"
 #include "psd_bord_host.inl"

@@ -1092,11 +1092,11 @@ PSD_KERNEL_B(PSD_STEP_NT) psd_zgq_step_train(psd_zgparams P, int p, int cstride)
 }
 
 // Bulk application of one window's rotation lists, by factor: grid = (tiles, p factors, 3 roles); tiles 64 wide
-PSD_D void psd_zgq_apply_body(const psd_zgparams& P, int n, int p, int role) {
+// (bx: the tile, l: the factor, 1-based — the block indices of psd_zgq_apply; psd_zgbqz loops over them)
+PSD_D void psd_zgq_apply_item(const psd_zgparams& P, int n, int p, int role, int bx, int l) {
     PSD_LDS_DECL;
     const psd_gapply_desc d = *P.desc;
     if (!d.active) return;
-    const int l = PSD_BLOCK_Y + 1;
     const int own = (role == 0) ? psd_zgrowner(P, l, p) : (role == 1) ? psd_zgcowner(P, l, p) : l;
     const int cnt = P.cnt[own - 1] < PSD_GTR_CAP ? P.cnt[own - 1] : PSD_GTR_CAP;
     if (cnt <= 0) return;
@@ -1106,7 +1106,7 @@ PSD_D void psd_zgq_apply_body(const psd_zgparams& P, int n, int p, int role) {
     psd_z* tile = (psd_z*)(psd_lds + sizeof(psd_ztr) * PSD_GTR_CAP);
     const bool h1x = d.h1mode == 1 && l == 1;
     if (role == 0) {
-        const int c0 = (h1x ? d.h1c0 : d.lc0) + PSD_BLOCK_X * T;
+        const int c0 = (h1x ? d.h1c0 : d.lc0) + bx * T;
         if (c0 > d.lc1) return;
         const int nc = (d.lc1 - c0 + 1 < T) ? (d.lc1 - c0 + 1) : T;
         if (h1x && c0 >= d.plo && c0 + nc - 1 <= d.phi) return;
@@ -1143,7 +1143,7 @@ PSD_D void psd_zgq_apply_body(const psd_zgparams& P, int n, int p, int role) {
         const bool h1r = h1x && role == 1;
         const int lo = (role == 1) ? (h1r ? 1 : d.rr0) : d.zr0;
         const int hi = (role == 1) ? (h1r ? n : d.rr1) : d.zr1;
-        const int r0 = lo + PSD_BLOCK_X * T;
+        const int r0 = lo + bx * T;
         if (r0 > hi) return;
         const int nr = (hi - r0 + 1 < T) ? (hi - r0 + 1) : T;
         psd_z* base = (role == 1) ? P.H : P.Z;
@@ -1176,6 +1176,10 @@ PSD_D void psd_zgq_apply_body(const psd_zgparams& P, int n, int p, int role) {
     }
 }
 
+PSD_D void psd_zgq_apply_body(const psd_zgparams& P, int n, int p, int role) {
+    psd_zgq_apply_item(P, n, p, role, PSD_BLOCK_X, PSD_BLOCK_Y + 1);
+}
+
 PSD_KERNEL_B(PSD_ZAPPLY_NT) psd_zgq_apply(psd_zgparams P, int n, int p) { psd_zgq_apply_body(P, n, p, PSD_BLOCK_Z); }
 
 // bulk updates of all cursors of a tick: pass 0 = rows and Z roles (grid.z = 2 M), pass 1 = columns role (grid.z = M)
@@ -1191,12 +1195,13 @@ PSD_KERNEL_B(PSD_ZAPPLY_NT) psd_zgq_apply_train(psd_zgparams P, int n, int p, in
 }
 
 // Deferred right side of H_1 after a zero-shift pass (generalized.jl:436-444)
-PSD_KERNEL psd_zgq_defer(psd_zgparams P, int n) {
+// (bx: the tile of PSD_NTHREADS rows — the block index of psd_zgq_defer; psd_zgbqz loops over it)
+PSD_D void psd_zgq_defer_body(const psd_zgparams& P, int n, int bx) {
     const psd_gapply_desc d = *P.desc;
     if (!d.active || d.defer_run != 1) return;
     const psd_mat<psd_z> H1 = psd_mat<psd_z>{P.H, n};
     const int NT = PSD_NTHREADS;
-    const int rbase = d.drow0 + PSD_BLOCK_X * NT;
+    const int rbase = d.drow0 + bx * NT;
     PSD_PAR_FOR(t, NT) {
         const int r = rbase + t;
         if (r <= d.djhi + 1 && d.djhi >= d.djlo) {
@@ -1214,8 +1219,10 @@ PSD_KERNEL psd_zgq_defer(psd_zgparams P, int n) {
     }
 }
 
-PSD_KERNEL psd_zgq_init(psd_zgparams P, int n, int p, int wantT, int wantZ, int W, int maxitfac, int maxlog,
-                        int hessmode, int train_want, int train_oc) {
+PSD_KERNEL psd_zgq_defer(psd_zgparams P, int n) { psd_zgq_defer_body(P, n, PSD_BLOCK_X); }
+
+PSD_D void psd_zgq_init_body(const psd_zgparams& P, int n, int p, int wantT, int wantZ, int W, int maxitfac, int maxlog,
+                             int hessmode, int train_want, int train_oc) {
     const psd_mat<psd_z> H1 = psd_mat<psd_z>{P.H, n};
     if (!hessmode) PSD_PAR_FOR(c, n) {
         for (int r = c + 3; r <= n; ++r) H1(r, c + 1) = zmk(0.0, 0.0);  // _gethess!
@@ -1250,13 +1257,18 @@ PSD_KERNEL psd_zgq_init(psd_zgparams P, int n, int p, int wantT, int wantZ, int 
     }
 }
 
+PSD_KERNEL psd_zgq_init(psd_zgparams P, int n, int p, int wantT, int wantZ, int W, int maxitfac, int maxlog,
+                        int hessmode, int train_want, int train_oc) {
+    psd_zgq_init_body(P, n, p, wantT, wantZ, W, maxitfac, maxlog, hessmode, train_want, train_oc);
+}
+
 // generalized.jl:860-908 with a signature, factor l (launched for l = p..2): diag(T_l) real >= 0; the phases go into
 // row j (S[l]) or column j (!S[l]) of T_l, column j of Z_l and column j (S[l-1]) or row j (!S[l-1]) of T_{l-1}.
 // grid = n blocks (one per j)
-PSD_KERNEL psd_zgq_phase(psd_zgparams P, int n, int l, int wantZ) {
+// (j: the diagonal position, 1-based — block index + 1 of psd_zgq_phase; psd_zgbqz loops over it)
+PSD_D void psd_zgq_phase_body(const psd_zgparams& P, int n, int l, int wantZ, int j) {
     PSD_LDS_DECL;
     psd_z* zs = (psd_z*)psd_lds;
-    const int j = PSD_BLOCK_X + 1;
     const psd_mat<psd_z> Hl = psd_zgfac(P, n, l);
     const psd_mat<psd_z> Hm = psd_zgfac(P, n, l - 1);
     const bool sl = psd_zgsig(P, l), sm = psd_zgsig(P, l - 1);
@@ -1292,11 +1304,13 @@ PSD_KERNEL psd_zgq_phase(psd_zgparams P, int n, int l, int wantZ) {
     }
 }
 
+PSD_KERNEL psd_zgq_phase(psd_zgparams P, int n, int l, int wantZ) { psd_zgq_phase_body(P, n, l, wantZ, PSD_BLOCK_X + 1); }
+
 // ---- stage 1 helpers of the complex signed Hessenberg reduction ------------------------------------------------------
+// (the bodies take the column the kernel's block index names, 1-based; psd_zgbhess1 loops over it)
 // in place B(r, c) = conj(A(n+1-c, n+1-r)).  grid = n (columns)
-PSD_KERNEL psd_zantitranspose(psd_z* A, int n) {
+PSD_D void psd_zantitranspose_body(psd_z* A, int n, int c) {
     const psd_mat<psd_z> M = psd_mat<psd_z>{A, n};
-    const int c = PSD_BLOCK_X + 1;
     PSD_PAR_FOR(t, n) {
         const int r = t + 1;
         const int r2 = n + 1 - c, c2 = n + 1 - r;
@@ -1309,9 +1323,9 @@ PSD_KERNEL psd_zantitranspose(psd_z* A, int n) {
         }
     }
 }
-PSD_KERNEL psd_zflip(psd_z* A, int n, int rows) {
+PSD_KERNEL psd_zantitranspose(psd_z* A, int n) { psd_zantitranspose_body(A, n, PSD_BLOCK_X + 1); }
+PSD_D void psd_zflip_body(psd_z* A, int n, int rows, int k) {
     const psd_mat<psd_z> M = psd_mat<psd_z>{A, n};
-    const int k = PSD_BLOCK_X + 1;
     if (rows == 0) {
         if (k > n / 2) return;
         PSD_PAR_FOR(t, n) {
@@ -1327,10 +1341,11 @@ PSD_KERNEL psd_zflip(psd_z* A, int n, int rows) {
         }
     }
 }
-PSD_KERNEL psd_ztril_zero(psd_z* A, int n) {
+PSD_KERNEL psd_zflip(psd_z* A, int n, int rows) { psd_zflip_body(A, n, rows, PSD_BLOCK_X + 1); }
+PSD_D void psd_ztril_zero_body(psd_z* A, int n, int c) {
     const psd_mat<psd_z> M = psd_mat<psd_z>{A, n};
-    const int c = PSD_BLOCK_X + 1;
     PSD_PAR_FOR(t, n) {
         if (t + 1 > c) M(t + 1, c) = zmk(0.0, 0.0);
     }
 }
+PSD_KERNEL psd_ztril_zero(psd_z* A, int n) { psd_ztril_zero_body(A, n, PSD_BLOCK_X + 1); }

@@ -175,11 +175,12 @@ PSD_KERNEL psd_zhess_apply2(psd_z* AL1, psd_z* AR1, int lc1, int nL1, int g1, ps
     }
 }
 
-PSD_KERNEL psd_zset_identity(psd_z* Q, int n) {
-    const int c = PSD_BLOCK_X + 1, j = PSD_BLOCK_Y + 1;
+// (c: the column, j: the factor, 1-based — the block indices of psd_zset_identity; psd_zgbhess1 loops over them)
+PSD_D void psd_zset_identity_body(psd_z* Q, int n, int c, int j) {
     const psd_mat<psd_z> M = psd_mat<psd_z>{Q + (size_t)(j - 1) * n * n, n};
     PSD_PAR_FOR(r, n) { M(r + 1, c) = zmk((r + 1 == c) ? 1.0 : 0.0, 0.0); }
 }
+PSD_KERNEL psd_zset_identity(psd_z* Q, int n) { psd_zset_identity_body(Q, n, PSD_BLOCK_X + 1, PSD_BLOCK_Y + 1); }
 
 // backward accumulation step of Q_j = H_{j,1} ... H_{j,n-1}: lmul!(H, Q), householder.jl:190-205
 // (bx: the tile of four columns, j: the factor, 1-based — the block indices of psd_zformq_step; psd_zbformq loops over them)

@@ -13,6 +13,12 @@
                     problems, in the same process and run, nb = 256, p = 8 over the orders of --complex-orders: the
                     measurement PSD_ZB_NMAX is set from (the largest order at which the batched call still wins).
 
+  --signed          the signed ComplexF64 family: Engine.zgpschur_batch_ against the loop of Engine.pschur_(..., S=S) over
+                    the same problems with the alternating signature (T, F, T, F, ...), nb = 256, p = 8 over the orders of
+                    --complex-orders: the measurement the order cap of the signed batch kernels is set from.  Loop and
+                    batch alternate, --reps times each after one warm-up pair; the row carries every repetition and the
+                    ratio of the fastest ones, and the largest eigenvalue difference between the two on the first problem.
+
 One JSON line per shape on stdout; --json FILE collects them."""
 import argparse
 import json
@@ -70,6 +76,35 @@ def time_batch(eng, probs, lr, cplx=False):
     return best
 
 
+def time_signed(eng, probs, S, lr, reps):
+    """Loop of single signed calls and the batched call, alternating; repetition 0 is the warm-up."""
+    import psdtest as pt
+
+    loops, batches, diff = [], [], None
+    for rep in range(reps + 1):
+        Ws = copies(probs)
+        dev = 0.0
+        t0 = time.perf_counter()
+        first = None
+        for W in Ws:
+            ps = eng.pschur_(W, lr, S=S)
+            dev += ps.stats.ms_total
+            first = first if first is not None else ps.values
+        loop = dict(wall_ms=1e3 * (time.perf_counter() - t0), ms_total=dev)
+        Ws = copies(probs)
+        t0 = time.perf_counter()
+        out = eng.zgpschur_batch_(Ws, S, lr)
+        wall = 1e3 * (time.perf_counter() - t0)
+        st = out[0].stats
+        batch = dict(wall_ms=wall, ms_hess=st.ms_hess, ms_iter=st.ms_iter, ms_copy=st.ms_copy, ms_total=st.ms_total,
+                     nsweeps=int(st.nsweeps))
+        diff = float(pt.match_eigs(first, out[0].values))
+        if rep > 0:
+            loops.append(loop)
+            batches.append(batch)
+    return loops, batches, diff
+
+
 def time_sweep(eng, nb, n, p):
     probs = factors(nb, n, p)
     for _ in range(2):
@@ -92,6 +127,8 @@ def main():
     ap.add_argument("--complex", dest="cplx", action="store_true")
     ap.add_argument("--complex-orders", default="8,16,32,64,96,128")
     ap.add_argument("--complex-nb", type=int, default=256)
+    ap.add_argument("--signed", action="store_true")
+    ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--lib", default=None, help="library to load instead of the package's (a build of another commit)")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
@@ -111,6 +148,22 @@ def main():
         for n in [int(x) for x in args.sweep_orders.split(",") if x]:
             rows.append(time_sweep(eng, 64, n, 8))
             print(json.dumps(rows[-1]), flush=True)
+    elif args.signed:
+        import numpy as np
+
+        for n in [int(x) for x in args.complex_orders.split(",") if x]:
+            nb, p = args.complex_nb, 8
+            S = [q % 2 == 0 for q in range(p)]
+            if args.lr == "L":
+                S = S[::-1]
+            probs = factors(nb, n, p, np.complex128)
+            loops, batches, diff = time_signed(eng, probs, S, args.lr, args.reps)
+            row = dict(nb=nb, n=n, p=p, lr=args.lr, dtype="complex128", S="".join("T" if x else "F" for x in S),
+                       loop=loops, batch=batches, eig_diff_problem0=diff)
+            row["wall_ratio"] = min(r["wall_ms"] for r in loops) / min(r["wall_ms"] for r in batches)
+            row["device_ratio"] = min(r["ms_total"] for r in loops) / min(r["ms_total"] for r in batches)
+            rows.append(row)
+            print(json.dumps(row), flush=True)
     elif args.cplx:
         import numpy as np
 
