@@ -285,6 +285,8 @@ struct psd_ctx {
     int hess_async = -1;  // links per panel-update launch of the two-stream form (0: off, < 0: by size)
     int hess_lookahead = 1;  // PSD_HESS_LOOKAHEAD=0: the two-launch form of psd_hess.h
     int hess_xcd = 1;        // chain strips that share a 128-byte line on one XCD (PSD_H2_XCD)
+    int hess_fit = 15;       // launches of the look-ahead reduction follow the trailing block (h2_launcher); PSD_H2_FIT=0: every launch
+                             // sized for the whole matrix; bits 1 / 2: chain grid / depth, 4 / 8: panel grid / depth (same results all)
 #endif
     // period sharding (psd_set_shard): this context holds the Schur vectors Z_j of a contiguous slice of the period
     int shard_rank = 0, shard_world = 1;
@@ -784,13 +786,17 @@ template <> struct h2_type<double> {
     static constexpr int NT = PSD_H2_NT, ROWS = PSD_H2_ROWS;
     static constexpr int CR_LARGE = 8;      // chain rows per block of the 32-column kernel (n > 1024)
     static constexpr int PIPE_NMAX = 2048;  // (every order of the look-ahead form: hessenberg_dev)
+    static constexpr bool FIT = true;       // the launches may follow the trailing block (psd_h2_fit_chain, psd_h2_fit_panel)
+    // columns per wavefront of a panel launch's bottom part, by the depth the ORDER asks for: the narrower launches of a
+    // reduction keep the column path of its first ones (the two paths are not written to give the same bits)
+    template <int NKB> static constexpr int CPW = (NKB <= 16) ? 4 : 1;
     template <int NK, int CR>
     static void link(int grid, size_t lds, hipStream_t s, const args& ha, int n, int i, int j, int nC, int nT) {
         hipLaunchKernelGGL((psd_hess2_link<NK, CR>), dim3(grid), dim3(NT), lds, s, ha, n, i, j, nC, nT);
     }
-    template <int NK>
-    static void bulk(int K, size_t lds, hipStream_t s, const args& ha, int n, int idx0, int nT) {
-        hipLaunchKernelGGL((psd_hess2_bulk<NK>), dim3(nT + (n + 3) / 4, K), dim3(NT), lds, s, ha, n, idx0, nT);
+    template <int NK, int CPW_>
+    static void bulk(int gridx, int K, size_t lds, hipStream_t s, const args& ha, int n, int idx0, int nT) {
+        hipLaunchKernelGGL((psd_hess2_bulk<NK, CPW_>), dim3(gridx, K), dim3(NT), lds, s, ha, n, idx0, nT);
     }
     static double*& ring(psd_ctx* c) { return c->h2ring; }
     static int& ring_n(psd_ctx* c) { return c->h2ring_n; }
@@ -813,13 +819,15 @@ template <> struct h2_type<psd_z> {
     static constexpr int NT = PSD_ZH2_NT, ROWS = PSD_ZH2_ROWS;
     static constexpr int CR_LARGE = 4;
     static constexpr int PIPE_NMAX = 1024;
+    static constexpr bool FIT = false;  // fixed full-size launches (the complex kernels' indexing has not been checked for narrower ones)
+    template <int NKB> static constexpr int CPW = 1;
     template <int NK, int CR>
     static void link(int grid, size_t lds, hipStream_t s, const args& ha, int n, int i, int j, int nC, int nT) {
         hipLaunchKernelGGL((psd_zhess2_link<NK, CR>), dim3(grid), dim3(NT), lds, s, ha, n, i, j, nC, nT);
     }
-    template <int NK>
-    static void bulk(int K, size_t lds, hipStream_t s, const args& ha, int n, int idx0, int nT) {
-        hipLaunchKernelGGL((psd_zhess2_bulk<NK>), dim3(nT + (n + 3) / 4, K), dim3(NT), lds, s, ha, n, idx0, nT);
+    template <int NK, int>
+    static void bulk(int gridx, int K, size_t lds, hipStream_t s, const args& ha, int n, int idx0, int nT) {
+        hipLaunchKernelGGL((psd_zhess2_bulk<NK>), dim3(gridx, K), dim3(NT), lds, s, ha, n, idx0, nT);
     }
     static double*& ring(psd_ctx* c) { return c->zh2ring; }
     static int& ring_n(psd_ctx* c) { return c->zh2ring_n; }
@@ -844,6 +852,61 @@ template <typename T, int CR> struct h2_grid {
     }
 };
 
+// One launch with the geometry of psd_hess2.h's rule: the instantiation of depth nk <= NKB (NKB: the depth the order asks
+// for, hessenberg2_dev), or the full-size launch (fit off: PSD_H2_FIT=0, or an element type without the narrower kernels).
+template <typename T, int NKB, int CR> struct h2_launcher {
+    typedef h2_type<T> Tr;
+    typedef typename Tr::args args;
+    static constexpr int CPW = Tr::template CPW<NKB>;
+    const h2_grid<T, CR> g;
+    const size_t lds;
+    const int n, p, GS;
+    const int fit;  // PSD_H2_FIT: 1 chain grid, 2 chain depth, 4 panel grid, 8 panel depth
+    const args& ha;
+    h2_launcher(psd_ctx* c, int n_, int p_, const args& ha_)
+        : g(n_, ha_.xcd), lds(h2_lds<T>(n_)), n(n_), p(p_), GS((ha_.xcd && CR < g.RPL) ? g.RPL / CR : 0), fit(Tr::FIT ? c->hess_fit : 0), ha(ha_) {}
+    // chain launch of link (i, j) — chain position (i - 1) p + (p - j); fused: with the panel update of the link before it
+    void link(hipStream_t s, int i, int j, bool fused) const {
+        psd_h2_geom q{NKB, g.nC, fused ? g.nT : 0, fused ? (n + 3) / 4 : 0};
+        if constexpr (Tr::FIT) {
+            if (fit) {
+                const psd_h2_geom f = psd_h2_fit_chain(n, p, (i - 1) * p + (p - j), CR, GS, fused);
+                if (fit & 1) q.nC = f.nC;
+                if (fit & 2) q.NK = f.NK;
+                if (fit & 4) q.nT = f.nT, q.nB = f.nB;
+                const int grid = q.nC + q.nT + q.nB;
+                switch (q.NK) {
+                    case 4: if constexpr (NKB > 4) return Tr::template link<4, CR>(grid, lds, s, ha, n, i, j, q.nC, q.nT); break;
+                    case 8: if constexpr (NKB > 8) return Tr::template link<8, CR>(grid, lds, s, ha, n, i, j, q.nC, q.nT); break;
+                    case 16: if constexpr (NKB > 16) return Tr::template link<16, CR>(grid, lds, s, ha, n, i, j, q.nC, q.nT); break;
+                    default: break;
+                }
+            }
+        }
+        Tr::template link<NKB, CR>(q.nC + q.nT + q.nB, lds, s, ha, n, i, j, q.nC, q.nT);
+    }
+    // the panel updates of links idx0 .. idx0 + K - 1 in one launch
+    void bulk(hipStream_t s, int idx0, int K) const {
+        psd_h2_geom q{NKB, 0, g.nT, (n + 3) / 4};
+        if constexpr (Tr::FIT) {
+            if (fit) {
+                psd_h2_geom f = q;
+                psd_h2_fit_panel(n, p, idx0, K, 4 * CPW, f);
+                if (fit & 4) q.nT = f.nT, q.nB = f.nB;
+                if (fit & 8) q.NK = f.NK;
+                const int gx = q.nT + q.nB > 0 ? q.nT + q.nB : 1;
+                switch (q.NK) {
+                    case 4: if constexpr (NKB > 4) return Tr::template bulk<4, CPW>(gx, K, lds, s, ha, n, idx0, q.nT); break;
+                    case 8: if constexpr (NKB > 8) return Tr::template bulk<8, CPW>(gx, K, lds, s, ha, n, idx0, q.nT); break;
+                    case 16: if constexpr (NKB > 16) return Tr::template bulk<16, CPW>(gx, K, lds, s, ha, n, idx0, q.nT); break;
+                    default: break;
+                }
+            }
+        }
+        Tr::template bulk<NKB, CPW>(q.nT + q.nB > 0 ? q.nT + q.nB : 1, K, lds, s, ha, n, idx0, q.nT);
+    }
+};
+
 // The events of the multi-stream forms: [3][8] chain-end rings, [8] panel-update ring, start, join.  All or none: when a
 // creation fails, the events made before it are destroyed and the context keeps what it had.
 constexpr size_t PSD_H2_EVENTS = 34;
@@ -865,10 +928,8 @@ int h2_events(psd_ctx* c) {
 // One-stream form: one launch per chain link, the panel updates ride one launch behind the chain
 template <typename T, int NK, int CR>
 int h2_launches(psd_ctx* c, int n, int p, const typename h2_type<T>::args& ha) {
-    const h2_grid<T, CR> g(n, ha.xcd);
-    const int grid = g.nC + g.nT + (n + 3) / 4;
-    const size_t lds = h2_lds<T>(n);
-    auto link = [&](int i, int j) { h2_type<T>::template link<NK, CR>(grid, lds, c->stream, ha, n, i, j, g.nC, g.nT); };
+    const h2_launcher<T, NK, CR> L(c, n, p, ha);
+    auto link = [&](int i, int j) { L.link(c->stream, i, j, true); };
     link(0, 1);  // the position before link (1, p): stages column 1 of A_p
     for (int i = 1; i <= n - 1; ++i)
         for (int j = p; j >= 1; --j) link(i, j);
@@ -900,8 +961,7 @@ int h2_chain(psd_ctx* c, int n, int p, const typename h2_type<T>::args& ha, int 
     } side_streams{c};
     PSD_CHECK(h2_events(c));
 
-    const h2_grid<T, CR> g(n, ha.xcd);
-    const size_t lds = h2_lds<T>(n);
+    const h2_launcher<T, NK, CR> L(c, n, p, ha);
     const int nbatch = (n - 1) * p / K + 1;  // link indices 0 .. (n - 1) p, the drain position
     // (an event is re-recorded 8 batches later; the chain awaits batch b while at most (p - K) / K < 8 later ones exist)
     hipEvent_t* evE = c->h2ev.data();       // [NS][8]: chain stream k reached the end of a batch
@@ -911,14 +971,14 @@ int h2_chain(psd_ctx* c, int n, int p, const typename h2_type<T>::args& ha, int 
     PSD_CHECK(hipEventRecord(evS, c->stream));  // (whatever ran on the main stream before: the memsets, the caller's work)
     PSD_CHECK(hipStreamWaitEvent(c->stream3, evS, 0));
     for (int k = 1; k < NS; ++k) PSD_CHECK(hipStreamWaitEvent(S[k], evS, 0));
-    Tr::template link<NK, CR>(g.nC, lds, S[0], ha, n, 0, 1, g.nC, 0);  // staging
+    L.link(S[0], 0, 1, false);  // staging
     const bool nobulk = psd_env_diag("PSD_H2_NOBULK") != nullptr;  // (timing experiment: the chain alone; results are wrong)
     auto batch = [&](int b) -> int {
         for (int k = 0; k < NS; ++k) {
             PSD_CHECK(hipEventRecord(evE[8 * k + (b & 7)], S[k]));
             PSD_CHECK(hipStreamWaitEvent(c->stream3, evE[8 * k + (b & 7)], 0));
         }
-        if (!nobulk) Tr::template bulk<NK>(K, lds, c->stream3, ha, n, b * K, g.nT);
+        if (!nobulk) L.bulk(c->stream3, b * K, K);
         PSD_CHECK(hipEventRecord(evB[b & 7], c->stream3));
         return 0;
     };
@@ -931,7 +991,7 @@ int h2_chain(psd_ctx* c, int n, int p, const typename h2_type<T>::args& ha, int 
             const int need = idx + 1 - p;
             for (int d = 0; d < NS; ++d)
                 if (need >= d && (need - d) % K == 0) PSD_CHECK(hipStreamWaitEvent(s, evB[((need - d) / K) & 7], 0));
-            Tr::template link<NK, CR>(g.nC, lds, s, ha, n, i, j, g.nC, 0);
+            L.link(s, i, j, false);
             // links nextb K .. nextb K + K - 1 have their reflectors once the chain has passed the last of them
             if (idx >= nextb * K + K - 1) PSD_CHECK(batch(nextb++));
         }
@@ -1736,6 +1796,7 @@ int psd_create(psd_ctx** ctx, int device) {
         if (hipStreamCreate(&c->stream4) != hipSuccess) c->stream4 = nullptr;
         if (const char* e = psd_env("PSD_H2_PIPE")) c->hess_pipe = atoi(e);
         if (const char* e = psd_env("PSD_H2_DEPTH")) c->hess_pipe_depth = atoi(e);
+        if (const char* e = psd_env("PSD_H2_FIT")) c->hess_fit = atoi(e);
     }
 #endif
 #ifndef PSD_HOSTSIM

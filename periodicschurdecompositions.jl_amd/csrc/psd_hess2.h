@@ -24,9 +24,10 @@
 #pragma once
 #include "psd_scalar.h"
 
+#define PSD_H2_ROWS 8  // rows of a panel strip above the left reflector
+
 #ifndef PSD_HOSTSIM
 #define PSD_H2_NT 256
-#define PSD_H2_ROWS 8
 #define PSD_H2_RING 256  // slots of the per-link ring (power of two)
 
 // The bounded wait of the pipe form (hand-over records that do not validate): bounded in TIME, not in poll rounds — a
@@ -198,6 +199,61 @@ PSD_D void psd_h2_larfg(double alpha, double xnorm, double& tau, double& beta, d
     tau = (beta - alpha) / beta;
     mult = acc * (1.0 / (alpha - beta));
     for (int q = 0; q < kount; ++q) beta *= sfmin;
+}
+
+// Launch geometry fitted to the trailing block (host side; PSD_H2_FIT=0 keeps the full-size launches).  Link q works on the
+// reflector rows r0_q .. n-1, and r0 only grows along the chain, so a launch needs neither the register depth nor the
+// workgroups of the whole matrix:
+//   NK  the smallest of 4, 8, 16, .. with 64 NK >= the widest extent the launch touches.  Every per-lane loop of the kernels
+//       runs its steps upwards under a guard against that extent, so a narrower instantiation drops exactly the steps the
+//       guard skips: the results are the same bits.  (The one unguarded loop, psd_h2_col_update, adds +0 * +0 for them:
+//       that changes a sum only from -0 to +0.)
+//   nC  block 0 + the chain strips of CR rows from the one that holds row r0_{q+1} down (with the XCD mapping: whole groups
+//       of 8 lines of GS strips, counted from the line that holds that strip — the kernel's own mapping)
+//   nT  the 8-row strips above the left reflector of the LAST link of a panel launch (R0 grows inside a batch)
+//   nB  the bottom groups of CPG columns that hold a column < n for the FIRST link of the launch
+// Invariants (tests/test_hess_fit_rule.py checks them for every launch of a few reductions): 64 NK covers every m, mR, mL
+// of the launch; every strip t with r0_{q+1} / CR <= t < ceil(n / CR) is some block's; every column i .. n-1 is in a group.
+struct psd_h2_geom {
+    int NK, nC, nT, nB;
+};
+// 0-based first reflector row of chain position idx = (i - 1) p + (p - j); in front of the chain: 0 (no reflector: the whole
+// matrix), behind it: n — the values the kernels use for rR and R0 there
+PSD_HD int psd_h2_row0(int n, int p, int idx) {
+    if (idx < 0) return 0;
+    if (idx >= (n - 1) * p) return n;
+    const int i = idx / p + 1, j = p - idx % p;
+    return ((j == 1) ? i + 1 : i) - 1;
+}
+PSD_HD int psd_h2_fit_nk(int ext) {
+    int nk = 4;  // (depth 2 for m <= 128 measured SLOWER than 4: n = 256, p = 64 reduction 81.7 -> 83.2 ms, profiles/hess_fit)
+    while (64 * nk < ext) nk *= 2;
+    return nk;
+}
+// panel part: the updates of links idx0 .. idx0 + K - 1 (left reflector: the link's, right reflector: the link before's)
+PSD_HD void psd_h2_fit_panel(int n, int p, int idx0, int K, int CPG, psd_h2_geom& g) {
+    const int Q = (n - 1) * p;
+    const int last = (idx0 + K - 1 < Q) ? idx0 + K - 1 : Q;
+    const int ci = (idx0 < 0) ? 1 : ((idx0 >= Q) ? n : idx0 / p + 1);  // first column right of the first link's
+    g.NK = psd_h2_fit_nk(n - psd_h2_row0(n, p, idx0 - 1));           // mR of the first link (>= its mL, >= every later one)
+    g.nT = (psd_h2_row0(n, p, last) + PSD_H2_ROWS - 1) / PSD_H2_ROWS;
+    g.nB = (n - ci + CPG - 1) / CPG;
+}
+// chain launch of position q (-1: staging); GS: strips per 128-byte line with the XCD mapping, else 0; fused: the launch
+// carries the panel update of link q - 1 (one-stream form, 4 columns per bottom group)
+PSD_HD psd_h2_geom psd_h2_fit_chain(int n, int p, int q, int CR, int GS, bool fused) {
+    psd_h2_geom g;
+    g.NK = psd_h2_fit_nk(n - psd_h2_row0(n, p, q));
+    g.nT = g.nB = 0;
+    if (fused) psd_h2_fit_panel(n, p, q - 1, 1, 4, g);  // (its NK is the wider: r0_{q-2} <= r0_q)
+    const int nc = (n + CR - 1) / CR, s0 = psd_h2_row0(n, p, q + 1) / CR;
+    if (GS > 1) {
+        const int nl = (nc + GS - 1) / GS - s0 / GS;
+        g.nC = 1 + (nl + 7) / 8 * 8 * GS;
+    } else {
+        g.nC = 1 + (nc > s0 ? nc - s0 : 0);
+    }
+    return g;
 }
 
 #ifndef PSD_HOSTSIM
@@ -390,7 +446,8 @@ PSD_D void psd_h2_bulk_body(const psd_hess2_args* G, int n, const psd_h2_link Lb
 // One launch = chain#q + bulk B(q-1).  The link index q is a launch argument (no dependent load in front of the data
 // loads; the launches are issued one by one: at 5-15 us each the host keeps up).  NK: ceil(n / 64) rounded up
 // (register panel depth); CR: rows per chain strip (8, or 4 for large n: twice the workgroups on the GEMV).
-// grid = nC + nT + nB blocks with nC = ceil(n / CR), nT = ceil(n / 8), nB = ceil(n / 4);
+// grid = nC + nT + nB blocks with nC = ceil(n / CR), nT = ceil(n / 8), nB = ceil(n / 4), or the counts and the narrower
+// NK that psd_h2_fit_chain gives for the link (the kernel only needs nC and nT to be the launch's own);
 // LDS: (n + 8 + 2 * PSD_H2_NT + 64) doubles.
 template <int NK, int CR>
 __global__ void __launch_bounds__(PSD_H2_NT, ((NK > 16 || NK * CR > 128) ? ((NK * CR > 256) ? 1 : 2) : 4)) psd_hess2_link(const psd_hess2_args Gv, int n, int qi, int qj, int nC, int nT) {
