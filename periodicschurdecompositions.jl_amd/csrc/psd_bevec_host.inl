@@ -1,6 +1,6 @@
 // Host driver of psd_d_eigvecs_batch / psd_d_eigvecs_batch_dev (psd_bevec.h): eigenvectors by back-substitution for nb
 // periodic Schur decompositions of one shape, as psd_d_pschur_batch leaves them.  Included at the end of psd_engine.cpp
-// behind psd_evec_host.inl (eigvecs_dev, psd_ev_root) and psd_batch_host.inl (psd_batchbuf, batch_group, batch_upload).
+// behind psd_evec_host.inl (eigvecs_dev, psd_ev_root) and psd_batch_host.inl (psd_batchbuf, batch_group, batch_staged).
 //
 // Per group of problems: the tables (row-block map, solve columns, roots, eigenvalues, the list of units) are built on
 // the host and uploaded once; then psd_bev_solve, psd_bev_backtransform for V_1, psd_bev_norm, psd_bev_backtransform for
@@ -37,12 +37,80 @@ struct bevec_call {
     char orient;
 };
 
+// The device part of a group, for both families (CPLX: the kernels of psd_zbevec.h): the tables of gc problems (itab, dtab,
+// the units behind them) go up, then the solve, the back-transformation of V_1, its norms and phases, the other factors,
+// and one read-back of the counters into cnt3 [gc][3]
+template <bool CPLX>
+int bevec_launch(const bevec_call& k, int gc, const double* dT, const double* dZ, std::vector<int>& itab,
+                 const std::vector<double>& dtab, const std::vector<int>& units, int nsm, double* dV, int32_t* cnt3,
+                 psd_bevec_stats* st) {
+    psd_ctx* c = k.c;
+    const int n = k.n, p = k.p, nmat = k.shifted ? p : 1;
+    const int nunits = (int)(units.size() / 2);
+    PSD_CHECK(psd_rt_memset(dV, 0, sizeof(double) * 2 * (size_t)gc * nmat * n * k.maxvec, c->stream));
+    if (nunits == 0) {
+        PSD_CHECK(psd_rt_sync(c->stream));
+        return 0;
+    }
+    itab.insert(itab.end(), units.begin(), units.end());
+    const size_t ncnt = 3 * (size_t)gc * n;
+    psd_batchbuf bI, bD, bX, bR, bS, bC;
+    PSD_CHECK(bI.alloc(sizeof(int) * itab.size()));
+    PSD_CHECK(bD.alloc(sizeof(double) * dtab.size()));
+    PSD_CHECK(bX.alloc(sizeof(double) * 2 * (size_t)gc * p * n * nsm));
+    if (p > 64) PSD_CHECK(bR.alloc(sizeof(double) * 4 * (size_t)nunits * p));
+    PSD_CHECK(bS.alloc(sizeof(double) * 2 * (size_t)gc * n));
+    PSD_CHECK(bC.alloc(sizeof(int) * ncnt));
+    PSD_CHECK(psd_rt_h2d(bI.ptr, itab.data(), sizeof(int) * itab.size(), c->stream));
+    PSD_CHECK(psd_rt_h2d(bD.ptr, dtab.data(), sizeof(double) * dtab.size(), c->stream));
+    PSD_CHECK(psd_rt_memset(bC.ptr, 0, sizeof(int) * ncnt, c->stream));
+    Timer tsolve, tback;
+    tsolve.start(c->stream);
+    psd_bev_args a;
+    a.T = dT; a.itab = (const int*)bI.ptr; a.dtab = bD.d(); a.X = bX.d(); a.R = bR.d(); a.cnt = (int*)bC.ptr;
+    a.n = n; a.p = p; a.nsm = nsm; a.nunits = nunits; a.gc = gc; a.six = k.six;
+    const int C = 64 / psd_bev_lw(p);
+    if (CPLX) PSD_LAUNCH(psd_zbev_solve, psd_dim3((nunits + C - 1) / C), 64, PSD_BEV_LDS, c->stream, a);
+    else PSD_LAUNCH(psd_bev_solve, psd_dim3((nunits + C - 1) / C), 64, PSD_BEV_LDS, c->stream, a);
+    st->nlaunch += 1;
+    st->ms_solve += tsolve.stop(c->stream);
+    // V_l = Z_l x_l: V_1 first, its norms and phases, then the other factors with the column factors
+    tback.start(c->stream);
+    psd_bev_bt_args g;
+    g.Z = dZ; g.X = bX.d(); g.itab = (const int*)bI.ptr; g.S = nullptr; g.cnt = (const int*)bC.ptr; g.V = dV;
+    g.n = n; g.p = p; g.nsm = nsm; g.nmat = nmat; g.maxvec = k.maxvec; g.z0 = 0; g.nz = 1;
+    const int tiles = (int)(((size_t)nsm * n + PSD_BEV_NT - 1) / PSD_BEV_NT);
+    if (CPLX) PSD_LAUNCH(psd_zbev_backtransform, psd_dim3(gc, tiles), PSD_BEV_NT, 0, c->stream, g);
+    else PSD_LAUNCH(psd_bev_backtransform, psd_dim3(gc, tiles), PSD_BEV_NT, 0, c->stream, g);
+    PSD_LAUNCH(psd_bev_norm, psd_dim3((int)(((size_t)gc * n + PSD_BEV_NT - 1) / PSD_BEV_NT)), PSD_BEV_NT, 0, c->stream, dV,
+               (const int*)bI.ptr, (const int*)bC.ptr, bS.d(), n, p, gc, nmat, k.maxvec);
+    st->nlaunch += 2;
+    if (nmat > 1) {
+        g.S = bS.d(); g.z0 = 1; g.nz = nmat - 1;
+        if (CPLX) PSD_LAUNCH(psd_zbev_backtransform, psd_dim3(gc * (nmat - 1), tiles), PSD_BEV_NT, 0, c->stream, g);
+        else PSD_LAUNCH(psd_bev_backtransform, psd_dim3(gc * (nmat - 1), tiles), PSD_BEV_NT, 0, c->stream, g);
+        st->nlaunch += 1;
+    }
+    st->ms_backtransform += tback.stop(c->stream);
+    std::vector<int> cnt(ncnt);
+    PSD_CHECK(psd_rt_d2h(cnt.data(), bC.ptr, sizeof(int) * ncnt, c->stream));
+    PSD_CHECK(psd_rt_sync(c->stream));
+    PSD_CHECK(psd_rt_last_error());
+    for (int q = 0; q < gc; ++q)
+        for (int j = 0; j < n; ++j) {
+            const int* e = cnt.data() + 3 * ((size_t)q * n + j);
+            cnt3[3 * q] += e[0];
+            cnt3[3 * q + 1] += e[1] > 0;
+            cnt3[3 * q + 2] += e[2];
+        }
+    return 0;
+}
+
 // gc problems resident on the device (dT, dZ [gc][p][n][n], dV [gc][nmat][maxvec][n] complex), their eigenvalues, completed
 // selections and row blocks; cnt3 [gc][3] receives the counters per problem
 int bevec_group(const bevec_call& k, int gc, const double* dT, const double* dZ, const double* wr, const double* wi,
                 const uint8_t* select, const int* bsz, double* dV, int32_t* cnt3, psd_bevec_stats* st) {
-    psd_ctx* c = k.c;
-    const int n = k.n, p = k.p, nmat = k.shifted ? p : 1;
+    const int n = k.n, p = k.p;
     const int IS = psd_bev_istride(n), IH = psd_bev_ihead(p), DS = psd_bev_dstride(n);
     std::vector<int> itab((size_t)IH + (size_t)gc * IS, 0), units;
     std::vector<double> dtab((size_t)gc * DS, 0.0);
@@ -84,81 +152,27 @@ int bevec_group(const bevec_call& k, int gc, const double* dT, const double* dZ,
         tab[7 * n] = ns;
         nsm = ns > nsm ? ns : nsm;
     }
-    const int nunits = (int)(units.size() / 2);
-    PSD_CHECK(psd_rt_memset(dV, 0, sizeof(double) * 2 * (size_t)gc * nmat * n * k.maxvec, c->stream));
-    if (nunits == 0) {
-        PSD_CHECK(psd_rt_sync(c->stream));
-        return 0;
-    }
-    itab.insert(itab.end(), units.begin(), units.end());
-    const size_t ncnt = 3 * (size_t)gc * n;
-    psd_batchbuf bI, bD, bX, bR, bS, bC;
-    PSD_CHECK(bI.alloc(sizeof(int) * itab.size()));
-    PSD_CHECK(bD.alloc(sizeof(double) * dtab.size()));
-    PSD_CHECK(bX.alloc(sizeof(double) * 2 * (size_t)gc * p * n * nsm));
-    if (p > 64) PSD_CHECK(bR.alloc(sizeof(double) * 4 * (size_t)nunits * p));
-    PSD_CHECK(bS.alloc(sizeof(double) * 2 * (size_t)gc * n));
-    PSD_CHECK(bC.alloc(sizeof(int) * ncnt));
-    PSD_CHECK(psd_rt_h2d(bI.ptr, itab.data(), sizeof(int) * itab.size(), c->stream));
-    PSD_CHECK(psd_rt_h2d(bD.ptr, dtab.data(), sizeof(double) * dtab.size(), c->stream));
-    PSD_CHECK(psd_rt_memset(bC.ptr, 0, sizeof(int) * ncnt, c->stream));
-    Timer tsolve, tback;
-    tsolve.start(c->stream);
-    psd_bev_args a;
-    a.T = dT; a.itab = (const int*)bI.ptr; a.dtab = bD.d(); a.X = bX.d(); a.R = bR.d(); a.cnt = (int*)bC.ptr;
-    a.n = n; a.p = p; a.nsm = nsm; a.nunits = nunits; a.gc = gc; a.six = k.six;
-    const int C = 64 / psd_bev_lw(p);
-    PSD_LAUNCH(psd_bev_solve, psd_dim3((nunits + C - 1) / C), 64, PSD_BEV_LDS, c->stream, a);
-    st->nlaunch += 1;
-    st->ms_solve += tsolve.stop(c->stream);
-    // V_l = Z_l x_l: V_1 first, its norms and phases, then the other factors with the column factors
-    tback.start(c->stream);
-    psd_bev_bt_args g;
-    g.Z = dZ; g.X = bX.d(); g.itab = (const int*)bI.ptr; g.S = nullptr; g.cnt = (const int*)bC.ptr; g.V = dV;
-    g.n = n; g.p = p; g.nsm = nsm; g.nmat = nmat; g.maxvec = k.maxvec; g.z0 = 0; g.nz = 1;
-    const int tiles = (int)(((size_t)nsm * n + PSD_BEV_NT - 1) / PSD_BEV_NT);
-    PSD_LAUNCH(psd_bev_backtransform, psd_dim3(gc, tiles), PSD_BEV_NT, 0, c->stream, g);
-    PSD_LAUNCH(psd_bev_norm, psd_dim3((int)(((size_t)gc * n + PSD_BEV_NT - 1) / PSD_BEV_NT)), PSD_BEV_NT, 0, c->stream, dV,
-               (const int*)bI.ptr, (const int*)bC.ptr, bS.d(), n, p, gc, nmat, k.maxvec);
-    st->nlaunch += 2;
-    if (nmat > 1) {
-        g.S = bS.d(); g.z0 = 1; g.nz = nmat - 1;
-        PSD_LAUNCH(psd_bev_backtransform, psd_dim3(gc * (nmat - 1), tiles), PSD_BEV_NT, 0, c->stream, g);
-        st->nlaunch += 1;
-    }
-    st->ms_backtransform += tback.stop(c->stream);
-    std::vector<int> cnt(ncnt);
-    PSD_CHECK(psd_rt_d2h(cnt.data(), bC.ptr, sizeof(int) * ncnt, c->stream));
-    PSD_CHECK(psd_rt_sync(c->stream));
-    PSD_CHECK(psd_rt_last_error());
-    for (int q = 0; q < gc; ++q)
-        for (int j = 0; j < n; ++j) {
-            const int* e = cnt.data() + 3 * ((size_t)q * n + j);
-            cnt3[3 * q] += e[0];
-            cnt3[3 * q + 1] += e[1] > 0;
-            cnt3[3 * q + 2] += e[2];
-        }
-    return 0;
+    return bevec_launch<false>(k, gc, dT, dZ, itab, dtab, units, nsm, dV, cnt3, st);
 }
 
-// above PSD_BEV_NMAX: the single path on the slices of the batch buffers (its V blocks are n x nvec: through a staging
-// block into the n x maxvec blocks of the batch)
-int bevec_single(const bevec_call& k, int gc, const double* dT, const double* dZ, const double* wr, const double* wi,
-                 uint8_t* select, const int* nvec, double* dV, int32_t* cnt3, psd_bevec_stats* st) {
+// above PSD_BEV_NMAX, for both families: the single path on the slices of the batch buffers (its V blocks are n x nvec:
+// through a staging block into the n x maxvec blocks of the batch).  lam [gc][n]: the eigenvalues; select: completed
+template <bool CPLX>
+int bevec_single(const bevec_call& k, int gc, const double* dT, const double* dZ, const std::complex<double>* lam,
+                 const uint8_t* select, const int* nvec, double* dV, int32_t* cnt3, psd_bevec_stats* st) {
     psd_ctx* c = k.c;
     const int n = k.n, p = k.p, nmat = k.shifted ? p : 1;
-    const size_t nn = (size_t)n * n, vb = 2 * (size_t)n * k.maxvec;
+    const size_t bd = (CPLX ? 2 : 1) * (size_t)n * n, vb = 2 * (size_t)n * k.maxvec;
     PSD_CHECK(psd_rt_memset(dV, 0, sizeof(double) * vb * nmat * gc, c->stream));
     psd_batchbuf stage;
     PSD_CHECK(stage.alloc(sizeof(double) * vb * nmat));
     for (int q = 0; q < gc; ++q) {
         if (nvec[q] == 0) continue;
-        std::vector<std::complex<double>> lam(n);
-        for (int i = 0; i < n; ++i) lam[i] = std::complex<double>(wr[(size_t)q * n + i], wi[(size_t)q * n + i]);
+        std::vector<uint8_t> sel(select + (size_t)q * n, select + (size_t)(q + 1) * n);
         psd_evec_stats es;
         memset(&es, 0, sizeof(es));
-        const int rc = eigvecs_dev<false>(c, n, p, dT + (size_t)q * p * nn, dZ + (size_t)q * p * nn, lam.data(), k.orient,
-                                          k.schurindex, select + (size_t)q * n, k.shifted, stage.d(), nvec[q], &es);
+        const int rc = eigvecs_dev<CPLX>(c, n, p, dT + (size_t)q * p * bd, dZ + (size_t)q * p * bd, lam + (size_t)q * n,
+                                         k.orient, k.schurindex, sel.data(), k.shifted, stage.d(), nvec[q], &es);
         if (rc != 0) return rc;
         for (int l = 0; l < nmat; ++l)
             PSD_CHECK(psd_rt_d2d(dV + ((size_t)q * nmat + l) * vb, stage.d() + 2 * (size_t)l * n * nvec[q],
@@ -175,10 +189,12 @@ int bevec_single(const bevec_call& k, int gc, const double* dT, const double* dZ
 }
 
 int bevec_run(const bevec_call& k, int gc, const double* dT, const double* dZ, const double* wr, const double* wi,
-              uint8_t* select, const int* bsz, const int* nvec, double* dV, int32_t* cnt3, psd_bevec_stats* st) {
+              const uint8_t* select, const int* bsz, const int* nvec, double* dV, int32_t* cnt3, psd_bevec_stats* st) {
     st->ngroups += 1;
-    if (k.n > k.c->bev_nmax) return bevec_single(k, gc, dT, dZ, wr, wi, select, nvec, dV, cnt3, st);
-    return bevec_group(k, gc, dT, dZ, wr, wi, select, bsz, dV, cnt3, st);
+    if (k.n <= k.c->bev_nmax) return bevec_group(k, gc, dT, dZ, wr, wi, select, bsz, dV, cnt3, st);
+    std::vector<std::complex<double>> lam((size_t)gc * k.n);
+    for (size_t e = 0; e < lam.size(); ++e) lam[e] = std::complex<double>(wr[e], wi[e]);
+    return bevec_single<false>(k, gc, dT, dZ, lam.data(), select, nvec, dV, cnt3, st);
 }
 
 int bevec_checked(psd_ctx* c, int nb, int n, int p, const void* T, const void* Z, const double* wr, const double* wi,
@@ -219,11 +235,8 @@ extern "C" {
 int psd_d_eigvecs_batch_dev(psd_ctx* c, int nb, int n, int p, const double* dT, const double* dZ, const double* wr,
                             const double* wi, char orient, int schurindex, uint8_t* select, int shifted, double* dV,
                             int maxvec, int* nvec, int32_t* pcnt, psd_bevec_stats* stats, int* info) {
-    int dummy;
-    if (!info) info = &dummy;
-    psd_bevec_stats local;
-    psd_bevec_stats* st = stats ? stats : &local;
-    memset(st, 0, sizeof(*st));
+    batch_call<psd_bevec_stats> entry(info, stats);
+    psd_bevec_stats* st = entry.s;
     if ((*info = bevec_checked(c, nb, n, p, dT, dZ, wr, wi, orient, schurindex, select, nvec, st)) != 0 || nb == 0)
         return *info;
     const size_t nn = (size_t)n * n, tot = (size_t)nb * n;
@@ -270,11 +283,8 @@ int psd_d_eigvecs_batch_dev(psd_ctx* c, int nb, int n, int p, const double* dT, 
 int psd_d_eigvecs_batch(psd_ctx* c, int nb, int n, int p, double* const* T, double* const* Z, const double* wr,
                         const double* wi, char orient, int schurindex, uint8_t* select, int shifted, double* const* V,
                         int maxvec, int* nvec, int32_t* pcnt, psd_bevec_stats* stats, int* info) {
-    int dummy;
-    if (!info) info = &dummy;
-    psd_bevec_stats local;
-    psd_bevec_stats* st = stats ? stats : &local;
-    memset(st, 0, sizeof(*st));
+    batch_call<psd_bevec_stats> entry(info, stats);
+    psd_bevec_stats* st = entry.s;
     if ((*info = bevec_checked(c, nb, n, p, T, Z, wr, wi, orient, schurindex, select, nvec, st)) != 0 || nb == 0)
         return *info;
     const size_t nn = (size_t)n * n, tot = (size_t)nb * n;
@@ -301,22 +311,14 @@ int psd_d_eigvecs_batch(psd_ctx* c, int nb, int n, int p, double* const* T, doub
         return *info = 0;
     }
     const bevec_call k{c, n, p, left ? schurindex - 1 : p - schurindex, schurindex, shifted, maxvec, left, orient};
-    int g = batch_group(c, nb, sizeof(double) * (2 * nn * p + vb * nmat + 2 * (size_t)p * n * mv));
-    psd_batchbuf dbuf[2], dV;
-    psd_hostbuf hst, hv;
-    if ((*info = batch_buffers(g, nn * p, 2, dbuf, hst)) != 0) return *info;
-    PSD_CHECK(dV.alloc(sizeof(double) * vb * nmat * g));
-    if (!hv.alloc(sizeof(double) * vb * nmat * g)) return *info = PSD_INFO_RUNTIME + 3;
-    for (int q0 = 0; q0 < nb; q0 += g) {
-        const int gc = nb - q0 < g ? nb - q0 : g;
-        if ((*info = batch_upload(c, T, q0, gc, p, nn, hst.d(), dbuf[0].d())) != 0) return *info;
-        if ((*info = batch_upload(c, Z, q0, gc, p, nn, hst.d(), dbuf[1].d())) != 0) return *info;
-        *info = bevec_run(k, gc, dbuf[0].d(), dbuf[1].d(), wr + (size_t)q0 * n, wi + (size_t)q0 * n,
-                          select + (size_t)q0 * n, bsz.data() + (size_t)q0 * n, nvec + q0, dV.d(),
-                          cnt3.data() + 3 * (size_t)q0, st);
-        if (*info != 0) return *info;
-        if ((*info = batch_download(c, V, q0, gc, nmat, vb, hv.d(), dV.d())) != 0) return *info;
-    }
+    const batch_list L[] = {{T, p, nn, BATCH_IN}, {Z, p, nn, BATCH_IN}, {V, nmat, vb, BATCH_OUT}};
+    auto body = [&](int q0, int gc, double* const* d) {
+        return bevec_run(k, gc, d[0], d[1], wr + (size_t)q0 * n, wi + (size_t)q0 * n, select + (size_t)q0 * n,
+                         bsz.data() + (size_t)q0 * n, nvec + q0, d[2], cnt3.data() + 3 * (size_t)q0, st);
+    };
+    const size_t per = sizeof(double) * (2 * nn * p + vb * nmat + 2 * (size_t)p * n * mv);
+    *info = batch_staged(c, nb, per, L, nullptr, batch_no_extra, body);
+    if (*info != 0) return *info;
     bevec_finish(nb, nvec, cnt3.data(), pcnt, st);
     return *info = 0;
 }

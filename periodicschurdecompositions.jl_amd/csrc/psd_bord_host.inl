@@ -1,6 +1,6 @@
 // Host drivers of psd_d_ordschur_batch / psd_d_ordschur_batch_dev (psd_bord.h): ordschur!(P, select) for nb periodic Schur
 // forms of one shape, as psd_d_pschur_batch leaves them.  Included at the end of psd_engine.cpp behind psd_batch_host.inl
-// (psd_batchbuf, batch_group, batch_buffers).
+// (psd_batchbuf, batch_group, batch_alloc_halving, batch_staged).
 //
 // Per group of problems: the selections go up once, then psd_bord — every problem's whole reordering in one launch —,
 // psd_bord_values and psd_bord_cleanup, and one read-back of the per-problem states, codes and eigenvalues.  Orders above
@@ -168,17 +168,9 @@ int bord_permute_dev(psd_ctx* c, int nb, int p, size_t nn, double* X, const std:
     }
     const size_t per = sizeof(double) * nn * p;
     if (gt == 0) {
-        gt = batch_group(c, nb, per);
-        for (;;) {
-            const int rc = tmp.alloc(per * gt);
-            if (rc == 0) break;
-            (void)psd_rt_last_error();
-            if (gt == 1) {
-                gt = 0;
-                return rc;
-            }
-            gt = (gt + 1) / 2;
-        }
+        int g = batch_group(c, nb, per);
+        if (int e = batch_alloc_halving(g, [&](int gg) { return tmp.alloc(per * gg); })) return e;
+        gt = g;
     }
     PSD_CHECK(dslot.alloc(sizeof(int) * (size_t)p));
     PSD_CHECK(psd_rt_h2d(dslot.ptr, slot.data(), sizeof(int) * (size_t)p, c->stream));
@@ -193,10 +185,30 @@ int bord_permute_dev(psd_ctx* c, int nb, int p, size_t nn, double* X, const std:
     return 0;
 }
 
-int bord_first_code(int nb, const int* infos) {
-    for (int q = 0; q < nb; ++q)
-        if (infos[q] != 0) return infos[q];
-    return 0;
+// The device-resident entries of both families: nb problems in H / Z (null: none) [nb][p] blocks of bd doubles in the user
+// order.  The factors stay where they are: to the internal order, groups of what the workspace allows through
+// group(q0, gc) — ws.alloc(g, n, p) in the halving loop unless the call takes the fallback —, and back to the user order.
+template <class Ws, class Group>
+int bord_dev_run(psd_ctx* c, int nb, int n, int p, size_t bd, double* H, double* Z, const std::vector<int>& slotA,
+                 const std::vector<int>& slotZ, bool fallback, size_t ws_bytes, Ws& ws, const int* pinfos, Group group) {
+    int g = batch_group(c, nb, ws_bytes);
+    if (!fallback)
+        if (int e = batch_alloc_halving(g, [&](int gg) { return ws.alloc(gg, n, p); })) return e;
+    psd_batchbuf tmp, dslot;
+    int gt = 0;
+    const int firstZ = (slotZ[0] == 0) ? 1 : 0;
+    if (int e = bord_permute_dev(c, nb, p, bd, H, slotA, 0, true, tmp, gt, dslot)) return e;
+    if (Z)
+        if (int e = bord_permute_dev(c, nb, p, bd, Z, slotZ, firstZ, true, tmp, gt, dslot)) return e;
+    int fatal = 0;
+    for (int q0 = 0; q0 < nb && fatal == 0; q0 += g) fatal = group(q0, (nb - q0 < g) ? (nb - q0) : g);
+    // back to the user order, also behind a runtime failure: the caller's blocks keep their places
+    int rc = bord_permute_dev(c, nb, p, bd, H, slotA, 0, false, tmp, gt, dslot);
+    if (rc == 0 && Z) rc = bord_permute_dev(c, nb, p, bd, Z, slotZ, firstZ, false, tmp, gt, dslot);
+    if (rc == 0) rc = psd_rt_sync(c->stream) != 0 ? PSD_INFO_RUNTIME + 1 : 0;
+    if (fatal != 0) return fatal;
+    if (rc != 0) return rc;
+    return batch_first_code(pinfos, nb);
 }
 
 }  // namespace
@@ -206,93 +218,43 @@ extern "C" {
 int psd_d_ordschur_batch_dev(psd_ctx* c, int nb, int n, int p, void* dT, void* dZ, char orient, int schurindex,
                              const uint8_t* select, int wantZ, double* wr, double* wi, int* infos, int* nswaps,
                              psd_stats* stats, int* info) {
-    int dummy;
-    if (!info) info = &dummy;
-    if (stats) memset(stats, 0, sizeof(*stats));
+    batch_call<psd_stats> k(info, stats);
     std::vector<int> slotA, slotZ;
     if ((*info = bord_checked(c, nb, n, p, dT, dZ, orient, schurindex, select, wantZ, wr, wi, slotA, slotZ)) != 0 || nb == 0)
         return *info;
     const size_t nn = (size_t)n * n;
-    psd_stats local;
-    memset(&local, 0, sizeof(local));
-    psd_stats* s = stats ? stats : &local;
-    std::vector<int> linfo(infos ? 0 : nb, 0);
-    int* pinfos = infos ? infos : linfo.data();
+    int* pinfos = k.infos(infos, nb);
     double* H = (double*)dT;
     double* Z = wantZ ? (double*)dZ : nullptr;
-    // the workspace of a group; the factors stay where they are
-    int g = batch_group(c, nb, bord_ws_bytes(n, p));
     bord_ws ws;
-    if (!bord_fallback(c, n, p)) {
-        for (;;) {
-            const int rc = ws.alloc(g, n, p);
-            if (rc == 0) break;
-            (void)psd_rt_last_error();
-            if (g == 1) return *info = rc;
-            g = (g + 1) / 2;
-        }
-    }
-    psd_batchbuf tmp, dslot;
-    int gt = 0;
-    const int firstZ = (slotZ[0] == 0) ? 1 : 0;
-    if ((*info = bord_permute_dev(c, nb, p, nn, H, slotA, 0, true, tmp, gt, dslot)) != 0) return *info;
-    if (Z && (*info = bord_permute_dev(c, nb, p, nn, Z, slotZ, firstZ, true, tmp, gt, dslot)) != 0) return *info;
-    int fatal = 0;
-    for (int q0 = 0; q0 < nb && fatal == 0; q0 += g) {
-        const int gc = (nb - q0 < g) ? (nb - q0) : g;
-        fatal = bord_group(c, gc, n, p, H + (size_t)q0 * p * nn, Z ? Z + (size_t)q0 * p * nn : nullptr,
-                           select + (size_t)q0 * n, wantZ, wr + (size_t)q0 * n, wi + (size_t)q0 * n, pinfos + q0,
-                           nswaps ? nswaps + q0 : nullptr, s, ws);
-    }
-    // back to the user order, also behind a runtime failure: the caller's blocks keep their places
-    int rc = bord_permute_dev(c, nb, p, nn, H, slotA, 0, false, tmp, gt, dslot);
-    if (rc == 0 && Z) rc = bord_permute_dev(c, nb, p, nn, Z, slotZ, firstZ, false, tmp, gt, dslot);
-    if (rc == 0) rc = psd_rt_sync(c->stream) != 0 ? PSD_INFO_RUNTIME + 1 : 0;
-    if (fatal != 0) return *info = fatal;
-    if (rc != 0) return *info = rc;
-    return *info = bord_first_code(nb, pinfos);
+    auto group = [&](int q0, int gc) {
+        return bord_group(c, gc, n, p, H + (size_t)q0 * p * nn, Z ? Z + (size_t)q0 * p * nn : nullptr, select + (size_t)q0 * n,
+                          wantZ, wr + (size_t)q0 * n, wi + (size_t)q0 * n, pinfos + q0, nswaps ? nswaps + q0 : nullptr, k.s, ws);
+    };
+    return *info = bord_dev_run(c, nb, n, p, nn, H, Z, slotA, slotZ, bord_fallback(c, n, p), bord_ws_bytes(n, p), ws, pinfos, group);
 }
 
 int psd_d_ordschur_batch(psd_ctx* c, int nb, int n, int p, double* const* T, double* const* Z, char orient, int schurindex,
                          const uint8_t* select, int wantZ, double* wr, double* wi, int* infos, int* nswaps, psd_stats* stats,
                          int* info) {
-    int dummy;
-    if (!info) info = &dummy;
-    if (stats) memset(stats, 0, sizeof(*stats));
+    batch_call<psd_stats> k(info, stats);
     std::vector<int> slotA, slotZ;
     if ((*info = bord_checked(c, nb, n, p, T, Z, orient, schurindex, select, wantZ, wr, wi, slotA, slotZ)) != 0 || nb == 0)
         return *info;
     const size_t nn = (size_t)n * n;
-    const int nz = wantZ ? 2 : 1;
-    int g = batch_group(c, nb, sizeof(double) * nz * nn * p + bord_ws_bytes(n, p));
-    psd_batchbuf dbuf[2];
-    psd_hostbuf hst;
-    if ((*info = batch_buffers(g, nn * p, nz, dbuf, hst)) != 0) return *info;
+    // user slot <-> internal slot on the way through the staging buffer, as psd_d_ordschur copies
+    const batch_list L[] = {{T, p, nn, BATCH_IN | BATCH_OUT, slotA.data()},
+                            {wantZ ? Z : nullptr, p, nn, BATCH_IN | BATCH_OUT, slotZ.data()}};
+    int* pinfos = k.infos(infos, nb);
     bord_ws ws;
-    if (!bord_fallback(c, n, p) && (*info = ws.alloc(g, n, p)) != 0) return *info;
-    psd_stats local;
-    memset(&local, 0, sizeof(local));
-    psd_stats* s = stats ? stats : &local;
-    std::vector<int> linfo(infos ? 0 : nb, 0);
-    int* pinfos = infos ? infos : linfo.data();
-    Timer tc;
-    for (int q0 = 0; q0 < nb; q0 += g) {
-        const int gc = (nb - q0 < g) ? (nb - q0) : g;
-        tc.start(c->stream);
-        // user slot <-> internal slot on the way through the staging buffer, as psd_d_ordschur copies
-        if ((*info = batch_upload(c, T, q0, gc, p, nn, hst.d(), dbuf[0].d(), slotA.data())) != 0) return *info;
-        if (wantZ && (*info = batch_upload(c, Z, q0, gc, p, nn, hst.d(), dbuf[1].d(), slotZ.data())) != 0) return *info;
-        double ms_copy = tc.stop(c->stream);
-        *info = bord_group(c, gc, n, p, dbuf[0].d(), wantZ ? dbuf[1].d() : nullptr, select + (size_t)q0 * n, wantZ,
-                           wr + (size_t)q0 * n, wi + (size_t)q0 * n, pinfos + q0, nswaps ? nswaps + q0 : nullptr, s, ws);
-        if (*info != 0) return *info;
-        tc.start(c->stream);
-        if ((*info = batch_download(c, T, q0, gc, p, nn, hst.d(), dbuf[0].d(), slotA.data())) != 0) return *info;
-        if (wantZ && (*info = batch_download(c, Z, q0, gc, p, nn, hst.d(), dbuf[1].d(), slotZ.data())) != 0) return *info;
-        ms_copy += tc.stop(c->stream);
-        s->ms_copy += ms_copy;
-    }
-    return *info = bord_first_code(nb, pinfos);
+    auto extra = [&](int g) { return bord_fallback(c, n, p) ? 0 : ws.alloc(g, n, p); };
+    auto body = [&](int q0, int gc, double* const* d) {
+        return bord_group(c, gc, n, p, d[0], d[1], select + (size_t)q0 * n, wantZ, wr + (size_t)q0 * n, wi + (size_t)q0 * n,
+                          pinfos + q0, nswaps ? nswaps + q0 : nullptr, k.s, ws);
+    };
+    *info = batch_staged(c, nb, sizeof(double) * (wantZ ? 2 : 1) * nn * p + bord_ws_bytes(n, p), L, k.s, extra, body);
+    if (*info != 0) return *info;
+    return *info = batch_first_code(pinfos, nb);
 }
 
 }  // extern "C"

@@ -14,12 +14,6 @@
 
 namespace {
 
-int zbatch_info_code(int pinfo) {
-    if (pinfo == PSD_LIST_OVERFLOW) return PSD_INFO_RUNTIME + 77;
-    if (pinfo == PSD_ZB_TICKCAP) return PSD_INFO_RUNTIME + 0xfffe;
-    return (pinfo != 0) ? (PSD_INFO_NOCONV + pinfo) : 0;
-}
-
 // generalized.jl:988-1082 with S all true (= PSD.jl:213-259) for nb problems: dH [nb][p][n][n], dtau [nb][p][n]
 int zbhessenberg_dev(psd_ctx* c, int nb, int n, int p, psd_z* dH, psd_z* dtau) {
     const size_t nn = (size_t)n * n;
@@ -54,7 +48,52 @@ int zbformq_dev(psd_ctx* c, int nb, int n, int p, psd_z* dH, const psd_z* dtau, 
     return 0;
 }
 
-void zbatch_add_state(psd_stats* s, const psd_zstate& st) {
+
+// Per-problem workspace of psd_zbqz / psd_zgbqz (Args: their argument struct) for nb problems, carved from one zeroed
+// allocation, every region 16-byte aligned; `extra` bytes follow the per-problem arrays (the signed kernel's signature).
+// alloc fills the workspace pointers and n, p, maxlog of A.
+template <class Args>
+struct zb_work {
+    psd_batchbuf buf;
+    Args A;
+    char* extra = nullptr;
+    int alloc(psd_ctx* c, int nb, int n, int p, int trcap, int maxlog, size_t extra_bytes = 0) {
+        using State = typename std::remove_pointer<decltype(A.st)>::type;
+        using Desc = typename std::remove_pointer<decltype(A.desc)>::type;
+        size_t off = 0;
+        auto carve = [&off](size_t bytes) {
+            const size_t o = off;
+            off += (bytes + 15) & ~(size_t)15;
+            return o;
+        };
+        const size_t o_st = carve(sizeof(State) * nb), o_desc = carve(sizeof(Desc) * nb);
+        const size_t o_tr = carve(sizeof(psd_ztr) * (size_t)nb * p * trcap), o_cnt = carve(sizeof(int) * (size_t)nb * p);
+        const size_t o_dG = carve(sizeof(psd_ztr) * (size_t)nb * (n + 2)), o_alpha = carve(sizeof(psd_z) * (size_t)nb * n);
+        const size_t o_beta = carve(sizeof(double) * (size_t)nb * n), o_asc = carve(sizeof(int) * (size_t)nb * n);
+        const size_t o_log = carve(sizeof(int) * (size_t)nb * 3 * maxlog), o_info = carve(sizeof(int) * nb);
+        const size_t o_extra = carve(extra_bytes);
+        PSD_CHECK(buf.alloc(off));
+        PSD_CHECK(psd_rt_memset(buf.ptr, 0, off, c->stream));
+        char* w = (char*)buf.ptr;
+        A.st = (State*)(w + o_st);
+        A.desc = (Desc*)(w + o_desc);
+        A.tr = (psd_ztr*)(w + o_tr);
+        A.cnt = (int*)(w + o_cnt);
+        A.dG = (psd_ztr*)(w + o_dG);
+        A.alpha = (psd_z*)(w + o_alpha);
+        A.beta = (double*)(w + o_beta);
+        A.ascale = (int*)(w + o_asc);
+        A.log = (int*)(w + o_log);
+        A.infos = (int*)(w + o_info);
+        extra = w + o_extra;
+        A.n = n; A.p = p; A.maxlog = maxlog;
+        return 0;
+    }
+};
+
+// what the kernel left in one problem's state (psd_zstate, psd_zgstate), added to the call's
+template <class State>
+void zbatch_add_state(psd_stats* s, const State& st) {
     s->niter += st.jiter;
     s->nsweeps += st.nsweeps;
     s->nrqpass += st.nzshift;
@@ -85,48 +124,17 @@ int zbiterate_dev(psd_ctx* c, int nb, int n, int p, psd_z* dH, psd_z* dZ, int wa
                                 nullptr, 0, &qinfo);
             if (batch_fatal(rc) && rc != PSD_INFO_RUNTIME + 77) return rc;
             infos[q] = rc;
-            s->niter += ps.niter;
-            s->nsweeps += ps.nsweeps;
-            s->nrqpass += ps.nrqpass;
-            s->ndefl1 += ps.ndefl1;
-            s->ndefl2 += ps.ndefl2;
-            s->nwindows += ps.nwindows;
-            s->nlog += ps.nlog;
-            s->nlaunch_step += ps.nlaunch_step;
+            batch_add_counts(s, ps);
         }
         s->window = W;
         return 0;
     }
-    // per-problem arrays of psd_zbqz_args, carved from one allocation (every region 16-byte aligned)
-    size_t off = 0;
-    auto carve = [&off](size_t bytes) {
-        const size_t o = off;
-        off += (bytes + 15) & ~(size_t)15;
-        return o;
-    };
-    const size_t o_st = carve(sizeof(psd_zstate) * nb), o_desc = carve(sizeof(psd_zapply_desc) * nb);
-    const size_t o_tr = carve(sizeof(psd_ztr) * (size_t)nb * p * PSD_ZTR_CAP), o_cnt = carve(sizeof(int) * (size_t)nb * p);
-    const size_t o_dG = carve(sizeof(psd_ztr) * (size_t)nb * (n + 2)), o_alpha = carve(sizeof(psd_z) * (size_t)nb * n);
-    const size_t o_beta = carve(sizeof(double) * (size_t)nb * n), o_asc = carve(sizeof(int) * (size_t)nb * n);
-    const size_t o_log = carve(sizeof(int) * (size_t)nb * 3 * maxlog), o_info = carve(sizeof(int) * nb);
-    psd_batchbuf ws;
-    PSD_CHECK(ws.alloc(off));
-    PSD_CHECK(psd_rt_memset(ws.ptr, 0, off, c->stream));
-    char* w = (char*)ws.ptr;
-    psd_zbqz_args A;
+    zb_work<psd_zbqz_args> ws;
+    if (int e = ws.alloc(c, nb, n, p, PSD_ZTR_CAP, maxlog)) return e;
+    psd_zbqz_args& A = ws.A;
     A.H = dH;
     A.Z = wantZ ? dZ : nullptr;
-    A.st = (psd_zstate*)(w + o_st);
-    A.desc = (psd_zapply_desc*)(w + o_desc);
-    A.tr = (psd_ztr*)(w + o_tr);
-    A.cnt = (int*)(w + o_cnt);
-    A.dG = (psd_ztr*)(w + o_dG);
-    A.alpha = (psd_z*)(w + o_alpha);
-    A.beta = (double*)(w + o_beta);
-    A.ascale = (int*)(w + o_asc);
-    A.log = (int*)(w + o_log);
-    A.infos = (int*)(w + o_info);
-    A.n = n; A.p = p; A.wantT = wantT; A.wantZ = wantZ; A.W = W; A.maxitfac = maxitfac; A.maxlog = maxlog;
+    A.wantT = wantT; A.wantZ = wantZ; A.W = W; A.maxitfac = maxitfac;
     const int nbmin = (W - 3 > 0) ? ((W - 3 < 8) ? (W - 3) : 8) : 1;  // (the bound of ziterate_dev's tick loop)
     A.cap = (long long)maxitfac * n * ((long long)n / nbmin + 4) + 4LL * n + 1024;
     size_t lds = step_lds_bytes(p, W, 16);
@@ -144,7 +152,7 @@ int zbiterate_dev(psd_ctx* c, int nb, int n, int p, psd_z* dH, psd_z* dZ, int wa
     PSD_CHECK(psd_rt_last_error());
     for (size_t e = 0; e < (size_t)nb * n; ++e) ascale[e] = hsc[e];
     for (int q = 0; q < nb; ++q) {
-        infos[q] = zbatch_info_code(hinfo[q]);
+        infos[q] = batch_info_code(hinfo[q]);
         zbatch_add_state(s, hst[q]);
     }
     s->nlaunch_step += 1;
@@ -158,42 +166,29 @@ int zpschur_batch_core(psd_ctx* c, int nb, int n, int p, psd_z* dA, bool left, i
                        double* alpha, double* beta, int32_t* ascale, int* infos, psd_stats* s) {
     memset(s, 0, sizeof(*s));
     if (c->shard_world > 1) return PSD_INFO_NOTIMPL;  // (a period-sharded context keeps a slice of Z: single problems only)
-    const size_t nn = (size_t)n * n;
     int rc = 0;
     if (n > c->zb_nmax && (rc = c->zreserve(n, p, false, 2 * maxitfac * n + n + 16)) != 0) return rc;
     psd_batchbuf dtau;
     PSD_CHECK(dtau.alloc(sizeof(psd_z) * (size_t)nb * p * n));
     Timer tall, tph;
     tall.start(c->stream);
-    // PSD.jl:127-131: 'L' works on the reversed sequence
-    if (left && p > 1)
-        PSD_LAUNCH(psd_breverse_blocks, psd_dim3(nb * (p / 2)), PSD_HESS_NT, 0, c->stream, (double*)dA, 2 * nn, p, 0, p);
-    tph.start(c->stream);
-    if ((rc = zbhessenberg_dev(c, nb, n, p, dA, (psd_z*)dtau.ptr)) != 0) return rc;
-    s->ms_hess = tph.stop(c->stream);
-    tph.start(c->stream);
-    if ((rc = zbformq_dev(c, nb, n, p, dA, (const psd_z*)dtau.ptr, wantZ ? dZ : nullptr)) != 0) return rc;
-    s->ms_formq = tph.stop(c->stream);
-    tph.start(c->stream);
-    if ((rc = zbiterate_dev(c, nb, n, p, dA, dZ, wantT, wantZ, maxitfac, alpha, beta, ascale, infos, s)) != 0) return rc;
-    s->ms_iter = tph.stop(c->stream);
-    // PSD.jl:1078-1092: undo the reversal; Z_1 stays, Z_2..Z_p reverse
-    if (left && p > 1) {
-        PSD_LAUNCH(psd_breverse_blocks, psd_dim3(nb * (p / 2)), PSD_HESS_NT, 0, c->stream, (double*)dA, 2 * nn, p, 0, p);
-        if (wantZ && p > 2)
-            PSD_LAUNCH(psd_breverse_blocks, psd_dim3(nb * ((p - 1) / 2)), PSD_HESS_NT, 0, c->stream, (double*)dZ, 2 * nn, p, 1,
-                       p - 1);
-    }
+    rc = batch_reversed(c, left, nb, p, 2 * (size_t)n * n, (double*)dA, wantZ ? (double*)dZ : nullptr, [&]() {
+        tph.start(c->stream);
+        if (int e = zbhessenberg_dev(c, nb, n, p, dA, (psd_z*)dtau.ptr)) return e;
+        s->ms_hess = tph.stop(c->stream);
+        tph.start(c->stream);
+        if (int e = zbformq_dev(c, nb, n, p, dA, (const psd_z*)dtau.ptr, wantZ ? dZ : nullptr)) return e;
+        s->ms_formq = tph.stop(c->stream);
+        tph.start(c->stream);
+        if (int e = zbiterate_dev(c, nb, n, p, dA, dZ, wantT, wantZ, maxitfac, alpha, beta, ascale, infos, s)) return e;
+        s->ms_iter = tph.stop(c->stream);
+        return 0;
+    });
+    if (rc != 0) return rc;
     s->ms_total = tall.stop(c->stream);
     s->bytes_hess = nb * 2.0 * 16.0 * p * (5.0 / 6.0) * (double)n * n * n;
     s->bytes_formq = wantZ ? nb * 2.0 * 16.0 * p * (double)n * n * n / 3.0 : 0.0;
     PSD_CHECK(psd_rt_last_error());
-    return 0;
-}
-
-int zbatch_worst(const int* infos, int nb) {
-    for (int q = 0; q < nb; ++q)
-        if (infos[q] != 0) return infos[q];
     return 0;
 }
 
@@ -202,159 +197,107 @@ int zbatch_worst(const int* infos, int nb) {
 extern "C" {
 
 int psd_z_phessenberg_batch(psd_ctx* c, int nb, int n, int p, double* const* A, double* tau, psd_stats* stats, int* info) {
-    int dummy;
-    if (!info) info = &dummy;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (!c) return *info = -1;
-    if (nb < 1) return *info = -2;
-    if ((*info = check_dims(n, p)) != 0) return *info = *info - 1;
+    batch_call<psd_stats> k(info, stats);
+    if ((*info = k.head(c, nb, n, p)) != 0) return *info;
     if (!A) return *info = -5;
     if (!tau) return *info = -6;
     if ((*info = c->zreserve(n, p, false, 16)) != 0) return *info;
     const size_t nn2 = 2 * (size_t)n * n;  // doubles of one factor
-    int g = batch_group(c, nb, sizeof(double) * (nn2 + 2 * (size_t)n) * p);
-    psd_batchbuf dH, dtau;
-    psd_hostbuf hst;
-    if ((*info = batch_buffers(g, nn2 * p, 1, &dH, hst)) != 0) return *info;
-    PSD_CHECK(dtau.alloc(sizeof(psd_z) * (size_t)g * p * n));
-    psd_stats local;
-    memset(&local, 0, sizeof(local));
-    psd_stats* s = stats ? stats : &local;
-    Timer tc, tk;
-    for (int q0 = 0; q0 < nb; q0 += g) {
-        const int gc = (nb - q0 < g) ? (nb - q0) : g;
-        tc.start(c->stream);
-        if ((*info = batch_upload(c, A, q0, gc, p, nn2, hst.d(), dH.d())) != 0) return *info;
-        s->ms_copy += tc.stop(c->stream);
+    const batch_list L[] = {{A, p, nn2, BATCH_IN | BATCH_OUT}};
+    psd_batchbuf dtau;
+    Timer tk;
+    auto extra = [&](int g) { return psd_rt_code(dtau.alloc(sizeof(psd_z) * (size_t)g * p * n)); };
+    auto body = [&](int q0, int gc, double* const* d) {
         tk.start(c->stream);
-        if ((*info = zbhessenberg_dev(c, gc, n, p, (psd_z*)dH.ptr, (psd_z*)dtau.ptr)) != 0) return *info;
-        s->ms_hess += tk.stop(c->stream);
-        tc.start(c->stream);
-        if ((*info = batch_download(c, A, q0, gc, p, nn2, hst.d(), dH.d())) != 0) return *info;
+        if (int e = zbhessenberg_dev(c, gc, n, p, (psd_z*)d[0], (psd_z*)dtau.ptr)) return e;
+        k.s->ms_hess += tk.stop(c->stream);
+        tk.start(c->stream);
         PSD_CHECK(psd_rt_d2h(tau + 2 * (size_t)q0 * p * n, dtau.ptr, sizeof(psd_z) * (size_t)gc * p * n, c->stream));
         PSD_CHECK(psd_rt_sync(c->stream));
-        s->ms_copy += tc.stop(c->stream);
-    }
+        k.s->ms_copy += tk.stop(c->stream);
+        return 0;
+    };
+    *info = batch_staged(c, nb, sizeof(double) * (nn2 + 2 * (size_t)n) * p, L, k.s, extra, body);
+    if (*info != 0) return *info;
     PSD_CHECK(psd_rt_last_error());
-    s->ms_total = s->ms_hess;
-    s->bytes_hess = nb * 2.0 * 16.0 * p * (5.0 / 6.0) * (double)n * n * n;
+    k.s->ms_total = k.s->ms_hess;
+    k.s->bytes_hess = nb * 2.0 * 16.0 * p * (5.0 / 6.0) * (double)n * n * n;
     return *info = 0;
 }
 
 int psd_z_pschur_batch_dev(psd_ctx* c, int nb, int n, int p, double* dA, char orient, int wantT, int wantZ, int maxitfac,
                            double* dZ, double* alpha, double* beta, int32_t* ascale, int* infos, int* schurindex,
                            psd_stats* stats, int* info) {
-    int dummy;
-    if (!info) info = &dummy;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (!c) return *info = -1;
-    if (nb < 1) return *info = -2;
-    if ((*info = check_dims(n, p)) != 0) return *info = *info - 1;
+    batch_call<psd_stats> k(info, stats);
+    if ((*info = k.head(c, nb, n, p)) != 0) return *info;
     if (!dA) return *info = -5;
     if (orient != 'R' && orient != 'L') return *info = -6;  // PSD.jl:175-177
     if (maxitfac < 1) return *info = -9;
     if (wantZ && !dZ) return *info = -10;
     if (!alpha || !beta || !ascale) return *info = -11;
-    psd_stats local;
-    psd_stats* s = stats ? stats : &local;
-    std::vector<int> linfo(infos ? 0 : nb, 0);
-    int* pinfos = infos ? infos : linfo.data();
+    int* pinfos = k.infos(infos, nb);
     const int rc = zpschur_batch_core(c, nb, n, p, reinterpret_cast<psd_z*>(dA), orient == 'L', wantT, wantZ, maxitfac,
-                                      reinterpret_cast<psd_z*>(dZ), alpha, beta, ascale, pinfos, s);
+                                      reinterpret_cast<psd_z*>(dZ), alpha, beta, ascale, pinfos, k.s);
     if (schurindex) *schurindex = (orient == 'L') ? p : 1;
-    return *info = (rc != 0) ? rc : zbatch_worst(pinfos, nb);
+    return *info = (rc != 0) ? rc : batch_first_code(pinfos, nb);
 }
 
 int psd_z_pschur_batch(psd_ctx* c, int nb, int n, int p, double* const* A, char orient, int wantT, int wantZ, int maxitfac,
                        double* const* Z, double* alpha, double* beta, int32_t* ascale, int* infos, int* schurindex,
                        psd_stats* stats, int* info) {
-    int dummy;
-    if (!info) info = &dummy;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (!c) return *info = -1;
-    if (nb < 1) return *info = -2;
-    if ((*info = check_dims(n, p)) != 0) return *info = *info - 1;
+    batch_call<psd_stats> k(info, stats);
+    if ((*info = k.head(c, nb, n, p)) != 0) return *info;
     if (!A) return *info = -5;
     if (orient != 'R' && orient != 'L') return *info = -6;
     if (maxitfac < 1) return *info = -9;
     if (wantZ && !Z) return *info = -10;
     if (!alpha || !beta || !ascale) return *info = -11;
     const size_t nn2 = 2 * (size_t)n * n;
-    int g = batch_group(c, nb, sizeof(double) * ((wantZ ? 2 : 1) * nn2 + 2 * (size_t)n) * p);
-    psd_batchbuf dbuf[2];
-    psd_hostbuf hst;
-    if ((*info = batch_buffers(g, nn2 * p, wantZ ? 2 : 1, dbuf, hst)) != 0) return *info;
-    psd_stats local;
-    memset(&local, 0, sizeof(local));
-    psd_stats* s = stats ? stats : &local;
-    std::vector<int> linfo(infos ? 0 : nb, 0);
-    int* pinfos = infos ? infos : linfo.data();
-    Timer tc;
-    for (int q0 = 0; q0 < nb; q0 += g) {
-        const int gc = (nb - q0 < g) ? (nb - q0) : g;
+    const batch_list L[] = {{A, p, nn2, BATCH_IN | BATCH_OUT}, {wantZ ? Z : nullptr, p, nn2, BATCH_OUT}};
+    int* pinfos = k.infos(infos, nb);
+    auto body = [&](int q0, int gc, double* const* d) {
         psd_stats gs;
-        tc.start(c->stream);
-        if ((*info = batch_upload(c, A, q0, gc, p, nn2, hst.d(), dbuf[0].d())) != 0) return *info;
-        double ms_copy = tc.stop(c->stream);
-        const int rc = zpschur_batch_core(c, gc, n, p, (psd_z*)dbuf[0].ptr, orient == 'L', wantT, wantZ, maxitfac,
-                                          (psd_z*)dbuf[1].ptr, alpha + 2 * (size_t)q0 * n, beta + (size_t)q0 * n,
-                                          ascale + (size_t)q0 * n, pinfos + q0, &gs);
-        if (rc != 0) return *info = rc;
-        tc.start(c->stream);
-        if ((*info = batch_download(c, A, q0, gc, p, nn2, hst.d(), dbuf[0].d())) != 0) return *info;
-        if (wantZ && (*info = batch_download(c, Z, q0, gc, p, nn2, hst.d(), dbuf[1].d())) != 0) return *info;
-        ms_copy += tc.stop(c->stream);
-        batch_add_stats(s, gs);
-        s->nlog += gs.nlog;
-        s->ms_copy += ms_copy;
-    }
+        // complex rule: the core returns call-wide codes only and each of them ends the group loop; the per-problem
+        // codes wait in pinfos
+        if (int e = zpschur_batch_core(c, gc, n, p, (psd_z*)d[0], orient == 'L', wantT, wantZ, maxitfac, (psd_z*)d[1],
+                                       alpha + 2 * (size_t)q0 * n, beta + (size_t)q0 * n, ascale + (size_t)q0 * n,
+                                       pinfos + q0, &gs))
+            return e;
+        batch_add_stats(k.s, gs, true);
+        return 0;
+    };
+    *info = batch_staged(c, nb, sizeof(double) * ((wantZ ? 2 : 1) * nn2 + 2 * (size_t)n) * p, L, k.s, batch_no_extra, body);
+    if (*info != 0) return *info;
     if (schurindex) *schurindex = (orient == 'L') ? p : 1;
-    return *info = zbatch_worst(pinfos, nb);
+    return *info = batch_first_code(pinfos, nb);
 }
 
 int psd_z_pschur_hess_batch(psd_ctx* c, int nb, int n, int p, double* const* H, double* const* Q, int wantT, int wantZ,
                             int maxitfac, double* alpha, double* beta, int32_t* ascale, int* infos, psd_stats* stats,
                             int* info) {
-    int dummy;
-    if (!info) info = &dummy;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (!c) return *info = -1;
-    if (nb < 1) return *info = -2;
-    if ((*info = check_dims(n, p)) != 0) return *info = *info - 1;
+    batch_call<psd_stats> k(info, stats);
+    if ((*info = k.head(c, nb, n, p)) != 0) return *info;
     if (!H) return *info = -5;
     if (wantZ && !Q) return *info = -6;
     if (maxitfac < 1) return *info = -9;
     if (!alpha || !beta || !ascale) return *info = -10;
     if (c->shard_world > 1) return *info = PSD_INFO_NOTIMPL;
     const size_t nn2 = 2 * (size_t)n * n;
-    int g = batch_group(c, nb, sizeof(double) * ((wantZ ? 2 : 1) * nn2 + 2 * (size_t)n) * p);
-    psd_batchbuf dbuf[2];
-    psd_hostbuf hst;
-    if ((*info = batch_buffers(g, nn2 * p, wantZ ? 2 : 1, dbuf, hst)) != 0) return *info;
-    psd_stats local;
-    memset(&local, 0, sizeof(local));
-    psd_stats* s = stats ? stats : &local;
-    std::vector<int> linfo(infos ? 0 : nb, 0);
-    int* pinfos = infos ? infos : linfo.data();
-    Timer tc, tk;
-    for (int q0 = 0; q0 < nb; q0 += g) {
-        const int gc = (nb - q0 < g) ? (nb - q0) : g;
-        tc.start(c->stream);
-        if ((*info = batch_upload(c, H, q0, gc, p, nn2, hst.d(), dbuf[0].d())) != 0) return *info;
-        if (wantZ && (*info = batch_upload(c, Q, q0, gc, p, nn2, hst.d(), dbuf[1].d())) != 0) return *info;
-        s->ms_copy += tc.stop(c->stream);
+    const batch_list L[] = {{H, p, nn2, BATCH_IN | BATCH_OUT}, {wantZ ? Q : nullptr, p, nn2, BATCH_IN | BATCH_OUT}};
+    int* pinfos = k.infos(infos, nb);
+    Timer tk;
+    auto body = [&](int q0, int gc, double* const* d) {
         tk.start(c->stream);
-        const int rc = zbiterate_dev(c, gc, n, p, (psd_z*)dbuf[0].ptr, (psd_z*)dbuf[1].ptr, wantT, wantZ, maxitfac,
-                                     alpha + 2 * (size_t)q0 * n, beta + (size_t)q0 * n, ascale + (size_t)q0 * n, pinfos + q0, s);
-        if (rc != 0) return *info = rc;
-        s->ms_iter += tk.stop(c->stream);
-        tc.start(c->stream);
-        if ((*info = batch_download(c, H, q0, gc, p, nn2, hst.d(), dbuf[0].d())) != 0) return *info;
-        if (wantZ && (*info = batch_download(c, Q, q0, gc, p, nn2, hst.d(), dbuf[1].d())) != 0) return *info;
-        s->ms_copy += tc.stop(c->stream);
-    }
-    s->ms_total = s->ms_iter;
-    return *info = zbatch_worst(pinfos, nb);
+        if (int e = zbiterate_dev(c, gc, n, p, (psd_z*)d[0], (psd_z*)d[1], wantT, wantZ, maxitfac, alpha + 2 * (size_t)q0 * n,
+                                  beta + (size_t)q0 * n, ascale + (size_t)q0 * n, pinfos + q0, k.s))
+            return e;
+        k.s->ms_iter += tk.stop(c->stream);
+        return 0;
+    };
+    *info = batch_staged(c, nb, sizeof(double) * ((wantZ ? 2 : 1) * nn2 + 2 * (size_t)n) * p, L, k.s, batch_no_extra, body);
+    if (*info != 0) return *info;
+    k.s->ms_total = k.s->ms_iter;
+    return *info = batch_first_code(pinfos, nb);
 }
 
 }  // extern "C"

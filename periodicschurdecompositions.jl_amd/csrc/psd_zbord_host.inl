@@ -145,96 +145,47 @@ extern "C" {
 int psd_z_ordschur_batch_dev(psd_ctx* c, int nb, int n, int p, void* dT, void* dZ, char orient, int schurindex,
                              const uint8_t* select, int wantZ, double* alpha, double* beta, int32_t* ascale, int* infos,
                              int* nswaps, psd_stats* stats, int* info) {
-    int dummy;
-    if (!info) info = &dummy;
-    if (stats) memset(stats, 0, sizeof(*stats));
+    batch_call<psd_stats> k(info, stats);
     std::vector<int> slotA, slotZ;
     if ((*info = zbord_checked(c, nb, n, p, dT, dZ, orient, schurindex, select, wantZ, alpha, beta, ascale, slotA, slotZ)) != 0 ||
         nb == 0)
         return *info;
     const size_t nn = (size_t)n * n;
-    psd_stats local;
-    memset(&local, 0, sizeof(local));
-    psd_stats* s = stats ? stats : &local;
-    std::vector<int> linfo(infos ? 0 : nb, 0);
-    int* pinfos = infos ? infos : linfo.data();
+    int* pinfos = k.infos(infos, nb);
     psd_z* H = (psd_z*)dT;
     psd_z* Z = wantZ ? (psd_z*)dZ : nullptr;
-    // the workspace of a group; the factors stay where they are
-    int g = batch_group(c, nb, zbord_ws_bytes(n, p));
     zbord_ws ws;
-    if (!zbord_fallback(c, n, p)) {
-        for (;;) {
-            const int rc = ws.alloc(g, n, p);
-            if (rc == 0) break;
-            (void)psd_rt_last_error();
-            if (g == 1) return *info = rc;
-            g = (g + 1) / 2;
-        }
-    }
-    psd_batchbuf tmp, dslot;
-    int gt = 0;
-    const int firstZ = (slotZ[0] == 0) ? 1 : 0;
-    if ((*info = bord_permute_dev(c, nb, p, 2 * nn, (double*)H, slotA, 0, true, tmp, gt, dslot)) != 0) return *info;
-    if (Z && (*info = bord_permute_dev(c, nb, p, 2 * nn, (double*)Z, slotZ, firstZ, true, tmp, gt, dslot)) != 0) return *info;
-    int fatal = 0;
-    for (int q0 = 0; q0 < nb && fatal == 0; q0 += g) {
-        const int gc = (nb - q0 < g) ? (nb - q0) : g;
-        fatal = zbord_group(c, gc, n, p, H + (size_t)q0 * p * nn, Z ? Z + (size_t)q0 * p * nn : nullptr,
-                            select + (size_t)q0 * n, wantZ, alpha + 2 * (size_t)q0 * n, beta + (size_t)q0 * n,
-                            ascale + (size_t)q0 * n, pinfos + q0, nswaps ? nswaps + q0 : nullptr, s, ws);
-    }
-    // back to the user order, also behind a runtime failure: the caller's blocks keep their places
-    int rc = bord_permute_dev(c, nb, p, 2 * nn, (double*)H, slotA, 0, false, tmp, gt, dslot);
-    if (rc == 0 && Z) rc = bord_permute_dev(c, nb, p, 2 * nn, (double*)Z, slotZ, firstZ, false, tmp, gt, dslot);
-    if (rc == 0) rc = psd_rt_sync(c->stream) != 0 ? PSD_INFO_RUNTIME + 1 : 0;
-    if (fatal != 0) return *info = fatal;
-    if (rc != 0) return *info = rc;
-    return *info = bord_first_code(nb, pinfos);
+    auto group = [&](int q0, int gc) {
+        return zbord_group(c, gc, n, p, H + (size_t)q0 * p * nn, Z ? Z + (size_t)q0 * p * nn : nullptr, select + (size_t)q0 * n,
+                           wantZ, alpha + 2 * (size_t)q0 * n, beta + (size_t)q0 * n, ascale + (size_t)q0 * n, pinfos + q0,
+                           nswaps ? nswaps + q0 : nullptr, k.s, ws);
+    };
+    return *info = bord_dev_run(c, nb, n, p, 2 * nn, (double*)H, (double*)Z, slotA, slotZ, zbord_fallback(c, n, p),
+                                zbord_ws_bytes(n, p), ws, pinfos, group);
 }
 
 int psd_z_ordschur_batch(psd_ctx* c, int nb, int n, int p, double* const* T, double* const* Z, char orient, int schurindex,
                          const uint8_t* select, int wantZ, double* alpha, double* beta, int32_t* ascale, int* infos,
                          int* nswaps, psd_stats* stats, int* info) {
-    int dummy;
-    if (!info) info = &dummy;
-    if (stats) memset(stats, 0, sizeof(*stats));
+    batch_call<psd_stats> k(info, stats);
     std::vector<int> slotA, slotZ;
     if ((*info = zbord_checked(c, nb, n, p, T, Z, orient, schurindex, select, wantZ, alpha, beta, ascale, slotA, slotZ)) != 0 ||
         nb == 0)
         return *info;
-    const size_t nn = (size_t)n * n, nn2 = 2 * nn;  // doubles of one factor
-    const int nz = wantZ ? 2 : 1;
-    int g = batch_group(c, nb, sizeof(double) * nz * nn2 * p + zbord_ws_bytes(n, p));
-    psd_batchbuf dbuf[2];
-    psd_hostbuf hst;
-    if ((*info = batch_buffers(g, nn2 * p, nz, dbuf, hst)) != 0) return *info;
+    const size_t nn2 = 2 * (size_t)n * n;  // doubles of one factor
+    // user slot <-> internal slot on the way through the staging buffer, as psd_z_ordschur copies
+    const batch_list L[] = {{T, p, nn2, BATCH_IN | BATCH_OUT, slotA.data()},
+                            {wantZ ? Z : nullptr, p, nn2, BATCH_IN | BATCH_OUT, slotZ.data()}};
+    int* pinfos = k.infos(infos, nb);
     zbord_ws ws;
-    if (!zbord_fallback(c, n, p) && (*info = ws.alloc(g, n, p)) != 0) return *info;
-    psd_stats local;
-    memset(&local, 0, sizeof(local));
-    psd_stats* s = stats ? stats : &local;
-    std::vector<int> linfo(infos ? 0 : nb, 0);
-    int* pinfos = infos ? infos : linfo.data();
-    Timer tc;
-    for (int q0 = 0; q0 < nb; q0 += g) {
-        const int gc = (nb - q0 < g) ? (nb - q0) : g;
-        tc.start(c->stream);
-        // user slot <-> internal slot on the way through the staging buffer, as psd_z_ordschur copies
-        if ((*info = batch_upload(c, T, q0, gc, p, nn2, hst.d(), dbuf[0].d(), slotA.data())) != 0) return *info;
-        if (wantZ && (*info = batch_upload(c, Z, q0, gc, p, nn2, hst.d(), dbuf[1].d(), slotZ.data())) != 0) return *info;
-        double ms_copy = tc.stop(c->stream);
-        *info = zbord_group(c, gc, n, p, (psd_z*)dbuf[0].ptr, wantZ ? (psd_z*)dbuf[1].ptr : nullptr, select + (size_t)q0 * n,
-                            wantZ, alpha + 2 * (size_t)q0 * n, beta + (size_t)q0 * n, ascale + (size_t)q0 * n, pinfos + q0,
-                            nswaps ? nswaps + q0 : nullptr, s, ws);
-        if (*info != 0) return *info;
-        tc.start(c->stream);
-        if ((*info = batch_download(c, T, q0, gc, p, nn2, hst.d(), dbuf[0].d(), slotA.data())) != 0) return *info;
-        if (wantZ && (*info = batch_download(c, Z, q0, gc, p, nn2, hst.d(), dbuf[1].d(), slotZ.data())) != 0) return *info;
-        ms_copy += tc.stop(c->stream);
-        s->ms_copy += ms_copy;
-    }
-    return *info = bord_first_code(nb, pinfos);
+    auto extra = [&](int g) { return zbord_fallback(c, n, p) ? 0 : ws.alloc(g, n, p); };
+    auto body = [&](int q0, int gc, double* const* d) {
+        return zbord_group(c, gc, n, p, (psd_z*)d[0], (psd_z*)d[1], select + (size_t)q0 * n, wantZ, alpha + 2 * (size_t)q0 * n,
+                           beta + (size_t)q0 * n, ascale + (size_t)q0 * n, pinfos + q0, nswaps ? nswaps + q0 : nullptr, k.s, ws);
+    };
+    *info = batch_staged(c, nb, sizeof(double) * (wantZ ? 2 : 1) * nn2 * p + zbord_ws_bytes(n, p), L, k.s, extra, body);
+    if (*info != 0) return *info;
+    return *info = batch_first_code(pinfos, nb);
 }
 
 }  // extern "C"

@@ -28,43 +28,15 @@ bool zgb_all_true(const uint8_t* S, int p) {
     return true;
 }
 
-// per-problem workspace of psd_zgbqz for nb problems, carved from one allocation (every region 16-byte aligned)
-struct zgb_work {
-    psd_batchbuf buf;
-    psd_zgbqz_args A;
-    int alloc(psd_ctx* c, int nb, int n, int p, int maxlog, const uint8_t* S) {
-        size_t off = 0;
-        auto carve = [&off](size_t bytes) {
-            const size_t o = off;
-            off += (bytes + 15) & ~(size_t)15;
-            return o;
-        };
-        const size_t o_st = carve(sizeof(psd_zgstate) * nb), o_desc = carve(sizeof(psd_gapply_desc) * nb);
-        const size_t o_tr = carve(sizeof(psd_ztr) * (size_t)nb * p * PSD_GTR_CAP), o_cnt = carve(sizeof(int) * (size_t)nb * p);
-        const size_t o_dG = carve(sizeof(psd_ztr) * (size_t)nb * (n + 2)), o_alpha = carve(sizeof(psd_z) * (size_t)nb * n);
-        const size_t o_beta = carve(sizeof(double) * (size_t)nb * n), o_asc = carve(sizeof(int) * (size_t)nb * n);
-        const size_t o_log = carve(sizeof(int) * (size_t)nb * 3 * maxlog), o_info = carve(sizeof(int) * nb);
-        const size_t o_S = carve((size_t)p);
-        PSD_CHECK(buf.alloc(off));
-        PSD_CHECK(psd_rt_memset(buf.ptr, 0, off, c->stream));
-        char* w = (char*)buf.ptr;
-        PSD_CHECK(psd_rt_h2d(w + o_S, S, (size_t)p, c->stream));
-        PSD_CHECK(psd_rt_sync(c->stream));  // (S may be a temporary of the caller)
-        A.S = (const unsigned char*)(w + o_S);
-        A.st = (psd_zgstate*)(w + o_st);
-        A.desc = (psd_gapply_desc*)(w + o_desc);
-        A.tr = (psd_ztr*)(w + o_tr);
-        A.cnt = (int*)(w + o_cnt);
-        A.dG = (psd_ztr*)(w + o_dG);
-        A.alpha = (psd_z*)(w + o_alpha);
-        A.beta = (double*)(w + o_beta);
-        A.ascale = (int*)(w + o_asc);
-        A.log = (int*)(w + o_log);
-        A.infos = (int*)(w + o_info);
-        A.n = n; A.p = p; A.maxlog = maxlog;
-        return 0;
-    }
-};
+// the workspace of psd_zgbqz for nb problems (zb_work, psd_zbatch_host.inl) with the signature S (host, p flags) behind it
+using zgb_work = zb_work<psd_zgbqz_args>;
+int zgb_work_alloc(psd_ctx* c, zgb_work& ws, int nb, int n, int p, int maxlog, const uint8_t* S) {
+    if (int e = ws.alloc(c, nb, n, p, PSD_GTR_CAP, maxlog, (size_t)p)) return e;
+    PSD_CHECK(psd_rt_h2d(ws.extra, S, (size_t)p, c->stream));
+    PSD_CHECK(psd_rt_sync(c->stream));  // (S may be a temporary of the caller)
+    ws.A.S = (const unsigned char*)ws.extra;
+    return 0;
+}
 
 // one launch of psd_zgbqz over nb problems; the states and per-problem codes (PSD_LIST_OVERFLOW, PSD_ZB_TICKCAP, level)
 // come back in hst / hinfo
@@ -114,7 +86,7 @@ int zgbhess_dev(psd_ctx* c, int nb, int n, int p, psd_z* dA, psd_z* dQ, const ui
         return 0;
     }
     zgb_work ws;
-    int rc = ws.alloc(c, nb, n, p, 16, S);
+    int rc = zgb_work_alloc(c, ws, nb, n, p, 16, S);
     if (rc != 0) return rc;
     Timer t;
     t.start(c->stream);
@@ -128,7 +100,7 @@ int zgbhess_dev(psd_ctx* c, int nb, int n, int p, psd_z* dA, psd_z* dQ, const ui
     s->ms_hess += ms1 + ms2;
     s->ms_formq += ms1;  // (stage 1 accumulates Q as it goes: the convention of zsghess_dev)
     for (int q = 0; q < nb; ++q) {
-        const int code = zbatch_info_code(hinfo[q]);
+        const int code = batch_info_code(hinfo[q]);
         if (infos) infos[q] = code;
         else if (code != 0) return code;
     }
@@ -157,21 +129,13 @@ int zgbiterate_dev(psd_ctx* c, int nb, int n, int p, psd_z* dH, psd_z* dZ, const
             if (rc == PSD_INFO_RUNTIME + 0xfffc) rc = PSD_INFO_RUNTIME + 0xfffe;  // (the tick bound of the single call)
             if (batch_fatal(rc) && rc != PSD_INFO_RUNTIME + 77 && rc != PSD_INFO_RUNTIME + 0xfffe) return rc;
             infos[q] = rc;
-            s->niter += ps.niter;
-            s->nsweeps += ps.nsweeps;
-            s->nrqpass += ps.nrqpass;
-            s->ndefl1 += ps.ndefl1;
-            s->ndefl2 += ps.ndefl2;
-            s->reserved += ps.reserved;
-            s->nwindows += ps.nwindows;
-            s->nlog += ps.nlog;
-            s->nlaunch_step += ps.nlaunch_step;
+            batch_add_counts(s, ps);  // (not maxits: the single signed call keeps its train sweeps there)
         }
         s->window = W;
         return 0;
     }
     zgb_work ws;
-    int rc = ws.alloc(c, nb, n, p, maxlog, S);
+    int rc = zgb_work_alloc(c, ws, nb, n, p, maxlog, S);
     if (rc != 0) return rc;
     std::vector<psd_zgstate> hst;
     std::vector<int> hinfo;
@@ -183,16 +147,9 @@ int zgbiterate_dev(psd_ctx* c, int nb, int n, int p, psd_z* dH, psd_z* dZ, const
     PSD_CHECK(psd_rt_sync(c->stream));
     for (size_t e = 0; e < (size_t)nb * n; ++e) ascale[e] = hsc[e];
     for (int q = 0; q < nb; ++q) {
-        const psd_zgstate& st = hst[q];
-        infos[q] = zbatch_info_code(hinfo[q]);
-        s->niter += st.jiter;
-        s->nsweeps += st.nsweeps;
-        s->nrqpass += st.nzshift;
-        s->ndefl1 += st.nsplit;
-        s->ndefl2 += st.ncase2;
-        s->reserved += st.ncase2 + 1000 * st.ncase3;
-        s->nwindows += st.nwindows;
-        s->nlog += st.nlog;
+        infos[q] = batch_info_code(hinfo[q]);
+        zbatch_add_state(s, hst[q]);
+        s->reserved += hst[q].ncase2 + 1000 * hst[q].ncase3;
     }
     s->nlaunch_step += 1;
     s->window = W;
@@ -214,27 +171,20 @@ int zgpschur_batch_core(psd_ctx* c, int nb, int n, int p, psd_z* dA, const uint8
                         int maxitfac, psd_z* dZ, double* alpha, double* beta, int32_t* ascale, int* infos, psd_stats* s) {
     memset(s, 0, sizeof(*s));
     if (c->shard_world > 1) return PSD_INFO_NOTIMPL;  // (a period-sharded context keeps a slice of Z: single problems only)
-    const size_t nn = (size_t)n * n;
     const std::vector<uint8_t> Sw = zgb_working_sig(S, p, left);
-    int rc = 0;
     Timer tall, tph;
     tall.start(c->stream);
-    if (left && p > 1)
-        PSD_LAUNCH(psd_breverse_blocks, psd_dim3(nb * (p / 2)), PSD_HESS_NT, 0, c->stream, (double*)dA, 2 * nn, p, 0, p);
-    std::vector<int> hinfos(nb, 0);
-    if ((rc = zgbhess_dev(c, nb, n, p, dA, wantZ ? dZ : nullptr, Sw.data(), hinfos.data(), s)) != 0) return rc;
-    tph.start(c->stream);
-    if ((rc = zgbiterate_dev(c, nb, n, p, dA, dZ, Sw.data(), wantT, wantZ, maxitfac, alpha, beta, ascale, infos, s)) != 0)
-        return rc;
-    s->ms_iter = tph.stop(c->stream);
-    for (int q = 0; q < nb; ++q)
-        if (hinfos[q] != 0) infos[q] = hinfos[q];  // (a reduction that gave up: what followed is not a decomposition)
-    if (left && p > 1) {
-        PSD_LAUNCH(psd_breverse_blocks, psd_dim3(nb * (p / 2)), PSD_HESS_NT, 0, c->stream, (double*)dA, 2 * nn, p, 0, p);
-        if (wantZ && p > 2)
-            PSD_LAUNCH(psd_breverse_blocks, psd_dim3(nb * ((p - 1) / 2)), PSD_HESS_NT, 0, c->stream, (double*)dZ, 2 * nn, p, 1,
-                       p - 1);
-    }
+    const int rc = batch_reversed(c, left, nb, p, 2 * (size_t)n * n, (double*)dA, wantZ ? (double*)dZ : nullptr, [&]() {
+        std::vector<int> hinfos(nb, 0);
+        if (int e = zgbhess_dev(c, nb, n, p, dA, wantZ ? dZ : nullptr, Sw.data(), hinfos.data(), s)) return e;
+        tph.start(c->stream);
+        if (int e = zgbiterate_dev(c, nb, n, p, dA, dZ, Sw.data(), wantT, wantZ, maxitfac, alpha, beta, ascale, infos, s)) return e;
+        s->ms_iter = tph.stop(c->stream);
+        for (int q = 0; q < nb; ++q)
+            if (hinfos[q] != 0) infos[q] = hinfos[q];  // (a reduction that gave up: what followed is not a decomposition)
+        return 0;
+    });
+    if (rc != 0) return rc;
     s->ms_total = tall.stop(c->stream);
     s->bytes_hess = nb * 2.0 * 16.0 * p * (double)n * n * n;
     PSD_CHECK(psd_rt_last_error());
@@ -247,52 +197,30 @@ extern "C" {
 
 int psd_z_gphessenberg_batch(psd_ctx* c, int nb, int n, int p, double* const* A, const uint8_t* S, double* const* Q,
                              psd_stats* stats, int* info) {
-    int dummy;
-    if (!info) info = &dummy;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (!c) return *info = -1;
-    if (nb < 1) return *info = -2;
-    if ((*info = check_dims(n, p)) != 0) return *info = *info - 1;
+    batch_call<psd_stats> k(info, stats);
+    if ((*info = k.head(c, nb, n, p)) != 0) return *info;
     if (!A) return *info = -5;
     if (S && !S[0]) return *info = -7;
     std::vector<uint8_t> Sw(p, 1);
     for (int j = 0; j < p; ++j) Sw[j] = (!S || S[j]) ? 1 : 0;
     const size_t nn2 = 2 * (size_t)n * n;  // doubles of one factor
-    int g = batch_group(c, nb, sizeof(double) * ((Q ? 2 : 1) * nn2 + 2 * (size_t)n) * p);
-    psd_batchbuf dbuf[2];
-    psd_hostbuf hst;
-    if ((*info = batch_buffers(g, nn2 * p, Q ? 2 : 1, dbuf, hst)) != 0) return *info;
-    psd_stats local;
-    memset(&local, 0, sizeof(local));
-    psd_stats* s = stats ? stats : &local;
-    Timer tc;
-    for (int q0 = 0; q0 < nb; q0 += g) {
-        const int gc = (nb - q0 < g) ? (nb - q0) : g;
-        tc.start(c->stream);
-        if ((*info = batch_upload(c, A, q0, gc, p, nn2, hst.d(), dbuf[0].d())) != 0) return *info;
-        s->ms_copy += tc.stop(c->stream);
-        if ((*info = zgbhess_dev(c, gc, n, p, (psd_z*)dbuf[0].ptr, Q ? (psd_z*)dbuf[1].ptr : nullptr, Sw.data(), nullptr, s)) != 0)
-            return *info;
-        tc.start(c->stream);
-        if ((*info = batch_download(c, A, q0, gc, p, nn2, hst.d(), dbuf[0].d())) != 0) return *info;
-        if (Q && (*info = batch_download(c, Q, q0, gc, p, nn2, hst.d(), dbuf[1].d())) != 0) return *info;
-        s->ms_copy += tc.stop(c->stream);
-    }
+    const batch_list L[] = {{A, p, nn2, BATCH_IN | BATCH_OUT}, {Q, p, nn2, BATCH_OUT}};
+    auto body = [&](int, int gc, double* const* d) {
+        return zgbhess_dev(c, gc, n, p, (psd_z*)d[0], (psd_z*)d[1], Sw.data(), nullptr, k.s);
+    };
+    *info = batch_staged(c, nb, sizeof(double) * ((Q ? 2 : 1) * nn2 + 2 * (size_t)n) * p, L, k.s, batch_no_extra, body);
+    if (*info != 0) return *info;
     PSD_CHECK(psd_rt_last_error());
-    s->ms_total = s->ms_hess;
-    s->bytes_hess = nb * 2.0 * 16.0 * p * (double)n * n * n;
+    k.s->ms_total = k.s->ms_hess;
+    k.s->bytes_hess = nb * 2.0 * 16.0 * p * (double)n * n * n;
     return *info = 0;
 }
 
 int psd_z_gpschur_batch_dev(psd_ctx* c, int nb, int n, int p, double* dA, const uint8_t* S, char orient, int wantT,
                             int wantZ, int maxitfac, double* dZ, double* alpha, double* beta, int32_t* ascale, int* infos,
                             int* schurindex, psd_stats* stats, int* info) {
-    int dummy;
-    if (!info) info = &dummy;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (!c) return *info = -1;
-    if (nb < 1) return *info = -2;
-    if ((*info = check_dims(n, p)) != 0) return *info = *info - 1;
+    batch_call<psd_stats> k(info, stats);
+    if ((*info = k.head(c, nb, n, p)) != 0) return *info;
     if (!dA) return *info = -5;
     if (orient != 'R' && orient != 'L') return *info = -6;  // PSD.jl:175-177
     if (S && !S[(orient == 'L') ? p - 1 : 0]) return *info = -7;  // generalized.jl:140
@@ -302,25 +230,18 @@ int psd_z_gpschur_batch_dev(psd_ctx* c, int nb, int n, int p, double* dA, const 
     if (zgb_all_true(S, p))  // (the tuned all-true path, as psd_z_pschur keeps it)
         return psd_z_pschur_batch_dev(c, nb, n, p, dA, orient, wantT, wantZ, maxitfac, dZ, alpha, beta, ascale, infos,
                                       schurindex, stats, info);
-    psd_stats local;
-    psd_stats* s = stats ? stats : &local;
-    std::vector<int> linfo(infos ? 0 : nb, 0);
-    int* pinfos = infos ? infos : linfo.data();
+    int* pinfos = k.infos(infos, nb);
     const int rc = zgpschur_batch_core(c, nb, n, p, reinterpret_cast<psd_z*>(dA), S, orient == 'L', wantT, wantZ, maxitfac,
-                                       reinterpret_cast<psd_z*>(dZ), alpha, beta, ascale, pinfos, s);
+                                       reinterpret_cast<psd_z*>(dZ), alpha, beta, ascale, pinfos, k.s);
     if (schurindex) *schurindex = (orient == 'L') ? p : 1;
-    return *info = (rc != 0) ? rc : zbatch_worst(pinfos, nb);
+    return *info = (rc != 0) ? rc : batch_first_code(pinfos, nb);
 }
 
 int psd_z_gpschur_batch(psd_ctx* c, int nb, int n, int p, double* const* A, const uint8_t* S, char orient, int wantT,
                         int wantZ, int maxitfac, double* const* Z, double* alpha, double* beta, int32_t* ascale, int* infos,
                         int* schurindex, psd_stats* stats, int* info) {
-    int dummy;
-    if (!info) info = &dummy;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (!c) return *info = -1;
-    if (nb < 1) return *info = -2;
-    if ((*info = check_dims(n, p)) != 0) return *info = *info - 1;
+    batch_call<psd_stats> k(info, stats);
+    if ((*info = k.head(c, nb, n, p)) != 0) return *info;
     if (!A) return *info = -5;
     if (orient != 'R' && orient != 'L') return *info = -6;
     if (S && !S[(orient == 'L') ? p - 1 : 0]) return *info = -7;
@@ -331,47 +252,30 @@ int psd_z_gpschur_batch(psd_ctx* c, int nb, int n, int p, double* const* A, cons
         return psd_z_pschur_batch(c, nb, n, p, A, orient, wantT, wantZ, maxitfac, Z, alpha, beta, ascale, infos, schurindex,
                                   stats, info);
     const size_t nn2 = 2 * (size_t)n * n;
-    int g = batch_group(c, nb, sizeof(double) * ((wantZ ? 2 : 1) * nn2 + 2 * (size_t)n) * p);
-    psd_batchbuf dbuf[2];
-    psd_hostbuf hst;
-    if ((*info = batch_buffers(g, nn2 * p, wantZ ? 2 : 1, dbuf, hst)) != 0) return *info;
-    psd_stats local;
-    memset(&local, 0, sizeof(local));
-    psd_stats* s = stats ? stats : &local;
-    std::vector<int> linfo(infos ? 0 : nb, 0);
-    int* pinfos = infos ? infos : linfo.data();
-    Timer tc;
-    for (int q0 = 0; q0 < nb; q0 += g) {
-        const int gc = (nb - q0 < g) ? (nb - q0) : g;
+    const batch_list L[] = {{A, p, nn2, BATCH_IN | BATCH_OUT}, {wantZ ? Z : nullptr, p, nn2, BATCH_OUT}};
+    int* pinfos = k.infos(infos, nb);
+    auto body = [&](int q0, int gc, double* const* d) {
         psd_stats gs;
-        tc.start(c->stream);
-        if ((*info = batch_upload(c, A, q0, gc, p, nn2, hst.d(), dbuf[0].d())) != 0) return *info;
-        double ms_copy = tc.stop(c->stream);
-        const int rc = zgpschur_batch_core(c, gc, n, p, (psd_z*)dbuf[0].ptr, S, orient == 'L', wantT, wantZ, maxitfac,
-                                           (psd_z*)dbuf[1].ptr, alpha + 2 * (size_t)q0 * n, beta + (size_t)q0 * n,
-                                           ascale + (size_t)q0 * n, pinfos + q0, &gs);
-        if (rc != 0) return *info = rc;
-        tc.start(c->stream);
-        if ((*info = batch_download(c, A, q0, gc, p, nn2, hst.d(), dbuf[0].d())) != 0) return *info;
-        if (wantZ && (*info = batch_download(c, Z, q0, gc, p, nn2, hst.d(), dbuf[1].d())) != 0) return *info;
-        ms_copy += tc.stop(c->stream);
-        batch_add_stats(s, gs);
-        s->nlog += gs.nlog;
-        s->ms_copy += ms_copy;
-    }
+        // complex rule: the core returns call-wide codes only and each of them ends the group loop; the per-problem
+        // codes wait in pinfos
+        if (int e = zgpschur_batch_core(c, gc, n, p, (psd_z*)d[0], S, orient == 'L', wantT, wantZ, maxitfac, (psd_z*)d[1],
+                                        alpha + 2 * (size_t)q0 * n, beta + (size_t)q0 * n, ascale + (size_t)q0 * n,
+                                        pinfos + q0, &gs))
+            return e;
+        batch_add_stats(k.s, gs, true);
+        return 0;
+    };
+    *info = batch_staged(c, nb, sizeof(double) * ((wantZ ? 2 : 1) * nn2 + 2 * (size_t)n) * p, L, k.s, batch_no_extra, body);
+    if (*info != 0) return *info;
     if (schurindex) *schurindex = (orient == 'L') ? p : 1;
-    return *info = zbatch_worst(pinfos, nb);
+    return *info = batch_first_code(pinfos, nb);
 }
 
 int psd_z_gpschur_hess_batch(psd_ctx* c, int nb, int n, int p, double* const* H, const uint8_t* S, double* const* Q,
                              int wantT, int wantZ, int maxitfac, double* alpha, double* beta, int32_t* ascale, int* infos,
                              psd_stats* stats, int* info) {
-    int dummy;
-    if (!info) info = &dummy;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (!c) return *info = -1;
-    if (nb < 1) return *info = -2;
-    if ((*info = check_dims(n, p)) != 0) return *info = *info - 1;
+    batch_call<psd_stats> k(info, stats);
+    if ((*info = k.head(c, nb, n, p)) != 0) return *info;
     if (!H) return *info = -5;
     if (wantZ && !Q) return *info = -6;
     if (S && !S[0]) return *info = -7;
@@ -381,34 +285,22 @@ int psd_z_gpschur_hess_batch(psd_ctx* c, int nb, int n, int p, double* const* H,
         return psd_z_pschur_hess_batch(c, nb, n, p, H, Q, wantT, wantZ, maxitfac, alpha, beta, ascale, infos, stats, info);
     if (c->shard_world > 1) return *info = PSD_INFO_NOTIMPL;
     const size_t nn2 = 2 * (size_t)n * n;
-    int g = batch_group(c, nb, sizeof(double) * ((wantZ ? 2 : 1) * nn2 + 2 * (size_t)n) * p);
-    psd_batchbuf dbuf[2];
-    psd_hostbuf hst;
-    if ((*info = batch_buffers(g, nn2 * p, wantZ ? 2 : 1, dbuf, hst)) != 0) return *info;
-    psd_stats local;
-    memset(&local, 0, sizeof(local));
-    psd_stats* s = stats ? stats : &local;
-    std::vector<int> linfo(infos ? 0 : nb, 0);
-    int* pinfos = infos ? infos : linfo.data();
-    Timer tc, tk;
-    for (int q0 = 0; q0 < nb; q0 += g) {
-        const int gc = (nb - q0 < g) ? (nb - q0) : g;
-        tc.start(c->stream);
-        if ((*info = batch_upload(c, H, q0, gc, p, nn2, hst.d(), dbuf[0].d())) != 0) return *info;
-        if (wantZ && (*info = batch_upload(c, Q, q0, gc, p, nn2, hst.d(), dbuf[1].d())) != 0) return *info;
-        s->ms_copy += tc.stop(c->stream);
+    const batch_list L[] = {{H, p, nn2, BATCH_IN | BATCH_OUT}, {wantZ ? Q : nullptr, p, nn2, BATCH_IN | BATCH_OUT}};
+    int* pinfos = k.infos(infos, nb);
+    Timer tk;
+    auto body = [&](int q0, int gc, double* const* d) {
         tk.start(c->stream);
-        const int rc = zgbiterate_dev(c, gc, n, p, (psd_z*)dbuf[0].ptr, (psd_z*)dbuf[1].ptr, S, wantT, wantZ, maxitfac,
-                                      alpha + 2 * (size_t)q0 * n, beta + (size_t)q0 * n, ascale + (size_t)q0 * n, pinfos + q0, s);
-        if (rc != 0) return *info = rc;
-        s->ms_iter += tk.stop(c->stream);
-        tc.start(c->stream);
-        if ((*info = batch_download(c, H, q0, gc, p, nn2, hst.d(), dbuf[0].d())) != 0) return *info;
-        if (wantZ && (*info = batch_download(c, Q, q0, gc, p, nn2, hst.d(), dbuf[1].d())) != 0) return *info;
-        s->ms_copy += tc.stop(c->stream);
-    }
-    s->ms_total = s->ms_iter;
-    return *info = zbatch_worst(pinfos, nb);
+        if (int e = zgbiterate_dev(c, gc, n, p, (psd_z*)d[0], (psd_z*)d[1], S, wantT, wantZ, maxitfac,
+                                   alpha + 2 * (size_t)q0 * n, beta + (size_t)q0 * n, ascale + (size_t)q0 * n, pinfos + q0, k.s))
+            return e;
+        k.s->ms_iter += tk.stop(c->stream);
+        return 0;
+    };
+    *info = batch_staged(c, nb, sizeof(double) * ((wantZ ? 2 : 1) * nn2 + 2 * (size_t)n) * p, L, k.s, batch_no_extra, body);
+    if (*info != 0) return *info;
+    k.s->ms_total = k.s->ms_iter;
+    return *info = batch_first_code(pinfos, nb);
 }
 
 }  // extern "C"
+

@@ -219,6 +219,67 @@ def case_argument_errors(eng):
     assert eng.pschur_batch([], infos_out=infos) == [] and infos == []
 
 
+def case_abi_codes(eng, shape=(5, 12, 3)):
+    """The argument codes of the four C entries of the real family, as zbatch_cases.case_abi_codes: the return value and
+    *info agree, code by code.  Every call ends in the argument checks, so the pointers are never followed (the packed
+    host block stands in for a device buffer)."""
+    import ctypes as C
+
+    nb, n, p = shape
+    probs = problems(*shape)
+    lib, ctx = eng.lib, eng.ctx
+    dp = C.POINTER(C.c_double)
+    A = work(probs[0])
+    ptrs = eng._ptrs(A)
+    dA = np.ascontiguousarray(np.array([pt.pack(A)]))
+    buf = C.c_void_p(dA.ctypes.data)
+    tau, w = np.zeros((p, n)), np.zeros(n)
+    wp, tp = w.ctypes.data_as(dp), tau.ctypes.data_as(dp)
+
+    def both(call):
+        """the code of a call, returned and stored alike"""
+        info = C.c_int(12345)
+        rc = call(C.byref(info))
+        assert rc == info.value, (rc, info.value)
+        return rc
+
+    def hess(c=ctx, nb_=1, n_=n, p_=p, A_=ptrs, tau_=tp):
+        return both(lambda ip: lib.psd_d_phessenberg_batch(c, nb_, n_, p_, A_, tau_, None, ip))
+
+    def host_(c=ctx, nb_=1, n_=n, p_=p, A_=ptrs, o=b"R", mi=30, wz=0, Z_=None, wr_=wp, wi_=wp):
+        return both(lambda ip: lib.psd_d_pschur_batch(c, nb_, n_, p_, A_, o, 1, wz, mi, Z_, wr_, wi_, None, None, None, ip))
+
+    def dev_(c=ctx, nb_=1, n_=n, p_=p, A_=buf, o=b"R", mi=30, wz=0, Z_=None, wr_=wp, wi_=wp):
+        return both(lambda ip: lib.psd_d_pschur_batch_dev(c, nb_, n_, p_, A_, o, 1, wz, mi, Z_, wr_, wi_, None, None, None, ip))
+
+    def hb_(c=ctx, nb_=1, n_=n, p_=p, H_=ptrs, mi=30, wz=0, Q_=None, wr_=wp, wi_=wp):
+        return both(lambda ip: lib.psd_d_pschur_hess_batch(c, nb_, n_, p_, H_, Q_, 1, wz, mi, wr_, wi_, None, None, ip))
+
+    assert hess(c=None) == -1 and hess(nb_=0) == -2 and hess(n_=0) == -3 and hess(p_=0) == -4
+    assert hess(A_=None) == -5 and hess(tau_=None) == -6
+    for f in (host_, dev_):
+        assert f(c=None) == -1 and f(nb_=0) == -2 and f(nb_=-3) == -2 and f(n_=0) == -3 and f(p_=0) == -4
+        assert f(A_=None) == -5 and f(o=b"X") == -6 and f(mi=0) == -9 and f(wz=1) == -10
+        assert f(wr_=None) == -11 and f(wi_=None) == -11
+    assert hb_(c=None) == -1 and hb_(nb_=0) == -2 and hb_(nb_=33) == -2  # (at most 32 problems side by side)
+    assert hb_(n_=0) == -3 and hb_(p_=0) == -4  # (returned and stored alike: the codes of psd_z_pschur_hess_batch)
+    assert hb_(H_=None) == -5 and hb_(wz=1) == -6 and hb_(mi=0) == -9 and hb_(wr_=None) == -10 and hb_(wi_=None) == -10
+    # the first bad argument decides
+    assert hb_(nb_=33, n_=0) == -2 and hb_(n_=0, p_=0) == -3 and host_(nb_=0, n_=0) == -2 and dev_(p_=0, A_=None) == -4
+    # a null info is allowed
+    assert lib.psd_d_pschur_hess_batch(ctx, 1, 0, p, ptrs, None, 1, 0, 30, wp, wp, None, None, None) == -3
+    assert lib.psd_d_pschur_batch(ctx, 0, n, p, ptrs, b"R", 1, 0, 30, None, wp, wp, None, None, None, None) == -2
+
+
+def _same_bits(whole, parts, p, withZ=True):
+    for q in range(len(whole)):
+        assert np.array_equal(whole[q].values, parts[q].values), q
+        for j in range(p):
+            assert np.array_equal(whole[q].Ts[j], parts[q].Ts[j]), (q, j)
+            if withZ:
+                assert np.array_equal(whole[q].Z[j], parts[q].Z[j]), (q, j)
+
+
 def case_groups(make_engine, shape=(6, 20, 3)):
     """A host entry whose batch does not fit the device at once works through it in groups (PSD_BATCH_GROUP lowers the
     group size): the same results as in one group, problem by problem."""
@@ -226,6 +287,8 @@ def case_groups(make_engine, shape=(6, 20, 3)):
     probs = problems(*shape)
     ref = make_engine({})
     eng = make_engine({"PSD_BATCH_GROUP": "4"})
+    # one list of matrices through the loop (no Z), bit for bit
+    _same_bits(ref.pschur_batch(probs, "L", wantZ=False), eng.pschur_batch(probs, "L", wantZ=False), p, withZ=False)
     whole = ref.pschur_batch(probs, "L")
     parts = eng.pschur_batch(probs, "L")
     for q in range(nb):
@@ -237,6 +300,18 @@ def case_groups(make_engine, shape=(6, 20, 3)):
     op, _ = eng.phessenberg_batch_(Wp)
     for q in range(nb):
         assert np.array_equal(ob[q][1], op[q][1]) and all(np.array_equal(Wb[q][j], Wp[q][j]) for j in range(p))
+    # the reduced factors through pschur_hess_batch_, bit for bit: H and Q both go up and come down (Q_j on entry: any
+    # orthogonal matrices, the same for both engines)
+    rng = np.random.default_rng(20)
+    Qs = [[np.asfortranarray(np.linalg.qr(rng.standard_normal((n, n)))[0]) for _ in range(p)] for _ in range(nb)]
+    infos_w, infos_p = [], []
+    hw = ref.pschur_hess_batch_([(H[0], H[1:], Q) for H, Q in zip([work(o[0]) for o in ob], [work(Q) for Q in Qs])],
+                                infos_out=infos_w)
+    hp = eng.pschur_hess_batch_([(H[0], H[1:], Q) for H, Q in zip([work(o[0]) for o in op], [work(Q) for Q in Qs])],
+                                infos_out=infos_p)
+    assert infos_w == infos_p == [0] * nb
+    _same_bits(hw, hp, p)
+    assert hw[0].stats.nsweeps > 0 and hp[0].stats.nsweeps > 0
 
 
 # ------------------------------------------------------------------------------------------------

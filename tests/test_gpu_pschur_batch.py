@@ -7,6 +7,7 @@ import re
 import pytest
 
 import batch_cases as bc
+import psd_amd
 
 pytestmark = pytest.mark.gpu
 
@@ -57,3 +58,21 @@ def test_above_the_cap(gpu_engine, lr):
 
 def test_device_resident(gpu_engine):
     bc.case_device_resident(gpu_engine)
+
+
+def test_argument_codes(gpu_engine):
+    bc.case_abi_codes(gpu_engine)
+
+
+def test_groups(monkeypatch):
+    import torch
+
+    torch.cuda.init()
+    monkeypatch.delenv("PSD_BATCH_GROUP", raising=False)
+
+    def make(env):
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        return psd_amd.Engine(device=0)
+
+    bc.case_groups(make)

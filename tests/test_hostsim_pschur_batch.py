@@ -41,6 +41,10 @@ def test_device_entry_and_argument_codes(sim_engine):
     bc.case_dev_abi(sim_engine)
 
 
+def test_argument_codes(sim_engine):
+    bc.case_abi_codes(sim_engine)
+
+
 def test_groups(built, monkeypatch):
     lib = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostsim", "_build", "libpsd_hostsim.so")
     monkeypatch.delenv("PSD_BATCH_GROUP", raising=False)
