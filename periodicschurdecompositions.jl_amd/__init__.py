@@ -102,13 +102,18 @@ class PeriodicSchur:
         return len(self.Ts)
 
 
+def _scaled_values(alpha, beta, alphascale):
+    """values = alpha ./ beta .* 2 .^ alphascale (src/generalized.jl:31-85), for one problem or a batch of them."""
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        return alpha / beta * np.exp2(alphascale.astype(np.float64))
+
+
 class GeneralizedPeriodicSchur(PeriodicSchur):
     """Mirror of `GeneralizedPeriodicSchur` (src/generalized.jl:31-85): eigenvalues in scaled form
     `values = alpha ./ beta .* 2 .^ alphascale`."""
 
     def __init__(self, S, Ts, Z, alpha, beta, alphascale, orientation, schurindex, stats=None, sweeplog=None):
-        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
-            values = alpha / beta * np.exp2(alphascale.astype(np.float64))
+        values = _scaled_values(alpha, beta, alphascale)
         super().__init__(Ts, Z, values, orientation, schurindex, stats, sweeplog)
         self.S = list(S)
         self.alpha, self.beta, self.alphascale = alpha, beta, alphascale
@@ -261,6 +266,56 @@ def _check_square(A):
     return n
 
 
+# What the Float64 and the ComplexF64 batch entries differ by: the ABI prefix, the numpy dtype (torch's has the same
+# name), and how the pschur entries of the family turn away a problem of the other one.
+_Family = collections.namedtuple("_Family", "tag dtype wrong_exc wrong_text")
+_D = _Family("d", np.float64, NotImplementedPSD, "pschur_batch: Float64 only (ComplexF64 problems: zpschur_batch)")
+_Z = _Family("z", np.complex128, TypeError, "zpschur_batch: ComplexF64 only (use pschur_batch for Float64 problems)")
+
+
+_ORD_WRONG = {_D: "ordschur_batch: Float64 only (use ordschur_ per problem for ComplexF64)",
+              _Z: "zordschur_batch: ComplexF64 only (Float64 problems: ordschur_batch)"}
+
+
+def _other_family(fam, cplx, every=False):
+    """Whether matrices (`cplx`: which of them are complex) belong to the other family: a complex one among Float64;
+    among ComplexF64 none complex, or with `every` not all (one complex matrix makes a problem complex: the in-place
+    contract turns the real ones away afterwards)."""
+    return any(cplx) if fam is _D else not (all(cplx) if every else any(cplx))
+
+
+def _eig_alloc(fam, shape, nan=False):
+    """The eigenvalue outputs of a batch call in ABI order, (wr, wi) or (alpha, beta, alphascale); `nan`: pre-filled
+    so that a row the library does not write reads NaN."""
+    if fam is _D:
+        return [np.full(shape, np.nan) if nan else np.zeros(shape), np.zeros(shape)]
+    return [np.full(shape, np.nan if nan else 0.0, dtype=np.complex128), np.ones(shape) if nan else np.zeros(shape),
+            np.zeros(shape, dtype=np.int32)]
+
+
+def _eig_values(eig):
+    """`values` from the eigenvalue arguments of either family."""
+    return eig[0] + 1j * eig[1] if len(eig) == 2 else _scaled_values(*eig)
+
+
+def _dev_blocks(X, fam, policy):
+    """[nb][p][n][n] blocks of column-major matrices from an [nb, p, n, n] tensor: the transpose of each factor,
+    contiguous (as partial_pschur), which is what the device entries return a transposed view of.  `policy`:
+      "copy":              always a fresh copy, the caller's tensor is never modified (pschur);
+      "inplace_if_blocks": a tensor that already is such a view, of the family's dtype, is used as it is and written
+                           IN PLACE; any other layout is copied and stays as it was (ordschur);
+      "readonly":          the blocks are only read: a copy only where .to() / .contiguous() need one (eigvecs)."""
+    import torch
+
+    dt = getattr(torch, np.dtype(fam.dtype).name)
+    if policy == "inplace_if_blocks" and X.dtype == dt and X.transpose(2, 3).is_contiguous():
+        return X.transpose(2, 3)
+    dX = X.to(dt).transpose(2, 3).contiguous()
+    if policy == "copy" and dX.data_ptr() == X.data_ptr():
+        dX = dX.clone()
+    return dX
+
+
 class Engine:
     """One device context (stream + workspace). One call at a time per Engine."""
 
@@ -315,36 +370,27 @@ class Engine:
                                        C.c_double, C.c_int, dp, dp, dp, ip, ip]
         lib.psd_d_checkpsd_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, u8p,
                                            C.c_char, C.c_int, C.c_double, C.c_int, dp, dp, dp, ip, ip]
-        lib.psd_d_pschur_hess_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, dpp, dpp, C.c_int, C.c_int, C.c_int,
-                                                dp, dp, ip, C.POINTER(Stats), ip]
-        lib.psd_d_phessenberg_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, dpp, dp, C.POINTER(Stats), ip]
-        lib.psd_d_pschur_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, dpp, C.c_char, C.c_int, C.c_int, C.c_int,
-                                           dpp, dp, dp, ip, ip, C.POINTER(Stats), ip]
-        lib.psd_d_pschur_batch_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_char, C.c_int,
-                                               C.c_int, C.c_int, C.c_void_p, dp, dp, ip, ip, C.POINTER(Stats), ip]
-        if hasattr(lib, "psd_z_pschur_batch"):  # (tools load builds of earlier commits to time their single calls)
-            lib.psd_z_phessenberg_batch.argtypes = lib.psd_d_phessenberg_batch.argtypes
-            for nm, mats in (("psd_z_pschur_batch", dpp), ("psd_z_pschur_batch_dev", C.c_void_p)):
-                getattr(lib, nm).argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, mats, C.c_char, C.c_int, C.c_int,
-                                             C.c_int, mats, dp, dp, i32p, ip, ip, C.POINTER(Stats), ip]
-            lib.psd_z_pschur_hess_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, dpp, dpp, C.c_int, C.c_int,
-                                                    C.c_int, dp, dp, i32p, ip, C.POINTER(Stats), ip]
-        if hasattr(lib, "psd_z_gpschur_batch"):  # (as above)
-            lib.psd_z_gphessenberg_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, dpp, C.POINTER(C.c_uint8), dpp,
-                                                     C.POINTER(Stats), ip]
-            for nm, mats in (("psd_z_gpschur_batch", dpp), ("psd_z_gpschur_batch_dev", C.c_void_p)):
-                getattr(lib, nm).argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, mats, C.POINTER(C.c_uint8), C.c_char,
-                                             C.c_int, C.c_int, C.c_int, mats, dp, dp, i32p, ip, ip, C.POINTER(Stats), ip]
-            lib.psd_z_gpschur_hess_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, dpp, C.POINTER(C.c_uint8), dpp,
-                                                     C.c_int, C.c_int, C.c_int, dp, dp, i32p, ip, C.POINTER(Stats), ip]
-        for nm, mats in (("psd_d_ordschur_batch", dpp), ("psd_d_ordschur_batch_dev", C.c_void_p)):
-            if hasattr(lib, nm):  # (tools load builds of earlier commits to time their single calls)
-                getattr(lib, nm).argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, mats, mats, C.c_char, C.c_int,
-                                             C.POINTER(C.c_uint8), C.c_int, dp, dp, ip, ip, C.POINTER(Stats), ip]
-        for nm, mats in (("psd_z_ordschur_batch", dpp), ("psd_z_ordschur_batch_dev", C.c_void_p)):
-            if hasattr(lib, nm):  # (as above)
-                getattr(lib, nm).argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, mats, mats, C.c_char, C.c_int,
-                                             C.POINTER(C.c_uint8), C.c_int, dp, dp, i32p, ip, ip, C.POINTER(Stats), ip]
+        # the batch entries: one description per entry family, crossed with d / z (the eigenvalue arguments), plain /
+        # signed (the signature after the factors) and host / dev (how the matrices are passed)
+        sp, head = C.POINTER(Stats), [C.c_void_p, C.c_int, C.c_int, C.c_int]  # (head: ctx, nb, n, p)
+        for t, eig in (("d", [dp, dp]), ("z", [dp, dp, i32p])):
+            sigs = {f"psd_{t}_phessenberg_batch": head + [dpp, dp, sp, ip],
+                    f"psd_{t}_gphessenberg_batch": head + [dpp, u8p, dpp, sp, ip]}
+            for g, sig in (("", []), ("g", [u8p])):
+                sigs[f"psd_{t}_{g}pschur_hess_batch"] = (head + [dpp] + sig + [dpp, C.c_int, C.c_int, C.c_int] + eig
+                                                         + [ip, sp, ip])
+            for dev, mats in (("", dpp), ("_dev", C.c_void_p)):
+                for g, sig in (("", []), ("g", [u8p])):
+                    sigs[f"psd_{t}_{g}pschur_batch{dev}"] = (head + [mats] + sig + [C.c_char, C.c_int, C.c_int, C.c_int,
+                                                                                     mats] + eig + [ip, ip, sp, ip])
+                sigs[f"psd_{t}_ordschur_batch{dev}"] = (head + [mats, mats, C.c_char, C.c_int, u8p, C.c_int] + eig
+                                                        + [ip, ip, sp, ip])
+                sigs[f"psd_{t}_eigvecs_batch{dev}"] = (head + [mats, mats] + eig + [C.c_char, C.c_int, u8p, C.c_int, mats,
+                                                                                    C.c_int, ip, i32p,
+                                                                                    C.POINTER(BevecStats), ip])
+            for nm, sig in sigs.items():
+                if hasattr(lib, nm):  # (tools load builds of earlier commits to time their single calls)
+                    getattr(lib, nm).argtypes = sig
         lib.psd_set_shard.argtypes = [C.c_void_p, C.c_int, C.c_int]
         lib.psd_shard_owned.argtypes = [C.c_void_p, C.c_int, C.c_char, u8p]
         for nm, dev in (("psd_d_partial_pschur", False), ("psd_z_partial_pschur", False),
@@ -382,15 +428,6 @@ class Engine:
             mats = C.c_void_p if dev else dpp
             getattr(lib, nm).argtypes = [C.c_void_p, C.c_int, C.c_int, mats, mats, u8p, C.c_char, C.c_int, u8p, C.c_int,
                                          C.c_int, mats, C.c_int, dp, C.POINTER(EvecStats), ip]
-        for nm, dev in (("psd_d_eigvecs_batch", False), ("psd_d_eigvecs_batch_dev", True)):
-            mats = C.c_void_p if dev else dpp
-            getattr(lib, nm).argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, mats, mats, dp, dp, C.c_char, C.c_int,
-                                         u8p, C.c_int, mats, C.c_int, ip, i32p, C.POINTER(BevecStats), ip]
-        for nm, dev in (("psd_z_eigvecs_batch", False), ("psd_z_eigvecs_batch_dev", True)):
-            if hasattr(lib, nm):  # (tools load builds of earlier commits to time their single calls)
-                mats = C.c_void_p if dev else dpp
-                getattr(lib, nm).argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, mats, mats, dp, dp, i32p, C.c_char,
-                                             C.c_int, u8p, C.c_int, mats, C.c_int, ip, i32p, C.POINTER(BevecStats), ip]
         self.ctx = C.c_void_p()
         rc = lib.psd_create(C.byref(self.ctx), device)
         if rc != 0:
@@ -806,89 +843,217 @@ class Engine:
             return PeriodicSchur(Ts, Zr, lam, "L", p, st, slog)
         return PeriodicSchur(H, Z, lam, "R", 1, st, slog)
 
-    def pschur_hess_batch_(self, problems, wantT=True, wantZ=True, maxitfac=30, infos_out=None):
-        """pschur!(H1, Hs; wantT, wantZ, Q, maxitfac) (src/PeriodicSchurDecompositions.jl:322-330) for a list of
-        problems of equal shape in ONE call (psd_d_pschur_hess_batch: what src/krylov.jl:575-592,800-829 issues one
-        by one).  `problems`: list of (H1, Hs) or (H1, Hs, Q); matrices are overwritten.  Returns a list of
-        PeriodicSchur; a problem that fails to converge raises like the single call, after all have run — the other
-        problems of the batch are complete then (a failure ends only the problem it occurs in).  `infos_out`: a list
-        that receives the per-problem info codes instead (nothing is raised for a failed problem then)."""
-        nb = len(problems)
-        if nb == 0:
-            return []
-        Hall, Qall = [], []
-        n = problems[0][0].shape[0]
-        p = len(problems[0][1]) + 1
-        for pr in problems:
-            H = [pr[0]] + list(pr[1])
-            if len(H) != p or _check_square(H) != n:
-                raise DimensionMismatch("the problems of a batch must have equal order and period")
-            self._as_work(H)
-            Hall += H
-            if wantZ:
-                Q = list(pr[2]) if len(pr) > 2 and pr[2] is not None else [np.asfortranarray(np.eye(n)) for _ in range(p)]
-                self._as_work(Q)
-                Qall += Q
-        wr = np.zeros((nb, n))
-        wi = np.zeros((nb, n))
-        infos = (C.c_int * nb)()
-        st = Stats()
-        info = C.c_int(0)
-        dp = C.POINTER(C.c_double)
-        self.lib.psd_d_pschur_hess_batch(self.ctx, nb, n, p, self._ptrs(Hall), self._ptrs(Qall) if wantZ else None,
-                                         int(wantT), int(wantZ), int(maxitfac), wr.ctypes.data_as(dp),
-                                         wi.ctypes.data_as(dp), infos, C.byref(st), C.byref(info))
-        if info.value < 0 or info.value >= INFO_NOTIMPL:
-            self._raise(info.value)
-        out = []
-        for q in range(nb):
-            Z = Qall[q * p:(q + 1) * p] if wantZ else []
-            out.append(PeriodicSchur(Hall[q * p:(q + 1) * p], Z, wr[q] + 1j * wi[q], "R", 1, st))
-        if infos_out is not None:
-            infos_out[:] = [int(infos[q]) for q in range(nb)]
-            return out
-        for q in range(nb):
-            self._raise(infos[q])
-        return out
-
-    def _batch_shape(self, problems):
-        """(n, p, flat list of factors) of a batch of general problems; DimensionMismatch unless all have one shape."""
-        n = p = None
+    # ---- The batch family (psd_?_*_batch): many small problems of one shape per call.  The Float64 and the ComplexF64
+    # entries (in the iteration 32 problems side by side / one wavefront per problem) share the wrappers below; what
+    # differs between them is an argument: the `_Family`, the text that turns the other family away, the rule for a
+    # fatal call-wide code (`_batch_finish`), the copy policy of device tensors (`_dev_blocks`).
+    def _batch_factors(self, fam, problems):
+        """(n, p, flat list of factors) of a batch of general problems; DimensionMismatch unless all have one shape, the
+        family's exception for a problem of the other one."""
+        shape = None
         flat = []
         for A in problems:
             A = list(A)
             if len(A) < 1:
                 raise DimensionMismatch("empty sequence")
-            if self._is_complex(A):
-                raise NotImplementedPSD("pschur_batch: Float64 only (ComplexF64 problems: zpschur_batch)")
-            nq = _check_square(A)
-            if n is None:
-                n, p = nq, len(A)
-            if nq != n or len(A) != p:
-                raise DimensionMismatch("the problems of a batch must have equal order and period")
+            if _other_family(fam, [np.iscomplexobj(a) for a in A]):
+                raise fam.wrong_exc(fam.wrong_text)
+            shape = self._batch_shape(A, shape)
             flat += A
-        return n, p, flat
+        return (*shape, flat)
 
-    def phessenberg_batch_(self, problems):
-        """phessenberg!(A) (src/PeriodicSchurDecompositions.jl:213-259) for a list of problems of equal shape in ONE call
-        (psd_d_phessenberg_batch).  `problems`: list of lists of p writable Fortran-ordered matrices, overwritten
-        LAPACK-style.  Returns a list of (H list, tau[p][n]) like phessenberg_, and the Stats of the call."""
+    @staticmethod
+    def _batch_shape(A, shape):
+        """(n, p) of the factors A of one problem, which must be `shape` (None: the first problem of a batch)."""
+        nq = _check_square(A)
+        if shape is not None and (nq, len(A)) != shape:
+            raise DimensionMismatch("the problems of a batch must have equal order and period")
+        return nq, len(A)
+
+    def _batch_hess(self, fam, problems, wantZ, wrong):
+        """(n, p, flat H, flat Q) of a batch of Hessenberg-triangular problems (H1, Hs[, Q]), all work arrays; a problem
+        without Q gets the identity.  `wrong`: the exception for a problem of the other family (None: left to the
+        in-place contract)."""
+        Hall, Qall = [], []
+        shape = None
+        for pr in problems:
+            H = [pr[0]] + list(pr[1])
+            shape = n, p = self._batch_shape(H, shape)
+            if wrong is not None and _other_family(fam, [np.iscomplexobj(h) for h in H]):
+                raise wrong
+            self._as_work(H, fam.dtype)
+            Hall += H
+            if wantZ:
+                Q = (list(pr[2]) if len(pr) > 2 and pr[2] is not None
+                     else [np.asfortranarray(np.eye(n, dtype=fam.dtype)) for _ in range(p)])
+                self._as_work(Q, fam.dtype)
+                Qall += Q
+        return n, p, Hall, Qall
+
+    def _batch_copies(self, fam, wrong, problems, every=False):
+        """The work copies behind the copying forms: Fortran-ordered copies of the factors of every problem, a list of
+        matrices or a PeriodicSchur (copied with its Z and values); `wrong` for a problem of the other family."""
+        def mats(A):
+            return [np.array(a, dtype=fam.dtype, order="F", copy=True) for a in A]
+
+        work = []
+        for A in problems:
+            dec = isinstance(A, PeriodicSchur)
+            if _other_family(fam, [np.iscomplexobj(a) for a in (A.Ts if dec else A)], every):
+                raise wrong
+            if dec:
+                cp = copy.copy(A)
+                cp.Ts, cp.Z, cp.values = mats(A.Ts), mats(A.Z), np.array(A.values, copy=True)
+            work.append(cp if dec else mats(A))
+        return work
+
+    def _dev_batch(self, fam, name, wrong, T, *Z, mixed=False):
+        """(nb, p, n) of a device batch: one [nb, p, n, n] torch tensor, or T with Z (None: no Schur vectors) of the
+        same shape.  `wrong`: the exception for tensors of the other family; `mixed`: a complex tensor next to a real
+        one is the error of eigvecs instead."""
+        ts = [T] + [z for z in Z if z is not None]
+        if T.dim() != 4 or T.shape[2] != T.shape[3] or any(z.shape != T.shape for z in ts[1:]):
+            raise DimensionMismatch("a device batch is [nb, p, n, n] tensors T and Z of square factors" if Z else
+                                    "a device batch is one [nb, p, n, n] tensor of square factors")
+        cplx = [t.is_complex() for t in ts]
+        if _other_family(fam, cplx, every=not mixed):
+            raise wrong
+        if mixed and not all(cplx) and fam is _Z:
+            raise TypeError("eigvecs: the factors T and the Schur vectors Z must be all real or all complex")
+        if not all(t.is_cuda for t in ts):
+            raise TypeError(f"device-resident {name} needs GPU tensors (use a list of PeriodicSchur for host input)" if Z
+                            else f"device-resident {name} needs a GPU tensor (use lists of numpy arrays for host input)")
+        return T.shape[0], T.shape[1], T.shape[2]
+
+    def _batch_finish(self, info, infos, infos_out, raiser, strict, result):
+        """The end of every batch call.  A fatal call-wide code `info` raises: always with `strict` (the Float64 pschur
+        entries and every ordschur entry), otherwise only when no problem carries that code (the ComplexF64 pschur
+        entries: a code that a problem carries is that problem's, the others are complete).  Then `result()` builds
+        what the call returns, and the per-problem codes `infos` go to `infos_out`, or the first non-zero one raises
+        through `raiser`."""
+        codes = list(infos)
+        if (info < 0 or info >= INFO_NOTIMPL) and (strict or info not in codes):
+            self._raise(info)
+        out = result()
+        if infos_out is not None:
+            infos_out[:] = codes
+            return out
+        for code in codes:
+            raiser(code)
+        return out
+
+    @staticmethod
+    def _batch_results(general, S, nb, p, Tall, Zall, eig, orient, si, st):
+        """The decompositions of a pschur batch call from its flat factor lists: PeriodicSchur, or with `general`
+        GeneralizedPeriodicSchur of signature S (None: all true)."""
+        if general:
+            S = [True] * p if S is None else S
+            return [GeneralizedPeriodicSchur(S, Tall[q * p:(q + 1) * p], Zall[q * p:(q + 1) * p], eig[0][q], eig[1][q],
+                                             eig[2][q], orient, si, st) for q in range(nb)]
+        values = _eig_values(eig)  # (each problem gets a row as an array of its own, not a view of the batch's)
+        return [PeriodicSchur(Tall[q * p:(q + 1) * p], Zall[q * p:(q + 1) * p], values[q].copy(), orient, si, st)
+                for q in range(nb)]
+
+    def _phessenberg_batch_(self, fam, problems):
         nb = len(problems)
         if nb == 0:
             return [], Stats()
-        n, p, flat = self._batch_shape(problems)
-        self._as_work(flat)
-        tau = np.zeros((nb, p, n))
+        n, p, flat = self._batch_factors(fam, problems)
+        self._as_work(flat, fam.dtype)
+        tau = np.zeros((nb, p, n), dtype=fam.dtype)
         st = Stats()
         info = C.c_int(0)
-        self.lib.psd_d_phessenberg_batch(self.ctx, nb, n, p, self._ptrs(flat), tau.ctypes.data_as(C.POINTER(C.c_double)),
-                                         C.byref(st), C.byref(info))
+        getattr(self.lib, f"psd_{fam.tag}_phessenberg_batch")(self.ctx, nb, n, p, self._ptrs(flat),
+                                                              *self._evec_ptrs([tau]), C.byref(st), C.byref(info))
         self._raise(info.value)
         out = []
         for q in range(nb):
             A = flat[q * p:(q + 1) * p]
             out.append(([np.triu(a, -1 if j == 0 else 0) for j, a in enumerate(A)], tau[q]))
         return out, st
+
+    def _pschur_batch_call(self, fam, Sarr, dev, nb, n, p, A, Z, orient, wantT, wantZ, maxitfac, infos_out, result):
+        """psd_?_[g]pschur_batch[_dev] on packed factors: A and Z flat lists of work arrays, or with `dev` device
+        blocks.  `result(eig, schurindex, stats)` builds what the call returns from the eigenvalue outputs."""
+        ptrs = (lambda X: C.c_void_p(X.data_ptr())) if dev else self._ptrs
+        eig = _eig_alloc(fam, (nb, n))
+        infos, si, st, info = (C.c_int * nb)(), C.c_int(0), Stats(), C.c_int(0)
+        fn = getattr(self.lib, f"psd_{fam.tag}_{'' if Sarr is None else 'g'}pschur_batch{'_dev' if dev else ''}")
+        fn(self.ctx, nb, n, p, ptrs(A), *([] if Sarr is None else [Sarr]), orient.encode(), int(wantT), int(wantZ),
+           int(maxitfac), ptrs(Z) if wantZ else None, *self._evec_ptrs(eig), infos, C.byref(si), C.byref(st),
+           C.byref(info))
+        return self._batch_finish(info.value, infos, infos_out, self._raise, fam is _D,
+                                  lambda: result(eig, si.value, st))
+
+    def _pschur_batch_(self, fam, name, problems, S, lr, wantZ, wantT, maxitfac, infos_out):
+        """pschur_batch_ / zpschur_batch_ / zgpschur_batch_ (`S` None: all true, the entry without a signature)."""
+        orient = char_lr(lr)
+        if hasattr(problems, "data_ptr"):
+            return self._pschur_batch_dev(fam, name, problems, S, orient, wantZ, wantT, maxitfac, infos_out)
+        nb = len(problems)
+        if nb == 0:
+            if infos_out is not None:
+                infos_out[:] = []
+            return []
+        n, p, A = self._batch_factors(fam, problems)
+        Sarr = None
+        if S is not None:
+            S, Sarr = self._zgbatch_sig(S, p, orient)
+        self._as_work(A, fam.dtype)
+        Z = [np.zeros((n, n), dtype=fam.dtype, order="F") for _ in range(nb * p)] if wantZ else []
+        return self._pschur_batch_call(
+            fam, Sarr, False, nb, n, p, A, Z, orient, wantT, wantZ, maxitfac, infos_out,
+            lambda eig, si, st: self._batch_results(S is not None, S, nb, p, A, Z, eig, orient, si, st))
+
+    def _pschur_batch_dev(self, fam, name, dA, S, orient, wantZ, wantT, maxitfac, infos_out):
+        import torch
+
+        wrong = fam.wrong_exc(fam.wrong_text if S is None else "zgpschur_batch: ComplexF64 only")
+        nb, p, n = self._dev_batch(fam, name, wrong, dA)
+        Sarr = None
+        if S is not None:
+            S, Sarr = self._zgbatch_sig(S, p, orient)
+        if nb == 0:
+            if infos_out is not None:
+                infos_out[:] = []
+            return dA.clone(), (dA.clone() if wantZ else None), np.zeros((0, n), dtype=complex), Stats()
+        dT = _dev_blocks(dA, fam, "copy")
+        dZ = torch.zeros_like(dT) if wantZ else None
+        torch.cuda.synchronize(dA.device)
+        return self._pschur_batch_call(
+            fam, Sarr, True, nb, n, p, dT, dZ, orient, wantT, wantZ, maxitfac, infos_out,
+            lambda eig, si, st: (dT.transpose(2, 3), (dZ.transpose(2, 3) if wantZ else None), _eig_values(eig), st))
+
+    def _pschur_hess_batch_(self, fam, problems, S, wrong, wantT, wantZ, maxitfac, infos_out):
+        """The three *_hess_batch_ entries on a non-empty batch (`S` None: no signature argument)."""
+        nb = len(problems)
+        n, p, Hall, Qall = self._batch_hess(fam, problems, wantZ, wrong)
+        sig = [] if S is None else [(C.c_uint8 * p)(*[1 if x else 0 for x in S])]
+        eig = _eig_alloc(fam, (nb, n))
+        infos, st, info = (C.c_int * nb)(), Stats(), C.c_int(0)
+        fn = getattr(self.lib, f"psd_{fam.tag}_{'' if S is None else 'g'}pschur_hess_batch")
+        fn(self.ctx, nb, n, p, self._ptrs(Hall), *sig, self._ptrs(Qall) if wantZ else None, int(wantT), int(wantZ),
+           int(maxitfac), *self._evec_ptrs(eig), infos, C.byref(st), C.byref(info))
+        return self._batch_finish(info.value, infos, infos_out, self._raise, fam is _D,
+                                  lambda: self._batch_results(fam is _Z, S, nb, p, Hall, Qall, eig, "R", 1, st))
+
+    def pschur_hess_batch_(self, problems, wantT=True, wantZ=True, maxitfac=30, infos_out=None):
+        """pschur!(H1, Hs; wantT, wantZ, Q, maxitfac) (src/PeriodicSchurDecompositions.jl:322-330) for a list of
+        problems of equal shape in ONE call (psd_d_pschur_hess_batch: what src/krylov.jl:575-592,800-829 issues one
+        by one).  `problems`: list of (H1, Hs) or (H1, Hs, Q); matrices are overwritten.  Returns a list of
+        PeriodicSchur; a problem that fails to converge raises like the single call, after all have run — the other
+        problems of the batch are complete then (a failure ends only the problem it occurs in).  `infos_out`: a list
+        that receives the per-problem info codes instead (nothing is raised for a failed problem then; an empty batch
+        leaves it as it is)."""
+        if len(problems) == 0:
+            return []
+        return self._pschur_hess_batch_(_D, problems, None, None, wantT, wantZ, maxitfac, infos_out)
+
+    def phessenberg_batch_(self, problems):
+        """phessenberg!(A) (src/PeriodicSchurDecompositions.jl:213-259) for a list of problems of equal shape in ONE call
+        (psd_d_phessenberg_batch).  `problems`: list of lists of p writable Fortran-ordered matrices, overwritten
+        LAPACK-style.  Returns a list of (H list, tau[p][n]) like phessenberg_, and the Stats of the call."""
+        return self._phessenberg_batch_(_D, problems)
 
     def pschur_batch_(self, problems, lr="R", wantZ=True, wantT=True, maxitfac=30, infos_out=None):
         """pschur!(A, lr; wantZ, wantT, maxitfac) (src/PeriodicSchurDecompositions.jl:120-152) for many small problems of
@@ -904,109 +1069,19 @@ class Engine:
         A problem that fails to converge raises like the single call, after all have run — the others are complete
         then.  `infos_out`: a list that receives the per-problem info codes instead (nothing is raised for a failed
         problem then)."""
-        orient = char_lr(lr)
-        if hasattr(problems, "data_ptr"):
-            return self._pschur_batch_dev(problems, orient, wantZ, wantT, maxitfac, infos_out)
-        nb = len(problems)
-        if nb == 0:
-            if infos_out is not None:
-                infos_out[:] = []
-            return []
-        n, p, flat = self._batch_shape(problems)
-        self._as_work(flat)
-        Zall = [np.zeros((n, n), order="F") for _ in range(nb * p)] if wantZ else []
-        wr = np.zeros((nb, n))
-        wi = np.zeros((nb, n))
-        infos = (C.c_int * nb)()
-        si = C.c_int(0)
-        st = Stats()
-        info = C.c_int(0)
-        dp = C.POINTER(C.c_double)
-        self.lib.psd_d_pschur_batch(self.ctx, nb, n, p, self._ptrs(flat), orient.encode(), int(wantT), int(wantZ),
-                                    int(maxitfac), self._ptrs(Zall) if wantZ else None, wr.ctypes.data_as(dp),
-                                    wi.ctypes.data_as(dp), infos, C.byref(si), C.byref(st), C.byref(info))
-        if info.value < 0 or info.value >= INFO_NOTIMPL:
-            self._raise(info.value)
-        out = []
-        for q in range(nb):
-            Z = Zall[q * p:(q + 1) * p] if wantZ else []
-            out.append(PeriodicSchur(flat[q * p:(q + 1) * p], Z, wr[q] + 1j * wi[q], orient, si.value, st))
-        if infos_out is not None:
-            infos_out[:] = [int(infos[q]) for q in range(nb)]
-            return out
-        for q in range(nb):
-            self._raise(infos[q])
-        return out
+        return self._pschur_batch_(_D, "pschur_batch", problems, None, lr, wantZ, wantT, maxitfac, infos_out)
 
     def pschur_batch(self, problems, lr="R", **kw):
         """Copying form of pschur_batch_: the factors are left untouched."""
-        if hasattr(problems, "data_ptr"):
-            return self.pschur_batch_(problems, lr, **kw)
-        for A in problems:
-            if self._is_complex(list(A)):
-                raise NotImplementedPSD("pschur_batch: Float64 only (ComplexF64 problems: zpschur_batch)")
-        work = [[np.array(a, dtype=np.float64, order="F", copy=True) for a in A] for A in problems]
-        return self.pschur_batch_(work, lr, **kw)
-
-    # ---- ComplexF64 batch family (psd_z_*_batch): one wavefront per problem in the iteration
-    def _zbatch_shape(self, problems):
-        """(n, p, flat list of factors) of a batch of complex problems; DimensionMismatch unless all have one shape,
-        TypeError for a problem without a complex factor (the Float64 family is pschur_batch)."""
-        n = p = None
-        flat = []
-        for A in problems:
-            A = list(A)
-            if len(A) < 1:
-                raise DimensionMismatch("empty sequence")
-            if not self._is_complex(A):
-                raise TypeError("zpschur_batch: ComplexF64 only (use pschur_batch for Float64 problems)")
-            nq = _check_square(A)
-            if n is None:
-                n, p = nq, len(A)
-            if nq != n or len(A) != p:
-                raise DimensionMismatch("the problems of a batch must have equal order and period")
-            flat += A
-        return n, p, flat
-
-    def _zbatch_finish(self, nb, n, p, Tall, Zall, alpha, beta, sc, infos, orient, si, st, info, infos_out,
-                       general=False, S=None):
-        if info.value < 0 or info.value >= INFO_NOTIMPL:
-            if not any(int(infos[q]) == info.value for q in range(nb)):  # (a call-wide code: nothing is complete)
-                self._raise(info.value)
-        out = []
-        for q in range(nb):
-            g = GeneralizedPeriodicSchur([True] * p if S is None else list(S), Tall[q * p:(q + 1) * p],
-                                         Zall[q * p:(q + 1) * p] if Zall else [],
-                                         alpha[q], beta[q], sc[q], orient, si, st)
-            out.append(g if general else PeriodicSchur(g.Ts, g.Z, g.values, orient, si, st))
-        if infos_out is not None:
-            infos_out[:] = [int(infos[q]) for q in range(nb)]
-            return out
-        for q in range(nb):
-            self._raise(infos[q])
-        return out
+        if not hasattr(problems, "data_ptr"):
+            problems = self._batch_copies(_D, _D.wrong_exc(_D.wrong_text), problems)
+        return self.pschur_batch_(problems, lr, **kw)
 
     def zphessenberg_batch_(self, problems):
         """phessenberg!(A) for a list of ComplexF64 problems of equal shape in ONE call (psd_z_phessenberg_batch): one
         workgroup reduces one problem.  `problems`: list of lists of p writable Fortran-ordered complex128 matrices,
         overwritten LAPACK-style.  Returns a list of (H list, tau[p][n]) like phessenberg_, and the Stats of the call."""
-        nb = len(problems)
-        if nb == 0:
-            return [], Stats()
-        n, p, flat = self._zbatch_shape(problems)
-        self._as_work(flat, np.complex128)
-        tau = np.zeros((nb, p, n), dtype=np.complex128)
-        st = Stats()
-        info = C.c_int(0)
-        self.lib.psd_z_phessenberg_batch(self.ctx, nb, n, p, self._ptrs(flat),
-                                         tau.view(np.float64).ctypes.data_as(C.POINTER(C.c_double)), C.byref(st),
-                                         C.byref(info))
-        self._raise(info.value)
-        out = []
-        for q in range(nb):
-            A = flat[q * p:(q + 1) * p]
-            out.append(([np.triu(a, -1 if j == 0 else 0) for j, a in enumerate(A)], tau[q]))
-        return out, st
+        return self._phessenberg_batch_(_Z, problems)
 
     def zpschur_batch_(self, problems, lr="R", wantZ=True, wantT=True, maxitfac=30, infos_out=None, S=None):
         """pschur!(A::Vector{Matrix{ComplexF64}}, lr; wantZ, wantT, maxitfac) for many small problems of equal shape in
@@ -1021,127 +1096,26 @@ class Engine:
         A problem that fails to converge raises like the single call, after all have run — the others are complete
         then.  `infos_out`: a list that receives the per-problem info codes instead (nothing is raised for a failed
         problem then)."""
-        if S is not None:
-            return self.zgpschur_batch_(problems, S, lr, wantZ=wantZ, wantT=wantT, maxitfac=maxitfac, infos_out=infos_out)
-        orient = char_lr(lr)
-        if hasattr(problems, "data_ptr"):
-            return self._zpschur_batch_dev(problems, orient, wantZ, wantT, maxitfac, infos_out)
-        nb = len(problems)
-        if nb == 0:
-            if infos_out is not None:
-                infos_out[:] = []
-            return []
-        n, p, flat = self._zbatch_shape(problems)
-        self._as_work(flat, np.complex128)
-        Zall = [np.zeros((n, n), dtype=np.complex128, order="F") for _ in range(nb * p)] if wantZ else []
-        alpha = np.zeros((nb, n), dtype=np.complex128)
-        beta = np.zeros((nb, n))
-        sc = np.zeros((nb, n), dtype=np.int32)
-        infos = (C.c_int * nb)()
-        si = C.c_int(0)
-        st = Stats()
-        info = C.c_int(0)
-        dp = C.POINTER(C.c_double)
-        self.lib.psd_z_pschur_batch(self.ctx, nb, n, p, self._ptrs(flat), orient.encode(), int(wantT), int(wantZ),
-                                    int(maxitfac), self._ptrs(Zall) if wantZ else None,
-                                    alpha.view(np.float64).ctypes.data_as(dp), beta.ctypes.data_as(dp),
-                                    sc.ctypes.data_as(C.POINTER(C.c_int32)), infos, C.byref(si), C.byref(st),
-                                    C.byref(info))
-        return self._zbatch_finish(nb, n, p, flat, Zall, alpha, beta, sc, infos, orient, si.value, st, info, infos_out)
+        name = "zpschur_batch" if S is None else "zgpschur_batch"
+        return self._pschur_batch_(_Z, name, problems, S, lr, wantZ, wantT, maxitfac, infos_out)
 
     def zpschur_batch(self, problems, lr="R", **kw):
         """Copying form of zpschur_batch_: the factors are left untouched."""
-        if hasattr(problems, "data_ptr"):
-            return self.zpschur_batch_(problems, lr, **kw)
-        for A in problems:
-            if not self._is_complex(list(A)):
-                raise TypeError("zpschur_batch: ComplexF64 only (use pschur_batch for Float64 problems)")
-        work = [[np.array(a, dtype=np.complex128, order="F", copy=True) for a in A] for A in problems]
-        return self.zpschur_batch_(work, lr, **kw)
+        if not hasattr(problems, "data_ptr"):
+            problems = self._batch_copies(_Z, _Z.wrong_exc(_Z.wrong_text), problems)
+        return self.zpschur_batch_(problems, lr, **kw)
 
     def zpschur_hess_batch_(self, problems, wantT=True, wantZ=True, maxitfac=30, infos_out=None):
         """pschur!(H1, Hs, S; wantT, wantZ, Q, maxitfac) for ComplexF64 with S all true (src/generalized.jl:166-175) for a
         list of Hessenberg-triangular problems of equal shape in ONE call (psd_z_pschur_hess_batch).  `problems`: list
         of (H1, Hs) or (H1, Hs, Q); matrices are overwritten.  Returns a list of GeneralizedPeriodicSchur, as zpschur_hess_
         does; failures and `infos_out` as zpschur_batch_."""
-        nb = len(problems)
-        if nb == 0:
+        if len(problems) == 0:
             if infos_out is not None:
                 infos_out[:] = []
             return []
-        Hall, Qall = [], []
-        n = problems[0][0].shape[0]
-        p = len(problems[0][1]) + 1
-        for pr in problems:
-            H = [pr[0]] + list(pr[1])
-            if len(H) != p or _check_square(H) != n:
-                raise DimensionMismatch("the problems of a batch must have equal order and period")
-            if not self._is_complex(H):
-                raise TypeError("zpschur_hess_batch_: ComplexF64 only (use pschur_hess_batch_ for Float64 problems)")
-            self._as_work(H, np.complex128)
-            Hall += H
-            if wantZ:
-                Q = (list(pr[2]) if len(pr) > 2 and pr[2] is not None
-                     else [np.asfortranarray(np.eye(n, dtype=np.complex128)) for _ in range(p)])
-                self._as_work(Q, np.complex128)
-                Qall += Q
-        alpha = np.zeros((nb, n), dtype=np.complex128)
-        beta = np.zeros((nb, n))
-        sc = np.zeros((nb, n), dtype=np.int32)
-        infos = (C.c_int * nb)()
-        st = Stats()
-        info = C.c_int(0)
-        dp = C.POINTER(C.c_double)
-        self.lib.psd_z_pschur_hess_batch(self.ctx, nb, n, p, self._ptrs(Hall), self._ptrs(Qall) if wantZ else None,
-                                         int(wantT), int(wantZ), int(maxitfac),
-                                         alpha.view(np.float64).ctypes.data_as(dp), beta.ctypes.data_as(dp),
-                                         sc.ctypes.data_as(C.POINTER(C.c_int32)), infos, C.byref(st), C.byref(info))
-        return self._zbatch_finish(nb, n, p, Hall, Qall, alpha, beta, sc, infos, "R", 1, st, info, infos_out, general=True)
-
-    def _zpschur_batch_dev(self, dA, orient, wantZ, wantT, maxitfac, infos_out):
-        import torch
-
-        if dA.dim() != 4 or dA.shape[2] != dA.shape[3]:
-            raise DimensionMismatch("a device batch is one [nb, p, n, n] tensor of square factors")
-        if not dA.is_complex():
-            raise TypeError("zpschur_batch: ComplexF64 only (use pschur_batch for Float64 problems)")
-        if not dA.is_cuda:
-            raise TypeError("device-resident zpschur_batch needs a GPU tensor (use lists of numpy arrays for host input)")
-        nb, p, n = dA.shape[0], dA.shape[1], dA.shape[2]
-        if nb == 0:
-            if infos_out is not None:
-                infos_out[:] = []
-            return dA.clone(), (dA.clone() if wantZ else None), np.zeros((0, n), dtype=complex), Stats()
-        # [nb][p][n][n] blocks of column-major matrices: the transpose of each factor, contiguous; always a copy
-        dT = dA.to(torch.complex128).transpose(2, 3).contiguous()
-        if dT.data_ptr() == dA.data_ptr():
-            dT = dT.clone()
-        dZ = torch.zeros_like(dT) if wantZ else None
-        alpha = np.zeros((nb, n), dtype=np.complex128)
-        beta = np.zeros((nb, n))
-        sc = np.zeros((nb, n), dtype=np.int32)
-        infos = (C.c_int * nb)()
-        si = C.c_int(0)
-        st = Stats()
-        info = C.c_int(0)
-        dp = C.POINTER(C.c_double)
-        torch.cuda.synchronize(dA.device)
-        self.lib.psd_z_pschur_batch_dev(self.ctx, nb, n, p, C.c_void_p(dT.data_ptr()), orient.encode(), int(wantT),
-                                        int(wantZ), int(maxitfac), C.c_void_p(dZ.data_ptr()) if wantZ else None,
-                                        alpha.view(np.float64).ctypes.data_as(dp), beta.ctypes.data_as(dp),
-                                        sc.ctypes.data_as(C.POINTER(C.c_int32)), infos, C.byref(si), C.byref(st),
-                                        C.byref(info))
-        if info.value < 0 or info.value >= INFO_NOTIMPL:
-            if not any(int(infos[q]) == info.value for q in range(nb)):
-                self._raise(info.value)
-        if infos_out is not None:
-            infos_out[:] = [int(infos[q]) for q in range(nb)]
-        else:
-            for q in range(nb):
-                self._raise(infos[q])
-        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
-            values = alpha / beta * np.exp2(sc.astype(np.float64))  # (as GeneralizedPeriodicSchur)
-        return dT.transpose(2, 3), (dZ.transpose(2, 3) if wantZ else None), values, st
+        wrong = TypeError("zpschur_hess_batch_: ComplexF64 only (use pschur_hess_batch_ for Float64 problems)")
+        return self._pschur_hess_batch_(_Z, problems, None, wrong, wantT, wantZ, maxitfac, infos_out)
 
     # ---- ComplexF64 batch family with a signed signature (psd_z_gp*_batch): gpschur(As, Bs) for many small problems
     def _zgbatch_sig(self, S, p, orient):
@@ -1162,7 +1136,7 @@ class Engine:
         nb = len(problems)
         if nb == 0:
             return [], Stats()
-        n, p, flat = self._zbatch_shape(problems)
+        n, p, flat = self._batch_factors(_Z, problems)
         self._as_work(flat, np.complex128)
         S, Sarr = self._zgbatch_sig(S, p, "R")
         Qall = [np.zeros((n, n), dtype=np.complex128, order="F") for _ in range(nb * p)] if wantQ else []
@@ -1182,135 +1156,30 @@ class Engine:
         factors; returns a list of GeneralizedPeriodicSchur.  Or one torch complex128 [nb, p, n, n] device tensor
         (device-resident entry, psd_z_gpschur_batch_dev; the input is not modified): returns (T, Z, values, stats).
         An all-true `S` runs the path of zpschur_batch_ (the same bits).  Failures and `infos_out` as zpschur_batch_."""
-        orient = char_lr(lr)
-        if hasattr(problems, "data_ptr"):
-            return self._zgpschur_batch_dev(problems, S, orient, wantZ, wantT, maxitfac, infos_out)
-        nb = len(problems)
-        if nb == 0:
-            if infos_out is not None:
-                infos_out[:] = []
-            return []
-        n, p, flat = self._zbatch_shape(problems)
-        S, Sarr = self._zgbatch_sig(S, p, orient)
-        self._as_work(flat, np.complex128)
-        Zall = [np.zeros((n, n), dtype=np.complex128, order="F") for _ in range(nb * p)] if wantZ else []
-        alpha = np.zeros((nb, n), dtype=np.complex128)
-        beta = np.zeros((nb, n))
-        sc = np.zeros((nb, n), dtype=np.int32)
-        infos = (C.c_int * nb)()
-        si = C.c_int(0)
-        st = Stats()
-        info = C.c_int(0)
-        dp = C.POINTER(C.c_double)
-        self.lib.psd_z_gpschur_batch(self.ctx, nb, n, p, self._ptrs(flat), Sarr, orient.encode(), int(wantT), int(wantZ),
-                                     int(maxitfac), self._ptrs(Zall) if wantZ else None,
-                                     alpha.view(np.float64).ctypes.data_as(dp), beta.ctypes.data_as(dp),
-                                     sc.ctypes.data_as(C.POINTER(C.c_int32)), infos, C.byref(si), C.byref(st),
-                                     C.byref(info))
-        return self._zbatch_finish(nb, n, p, flat, Zall, alpha, beta, sc, infos, orient, si.value, st, info, infos_out,
-                                   general=True, S=S)
+        return self._pschur_batch_(_Z, "zgpschur_batch", problems, S, lr, wantZ, wantT, maxitfac, infos_out)
 
     def zgpschur_batch(self, problems, S, lr="R", **kw):
         """Copying form of zgpschur_batch_: the factors are left untouched."""
-        if hasattr(problems, "data_ptr"):
-            return self.zgpschur_batch_(problems, S, lr, **kw)
-        for A in problems:
-            if not self._is_complex(list(A)):
-                raise TypeError("zgpschur_batch: ComplexF64 only")
-        work = [[np.array(a, dtype=np.complex128, order="F", copy=True) for a in A] for A in problems]
-        return self.zgpschur_batch_(work, S, lr, **kw)
+        if not hasattr(problems, "data_ptr"):
+            problems = self._batch_copies(_Z, TypeError("zgpschur_batch: ComplexF64 only"), problems)
+        return self.zgpschur_batch_(problems, S, lr, **kw)
 
     def zgpschur_hess_batch_(self, problems, S, wantT=True, wantZ=True, maxitfac=30, infos_out=None):
         """pschur!(H1, Hs, S; wantT, wantZ, Q, maxitfac) for ComplexF64 (src/generalized.jl:166-175) for a list of
         Hessenberg-triangular problems of equal shape and ONE signature in ONE call (psd_z_gpschur_hess_batch).
         `problems`: list of (H1, Hs) or (H1, Hs, Q); matrices are overwritten.  Returns a list of
         GeneralizedPeriodicSchur, as zpschur_hess_ does; failures and `infos_out` as zpschur_batch_."""
-        nb = len(problems)
-        if nb == 0:
+        if len(problems) == 0:
             if infos_out is not None:
                 infos_out[:] = []
             return []
-        Hall, Qall = [], []
-        n = problems[0][0].shape[0]
-        p = len(problems[0][1]) + 1
         S = [bool(x) for x in S]
-        if len(S) != p:
+        if len(S) != len(problems[0][1]) + 1:
             raise DimensionMismatch("S must have one entry per factor")
         if not S[0]:
             raise ValueError("Signature entry S[1] must be true")  # src/generalized.jl:182
-        for pr in problems:
-            H = [pr[0]] + list(pr[1])
-            if len(H) != p or _check_square(H) != n:
-                raise DimensionMismatch("the problems of a batch must have equal order and period")
-            if not self._is_complex(H):
-                raise TypeError("zgpschur_hess_batch_: ComplexF64 only")
-            self._as_work(H, np.complex128)
-            Hall += H
-            if wantZ:
-                Q = (list(pr[2]) if len(pr) > 2 and pr[2] is not None
-                     else [np.asfortranarray(np.eye(n, dtype=np.complex128)) for _ in range(p)])
-                self._as_work(Q, np.complex128)
-                Qall += Q
-        alpha = np.zeros((nb, n), dtype=np.complex128)
-        beta = np.zeros((nb, n))
-        sc = np.zeros((nb, n), dtype=np.int32)
-        infos = (C.c_int * nb)()
-        st = Stats()
-        info = C.c_int(0)
-        dp = C.POINTER(C.c_double)
-        Sarr = (C.c_uint8 * p)(*[1 if x else 0 for x in S])
-        self.lib.psd_z_gpschur_hess_batch(self.ctx, nb, n, p, self._ptrs(Hall), Sarr, self._ptrs(Qall) if wantZ else None,
-                                          int(wantT), int(wantZ), int(maxitfac),
-                                          alpha.view(np.float64).ctypes.data_as(dp), beta.ctypes.data_as(dp),
-                                          sc.ctypes.data_as(C.POINTER(C.c_int32)), infos, C.byref(st), C.byref(info))
-        return self._zbatch_finish(nb, n, p, Hall, Qall, alpha, beta, sc, infos, "R", 1, st, info, infos_out, general=True,
-                                   S=S)
-
-    def _zgpschur_batch_dev(self, dA, S, orient, wantZ, wantT, maxitfac, infos_out):
-        import torch
-
-        if dA.dim() != 4 or dA.shape[2] != dA.shape[3]:
-            raise DimensionMismatch("a device batch is one [nb, p, n, n] tensor of square factors")
-        if not dA.is_complex():
-            raise TypeError("zgpschur_batch: ComplexF64 only")
-        if not dA.is_cuda:
-            raise TypeError("device-resident zgpschur_batch needs a GPU tensor (use lists of numpy arrays for host input)")
-        nb, p, n = dA.shape[0], dA.shape[1], dA.shape[2]
-        S, Sarr = self._zgbatch_sig(S, p, orient)
-        if nb == 0:
-            if infos_out is not None:
-                infos_out[:] = []
-            return dA.clone(), (dA.clone() if wantZ else None), np.zeros((0, n), dtype=complex), Stats()
-        # [nb][p][n][n] blocks of column-major matrices: the transpose of each factor, contiguous; always a copy
-        dT = dA.to(torch.complex128).transpose(2, 3).contiguous()
-        if dT.data_ptr() == dA.data_ptr():
-            dT = dT.clone()
-        dZ = torch.zeros_like(dT) if wantZ else None
-        alpha = np.zeros((nb, n), dtype=np.complex128)
-        beta = np.zeros((nb, n))
-        sc = np.zeros((nb, n), dtype=np.int32)
-        infos = (C.c_int * nb)()
-        si = C.c_int(0)
-        st = Stats()
-        info = C.c_int(0)
-        dp = C.POINTER(C.c_double)
-        torch.cuda.synchronize(dA.device)
-        self.lib.psd_z_gpschur_batch_dev(self.ctx, nb, n, p, C.c_void_p(dT.data_ptr()), Sarr, orient.encode(), int(wantT),
-                                         int(wantZ), int(maxitfac), C.c_void_p(dZ.data_ptr()) if wantZ else None,
-                                         alpha.view(np.float64).ctypes.data_as(dp), beta.ctypes.data_as(dp),
-                                         sc.ctypes.data_as(C.POINTER(C.c_int32)), infos, C.byref(si), C.byref(st),
-                                         C.byref(info))
-        if info.value < 0 or info.value >= INFO_NOTIMPL:
-            if not any(int(infos[q]) == info.value for q in range(nb)):
-                self._raise(info.value)
-        if infos_out is not None:
-            infos_out[:] = [int(infos[q]) for q in range(nb)]
-        else:
-            for q in range(nb):
-                self._raise(infos[q])
-        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
-            values = alpha / beta * np.exp2(sc.astype(np.float64))  # (as GeneralizedPeriodicSchur)
-        return dT.transpose(2, 3), (dZ.transpose(2, 3) if wantZ else None), values, st
+        wrong = TypeError("zgpschur_hess_batch_: ComplexF64 only")
+        return self._pschur_hess_batch_(_Z, problems, S, wrong, wantT, wantZ, maxitfac, infos_out)
 
     def gpschur_batch(self, As_list, Bs_list, **kw):
         """gpschur(As, Bs) (src/generalized.jl:1191-1211) for many pairs of series of equal shape in ONE call: the
@@ -1319,66 +1188,23 @@ class Engine:
         if len(As_list) != len(Bs_list):
             raise DimensionMismatch("one Bs per As")
         cz = lambda m: np.array(m, dtype=np.complex128, order="F", copy=True)  # noqa: E731
-        problems, Ss = [], None
+        problems = []
         for As, Bs in zip(As_list, Bs_list):
             ph = len(As)
             if len(Bs) != ph:
                 raise DimensionMismatch("As and Bs must have the same length")
             ib = 0 if ph == 1 else ph - 2
-            Cs, Sq = [cz(As[ph - 1]), cz(Bs[ib])], [True, False]
+            Cs = [cz(As[ph - 1]), cz(Bs[ib])]
             for j in range(ph - 1, 0, -1):  # j = ph-1 .. 1 (1-based), as gpschur
                 Cs.append(cz(As[j - 1]))
                 jx = ph if j == 1 else j - 1
                 Cs.append(cz(Bs[jx - 1]))
-                Sq += [True, False]
-            if Ss is not None and Sq != Ss:
-                raise DimensionMismatch("the problems of a batch must have equal order and period")
-            Ss = Sq
             problems.append(Cs)
         if not problems:
             return []
-        return self.zgpschur_batch_(problems, Ss, "R", **kw)
+        # (pairs of another length make a problem of another period: turned away with those of another order)
+        return self.zgpschur_batch_(problems, [True, False] * len(As_list[0]), "R", **kw)
 
-    def _pschur_batch_dev(self, dA, orient, wantZ, wantT, maxitfac, infos_out):
-        import torch
-
-        if dA.dim() != 4 or dA.shape[2] != dA.shape[3]:
-            raise DimensionMismatch("a device batch is one [nb, p, n, n] tensor of square factors")
-        if dA.is_complex():
-            raise NotImplementedPSD("pschur_batch: Float64 only (ComplexF64 problems: zpschur_batch)")
-        if not dA.is_cuda:
-            raise TypeError("device-resident pschur_batch needs a GPU tensor (use lists of numpy arrays for host input)")
-        nb, p, n = dA.shape[0], dA.shape[1], dA.shape[2]
-        if nb == 0:
-            if infos_out is not None:
-                infos_out[:] = []
-            return dA.clone(), (dA.clone() if wantZ else None), np.zeros((0, n), dtype=complex), Stats()
-        # [nb][p][n][n] blocks of column-major matrices: the transpose of each factor, contiguous (as partial_pschur);
-        # always a copy, the caller's tensor stays as it is
-        dT = dA.to(torch.float64).transpose(2, 3).contiguous()
-        if dT.data_ptr() == dA.data_ptr():
-            dT = dT.clone()
-        dZ = torch.zeros_like(dT) if wantZ else None
-        wr = np.zeros((nb, n))
-        wi = np.zeros((nb, n))
-        infos = (C.c_int * nb)()
-        si = C.c_int(0)
-        st = Stats()
-        info = C.c_int(0)
-        dp = C.POINTER(C.c_double)
-        torch.cuda.synchronize(dA.device)
-        self.lib.psd_d_pschur_batch_dev(self.ctx, nb, n, p, C.c_void_p(dT.data_ptr()), orient.encode(), int(wantT),
-                                        int(wantZ), int(maxitfac), C.c_void_p(dZ.data_ptr()) if wantZ else None,
-                                        wr.ctypes.data_as(dp), wi.ctypes.data_as(dp), infos, C.byref(si), C.byref(st),
-                                        C.byref(info))
-        if info.value < 0 or info.value >= INFO_NOTIMPL:
-            self._raise(info.value)
-        if infos_out is not None:
-            infos_out[:] = [int(infos[q]) for q in range(nb)]
-        else:
-            for q in range(nb):
-                self._raise(infos[q])
-        return dT.transpose(2, 3), (dZ.transpose(2, 3) if wantZ else None), wr + 1j * wi, st
 
     def ordschur_(self, P, select, wantZ=True, Z=None):
         """LinearAlgebra.ordschur!(P, select; wantZ, Z) — src/ordschur.jl:11-73 (ComplexF64).  Mutates and returns P.
@@ -1426,8 +1252,7 @@ class Engine:
         if 2000 <= iv < 3000:
             raise IllConditionedException(iv - 2000)
         self._raise(iv)
-        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
-            P.values = alpha / beta * np.exp2(sc.astype(np.float64))
+        P.values = _scaled_values(alpha, beta, sc)
         if isinstance(P, GeneralizedPeriodicSchur):
             P.alpha, P.beta, P.alphascale = alpha, beta, sc
         P.stats = st
@@ -1464,8 +1289,7 @@ class Engine:
         if 2000 <= iv < 3000:
             raise IllConditionedException(iv - 2000)
         self._raise(iv)
-        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
-            P.values = alpha / beta * np.exp2(sc.astype(np.float64))
+        P.values = _scaled_values(alpha, beta, sc)
         P.alpha, P.beta, P.alphascale = alpha, beta, sc
         P.stats = st
         return P
@@ -1514,6 +1338,145 @@ class Engine:
         except ValueError:
             raise DimensionMismatch("select must be [nb][n] flags or one row of n: one entry per eigenvalue") from None
 
+    def _batch_decomps(self, fam, name, wrong, problems, needZ, work):
+        """(n, p, orientation, schurindex, flat Ts) of a batch of PeriodicSchur, which must agree in all four and be of
+        the family.  `needZ`: the Schur vectors are required, of the family like the factors, and returned as a flat
+        list too (eigvecs); otherwise they may be missing and are the caller's business (ordschur).  `work`: the factors
+        are returned as they are, for the in-place contract (ordschur mutates); otherwise as read-only Fortran copies
+        (eigvecs never writes the problems).
+
+        Which kinds of factors T and vectors Z each entry turns away (`wrong`: the entry's own exception; "mixed": the
+        TypeError of the single eigvecs call; otherwise the problem goes on, to the in-place contract for ordschur):
+                            T real, Z real   T real, Z complex   T complex, Z real   T complex, Z complex
+            ordschur  d     -                wrong               wrong               wrong
+            ordschur  z     wrong            wrong               -                   -
+            eigvecs   d     -                mixed               wrong               wrong
+            eigvecs   z     wrong            mixed               mixed               -
+        (a list of factors or of vectors that is only partly complex: `any` for d, `all` for z, as the code says)."""
+        n = None
+        Ts, Zs = [], []
+        for ps in problems:
+            if isinstance(ps, GeneralizedPeriodicSchur) and not all(ps.S):
+                raise NotImplementedPSD(f"{name}: signed GeneralizedPeriodicSchur "
+                                        f"(use {'geigvecs' if needZ else 'ordschur_'} per problem)")
+            if needZ and (len(ps.Z) == 0 or ps.Z[0].shape[0] == 0):
+                raise ValueError("eigvecs requires Schur vectors in the PSD")  # vectors.jl:30-32
+            cT, cZ = [np.iscomplexobj(t) for t in ps.Ts], [np.iscomplexobj(z) for z in ps.Z]
+            if needZ:  # eigvecs: factors and vectors of different kinds are the error of the single call
+                other = any(cT) if fam is _D else not any(cT + cZ)
+                mixed = any(cZ) if fam is _D else not all(cT + cZ)
+            else:  # ordschur: real vectors beside complex factors are left to the in-place contract
+                other = any(cT + cZ) if fam is _D else not all(cT)
+                mixed = False
+            if other:
+                raise wrong
+            if mixed:
+                raise TypeError("eigvecs: the factors T and the Schur vectors Z must be all real or all complex")
+            nq = ps.Ts[0].shape[0] if needZ else _check_square(ps.Ts)
+            if n is None:
+                n, p, orient, si = nq, len(ps.Ts), ps.orientation, ps.schurindex
+            if (nq != n or len(ps.Ts) != p or (needZ and len(ps.Z) != p) or ps.orientation != orient
+                    or ps.schurindex != si or any(a.shape != (n, n) for a in list(ps.Ts) + list(ps.Z))):
+                raise DimensionMismatch("the problems of a batch must have equal order, period, orientation and schurindex")
+            Ts += ps.Ts if work else [np.asfortranarray(t, dtype=fam.dtype) for t in ps.Ts]
+            if needZ:
+                Zs += ps.Z if work else [np.asfortranarray(z, dtype=fam.dtype) for z in ps.Z]
+        return (n, p, orient, si, Ts) + ((Zs,) if needZ else ())
+
+    def _ordschur_batch_call(self, fam, name, dev, nb, n, p, T, Z, orient, si, sel, wantZ, infos_out, result):
+        """psd_?_ordschur_batch[_dev] on packed factors: T and Z flat lists of work arrays, or with `dev` device blocks
+        (the values row of a problem that failed is NaN then).  Leaves the call's stats and swap counts in
+        self.<name>_stats / _nswaps; `result(eig, codes, nswaps, stats)` builds what the call returns."""
+        ptrs = (lambda X: C.c_void_p(X.data_ptr())) if dev else self._ptrs
+        eig = _eig_alloc(fam, (nb, n), nan=dev)
+        infos, nsw, st, info = (C.c_int * nb)(), (C.c_int * nb)(), Stats(), C.c_int(0)
+        fn = getattr(self.lib, f"psd_{fam.tag}_ordschur_batch{'_dev' if dev else ''}")
+        fn(self.ctx, nb, n, p, ptrs(T), ptrs(Z) if wantZ else None, orient.encode(), int(si),
+           sel.ctypes.data_as(C.POINTER(C.c_uint8)), int(wantZ), *self._evec_ptrs(eig), infos, nsw, C.byref(st),
+           C.byref(info))
+
+        def done():
+            self._ordschur_batch_attrs(name, st, np.array(list(nsw), dtype=np.int32))
+            return result(eig, infos, nsw, st)
+
+        return self._batch_finish(info.value, infos, infos_out, self._raise_ord, True, done)
+
+    def _ordschur_batch_attrs(self, name, st, nswaps):
+        setattr(self, name + "_stats", st)
+        setattr(self, name + "_nswaps", nswaps)
+
+    def _ordschur_batch_(self, fam, name, problems, args, wantZ, infos_out, lr, schurindex):
+        """ordschur_batch_ / zordschur_batch_."""
+        wrong = NotImplementedPSD(_ORD_WRONG[fam])
+        if hasattr(problems, "data_ptr"):
+            if len(args) != 2:
+                raise TypeError(f"{name}_(T, Z, select, lr=..., schurindex=...)")
+            return self._ordschur_batch_dev(fam, name, wrong, problems, args[0], args[1], lr, schurindex, wantZ, infos_out)
+        if len(args) != 1:
+            raise TypeError(f"{name}_(problems, select, wantZ=True)")
+        problems = list(problems)
+        nb = len(problems)
+        if nb == 0:
+            if infos_out is not None:
+                infos_out[:] = []
+            self._ordschur_batch_attrs(name, Stats(), np.zeros(0, dtype=np.int32))
+            return []
+        n, p, orient, si, Ts = self._batch_decomps(fam, name, wrong, problems, needZ=False, work=True)
+        if si not in (1, p):
+            raise ValueError("only implemented for schurindex in (1,p)")  # src/ordschur.jl:32, src/rordschur.jl:25
+        wantZ = bool(wantZ) and all(len(ps.Z) > 0 for ps in problems)
+        Zs = []
+        if wantZ:
+            for ps in problems:
+                if len(ps.Z) != p:
+                    raise DimensionMismatch("one Z per factor")
+                Zs += ps.Z
+        sel = self._ord_batch_select(args[0], nb, n)
+        self._as_work(Ts, fam.dtype)
+        self._as_work(Zs, fam.dtype)
+
+        def result(eig, infos, nsw, st):
+            values = _eig_values(eig)
+            for q, ps in enumerate(problems):
+                if infos[q] == 0:  # (a problem that failed keeps its old values)
+                    ps.values = values[q].copy()  # (its own array, not a view that keeps the batch's alive)
+                    if fam is _Z and isinstance(ps, GeneralizedPeriodicSchur):  # (the real entry has no scaled form)
+                        ps.alpha, ps.beta, ps.alphascale = eig[0][q].copy(), eig[1][q].copy(), eig[2][q].copy()
+                ps.stats = Stats.from_buffer_copy(st)
+                ps.stats.nsweeps = nsw[q]
+            return problems
+
+        return self._ordschur_batch_call(fam, name, False, nb, n, p, Ts, Zs, char_lr(orient), si, sel, wantZ, infos_out,
+                                         result)
+
+    def _ordschur_batch_dev(self, fam, name, wrong, T, Z, select, lr, schurindex, wantZ, infos_out):
+        import torch
+
+        nb, p, n = self._dev_batch(fam, name, wrong, T, Z)
+        wantZ = bool(wantZ) and Z is not None
+        orient = char_lr(lr)
+        if schurindex not in (1, p):
+            raise ValueError("only implemented for schurindex in (1,p)")  # src/ordschur.jl:32, src/rordschur.jl:25
+        if nb == 0:
+            if infos_out is not None:
+                infos_out[:] = []
+            self._ordschur_batch_attrs(name, Stats(), np.zeros(0, dtype=np.int32))
+            return T, Z, np.zeros((0, n), dtype=complex), getattr(self, name + "_stats")
+        sel = self._ord_batch_select(select, nb, n)
+        dT = _dev_blocks(T, fam, "inplace_if_blocks")
+        dZ = _dev_blocks(Z, fam, "inplace_if_blocks") if wantZ else None
+        torch.cuda.synchronize(T.device)
+        return self._ordschur_batch_call(
+            fam, name, True, nb, n, p, dT, dZ, orient, schurindex, sel, wantZ, infos_out,
+            lambda eig, infos, nsw, st: (dT.transpose(2, 3), (dZ.transpose(2, 3) if wantZ else Z), _eig_values(eig), st))
+
+    def _ordschur_batch(self, fam, inplace, problems, args, kw):
+        """The copying forms of the two above."""
+        if hasattr(problems, "data_ptr"):
+            Z = args[0] if len(args) > 0 else None
+            return inplace(problems.clone(), Z.clone() if Z is not None else None, *args[1:], **kw)
+        return inplace(self._batch_copies(fam, NotImplementedPSD(_ORD_WRONG[fam]), problems, every=True), *args, **kw)
+
     def ordschur_batch_(self, problems, *args, wantZ=True, infos_out=None, lr="R", schurindex=1):
         """LinearAlgebra.ordschur!(P, select; wantZ) (src/rordschur.jl:3-132) for MANY small decompositions of one shape
         in ONE call (psd_d_ordschur_batch): the follow-up of pschur_batch.  Float64, all-true signature.  Per problem
@@ -1536,138 +1499,11 @@ class Engine:
         ill-conditioned swap: IllConditionedException) ends alone, a consistent decomposition with its old `values`;
         the exception of the first such problem is raised after all have run — the others are complete then.
         `infos_out`: a list that receives the per-problem codes instead (nothing is raised for a failed problem)."""
-        if hasattr(problems, "data_ptr"):
-            if len(args) != 2:
-                raise TypeError("ordschur_batch_(T, Z, select, lr=..., schurindex=...)")
-            return self._ordschur_batch_dev(problems, args[0], args[1], lr, schurindex, wantZ, infos_out)
-        if len(args) != 1:
-            raise TypeError("ordschur_batch_(problems, select, wantZ=True)")
-        problems = list(problems)
-        nb = len(problems)
-        if nb == 0:
-            if infos_out is not None:
-                infos_out[:] = []
-            self.ordschur_batch_stats = Stats()
-            self.ordschur_batch_nswaps = np.zeros(0, dtype=np.int32)
-            return []
-        n = p = None
-        Ts, Zs = [], []
-        for ps in problems:
-            if isinstance(ps, GeneralizedPeriodicSchur) and not all(ps.S):
-                raise NotImplementedPSD("ordschur_batch: signed GeneralizedPeriodicSchur (use ordschur_ per problem)")
-            if any(np.iscomplexobj(t) for t in ps.Ts) or any(np.iscomplexobj(z) for z in ps.Z):
-                raise NotImplementedPSD("ordschur_batch: Float64 only (use ordschur_ per problem for ComplexF64)")
-            nq = _check_square(ps.Ts)
-            if n is None:
-                n, p, orient, si = nq, len(ps.Ts), ps.orientation, ps.schurindex
-            if (nq != n or len(ps.Ts) != p or ps.orientation != orient or ps.schurindex != si
-                    or any(z.shape != (n, n) for z in ps.Z)):
-                raise DimensionMismatch("the problems of a batch must have equal order, period, orientation and schurindex")
-            Ts += list(ps.Ts)
-        if si not in (1, p):
-            raise ValueError("only implemented for schurindex in (1,p)")  # src/rordschur.jl:25
-        wantZ = bool(wantZ) and all(len(ps.Z) > 0 for ps in problems)
-        if wantZ:
-            for ps in problems:
-                if len(ps.Z) != p:
-                    raise DimensionMismatch("one Z per factor")
-                Zs += list(ps.Z)
-        sel = self._ord_batch_select(args[0], nb, n)
-        self._as_work(Ts)
-        self._as_work(Zs)
-        wr, wi = np.zeros((nb, n)), np.zeros((nb, n))
-        infos = (C.c_int * nb)()
-        nsw = (C.c_int * nb)()
-        st = Stats()
-        info = C.c_int(0)
-        dp = C.POINTER(C.c_double)
-        self.lib.psd_d_ordschur_batch(self.ctx, nb, n, p, self._ptrs(Ts), self._ptrs(Zs) if wantZ else None,
-                                      char_lr(orient).encode(), int(si), sel.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                      int(wantZ), wr.ctypes.data_as(dp), wi.ctypes.data_as(dp), infos, nsw, C.byref(st),
-                                      C.byref(info))
-        if info.value < 0 or info.value >= INFO_NOTIMPL:
-            self._raise(info.value)
-        self.ordschur_batch_stats = st
-        self.ordschur_batch_nswaps = np.array(list(nsw), dtype=np.int32)
-        for q, ps in enumerate(problems):
-            if infos[q] == 0:
-                ps.values = wr[q] + 1j * wi[q]
-            ps.stats = Stats.from_buffer_copy(st)
-            ps.stats.nsweeps = nsw[q]
-        if infos_out is not None:
-            infos_out[:] = [int(infos[q]) for q in range(nb)]
-            return problems
-        for q in range(nb):
-            self._raise_ord(infos[q])
-        return problems
+        return self._ordschur_batch_(_D, "ordschur_batch", problems, args, wantZ, infos_out, lr, schurindex)
 
     def ordschur_batch(self, problems, *args, **kw):
         """Copying form of ordschur_batch_: the decompositions are left untouched (device tensors are copied too)."""
-        if hasattr(problems, "data_ptr"):
-            Z = args[0] if len(args) > 0 else None
-            return self.ordschur_batch_(problems.clone(), Z.clone() if Z is not None else None, *args[1:], **kw)
-        work = []
-        for ps in problems:
-            if any(np.iscomplexobj(t) for t in ps.Ts):
-                raise NotImplementedPSD("ordschur_batch: Float64 only (use ordschur_ per problem for ComplexF64)")
-            cp = copy.copy(ps)
-            cp.Ts = [np.array(t, dtype=np.float64, order="F", copy=True) for t in ps.Ts]
-            cp.Z = [np.array(z, dtype=np.float64, order="F", copy=True) for z in ps.Z]
-            cp.values = np.array(ps.values, copy=True)
-            work.append(cp)
-        return self.ordschur_batch_(work, *args, **kw)
-
-    def _ordschur_batch_dev(self, T, Z, select, lr, schurindex, wantZ, infos_out):
-        import torch
-
-        wantZ = bool(wantZ) and Z is not None
-        if T.dim() != 4 or T.shape[2] != T.shape[3] or (Z is not None and Z.shape != T.shape):
-            raise DimensionMismatch("a device batch is [nb, p, n, n] tensors T and Z of square factors")
-        if T.is_complex() or (Z is not None and Z.is_complex()):
-            raise NotImplementedPSD("ordschur_batch: Float64 only (use ordschur_ per problem for ComplexF64)")
-        if not (T.is_cuda and (Z is None or Z.is_cuda)):
-            raise TypeError("device-resident ordschur_batch needs GPU tensors (use a list of PeriodicSchur for host input)")
-        nb, p, n = T.shape[0], T.shape[1], T.shape[2]
-        orient = char_lr(lr)
-        if schurindex not in (1, p):
-            raise ValueError("only implemented for schurindex in (1,p)")  # src/rordschur.jl:25
-        if nb == 0:
-            if infos_out is not None:
-                infos_out[:] = []
-            return T, Z, np.zeros((0, n), dtype=complex), Stats()
-        sel = self._ord_batch_select(select, nb, n)
-
-        def blocks(X):
-            # [nb][p][n][n] blocks of column-major matrices: the transpose of each factor, contiguous.  What
-            # pschur_batch_ returns is a view of exactly that: used as it is, in place
-            Xt = X.transpose(2, 3)
-            if X.dtype == torch.float64 and Xt.is_contiguous():
-                return Xt
-            return X.to(torch.float64).transpose(2, 3).contiguous()
-
-        dT = blocks(T)
-        dZ = blocks(Z) if wantZ else None
-        wr, wi = np.full((nb, n), np.nan), np.zeros((nb, n))
-        infos = (C.c_int * nb)()
-        nsw = (C.c_int * nb)()
-        st = Stats()
-        info = C.c_int(0)
-        dp = C.POINTER(C.c_double)
-        torch.cuda.synchronize(T.device)
-        self.lib.psd_d_ordschur_batch_dev(self.ctx, nb, n, p, C.c_void_p(dT.data_ptr()),
-                                          C.c_void_p(dZ.data_ptr()) if wantZ else None, orient.encode(), int(schurindex),
-                                          sel.ctypes.data_as(C.POINTER(C.c_uint8)), int(wantZ), wr.ctypes.data_as(dp),
-                                          wi.ctypes.data_as(dp), infos, nsw, C.byref(st), C.byref(info))
-        if info.value < 0 or info.value >= INFO_NOTIMPL:
-            self._raise(info.value)
-        self.ordschur_batch_stats = st
-        self.ordschur_batch_nswaps = np.array(list(nsw), dtype=np.int32)
-        if infos_out is not None:
-            infos_out[:] = [int(infos[q]) for q in range(nb)]
-        else:
-            for q in range(nb):
-                self._raise_ord(infos[q])
-        return dT.transpose(2, 3), (dZ.transpose(2, 3) if wantZ else Z), wr + 1j * wi, st
+        return self._ordschur_batch(_D, self.ordschur_batch_, problems, args, kw)
 
     def zordschur_batch_(self, problems, *args, wantZ=True, infos_out=None, lr="R", schurindex=1):
         """LinearAlgebra.ordschur!(P, select; wantZ) (src/ordschur.jl:11-73) for MANY small ComplexF64 decompositions of
@@ -1692,150 +1528,11 @@ class Engine:
         consistent decomposition with its old `values`; the exception of the first such problem is raised after all
         have run — the others are complete then.  `infos_out`: a list that receives the per-problem codes instead
         (nothing is raised for a failed problem)."""
-        if hasattr(problems, "data_ptr"):
-            if len(args) != 2:
-                raise TypeError("zordschur_batch_(T, Z, select, lr=..., schurindex=...)")
-            return self._zordschur_batch_dev(problems, args[0], args[1], lr, schurindex, wantZ, infos_out)
-        if len(args) != 1:
-            raise TypeError("zordschur_batch_(problems, select, wantZ=True)")
-        problems = list(problems)
-        nb = len(problems)
-        if nb == 0:
-            if infos_out is not None:
-                infos_out[:] = []
-            self.zordschur_batch_stats = Stats()
-            self.zordschur_batch_nswaps = np.zeros(0, dtype=np.int32)
-            return []
-        n = p = None
-        Ts, Zs = [], []
-        for ps in problems:
-            if isinstance(ps, GeneralizedPeriodicSchur) and not all(ps.S):
-                raise NotImplementedPSD("zordschur_batch: signed GeneralizedPeriodicSchur (use ordschur_ per problem)")
-            if not all(np.iscomplexobj(t) for t in ps.Ts):
-                raise NotImplementedPSD("zordschur_batch: ComplexF64 only (Float64 problems: ordschur_batch)")
-            nq = _check_square(ps.Ts)
-            if n is None:
-                n, p, orient, si = nq, len(ps.Ts), ps.orientation, ps.schurindex
-            if (nq != n or len(ps.Ts) != p or ps.orientation != orient or ps.schurindex != si
-                    or any(z.shape != (n, n) for z in ps.Z)):
-                raise DimensionMismatch("the problems of a batch must have equal order, period, orientation and schurindex")
-            Ts += list(ps.Ts)
-        if si not in (1, p):
-            raise ValueError("only implemented for schurindex in (1,p)")  # src/ordschur.jl:32
-        wantZ = bool(wantZ) and all(len(ps.Z) > 0 for ps in problems)
-        if wantZ:
-            for ps in problems:
-                if len(ps.Z) != p:
-                    raise DimensionMismatch("one Z per factor")
-                Zs += list(ps.Z)
-        sel = self._ord_batch_select(args[0], nb, n)
-        self._as_work(Ts, np.complex128)
-        self._as_work(Zs, np.complex128)
-        alpha = np.zeros((nb, n), dtype=np.complex128)
-        beta = np.zeros((nb, n))
-        sc = np.zeros((nb, n), dtype=np.int32)
-        infos = (C.c_int * nb)()
-        nsw = (C.c_int * nb)()
-        st = Stats()
-        info = C.c_int(0)
-        dp = C.POINTER(C.c_double)
-        self.lib.psd_z_ordschur_batch(self.ctx, nb, n, p, self._ptrs(Ts), self._ptrs(Zs) if wantZ else None,
-                                      char_lr(orient).encode(), int(si), sel.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                      int(wantZ), alpha.view(np.float64).ctypes.data_as(dp), beta.ctypes.data_as(dp),
-                                      sc.ctypes.data_as(C.POINTER(C.c_int32)), infos, nsw, C.byref(st), C.byref(info))
-        if info.value < 0 or info.value >= INFO_NOTIMPL:
-            self._raise(info.value)
-        self.zordschur_batch_stats = st
-        self.zordschur_batch_nswaps = np.array(list(nsw), dtype=np.int32)
-        for q, ps in enumerate(problems):
-            if infos[q] == 0:
-                with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
-                    ps.values = alpha[q] / beta[q] * np.exp2(sc[q].astype(np.float64))
-                if isinstance(ps, GeneralizedPeriodicSchur):
-                    ps.alpha, ps.beta, ps.alphascale = alpha[q].copy(), beta[q].copy(), sc[q].copy()
-            ps.stats = Stats.from_buffer_copy(st)
-            ps.stats.nsweeps = nsw[q]
-        if infos_out is not None:
-            infos_out[:] = [int(infos[q]) for q in range(nb)]
-            return problems
-        for q in range(nb):
-            self._raise_ord(infos[q])
-        return problems
+        return self._ordschur_batch_(_Z, "zordschur_batch", problems, args, wantZ, infos_out, lr, schurindex)
 
     def zordschur_batch(self, problems, *args, **kw):
         """Copying form of zordschur_batch_: the decompositions are left untouched (device tensors are copied too)."""
-        if hasattr(problems, "data_ptr"):
-            Z = args[0] if len(args) > 0 else None
-            return self.zordschur_batch_(problems.clone(), Z.clone() if Z is not None else None, *args[1:], **kw)
-        work = []
-        for ps in problems:
-            if not all(np.iscomplexobj(t) for t in ps.Ts):
-                raise NotImplementedPSD("zordschur_batch: ComplexF64 only (Float64 problems: ordschur_batch)")
-            cp = copy.copy(ps)
-            cp.Ts = [np.array(t, dtype=np.complex128, order="F", copy=True) for t in ps.Ts]
-            cp.Z = [np.array(z, dtype=np.complex128, order="F", copy=True) for z in ps.Z]
-            cp.values = np.array(ps.values, copy=True)
-            work.append(cp)
-        return self.zordschur_batch_(work, *args, **kw)
-
-    def _zordschur_batch_dev(self, T, Z, select, lr, schurindex, wantZ, infos_out):
-        import torch
-
-        wantZ = bool(wantZ) and Z is not None
-        if T.dim() != 4 or T.shape[2] != T.shape[3] or (Z is not None and Z.shape != T.shape):
-            raise DimensionMismatch("a device batch is [nb, p, n, n] tensors T and Z of square factors")
-        if not T.is_complex() or (Z is not None and not Z.is_complex()):
-            raise NotImplementedPSD("zordschur_batch: ComplexF64 only (Float64 problems: ordschur_batch)")
-        if not (T.is_cuda and (Z is None or Z.is_cuda)):
-            raise TypeError("device-resident zordschur_batch needs GPU tensors (use a list of PeriodicSchur for host input)")
-        nb, p, n = T.shape[0], T.shape[1], T.shape[2]
-        orient = char_lr(lr)
-        if schurindex not in (1, p):
-            raise ValueError("only implemented for schurindex in (1,p)")  # src/ordschur.jl:32
-        if nb == 0:
-            if infos_out is not None:
-                infos_out[:] = []
-            self.zordschur_batch_stats = Stats()
-            self.zordschur_batch_nswaps = np.zeros(0, dtype=np.int32)
-            return T, Z, np.zeros((0, n), dtype=complex), self.zordschur_batch_stats
-        sel = self._ord_batch_select(select, nb, n)
-
-        def blocks(X):
-            # [nb][p][n][n] blocks of column-major matrices: the transpose of each factor, contiguous.  What
-            # zpschur_batch_ returns is a view of exactly that: used as it is, in place
-            Xt = X.transpose(2, 3)
-            if X.dtype == torch.complex128 and Xt.is_contiguous():
-                return Xt
-            return X.to(torch.complex128).transpose(2, 3).contiguous()
-
-        dT = blocks(T)
-        dZ = blocks(Z) if wantZ else None
-        alpha = np.full((nb, n), np.nan, dtype=np.complex128)
-        beta = np.ones((nb, n))
-        sc = np.zeros((nb, n), dtype=np.int32)
-        infos = (C.c_int * nb)()
-        nsw = (C.c_int * nb)()
-        st = Stats()
-        info = C.c_int(0)
-        dp = C.POINTER(C.c_double)
-        torch.cuda.synchronize(T.device)
-        self.lib.psd_z_ordschur_batch_dev(self.ctx, nb, n, p, C.c_void_p(dT.data_ptr()),
-                                          C.c_void_p(dZ.data_ptr()) if wantZ else None, orient.encode(), int(schurindex),
-                                          sel.ctypes.data_as(C.POINTER(C.c_uint8)), int(wantZ),
-                                          alpha.view(np.float64).ctypes.data_as(dp), beta.ctypes.data_as(dp),
-                                          sc.ctypes.data_as(C.POINTER(C.c_int32)), infos, nsw, C.byref(st), C.byref(info))
-        if info.value < 0 or info.value >= INFO_NOTIMPL:
-            self._raise(info.value)
-        self.zordschur_batch_stats = st
-        self.zordschur_batch_nswaps = np.array(list(nsw), dtype=np.int32)
-        if infos_out is not None:
-            infos_out[:] = [int(infos[q]) for q in range(nb)]
-        else:
-            for q in range(nb):
-                self._raise_ord(infos[q])
-        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
-            values = alpha / beta * np.exp2(sc.astype(np.float64))
-        return dT.transpose(2, 3), (dZ.transpose(2, 3) if wantZ else Z), values, st
+        return self._ordschur_batch(_Z, self.zordschur_batch_, problems, args, kw)
 
     def eigvecs(self, ps0, select, shifted=True, method="ordschur"):
         """LinearAlgebra.eigvecs(ps::PeriodicSchur, select; shifted) — src/vectors.jl:25-138: selected right
@@ -2020,6 +1717,95 @@ class Engine:
         self.eigvecs_stats = st
         return [dV[l, :nvec, :].transpose(0, 1) for l in range(nmat)]
 
+    @staticmethod
+    def _batch_select(select, nb, n):
+        """[nb][n] flags (uint8, contiguous, a copy) from [nb][n] or one [n] row for every problem."""
+        sel = np.asarray(select)
+        if sel.ndim == 1 and sel.shape[0] == n:
+            sel = np.broadcast_to(sel, (nb, n))
+        if sel.shape != (nb, n):
+            raise ValueError("argument 9 invalid: `select` must be [nb][n] flags or one row of n "
+                             "(its length must correspond to the rank of the Schur space)")  # vectors.jl:34-36
+        return np.ascontiguousarray(sel.astype(bool), dtype=np.uint8)
+
+    def _eigvecs_batch_call(self, fam, dev, nb, n, p, T, Z, ev, orient, si, sel, shifted, V=None, maxvec=0):
+        """One call of psd_?_eigvecs_batch[_dev] on packed factors (T, Z, V: ctypes arguments; ev: the eigenvalue
+        arguments).  Without V the size query (select completed); with V the stats and counters of the call are left in
+        self.eigvecs_batch_*.  Returns the vectors per problem, nvec."""
+        nvec = (C.c_int * nb)()
+        cnts = np.zeros((nb, 3), dtype=np.int32)
+        st = BevecStats()
+        info = C.c_int(0)
+        fn = getattr(self.lib, f"psd_{fam.tag}_eigvecs_batch{'_dev' if dev else ''}")
+        fn(self.ctx, nb, n, p, T, Z, *self._evec_ptrs(ev), orient.encode(), int(si),
+           sel.ctypes.data_as(C.POINTER(C.c_uint8)), int(bool(shifted)), V, maxvec, nvec,
+           cnts.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(st), C.byref(info))
+        self._raise(info.value)
+        if V is not None:
+            self.eigvecs_batch_stats = st
+            self.eigvecs_batch_counts = cnts
+        return nvec
+
+    def _eigvecs_batch(self, fam, name, wrong, problems, args, shifted, lr, schurindex):
+        """eigvecs_batch / zeigvecs_batch."""
+        if hasattr(problems, "data_ptr"):
+            if len(args) != 3:
+                raise TypeError(f"{name}(T, Z, values, select, lr=..., schurindex=...)")
+            return self._eigvecs_batch_dev(fam, name, wrong, problems, args[0], args[1], args[2], lr, schurindex, shifted)
+        if len(args) != 1:
+            raise TypeError(f"{name}(problems, select, shifted=True)")
+        problems = list(problems)
+        nb = len(problems)
+        if nb == 0:
+            self.eigvecs_batch_stats = BevecStats()
+            self.eigvecs_batch_counts = np.zeros((0, 3), dtype=np.int32)
+            return []
+        n, p, orient, si, Ts, Zs = self._batch_decomps(fam, name, wrong, problems, needZ=True, work=False)
+        sel = self._batch_select(args[0], nb, n)
+        if fam is _D:
+            vals = np.array([np.asarray(ps.values, dtype=np.complex128) for ps in problems])
+            ev = [np.ascontiguousarray(vals.real), np.ascontiguousarray(vals.imag)]
+        else:
+            vals = [self._evec_values(ps, True) for ps in problems]
+            ev = [np.ascontiguousarray(np.array([v[k] for v in vals])) for k in range(3)]
+        call = (fam, False, nb, n, p, self._ptrs(Ts), self._ptrs(Zs), ev, orient, si, sel, shifted)
+        maxvec = max(self._eigvecs_batch_call(*call))
+        nmat = p if shifted else 1
+        Vs = [np.zeros((n, maxvec), dtype=np.complex128, order="F") for _ in range(nb * nmat)]
+        nvec = self._eigvecs_batch_call(*call, self._ptrs(Vs), maxvec)
+        return [[np.asfortranarray(Vs[q * nmat + l][:, :nvec[q]]) for l in range(nmat)] for q in range(nb)]
+
+    def _eigvecs_batch_dev(self, fam, name, wrong, T, Z, values, select, lr, schurindex, shifted):
+        import torch
+
+        if Z is None:
+            raise ValueError("eigvecs requires Schur vectors in the PSD")
+        nb, p, n = self._dev_batch(fam, name, wrong, T, Z, mixed=True)
+        orient = char_lr(lr)
+        nmat = p if shifted else 1
+        if nb == 0:
+            self.eigvecs_batch_stats = BevecStats()
+            self.eigvecs_batch_counts = np.zeros((0, 3), dtype=np.int32)
+            return torch.zeros((0, nmat, n, 0), dtype=torch.complex128, device=T.device), np.zeros(0, dtype=np.int32)
+        sel = self._batch_select(select, nb, n)
+        vals = np.ascontiguousarray(values, dtype=np.complex128)
+        if vals.shape != (nb, n):
+            raise DimensionMismatch("values must be [nb, n]")
+        # (the complex entry as eigvecs_dev passes them: alpha = values, beta = 1, scale 0)
+        ev = ([np.ascontiguousarray(vals.real), np.ascontiguousarray(vals.imag)] if fam is _D
+              else [vals, np.ones((nb, n)), np.zeros((nb, n), dtype=np.int32)])
+        dT, dZ = _dev_blocks(T, fam, "readonly"), _dev_blocks(Z, fam, "readonly")
+        call = (fam, True, nb, n, p, C.c_void_p(dT.data_ptr()), C.c_void_p(dZ.data_ptr()), ev, orient, schurindex, sel,
+                shifted)
+        torch.cuda.synchronize(T.device)
+        maxvec = max(self._eigvecs_batch_call(*call))
+        dV = torch.empty((nb, nmat, max(maxvec, 1), n), dtype=torch.complex128, device=T.device)
+        if maxvec == 0:
+            dV.zero_()
+        torch.cuda.synchronize(T.device)
+        nvec = self._eigvecs_batch_call(*call, C.c_void_p(dV.data_ptr()), max(maxvec, 1))
+        return dV[:, :, :maxvec, :].transpose(2, 3), np.array(list(nvec), dtype=np.int32)
+
     def eigvecs_batch(self, problems, *args, shifted=True, lr="R", schurindex=1):
         """eigvecs(ps, select; shifted) by periodic back-substitution for MANY small decompositions of one shape in ONE
         call (psd_d_eigvecs_batch): the follow-up of pschur_batch.  Float64, all-true signature.  Per problem the result
@@ -2037,118 +1823,8 @@ class Engine:
         pschur_batch info was non-zero.  The stats of the call are left in `self.eigvecs_batch_stats` (BevecStats), the
         per-problem counters (perturbed pivots, rescaled columns, zero eigenvalues) in `self.eigvecs_batch_counts`
         ([nb, 3])."""
-        if hasattr(problems, "data_ptr"):
-            if len(args) != 3:
-                raise TypeError("eigvecs_batch(T, Z, values, select, lr=..., schurindex=...)")
-            return self._eigvecs_batch_dev(problems, args[0], args[1], args[2], lr, schurindex, shifted)
-        if len(args) != 1:
-            raise TypeError("eigvecs_batch(problems, select, shifted=True)")
-        problems = list(problems)
-        nb = len(problems)
-        if nb == 0:
-            self.eigvecs_batch_stats = BevecStats()
-            self.eigvecs_batch_counts = np.zeros((0, 3), dtype=np.int32)
-            return []
-        n = p = None
-        Ts, Zs = [], []
-        for ps in problems:
-            if isinstance(ps, GeneralizedPeriodicSchur) and not all(ps.S):
-                raise NotImplementedPSD("eigvecs_batch: signed GeneralizedPeriodicSchur (use geigvecs per problem)")
-            if len(ps.Z) == 0 or ps.Z[0].shape[0] == 0:
-                raise ValueError("eigvecs requires Schur vectors in the PSD")  # vectors.jl:30-32
-            if any(np.iscomplexobj(t) for t in ps.Ts):
-                raise NotImplementedPSD("eigvecs_batch: Float64 only (ComplexF64 problems: zeigvecs_batch)")
-            if any(np.iscomplexobj(z) for z in ps.Z):
-                raise TypeError("eigvecs: the factors T and the Schur vectors Z must be all real or all complex")
-            nq = ps.Ts[0].shape[0]
-            if n is None:
-                n, p, orient, si = nq, len(ps.Ts), ps.orientation, ps.schurindex
-            if (nq != n or len(ps.Ts) != p or len(ps.Z) != p or ps.orientation != orient or ps.schurindex != si
-                    or any(t.shape != (n, n) for t in ps.Ts) or any(z.shape != (n, n) for z in ps.Z)):
-                raise DimensionMismatch("the problems of a batch must have equal order, period, orientation and schurindex")
-            Ts += [np.asfortranarray(t, dtype=np.float64) for t in ps.Ts]  # (read only: the problems are never written)
-            Zs += [np.asfortranarray(z, dtype=np.float64) for z in ps.Z]
-        sel = self._batch_select(args[0], nb, n)
-        vals = np.array([np.asarray(ps.values, dtype=np.complex128) for ps in problems])
-        wr, wi = np.ascontiguousarray(vals.real), np.ascontiguousarray(vals.imag)
-        dp, u8p = C.POINTER(C.c_double), C.POINTER(C.c_uint8)
-        nvec = (C.c_int * nb)()
-        cnts = np.zeros((nb, 3), dtype=np.int32)
-        st = BevecStats()
-        info = C.c_int(0)
-        head = [self.ctx, nb, n, p, self._ptrs(Ts), self._ptrs(Zs), wr.ctypes.data_as(dp), wi.ctypes.data_as(dp),
-                orient.encode(), int(si), sel.ctypes.data_as(u8p), int(bool(shifted))]
-        tail = [nvec, cnts.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(st), C.byref(info)]
-        self.lib.psd_d_eigvecs_batch(*head, None, 0, *tail)  # size query: select completed, nvec
-        self._raise(info.value)
-        maxvec = max(nvec)
-        nmat = p if shifted else 1
-        Vs = [np.zeros((n, maxvec), dtype=np.complex128, order="F") for _ in range(nb * nmat)]
-        self.lib.psd_d_eigvecs_batch(*head, self._ptrs(Vs), maxvec, *tail)
-        self._raise(info.value)
-        self.eigvecs_batch_stats = st
-        self.eigvecs_batch_counts = cnts
-        return [[np.asfortranarray(Vs[q * nmat + l][:, :nvec[q]]) for l in range(nmat)] for q in range(nb)]
-
-    @staticmethod
-    def _batch_select(select, nb, n):
-        """[nb][n] flags (uint8, contiguous, a copy) from [nb][n] or one [n] row for every problem."""
-        sel = np.asarray(select)
-        if sel.ndim == 1 and sel.shape[0] == n:
-            sel = np.broadcast_to(sel, (nb, n))
-        if sel.shape != (nb, n):
-            raise ValueError("argument 9 invalid: `select` must be [nb][n] flags or one row of n "
-                             "(its length must correspond to the rank of the Schur space)")  # vectors.jl:34-36
-        return np.ascontiguousarray(sel.astype(bool), dtype=np.uint8)
-
-    def _eigvecs_batch_dev(self, T, Z, values, select, lr, schurindex, shifted):
-        import torch
-
-        if Z is None:
-            raise ValueError("eigvecs requires Schur vectors in the PSD")
-        if T.dim() != 4 or T.shape[2] != T.shape[3] or Z.shape != T.shape:
-            raise DimensionMismatch("a device batch is [nb, p, n, n] tensors T and Z of square factors")
-        if T.is_complex() or Z.is_complex():
-            raise NotImplementedPSD("eigvecs_batch: Float64 only (ComplexF64 problems: zeigvecs_batch)")
-        if not (T.is_cuda and Z.is_cuda):
-            raise TypeError("device-resident eigvecs_batch needs GPU tensors (use a list of PeriodicSchur for host input)")
-        nb, p, n = T.shape[0], T.shape[1], T.shape[2]
-        orient = char_lr(lr)
-        nmat = p if shifted else 1
-        if nb == 0:
-            self.eigvecs_batch_stats = BevecStats()
-            self.eigvecs_batch_counts = np.zeros((0, 3), dtype=np.int32)
-            return torch.zeros((0, nmat, n, 0), dtype=torch.complex128, device=T.device), np.zeros(0, dtype=np.int32)
-        sel = self._batch_select(select, nb, n)
-        vals = np.asarray(values, dtype=np.complex128)
-        if vals.shape != (nb, n):
-            raise DimensionMismatch("values must be [nb, n]")
-        wr, wi = np.ascontiguousarray(vals.real), np.ascontiguousarray(vals.imag)
-        # [nb][p][n][n] blocks of column-major matrices: the transpose of each factor, contiguous (what pschur_batch_
-        # returns a view of: no copy then)
-        dT = T.to(torch.float64).transpose(2, 3).contiguous()
-        dZ = Z.to(torch.float64).transpose(2, 3).contiguous()
-        dp, u8p = C.POINTER(C.c_double), C.POINTER(C.c_uint8)
-        nvec = (C.c_int * nb)()
-        cnts = np.zeros((nb, 3), dtype=np.int32)
-        st = BevecStats()
-        info = C.c_int(0)
-        head = [self.ctx, nb, n, p, C.c_void_p(dT.data_ptr()), C.c_void_p(dZ.data_ptr()), wr.ctypes.data_as(dp),
-                wi.ctypes.data_as(dp), orient.encode(), int(schurindex), sel.ctypes.data_as(u8p), int(bool(shifted))]
-        tail = [nvec, cnts.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(st), C.byref(info)]
-        torch.cuda.synchronize(T.device)
-        self.lib.psd_d_eigvecs_batch_dev(*head, None, 0, *tail)  # size query
-        self._raise(info.value)
-        maxvec = max(nvec)
-        dV = torch.empty((nb, nmat, max(maxvec, 1), n), dtype=torch.complex128, device=T.device)
-        if maxvec == 0:
-            dV.zero_()
-        torch.cuda.synchronize(T.device)
-        self.lib.psd_d_eigvecs_batch_dev(*head, C.c_void_p(dV.data_ptr()), max(maxvec, 1), *tail)
-        self._raise(info.value)
-        self.eigvecs_batch_stats = st
-        self.eigvecs_batch_counts = cnts
-        return dV[:, :, :maxvec, :].transpose(2, 3), np.array(list(nvec), dtype=np.int32)
+        wrong = NotImplementedPSD("eigvecs_batch: Float64 only (ComplexF64 problems: zeigvecs_batch)")
+        return self._eigvecs_batch(_D, "eigvecs_batch", wrong, problems, args, shifted, lr, schurindex)
 
     def zeigvecs_batch(self, problems, *args, shifted=True, lr="R", schurindex=1):
         """eigvecs(ps, select; shifted) by periodic back-substitution for MANY small ComplexF64 decompositions of one
@@ -2166,107 +1842,9 @@ class Engine:
         `select`: [nb][n] flags, or one [n] row used for every problem, used as given.  A problem whose row is all false
         costs nothing and gets no columns.  Stats and counters are left in `self.eigvecs_batch_stats` and
         `self.eigvecs_batch_counts`, as by eigvecs_batch."""
-        if hasattr(problems, "data_ptr"):
-            if len(args) != 3:
-                raise TypeError("zeigvecs_batch(T, Z, values, select, lr=..., schurindex=...)")
-            return self._zeigvecs_batch_dev(problems, args[0], args[1], args[2], lr, schurindex, shifted)
-        if len(args) != 1:
-            raise TypeError("zeigvecs_batch(problems, select, shifted=True)")
-        problems = list(problems)
-        nb = len(problems)
-        if nb == 0:
-            self.eigvecs_batch_stats = BevecStats()
-            self.eigvecs_batch_counts = np.zeros((0, 3), dtype=np.int32)
-            return []
-        n = p = None
-        Ts, Zs = [], []
-        for ps in problems:
-            if isinstance(ps, GeneralizedPeriodicSchur) and not all(ps.S):
-                raise NotImplementedPSD("zeigvecs_batch: signed GeneralizedPeriodicSchur (use geigvecs per problem)")
-            if len(ps.Z) == 0 or ps.Z[0].shape[0] == 0:
-                raise ValueError("eigvecs requires Schur vectors in the PSD")  # vectors.jl:30-32
-            cplx = [np.iscomplexobj(a) for a in list(ps.Ts) + list(ps.Z)]
-            if not any(cplx):
-                raise TypeError("zeigvecs_batch: ComplexF64 only (Float64 problems: eigvecs_batch)")
-            if not all(cplx):
-                raise TypeError("eigvecs: the factors T and the Schur vectors Z must be all real or all complex")
-            nq = ps.Ts[0].shape[0]
-            if n is None:
-                n, p, orient, si = nq, len(ps.Ts), ps.orientation, ps.schurindex
-            if (nq != n or len(ps.Ts) != p or len(ps.Z) != p or ps.orientation != orient or ps.schurindex != si
-                    or any(t.shape != (n, n) for t in ps.Ts) or any(z.shape != (n, n) for z in ps.Z)):
-                raise DimensionMismatch("the problems of a batch must have equal order, period, orientation and schurindex")
-            Ts += [np.asfortranarray(t, dtype=np.complex128) for t in ps.Ts]  # (read only: the problems are never written)
-            Zs += [np.asfortranarray(z, dtype=np.complex128) for z in ps.Z]
-        sel = self._batch_select(args[0], nb, n)
-        vals = [self._evec_values(ps, True) for ps in problems]
-        alpha, beta, sc = (np.ascontiguousarray(np.array([v[k] for v in vals])) for k in range(3))
-        nvec = (C.c_int * nb)()
-        cnts = np.zeros((nb, 3), dtype=np.int32)
-        st = BevecStats()
-        info = C.c_int(0)
-        head = [self.ctx, nb, n, p, self._ptrs(Ts), self._ptrs(Zs)] + self._evec_ptrs([alpha, beta, sc]) + [
-            orient.encode(), int(si), sel.ctypes.data_as(C.POINTER(C.c_uint8)), int(bool(shifted))]
-        tail = [nvec, cnts.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(st), C.byref(info)]
-        self.lib.psd_z_eigvecs_batch(*head, None, 0, *tail)  # size query: nvec
-        self._raise(info.value)
-        maxvec = max(nvec)
-        nmat = p if shifted else 1
-        Vs = [np.zeros((n, maxvec), dtype=np.complex128, order="F") for _ in range(nb * nmat)]
-        self.lib.psd_z_eigvecs_batch(*head, self._ptrs(Vs), maxvec, *tail)
-        self._raise(info.value)
-        self.eigvecs_batch_stats = st
-        self.eigvecs_batch_counts = cnts
-        return [[np.asfortranarray(Vs[q * nmat + l][:, :nvec[q]]) for l in range(nmat)] for q in range(nb)]
+        wrong = TypeError("zeigvecs_batch: ComplexF64 only (Float64 problems: eigvecs_batch)")
+        return self._eigvecs_batch(_Z, "zeigvecs_batch", wrong, problems, args, shifted, lr, schurindex)
 
-    def _zeigvecs_batch_dev(self, T, Z, values, select, lr, schurindex, shifted):
-        import torch
-
-        if Z is None:
-            raise ValueError("eigvecs requires Schur vectors in the PSD")
-        if T.dim() != 4 or T.shape[2] != T.shape[3] or Z.shape != T.shape:
-            raise DimensionMismatch("a device batch is [nb, p, n, n] tensors T and Z of square factors")
-        if not T.is_complex() and not Z.is_complex():
-            raise TypeError("zeigvecs_batch: ComplexF64 only (Float64 problems: eigvecs_batch)")
-        if not (T.is_complex() and Z.is_complex()):
-            raise TypeError("eigvecs: the factors T and the Schur vectors Z must be all real or all complex")
-        if not (T.is_cuda and Z.is_cuda):
-            raise TypeError("device-resident zeigvecs_batch needs GPU tensors (use a list of PeriodicSchur for host input)")
-        nb, p, n = T.shape[0], T.shape[1], T.shape[2]
-        orient = char_lr(lr)
-        nmat = p if shifted else 1
-        if nb == 0:
-            self.eigvecs_batch_stats = BevecStats()
-            self.eigvecs_batch_counts = np.zeros((0, 3), dtype=np.int32)
-            return torch.zeros((0, nmat, n, 0), dtype=torch.complex128, device=T.device), np.zeros(0, dtype=np.int32)
-        sel = self._batch_select(select, nb, n)
-        vals = np.ascontiguousarray(values, dtype=np.complex128)
-        if vals.shape != (nb, n):
-            raise DimensionMismatch("values must be [nb, n]")
-        # [nb][p][n][n] blocks of column-major matrices: the transpose of each factor, contiguous (what zpschur_batch_
-        # returns a view of: no copy then)
-        dT = T.to(torch.complex128).transpose(2, 3).contiguous()
-        dZ = Z.to(torch.complex128).transpose(2, 3).contiguous()
-        nvec = (C.c_int * nb)()
-        cnts = np.zeros((nb, 3), dtype=np.int32)
-        st = BevecStats()
-        info = C.c_int(0)
-        ev = [vals, np.ones((nb, n)), np.zeros((nb, n), dtype=np.int32)]  # (as eigvecs_dev passes them)
-        head = [self.ctx, nb, n, p, C.c_void_p(dT.data_ptr()), C.c_void_p(dZ.data_ptr())] + self._evec_ptrs(ev) + [
-            orient.encode(), int(schurindex), sel.ctypes.data_as(C.POINTER(C.c_uint8)), int(bool(shifted))]
-        tail = [nvec, cnts.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(st), C.byref(info)]
-        self.lib.psd_z_eigvecs_batch_dev(*head, None, 0, *tail)  # size query
-        self._raise(info.value)
-        maxvec = max(nvec)
-        dV = torch.empty((nb, nmat, max(maxvec, 1), n), dtype=torch.complex128, device=T.device)
-        if maxvec == 0:
-            dV.zero_()
-        torch.cuda.synchronize(T.device)
-        self.lib.psd_z_eigvecs_batch_dev(*head, C.c_void_p(dV.data_ptr()), max(maxvec, 1), *tail)
-        self._raise(info.value)
-        self.eigvecs_batch_stats = st
-        self.eigvecs_batch_counts = cnts
-        return dV[:, :, :maxvec, :].transpose(2, 3), np.array(list(nvec), dtype=np.int32)
 
     def geigvecs(self, P, select, shifted=True):
         """Eigenvectors of a signed or singular periodic product (psd_d_geigvecs / psd_z_geigvecs): periodic
@@ -2756,8 +2334,7 @@ class Engine:
                                   beta.ctypes.data_as(dp), sc.ctypes.data_as(i32p), C.byref(si), C.byref(st),
                                   log.ctypes.data_as(i32p), maxlog, C.byref(info))
         self._raise(info.value)
-        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
-            lam = alpha / beta * np.exp2(sc.astype(np.float64))
+        lam = _scaled_values(alpha, beta, sc)
         nl = min(st.nlog, maxlog)
         return lam, si.value, st, log[: 3 * nl].reshape(-1, 3).copy()
 

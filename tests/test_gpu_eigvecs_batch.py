@@ -64,3 +64,20 @@ def test_pipeline_device_resident(gpu_engine, lr):
 
 def test_errors(gpu_engine):
     bc.case_errors(gpu_engine, lambda: psd_amd.Engine(device=0))
+
+
+def test_empty_device_batch(gpu_engine):
+    """nb = 0: the shapes and dtypes of a call describe themselves, its stats are those of no problem, no kernel runs"""
+    import numpy as np
+    import torch
+
+    T = torch.zeros((0, 2, 3, 3), dtype=torch.float64, device="cuda")
+    gpu_engine.eigvecs_batch_stats = gpu_engine.eigvecs_batch_counts = None
+    V, nvec = gpu_engine.eigvecs_batch(T, T.clone(), np.zeros((0, 3)), np.zeros((0, 3), dtype=bool))
+    assert tuple(V.shape) == (0, 2, 3, 0) and V.dtype == torch.complex128 and V.is_cuda
+    assert nvec.shape == (0,) and nvec.dtype == np.int32
+    st = gpu_engine.eigvecs_batch_stats
+    assert isinstance(st, psd_amd.BevecStats) and st.nb == 0 and st.nlaunch == 0
+    assert gpu_engine.eigvecs_batch_counts.shape == (0, 3) and gpu_engine.eigvecs_batch_counts.dtype == np.int32
+    V1, _ = gpu_engine.eigvecs_batch(T, T.clone(), np.zeros((0, 3)), [True] * 3, shifted=False)
+    assert tuple(V1.shape) == (0, 1, 3, 0)

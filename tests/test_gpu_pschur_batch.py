@@ -76,3 +76,30 @@ def test_groups(monkeypatch):
         return psd_amd.Engine(device=0)
 
     bc.case_groups(make)
+
+
+def test_empty_device_batch(gpu_engine):
+    """nb = 0: the shapes and dtypes of a call describe themselves, and no kernel runs"""
+    import numpy as np
+    import torch
+
+    dA = torch.zeros((0, 2, 3, 3), dtype=torch.float64, device="cuda")
+    infos = [7]
+    T, Z, values, st = gpu_engine.pschur_batch_(dA, infos_out=infos)
+    assert tuple(T.shape) == tuple(Z.shape) == (0, 2, 3, 3) and T.dtype == Z.dtype == torch.float64 and T.is_cuda
+    assert values.shape == (0, 3) and values.dtype == np.complex128 and infos == []
+    assert isinstance(st, psd_amd.Stats) and st.nlaunch_step == 0 and st.niter == 0
+    assert gpu_engine.pschur_batch(dA, "L", wantZ=False)[1] is None
+
+
+def test_device_input_is_left(gpu_engine):
+    """the device entry always works on a copy, also of a tensor that already has the layout it works on"""
+    import numpy as np
+    import torch
+
+    A = torch.from_numpy(np.random.default_rng(5).standard_normal((3, 2, 4, 4))).cuda()
+    keep = A.clone()
+    for X in (A, A.transpose(2, 3)):  # (contiguous; a transposed view of contiguous blocks)
+        T, Z, values, _ = gpu_engine.pschur_batch_(X)
+        assert torch.equal(A, keep) and T.data_ptr() != A.data_ptr() and Z.data_ptr() != A.data_ptr()
+        assert not torch.equal(T, X) and values.shape == (3, 4)

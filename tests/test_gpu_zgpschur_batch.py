@@ -81,3 +81,19 @@ def test_device_resident(gpu_engine):
 def test_above_the_cap(gpu_engine):
     """order cap + 1: the single call's signed reduction and iteration, problem by problem on the batch buffer"""
     gc.case_above_cap(gpu_engine, _zgb_nmax() + 1)
+
+
+def test_empty_device_batch(gpu_engine):
+    """nb = 0: the shapes and dtypes of a call describe themselves, and no kernel runs; the signature is still checked"""
+    import numpy as np
+    import torch
+
+    dA = torch.zeros((0, 2, 3, 3), dtype=torch.complex128, device="cuda")
+    infos = [7]
+    T, Z, values, st = gpu_engine.zgpschur_batch_(dA, [True, False], infos_out=infos)
+    assert tuple(T.shape) == tuple(Z.shape) == (0, 2, 3, 3) and T.dtype == Z.dtype == torch.complex128 and T.is_cuda
+    assert values.shape == (0, 3) and values.dtype == np.complex128 and infos == []
+    assert isinstance(st, psd_amd.Stats) and st.nlaunch_step == 0 and st.niter == 0
+    assert gpu_engine.zpschur_batch(dA, "L", S=[False, True], wantZ=False)[1] is None
+    with pytest.raises(psd_amd.DimensionMismatch):
+        gpu_engine.zgpschur_batch_(dA, [True, False, True])

@@ -93,3 +93,39 @@ def test_device_entry_bits_grouped(make_engine):
 @pytest.mark.parametrize("lr", ["R", "L"])
 def test_device_resident_chain(gpu_engine, lr):
     zc.case_device_chain(gpu_engine, lr)
+
+
+def test_empty_device_batch(gpu_engine):
+    """nb = 0: the tensors come back as they are, the call's stats and swap counts are those of no problem, no kernel runs"""
+    import numpy as np
+    import torch
+
+    T = torch.zeros((0, 2, 3, 3), dtype=torch.complex128, device="cuda")
+    Z = T.clone()
+    gpu_engine.zordschur_batch_stats, gpu_engine.zordschur_batch_nswaps = None, np.ones(3, dtype=np.int32)
+    infos = [7]
+    T0, Z0, values, st = gpu_engine.zordschur_batch_(T, Z, np.zeros((0, 3), dtype=bool), infos_out=infos)
+    assert T0 is T and Z0 is Z and values.shape == (0, 3) and values.dtype == np.complex128 and infos == []
+    assert isinstance(st, psd_amd.Stats) and st.nlaunch_step == 0 and st.nsweeps == 0
+    assert gpu_engine.zordschur_batch_stats.nlaunch_step == 0 and gpu_engine.zordschur_batch_stats.nsweeps == 0
+    assert gpu_engine.zordschur_batch_nswaps.shape == (0,) and gpu_engine.zordschur_batch_nswaps.dtype == np.int32
+    T1, Z1, _, _ = gpu_engine.zordschur_batch(T, None, [True] * 3, lr="L", schurindex=2, wantZ=False)
+    assert tuple(T1.shape) == (0, 2, 3, 3) and T1.dtype == torch.complex128 and Z1 is None
+
+
+def test_device_copy_policy(gpu_engine):
+    """what zpschur_batch_ returns is reordered in place; any other layout is copied and stays as it was"""
+    import numpy as np
+    import torch
+
+    rng = np.random.default_rng(8)
+    A = torch.from_numpy(rng.standard_normal((3, 2, 4, 4)) + 1j * rng.standard_normal((3, 2, 4, 4))).cuda()
+    T, Z, values, _ = gpu_engine.zpschur_batch_(A)
+    sels = np.array([zc.median_select(v) for v in values])
+    T1, Z1, values1, _ = gpu_engine.zordschur_batch_(T, Z, sels)
+    assert T1.data_ptr() == T.data_ptr() and Z1.data_ptr() == Z.data_ptr() and T1.stride() == T.stride()
+    Tc, Zc = T1.contiguous(), Z1.contiguous()
+    keepT, keepZ = Tc.clone(), Zc.clone()
+    T2, Z2, _, _ = gpu_engine.zordschur_batch_(Tc, Zc, ~np.array([zc.median_select(v) for v in values1]))
+    assert T2.data_ptr() != Tc.data_ptr() and Z2.data_ptr() != Zc.data_ptr()
+    assert torch.equal(Tc, keepT) and torch.equal(Zc, keepZ) and not torch.equal(T2, Tc)

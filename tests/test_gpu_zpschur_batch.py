@@ -77,3 +77,31 @@ def test_above_the_cap(gpu_engine, lr):
     """order PSD_ZB_NMAX + 1: the single call's reduction, Q formation and iteration, problem by problem on the batch
     buffer"""
     zc.case_full(gpu_engine, (2, _zb_nmax() + 1, 2), lr)
+
+
+def test_empty_device_batch(gpu_engine):
+    """nb = 0: the shapes and dtypes of a call describe themselves, and no kernel runs"""
+    import numpy as np
+    import torch
+
+    dA = torch.zeros((0, 2, 3, 3), dtype=torch.complex128, device="cuda")
+    infos = [7]
+    T, Z, values, st = gpu_engine.zpschur_batch_(dA, infos_out=infos)
+    assert tuple(T.shape) == tuple(Z.shape) == (0, 2, 3, 3) and T.dtype == Z.dtype == torch.complex128 and T.is_cuda
+    assert values.shape == (0, 3) and values.dtype == np.complex128 and infos == []
+    assert isinstance(st, psd_amd.Stats) and st.nlaunch_step == 0 and st.niter == 0
+    assert gpu_engine.zpschur_batch(dA, "L", wantZ=False)[1] is None
+
+
+def test_device_input_is_left(gpu_engine):
+    """the device entry always works on a copy, also of a tensor that already has the layout it works on"""
+    import numpy as np
+    import torch
+
+    rng = np.random.default_rng(6)
+    A = torch.from_numpy(rng.standard_normal((3, 2, 4, 4)) + 1j * rng.standard_normal((3, 2, 4, 4))).cuda()
+    keep = A.clone()
+    for X in (A, A.transpose(2, 3)):  # (contiguous; a transposed view of contiguous blocks)
+        T, Z, values, _ = gpu_engine.zpschur_batch_(X)
+        assert torch.equal(A, keep) and T.data_ptr() != A.data_ptr() and Z.data_ptr() != A.data_ptr()
+        assert not torch.equal(T, X) and values.shape == (3, 4)
