@@ -35,6 +35,7 @@
 #include <climits>
 #include <initializer_list>
 #include <new>
+#include <optional>
 #include <vector>
 
 #ifdef PSD_HOSTSIM
@@ -691,19 +692,6 @@ struct psd_poller {
 #endif
 
 namespace {
-
-void fill_bytes(psd_stats* s, int n, int p, int wantT, int wantZ, const std::vector<int>& log) {
-    if (!s) return;
-    double b = 0.0;
-    const double E = 8.0;
-    for (size_t q = 0; q + 2 < log.size(); q += 3) {
-        if (log[q] != 0) continue;
-        const double w = log[q + 2] - log[q + 1] + 1;
-        if (!wantT) b += 2 * E * p * w * w + (wantZ ? 2 * E * p * w * n : 0.0);
-        else b += 2 * E * p * w * (wantZ ? (2.0 * n + 1) : (n + 1.0));
-    }
-    s->bytes_sweeps = b;
-}
 
 // Which form the multi-stream Hessenberg reductions of this context take (see psd_create): the pipe form needs the
 // fourth stream; PSD_H2_PIPE=2 forces it, =0 forbids it; a period-sharded context always takes it (every rank must
@@ -1661,9 +1649,65 @@ void stats_from_state(psd_stats* s, const psd_rstate& st) {
     s->reserved = st.ntrainsweeps;
 }
 
-// shared tail: run the iteration, fetch eigenvalues / log
+// The code of an iteration that ran to its end, from the info of its device state.
+int state_info_code(int info) {
+    if (info == PSD_LIST_OVERFLOW) return PSD_INFO_RUNTIME + 77;
+    return info != 0 ? PSD_INFO_NOCONV + info : 0;
+}
+
+// Where the eigenvalues of an engine lie on the device and where the caller wants them: a[n] of `asize` bytes each (wr,
+// or the complex alpha), b[n] doubles (wi, or beta) and, for the scaled engines, the exponents (scale null: none).
+struct eig_arrays {
+    const void* da;
+    size_t asize;
+    const double* db;
+    const int* dscale;
+    double *a, *b;
+    int32_t* scale;
+};
+// The sweep log of an engine (dlog null: it keeps none) and how its rows count for bytes_sweeps: E bytes per element,
+// rows of code 0 with `rot0` rotations per position, rows of code 4 (where code4) with one.
+struct sweep_log {
+    const int* dlog;
+    double E;
+    bool code4;
+    double rot0;
+};
+
+// What follows every *iterate_dev: the eigenvalues and the log come down (the log clipped at maxlog rows) behind one
+// wait, bytes_sweeps and the caller's sweeplog are filled from the log, info becomes a code.
+int iteration_tail(psd_ctx* c, int n, int p, int wantT, int wantZ, int nlog, int info, int maxlog, const eig_arrays& ev,
+                   const sweep_log& lg, psd_stats* stats, int32_t* sweeplog, int64_t maxlog_user) {
+    PSD_CHECK(psd_rt_d2h(ev.a, ev.da, ev.asize * n, c->stream));
+    PSD_CHECK(psd_rt_d2h(ev.b, ev.db, sizeof(double) * n, c->stream));
+    std::vector<int> hsc(ev.scale ? n : 0, 0);
+    if (ev.scale) PSD_CHECK(psd_rt_d2h(hsc.data(), ev.dscale, sizeof(int) * n, c->stream));
+    const int nl = !lg.dlog ? 0 : (nlog < maxlog ? nlog : maxlog);
+    std::vector<int> hlog((size_t)3 * nl + 3, 0);
+    if (nl > 0) PSD_CHECK(psd_rt_d2h(hlog.data(), lg.dlog, sizeof(int) * 3 * (size_t)nl, c->stream));
+    PSD_CHECK(psd_rt_sync(c->stream));
+    for (size_t q = 0; q < hsc.size(); ++q) ev.scale[q] = hsc[q];
+    if (stats) {
+        double b = 0.0;
+        for (int q = 0; q < nl; ++q)
+            if (hlog[3 * q] == 0 || (lg.code4 && hlog[3 * q] == 4)) {
+                const double w = hlog[3 * q + 2] - hlog[3 * q + 1] + 1;
+                const double rot = (hlog[3 * q] == 0) ? lg.rot0 : 1.0;
+                if (!wantT) b += rot * 2 * lg.E * p * w * w + (wantZ ? rot * 2 * lg.E * p * w * n : 0.0);
+                else b += rot * 2 * lg.E * p * w * (wantZ ? (2.0 * n + 1) : (n + 1.0));
+            }
+        stats->bytes_sweeps = b;
+    }
+    if (sweeplog) {
+        const int64_t m = nl < maxlog_user ? nl : maxlog_user;
+        for (int64_t q = 0; q < 3 * m; ++q) sweeplog[q] = hlog[q];
+    }
+    return state_info_code(info);
+}
+
+// run the iteration, then the shared tail
 int run_iteration(psd_ctx* c, int n, int p, double* dH, double* dZ, int wantT, int wantZ, int maxitfac, double* wr,
-                  double* wi, psd_stats* stats, int32_t* sweeplog, int64_t maxlog_user, int* info) {
+                  double* wi, psd_stats* stats, int32_t* sweeplog, int64_t maxlog_user) {
     const int maxlog = 2 * maxitfac * n + n + 16;
     if (n == 1) {  // PSD.jl:333-352
         PSD_LAUNCH(psd_scalar_product, psd_dim3(1), 64, 0, c->stream, (const double*)dH, p, c->wr, c->wi);
@@ -1671,30 +1715,14 @@ int run_iteration(psd_ctx* c, int n, int p, double* dH, double* dZ, int wantT, i
         PSD_CHECK(psd_rt_d2h(wr, c->wr, sizeof(double), c->stream));
         PSD_CHECK(psd_rt_d2h(wi, c->wi, sizeof(double), c->stream));
         PSD_CHECK(psd_rt_sync(c->stream));
-        *info = 0;
         return 0;
     }
     psd_rstate st;
-    int rc = iterate_dev(c, n, p, dH, dZ, wantT, wantZ, maxitfac, &st, stats, maxlog);
-    if (rc != 0) {
-        *info = rc;
-        return rc;
-    }
+    if (int rc = iterate_dev(c, n, p, dH, dZ, wantT, wantZ, maxitfac, &st, stats, maxlog)) return rc;
     stats_from_state(stats, st);
-    PSD_CHECK(psd_rt_d2h(wr, c->wr, sizeof(double) * n, c->stream));
-    PSD_CHECK(psd_rt_d2h(wi, c->wi, sizeof(double) * n, c->stream));
-    const int nl = st.nlog < maxlog ? st.nlog : maxlog;
-    std::vector<int> hlog((size_t)3 * nl + 3, 0);
-    if (nl > 0) PSD_CHECK(psd_rt_d2h(hlog.data(), c->log, sizeof(int) * 3 * (size_t)nl, c->stream));
-    PSD_CHECK(psd_rt_sync(c->stream));
-    hlog.resize((size_t)3 * nl);
-    fill_bytes(stats, n, p, wantT, wantZ, hlog);
-    if (sweeplog) {
-        const int64_t m = nl < maxlog_user ? nl : maxlog_user;
-        for (int64_t q = 0; q < 3 * m; ++q) sweeplog[q] = hlog[q];
-    }
-    *info = (st.info == PSD_LIST_OVERFLOW) ? (PSD_INFO_RUNTIME + 77) : ((st.info != 0) ? (PSD_INFO_NOCONV + st.info) : 0);
-    return *info;
+    return iteration_tail(c, n, p, wantT, wantZ, st.nlog, st.info, maxlog,
+                          {c->wr, sizeof(double), c->wi, nullptr, wr, wi, nullptr}, {c->log, 8.0, false, 1.0}, stats, sweeplog,
+                          maxlog_user);
 }
 
 int check_dims(int n, int p) {
@@ -1718,6 +1746,77 @@ int stage_out(psd_ctx* c, T* const* M, const void* dev, int p, size_t bytes, con
     for (int j = 0; j < p; ++j)
         if (int e = psd_rt_d2h(M[slot ? slot[j] : j], (const char*)dev + j * bytes, bytes, c->stream)) return e;
     return 0;
+}
+
+// Prologue and epilogue of every extern "C" single-problem entry: info may be null, the statistics start from zero (the
+// body gets the caller's block, or a scratch one when there is none), a null context is argument 1, and whatever the
+// body returns — an argument code, a PSD_CHECK, the code of a driver — is also *info.
+template <class Body>
+int psd_entry(psd_ctx* c, psd_stats* stats, int* info, Body body) {
+    int code;
+    psd_stats scratch;
+    if (!info) info = &code;
+    if (!stats) stats = &scratch;
+    memset(stats, 0, sizeof(*stats));
+    return *info = c ? body(stats) : -1;
+}
+
+// The matrices of one staged call: the factors T go up and come down; the transformations Z (null: none) come down, and
+// go up first where z_in.  p blocks of `bytes` each; slotT / slotZ as stage_in takes them.  ms_copy (null: the copies
+// are not timed, and no event is made for them): the time of both staging phases, written once they are through.
+// more: one further array that comes down behind the matrices (the reflector scalars).
+struct staged {
+    double* const* T;
+    void* dT;
+    double* const* Z;
+    void* dZ;
+    bool z_in;
+    size_t bytes;
+    const int* slotT = nullptr;
+    const int* slotZ = nullptr;
+    double* ms_copy = nullptr;
+    void* more = nullptr;
+    const void* dmore = nullptr;
+    size_t more_bytes = 0;
+};
+
+// One staged call: the matrices go up, run() works on the device buffers, and unless its code is a hard one (an argument,
+// PSD_INFO_NOTIMPL and above: the device holds nothing worth having) they come down again behind one wait.
+template <class Run>
+int staged_call(psd_ctx* c, int p, const staged& g, Run run) {
+    std::optional<Timer> tc;
+    if (g.ms_copy) tc.emplace();
+    if (tc) tc->start(c->stream);
+    PSD_CHECK(stage_in(c, g.dT, g.T, p, g.bytes, g.slotT));
+    if (g.Z && g.z_in) PSD_CHECK(stage_in(c, g.dZ, g.Z, p, g.bytes, g.slotZ));
+    const double ms_in = tc ? tc->stop(c->stream) : 0.0;
+    const int rc = run();
+    if (rc < 0 || rc >= PSD_INFO_NOTIMPL) return rc;
+    if (tc) tc->start(c->stream);
+    PSD_CHECK(stage_out(c, g.T, g.dT, p, g.bytes, g.slotT));
+    if (g.Z) PSD_CHECK(stage_out(c, g.Z, g.dZ, p, g.bytes, g.slotZ));
+    if (g.more) PSD_CHECK(psd_rt_d2h(g.more, g.dmore, g.more_bytes, c->stream));
+    PSD_CHECK(psd_rt_sync(c->stream));
+    if (tc) *g.ms_copy = ms_in + tc->stop(c->stream);
+    return rc;
+}
+
+// The working order of a signed entry: slot maps as ord_slots makes them and the signature in that order (S null: all
+// true).  -7: schurindex not in (1, p); -5: the entry of S that lands leftmost is false (generalized.jl:140,
+// rgeneralized.jl:37).
+struct signed_order {
+    std::vector<int> sA, sZ;
+    std::vector<uint8_t> S;
+    bool alltrue = true;
+};
+int signed_slots(char orient, int schurindex, int p, const uint8_t* S, signed_order& o) {
+    if (!ord_slots(orient, schurindex, p, o.sA, o.sZ)) return -7;
+    o.S.assign(p, 1);
+    for (int j = 0; j < p; ++j) {
+        o.S[j] = (!S || S[o.sA[j]]) ? 1 : 0;
+        o.alltrue = o.alltrue && o.S[j];
+    }
+    return o.S[0] ? 0 : -5;
 }
 
 }  // namespace
@@ -1948,150 +2047,177 @@ int psd_set_profile(psd_ctx* c, int profile) {
 }
 
 int psd_d_phessenberg(psd_ctx* c, int n, int p, double* const* A, double* tau, psd_stats* stats, int* info) {
-    int dummy;
-    if (!info) info = &dummy;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (!c) return *info = -1;
-    if ((*info = check_dims(n, p)) != 0) return *info;
-    if (!A || !tau) return *info = -4;
-    const int maxlog = 16;
-    if ((*info = c->reserve(n, p, true, maxlog)) != 0) return *info;
-    const size_t nn = (size_t)n * n;
-    Timer tc, tk;
-    tc.start(c->stream);
-    PSD_CHECK(stage_in(c, c->dH, A, p, nn * 8));
-    double ms_copy = tc.stop(c->stream);
-    tk.start(c->stream);
-    if ((*info = hessenberg_dev(c, n, p, c->dH, c->tau)) != 0) return *info;
-    double ms = tk.stop(c->stream);
-    tc.start(c->stream);
-    PSD_CHECK(stage_out(c, A, c->dH, p, nn * 8));
-    PSD_CHECK(psd_rt_d2h(tau, c->tau, sizeof(double) * (size_t)n * p, c->stream));
-    PSD_CHECK(psd_rt_sync(c->stream));
-    ms_copy += tc.stop(c->stream);
-    PSD_CHECK(psd_rt_last_error());
-    if (stats) {
-        stats->ms_hess = ms;
-        stats->ms_total = ms;
-        stats->ms_copy = ms_copy;
-        stats->bytes_hess = 2.0 * 8.0 * p * (5.0 / 6.0) * (double)n * n * n;
-    }
-    return *info = 0;
+    return psd_entry(c, stats, info, [&](psd_stats* s) -> int {
+        if (int e = check_dims(n, p)) return e;
+        if (!A || !tau) return -4;
+        if (int e = c->reserve(n, p, true, 16)) return e;
+        double ms = 0.0;
+        staged g{A, c->dH, nullptr, nullptr, false, (size_t)n * n * 8};
+        g.ms_copy = &s->ms_copy;
+        g.more = tau;
+        g.dmore = c->tau;
+        g.more_bytes = sizeof(double) * (size_t)n * p;
+        if (int rc = staged_call(c, p, g, [&] {
+                Timer tk;
+                tk.start(c->stream);
+                const int rc = hessenberg_dev(c, n, p, c->dH, c->tau);
+                if (rc == 0) ms = tk.stop(c->stream);
+                return rc;
+            }))
+            return rc;
+        PSD_CHECK(psd_rt_last_error());
+        s->ms_hess = s->ms_total = ms;
+        s->bytes_hess = 2.0 * 8.0 * p * (5.0 / 6.0) * (double)n * n * n;
+        return 0;
+    });
 }
 
-int psd_d_pschur_dev(psd_ctx* c, int n, int p, double* dA, char orient, int wantT, int wantZ, int maxitfac, double* dZ,
-                     double* wr, double* wi, int* schurindex, psd_stats* stats, int32_t* sweeplog, int64_t maxlog,
-                     int* info) {
-    int dummy;
-    if (!info) info = &dummy;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (!c) return *info = -1;
-    if ((*info = check_dims(n, p)) != 0) return *info;
-    if (!dA) return *info = -4;
-    if (orient != 'R' && orient != 'L') return *info = -5;  // PSD.jl:175-177
-    if (maxitfac < 1) return *info = -8;
-    if (wantZ && !dZ) return *info = -9;
-    if (!wr || !wi) return *info = -10;
+}  // extern "C"
+
+namespace {
+
+// (the ComplexF64 drivers, defined with the complex path below)
+int zhessenberg_dev(psd_ctx* c, int n, int p, psd_z* dH, psd_z* dtau);
+int zformq_dev(psd_ctx* c, int n, int p, const psd_z* dH, const psd_z* dtau, psd_z* dQ);
+int zrun_iteration(psd_ctx* c, int n, int p, psd_z* dH, psd_z* dZ, int wantT, int wantZ, int maxitfac, double* alpha,
+                   double* beta, int32_t* ascale, psd_stats* stats, int32_t* sweeplog, int64_t maxlog_user);
+
+// What psd_d_pschur_dev and psd_z_pschur_dev differ in: the element, the drivers of the three phases, the workspace.
+// Eig: the caller's eigenvalue arrays as the iteration takes them.
+struct pschur_real {
+    typedef double T;
+    struct Eig {
+        double *wr, *wi;
+    };
+    static constexpr double E = 8.0;
+    static constexpr int ROWS = 1;  // rows of doubles per matrix row, for psd_reverse_blocks
+    static int reserve(psd_ctx* c, int n, int p, int mlog) { return c->reserve(n, p, false, mlog); }
+    static T* tau(psd_ctx* c) { return c->tau; }
+    static int hess(psd_ctx* c, int n, int p, T* dA, T* tau) { return hessenberg_dev(c, n, p, dA, tau); }
+    static int formq(psd_ctx* c, int n, int p, const T* dA, const T* tau, T* dQ) { return formq_dev(c, n, p, dA, tau, dQ); }
+    static void triu(psd_ctx* c, int n, int p, T* dA) { PSD_LAUNCH(psd_triu, psd_dim3(n, p), 64, 0, c->stream, dA, n); }
+    static int iterate(psd_ctx* c, int n, int p, T* dA, T* dZ, int wantT, int wantZ, int maxitfac, const Eig& e,
+                       psd_stats* s, int32_t* sweeplog, int64_t maxlog) {
+        return run_iteration(c, n, p, dA, dZ, wantT, wantZ, maxitfac, e.wr, e.wi, s, sweeplog, maxlog);
+    }
+};
+struct pschur_cplx {
+    typedef psd_z T;
+    struct Eig {
+        double *alpha, *beta;
+        int32_t* ascale;
+    };
+    static constexpr double E = 16.0;
+    static constexpr int ROWS = 2;
+    static int reserve(psd_ctx* c, int n, int p, int mlog) { return c->zreserve(n, p, false, mlog); }
+    static T* tau(psd_ctx* c) { return c->ztau; }
+    static int hess(psd_ctx* c, int n, int p, T* dA, T* tau) { return zhessenberg_dev(c, n, p, dA, tau); }
+    static int formq(psd_ctx* c, int n, int p, const T* dA, const T* tau, T* dQ) { return zformq_dev(c, n, p, dA, tau, dQ); }
+    static void triu(psd_ctx* c, int n, int p, T* dA) { PSD_LAUNCH(psd_ztriu, psd_dim3(n, p), 64, 0, c->stream, dA, n); }
+    static int iterate(psd_ctx* c, int n, int p, T* dA, T* dZ, int wantT, int wantZ, int maxitfac, const Eig& e,
+                       psd_stats* s, int32_t* sweeplog, int64_t maxlog) {
+        return zrun_iteration(c, n, p, dA, dZ, wantT, wantZ, maxitfac, e.alpha, e.beta, e.ascale, s, sweeplog, maxlog);
+    }
+};
+
+// pschur!(A, lr) on operands that lie on the device: the body of psd_d_pschur_dev and psd_z_pschur_dev behind their
+// argument checks.  Reduction, Q, iteration, each timed with the stream's events; 'L' works on the reversed sequence
+// (PSD.jl:127-131) and undoes the reversal at the end: Z_1 stays, Z_2..Z_p reverse (PSD.jl:1078-1092).
+template <class K>
+int pschur_dev_body(psd_ctx* c, int n, int p, typename K::T* dA, char orient, int wantT, int wantZ, int maxitfac,
+                    typename K::T* dZ, const typename K::Eig& eig, int* schurindex, psd_stats* s, int32_t* sweeplog,
+                    int64_t maxlog) {
     const bool left = orient == 'L';
-    const int mlog = 2 * maxitfac * n + n + 16;
-    if ((*info = c->reserve(n, p, false, mlog)) != 0) return *info;
+    if (int e = K::reserve(c, n, p, 2 * maxitfac * n + n + 16)) return e;
+    double* const rA = reinterpret_cast<double*>(dA);
+    double* const rZ = reinterpret_cast<double*>(dZ);
     Timer tall, tph;
     tall.start(c->stream);
-    // PSD.jl:127-131: 'L' works on the reversed sequence
-    if (left && p > 1) PSD_LAUNCH(psd_reverse_blocks, psd_dim3(n, p / 2), 64, 0, c->stream, dA, n, n, 0, p);
+    if (left && p > 1) PSD_LAUNCH(psd_reverse_blocks, psd_dim3(n, p / 2), 64, 0, c->stream, rA, K::ROWS * n, n, 0, p);
     tph.start(c->stream);
-    if ((*info = hessenberg_dev(c, n, p, dA, c->tau)) != 0) return *info;
+    if (int e = K::hess(c, n, p, dA, K::tau(c))) return e;
     const double ms_hess = tph.stop(c->stream);
     tph.start(c->stream);
-    if (wantZ) {
-        if ((*info = formq_dev(c, n, p, dA, c->tau, dZ)) != 0) return *info;
-    }
-    PSD_LAUNCH(psd_triu, psd_dim3(n, p), 64, 0, c->stream, dA, n);
+    if (wantZ)
+        if (int e = K::formq(c, n, p, dA, K::tau(c), dZ)) return e;
+    K::triu(c, n, p, dA);
     const double ms_formq = tph.stop(c->stream);
     tph.start(c->stream);
-    psd_stats local;
-    memset(&local, 0, sizeof(local));
-    psd_stats* s = stats ? stats : &local;
-    int rc = run_iteration(c, n, p, dA, dZ, wantT, wantZ, maxitfac, wr, wi, s, sweeplog, maxlog, info);
+    const int rc = K::iterate(c, n, p, dA, dZ, wantT, wantZ, maxitfac, eig, s, sweeplog, maxlog);
     const double ms_iter = tph.stop(c->stream);
-    // PSD.jl:1078-1092: undo the reversal; Z_1 stays, Z_2..Z_p reverse
     if (left && p > 1) {
-        PSD_LAUNCH(psd_reverse_blocks, psd_dim3(n, p / 2), 64, 0, c->stream, dA, n, n, 0, p);
-        if (wantZ && p > 2) PSD_LAUNCH(psd_reverse_blocks, psd_dim3(n, (p - 1) / 2), 64, 0, c->stream, dZ, n, n, 1, p - 1);
+        PSD_LAUNCH(psd_reverse_blocks, psd_dim3(n, p / 2), 64, 0, c->stream, rA, K::ROWS * n, n, 0, p);
+        if (wantZ && p > 2)
+            PSD_LAUNCH(psd_reverse_blocks, psd_dim3(n, (p - 1) / 2), 64, 0, c->stream, rZ, K::ROWS * n, n, 1, p - 1);
     }
     s->ms_hess = ms_hess;
     s->ms_formq = ms_formq;
     s->ms_iter = ms_iter;
     s->ms_total = tall.stop(c->stream);
-    s->bytes_hess = 2.0 * 8.0 * p * (5.0 / 6.0) * (double)n * n * n;
-    s->bytes_formq = wantZ ? 2.0 * 8.0 * p * (double)n * n * n / 3.0 : 0.0;
+    s->bytes_hess = 2.0 * K::E * p * (5.0 / 6.0) * (double)n * n * n;
+    s->bytes_formq = wantZ ? 2.0 * K::E * p * (double)n * n * n / 3.0 : 0.0;
     if (schurindex) *schurindex = left ? p : 1;
     return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int psd_d_pschur_dev(psd_ctx* c, int n, int p, double* dA, char orient, int wantT, int wantZ, int maxitfac, double* dZ,
+                     double* wr, double* wi, int* schurindex, psd_stats* stats, int32_t* sweeplog, int64_t maxlog,
+                     int* info) {
+    return psd_entry(c, stats, info, [&](psd_stats* s) -> int {
+        if (int e = check_dims(n, p)) return e;
+        if (!dA) return -4;
+        if (orient != 'R' && orient != 'L') return -5;  // PSD.jl:175-177
+        if (maxitfac < 1) return -8;
+        if (wantZ && !dZ) return -9;
+        if (!wr || !wi) return -10;
+        return pschur_dev_body<pschur_real>(c, n, p, dA, orient, wantT, wantZ, maxitfac, dZ, {wr, wi}, schurindex, s,
+                                            sweeplog, maxlog);
+    });
 }
 
 int psd_d_pschur(psd_ctx* c, int n, int p, double* const* A, const uint8_t* S, char orient, int wantT, int wantZ,
                  int maxitfac, double* const* Z, double* wr, double* wi, int* schurindex, psd_stats* stats,
                  int32_t* sweeplog, int64_t maxlog, int* info) {
-    int dummy;
-    if (!info) info = &dummy;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (!c) return *info = -1;
-    if ((*info = check_dims(n, p)) != 0) return *info;
-    if (!A) return *info = -4;
-    if (S)
-        for (int j = 0; j < p; ++j)
-            if (!S[j]) return *info = PSD_INFO_NOTIMPL;  // signed case: src/rgeneralized.jl (not in this build)
-    if (orient != 'R' && orient != 'L') return *info = -6;
-    if (wantZ && !Z) return *info = -10;
-    const int mlog = 2 * (maxitfac > 0 ? maxitfac : 1) * n + n + 16;
-    if ((*info = c->reserve(n, p, true, mlog)) != 0) return *info;
-    const size_t nn = (size_t)n * n;
-    Timer tc;
-    tc.start(c->stream);
-    PSD_CHECK(stage_in(c, c->dH, A, p, nn * 8));
-    double ms_copy = tc.stop(c->stream);
-    psd_stats local;
-    psd_stats* s = stats ? stats : &local;
-    int rc = psd_d_pschur_dev(c, n, p, c->dH, orient, wantT, wantZ, maxitfac, wantZ ? c->dZ : nullptr, wr, wi,
-                              schurindex, s, sweeplog, maxlog, info);
-    if (rc < 0 || rc >= PSD_INFO_NOTIMPL) return rc;
-    tc.start(c->stream);
-    PSD_CHECK(stage_out(c, A, c->dH, p, nn * 8));
-    if (wantZ) PSD_CHECK(stage_out(c, Z, c->dZ, p, nn * 8));
-    PSD_CHECK(psd_rt_sync(c->stream));
-    ms_copy += tc.stop(c->stream);
-    s->ms_copy = ms_copy;
-    return rc;
+    return psd_entry(c, stats, info, [&](psd_stats* s) -> int {
+        if (int e = check_dims(n, p)) return e;
+        if (!A) return -4;
+        if (S)
+            for (int j = 0; j < p; ++j)
+                if (!S[j]) return PSD_INFO_NOTIMPL;  // signed case: src/rgeneralized.jl (psd_d_gpschur)
+        if (orient != 'R' && orient != 'L') return -6;
+        if (wantZ && !Z) return -10;
+        if (int e = c->reserve(n, p, true, 2 * (maxitfac > 0 ? maxitfac : 1) * n + n + 16)) return e;
+        staged g{A, c->dH, wantZ ? Z : nullptr, c->dZ, false, (size_t)n * n * 8};
+        g.ms_copy = &s->ms_copy;
+        return staged_call(c, p, g, [&] {  // (the device entry starts the statistics afresh and checks the rest)
+            return psd_d_pschur_dev(c, n, p, c->dH, orient, wantT, wantZ, maxitfac, wantZ ? c->dZ : nullptr, wr, wi,
+                                    schurindex, s, sweeplog, maxlog, nullptr);
+        });
+    });
 }
 
 int psd_d_pschur_hess(psd_ctx* c, int n, int p, double* const* H, double* const* Q, int wantT, int wantZ, int maxitfac,
                       double* wr, double* wi, psd_stats* stats, int32_t* sweeplog, int64_t maxlog, int* info) {
-    int dummy;
-    if (!info) info = &dummy;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (!c) return *info = -1;
-    if ((*info = check_dims(n, p)) != 0) return *info;
-    if (!H) return *info = -4;
-    if (wantZ && !Q) return *info = -5;
-    if (maxitfac < 1) return *info = -8;
-    const int mlog = 2 * maxitfac * n + n + 16;
-    if ((*info = c->reserve(n, p, true, mlog)) != 0) return *info;
-    const size_t nn = (size_t)n * n;
-    PSD_CHECK(stage_in(c, c->dH, H, p, nn * 8));
-    if (wantZ) PSD_CHECK(stage_in(c, c->dZ, Q, p, nn * 8));
-    psd_stats local;
-    memset(&local, 0, sizeof(local));
-    psd_stats* s = stats ? stats : &local;
-    Timer t;
-    t.start(c->stream);
-    int rc = run_iteration(c, n, p, c->dH, wantZ ? c->dZ : nullptr, wantT, wantZ, maxitfac, wr, wi, s, sweeplog, maxlog,
-                           info);
-    s->ms_iter = s->ms_total = t.stop(c->stream);
-    if (rc < 0 || rc >= PSD_INFO_NOTIMPL) return rc;
-    PSD_CHECK(stage_out(c, H, c->dH, p, nn * 8));
-    if (wantZ) PSD_CHECK(stage_out(c, Q, c->dZ, p, nn * 8));
-    PSD_CHECK(psd_rt_sync(c->stream));
-    return rc;
+    return psd_entry(c, stats, info, [&](psd_stats* s) -> int {
+        if (int e = check_dims(n, p)) return e;
+        if (!H) return -4;
+        if (wantZ && !Q) return -5;
+        if (maxitfac < 1) return -8;
+        if (int e = c->reserve(n, p, true, 2 * maxitfac * n + n + 16)) return e;
+        staged g{H, c->dH, wantZ ? Q : nullptr, c->dZ, true, (size_t)n * n * 8};
+        return staged_call(c, p, g, [&] {
+            Timer t;
+            t.start(c->stream);
+            const int rc = run_iteration(c, n, p, c->dH, wantZ ? c->dZ : nullptr, wantT, wantZ, maxitfac, wr, wi, s, sweeplog,
+                                         maxlog);
+            s->ms_iter = s->ms_total = t.stop(c->stream);
+            return rc;
+        });
+    });
 }
 
 }  // extern "C"
@@ -2421,50 +2547,27 @@ int ziterate_dev(psd_ctx* c, int n, int p, psd_z* dH, psd_z* dZ, int wantT, int 
     return 0;
 }
 
+void stats_from_state(psd_stats* s, const psd_zstate& st) {
+    if (!s) return;
+    s->niter = st.jiter;
+    s->nsweeps = st.nsweeps;
+    s->nrqpass = st.nzshift;
+    s->ndefl1 = st.nsplit;
+    s->ndefl2 = st.ncase2;
+    s->nwindows = st.nwindows;
+    s->nlog = st.nlog;
+    for (int q = 0; q < 6; ++q) s->step_cycles[q] = st.cyc[q];
+}
+
 int zrun_iteration(psd_ctx* c, int n, int p, psd_z* dH, psd_z* dZ, int wantT, int wantZ, int maxitfac, double* alpha,
-                   double* beta, int32_t* ascale, psd_stats* stats, int32_t* sweeplog, int64_t maxlog_user, int* info) {
+                   double* beta, int32_t* ascale, psd_stats* stats, int32_t* sweeplog, int64_t maxlog_user) {
     const int maxlog = 2 * maxitfac * n + n + 16;
     psd_zstate st;
-    int rc = ziterate_dev(c, n, p, dH, dZ, wantT, wantZ, maxitfac, &st, stats, maxlog);
-    if (rc != 0) {
-        *info = rc;
-        return rc;
-    }
-    if (stats) {
-        stats->niter = st.jiter;
-        stats->nsweeps = st.nsweeps;
-        stats->nrqpass = st.nzshift;
-        stats->ndefl1 = st.nsplit;
-        stats->ndefl2 = st.ncase2;
-        stats->nwindows = st.nwindows;
-        stats->nlog = st.nlog;
-        for (int q = 0; q < 6; ++q) stats->step_cycles[q] = st.cyc[q];
-    }
-    PSD_CHECK(psd_rt_d2h(alpha, c->zalpha, sizeof(psd_z) * n, c->stream));
-    PSD_CHECK(psd_rt_d2h(beta, c->zbeta, sizeof(double) * n, c->stream));
-    std::vector<int> hsc(n, 0);
-    PSD_CHECK(psd_rt_d2h(hsc.data(), c->zascale, sizeof(int) * n, c->stream));
-    const int nl = st.nlog < maxlog ? st.nlog : maxlog;
-    std::vector<int> hlog((size_t)3 * nl + 3, 0);
-    if (nl > 0) PSD_CHECK(psd_rt_d2h(hlog.data(), c->zlog, sizeof(int) * 3 * (size_t)nl, c->stream));
-    PSD_CHECK(psd_rt_sync(c->stream));
-    for (int q = 0; q < n; ++q) ascale[q] = hsc[q];
-    if (stats) {  // algorithmic bytes of the sweeps, E = 16
-        double b = 0.0;
-        for (int q = 0; q < nl; ++q)
-            if (hlog[3 * q] == 0 || hlog[3 * q] == 4) {
-                const double w = hlog[3 * q + 2] - hlog[3 * q + 1] + 1;
-                if (!wantT) b += 2 * 16.0 * p * w * w + (wantZ ? 2 * 16.0 * p * w * n : 0.0);
-                else b += 2 * 16.0 * p * w * (wantZ ? (2.0 * n + 1) : (n + 1.0));
-            }
-        stats->bytes_sweeps = b;
-    }
-    if (sweeplog) {
-        const int64_t m = nl < maxlog_user ? nl : maxlog_user;
-        for (int64_t q = 0; q < 3 * m; ++q) sweeplog[q] = hlog[q];
-    }
-    *info = (st.info == PSD_LIST_OVERFLOW) ? (PSD_INFO_RUNTIME + 77) : ((st.info != 0) ? (PSD_INFO_NOCONV + st.info) : 0);
-    return *info;
+    if (int rc = ziterate_dev(c, n, p, dH, dZ, wantT, wantZ, maxitfac, &st, stats, maxlog)) return rc;
+    stats_from_state(stats, st);
+    return iteration_tail(c, n, p, wantT, wantZ, st.nlog, st.info, maxlog,
+                          {c->zalpha, sizeof(psd_z), c->zbeta, c->zascale, alpha, beta, ascale}, {c->zlog, 16.0, true, 1.0},
+                          stats, sweeplog, maxlog_user);
 }
 
 }  // namespace
@@ -2596,30 +2699,29 @@ int zgiterate_dev(psd_ctx* c, int n, int p, psd_z* dH, psd_z* dZ, const uint8_t*
     return 0;
 }
 
+void stats_from_state(psd_stats* s, const psd_zgstate& st) {
+    if (!s) return;
+    s->niter = st.jiter;
+    s->nsweeps = st.nsweeps;
+    s->nrqpass = st.nzshift;
+    s->ndefl1 = st.nsplit;
+    s->ndefl2 = st.ncase2;
+    s->reserved = st.ncase2 + 1000 * st.ncase3;
+    s->maxits = st.ntrainsweeps;  // (signed path: sweeps that ran inside multishift trains)
+    s->nwindows = st.nwindows;
+    s->nlog = st.nlog;
+}
+
+// (the complex signed engine hands no sweep log to the host)
 int zgrun_iteration(psd_ctx* c, int n, int p, psd_z* dH, psd_z* dZ, const uint8_t* S, int wantT, int wantZ,
-                    int maxitfac, double* alpha, double* beta, int32_t* ascale, psd_stats* stats, int* info) {
+                    int maxitfac, double* alpha, double* beta, int32_t* ascale, psd_stats* stats) {
     const int maxlog = 2 * maxitfac * n + n + 16;
     psd_zgstate st;
-    int rc = zgiterate_dev(c, n, p, dH, dZ, S, wantT, wantZ, maxitfac, &st, stats, maxlog, 0);
-    if (rc != 0) return *info = rc;
-    if (stats) {
-        stats->niter = st.jiter;
-        stats->nsweeps = st.nsweeps;
-        stats->nrqpass = st.nzshift;
-        stats->ndefl1 = st.nsplit;
-        stats->ndefl2 = st.ncase2;
-        stats->reserved = st.ncase2 + 1000 * st.ncase3;
-        stats->maxits = st.ntrainsweeps;  // (signed path: sweeps that ran inside multishift trains)
-        stats->nwindows = st.nwindows;
-        stats->nlog = st.nlog;
-    }
-    PSD_CHECK(psd_rt_d2h(alpha, c->zalpha, sizeof(psd_z) * n, c->stream));
-    PSD_CHECK(psd_rt_d2h(beta, c->zbeta, sizeof(double) * n, c->stream));
-    std::vector<int> hsc(n, 0);
-    PSD_CHECK(psd_rt_d2h(hsc.data(), c->zascale, sizeof(int) * n, c->stream));
-    PSD_CHECK(psd_rt_sync(c->stream));
-    for (int q = 0; q < n; ++q) ascale[q] = hsc[q];
-    return *info = (st.info == PSD_LIST_OVERFLOW) ? (PSD_INFO_RUNTIME + 77) : ((st.info != 0) ? (PSD_INFO_NOCONV + st.info) : 0);
+    if (int rc = zgiterate_dev(c, n, p, dH, dZ, S, wantT, wantZ, maxitfac, &st, stats, maxlog, 0)) return rc;
+    stats_from_state(stats, st);
+    return iteration_tail(c, n, p, wantT, wantZ, st.nlog, st.info, maxlog,
+                          {c->zalpha, sizeof(psd_z), c->zbeta, c->zascale, alpha, beta, ascale}, {nullptr, 16.0, true, 1.0},
+                          stats, nullptr, 0);
 }
 
 // _phessenberg!(A, S; wantQ) for ComplexF64 on device — generalized.jl:988-1082
@@ -2679,68 +2781,47 @@ int zsghess_dev(psd_ctx* c, int n, int p, psd_z* dA, psd_z* dQ, const uint8_t* S
     return rc;
 }
 
-// pschur!(A, S, lr) for ComplexF64 with a signed S — generalized.jl:108-148
+// pschur!(A, S, lr) for ComplexF64 with a signed S — generalized.jl:108-148: the signed Hessenberg reduction, then the
+// signed periodic QZ, in working order (the reversal of generalized.jl:910-927 for 'L', the identity for 'R')
 int zsigned_pschur_host(psd_ctx* c, int n, int p, double* const* A, const uint8_t* S, char orient, int wantT, int wantZ,
                         int maxitfac, double* const* Z, double* alpha, double* beta, int32_t* ascale, int* schurindex,
-                        psd_stats* stats, int* info) {
-    if (maxitfac < 1) return *info = -9;
+                        psd_stats* s) {
+    if (maxitfac < 1) return -9;
     const bool left = orient == 'L';
-    std::vector<int> sA, sZ;  // the reversal of generalized.jl:910-927 for 'L' (schurindex p), the identity for 'R'
-    ord_slots(orient, left ? p : 1, p, sA, sZ);
-    std::vector<uint8_t> Sarg(p, 1);
-    for (int j = 0; j < p; ++j) Sarg[j] = S[sA[j]] ? 1 : 0;
-    if (!Sarg[0]) return *info = -5;  // generalized.jl:140
-    const int mlog = 2 * maxitfac * n + n + 16;
-    if ((*info = c->zreserve(n, p, true, mlog)) != 0) return *info;
-    if ((*info = c->zgreserve(n, p)) != 0) return *info;
-    const size_t nn = (size_t)n * n;
-    PSD_CHECK(stage_in(c, c->zH, A, p, nn * 16, sA.data()));
-    psd_stats local;
-    memset(&local, 0, sizeof(local));
-    psd_stats* s = stats ? stats : &local;
-    Timer tt;
-    tt.start(c->stream);
-    if ((*info = zsghess_dev(c, n, p, c->zH, wantZ ? c->zZ : nullptr, Sarg.data(), s)) != 0) return *info;
-    const double keep_hess = s->ms_hess, keep_formq = s->ms_formq, keep_bh = s->bytes_hess;
-    Timer ti;
-    ti.start(c->stream);
-    int rc = zgrun_iteration(c, n, p, c->zH, wantZ ? c->zZ : nullptr, Sarg.data(), wantT, wantZ, maxitfac, alpha, beta,
-                             ascale, s, info);
-    s->ms_hess = keep_hess;
-    s->ms_formq = keep_formq;
-    s->bytes_hess = keep_bh;
-    s->ms_iter = ti.stop(c->stream);
-    s->ms_total = tt.stop(c->stream);
-    if (schurindex) *schurindex = left ? p : 1;
-    if (rc < 0 || rc >= PSD_INFO_NOTIMPL) return rc;
-    PSD_CHECK(stage_out(c, A, c->zH, p, nn * 16, sA.data()));
-    if (wantZ) PSD_CHECK(stage_out(c, Z, c->zZ, p, nn * 16, sZ.data()));
-    PSD_CHECK(psd_rt_sync(c->stream));
-    return rc;
+    signed_order o;
+    if (int e = signed_slots(orient, left ? p : 1, p, S, o)) return e;
+    if (int e = c->zreserve(n, p, true, 2 * maxitfac * n + n + 16)) return e;
+    if (int e = c->zgreserve(n, p)) return e;
+    staged g{A, c->zH, wantZ ? Z : nullptr, c->zZ, false, (size_t)n * n * 16, o.sA.data(), o.sZ.data()};
+    return staged_call(c, p, g, [&]() -> int {
+        Timer tt;
+        tt.start(c->stream);
+        if (int e = zsghess_dev(c, n, p, c->zH, wantZ ? c->zZ : nullptr, o.S.data(), s)) return e;
+        Timer ti;
+        ti.start(c->stream);
+        const int rc = zgrun_iteration(c, n, p, c->zH, wantZ ? c->zZ : nullptr, o.S.data(), wantT, wantZ, maxitfac, alpha,
+                                       beta, ascale, s);
+        s->ms_iter = ti.stop(c->stream);
+        s->ms_total = tt.stop(c->stream);
+        if (schurindex) *schurindex = left ? p : 1;
+        return rc;
+    });
 }
 
 // pschur!(H1, Hs, S; ...) for ComplexF64 with a signed S — generalized.jl:166-931
 int zsigned_hess_host(psd_ctx* c, int n, int p, double* const* H, const uint8_t* S, double* const* Q, int wantT,
-                      int wantZ, int maxitfac, double* alpha, double* beta, int32_t* ascale, psd_stats* stats, int* info) {
-    const int mlog = 2 * maxitfac * n + n + 16;
-    if ((*info = c->zreserve(n, p, true, mlog)) != 0) return *info;
-    if ((*info = c->zgreserve(n, p)) != 0) return *info;
-    const size_t nn = (size_t)n * n;
-    PSD_CHECK(stage_in(c, c->zH, H, p, nn * 16));
-    if (wantZ) PSD_CHECK(stage_in(c, c->zZ, Q, p, nn * 16));
-    psd_stats local;
-    memset(&local, 0, sizeof(local));
-    psd_stats* s = stats ? stats : &local;
-    Timer t;
-    t.start(c->stream);
-    int rc = zgrun_iteration(c, n, p, c->zH, wantZ ? c->zZ : nullptr, S, wantT, wantZ, maxitfac, alpha, beta, ascale, s,
-                             info);
-    s->ms_iter = s->ms_total = t.stop(c->stream);
-    if (rc < 0 || rc >= PSD_INFO_NOTIMPL) return rc;
-    PSD_CHECK(stage_out(c, H, c->zH, p, nn * 16));
-    if (wantZ) PSD_CHECK(stage_out(c, Q, c->zZ, p, nn * 16));
-    PSD_CHECK(psd_rt_sync(c->stream));
-    return rc;
+                      int wantZ, int maxitfac, double* alpha, double* beta, int32_t* ascale, psd_stats* s) {
+    if (int e = c->zreserve(n, p, true, 2 * maxitfac * n + n + 16)) return e;
+    if (int e = c->zgreserve(n, p)) return e;
+    staged g{H, c->zH, wantZ ? Q : nullptr, c->zZ, true, (size_t)n * n * 16};
+    return staged_call(c, p, g, [&] {
+        Timer t;
+        t.start(c->stream);
+        const int rc = zgrun_iteration(c, n, p, c->zH, wantZ ? c->zZ : nullptr, S, wantT, wantZ, maxitfac, alpha, beta,
+                                       ascale, s);
+        s->ms_iter = s->ms_total = t.stop(c->stream);
+        return rc;
+    });
 }
 
 }  // namespace
@@ -2750,174 +2831,107 @@ extern "C" {
 // _phessenberg!(A, S) for ComplexF64 — generalized.jl:988-1082
 int psd_z_gphessenberg(psd_ctx* c, int n, int p, double* const* A, const uint8_t* S, double* const* Q, psd_stats* stats,
                        int* info) {
-    int dummy;
-    if (!info) info = &dummy;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (!c) return *info = -1;
-    if ((*info = check_dims(n, p)) != 0) return *info;
-    if (!A) return *info = -4;
-    if (S && !S[0]) return *info = -5;
-    if ((*info = c->zreserve(n, p, true, 16)) != 0) return *info;
-    if ((*info = c->zgreserve(n, p)) != 0) return *info;
-    const size_t nn = (size_t)n * n;
-    PSD_CHECK(stage_in(c, c->zH, A, p, nn * 16));
-    *info = zsghess_dev(c, n, p, c->zH, Q ? c->zZ : nullptr, S, stats);
-    if (*info != 0) return *info;
-    PSD_CHECK(stage_out(c, A, c->zH, p, nn * 16));
-    if (Q) PSD_CHECK(stage_out(c, Q, c->zZ, p, nn * 16));
-    PSD_CHECK(psd_rt_sync(c->stream));
-    return 0;
+    return psd_entry(c, stats, info, [&](psd_stats* s) -> int {
+        if (int e = check_dims(n, p)) return e;
+        if (!A) return -4;
+        if (S && !S[0]) return -5;
+        if (int e = c->zreserve(n, p, true, 16)) return e;
+        if (int e = c->zgreserve(n, p)) return e;
+        staged g{A, c->zH, Q, c->zZ, false, (size_t)n * n * 16};
+        return staged_call(c, p, g, [&] { return zsghess_dev(c, n, p, c->zH, Q ? c->zZ : nullptr, S, s); });
+    });
 }
 
 int psd_z_phessenberg(psd_ctx* c, int n, int p, double* const* A, double* tau, psd_stats* stats, int* info) {
-    int dummy;
-    if (!info) info = &dummy;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (!c) return *info = -1;
-    if ((*info = check_dims(n, p)) != 0) return *info;
-    if (!A || !tau) return *info = -4;
-    if ((*info = c->zreserve(n, p, true, 16)) != 0) return *info;
-    const size_t nn = (size_t)n * n;
-    PSD_CHECK(stage_in(c, c->zH, A, p, nn * 16));
-    Timer tk;
-    tk.start(c->stream);
-    if ((*info = zhessenberg_dev(c, n, p, c->zH, c->ztau)) != 0) return *info;
-    const double ms = tk.stop(c->stream);
-    PSD_CHECK(stage_out(c, A, c->zH, p, nn * 16));
-    PSD_CHECK(psd_rt_d2h(tau, c->ztau, sizeof(psd_z) * (size_t)n * p, c->stream));
-    PSD_CHECK(psd_rt_sync(c->stream));
-    PSD_CHECK(psd_rt_last_error());
-    if (stats) {
-        stats->ms_hess = stats->ms_total = ms;
-        stats->bytes_hess = 2.0 * 16.0 * p * (5.0 / 6.0) * (double)n * n * n;
-    }
-    return *info = 0;
+    return psd_entry(c, stats, info, [&](psd_stats* s) -> int {
+        if (int e = check_dims(n, p)) return e;
+        if (!A || !tau) return -4;
+        if (int e = c->zreserve(n, p, true, 16)) return e;
+        double ms = 0.0;
+        staged g{A, c->zH, nullptr, nullptr, false, (size_t)n * n * 16};
+        g.more = tau;
+        g.dmore = c->ztau;
+        g.more_bytes = sizeof(psd_z) * (size_t)n * p;
+        if (int rc = staged_call(c, p, g, [&] {
+                Timer tk;
+                tk.start(c->stream);
+                const int rc = zhessenberg_dev(c, n, p, c->zH, c->ztau);
+                if (rc == 0) ms = tk.stop(c->stream);
+                return rc;
+            }))
+            return rc;
+        PSD_CHECK(psd_rt_last_error());
+        s->ms_hess = s->ms_total = ms;
+        s->bytes_hess = 2.0 * 16.0 * p * (5.0 / 6.0) * (double)n * n * n;
+        return 0;
+    });
 }
 
-int psd_z_pschur_dev(psd_ctx* c, int n, int p, double* dA_, char orient, int wantT, int wantZ, int maxitfac, double* dZ_,
+int psd_z_pschur_dev(psd_ctx* c, int n, int p, double* dA, char orient, int wantT, int wantZ, int maxitfac, double* dZ,
                      double* alpha, double* beta, int32_t* ascale, int* schurindex, psd_stats* stats,
                      int32_t* sweeplog, int64_t maxlog, int* info) {
-    int dummy;
-    if (!info) info = &dummy;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (!c) return *info = -1;
-    if ((*info = check_dims(n, p)) != 0) return *info;
-    if (!dA_) return *info = -4;
-    if (orient != 'R' && orient != 'L') return *info = -5;
-    if (maxitfac < 1) return *info = -8;
-    if (wantZ && !dZ_) return *info = -9;
-    if (!alpha || !beta || !ascale) return *info = -10;
-    psd_z* dA = reinterpret_cast<psd_z*>(dA_);
-    psd_z* dZ = reinterpret_cast<psd_z*>(dZ_);
-    const bool left = orient == 'L';
-    const int mlog = 2 * maxitfac * n + n + 16;
-    if ((*info = c->zreserve(n, p, false, mlog)) != 0) return *info;
-    Timer tall, tph;
-    tall.start(c->stream);
-    if (left && p > 1) PSD_LAUNCH(psd_reverse_blocks, psd_dim3(n, p / 2), 64, 0, c->stream, dA_, 2 * n, n, 0, p);
-    tph.start(c->stream);
-    if ((*info = zhessenberg_dev(c, n, p, dA, c->ztau)) != 0) return *info;
-    const double ms_hess = tph.stop(c->stream);
-    tph.start(c->stream);
-    if (wantZ) {
-        if ((*info = zformq_dev(c, n, p, dA, c->ztau, dZ)) != 0) return *info;
-    }
-    PSD_LAUNCH(psd_ztriu, psd_dim3(n, p), 64, 0, c->stream, dA, n);
-    const double ms_formq = tph.stop(c->stream);
-    tph.start(c->stream);
-    psd_stats local;
-    memset(&local, 0, sizeof(local));
-    psd_stats* s = stats ? stats : &local;
-    int rc = zrun_iteration(c, n, p, dA, dZ, wantT, wantZ, maxitfac, alpha, beta, ascale, s, sweeplog, maxlog, info);
-    const double ms_iter = tph.stop(c->stream);
-    if (left && p > 1) {
-        PSD_LAUNCH(psd_reverse_blocks, psd_dim3(n, p / 2), 64, 0, c->stream, dA_, 2 * n, n, 0, p);
-        if (wantZ && p > 2)
-            PSD_LAUNCH(psd_reverse_blocks, psd_dim3(n, (p - 1) / 2), 64, 0, c->stream, dZ_, 2 * n, n, 1, p - 1);
-    }
-    s->ms_hess = ms_hess;
-    s->ms_formq = ms_formq;
-    s->ms_iter = ms_iter;
-    s->ms_total = tall.stop(c->stream);
-    s->bytes_hess = 2.0 * 16.0 * p * (5.0 / 6.0) * (double)n * n * n;
-    s->bytes_formq = wantZ ? 2.0 * 16.0 * p * (double)n * n * n / 3.0 : 0.0;
-    if (schurindex) *schurindex = left ? p : 1;
-    return rc;
+    return psd_entry(c, stats, info, [&](psd_stats* s) -> int {
+        if (int e = check_dims(n, p)) return e;
+        if (!dA) return -4;
+        if (orient != 'R' && orient != 'L') return -5;
+        if (maxitfac < 1) return -8;
+        if (wantZ && !dZ) return -9;
+        if (!alpha || !beta || !ascale) return -10;
+        return pschur_dev_body<pschur_cplx>(c, n, p, reinterpret_cast<psd_z*>(dA), orient, wantT, wantZ, maxitfac,
+                                            reinterpret_cast<psd_z*>(dZ), {alpha, beta, ascale}, schurindex, s, sweeplog,
+                                            maxlog);
+    });
 }
 
 int psd_z_pschur(psd_ctx* c, int n, int p, double* const* A, const uint8_t* S, char orient, int wantT, int wantZ,
                  int maxitfac, double* const* Z, double* alpha, double* beta, int32_t* ascale, int* schurindex,
                  psd_stats* stats, int32_t* sweeplog, int64_t maxlog, int* info) {
-    int dummy;
-    if (!info) info = &dummy;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (!c) return *info = -1;
-    if ((*info = check_dims(n, p)) != 0) return *info;
-    if (!A) return *info = -4;
-    if (orient != 'R' && orient != 'L') return *info = -6;
-    if (wantZ && !Z) return *info = -10;
-    if (S)
-        for (int j = 0; j < p; ++j)
-            if (!S[j])  // signed case (generalized.jl:138-146)
-                return zsigned_pschur_host(c, n, p, A, S, orient, wantT, wantZ, maxitfac, Z, alpha, beta, ascale,
-                                           schurindex, stats, info);
-    const int mlog = 2 * (maxitfac > 0 ? maxitfac : 1) * n + n + 16;
-    if ((*info = c->zreserve(n, p, true, mlog)) != 0) return *info;
-    const size_t nn = (size_t)n * n;
-    Timer tc;
-    tc.start(c->stream);
-    PSD_CHECK(stage_in(c, c->zH, A, p, nn * 16));
-    double ms_copy = tc.stop(c->stream);
-    psd_stats local;
-    psd_stats* s = stats ? stats : &local;
-    int rc = psd_z_pschur_dev(c, n, p, reinterpret_cast<double*>(c->zH), orient, wantT, wantZ, maxitfac,
-                              wantZ ? reinterpret_cast<double*>(c->zZ) : nullptr, alpha, beta, ascale, schurindex, s,
-                              sweeplog, maxlog, info);
-    if (rc < 0 || rc >= PSD_INFO_NOTIMPL) return rc;
-    tc.start(c->stream);
-    PSD_CHECK(stage_out(c, A, c->zH, p, nn * 16));
-    if (wantZ) PSD_CHECK(stage_out(c, Z, c->zZ, p, nn * 16));
-    PSD_CHECK(psd_rt_sync(c->stream));
-    ms_copy += tc.stop(c->stream);
-    s->ms_copy = ms_copy;
-    return rc;
+    return psd_entry(c, stats, info, [&](psd_stats* s) -> int {
+        if (int e = check_dims(n, p)) return e;
+        if (!A) return -4;
+        if (orient != 'R' && orient != 'L') return -6;
+        if (wantZ && !Z) return -10;
+        if (S)
+            for (int j = 0; j < p; ++j)
+                if (!S[j])  // signed case (generalized.jl:138-146)
+                    return zsigned_pschur_host(c, n, p, A, S, orient, wantT, wantZ, maxitfac, Z, alpha, beta, ascale,
+                                               schurindex, s);
+        if (int e = c->zreserve(n, p, true, 2 * (maxitfac > 0 ? maxitfac : 1) * n + n + 16)) return e;
+        staged g{A, c->zH, wantZ ? Z : nullptr, c->zZ, false, (size_t)n * n * 16};
+        g.ms_copy = &s->ms_copy;
+        return staged_call(c, p, g, [&] {  // (the device entry starts the statistics afresh and checks the rest)
+            return psd_z_pschur_dev(c, n, p, reinterpret_cast<double*>(c->zH), orient, wantT, wantZ, maxitfac,
+                                    wantZ ? reinterpret_cast<double*>(c->zZ) : nullptr, alpha, beta, ascale, schurindex, s,
+                                    sweeplog, maxlog, nullptr);
+        });
+    });
 }
 
 int psd_z_pschur_hess(psd_ctx* c, int n, int p, double* const* H, const uint8_t* S, double* const* Q, int wantT,
                       int wantZ, int maxitfac, double* alpha, double* beta, int32_t* ascale, psd_stats* stats,
                       int32_t* sweeplog, int64_t maxlog, int* info) {
-    int dummy;
-    if (!info) info = &dummy;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (!c) return *info = -1;
-    if ((*info = check_dims(n, p)) != 0) return *info;
-    if (!H) return *info = -4;
-    bool signedS = false;
-    if (S) {
-        if (!S[0]) return *info = -5;  // generalized.jl:182
-        for (int j = 0; j < p; ++j) signedS = signedS || !S[j];
-    }
-    if (wantZ && !Q) return *info = -6;
-    if (maxitfac < 1) return *info = -9;
-    if (signedS) return zsigned_hess_host(c, n, p, H, S, Q, wantT, wantZ, maxitfac, alpha, beta, ascale, stats, info);
-    const int mlog = 2 * maxitfac * n + n + 16;
-    if ((*info = c->zreserve(n, p, true, mlog)) != 0) return *info;
-    const size_t nn = (size_t)n * n;
-    PSD_CHECK(stage_in(c, c->zH, H, p, nn * 16));
-    if (wantZ) PSD_CHECK(stage_in(c, c->zZ, Q, p, nn * 16));
-    psd_stats local;
-    memset(&local, 0, sizeof(local));
-    psd_stats* s = stats ? stats : &local;
-    Timer t;
-    t.start(c->stream);
-    int rc = zrun_iteration(c, n, p, c->zH, wantZ ? c->zZ : nullptr, wantT, wantZ, maxitfac, alpha, beta, ascale, s,
-                            sweeplog, maxlog, info);
-    s->ms_iter = s->ms_total = t.stop(c->stream);
-    if (rc < 0 || rc >= PSD_INFO_NOTIMPL) return rc;
-    PSD_CHECK(stage_out(c, H, c->zH, p, nn * 16));
-    if (wantZ) PSD_CHECK(stage_out(c, Q, c->zZ, p, nn * 16));
-    PSD_CHECK(psd_rt_sync(c->stream));
-    return rc;
+    return psd_entry(c, stats, info, [&](psd_stats* s) -> int {
+        if (int e = check_dims(n, p)) return e;
+        if (!H) return -4;
+        bool signedS = false;
+        if (S) {
+            if (!S[0]) return -5;  // generalized.jl:182
+            for (int j = 0; j < p; ++j) signedS = signedS || !S[j];
+        }
+        if (wantZ && !Q) return -6;
+        if (maxitfac < 1) return -9;
+        if (signedS) return zsigned_hess_host(c, n, p, H, S, Q, wantT, wantZ, maxitfac, alpha, beta, ascale, s);
+        if (int e = c->zreserve(n, p, true, 2 * maxitfac * n + n + 16)) return e;
+        staged g{H, c->zH, wantZ ? Q : nullptr, c->zZ, true, (size_t)n * n * 16};
+        return staged_call(c, p, g, [&] {
+            Timer t;
+            t.start(c->stream);
+            const int rc = zrun_iteration(c, n, p, c->zH, wantZ ? c->zZ : nullptr, wantT, wantZ, maxitfac, alpha, beta, ascale,
+                                          s, sweeplog, maxlog);
+            s->ms_iter = s->ms_total = t.stop(c->stream);
+            return rc;
+        });
+    });
 }
 
 }  // extern "C"
@@ -3129,27 +3143,21 @@ extern "C" {
 int psd_z_ordschur(psd_ctx* c, int n, int p, double* const* T, double* const* Z, char orient, int schurindex,
                    const uint8_t* select, int wantZ, double* alpha, double* beta, int32_t* ascale, psd_stats* stats,
                    int* info) {
-    int dummy;
-    if (!info) info = &dummy;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (!c) return *info = -1;
-    if ((*info = check_dims(n, p)) != 0) return *info;
-    if (!T) return *info = -4;
-    if (wantZ && !Z) return *info = -5;
-    if (orient != 'R' && orient != 'L') return *info = -6;
-    if (!select) return *info = -8;
-    std::vector<int> slotA, slotZ;
-    if (!ord_slots(orient, schurindex, p, slotA, slotZ)) return *info = -7;  // ArgumentError, ordschur.jl:32
-    if ((*info = c->zreserve(n, p, true, 16)) != 0) return *info;
-    const size_t nn = (size_t)n * n;
-    PSD_CHECK(stage_in(c, c->zH, T, p, nn * 16, slotA.data()));
-    if (wantZ) PSD_CHECK(stage_in(c, c->zZ, Z, p, nn * 16, slotZ.data()));
-    int rc = zordschur_dev(c, n, p, c->zH, c->zZ, select, wantZ, alpha, beta, ascale, stats, info);
-    if (rc < 0 || rc >= PSD_INFO_NOTIMPL) return rc;
-    PSD_CHECK(stage_out(c, T, c->zH, p, nn * 16, slotA.data()));
-    if (wantZ) PSD_CHECK(stage_out(c, Z, c->zZ, p, nn * 16, slotZ.data()));
-    PSD_CHECK(psd_rt_sync(c->stream));
-    return rc;
+    return psd_entry(c, stats, info, [&](psd_stats* s) -> int {
+        if (int e = check_dims(n, p)) return e;
+        if (!T) return -4;
+        if (wantZ && !Z) return -5;
+        if (orient != 'R' && orient != 'L') return -6;
+        if (!select) return -8;
+        std::vector<int> slotA, slotZ;
+        if (!ord_slots(orient, schurindex, p, slotA, slotZ)) return -7;  // ArgumentError, ordschur.jl:32
+        if (int e = c->zreserve(n, p, true, 16)) return e;
+        staged g{T, c->zH, wantZ ? Z : nullptr, c->zZ, true, (size_t)n * n * 16, slotA.data(), slotZ.data()};
+        return staged_call(c, p, g, [&] {
+            int code;  // (the reordering drivers also leave their code here)
+            return zordschur_dev(c, n, p, c->zH, c->zZ, select, wantZ, alpha, beta, ascale, s, &code);
+        });
+    });
 }
 
 }  // extern "C"
@@ -3254,27 +3262,21 @@ extern "C" {
 
 int psd_d_ordschur(psd_ctx* c, int n, int p, double* const* T, double* const* Z, char orient, int schurindex,
                    const uint8_t* select, int wantZ, double* wr, double* wi, psd_stats* stats, int* info) {
-    int dummy;
-    if (!info) info = &dummy;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (!c) return *info = -1;
-    if ((*info = check_dims(n, p)) != 0) return *info;
-    if (!T) return *info = -4;
-    if (wantZ && !Z) return *info = -5;
-    if (orient != 'R' && orient != 'L') return *info = -6;
-    if (!select) return *info = -8;
-    std::vector<int> slotA, slotZ;
-    if (!ord_slots(orient, schurindex, p, slotA, slotZ)) return *info = -7;  // rordschur.jl:25
-    if ((*info = c->reserve(n, p, true, 16)) != 0) return *info;
-    const size_t nn = (size_t)n * n;
-    PSD_CHECK(stage_in(c, c->dH, T, p, nn * 8, slotA.data()));
-    if (wantZ) PSD_CHECK(stage_in(c, c->dZ, Z, p, nn * 8, slotZ.data()));
-    int rc = rordschur_dev(c, n, p, c->dH, c->dZ, select, wantZ, wr, wi, stats, info);
-    if (rc < 0 || rc >= PSD_INFO_NOTIMPL) return rc;
-    PSD_CHECK(stage_out(c, T, c->dH, p, nn * 8, slotA.data()));
-    if (wantZ) PSD_CHECK(stage_out(c, Z, c->dZ, p, nn * 8, slotZ.data()));
-    PSD_CHECK(psd_rt_sync(c->stream));
-    return rc;
+    return psd_entry(c, stats, info, [&](psd_stats* s) -> int {
+        if (int e = check_dims(n, p)) return e;
+        if (!T) return -4;
+        if (wantZ && !Z) return -5;
+        if (orient != 'R' && orient != 'L') return -6;
+        if (!select) return -8;
+        std::vector<int> slotA, slotZ;
+        if (!ord_slots(orient, schurindex, p, slotA, slotZ)) return -7;  // rordschur.jl:25
+        if (int e = c->reserve(n, p, true, 16)) return e;
+        staged g{T, c->dH, wantZ ? Z : nullptr, c->dZ, true, (size_t)n * n * 8, slotA.data(), slotZ.data()};
+        return staged_call(c, p, g, [&] {
+            int code;  // (the reordering drivers also leave their code here)
+            return rordschur_dev(c, n, p, c->dH, c->dZ, select, wantZ, wr, wi, s, &code);
+        });
+    });
 }
 
 }  // extern "C"
@@ -3453,55 +3455,32 @@ int giterate_dev(psd_ctx* c, int n, int p, double* dH, double* dZ, const uint8_t
     return 0;
 }
 
+void stats_from_state(psd_stats* s, const psd_gstate& st) {
+    if (!s) return;
+    s->niter = st.jiter;
+    s->nsweeps = st.nsweeps;
+    s->nrqpass = st.nzshift;
+    s->ndefl1 = st.nsplit;
+    s->ndefl2 = st.n2real + st.n2cplx;
+    s->nwindows = st.nwindows;
+    s->nlog = st.nlog;
+    s->reserved = st.ncase2 + 1000 * st.ncase3;
+    s->maxits = st.ntrainsweeps;  // (signed path: sweeps that ran inside multishift trains)
+    for (int q = 0; q < 6; ++q) s->step_cycles[q] = st.cyc[q];
+}
+
+// (bytes_sweeps: a sweep of the real signed engine applies two rotations per (j, l))
 int grun_iteration(psd_ctx* c, int n, int p, double* dH, double* dZ, const uint8_t* S, int wantT, int wantZ,
                    int maxitfac, double* alpha, double* beta, int32_t* ascale, psd_stats* stats, int32_t* sweeplog,
-                   int64_t maxlog_user, int* info) {
+                   int64_t maxlog_user) {
     const int maxlog = 2 * maxitfac * n + n + 16;
-    if ((*info = c->greserve(n, p, maxlog)) != 0) return *info;
+    if (int e = c->greserve(n, p, maxlog)) return e;
     psd_gstate st;
-    int rc = giterate_dev(c, n, p, dH, dZ, S, wantT, wantZ, maxitfac, &st, stats, maxlog);
-    if (rc != 0) {
-        *info = rc;
-        return rc;
-    }
-    if (stats) {
-        stats->niter = st.jiter;
-        stats->nsweeps = st.nsweeps;
-        stats->nrqpass = st.nzshift;
-        stats->ndefl1 = st.nsplit;
-        stats->ndefl2 = st.n2real + st.n2cplx;
-        stats->nwindows = st.nwindows;
-        stats->nlog = st.nlog;
-        stats->reserved = st.ncase2 + 1000 * st.ncase3;
-        stats->maxits = st.ntrainsweeps;  // (signed path: sweeps that ran inside multishift trains)
-        for (int q = 0; q < 6; ++q) stats->step_cycles[q] = st.cyc[q];
-    }
-    PSD_CHECK(psd_rt_d2h(alpha, c->galpha, sizeof(psd_z) * n, c->stream));
-    PSD_CHECK(psd_rt_d2h(beta, c->gbeta, sizeof(double) * n, c->stream));
-    std::vector<int> hsc(n, 0);
-    PSD_CHECK(psd_rt_d2h(hsc.data(), c->gascale, sizeof(int) * n, c->stream));
-    const int nl = st.nlog < maxlog ? st.nlog : maxlog;
-    std::vector<int> hlog((size_t)3 * nl + 3, 0);
-    if (nl > 0) PSD_CHECK(psd_rt_d2h(hlog.data(), c->glog, sizeof(int) * 3 * (size_t)nl, c->stream));
-    PSD_CHECK(psd_rt_sync(c->stream));
-    for (int q = 0; q < n; ++q) ascale[q] = hsc[q];
-    if (stats) {  // algorithmic bytes of the sweeps: two rotations per (j, l), E = 8
-        double b = 0.0;
-        for (int q = 0; q < nl; ++q)
-            if (hlog[3 * q] == 0 || hlog[3 * q] == 4) {
-                const double w = hlog[3 * q + 2] - hlog[3 * q + 1] + 1;
-                const double rot = (hlog[3 * q] == 0) ? 2.0 : 1.0;
-                if (!wantT) b += rot * 2 * 8.0 * p * w * w + (wantZ ? rot * 2 * 8.0 * p * w * n : 0.0);
-                else b += rot * 2 * 8.0 * p * w * (wantZ ? (2.0 * n + 1) : (n + 1.0));
-            }
-        stats->bytes_sweeps = b;
-    }
-    if (sweeplog) {
-        const int64_t m = nl < maxlog_user ? nl : maxlog_user;
-        for (int64_t q = 0; q < 3 * m; ++q) sweeplog[q] = hlog[q];
-    }
-    *info = (st.info == PSD_LIST_OVERFLOW) ? (PSD_INFO_RUNTIME + 77) : ((st.info != 0) ? (PSD_INFO_NOCONV + st.info) : 0);
-    return *info;
+    if (int rc = giterate_dev(c, n, p, dH, dZ, S, wantT, wantZ, maxitfac, &st, stats, maxlog)) return rc;
+    stats_from_state(stats, st);
+    return iteration_tail(c, n, p, wantT, wantZ, st.nlog, st.info, maxlog,
+                          {c->galpha, sizeof(psd_z), c->gbeta, c->gascale, alpha, beta, ascale}, {c->glog, 8.0, true, 2.0},
+                          stats, sweeplog, maxlog_user);
 }
 
 // _phessenberg!(A, S; wantQ) on device — generalized.jl:988-1082.  dA [p][n][n] internal order, overwritten by
@@ -3573,121 +3552,82 @@ extern "C" {
 // _phessenberg!(A, S) — generalized.jl:988-1082 (Float64).  A[l] overwritten by H_l, Q[l] = Qs[l].
 int psd_d_gphessenberg(psd_ctx* c, int n, int p, double* const* A, const uint8_t* S, double* const* Q, psd_stats* stats,
                        int* info) {
-    int dummy;
-    if (!info) info = &dummy;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (!c) return *info = -1;
-    if ((*info = check_dims(n, p)) != 0) return *info;
-    if (!A) return *info = -4;
-    if (S && !S[0]) return *info = -5;  // generalized.jl:990
-    if ((*info = c->reserve(n, p, true, 16)) != 0) return *info;
-    const size_t nn = (size_t)n * n;
-    PSD_CHECK(stage_in(c, c->dH, A, p, nn * 8));
-    *info = sghess_dev(c, n, p, c->dH, Q ? c->dZ : nullptr, S, stats);
-    if (*info != 0) return *info;
-    PSD_CHECK(stage_out(c, A, c->dH, p, nn * 8));
-    if (Q) PSD_CHECK(stage_out(c, Q, c->dZ, p, nn * 8));
-    PSD_CHECK(psd_rt_sync(c->stream));
-    return 0;
+    return psd_entry(c, stats, info, [&](psd_stats* s) -> int {
+        if (int e = check_dims(n, p)) return e;
+        if (!A) return -4;
+        if (S && !S[0]) return -5;  // generalized.jl:990
+        if (int e = c->reserve(n, p, true, 16)) return e;
+        staged g{A, c->dH, Q, c->dZ, false, (size_t)n * n * 8};
+        return staged_call(c, p, g, [&] { return sghess_dev(c, n, p, c->dH, Q ? c->dZ : nullptr, S, s); });
+    });
 }
 
-// pschur!(A, S, lr; wantZ, wantT) for Float64 — rgeneralized.jl:3-45.  User-order in/out as psd_d_pschur.
+// pschur!(A, S, lr; wantZ, wantT) for Float64 — rgeneralized.jl:3-45.  User-order in/out as psd_d_pschur; the working
+// order is the reversal of rgeneralized.jl:1062-1071 for 'L' (schurindex p).
 int psd_d_gpschur(psd_ctx* c, int n, int p, double* const* A, const uint8_t* S, char orient, int wantT, int wantZ,
                   int maxitfac, double* const* Z, double* alpha, double* beta, int32_t* ascale, int* schurindex,
                   psd_stats* stats, int* info) {
-    int dummy;
-    if (!info) info = &dummy;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (!c) return *info = -1;
-    if ((*info = check_dims(n, p)) != 0) return *info;
-    if (!A) return *info = -4;
-    if (orient != 'R' && orient != 'L') return *info = -6;
-    if (wantZ && !Z) return *info = -10;
-    if (maxitfac < 1) return *info = -9;
-    const bool left = orient == 'L';
-    std::vector<int> sA, sZ;  // internal j <- user slot: the reversal of rgeneralized.jl:1062-1071 for 'L' (schurindex p)
-    ord_slots(orient, left ? p : 1, p, sA, sZ);
-    std::vector<uint8_t> Sarg(p, 1);
-    bool alltrue = true;
-    for (int j = 0; j < p; ++j) {
-        Sarg[j] = (!S || S[sA[j]]) ? 1 : 0;
-        alltrue = alltrue && Sarg[j];
-    }
-    if (!Sarg[0]) return *info = -5;  // rgeneralized.jl:37
-    if ((*info = c->reserve(n, p, true, 16)) != 0) return *info;
-    const size_t nn = (size_t)n * n;
-    Timer tc;
-    tc.start(c->stream);
-    PSD_CHECK(stage_in(c, c->dH, A, p, nn * 8, sA.data()));
-    double ms_copy = tc.stop(c->stream);
-    psd_stats local;
-    memset(&local, 0, sizeof(local));
-    psd_stats* s = stats ? stats : &local;
-    Timer tt;
-    tt.start(c->stream);
-    if (alltrue) {  // rgeneralized.jl:21-34: Householder phessenberg!, explicit Q
-        Timer t;
-        t.start(c->stream);
-        if ((*info = hessenberg_dev(c, n, p, c->dH, c->tau)) != 0) return *info;
-        s->ms_hess = t.stop(c->stream);
-        if (wantZ) {
-            t.start(c->stream);
-            if ((*info = formq_dev(c, n, p, c->dH, c->tau, c->dZ)) != 0) return *info;
-            s->ms_formq = t.stop(c->stream);
-        }
-        PSD_LAUNCH(psd_triu, psd_dim3(n, p), 64, 0, c->stream, c->dH, n);
-    } else {
-        if ((*info = sghess_dev(c, n, p, c->dH, wantZ ? c->dZ : nullptr, Sarg.data(), s)) != 0) return *info;
-    }
-    Timer ti;
-    ti.start(c->stream);
-    const double keep_hess = s->ms_hess, keep_formq = s->ms_formq, keep_bh = s->bytes_hess;
-    int rc = grun_iteration(c, n, p, c->dH, wantZ ? c->dZ : nullptr, Sarg.data(), wantT, wantZ, maxitfac, alpha, beta,
-                            ascale, s, nullptr, 0, info);
-    s->ms_hess = keep_hess;
-    s->ms_formq = keep_formq;
-    s->bytes_hess = keep_bh;
-    s->ms_iter = ti.stop(c->stream);
-    s->ms_total = tt.stop(c->stream);
-    if (schurindex) *schurindex = left ? p : 1;
-    if (rc < 0 || rc >= PSD_INFO_NOTIMPL) return rc;
-    tc.start(c->stream);
-    PSD_CHECK(stage_out(c, A, c->dH, p, nn * 8, sA.data()));
-    if (wantZ) PSD_CHECK(stage_out(c, Z, c->dZ, p, nn * 8, sZ.data()));
-    PSD_CHECK(psd_rt_sync(c->stream));
-    s->ms_copy = ms_copy + tc.stop(c->stream);
-    return rc;
+    return psd_entry(c, stats, info, [&](psd_stats* s) -> int {
+        if (int e = check_dims(n, p)) return e;
+        if (!A) return -4;
+        if (orient != 'R' && orient != 'L') return -6;
+        if (wantZ && !Z) return -10;
+        if (maxitfac < 1) return -9;
+        const bool left = orient == 'L';
+        signed_order o;
+        if (int e = signed_slots(orient, left ? p : 1, p, S, o)) return e;  // rgeneralized.jl:37
+        if (int e = c->reserve(n, p, true, 16)) return e;
+        staged g{A, c->dH, wantZ ? Z : nullptr, c->dZ, false, (size_t)n * n * 8, o.sA.data(), o.sZ.data()};
+        g.ms_copy = &s->ms_copy;
+        return staged_call(c, p, g, [&]() -> int {
+            Timer tt;
+            tt.start(c->stream);
+            if (o.alltrue) {  // rgeneralized.jl:21-34: Householder phessenberg!, explicit Q
+                Timer t;
+                t.start(c->stream);
+                if (int e = hessenberg_dev(c, n, p, c->dH, c->tau)) return e;
+                s->ms_hess = t.stop(c->stream);
+                if (wantZ) {
+                    t.start(c->stream);
+                    if (int e = formq_dev(c, n, p, c->dH, c->tau, c->dZ)) return e;
+                    s->ms_formq = t.stop(c->stream);
+                }
+                PSD_LAUNCH(psd_triu, psd_dim3(n, p), 64, 0, c->stream, c->dH, n);
+            } else {
+                if (int e = sghess_dev(c, n, p, c->dH, wantZ ? c->dZ : nullptr, o.S.data(), s)) return e;
+            }
+            Timer ti;
+            ti.start(c->stream);
+            const int rc = grun_iteration(c, n, p, c->dH, wantZ ? c->dZ : nullptr, o.S.data(), wantT, wantZ, maxitfac, alpha,
+                                          beta, ascale, s, nullptr, 0);
+            s->ms_iter = ti.stop(c->stream);
+            s->ms_total = tt.stop(c->stream);
+            if (schurindex) *schurindex = left ? p : 1;
+            return rc;
+        });
+    });
 }
 
 int psd_d_gpschur_hess(psd_ctx* c, int n, int p, double* const* H, const uint8_t* S, double* const* Q, int wantT,
                        int wantZ, int maxitfac, double* alpha, double* beta, int32_t* ascale, psd_stats* stats,
                        int32_t* sweeplog, int64_t maxlog, int* info) {
-    int dummy;
-    if (!info) info = &dummy;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (!c) return *info = -1;
-    if ((*info = check_dims(n, p)) != 0) return *info;
-    if (!H) return *info = -4;
-    if (S && !S[0]) return *info = -5;  // rgeneralized.jl:73
-    if (wantZ && !Q) return *info = -6;
-    if (maxitfac < 1) return *info = -9;
-    if ((*info = c->reserve(n, p, true, 16)) != 0) return *info;
-    const size_t nn = (size_t)n * n;
-    PSD_CHECK(stage_in(c, c->dH, H, p, nn * 8));
-    if (wantZ) PSD_CHECK(stage_in(c, c->dZ, Q, p, nn * 8));
-    psd_stats local;
-    memset(&local, 0, sizeof(local));
-    psd_stats* s = stats ? stats : &local;
-    Timer t;
-    t.start(c->stream);
-    int rc = grun_iteration(c, n, p, c->dH, wantZ ? c->dZ : nullptr, S, wantT, wantZ, maxitfac, alpha, beta, ascale, s,
-                            sweeplog, maxlog, info);
-    s->ms_iter = s->ms_total = t.stop(c->stream);
-    if (rc < 0 || rc >= PSD_INFO_NOTIMPL) return rc;
-    PSD_CHECK(stage_out(c, H, c->dH, p, nn * 8));
-    if (wantZ) PSD_CHECK(stage_out(c, Q, c->dZ, p, nn * 8));
-    PSD_CHECK(psd_rt_sync(c->stream));
-    return rc;
+    return psd_entry(c, stats, info, [&](psd_stats* s) -> int {
+        if (int e = check_dims(n, p)) return e;
+        if (!H) return -4;
+        if (S && !S[0]) return -5;  // rgeneralized.jl:73
+        if (wantZ && !Q) return -6;
+        if (maxitfac < 1) return -9;
+        if (int e = c->reserve(n, p, true, 16)) return e;
+        staged g{H, c->dH, wantZ ? Q : nullptr, c->dZ, true, (size_t)n * n * 8};
+        return staged_call(c, p, g, [&] {
+            Timer t;
+            t.start(c->stream);
+            const int rc = grun_iteration(c, n, p, c->dH, wantZ ? c->dZ : nullptr, S, wantT, wantZ, maxitfac, alpha, beta,
+                                          ascale, s, sweeplog, maxlog);
+            s->ms_iter = s->ms_total = t.stop(c->stream);
+            return rc;
+        });
+    });
 }
 
 }  // extern "C"
@@ -3768,34 +3708,26 @@ int zgordschur_dev(psd_ctx* c, int n, int p, psd_z* dH, psd_z* dZ, const uint8_t
 // host entry shared by the complex and the (promoted) real case; T/Z: p host matrices of n*n complex
 int gordschur_host(psd_ctx* c, int n, int p, double* const* T, double* const* Z, const uint8_t* S, char orient,
                    int schurindex, const uint8_t* select, int wantZ, double* alpha, double* beta, int32_t* ascale,
-                   psd_stats* stats, int* info) {
-    std::vector<int> sA, sZ;  // internal j <- user slot
-    if (!ord_slots(orient, schurindex, p, sA, sZ)) return *info = -7;  // ArgumentError, ordschur.jl:32
-    if ((*info = c->zreserve(n, p, true, 16)) != 0) return *info;
-    if ((*info = c->zgreserve(n, p)) != 0) return *info;
-    const size_t nn = (size_t)n * n;
-    std::vector<uint8_t> Sint(p, 1);
-    for (int j = 0; j < p; ++j) Sint[j] = S[sA[j]] ? 1 : 0;
-    if (!Sint[0]) return *info = -5;
-    PSD_CHECK(stage_in(c, c->zH, T, p, nn * 16, sA.data()));
-    if (wantZ) PSD_CHECK(stage_in(c, c->zZ, Z, p, nn * 16, sZ.data()));
-    int rc = zgordschur_dev(c, n, p, c->zH, c->zZ, Sint.data(), select, wantZ, alpha, beta, ascale, stats, info);
-    if (rc < 0 || rc >= PSD_INFO_NOTIMPL) return rc;
-    PSD_CHECK(stage_out(c, T, c->zH, p, nn * 16, sA.data()));
-    if (wantZ) PSD_CHECK(stage_out(c, Z, c->zZ, p, nn * 16, sZ.data()));
-    PSD_CHECK(psd_rt_sync(c->stream));
-    return rc;
+                   psd_stats* s) {
+    signed_order o;  // internal j <- user slot
+    if (int e = signed_slots(orient, schurindex, p, S, o)) return e;  // ArgumentError, ordschur.jl:32; generalized.jl:182
+    if (int e = c->zreserve(n, p, true, 16)) return e;
+    if (int e = c->zgreserve(n, p)) return e;
+    staged g{T, c->zH, wantZ ? Z : nullptr, c->zZ, true, (size_t)n * n * 16, o.sA.data(), o.sZ.data()};
+    return staged_call(c, p, g, [&] {
+        int code;  // (the reordering drivers also leave their code here)
+        return zgordschur_dev(c, n, p, c->zH, c->zZ, o.S.data(), select, wantZ, alpha, beta, ascale, s, &code);
+    });
 }
 
-int gord_check_args(psd_ctx* c, int n, int p, const void* T, const void* Z, const uint8_t* S, char orient,
-                    const uint8_t* select, int wantZ, int* info) {
-    if (!c) return *info = -1;
-    if ((*info = check_dims(n, p)) != 0) return *info;
-    if (!T) return *info = -4;
-    if (wantZ && !Z) return *info = -5;
-    if (!S) return *info = -5;
-    if (orient != 'R' && orient != 'L') return *info = -6;
-    if (!select) return *info = -8;
+int gord_check_args(int n, int p, const void* T, const void* Z, const uint8_t* S, char orient, const uint8_t* select,
+                    int wantZ) {
+    if (int e = check_dims(n, p)) return e;
+    if (!T) return -4;
+    if (wantZ && !Z) return -5;
+    if (!S) return -5;
+    if (orient != 'R' && orient != 'L') return -6;
+    if (!select) return -8;
     return 0;
 }
 
@@ -3806,69 +3738,61 @@ extern "C" {
 int psd_z_gordschur(psd_ctx* c, int n, int p, double* const* T, double* const* Z, const uint8_t* S, char orient,
                     int schurindex, const uint8_t* select, int wantZ, double* alpha, double* beta, int32_t* ascale,
                     psd_stats* stats, int* info) {
-    int dummy;
-    if (!info) info = &dummy;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (gord_check_args(c, n, p, T, Z, S, orient, select, wantZ, info) != 0) return *info;
-    return gordschur_host(c, n, p, T, Z, S, orient, schurindex, select, wantZ, alpha, beta, ascale, stats, info);
+    return psd_entry(c, stats, info, [&](psd_stats* s) -> int {
+        if (int e = gord_check_args(n, p, T, Z, S, orient, select, wantZ)) return e;
+        return gordschur_host(c, n, p, T, Z, S, orient, schurindex, select, wantZ, alpha, beta, ascale, s);
+    });
 }
 
 // Float64 with a real spectrum (T1 triangular): promoted to the complex kernel, whose rotations stay real on real data.
-// A 2x2 block in T1 (conjugate pair) needs the signed block swap of sylswap.jl:197-538: PSD_INFO_NOTIMPL.
+// A 2x2 block in T1 (conjugate pair): the signed block swaps of sylswap.jl:197-538 in real arithmetic.
 int psd_d_gordschur(psd_ctx* c, int n, int p, double* const* T, double* const* Z, const uint8_t* S, char orient,
                     int schurindex, const uint8_t* select, int wantZ, double* alpha, double* beta, int32_t* ascale,
                     psd_stats* stats, int* info) {
-    int dummy;
-    if (!info) info = &dummy;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (gord_check_args(c, n, p, T, Z, S, orient, select, wantZ, info) != 0) return *info;
-    if (schurindex < 1 || schurindex > p) return *info = -7;
-    const size_t nn = (size_t)n * n;
-    bool pairs = false;
-    {
-        const double* T1 = T[schurindex - 1];
-        for (int j = 0; j + 1 < n; ++j)
-            if (T1[(size_t)j * n + (j + 1)] != 0.0) pairs = true;
-    }
-    if (pairs) {  // 2x2 blocks: signed block swaps in real arithmetic (sylswap.jl:197-538)
-        std::vector<int> sA, sZ;
-        if (!ord_slots(orient, schurindex, p, sA, sZ)) return *info = -7;
-        if ((*info = c->reserve(n, p, true, 16)) != 0) return *info;
-        std::vector<uint8_t> Sint(p, 1);
-        for (int j = 0; j < p; ++j) Sint[j] = S[sA[j]] ? 1 : 0;
-        if (!Sint[0]) return *info = -5;
-        PSD_CHECK(stage_in(c, c->dH, T, p, nn * 8, sA.data()));
-        if (wantZ) PSD_CHECK(stage_in(c, c->dZ, Z, p, nn * 8, sZ.data()));
-        int rc = rordschur_dev(c, n, p, c->dH, c->dZ, select, wantZ, nullptr, nullptr, stats, info, Sint.data(), alpha, beta,
-                               ascale);
-        if (rc < 0 || rc >= PSD_INFO_NOTIMPL) return rc;
-        PSD_CHECK(stage_out(c, T, c->dH, p, nn * 8, sA.data()));
-        if (wantZ) PSD_CHECK(stage_out(c, Z, c->dZ, p, nn * 8, sZ.data()));
-        PSD_CHECK(psd_rt_sync(c->stream));
-        return rc;
-    }
-    // (only the promotion needs host copies: gordschur_host stages from and into them)
-    std::vector<std::vector<psd_z>> Tz(p), Zz(wantZ ? p : 0);
-    std::vector<double*> Tp(p), Zp(wantZ ? p : 0);
-    for (int j = 0; j < p; ++j) {
-        Tz[j].resize(nn);
-        for (size_t q = 0; q < nn; ++q) Tz[j][q] = zmk(T[j][q], 0.0);
-        Tp[j] = reinterpret_cast<double*>(Tz[j].data());
-        if (wantZ) {
-            Zz[j].resize(nn);
-            for (size_t q = 0; q < nn; ++q) Zz[j][q] = zmk(Z[j][q], 0.0);
-            Zp[j] = reinterpret_cast<double*>(Zz[j].data());
+    return psd_entry(c, stats, info, [&](psd_stats* s) -> int {
+        if (int e = gord_check_args(n, p, T, Z, S, orient, select, wantZ)) return e;
+        if (schurindex < 1 || schurindex > p) return -7;
+        const size_t nn = (size_t)n * n;
+        bool pairs = false;
+        {
+            const double* T1 = T[schurindex - 1];
+            for (int j = 0; j + 1 < n; ++j)
+                if (T1[(size_t)j * n + (j + 1)] != 0.0) pairs = true;
         }
-    }
-    int rc = gordschur_host(c, n, p, Tp.data(), Zp.data(), S, orient, schurindex, select, wantZ, alpha, beta, ascale, stats,
-                            info);
-    if (rc < 0 || rc >= PSD_INFO_NOTIMPL) return rc;
-    for (int j = 0; j < p; ++j) {
-        for (size_t q = 0; q < nn; ++q) T[j][q] = Tz[j][q].re;
-        if (wantZ)
-            for (size_t q = 0; q < nn; ++q) Z[j][q] = Zz[j][q].re;
-    }
-    return rc;
+        if (pairs) {
+            signed_order o;
+            if (int e = signed_slots(orient, schurindex, p, S, o)) return e;
+            if (int e = c->reserve(n, p, true, 16)) return e;
+            staged g{T, c->dH, wantZ ? Z : nullptr, c->dZ, true, nn * 8, o.sA.data(), o.sZ.data()};
+            return staged_call(c, p, g, [&] {
+                int code;  // (the reordering drivers also leave their code here)
+                return rordschur_dev(c, n, p, c->dH, c->dZ, select, wantZ, nullptr, nullptr, s, &code, o.S.data(), alpha,
+                                     beta, ascale);
+            });
+        }
+        // (only the promotion needs host copies: gordschur_host stages from and into them)
+        std::vector<std::vector<psd_z>> Tz(p), Zz(wantZ ? p : 0);
+        std::vector<double*> Tp(p), Zp(wantZ ? p : 0);
+        for (int j = 0; j < p; ++j) {
+            Tz[j].resize(nn);
+            for (size_t q = 0; q < nn; ++q) Tz[j][q] = zmk(T[j][q], 0.0);
+            Tp[j] = reinterpret_cast<double*>(Tz[j].data());
+            if (wantZ) {
+                Zz[j].resize(nn);
+                for (size_t q = 0; q < nn; ++q) Zz[j][q] = zmk(Z[j][q], 0.0);
+                Zp[j] = reinterpret_cast<double*>(Zz[j].data());
+            }
+        }
+        const int rc = gordschur_host(c, n, p, Tp.data(), Zp.data(), S, orient, schurindex, select, wantZ, alpha, beta,
+                                      ascale, s);
+        if (rc < 0 || rc >= PSD_INFO_NOTIMPL) return rc;
+        for (int j = 0; j < p; ++j) {
+            for (size_t q = 0; q < nn; ++q) T[j][q] = Tz[j][q].re;
+            if (wantZ)
+                for (size_t q = 0; q < nn; ++q) Z[j][q] = Zz[j][q].re;
+        }
+        return rc;
+    });
 }
 
 }  // extern "C"
@@ -3876,23 +3800,37 @@ int psd_d_gordschur(psd_ctx* c, int n, int p, double* const* T, double* const* Z
 // ------------------------------------------------------------------------------------------------
 // _rphessenberg!(Ap, A, Q) — rhessx.jl:55-109
 namespace {
+
+// Device buffers that live for one call: freed on every way out of it.
+struct dev_buffers {
+    std::vector<void*> held;
+    ~dev_buffers() {
+        for (void* q : held) psd_rt_free(q);
+    }
+    template <class T>
+    int alloc(T*& ptr, size_t bytes) {
+        void* q = nullptr;
+        if (int e = psd_rt_malloc(&q, bytes)) return e;
+        held.push_back(q);
+        ptr = static_cast<T*>(q);
+        return 0;
+    }
+};
+
 template <class O, int ES>
-int rphessenberg_host(psd_ctx* c, int m, int n, int p, double* Ap, double* const* A, double* const* Q, int nq, int nqc,
-                      int* info) {
+int rphessenberg_host(psd_ctx* c, int m, int n, int p, double* Ap, double* const* A, double* const* Q, int nq, int nqc) {
     typedef typename O::T T;
-    int dummy;
-    if (!info) info = &dummy;
-    if (!c) return *info = -1;
-    if (n < 1 || !(m == n || m == n + 1)) return *info = -2;  // ArgumentError, rhessx.jl:62
-    if (p < 1) return *info = -3;
-    if (!Ap) return *info = -4;
-    if (p > 1 && !A) return *info = -5;
-    if (Q && (nq < 1 || nqc < n)) return *info = -8;
+    if (n < 1 || !(m == n || m == n + 1)) return -2;  // ArgumentError, rhessx.jl:62
+    if (p < 1) return -3;
+    if (!Ap) return -4;
+    if (p > 1 && !A) return -5;
+    if (Q && (nq < 1 || nqc < n)) return -8;
     const size_t nap = (size_t)m * n, nn = (size_t)n * n, nqq = (size_t)nq * nqc;
+    dev_buffers dev;
     T *dAp = nullptr, *dA = nullptr, *dQ = nullptr;
-    PSD_CHECK(psd_rt_malloc((void**)&dAp, nap * ES));
-    PSD_CHECK(psd_rt_malloc((void**)&dA, (p > 1 ? (size_t)(p - 1) * nn : 1) * ES));
-    if (Q) PSD_CHECK(psd_rt_malloc((void**)&dQ, (size_t)p * nqq * ES));
+    PSD_CHECK(dev.alloc(dAp, nap * ES));
+    PSD_CHECK(dev.alloc(dA, (p > 1 ? (size_t)(p - 1) * nn : 1) * ES));
+    if (Q) PSD_CHECK(dev.alloc(dQ, (size_t)p * nqq * ES));
     PSD_CHECK(psd_rt_h2d(dAp, Ap, nap * ES, c->stream));
     PSD_CHECK(stage_in(c, dA, A, p - 1, nn * ES));
     if (Q) PSD_CHECK(stage_in(c, dQ, Q, p, nqq * ES));
@@ -3903,21 +3841,22 @@ int rphessenberg_host(psd_ctx* c, int m, int n, int p, double* Ap, double* const
     if (Q) PSD_CHECK(stage_out(c, Q, dQ, p, nqq * ES));
     PSD_CHECK(psd_rt_sync(c->stream));
     PSD_CHECK(psd_rt_last_error());
-    psd_rt_free(dAp);
-    psd_rt_free(dA);
-    if (dQ) psd_rt_free(dQ);
-    return *info = 0;
+    return 0;
 }
 }  // namespace
 
 extern "C" {
 int psd_d_rphessenberg(psd_ctx* c, int m, int n, int p, double* Ap, double* const* A, double* const* Q, int nq, int nqc,
                        int* info) {
-    return rphessenberg_host<psd_rh_real, 8>(c, m, n, p, Ap, A, Q, nq, nqc, info);
+    return psd_entry(c, nullptr, info, [&](psd_stats*) {
+        return rphessenberg_host<psd_rh_real, 8>(c, m, n, p, Ap, A, Q, nq, nqc);
+    });
 }
 int psd_z_rphessenberg(psd_ctx* c, int m, int n, int p, double* Ap, double* const* A, double* const* Q, int nq, int nqc,
                        int* info) {
-    return rphessenberg_host<psd_rh_cplx, 16>(c, m, n, p, Ap, A, Q, nq, nqc, info);
+    return psd_entry(c, nullptr, info, [&](psd_stats*) {
+        return rphessenberg_host<psd_rh_cplx, 16>(c, m, n, p, Ap, A, Q, nq, nqc);
+    });
 }
 }  // extern "C"
 

@@ -118,10 +118,9 @@ int zbiterate_dev(psd_ctx* c, int nb, int n, int p, psd_z* dH, psd_z* dZ, int wa
         for (int q = 0; q < nb; ++q) {
             psd_stats ps;
             memset(&ps, 0, sizeof(ps));
-            int qinfo = 0;
             rc = zrun_iteration(c, n, p, dH + (size_t)q * p * nn, wantZ ? dZ + (size_t)q * p * nn : nullptr, wantT, wantZ,
                                 maxitfac, alpha + 2 * (size_t)q * n, beta + (size_t)q * n, ascale + (size_t)q * n, &ps,
-                                nullptr, 0, &qinfo);
+                                nullptr, 0);
             if (batch_fatal(rc) && rc != PSD_INFO_RUNTIME + 77) return rc;
             infos[q] = rc;
             batch_add_counts(s, ps);

@@ -123,9 +123,8 @@ int zgbiterate_dev(psd_ctx* c, int nb, int n, int p, psd_z* dH, psd_z* dZ, const
         for (int q = 0; q < nb; ++q) {
             psd_stats ps;
             memset(&ps, 0, sizeof(ps));
-            int qinfo = 0;
             rc = zgrun_iteration(c, n, p, dH + (size_t)q * p * nn, wantZ ? dZ + (size_t)q * p * nn : nullptr, S, wantT, wantZ,
-                                 maxitfac, alpha + 2 * (size_t)q * n, beta + (size_t)q * n, ascale + (size_t)q * n, &ps, &qinfo);
+                                 maxitfac, alpha + 2 * (size_t)q * n, beta + (size_t)q * n, ascale + (size_t)q * n, &ps);
             if (rc == PSD_INFO_RUNTIME + 0xfffc) rc = PSD_INFO_RUNTIME + 0xfffe;  // (the tick bound of the single call)
             if (batch_fatal(rc) && rc != PSD_INFO_RUNTIME + 77 && rc != PSD_INFO_RUNTIME + 0xfffe) return rc;
             infos[q] = rc;
