@@ -275,6 +275,7 @@ _Z = _Family("z", np.complex128, TypeError, "zpschur_batch: ComplexF64 only (use
 
 _ORD_WRONG = {_D: "ordschur_batch: Float64 only (use ordschur_ per problem for ComplexF64)",
               _Z: "zordschur_batch: ComplexF64 only (Float64 problems: ordschur_batch)"}
+_GORD_WRONG = "zgordschur_batch: ComplexF64 only (use ordschur_ per problem for a signed Float64 decomposition)"
 
 
 def _other_family(fam, cplx, every=False):
@@ -383,8 +384,9 @@ class Engine:
                 for g, sig in (("", []), ("g", [u8p])):
                     sigs[f"psd_{t}_{g}pschur_batch{dev}"] = (head + [mats] + sig + [C.c_char, C.c_int, C.c_int, C.c_int,
                                                                                      mats] + eig + [ip, ip, sp, ip])
-                sigs[f"psd_{t}_ordschur_batch{dev}"] = (head + [mats, mats, C.c_char, C.c_int, u8p, C.c_int] + eig
-                                                        + [ip, ip, sp, ip])
+                for g, sig in (("", []), ("g", [u8p])):
+                    sigs[f"psd_{t}_{g}ordschur_batch{dev}"] = (head + [mats, mats] + sig + [C.c_char, C.c_int, u8p, C.c_int]
+                                                               + eig + [ip, ip, sp, ip])
                 sigs[f"psd_{t}_eigvecs_batch{dev}"] = (head + [mats, mats] + eig + [C.c_char, C.c_int, u8p, C.c_int, mats,
                                                                                     C.c_int, ip, i32p,
                                                                                     C.POINTER(BevecStats), ip])
@@ -1338,12 +1340,13 @@ class Engine:
         except ValueError:
             raise DimensionMismatch("select must be [nb][n] flags or one row of n: one entry per eigenvalue") from None
 
-    def _batch_decomps(self, fam, name, wrong, problems, needZ, work):
+    def _batch_decomps(self, fam, name, wrong, problems, needZ, work, signed=False):
         """(n, p, orientation, schurindex, flat Ts) of a batch of PeriodicSchur, which must agree in all four and be of
         the family.  `needZ`: the Schur vectors are required, of the family like the factors, and returned as a flat
         list too (eigvecs); otherwise they may be missing and are the caller's business (ordschur).  `work`: the factors
         are returned as they are, for the in-place contract (ordschur mutates); otherwise as read-only Fortran copies
-        (eigvecs never writes the problems).
+        (eigvecs never writes the problems).  `signed`: the entry takes signed GeneralizedPeriodicSchur, which must
+        agree in S too; the common signature (all true for a plain PeriodicSchur) is returned last.
 
         Which kinds of factors T and vectors Z each entry turns away (`wrong`: the entry's own exception; "mixed": the
         TypeError of the single eigvecs call; otherwise the problem goes on, to the in-place contract for ordschur):
@@ -1353,10 +1356,10 @@ class Engine:
             eigvecs   d     -                mixed               wrong               wrong
             eigvecs   z     wrong            mixed               mixed               -
         (a list of factors or of vectors that is only partly complex: `any` for d, `all` for z, as the code says)."""
-        n = None
+        n = S = None
         Ts, Zs = [], []
         for ps in problems:
-            if isinstance(ps, GeneralizedPeriodicSchur) and not all(ps.S):
+            if not signed and isinstance(ps, GeneralizedPeriodicSchur) and not all(ps.S):
                 raise NotImplementedPSD(f"{name}: signed GeneralizedPeriodicSchur "
                                         f"(use {'geigvecs' if needZ else 'ordschur_'} per problem)")
             if needZ and (len(ps.Z) == 0 or ps.Z[0].shape[0] == 0):
@@ -1378,20 +1381,29 @@ class Engine:
             if (nq != n or len(ps.Ts) != p or (needZ and len(ps.Z) != p) or ps.orientation != orient
                     or ps.schurindex != si or any(a.shape != (n, n) for a in list(ps.Ts) + list(ps.Z))):
                 raise DimensionMismatch("the problems of a batch must have equal order, period, orientation and schurindex")
+            if signed:
+                Sq = [bool(x) for x in getattr(ps, "S", [True] * p)]
+                S = Sq if S is None else S
+                if Sq != S:
+                    raise DimensionMismatch("the problems of a batch must have equal signatures S")
             Ts += ps.Ts if work else [np.asfortranarray(t, dtype=fam.dtype) for t in ps.Ts]
             if needZ:
                 Zs += ps.Z if work else [np.asfortranarray(z, dtype=fam.dtype) for z in ps.Z]
-        return (n, p, orient, si, Ts) + ((Zs,) if needZ else ())
+        return (n, p, orient, si, Ts) + ((Zs,) if needZ else ()) + ((S,) if signed else ())
 
-    def _ordschur_batch_call(self, fam, name, dev, nb, n, p, T, Z, orient, si, sel, wantZ, infos_out, result):
-        """psd_?_ordschur_batch[_dev] on packed factors: T and Z flat lists of work arrays, or with `dev` device blocks
-        (the values row of a problem that failed is NaN then).  Leaves the call's stats and swap counts in
-        self.<name>_stats / _nswaps; `result(eig, codes, nswaps, stats)` builds what the call returns."""
+    def _ordschur_batch_call(self, fam, name, dev, nb, n, p, T, Z, orient, si, sel, wantZ, infos_out, result, S=None):
+        """psd_?_[g]ordschur_batch[_dev] on packed factors: T and Z flat lists of work arrays, or with `dev` device
+        blocks (the values row of a problem that failed is NaN then); `S`: the signature of the signed entry (None: the
+        entry without one).  Leaves the call's stats and swap counts in self.<name>_stats / _nswaps;
+        `result(eig, codes, nswaps, stats)` builds what the call returns."""
+        if S is not None and not S[si - 1]:
+            raise ValueError("The entry of S at schurindex must be true")  # src/generalized.jl:182
         ptrs = (lambda X: C.c_void_p(X.data_ptr())) if dev else self._ptrs
         eig = _eig_alloc(fam, (nb, n), nan=dev)
         infos, nsw, st, info = (C.c_int * nb)(), (C.c_int * nb)(), Stats(), C.c_int(0)
-        fn = getattr(self.lib, f"psd_{fam.tag}_ordschur_batch{'_dev' if dev else ''}")
-        fn(self.ctx, nb, n, p, ptrs(T), ptrs(Z) if wantZ else None, orient.encode(), int(si),
+        fn = getattr(self.lib, f"psd_{fam.tag}_{'' if S is None else 'g'}ordschur_batch{'_dev' if dev else ''}")
+        sig = [] if S is None else [(C.c_uint8 * p)(*[1 if x else 0 for x in S])]
+        fn(self.ctx, nb, n, p, ptrs(T), ptrs(Z) if wantZ else None, *sig, orient.encode(), int(si),
            sel.ctypes.data_as(C.POINTER(C.c_uint8)), int(wantZ), *self._evec_ptrs(eig), infos, nsw, C.byref(st),
            C.byref(info))
 
@@ -1405,13 +1417,15 @@ class Engine:
         setattr(self, name + "_stats", st)
         setattr(self, name + "_nswaps", nswaps)
 
-    def _ordschur_batch_(self, fam, name, problems, args, wantZ, infos_out, lr, schurindex):
-        """ordschur_batch_ / zordschur_batch_."""
-        wrong = NotImplementedPSD(_ORD_WRONG[fam])
+    def _ordschur_batch_(self, fam, name, problems, args, wantZ, infos_out, lr, schurindex, signed=False, S=None):
+        """ordschur_batch_ / zordschur_batch_ / zgordschur_batch_ (`signed`: the entry with a signature, which the
+        problems carry; `S`: that of device tensors)."""
+        wrong = NotImplementedPSD(_GORD_WRONG if signed else _ORD_WRONG[fam])
         if hasattr(problems, "data_ptr"):
             if len(args) != 2:
                 raise TypeError(f"{name}_(T, Z, select, lr=..., schurindex=...)")
-            return self._ordschur_batch_dev(fam, name, wrong, problems, args[0], args[1], lr, schurindex, wantZ, infos_out)
+            return self._ordschur_batch_dev(fam, name, wrong, problems, args[0], args[1], lr, schurindex, wantZ, infos_out,
+                                            signed, S)
         if len(args) != 1:
             raise TypeError(f"{name}_(problems, select, wantZ=True)")
         problems = list(problems)
@@ -1421,7 +1435,8 @@ class Engine:
                 infos_out[:] = []
             self._ordschur_batch_attrs(name, Stats(), np.zeros(0, dtype=np.int32))
             return []
-        n, p, orient, si, Ts = self._batch_decomps(fam, name, wrong, problems, needZ=False, work=True)
+        n, p, orient, si, Ts, *S = self._batch_decomps(fam, name, wrong, problems, needZ=False, work=True, signed=signed)
+        S = S[0] if S else None  # (the entries without a signature pass none on)
         if si not in (1, p):
             raise ValueError("only implemented for schurindex in (1,p)")  # src/ordschur.jl:32, src/rordschur.jl:25
         wantZ = bool(wantZ) and all(len(ps.Z) > 0 for ps in problems)
@@ -1447,12 +1462,16 @@ class Engine:
             return problems
 
         return self._ordschur_batch_call(fam, name, False, nb, n, p, Ts, Zs, char_lr(orient), si, sel, wantZ, infos_out,
-                                         result)
+                                         result, S)
 
-    def _ordschur_batch_dev(self, fam, name, wrong, T, Z, select, lr, schurindex, wantZ, infos_out):
+    def _ordschur_batch_dev(self, fam, name, wrong, T, Z, select, lr, schurindex, wantZ, infos_out, signed=False, S=None):
         import torch
 
         nb, p, n = self._dev_batch(fam, name, wrong, T, Z)
+        if signed:
+            S = [True] * p if S is None else [bool(x) for x in S]
+            if len(S) != p:
+                raise DimensionMismatch("length of S must match the period")
         wantZ = bool(wantZ) and Z is not None
         orient = char_lr(lr)
         if schurindex not in (1, p):
@@ -1468,14 +1487,15 @@ class Engine:
         torch.cuda.synchronize(T.device)
         return self._ordschur_batch_call(
             fam, name, True, nb, n, p, dT, dZ, orient, schurindex, sel, wantZ, infos_out,
-            lambda eig, infos, nsw, st: (dT.transpose(2, 3), (dZ.transpose(2, 3) if wantZ else Z), _eig_values(eig), st))
+            lambda eig, infos, nsw, st: (dT.transpose(2, 3), (dZ.transpose(2, 3) if wantZ else Z), _eig_values(eig), st), S)
 
-    def _ordschur_batch(self, fam, inplace, problems, args, kw):
-        """The copying forms of the two above."""
+    def _ordschur_batch(self, fam, inplace, problems, args, kw, wrong=None):
+        """The copying forms of the three above."""
         if hasattr(problems, "data_ptr"):
             Z = args[0] if len(args) > 0 else None
             return inplace(problems.clone(), Z.clone() if Z is not None else None, *args[1:], **kw)
-        return inplace(self._batch_copies(fam, NotImplementedPSD(_ORD_WRONG[fam]), problems, every=True), *args, **kw)
+        wrong = NotImplementedPSD(wrong or _ORD_WRONG[fam])
+        return inplace(self._batch_copies(fam, wrong, problems, every=True), *args, **kw)
 
     def ordschur_batch_(self, problems, *args, wantZ=True, infos_out=None, lr="R", schurindex=1):
         """LinearAlgebra.ordschur!(P, select; wantZ) (src/rordschur.jl:3-132) for MANY small decompositions of one shape
@@ -1533,6 +1553,29 @@ class Engine:
     def zordschur_batch(self, problems, *args, **kw):
         """Copying form of zordschur_batch_: the decompositions are left untouched (device tensors are copied too)."""
         return self._ordschur_batch(_Z, self.zordschur_batch_, problems, args, kw)
+
+    def zgordschur_batch_(self, problems, *args, wantZ=True, infos_out=None, lr="R", schurindex=1, S=None):
+        """LinearAlgebra.ordschur!(P::GeneralizedPeriodicSchur, select; wantZ) (src/ordschur.jl:11-96, the signed swaps of
+        src/sylswap.jl:638-764) for MANY small ComplexF64 decompositions of one shape and ONE signature in ONE call
+        (psd_z_gordschur_batch): the follow-up of zgpschur_batch / gpschur_batch, the signed counterpart of
+        zordschur_batch_.  Per problem the result contract is that of `ordschur_`; a problem's result does not depend on
+        its place in the batch.  An all-true signature runs the path of zordschur_batch_ (the same bits).
+
+        zgordschur_batch_(problems, select, wantZ=True, infos_out=None): `problems` a list of complex
+        GeneralizedPeriodicSchur of equal order, period, orientation, schurindex (1 or p) and S, with writable
+        Fortran-ordered complex128 factors; each is mutated (Ts, Z, values, alpha, beta, alphascale, stats) and the list
+        returned.  The `stats` of a problem are the call's, with `nsweeps` its own swap count; the call's own are left
+        in `self.zgordschur_batch_stats`, the swap counts in `self.zgordschur_batch_nswaps` ([nb]).
+        zgordschur_batch_(T, Z, select, S=..., lr=..., schurindex=..., wantZ=True, infos_out=None): the torch outputs
+        of the device-resident zgpschur_batch_ ([nb, p, n, n] complex128 tensors; Z may be None with wantZ=False) and
+        the signature of that call; returns (T, Z, values, stats), in place or through a copy as zordschur_batch_ does.
+
+        `select`, rejected swaps and `infos_out` as zordschur_batch_."""
+        return self._ordschur_batch_(_Z, "zgordschur_batch", problems, args, wantZ, infos_out, lr, schurindex, True, S)
+
+    def zgordschur_batch(self, problems, *args, **kw):
+        """Copying form of zgordschur_batch_: the decompositions are left untouched (device tensors are copied too)."""
+        return self._ordschur_batch(_Z, self.zgordschur_batch_, problems, args, kw, _GORD_WRONG)
 
     def eigvecs(self, ps0, select, shifted=True, method="ordschur"):
         """LinearAlgebra.eigvecs(ps::PeriodicSchur, select; shifted) — src/vectors.jl:25-138: selected right

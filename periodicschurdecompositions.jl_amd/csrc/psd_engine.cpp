@@ -28,6 +28,7 @@
 #include "psd_zbqz.h"
 #include "psd_zgbqz.h"
 #include "psd_zbord.h"
+#include "psd_zgbord.h"
 
 #include "../../include/psd_mi355x.h"
 
@@ -3954,4 +3955,5 @@ extern "C" int psd_dbg_apply_bench(psd_ctx* c, int n, int p, int nwin, int W, in
 #include "psd_zbevec_host.inl"
 #include "psd_bord_host.inl"
 #include "psd_zbord_host.inl"
+#include "psd_zgbord_host.inl"
 #include "psd_diag_scalar.inl"

@@ -241,19 +241,22 @@ PSD_KERNEL psd_zgord_init(psd_zgoparams O, int n, int p, int wantZ, int W) {
     }
 }
 
-// ordschur.jl:75-96 _updateλ!(P::GeneralizedPeriodicSchur): scaled eigenvalue j from the diagonals.  grid over j
+// ordschur.jl:75-96 _updateλ!(P::GeneralizedPeriodicSchur): scaled eigenvalue j from the diagonals
+PSD_D void psd_zgord_value_at(const psd_zgparams& P, int n, int p, int j) {
+    psd_z a;
+    double b;
+    int sc;
+    psd_zg_safeprod(P, n, p, j, a, b, sc);
+    P.alpha[j - 1] = a;
+    P.beta[j - 1] = b;
+    P.ascale[j - 1] = sc;
+}
+
+// grid over j
 PSD_KERNEL psd_zgord_values(psd_zgparams P, int n, int p) {
     const int NT = PSD_NTHREADS;
     PSD_PAR_FOR(t, NT) {
         const int j = 1 + PSD_BLOCK_X * NT + t;
-        if (j <= n) {
-            psd_z a;
-            double b;
-            int sc;
-            psd_zg_safeprod(P, n, p, j, a, b, sc);
-            P.alpha[j - 1] = a;
-            P.beta[j - 1] = b;
-            P.ascale[j - 1] = sc;
-        }
+        if (j <= n) psd_zgord_value_at(P, n, p, j);
     }
 }

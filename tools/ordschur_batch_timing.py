@@ -12,7 +12,11 @@ median modulus are selected per problem (the stable half of a Floquet spectrum),
   --complex         the ComplexF64 family on the same shapes: Engine.zpschur_batch decomposes complex bench_factors, one
                     Engine.zordschur_batch_ call (psd_z_ordschur_batch) against the loop of Engine.ordschur_
                     (psd_z_ordschur) over the same problems, both host entries with their copies, and the device-resident
-                    entry.
+                    entry;
+  --signed          the signed ComplexF64 family on the same shapes: Engine.zgpschur_batch decomposes complex bench_factors
+                    under the alternating signature (T, F, T, F, ...) — a pencil sequence —, one Engine.zgordschur_batch_
+                    call (psd_z_gordschur_batch) against the loop of Engine.ordschur_ (psd_z_gordschur) over the same
+                    problems, and the device-resident entry.
 
 The second of two runs of each is reported.  One JSON line per shape on stdout; --json FILE collects them."""
 import argparse
@@ -33,8 +37,19 @@ def parse_shapes(text):
 def clones(pss):
     import psd_amd
 
-    return [psd_amd.PeriodicSchur([t.copy(order="F") for t in ps.Ts], [z.copy(order="F") for z in ps.Z], ps.values.copy(),
-                                  ps.orientation, ps.schurindex) for ps in pss]
+    def mats(ps):
+        return [t.copy(order="F") for t in ps.Ts], [z.copy(order="F") for z in ps.Z]
+
+    if isinstance(pss[0], psd_amd.GeneralizedPeriodicSchur):
+        return [psd_amd.GeneralizedPeriodicSchur(list(ps.S), *mats(ps), ps.alpha.copy(), ps.beta.copy(), ps.alphascale.copy(),
+                                                 ps.orientation, ps.schurindex) for ps in pss]
+    return [psd_amd.PeriodicSchur(*mats(ps), ps.values.copy(), ps.orientation, ps.schurindex) for ps in pss]
+
+
+def entry(eng, family):
+    """(the in-place batched method, the name of its stats attribute) of a family: "d", "z" or "zg"."""
+    name = {"d": "ordschur_batch", "z": "zordschur_batch", "zg": "zgordschur_batch"}[family]
+    return getattr(eng, name + "_"), name + "_stats"
 
 
 def time_loop(eng, pss, sels):
@@ -51,22 +66,26 @@ def time_loop(eng, pss, sels):
     return best
 
 
-def time_batch(eng, pss, sels, cplx=False):
+def time_batch(eng, pss, sels, family="d"):
+    fn, stats = entry(eng, family)
     best = None
     for _ in range(2):
         work = clones(pss)
         t0 = time.perf_counter()
-        (eng.zordschur_batch_ if cplx else eng.ordschur_batch_)(work, sels)
+        fn(work, sels)
         wall = 1e3 * (time.perf_counter() - t0)
-        st = eng.zordschur_batch_stats if cplx else eng.ordschur_batch_stats
+        st = getattr(eng, stats)
         best = dict(wall_ms=wall, ms_total=st.ms_total, ms_copy=st.ms_copy, nswaps=int(st.nsweeps), nwindows=int(st.nwindows),
                     window=int(st.window), launches=int(st.nlaunch_step))
     return best
 
 
-def time_dev(eng, pss, sels, lr, cplx=False):
+def time_dev(eng, pss, sels, lr, family="d"):
     import numpy as np
     import torch
+
+    fn, stats = entry(eng, family)
+    kw = dict(S=pss[0].S) if family == "zg" else {}
 
     T0 = torch.from_numpy(np.array([[np.array(t) for t in ps.Ts] for ps in pss])).cuda().transpose(2, 3).contiguous().transpose(2, 3)
     Z0 = torch.from_numpy(np.array([[np.array(z) for z in ps.Z] for ps in pss])).cuda().transpose(2, 3).contiguous().transpose(2, 3)
@@ -75,9 +94,9 @@ def time_dev(eng, pss, sels, lr, cplx=False):
         T, Z = T0.clone(), Z0.clone()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        (eng.zordschur_batch_ if cplx else eng.ordschur_batch_)(T, Z, sels, lr=lr, schurindex=pss[0].schurindex)
+        fn(T, Z, sels, lr=lr, schurindex=pss[0].schurindex, **kw)
         torch.cuda.synchronize()
-        st = eng.zordschur_batch_stats if cplx else eng.ordschur_batch_stats
+        st = getattr(eng, stats)
         best = dict(wall_ms=1e3 * (time.perf_counter() - t0), ms_total=st.ms_total)
     return best
 
@@ -89,6 +108,7 @@ def main():
     ap.add_argument("--lr", default="R")
     ap.add_argument("--loop-only", action="store_true")
     ap.add_argument("--complex", dest="cplx", action="store_true")
+    ap.add_argument("--signed", action="store_true", help="signed ComplexF64 problems, alternating signature")
     ap.add_argument("--lib", default=None, help="library to load instead of the package's (a build of another commit)")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
@@ -102,17 +122,22 @@ def main():
 
     eng = psd_amd.Engine(0, libpath=args.lib)
     rows = []
+    family = "zg" if args.signed else "z" if args.cplx else "d"
     for (nb, n, p) in parse_shapes(args.shapes):
-        if args.cplx:
+        if args.signed:
+            S = [q % 2 == 0 for q in range(p)]
+            pss = eng.zgpschur_batch([pt.bench_factors(n, p, seed=9000 + q, dtype=np.complex128) for q in range(nb)],
+                                     S[::-1] if args.lr == "L" else S, args.lr)
+        elif args.cplx:
             pss = eng.zpschur_batch([pt.bench_factors(n, p, seed=9000 + q, dtype=np.complex128) for q in range(nb)], args.lr)
         else:
             pss = eng.pschur_batch([pt.bench_factors(n, p, seed=9000 + q) for q in range(nb)], args.lr)
         sels = np.array([np.abs(ps.values) <= np.sort(np.abs(ps.values))[n // 2] for ps in pss])
-        row = dict(nb=nb, n=n, p=p, lr=args.lr, dtype="complex128" if args.cplx else "float64",
+        row = dict(nb=nb, n=n, p=p, lr=args.lr, dtype="float64" if family == "d" else "complex128", signed=args.signed,
                    loop=time_loop(eng, pss, sels))
         if not args.loop_only:
-            row["batch"] = time_batch(eng, pss, sels, args.cplx)
-            row["dev"] = time_dev(eng, pss, sels, args.lr, args.cplx)
+            row["batch"] = time_batch(eng, pss, sels, family)
+            row["dev"] = time_dev(eng, pss, sels, args.lr, family)
             row["wall_ratio"] = row["loop"]["wall_ms"] / row["batch"]["wall_ms"]
             row["device_ratio"] = row["loop"]["ms_total"] / row["batch"]["ms_total"] if row["batch"]["ms_total"] else None
             row["swaps_per_s"] = 1e3 * row["batch"]["nswaps"] / row["batch"]["wall_ms"]
