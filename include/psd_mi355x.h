@@ -719,6 +719,42 @@ int psd_z_eigvecs_batch_dev(psd_ctx* ctx, int nb, int n, int p, const double* dT
                             const uint8_t* select, int shifted, double* dV, int maxvec, int* nvec, int32_t* pcnt,
                             psd_bevec_stats* stats, int* info);
 
+/* ---- zgeigvecs_batch: eigenvectors of many small signed ComplexF64 periodic Schur forms in one call ----------------
+ * psd_z_geigvecs (homogeneous back-substitution, the periodic form of xTGEVC) for nb generalized decompositions of one
+ * shape (n, p) and ONE signature, as psd_z_gpschur_batch / psd_z_gordschur_batch leave them: ComplexF64, one orient and
+ * schurindex (any in 1..p) for the whole batch; the conventions of psd_z_eigvecs_batch.  Per problem the result contract
+ * is that of psd_z_geigvecs: one column per selected row, top to bottom, the scalars a_l = T_l(k, k) at the column's own
+ * row k, the relations of the signature table above, ||V_1(:, j)|| = 1 with the largest-modulus entry real and positive;
+ * a zero or infinite eigenvalue (a zero a_l) gives a valid finite column (counted), pivots below smin are replaced
+ * (counted), columns past 2^500 are rescaled by a power of two (counted).  A problem's vectors do not depend on its place
+ * in the batch or on the grouping (bit for bit).  A NULL or all-true S runs this path too, not psd_z_eigvecs_batch: the
+ * contract differs on zero eigenvalues and on a.  Up to order 128 the whole back-substitution of a group is one launch
+ * (psd_zgbev_solve: several columns per wavefront for p <= 32, the scalars read from the factors on the device) and the
+ * call makes four launches with shifted and p > 1, three otherwise, whatever nb and n are; the device entry makes one
+ * more, the gather of the diagonals, when a is not NULL; none when nothing is selected (stats->nlaunch).  Above,
+ * psd_z_geigvecs_dev's driver runs problem by problem on the slices of the batch buffers.  PSD_BATCH_GROUP acts as for
+ * psd_d_eigvecs_batch.
+ *
+ * T, Z: nb * p pointers to n x n interleaved complex matrices (problem-major, user order).  S: host [p] flags in user
+ * order, or NULL (all true).  select: host [nb][n], used as given; nvec[q] is the count of its row q, and a problem whose
+ * row is all false costs nothing.  V, maxvec, nvec and V = NULL (a size query) as for psd_z_eigvecs_batch.  a: host
+ * [nb][maxvec][p] complex interleaved — per problem column-major p x maxvec with ld p, as psd_z_geigvecs lays it out, the
+ * columns at and beyond nvec[q] zero — or NULL.  pcnt: host [nb][3] or NULL: perturbed pivots, rescaled columns, columns
+ * with a zero or infinite eigenvalue per problem; stats->nzero is the sum of the third.
+ * info: 0; -1 ctx NULL; -2 n < 1; -3 p < 1; -4 T NULL; -5 Z NULL; (-6 is not used: there are no eigenvalue arguments);
+ * -7 orient; -8 schurindex not in 1..p; -9 select NULL; -10 maxvec below the largest nvec; -11 nb < 0; -12 nvec NULL;
+ * PSD_INFO_NOTIMPL on a period-sharded context; PSD_INFO_RUNTIME + k.  nb == 0 returns 0 and touches nothing. */
+int psd_z_geigvecs_batch(psd_ctx* ctx, int nb, int n, int p, double* const* T, double* const* Z, const uint8_t* S,
+                         char orient, int schurindex, const uint8_t* select, int shifted, double* const* V, int maxvec,
+                         double* a, int* nvec, int32_t* pcnt, psd_bevec_stats* stats, int* info);
+/* Device-resident variant: dT, dZ device [nb][p][n][n] interleaved column-major blocks in user order (what
+ * psd_z_gpschur_batch_dev / psd_z_gordschur_batch_dev leave), dV a device block [nb][nmat][maxvec][n] of interleaved
+ * complex values.  S, select, a, nvec and pcnt are host arrays; a costs one gather kernel and one read-back for the whole
+ * batch, skipped when it is NULL. */
+int psd_z_geigvecs_batch_dev(psd_ctx* ctx, int nb, int n, int p, const double* dT, const double* dZ, const uint8_t* S,
+                             char orient, int schurindex, const uint8_t* select, int shifted, double* dV, int maxvec,
+                             double* a, int* nvec, int32_t* pcnt, psd_bevec_stats* stats, int* info);
+
 /* ---- ordschur_batch: reorder many small periodic Schur forms in one call ------------------------------------------
  * psd_d_ordschur (rordschur.jl:3-132) for nb decompositions of one shape (n, p), as psd_d_pschur_batch leaves them:
  * Float64, all-true signature, one orient and schurindex (1 or p) for the whole batch.  Per problem the result contract

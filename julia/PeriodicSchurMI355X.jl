@@ -24,7 +24,7 @@ import PeriodicSchurDecompositions: pschur!, pschur, phessenberg!, gpschur, Peri
 const PSD = PeriodicSchurDecompositions
 using ArnoldiMethod: ArnoldiMethod
 
-export set_train!, engine_version, pschur_batch!, pschur_batch, gpschur_batch, eigvecs_batch_device, ordschur_batch!
+export set_train!, engine_version, pschur_batch!, pschur_batch, gpschur_batch, eigvecs_batch_device, geigvecs_batch_device, ordschur_batch!
 
 const libpsd = get(ENV, "LIBPSD_MI355X", joinpath(@__DIR__, "..", "periodicschurdecompositions.jl_amd", "libpsd_mi355x.so"))
 
@@ -495,6 +495,53 @@ function eigvecs_batch_device(problems::Vector{<:PeriodicSchur{ComplexF64}}, sel
         end
         info[] != 0 && _throw(info[])
         return [[V[(q - 1) * nmat + l][:, 1:nvec[q]] for l in 1:nmat] for q in 1:nb]
+    end
+end
+
+# geigvecs_batch_device(problems, select; shifted) — geigvecs_device for many small signed ComplexF64 decompositions of one
+# shape and one signature in one call (psd_z_geigvecs_batch), the follow-up of gpschur_batch and of the signed
+# ordschur_batch!.  Returns, per problem, (Vs, a) as geigvecs_device does; `select` is used as given; a zero or infinite
+# eigenvalue gives a valid column.  (Like the rest of this file it has not been executed: no Julia toolchain; the tested
+# mirror is Engine.zgeigvecs_batch.)
+function geigvecs_batch_device(problems::Vector{<:GeneralizedPeriodicSchur{ComplexF64}}, select::AbstractVector;
+                               shifted::Bool = true)
+    nb = length(problems)
+    nb == 0 && return Tuple{Vector{Matrix{ComplexF64}}, Matrix{ComplexF64}}[]
+    ps1 = problems[1]
+    p = ps1.period; n = size(ps1.T1, 1); js = ps1.schurindex; orient = ps1.orientation
+    S = UInt8.(collect(ps1.S))
+    (isempty(ps1.Z) || size(ps1.Z[1], 1) == 0) && throw(ArgumentError("geigvecs requires Schur vectors in the PSD"))
+    sel = zeros(UInt8, n, nb)
+    for (q, ps) in enumerate(problems)
+        (ps.period == p && size(ps.T1, 1) == n && ps.schurindex == js && ps.orientation == orient) ||
+            throw(DimensionMismatch("the problems of a batch must have equal order, period, orientation and schurindex"))
+        UInt8.(collect(ps.S)) == S || throw(DimensionMismatch("the problems of a batch must have equal signatures S"))
+        sq = select[1] isa Bool ? select : select[q]
+        length(sq) == n || throw(ArgumentError("length of `select` must correspond to rank of Schur (sub-)space"))
+        sel[:, q] .= UInt8.(sq)
+    end
+    # user order: T1 at schurindex, the others around it
+    T = reduce(vcat, [[j == js ? ps.T1 : ps.T[j < js ? j : j - 1] for j in 1:p] for ps in problems])
+    Z = reduce(vcat, [ps.Z for ps in problems])
+    nvec = zeros(Cint, nb); info = Ref{Cint}(0)
+    Tp = _ptrs(T); Zp = _ptrs(Z)
+    nmat = shifted ? p : 1
+    call(Vp, maxvec, a) = ccall((:psd_z_geigvecs_batch, libpsd), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ptr{UInt8}, Cchar, Cint, Ptr{UInt8}, Cint,
+         Ptr{Ptr{ComplexF64}}, Cint, Ptr{ComplexF64}, Ptr{Cint}, Ptr{Int32}, Ptr{Cvoid}, Ref{Cint}),
+        ctx().ptr, nb, n, p, Tp, Zp, S, orient, js, sel, shifted, Vp, maxvec, a, nvec, C_NULL, C_NULL, info)
+    GC.@preserve T Z S sel nvec begin
+        call(C_NULL, 0, C_NULL)                           # size query: nvec
+        info[] != 0 && _throw(info[])
+        maxvec = Int(maximum(nvec))
+        V = [zeros(ComplexF64, n, maxvec) for _ in 1:(nb * nmat)]
+        a = zeros(ComplexF64, p, maxvec, nb)
+        Vp = [pointer(v) for v in V]
+        GC.@preserve V Vp a begin
+            call(Vp, maxvec, a)
+        end
+        info[] != 0 && _throw(info[])
+        return [([V[(q - 1) * nmat + l][:, 1:nvec[q]] for l in 1:nmat], a[:, 1:nvec[q], q]) for q in 1:nb]
     end
 end
 

@@ -39,11 +39,13 @@ struct bevec_call {
 
 // The device part of a group, for both families (CPLX: the kernels of psd_zbevec.h): the tables of gc problems (itab, dtab,
 // the units behind them) go up, then the solve, the back-transformation of V_1, its norms and phases, the other factors,
-// and one read-back of the counters into cnt3 [gc][3]
+// and one read-back of the counters into cnt3 [gc][3].  sgn (complex only): the senses of the working factors of a signed
+// batch — psd_zgbev_solve (psd_zgbevec.h) is the solve then, there are no doubles to upload (dtab is empty), and the third
+// counter is the columns with a zero scalar, from flags of their own behind the counters (no NaN columns)
 template <bool CPLX>
 int bevec_launch(const bevec_call& k, int gc, const double* dT, const double* dZ, std::vector<int>& itab,
                  const std::vector<double>& dtab, const std::vector<int>& units, int nsm, double* dV, int32_t* cnt3,
-                 psd_bevec_stats* st) {
+                 psd_bevec_stats* st, const int* sgn = nullptr) {
     psd_ctx* c = k.c;
     const int n = k.n, p = k.p, nmat = k.shifted ? p : 1;
     const int nunits = (int)(units.size() / 2);
@@ -53,24 +55,30 @@ int bevec_launch(const bevec_call& k, int gc, const double* dT, const double* dZ
         return 0;
     }
     itab.insert(itab.end(), units.begin(), units.end());
-    const size_t ncnt = 3 * (size_t)gc * n;
+    const size_t isgn = itab.size();
+    if (sgn) itab.insert(itab.end(), sgn, sgn + p);
+    const size_t ncnt = 3 * (size_t)gc * n, nflag = sgn ? (size_t)gc * n : 0;
     psd_batchbuf bI, bD, bX, bR, bS, bC;
     PSD_CHECK(bI.alloc(sizeof(int) * itab.size()));
-    PSD_CHECK(bD.alloc(sizeof(double) * dtab.size()));
+    if (!dtab.empty()) PSD_CHECK(bD.alloc(sizeof(double) * dtab.size()));
     PSD_CHECK(bX.alloc(sizeof(double) * 2 * (size_t)gc * p * n * nsm));
     if (p > 64) PSD_CHECK(bR.alloc(sizeof(double) * 4 * (size_t)nunits * p));
     PSD_CHECK(bS.alloc(sizeof(double) * 2 * (size_t)gc * n));
-    PSD_CHECK(bC.alloc(sizeof(int) * ncnt));
+    PSD_CHECK(bC.alloc(sizeof(int) * (ncnt + nflag)));
     PSD_CHECK(psd_rt_h2d(bI.ptr, itab.data(), sizeof(int) * itab.size(), c->stream));
-    PSD_CHECK(psd_rt_h2d(bD.ptr, dtab.data(), sizeof(double) * dtab.size(), c->stream));
-    PSD_CHECK(psd_rt_memset(bC.ptr, 0, sizeof(int) * ncnt, c->stream));
+    if (!dtab.empty()) PSD_CHECK(psd_rt_h2d(bD.ptr, dtab.data(), sizeof(double) * dtab.size(), c->stream));
+    PSD_CHECK(psd_rt_memset(bC.ptr, 0, sizeof(int) * (ncnt + nflag), c->stream));
     Timer tsolve, tback;
     tsolve.start(c->stream);
     psd_bev_args a;
     a.T = dT; a.itab = (const int*)bI.ptr; a.dtab = bD.d(); a.X = bX.d(); a.R = bR.d(); a.cnt = (int*)bC.ptr;
     a.n = n; a.p = p; a.nsm = nsm; a.nunits = nunits; a.gc = gc; a.six = k.six;
     const int C = 64 / psd_bev_lw(p);
-    if (CPLX) PSD_LAUNCH(psd_zbev_solve, psd_dim3((nunits + C - 1) / C), 64, PSD_BEV_LDS, c->stream, a);
+    if (sgn) {
+        psd_zgbev_args ga;
+        ga.b = a; ga.sgn = (const int*)bI.ptr + isgn; ga.zc = (int*)bC.ptr + ncnt;
+        PSD_LAUNCH(psd_zgbev_solve, psd_dim3((nunits + C - 1) / C), 64, PSD_ZGBEV_LDS, c->stream, ga);
+    } else if (CPLX) PSD_LAUNCH(psd_zbev_solve, psd_dim3((nunits + C - 1) / C), 64, PSD_BEV_LDS, c->stream, a);
     else PSD_LAUNCH(psd_bev_solve, psd_dim3((nunits + C - 1) / C), 64, PSD_BEV_LDS, c->stream, a);
     st->nlaunch += 1;
     st->ms_solve += tsolve.stop(c->stream);
@@ -92,8 +100,8 @@ int bevec_launch(const bevec_call& k, int gc, const double* dT, const double* dZ
         st->nlaunch += 1;
     }
     st->ms_backtransform += tback.stop(c->stream);
-    std::vector<int> cnt(ncnt);
-    PSD_CHECK(psd_rt_d2h(cnt.data(), bC.ptr, sizeof(int) * ncnt, c->stream));
+    std::vector<int> cnt(ncnt + nflag);
+    PSD_CHECK(psd_rt_d2h(cnt.data(), bC.ptr, sizeof(int) * (ncnt + nflag), c->stream));
     PSD_CHECK(psd_rt_sync(c->stream));
     PSD_CHECK(psd_rt_last_error());
     for (int q = 0; q < gc; ++q)
@@ -101,7 +109,7 @@ int bevec_launch(const bevec_call& k, int gc, const double* dT, const double* dZ
             const int* e = cnt.data() + 3 * ((size_t)q * n + j);
             cnt3[3 * q] += e[0];
             cnt3[3 * q + 1] += e[1] > 0;
-            cnt3[3 * q + 2] += e[2];
+            cnt3[3 * q + 2] += sgn ? cnt[ncnt + (size_t)q * n + j] : e[2];
         }
     return 0;
 }
@@ -155,14 +163,15 @@ int bevec_group(const bevec_call& k, int gc, const double* dT, const double* dZ,
     return bevec_launch<false>(k, gc, dT, dZ, itab, dtab, units, nsm, dV, cnt3, st);
 }
 
-// above PSD_BEV_NMAX, for both families: the single path on the slices of the batch buffers (its V blocks are n x nvec:
-// through a staging block into the n x maxvec blocks of the batch).  lam [gc][n]: the eigenvalues; select: completed
-template <bool CPLX>
-int bevec_single(const bevec_call& k, int gc, const double* dT, const double* dZ, const std::complex<double>* lam,
-                 const uint8_t* select, const int* nvec, double* dV, int32_t* cnt3, psd_bevec_stats* st) {
+// above PSD_BEV_NMAX, for every family: a single path on the slices of the batch buffers (its V blocks are n x nvec:
+// through a staging block into the n x maxvec blocks of the batch).  select: completed; single(q, sel, dVq, es) runs the
+// single driver on problem q with its row of select, for nvec[q] columns
+template <class Single>
+int bevec_single_loop(const bevec_call& k, int gc, const uint8_t* select, const int* nvec, double* dV, int32_t* cnt3,
+                      psd_bevec_stats* st, Single single) {
     psd_ctx* c = k.c;
     const int n = k.n, p = k.p, nmat = k.shifted ? p : 1;
-    const size_t bd = (CPLX ? 2 : 1) * (size_t)n * n, vb = 2 * (size_t)n * k.maxvec;
+    const size_t vb = 2 * (size_t)n * k.maxvec;
     PSD_CHECK(psd_rt_memset(dV, 0, sizeof(double) * vb * nmat * gc, c->stream));
     psd_batchbuf stage;
     PSD_CHECK(stage.alloc(sizeof(double) * vb * nmat));
@@ -171,8 +180,7 @@ int bevec_single(const bevec_call& k, int gc, const double* dT, const double* dZ
         std::vector<uint8_t> sel(select + (size_t)q * n, select + (size_t)(q + 1) * n);
         psd_evec_stats es;
         memset(&es, 0, sizeof(es));
-        const int rc = eigvecs_dev<CPLX>(c, n, p, dT + (size_t)q * p * bd, dZ + (size_t)q * p * bd, lam + (size_t)q * n,
-                                         k.orient, k.schurindex, sel.data(), k.shifted, stage.d(), nvec[q], &es);
+        const int rc = single(q, sel.data(), stage.d(), &es);
         if (rc != 0) return rc;
         for (int l = 0; l < nmat; ++l)
             PSD_CHECK(psd_rt_d2d(dV + ((size_t)q * nmat + l) * vb, stage.d() + 2 * (size_t)l * n * nvec[q],
@@ -185,6 +193,28 @@ int bevec_single(const bevec_call& k, int gc, const double* dT, const double* dZ
         st->ms_backtransform += es.ms_backtransform;
         st->nlaunch += 3 + 2 * ((n + PSD_EV_CH - 1) / PSD_EV_CH);  // (an upper bound: a launch pair per chunk)
     }
+    return 0;
+}
+
+// eigvecs_dev as that single path.  lam [gc][n]: the eigenvalues
+template <bool CPLX>
+int bevec_single(const bevec_call& k, int gc, const double* dT, const double* dZ, const std::complex<double>* lam,
+                 const uint8_t* select, const int* nvec, double* dV, int32_t* cnt3, psd_bevec_stats* st) {
+    const int n = k.n, p = k.p;
+    const size_t bd = (CPLX ? 2 : 1) * (size_t)n * n;
+    return bevec_single_loop(k, gc, select, nvec, dV, cnt3, st, [&](int q, uint8_t* sel, double* dVq, psd_evec_stats* es) {
+        return eigvecs_dev<CPLX>(k.c, n, p, dT + (size_t)q * p * bd, dZ + (size_t)q * p * bd, lam + (size_t)q * n, k.orient,
+                                 k.schurindex, sel, k.shifted, dVq, nvec[q], es);
+    });
+}
+
+// the group loop of a device entry: groups of at most batch_group(c, nb, per) problems, body(q0, gc) for each (a
+// non-zero code ends the call)
+template <class Body>
+int bevec_dev_groups(psd_ctx* c, int nb, size_t per, Body body) {
+    const int g = batch_group(c, nb, per);
+    for (int q0 = 0; q0 < nb; q0 += g)
+        if (const int rc = body(q0, nb - q0 < g ? nb - q0 : g)) return rc;
     return 0;
 }
 
@@ -264,14 +294,12 @@ int psd_d_eigvecs_batch_dev(psd_ctx* c, int nb, int n, int p, const double* dT, 
     if (any) {
         const bevec_call k{c, n, p, left ? schurindex - 1 : p - schurindex, schurindex, shifted, maxvec, left, orient};
         const int nmat = shifted ? p : 1;
-        const int g = batch_group(c, nb, sizeof(double) * 2 * (size_t)p * n * (mv > 0 ? mv : 1));
-        for (int q0 = 0; q0 < nb; q0 += g) {
-            const int gc = nb - q0 < g ? nb - q0 : g;
-            *info = bevec_run(k, gc, dT + (size_t)q0 * p * nn, dZ + (size_t)q0 * p * nn, wr + (size_t)q0 * n,
-                              wi + (size_t)q0 * n, select + (size_t)q0 * n, bsz.data() + (size_t)q0 * n, nvec + q0,
-                              dV + 2 * (size_t)q0 * nmat * n * maxvec, cnt3.data() + 3 * (size_t)q0, st);
-            if (*info != 0) return *info;
-        }
+        *info = bevec_dev_groups(c, nb, sizeof(double) * 2 * (size_t)p * n * (mv > 0 ? mv : 1), [&](int q0, int gc) {
+            return bevec_run(k, gc, dT + (size_t)q0 * p * nn, dZ + (size_t)q0 * p * nn, wr + (size_t)q0 * n,
+                             wi + (size_t)q0 * n, select + (size_t)q0 * n, bsz.data() + (size_t)q0 * n, nvec + q0,
+                             dV + 2 * (size_t)q0 * nmat * n * maxvec, cnt3.data() + 3 * (size_t)q0, st);
+        });
+        if (*info != 0) return *info;
     } else {
         PSD_CHECK(psd_rt_memset(dV, 0, sizeof(double) * 2 * (size_t)nb * (shifted ? p : 1) * n * maxvec, c->stream));
         PSD_CHECK(psd_rt_sync(c->stream));

@@ -84,17 +84,31 @@ PSD_HD psd_gm<B> psd_gm_compose(const psd_gm<B>& m2, const psd_gm<B>& m1) {
     return r;
 }
 
+// What a map takes from its column beside the factors' entries — the scalar a_l, the sense of working factor l and the
+// update product r_l(row) — as the single path keeps them: a in the uploaded table, r in the GEMM's R buffer.  (The
+// batched path, psd_zgbevec.h, reads a from the factors and keeps r in LDS: its own source type.)
+template <bool CPLX>
+struct psd_gev_src {
+    const psd_gev_args& g;
+    const psd_ev_col<CPLX>& col;
+    PSD_HD psd_z a(int l) const {
+        return zmk(g.ac[2 * ((size_t)l * g.e.ns + col.j)], g.ac[2 * ((size_t)l * g.e.ns + col.j) + 1]);
+    }
+    PSD_HD bool fwd(int l) const { return g.sgn[l] != 0; }
+    PSD_HD psd_z r(int l, int i) const { return col.r(l, i); }
+};
+
 // the map of working factor l on the row block (i, B) of column col.j (own: no r, the rows below are zero)
-template <bool CPLX, int B>
-PSD_HD psd_gm<B> psd_gev_map(const psd_gev_args& g, const psd_ev_col<CPLX>& col, int l, int i, bool own) {
+template <bool CPLX, int B, class SRC>
+PSD_HD psd_gm<B> psd_gev_map(const SRC& g, const psd_ev_col<CPLX>& col, int l, int i, bool own) {
     psd_z D[2][2];
     col.d(l, i, B, D);
-    const psd_z a = zmk(g.ac[2 * ((size_t)l * g.e.ns + col.j)], g.ac[2 * ((size_t)l * g.e.ns + col.j) + 1]);
+    const psd_z a = g.a(l);
     psd_z r[2] = {zmk(0.0, 0.0), zmk(0.0, 0.0)};
     if (!own)
-        for (int q = 0; q < B; ++q) r[q] = col.r(l, i + q);
+        for (int q = 0; q < B; ++q) r[q] = g.r(l, i + q);
     psd_gm<B> m;
-    if (g.sgn[l]) {
+    if (g.fwd(l)) {
         for (int q = 0; q < B; ++q) {
             m.b[q] = r[q];
             for (int k = 0; k < B; ++k) m.A[q][k] = D[q][k];
@@ -129,10 +143,11 @@ PSD_HD int psd_gev_ilogb(psd_z z) {
 
 // y_l of every factor l of lane t on the row block (i, B): y = mant * 2^e.  store = false: the largest exponent of the
 // segment into mx and the perturbed pivots (counted at factor 0) into np; store = true: X rows i.. scaled by 2^-shift.
-template <bool CPLX, int B>
-PSD_D void psd_gev_lane(const psd_gev_args& g, const psd_ev_col<CPLX>& col, const psd_gm<B>* inc, const psd_gm<B>* suf,
-                        int t, int i, bool own, const psd_z* y0, bool store, int shift, int& mx, int& np) {
-    const int p = g.e.p;
+// inc, suf: the scans of the column's nl lanes (the wavefront, or a sub-group of it in the batched layout).
+template <bool CPLX, int B, class SRC>
+PSD_D void psd_gev_lane(const SRC& g, const psd_ev_col<CPLX>& col, const psd_gm<B>* inc, const psd_gm<B>* suf, int t,
+                        int nl, int i, bool own, const psd_z* y0, bool store, int shift, int& mx, int& np) {
+    const int p = col.a.p;
     const double eps = PSD_DBL_EPS, tiny = PSD_DBL_MIN;
     int lo, hi;
     psd_ev_seg(t, p, lo, hi);
@@ -154,7 +169,7 @@ PSD_D void psd_gev_lane(const psd_gev_args& g, const psd_ev_col<CPLX>& col, cons
             // the period from l: suffix l .. p-1 (this segment's factors, then the lanes after it), then the prefix
             psd_gm<B> s = psd_gm_ident<B>();
             for (int k = l; k < hi; ++k) s = psd_gm_compose(psd_gev_map<CPLX, B>(g, col, k, i, false), s);
-            if (t < 63) s = psd_gm_compose(suf[t + 1], s);
+            if (t + 1 < nl) s = psd_gm_compose(suf[t + 1], s);
             const psd_gm<B> T = psd_gm_compose(pre, s);
             double ref = zabs(T.c);
             for (int q = 0; q < B; ++q)
@@ -205,6 +220,7 @@ PSD_D void psd_gev_lane(const psd_gev_args& g, const psd_ev_col<CPLX>& col, cons
 template <bool CPLX, int B>
 PSD_D void psd_gev_row(const psd_gev_args& g, const psd_ev_col<CPLX>& col, char* lds, int i, int i1, bool own) {
     const psd_ev_args& a = g.e;
+    const psd_gev_src<CPLX> src{g, col};
     const int j = col.j, p = a.p, ke = a.kend[j];
     const int kin = ke < a.r1 ? ke : a.r1;
     psd_gm<B>* F = (psd_gm<B>*)lds;  // [2][64] inclusive forward scan
@@ -224,7 +240,7 @@ PSD_D void psd_gev_row(const psd_gev_args& g, const psd_ev_col<CPLX>& col, char*
                     col.setr(l, i + q, s);
                 }
             }
-            seg = psd_gm_compose(psd_gev_map<CPLX, B>(g, col, l, i, own), seg);
+            seg = psd_gm_compose(psd_gev_map<CPLX, B>(src, col, l, i, own), seg);
         }
         F[t] = seg;
         Sf[t] = seg;
@@ -262,7 +278,7 @@ PSD_D void psd_gev_row(const psd_gev_args& g, const psd_ev_col<CPLX>& col, char*
     // the largest entry y_l(I) will have: a column growing past 2^PSD_EV_BIG is scaled down first
     PSD_PAR_FOR(t, 64) {
         int mx, np;
-        psd_gev_lane<CPLX, B>(g, col, inc, suf, t, i, own, y0, false, 0, mx, np);
+        psd_gev_lane<CPLX, B>(src, col, inc, suf, t, 64, i, own, y0, false, 0, mx, np);
         red[t] = mx;
         if (t == 0 && np) a.cnt[3 * j] += np;
     }
@@ -275,7 +291,7 @@ PSD_D void psd_gev_row(const psd_gev_args& g, const psd_ev_col<CPLX>& col, char*
         int lo, hi, mx, np;
         psd_ev_seg(t, p, lo, hi);
         if (shift) col.rescale(lo, hi, i1, i, shift);
-        psd_gev_lane<CPLX, B>(g, col, inc, suf, t, i, own, y0, true, shift, mx, np);
+        psd_gev_lane<CPLX, B>(src, col, inc, suf, t, 64, i, own, y0, true, shift, mx, np);
     }
     PSD_SYNC();
 }

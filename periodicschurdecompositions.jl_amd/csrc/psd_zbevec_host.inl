@@ -24,14 +24,16 @@ std::vector<std::complex<double>> zbevec_values(int gc, int n, const double* alp
     return lam;
 }
 
-// gc problems resident on the device (dT, dZ [gc][p][n][n] complex, dV [gc][nmat][maxvec][n] complex), their eigenvalues
-// and selections; cnt3 [gc][3] receives the counters per problem
-int zbevec_group(const bevec_call& k, int gc, const double* dT, const double* dZ, const std::complex<double>* lam,
-                 const uint8_t* select, double* dV, int32_t* cnt3, psd_bevec_stats* st) {
+// The tables of gc complex problems from their selections: the integers (itab), the units, and with lam [gc][n] the doubles
+// (dtab: roots and eigenvalues); the signed path (psd_zgbevec_host.inl) has no eigenvalues, passes lam = nullptr and leaves
+// dtab empty.  Returns the largest number of solve columns of a problem.
+int zbevec_tables(const bevec_call& k, int gc, const std::complex<double>* lam, const uint8_t* select,
+                  std::vector<int>& itab, std::vector<double>& dtab, std::vector<int>& units) {
     const int n = k.n, p = k.p;
     const int IS = psd_bev_istride(n), IH = psd_bev_ihead(p), DS = psd_bev_dstride(n);
-    std::vector<int> itab((size_t)IH + (size_t)gc * IS, 0), units;
-    std::vector<double> dtab((size_t)gc * DS, 0.0);
+    itab.assign((size_t)IH + (size_t)gc * IS, 0);
+    dtab.assign(lam ? (size_t)gc * DS : 0, 0.0);
+    units.clear();
     for (int j = 0; j < p; ++j) {  // working form (left orientation), as eigvecs_dev
         itab[j] = k.left ? j : p - 1 - j;
         itab[p + j] = k.left ? j : (p - j) % p;
@@ -39,25 +41,29 @@ int zbevec_group(const bevec_call& k, int gc, const double* dT, const double* dZ
     int nsm = 0;
     for (int q = 0; q < gc; ++q) {
         int* tab = itab.data() + IH + (size_t)q * IS;
-        double* dt = dtab.data() + (size_t)q * DS;
-        const std::complex<double>* l = lam + (size_t)q * n;
+        double* dt = lam ? dtab.data() + (size_t)q * DS : nullptr;
+        const std::complex<double>* l = lam ? lam + (size_t)q * n : nullptr;
         int ns = 0;
         for (int i = 0; i < n; ++i) {
             tab[i] = 1;  // (every row block is one row; the kernel does not look)
-            dt[4 * n + 2 * i] = l[i].real();
-            dt[4 * n + 2 * i + 1] = l[i].imag();
+            if (l) {
+                dt[4 * n + 2 * i] = l[i].real();
+                dt[4 * n + 2 * i + 1] = l[i].imag();
+            }
             if (!select[(size_t)q * n + i]) continue;
-            const std::complex<double> u = psd_ev_root(l[i], p);
             tab[n + ns] = i;
             tab[2 * n + ns] = 1;
             tab[3 * n + ns] = i + 1;
             tab[4 * n + ns] = ns;
             tab[5 * n + ns] = 0;
             tab[6 * n + ns] = i + 1;
-            dt[2 * ns] = u.real();
-            dt[2 * ns + 1] = u.imag();
-            dt[2 * n + 2 * ns] = l[i].real();
-            dt[2 * n + 2 * ns + 1] = l[i].imag();
+            if (l) {
+                const std::complex<double> u = psd_ev_root(l[i], p);
+                dt[2 * ns] = u.real();
+                dt[2 * ns + 1] = u.imag();
+                dt[2 * n + 2 * ns] = l[i].real();
+                dt[2 * n + 2 * ns + 1] = l[i].imag();
+            }
             units.push_back(q);
             units.push_back(ns);
             ++ns;
@@ -65,6 +71,16 @@ int zbevec_group(const bevec_call& k, int gc, const double* dT, const double* dZ
         tab[7 * n] = ns;
         nsm = ns > nsm ? ns : nsm;
     }
+    return nsm;
+}
+
+// gc problems resident on the device (dT, dZ [gc][p][n][n] complex, dV [gc][nmat][maxvec][n] complex), their eigenvalues
+// and selections; cnt3 [gc][3] receives the counters per problem
+int zbevec_group(const bevec_call& k, int gc, const double* dT, const double* dZ, const std::complex<double>* lam,
+                 const uint8_t* select, double* dV, int32_t* cnt3, psd_bevec_stats* st) {
+    std::vector<int> itab, units;
+    std::vector<double> dtab;
+    const int nsm = zbevec_tables(k, gc, lam, select, itab, dtab, units);
     return bevec_launch<true>(k, gc, dT, dZ, itab, dtab, units, nsm, dV, cnt3, st);
 }
 
@@ -110,14 +126,12 @@ int psd_z_eigvecs_batch_dev(psd_ctx* c, int nb, int n, int p, const double* dT, 
     std::vector<int32_t> cnt3(3 * (size_t)nb, 0);
     if (mv > 0) {
         const bevec_call k{c, n, p, 0, schurindex, shifted, maxvec, left, orient};
-        const int g = batch_group(c, nb, sizeof(double) * 2 * (size_t)p * n * mv);
-        for (int q0 = 0; q0 < nb; q0 += g) {
-            const int gc = nb - q0 < g ? nb - q0 : g;
-            *info = zbevec_run(k, gc, dT + (size_t)q0 * p * nn2, dZ + (size_t)q0 * p * nn2, alpha + 2 * (size_t)q0 * n,
-                               beta + (size_t)q0 * n, ascale ? ascale + (size_t)q0 * n : nullptr, select + (size_t)q0 * n,
-                               nvec + q0, dV + 2 * (size_t)q0 * nmat * n * maxvec, cnt3.data() + 3 * (size_t)q0, st);
-            if (*info != 0) return *info;
-        }
+        *info = bevec_dev_groups(c, nb, sizeof(double) * 2 * (size_t)p * n * mv, [&](int q0, int gc) {
+            return zbevec_run(k, gc, dT + (size_t)q0 * p * nn2, dZ + (size_t)q0 * p * nn2, alpha + 2 * (size_t)q0 * n,
+                              beta + (size_t)q0 * n, ascale ? ascale + (size_t)q0 * n : nullptr, select + (size_t)q0 * n,
+                              nvec + q0, dV + 2 * (size_t)q0 * nmat * n * maxvec, cnt3.data() + 3 * (size_t)q0, st);
+        });
+        if (*info != 0) return *info;
     } else {
         PSD_CHECK(psd_rt_memset(dV, 0, sizeof(double) * 2 * (size_t)nb * nmat * n * maxvec, c->stream));
         PSD_CHECK(psd_rt_sync(c->stream));

@@ -13,6 +13,9 @@ device times and the launches of the stats, and the largest difference between t
              (PSD_BEV_NMAX in the environment), so that every order takes the batched kernels
   --complex  ComplexF64 factors: zpschur_batch_, then Engine.zeigvecs_batch (psd_z_eigvecs_batch_dev) against the loop
              of Engine.eigvecs_dev on the complex T, Z
+  --signed   signed ComplexF64 problems (alternating signature): zgpschur_batch_, then Engine.zgeigvecs_batch
+             (psd_z_geigvecs_batch_dev) against the loop of Engine.geigvecs_dev on the same device tensors; nb = 256,
+             n in {8, 16, 32, 64}, p in {4, 16}; one warm-up, then the median of five alternating runs of each
 
 Every shape runs in a process of its own under `timeout`; the tool stops at the first one that fails.  One JSON line per
 shape on stdout; --json FILE collects them."""
@@ -93,6 +96,76 @@ def run_one(nb, n, p, lr, sweep, cplx=False):
     print(json.dumps(row), flush=True)
 
 
+def signed_shapes():
+    return [(256, n, p) for n in (8, 16, 32, 64) for p in (4, 16)]
+
+
+def run_signed(nb, n, p, lr, repeats=5):
+    """--signed: zgpschur_batch_ with the alternating signature, then Engine.zgeigvecs_batch against the loop of
+    Engine.geigvecs_dev on the same device tensors.  One warm-up of each, then `repeats` timed runs of each, alternating;
+    the medians and the extremes are reported."""
+    import numpy as np
+    import torch
+
+    torch.cuda.init()
+    import psd_amd
+
+    eng = psd_amd.Engine(0)
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(9000 + n + 1000 * p)
+    A = torch.eye(n, dtype=torch.complex128, device="cuda") + 0.5 * torch.randn(
+        (nb, p, n, n), dtype=torch.complex128, device="cuda", generator=gen) / np.sqrt(n)
+    S = [l % 2 == 0 for l in range(p)]
+    infos = []
+    T, Z, values, _ = eng.zgpschur_batch_(A, S, lr, infos_out=infos)
+    si = p if lr == "L" else 1
+    select = np.ones((nb, n), dtype=bool)
+    select[[q for q in range(nb) if infos[q] != 0]] = False  # (a problem that did not converge is skipped)
+    Tc, Zc = T.transpose(2, 3), Z.transpose(2, 3)  # the [nb][p][n][n] column-major blocks, contiguous
+    assert Tc.is_contiguous() and Zc.is_contiguous()
+    row = dict(nb=nb, n=n, p=p, lr=lr, nfailed=int(sum(1 for i in infos if i != 0)), signed=True, repeats=repeats)
+
+    def batch():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = eng.zgeigvecs_batch(T, Z, select, S=S, lr=lr, schurindex=si)
+        torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t0), out
+
+    def loop():
+        torch.cuda.synchronize()
+        singles = []
+        t0 = time.perf_counter()
+        for q in range(nb):
+            singles.append(eng.geigvecs_dev(Tc[q], Zc[q], select[q], lr, si, S=S) if select[q, 0] else None)
+        torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t0), singles
+
+    batch(), loop()  # warm-up
+    tb, tl = [], []
+    for _ in range(repeats):
+        ms, (V, a, nvec) = batch()
+        tb.append(ms)
+        st = eng.eigvecs_batch_stats
+        ms, singles = loop()
+        tl.append(ms)
+    row["batch"] = dict(wall_ms=float(np.median(tb)), wall_ms_min=min(tb), wall_ms_max=max(tb), ms_solve=st.ms_solve,
+                        ms_backtransform=st.ms_backtransform, nlaunch=int(st.nlaunch), ngroups=int(st.ngroups),
+                        nvec=int(st.nvec_total), nzero=int(st.nzero), nperturbed=int(st.nperturbed))
+    row["loop"] = dict(wall_ms=float(np.median(tl)), wall_ms_min=min(tl), wall_ms_max=max(tl))
+    diff = adiff = 0.0
+    for q in range(0, nb, max(1, nb // 8)):
+        if singles[q] is not None:
+            Vs, aq = singles[q]
+            for l in range(p):
+                diff = max(diff, (V[q, l][:, :nvec[q]] - Vs[l]).abs().max().item())
+            adiff = max(adiff, float(np.abs(a[q][:, :nvec[q]] - aq).max()))
+    row["max_abs_diff"] = diff
+    row["max_abs_diff_a"] = adiff
+    row["wall_ratio"] = row["loop"]["wall_ms"] / row["batch"]["wall_ms"]
+    print(json.dumps(row), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--shapes", default=None, help="nb x n x p, comma separated (default: the grid above)")
@@ -100,15 +173,21 @@ def main():
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--sweep-orders", default="64,96,128,160,192,256")
     ap.add_argument("--complex", action="store_true", dest="cplx")
+    ap.add_argument("--signed", action="store_true")
     ap.add_argument("--timeout", type=int, default=240, help="seconds per shape")
     ap.add_argument("--json", default=None)
     ap.add_argument("--one", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.one and args.signed:
+        run_signed(*parse_shapes(args.one)[0], args.lr)
+        return 0
     if args.one:
         run_one(*parse_shapes(args.one)[0], args.lr, args.sweep, args.cplx)
         return 0
     if args.shapes:
         shapes = parse_shapes(args.shapes)
+    elif args.signed:
+        shapes = signed_shapes()
     elif args.sweep:
         shapes = [(64, int(x), 4) for x in args.sweep_orders.split(",") if x]
     else:
@@ -117,7 +196,7 @@ def main():
     for s in shapes:
         cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--one",
                "%dx%dx%d" % s, "--lr", args.lr] + (["--sweep"] if args.sweep else []) + (
-                   ["--complex"] if args.cplx else [])
+                   ["--complex"] if args.cplx else []) + (["--signed"] if args.signed else [])
         pr = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
         sys.stdout.write(pr.stdout)
         sys.stdout.flush()
