@@ -6,6 +6,10 @@
 // the host and uploaded once; then psd_bev_solve, psd_bev_backtransform for V_1, psd_bev_norm, psd_bev_backtransform for
 // the other factors — four launches whatever nb and n are — and one read-back of the counters.  Orders above
 // PSD_BEV_NMAX run eigvecs_dev problem by problem on the slices of the batch buffers.
+//
+// The complex and signed drivers (psd_zbevec_host.inl, psd_zgbevec_host.inl) come in behind this file and share the
+// argument checks, the call description, bevec_launch, the single-path loop, the statistics and the bodies of the two
+// kinds of entry (bevec_entry_dev, bevec_entry_host).
 
 namespace {
 
@@ -258,6 +262,49 @@ void bevec_finish(int nb, const int* nvec, const int32_t* cnt3, int32_t* pcnt, p
     if (pcnt) memcpy(pcnt, cnt3, sizeof(int32_t) * 3 * (size_t)nb);
 }
 
+// The device entry of every family behind its checks and counts (mv: the most columns of a problem, at most k.maxvec): nb
+// problems in dT / dZ [nb][p] blocks of bd doubles, dV [nb][nmat][maxvec][n] complex.  run(q0, gc, dT, dZ, dV, cnt3) is
+// the family's group run on the device blocks and counters of the problems from q0 on.
+template <class Run>
+int bevec_entry_dev(const bevec_call& k, int nb, size_t bd, const double* dT, const double* dZ, double* dV, int mv,
+                    const int* nvec, int32_t* pcnt, psd_bevec_stats* st, Run run) {
+    psd_ctx* c = k.c;
+    const int n = k.n, p = k.p, nmat = k.shifted ? p : 1;
+    std::vector<int32_t> cnt3(3 * (size_t)nb, 0);
+    if (mv > 0) {
+        const int rc = bevec_dev_groups(c, nb, sizeof(double) * 2 * (size_t)p * n * mv, [&](int q0, int gc) {
+            return run(q0, gc, dT + (size_t)q0 * p * bd, dZ + (size_t)q0 * p * bd, dV + 2 * (size_t)q0 * nmat * n * k.maxvec,
+                       cnt3.data() + 3 * (size_t)q0);
+        });
+        if (rc != 0) return rc;
+    } else {  // nothing selected
+        PSD_CHECK(psd_rt_memset(dV, 0, sizeof(double) * 2 * (size_t)nb * nmat * n * k.maxvec, c->stream));
+        PSD_CHECK(psd_rt_sync(c->stream));
+    }
+    bevec_finish(nb, nvec, cnt3.data(), pcnt, st);
+    return 0;
+}
+
+// The host entry likewise: T, Z (nb * p matrices of bd doubles) and V (nb * nmat of n x maxvec complex) through the
+// staged group loop (16 bytes per element of V and of the X planes)
+template <class Run>
+int bevec_entry_host(const bevec_call& k, int nb, size_t bd, double* const* T, double* const* Z, double* const* V, int mv,
+                     const int* nvec, int32_t* pcnt, psd_bevec_stats* st, Run run) {
+    const int n = k.n, p = k.p, nmat = k.shifted ? p : 1;
+    const size_t vb = 2 * (size_t)n * k.maxvec;
+    std::vector<int32_t> cnt3(3 * (size_t)nb, 0);
+    if (mv == 0 || k.maxvec == 0) {  // nothing selected
+        for (size_t e = 0; e < (size_t)nb * nmat; ++e) memset(V[e], 0, sizeof(double) * vb);
+    } else {
+        const batch_list L[] = {{T, p, bd, BATCH_IN}, {Z, p, bd, BATCH_IN}, {V, nmat, vb, BATCH_OUT}};
+        auto body = [&](int q0, int gc, double* const* d) { return run(q0, gc, d[0], d[1], d[2], cnt3.data() + 3 * (size_t)q0); };
+        const size_t per = sizeof(double) * (2 * bd * p + vb * nmat + 2 * (size_t)p * n * mv);
+        if (const int rc = batch_staged(k.c, nb, per, L, nullptr, batch_no_extra, body)) return rc;
+    }
+    bevec_finish(nb, nvec, cnt3.data(), pcnt, st);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -290,22 +337,13 @@ int psd_d_eigvecs_batch_dev(psd_ctx* c, int nb, int n, int p, const double* dT, 
     for (int q = 0; q < nb; ++q) mv = nvec[q] > mv ? nvec[q] : mv;
     if (!dV) return *info = 0;
     if (mv > maxvec) return *info = -10;
-    std::vector<int32_t> cnt3(3 * (size_t)nb, 0);
-    if (any) {
-        const bevec_call k{c, n, p, left ? schurindex - 1 : p - schurindex, schurindex, shifted, maxvec, left, orient};
-        const int nmat = shifted ? p : 1;
-        *info = bevec_dev_groups(c, nb, sizeof(double) * 2 * (size_t)p * n * (mv > 0 ? mv : 1), [&](int q0, int gc) {
-            return bevec_run(k, gc, dT + (size_t)q0 * p * nn, dZ + (size_t)q0 * p * nn, wr + (size_t)q0 * n,
-                             wi + (size_t)q0 * n, select + (size_t)q0 * n, bsz.data() + (size_t)q0 * n, nvec + q0,
-                             dV + 2 * (size_t)q0 * nmat * n * maxvec, cnt3.data() + 3 * (size_t)q0, st);
-        });
-        if (*info != 0) return *info;
-    } else {
-        PSD_CHECK(psd_rt_memset(dV, 0, sizeof(double) * 2 * (size_t)nb * (shifted ? p : 1) * n * maxvec, c->stream));
-        PSD_CHECK(psd_rt_sync(c->stream));
-    }
-    bevec_finish(nb, nvec, cnt3.data(), pcnt, st);
-    return *info = 0;
+    // (a selected row is a column or two: mv > 0 exactly when anything is selected)
+    const bevec_call k{c, n, p, left ? schurindex - 1 : p - schurindex, schurindex, shifted, maxvec, left, orient};
+    return *info = bevec_entry_dev(k, nb, nn, dT, dZ, dV, mv, nvec, pcnt, st,
+                                   [&](int q0, int gc, const double* dTg, const double* dZg, double* dVg, int32_t* cnt3) {
+        return bevec_run(k, gc, dTg, dZg, wr + (size_t)q0 * n, wi + (size_t)q0 * n, select + (size_t)q0 * n,
+                         bsz.data() + (size_t)q0 * n, nvec + q0, dVg, cnt3, st);
+    });
 }
 
 int psd_d_eigvecs_batch(psd_ctx* c, int nb, int n, int p, double* const* T, double* const* Z, const double* wr,
@@ -317,8 +355,6 @@ int psd_d_eigvecs_batch(psd_ctx* c, int nb, int n, int p, double* const* T, doub
         return *info;
     const size_t nn = (size_t)n * n, tot = (size_t)nb * n;
     const bool left = orient == 'L';
-    bool any = false;
-    for (size_t e = 0; e < tot && !any; ++e) any = select[e] != 0;
     std::vector<double> sub(tot, 0.0);  // (the factors are on the host: no kernel)
     for (int q = 0; q < nb; ++q) {
         const double* t = T[(size_t)q * p + schurindex - 1];
@@ -330,25 +366,12 @@ int psd_d_eigvecs_batch(psd_ctx* c, int nb, int n, int p, double* const* T, doub
     for (int q = 0; q < nb; ++q) mv = nvec[q] > mv ? nvec[q] : mv;
     if (!V) return *info = 0;
     if (mv > maxvec) return *info = -10;
-    const int nmat = shifted ? p : 1;
-    const size_t vb = 2 * (size_t)n * maxvec;
-    std::vector<int32_t> cnt3(3 * (size_t)nb, 0);
-    if (!any || maxvec == 0) {
-        for (size_t e = 0; e < (size_t)nb * nmat; ++e) memset(V[e], 0, sizeof(double) * vb);
-        bevec_finish(nb, nvec, cnt3.data(), pcnt, st);
-        return *info = 0;
-    }
     const bevec_call k{c, n, p, left ? schurindex - 1 : p - schurindex, schurindex, shifted, maxvec, left, orient};
-    const batch_list L[] = {{T, p, nn, BATCH_IN}, {Z, p, nn, BATCH_IN}, {V, nmat, vb, BATCH_OUT}};
-    auto body = [&](int q0, int gc, double* const* d) {
-        return bevec_run(k, gc, d[0], d[1], wr + (size_t)q0 * n, wi + (size_t)q0 * n, select + (size_t)q0 * n,
-                         bsz.data() + (size_t)q0 * n, nvec + q0, d[2], cnt3.data() + 3 * (size_t)q0, st);
-    };
-    const size_t per = sizeof(double) * (2 * nn * p + vb * nmat + 2 * (size_t)p * n * mv);
-    *info = batch_staged(c, nb, per, L, nullptr, batch_no_extra, body);
-    if (*info != 0) return *info;
-    bevec_finish(nb, nvec, cnt3.data(), pcnt, st);
-    return *info = 0;
+    return *info = bevec_entry_host(k, nb, nn, T, Z, V, mv, nvec, pcnt, st,
+                                    [&](int q0, int gc, const double* dTg, const double* dZg, double* dVg, int32_t* cnt3) {
+        return bevec_run(k, gc, dTg, dZg, wr + (size_t)q0 * n, wi + (size_t)q0 * n, select + (size_t)q0 * n,
+                         bsz.data() + (size_t)q0 * n, nvec + q0, dVg, cnt3, st);
+    });
 }
 
 }  // extern "C"

@@ -11,6 +11,11 @@
 //
 // Above PSD_ZB_NMAX the three steps are those of the single call — zhessenberg_dev, zformq_dev, ziterate_dev —, problem
 // by problem on the slices of the batch buffer.  A batch of one goes through the same kernels as any other.
+//
+// The signed driver (psd_zgbatch_host.inl) comes in behind this file and shares its workspace (zb_work), the launch and
+// read-back of the iteration kernel (zb_launch), the fallback loop above the cap (zb_single_loop) and the bodies of the
+// three kinds of entry with their argument codes (zb_pschur_batch_dev, zb_pschur_batch, zb_pschur_hess_batch), which take
+// the signature.
 
 namespace {
 
@@ -103,6 +108,74 @@ void zbatch_add_state(psd_stats* s, const State& st) {
     s->nlog += st.nlog;
 }
 
+// what psd_zbqz asks of zb_launch (the signed kernel: zgbqz_signed, psd_zgbatch_host.inl)
+struct zbqz_unsigned {
+    using args_t = psd_zbqz_args;
+    using state_t = psd_zstate;
+    static constexpr int capk = 4;  // (the slack of ziterate_dev's tick loop)
+    static size_t apply_lds(int W) { return psd_zbqz_apply_lds_bytes(W); }
+    static void set_hessmode(args_t&, int) {}
+    static const void* kernel() { return reinterpret_cast<const void*>(psd_zbqz); }
+    static void launch(psd_ctx* c, int nb, size_t lds, const args_t& A) {
+        PSD_LAUNCH(psd_zbqz, psd_dim3(nb), PSD_STEP_NT, lds, c->stream, A);
+    }
+};
+
+// One launch of the iteration kernel K over the nb problems of ws (dH / dZ [nb][p][n][n]) and one read-back: the states
+// and what the kernel left as per-problem codes (PSD_LIST_OVERFLOW, PSD_ZB_TICKCAP, level) in hst / hinfo, and with alpha
+// (nb * n complex pairs, host) the scaled eigenvalues in alpha, beta, ascale.  hessmode: stage 2 of the signed reduction.
+template <class K>
+int zb_launch(psd_ctx* c, zb_work<typename K::args_t>& ws, int nb, psd_z* dH, psd_z* dZ, int wantT, int wantZ, int maxitfac,
+              int hessmode, std::vector<typename K::state_t>& hst, std::vector<int>& hinfo, double* alpha = nullptr,
+              double* beta = nullptr, int32_t* ascale = nullptr) {
+    typename K::args_t& A = ws.A;
+    const int n = A.n, p = A.p;
+    const int W = choose_window(p, 16);
+    if (W == 0) return PSD_INFO_NOTIMPL;
+    A.H = dH;
+    A.Z = wantZ ? dZ : nullptr;
+    A.wantT = wantT; A.wantZ = wantZ; A.W = W; A.maxitfac = maxitfac;
+    K::set_hessmode(A, hessmode);
+    const int nbmin = (W - 3 > 0) ? ((W - 3 < 8) ? (W - 3) : 8) : 1;  // (the bound of the single drivers' tick loops)
+    A.cap = (long long)maxitfac * n * ((long long)n / nbmin + K::capk) + (long long)K::capk * n + 1024 +
+            (hessmode ? (long long)n * n : 0);
+    const size_t lds = std::max(step_lds_bytes(p, W, 16), K::apply_lds(W));
+    PSD_CHECK(c->lds_limit(K::kernel(), lds));
+    K::launch(c, nb, lds, A);
+    const size_t nv = alpha ? (size_t)nb * n : 0;
+    std::vector<int> hsc(nv);
+    hst.resize(nb);
+    hinfo.resize(nb);
+    PSD_CHECK(psd_rt_d2h(hst.data(), A.st, sizeof(typename K::state_t) * nb, c->stream));
+    PSD_CHECK(psd_rt_d2h(hinfo.data(), A.infos, sizeof(int) * nb, c->stream));
+    if (alpha) {
+        PSD_CHECK(psd_rt_d2h(alpha, A.alpha, sizeof(psd_z) * nv, c->stream));
+        PSD_CHECK(psd_rt_d2h(beta, A.beta, sizeof(double) * nv, c->stream));
+        PSD_CHECK(psd_rt_d2h(hsc.data(), A.ascale, sizeof(int) * nv, c->stream));
+    }
+    PSD_CHECK(psd_rt_sync(c->stream));
+    PSD_CHECK(psd_rt_last_error());
+    for (size_t e = 0; e < nv; ++e) ascale[e] = hsc[e];
+    return 0;
+}
+
+// Above the order cap: single(q, &ps) runs the single-problem iteration on problem q.  A code that ends a single call
+// ends the batch too unless it is one of `stay` (a list overflow, a tick bound: that problem's alone); W: the window the
+// call reports.
+template <class Single>
+int zb_single_loop(int nb, int W, int* infos, psd_stats* s, std::initializer_list<int> stay, Single single) {
+    for (int q = 0; q < nb; ++q) {
+        psd_stats ps;
+        memset(&ps, 0, sizeof(ps));
+        const int rc = single(q, &ps);
+        if (batch_fatal(rc) && std::find(stay.begin(), stay.end(), rc) == stay.end()) return rc;
+        infos[q] = rc;
+        batch_add_counts(s, ps);
+    }
+    s->window = W;
+    return 0;
+}
+
 // The iteration for nb Hessenberg-triangular problems on the device: dH / dZ [nb][p][n][n] internal order (dZ holds the
 // Q_j on entry).  alpha (nb * n complex pairs), beta, ascale (nb * n), infos (nb): host.  Per-problem codes go to infos;
 // the return value is a call-wide (runtime / not-implemented) code or 0.
@@ -113,43 +186,18 @@ int zbiterate_dev(psd_ctx* c, int nb, int n, int p, psd_z* dH, psd_z* dZ, int wa
     if (W == 0) return PSD_INFO_NOTIMPL;
     const int maxlog = 2 * maxitfac * n + n + 16;
     if (n > c->zb_nmax) {
-        int rc = c->zreserve(n, p, false, maxlog);
-        if (rc != 0) return rc;
-        for (int q = 0; q < nb; ++q) {
-            psd_stats ps;
-            memset(&ps, 0, sizeof(ps));
-            rc = zrun_iteration(c, n, p, dH + (size_t)q * p * nn, wantZ ? dZ + (size_t)q * p * nn : nullptr, wantT, wantZ,
-                                maxitfac, alpha + 2 * (size_t)q * n, beta + (size_t)q * n, ascale + (size_t)q * n, &ps,
-                                nullptr, 0);
-            if (batch_fatal(rc) && rc != PSD_INFO_RUNTIME + 77) return rc;
-            infos[q] = rc;
-            batch_add_counts(s, ps);
-        }
-        s->window = W;
-        return 0;
+        if (int e = c->zreserve(n, p, false, maxlog)) return e;
+        return zb_single_loop(nb, W, infos, s, {PSD_INFO_RUNTIME + 77}, [&](int q, psd_stats* ps) {
+            return zrun_iteration(c, n, p, dH + (size_t)q * p * nn, wantZ ? dZ + (size_t)q * p * nn : nullptr, wantT, wantZ,
+                                  maxitfac, alpha + 2 * (size_t)q * n, beta + (size_t)q * n, ascale + (size_t)q * n, ps, nullptr,
+                                  0);
+        });
     }
     zb_work<psd_zbqz_args> ws;
     if (int e = ws.alloc(c, nb, n, p, PSD_ZTR_CAP, maxlog)) return e;
-    psd_zbqz_args& A = ws.A;
-    A.H = dH;
-    A.Z = wantZ ? dZ : nullptr;
-    A.wantT = wantT; A.wantZ = wantZ; A.W = W; A.maxitfac = maxitfac;
-    const int nbmin = (W - 3 > 0) ? ((W - 3 < 8) ? (W - 3) : 8) : 1;  // (the bound of ziterate_dev's tick loop)
-    A.cap = (long long)maxitfac * n * ((long long)n / nbmin + 4) + 4LL * n + 1024;
-    size_t lds = step_lds_bytes(p, W, 16);
-    if (psd_zbqz_apply_lds_bytes(W) > lds) lds = psd_zbqz_apply_lds_bytes(W);
-    PSD_CHECK(c->lds_limit(reinterpret_cast<const void*>(psd_zbqz), lds));
-    PSD_LAUNCH(psd_zbqz, psd_dim3(nb), PSD_STEP_NT, lds, c->stream, A);
-    std::vector<psd_zstate> hst(nb);
-    std::vector<int> hsc((size_t)nb * n), hinfo(nb);
-    PSD_CHECK(psd_rt_d2h(hst.data(), A.st, sizeof(psd_zstate) * nb, c->stream));
-    PSD_CHECK(psd_rt_d2h(alpha, A.alpha, sizeof(psd_z) * (size_t)nb * n, c->stream));
-    PSD_CHECK(psd_rt_d2h(beta, A.beta, sizeof(double) * (size_t)nb * n, c->stream));
-    PSD_CHECK(psd_rt_d2h(hsc.data(), A.ascale, sizeof(int) * (size_t)nb * n, c->stream));
-    PSD_CHECK(psd_rt_d2h(hinfo.data(), A.infos, sizeof(int) * nb, c->stream));
-    PSD_CHECK(psd_rt_sync(c->stream));
-    PSD_CHECK(psd_rt_last_error());
-    for (size_t e = 0; e < (size_t)nb * n; ++e) ascale[e] = hsc[e];
+    std::vector<psd_zstate> hst;
+    std::vector<int> hinfo;
+    if (int e = zb_launch<zbqz_unsigned>(c, ws, nb, dH, dZ, wantT, wantZ, maxitfac, 0, hst, hinfo, alpha, beta, ascale)) return e;
     for (int q = 0; q < nb; ++q) {
         infos[q] = batch_info_code(hinfo[q]);
         zbatch_add_state(s, hst[q]);
@@ -191,6 +239,114 @@ int zpschur_batch_core(psd_ctx* c, int nb, int n, int p, psd_z* dA, bool left, i
     return 0;
 }
 
+// The entries below are those of the signed family too (psd_zgbatch_host.inl), which passes its signature S; the unsigned
+// entries pass S = null, and an all-true S is the same call (the tuned all-true kernels).
+bool zgb_all_true(const uint8_t* S, int p) {
+    if (S)
+        for (int j = 0; j < p; ++j)
+            if (!S[j]) return false;
+    return true;
+}
+int zgbiterate_dev(psd_ctx* c, int nb, int n, int p, psd_z* dH, psd_z* dZ, const uint8_t* S, int wantT, int wantZ,
+                   int maxitfac, double* alpha, double* beta, int32_t* ascale, int* infos, psd_stats* s);
+int zgpschur_batch_core(psd_ctx* c, int nb, int n, int p, psd_z* dA, const uint8_t* S, bool left, int wantT, int wantZ,
+                        int maxitfac, psd_z* dZ, double* alpha, double* beta, int32_t* ascale, int* infos, psd_stats* s);
+
+// the head of the pschur entries: the argument codes; returns true when the call is over
+bool zb_pschur_head(const batch_call<psd_stats>& k, psd_ctx* c, int nb, int n, int p, const void* A, const uint8_t* S,
+                    char orient, int maxitfac, int wantZ, const void* Z, const double* alpha, const double* beta,
+                    const int32_t* ascale, int* info) {
+    if ((*info = k.head(c, nb, n, p)) != 0) return true;
+    if (!A) *info = -5;
+    else if (orient != 'R' && orient != 'L') *info = -6;  // PSD.jl:175-177
+    else if (S && !S[(orient == 'L') ? p - 1 : 0]) *info = -7;  // generalized.jl:140
+    else if (maxitfac < 1) *info = -9;
+    else if (wantZ && !Z) *info = -10;
+    else if (!alpha || !beta || !ascale) *info = -11;
+    return *info != 0;
+}
+
+// The cores return call-wide codes only and each of them ends the call; the per-problem codes wait in the infos.
+int zb_pschur_batch_dev(psd_ctx* c, int nb, int n, int p, double* dA, const uint8_t* S, char orient, int wantT, int wantZ,
+                        int maxitfac, double* dZ, double* alpha, double* beta, int32_t* ascale, int* infos, int* schurindex,
+                        psd_stats* stats, int* info) {
+    batch_call<psd_stats> k(info, stats);
+    if (zb_pschur_head(k, c, nb, n, p, dA, S, orient, maxitfac, wantZ, dZ, alpha, beta, ascale, info)) return *info;
+    int* pinfos = k.infos(infos, nb);
+    psd_z* A = reinterpret_cast<psd_z*>(dA);
+    psd_z* Z = reinterpret_cast<psd_z*>(dZ);
+    const bool left = orient == 'L';
+    const int rc = zgb_all_true(S, p)
+                       ? zpschur_batch_core(c, nb, n, p, A, left, wantT, wantZ, maxitfac, Z, alpha, beta, ascale, pinfos, k.s)
+                       : zgpschur_batch_core(c, nb, n, p, A, S, left, wantT, wantZ, maxitfac, Z, alpha, beta, ascale, pinfos, k.s);
+    if (schurindex) *schurindex = left ? p : 1;
+    return *info = (rc != 0) ? rc : batch_first_code(pinfos, nb);
+}
+
+int zb_pschur_batch(psd_ctx* c, int nb, int n, int p, double* const* A, const uint8_t* S, char orient, int wantT, int wantZ,
+                    int maxitfac, double* const* Z, double* alpha, double* beta, int32_t* ascale, int* infos, int* schurindex,
+                    psd_stats* stats, int* info) {
+    batch_call<psd_stats> k(info, stats);
+    if (zb_pschur_head(k, c, nb, n, p, A, S, orient, maxitfac, wantZ, Z, alpha, beta, ascale, info)) return *info;
+    const size_t nn2 = 2 * (size_t)n * n;  // doubles of one factor
+    const batch_list L[] = {{A, p, nn2, BATCH_IN | BATCH_OUT}, {wantZ ? Z : nullptr, p, nn2, BATCH_OUT}};
+    int* pinfos = k.infos(infos, nb);
+    const bool left = orient == 'L', plain = zgb_all_true(S, p);
+    auto body = [&](int q0, int gc, double* const* d) {
+        psd_stats gs;
+        psd_z* dA = (psd_z*)d[0];
+        psd_z* dZ = (psd_z*)d[1];
+        double* al = alpha + 2 * (size_t)q0 * n;
+        double* be = beta + (size_t)q0 * n;
+        int32_t* sc = ascale + (size_t)q0 * n;
+        if (int e = plain ? zpschur_batch_core(c, gc, n, p, dA, left, wantT, wantZ, maxitfac, dZ, al, be, sc, pinfos + q0, &gs)
+                          : zgpschur_batch_core(c, gc, n, p, dA, S, left, wantT, wantZ, maxitfac, dZ, al, be, sc, pinfos + q0, &gs))
+            return e;
+        batch_add_stats(k.s, gs, true);
+        return 0;
+    };
+    *info = batch_staged(c, nb, sizeof(double) * ((wantZ ? 2 : 1) * nn2 + 2 * (size_t)n) * p, L, k.s, batch_no_extra, body);
+    if (*info != 0) return *info;
+    if (schurindex) *schurindex = left ? p : 1;
+    return *info = batch_first_code(pinfos, nb);
+}
+
+// noval: the code of missing eigenvalue arrays, which the two entries number differently
+int zb_pschur_hess_batch(psd_ctx* c, int nb, int n, int p, double* const* H, const uint8_t* S, double* const* Q, int wantT,
+                         int wantZ, int maxitfac, double* alpha, double* beta, int32_t* ascale, int* infos, psd_stats* stats,
+                         int* info, int noval) {
+    batch_call<psd_stats> k(info, stats);
+    if ((*info = k.head(c, nb, n, p)) != 0) return *info;
+    if (!H) return *info = -5;
+    if (wantZ && !Q) return *info = -6;
+    if (S && !S[0]) return *info = -7;
+    if (maxitfac < 1) return *info = -9;
+    if (!alpha || !beta || !ascale) return *info = noval;
+    if (c->shard_world > 1) return *info = PSD_INFO_NOTIMPL;
+    const size_t nn2 = 2 * (size_t)n * n;
+    const batch_list L[] = {{H, p, nn2, BATCH_IN | BATCH_OUT}, {wantZ ? Q : nullptr, p, nn2, BATCH_IN | BATCH_OUT}};
+    int* pinfos = k.infos(infos, nb);
+    const bool plain = zgb_all_true(S, p);
+    Timer tk;
+    auto body = [&](int q0, int gc, double* const* d) {
+        psd_z* dH = (psd_z*)d[0];
+        psd_z* dZ = (psd_z*)d[1];
+        double* al = alpha + 2 * (size_t)q0 * n;
+        double* be = beta + (size_t)q0 * n;
+        int32_t* sc = ascale + (size_t)q0 * n;
+        tk.start(c->stream);
+        if (int e = plain ? zbiterate_dev(c, gc, n, p, dH, dZ, wantT, wantZ, maxitfac, al, be, sc, pinfos + q0, k.s)
+                          : zgbiterate_dev(c, gc, n, p, dH, dZ, S, wantT, wantZ, maxitfac, al, be, sc, pinfos + q0, k.s))
+            return e;
+        k.s->ms_iter += tk.stop(c->stream);
+        return 0;
+    };
+    *info = batch_staged(c, nb, sizeof(double) * ((wantZ ? 2 : 1) * nn2 + 2 * (size_t)n) * p, L, k.s, batch_no_extra, body);
+    if (*info != 0) return *info;
+    k.s->ms_total = k.s->ms_iter;
+    return *info = batch_first_code(pinfos, nb);
+}
+
 }  // namespace
 
 extern "C" {
@@ -227,76 +383,21 @@ int psd_z_phessenberg_batch(psd_ctx* c, int nb, int n, int p, double* const* A, 
 int psd_z_pschur_batch_dev(psd_ctx* c, int nb, int n, int p, double* dA, char orient, int wantT, int wantZ, int maxitfac,
                            double* dZ, double* alpha, double* beta, int32_t* ascale, int* infos, int* schurindex,
                            psd_stats* stats, int* info) {
-    batch_call<psd_stats> k(info, stats);
-    if ((*info = k.head(c, nb, n, p)) != 0) return *info;
-    if (!dA) return *info = -5;
-    if (orient != 'R' && orient != 'L') return *info = -6;  // PSD.jl:175-177
-    if (maxitfac < 1) return *info = -9;
-    if (wantZ && !dZ) return *info = -10;
-    if (!alpha || !beta || !ascale) return *info = -11;
-    int* pinfos = k.infos(infos, nb);
-    const int rc = zpschur_batch_core(c, nb, n, p, reinterpret_cast<psd_z*>(dA), orient == 'L', wantT, wantZ, maxitfac,
-                                      reinterpret_cast<psd_z*>(dZ), alpha, beta, ascale, pinfos, k.s);
-    if (schurindex) *schurindex = (orient == 'L') ? p : 1;
-    return *info = (rc != 0) ? rc : batch_first_code(pinfos, nb);
+    return zb_pschur_batch_dev(c, nb, n, p, dA, nullptr, orient, wantT, wantZ, maxitfac, dZ, alpha, beta, ascale, infos,
+                               schurindex, stats, info);
 }
 
 int psd_z_pschur_batch(psd_ctx* c, int nb, int n, int p, double* const* A, char orient, int wantT, int wantZ, int maxitfac,
                        double* const* Z, double* alpha, double* beta, int32_t* ascale, int* infos, int* schurindex,
                        psd_stats* stats, int* info) {
-    batch_call<psd_stats> k(info, stats);
-    if ((*info = k.head(c, nb, n, p)) != 0) return *info;
-    if (!A) return *info = -5;
-    if (orient != 'R' && orient != 'L') return *info = -6;
-    if (maxitfac < 1) return *info = -9;
-    if (wantZ && !Z) return *info = -10;
-    if (!alpha || !beta || !ascale) return *info = -11;
-    const size_t nn2 = 2 * (size_t)n * n;
-    const batch_list L[] = {{A, p, nn2, BATCH_IN | BATCH_OUT}, {wantZ ? Z : nullptr, p, nn2, BATCH_OUT}};
-    int* pinfos = k.infos(infos, nb);
-    auto body = [&](int q0, int gc, double* const* d) {
-        psd_stats gs;
-        // complex rule: the core returns call-wide codes only and each of them ends the group loop; the per-problem
-        // codes wait in pinfos
-        if (int e = zpschur_batch_core(c, gc, n, p, (psd_z*)d[0], orient == 'L', wantT, wantZ, maxitfac, (psd_z*)d[1],
-                                       alpha + 2 * (size_t)q0 * n, beta + (size_t)q0 * n, ascale + (size_t)q0 * n,
-                                       pinfos + q0, &gs))
-            return e;
-        batch_add_stats(k.s, gs, true);
-        return 0;
-    };
-    *info = batch_staged(c, nb, sizeof(double) * ((wantZ ? 2 : 1) * nn2 + 2 * (size_t)n) * p, L, k.s, batch_no_extra, body);
-    if (*info != 0) return *info;
-    if (schurindex) *schurindex = (orient == 'L') ? p : 1;
-    return *info = batch_first_code(pinfos, nb);
+    return zb_pschur_batch(c, nb, n, p, A, nullptr, orient, wantT, wantZ, maxitfac, Z, alpha, beta, ascale, infos, schurindex,
+                           stats, info);
 }
 
 int psd_z_pschur_hess_batch(psd_ctx* c, int nb, int n, int p, double* const* H, double* const* Q, int wantT, int wantZ,
                             int maxitfac, double* alpha, double* beta, int32_t* ascale, int* infos, psd_stats* stats,
                             int* info) {
-    batch_call<psd_stats> k(info, stats);
-    if ((*info = k.head(c, nb, n, p)) != 0) return *info;
-    if (!H) return *info = -5;
-    if (wantZ && !Q) return *info = -6;
-    if (maxitfac < 1) return *info = -9;
-    if (!alpha || !beta || !ascale) return *info = -10;
-    if (c->shard_world > 1) return *info = PSD_INFO_NOTIMPL;
-    const size_t nn2 = 2 * (size_t)n * n;
-    const batch_list L[] = {{H, p, nn2, BATCH_IN | BATCH_OUT}, {wantZ ? Q : nullptr, p, nn2, BATCH_IN | BATCH_OUT}};
-    int* pinfos = k.infos(infos, nb);
-    Timer tk;
-    auto body = [&](int q0, int gc, double* const* d) {
-        tk.start(c->stream);
-        if (int e = zbiterate_dev(c, gc, n, p, (psd_z*)d[0], (psd_z*)d[1], wantT, wantZ, maxitfac, alpha + 2 * (size_t)q0 * n,
-                                  beta + (size_t)q0 * n, ascale + (size_t)q0 * n, pinfos + q0, k.s))
-            return e;
-        k.s->ms_iter += tk.stop(c->stream);
-        return 0;
-    };
-    *info = batch_staged(c, nb, sizeof(double) * ((wantZ ? 2 : 1) * nn2 + 2 * (size_t)n) * p, L, k.s, batch_no_extra, body);
-    if (*info != 0) return *info;
-    k.s->ms_total = k.s->ms_iter;
-    return *info = batch_first_code(pinfos, nb);
+    return zb_pschur_hess_batch(c, nb, n, p, H, nullptr, Q, wantT, wantZ, maxitfac, alpha, beta, ascale, infos, stats, info, -10);
 }
 
 }  // extern "C"

@@ -1,7 +1,8 @@
 // Host driver of psd_z_eigvecs_batch / psd_z_eigvecs_batch_dev (psd_zbevec.h): eigenvectors by back-substitution for nb
 // ComplexF64 periodic Schur decompositions of one shape, as psd_z_pschur_batch leaves them.  Included at the end of
 // psd_engine.cpp behind psd_bevec_host.inl, whose argument checks, call description, statistics and group plumbing it
-// shares (bevec_checked, bevec_call, bevec_launch, bevec_single, bevec_finish; batch_staged).
+// shares (bevec_checked, bevec_call, bevec_launch, bevec_single, bevec_entry_dev, bevec_entry_host).  zbevec_head is the
+// head of the signed entries (psd_zgbevec_host.inl) too.
 //
 // A complex form is triangular in every factor, so nothing is read back before the solve: `select` is used as given and
 // every selected row is one solve column.  Per group of problems: the tables are built on the host and uploaded once; then
@@ -84,11 +85,16 @@ int zbevec_group(const bevec_call& k, int gc, const double* dT, const double* dZ
     return bevec_launch<true>(k, gc, dT, dZ, itab, dtab, units, nsm, dV, cnt3, st);
 }
 
-int zbevec_run(const bevec_call& k, int gc, const double* dT, const double* dZ, const double* alpha, const double* beta,
-               const int32_t* ascale, const uint8_t* select, const int* nvec, double* dV, int32_t* cnt3,
+// the problems [q0, q0 + gc) of a call: their blocks on the device and counters; alpha, beta, ascale, select, nvec: the
+// rows of the whole call
+int zbevec_run(const bevec_call& k, int q0, int gc, const double* dT, const double* dZ, const double* alpha,
+               const double* beta, const int32_t* ascale, const uint8_t* select, const int* nvec, double* dV, int32_t* cnt3,
                psd_bevec_stats* st) {
     st->ngroups += 1;
-    const auto lam = zbevec_values(gc, k.n, alpha, beta, ascale);
+    const size_t r0 = (size_t)q0 * k.n;
+    const auto lam = zbevec_values(gc, k.n, alpha + 2 * r0, beta + r0, ascale ? ascale + r0 : nullptr);
+    select += r0;
+    nvec += q0;
     if (k.n > k.c->bev_nmax) return bevec_single<true>(k, gc, dT, dZ, lam.data(), select, nvec, dV, cnt3, st);
     return zbevec_group(k, gc, dT, dZ, lam.data(), select, dV, cnt3, st);
 }
@@ -105,6 +111,22 @@ int zbevec_count(int nb, int n, const uint8_t* select, int* nvec) {
     return mv;
 }
 
+// What the four complex entries start with: the codes, the counts, the size query (V null).  alpha, beta: the eigenvalue
+// arguments of the unsigned entries (-6).  Returns true when the call is over (*info set).
+bool zbevec_head(psd_ctx* c, int nb, int n, int p, const void* T, const void* Z, const double* alpha, const double* beta,
+                 char orient, int schurindex, const uint8_t* select, const void* V, int maxvec, int* nvec,
+                 psd_bevec_stats* st, int& mv, int* info) {
+    if ((*info = bevec_checked(c, nb, n, p, T, Z, alpha, beta, orient, schurindex, select, nvec, st)) != 0 || nb == 0)
+        return true;
+    mv = zbevec_count(nb, n, select, nvec);
+    if (!V) return true;
+    if (mv > maxvec) {
+        *info = -10;
+        return true;
+    }
+    return false;
+}
+
 }  // namespace
 
 extern "C" {
@@ -115,29 +137,13 @@ int psd_z_eigvecs_batch_dev(psd_ctx* c, int nb, int n, int p, const double* dT, 
                             int* info) {
     batch_call<psd_bevec_stats> entry(info, stats);
     psd_bevec_stats* st = entry.s;
-    if ((*info = bevec_checked(c, nb, n, p, dT, dZ, alpha, beta, orient, schurindex, select, nvec, st)) != 0 || nb == 0)
-        return *info;
-    const size_t nn2 = 2 * (size_t)n * n;
-    const bool left = orient == 'L';
-    const int mv = zbevec_count(nb, n, select, nvec);
-    if (!dV) return *info = 0;
-    if (mv > maxvec) return *info = -10;
-    const int nmat = shifted ? p : 1;
-    std::vector<int32_t> cnt3(3 * (size_t)nb, 0);
-    if (mv > 0) {
-        const bevec_call k{c, n, p, 0, schurindex, shifted, maxvec, left, orient};
-        *info = bevec_dev_groups(c, nb, sizeof(double) * 2 * (size_t)p * n * mv, [&](int q0, int gc) {
-            return zbevec_run(k, gc, dT + (size_t)q0 * p * nn2, dZ + (size_t)q0 * p * nn2, alpha + 2 * (size_t)q0 * n,
-                              beta + (size_t)q0 * n, ascale ? ascale + (size_t)q0 * n : nullptr, select + (size_t)q0 * n,
-                              nvec + q0, dV + 2 * (size_t)q0 * nmat * n * maxvec, cnt3.data() + 3 * (size_t)q0, st);
-        });
-        if (*info != 0) return *info;
-    } else {
-        PSD_CHECK(psd_rt_memset(dV, 0, sizeof(double) * 2 * (size_t)nb * nmat * n * maxvec, c->stream));
-        PSD_CHECK(psd_rt_sync(c->stream));
-    }
-    bevec_finish(nb, nvec, cnt3.data(), pcnt, st);
-    return *info = 0;
+    int mv = 0;
+    if (zbevec_head(c, nb, n, p, dT, dZ, alpha, beta, orient, schurindex, select, dV, maxvec, nvec, st, mv, info)) return *info;
+    const bevec_call k{c, n, p, 0, schurindex, shifted, maxvec, orient == 'L', orient};
+    return *info = bevec_entry_dev(k, nb, 2 * (size_t)n * n, dT, dZ, dV, mv, nvec, pcnt, st,
+                                   [&](int q0, int gc, const double* dTg, const double* dZg, double* dVg, int32_t* cnt3) {
+        return zbevec_run(k, q0, gc, dTg, dZg, alpha, beta, ascale, select, nvec, dVg, cnt3, st);
+    });
 }
 
 int psd_z_eigvecs_batch(psd_ctx* c, int nb, int n, int p, double* const* T, double* const* Z, const double* alpha,
@@ -146,34 +152,13 @@ int psd_z_eigvecs_batch(psd_ctx* c, int nb, int n, int p, double* const* T, doub
                         int* info) {
     batch_call<psd_bevec_stats> entry(info, stats);
     psd_bevec_stats* st = entry.s;
-    if ((*info = bevec_checked(c, nb, n, p, T, Z, alpha, beta, orient, schurindex, select, nvec, st)) != 0 || nb == 0)
-        return *info;
-    const size_t nn2 = 2 * (size_t)n * n;
-    const bool left = orient == 'L';
-    const int mv = zbevec_count(nb, n, select, nvec);
-    if (!V) return *info = 0;
-    if (mv > maxvec) return *info = -10;
-    const int nmat = shifted ? p : 1;
-    const size_t vb = 2 * (size_t)n * maxvec;
-    std::vector<int32_t> cnt3(3 * (size_t)nb, 0);
-    if (mv == 0 || maxvec == 0) {
-        for (size_t e = 0; e < (size_t)nb * nmat; ++e) memset(V[e], 0, sizeof(double) * vb);
-        bevec_finish(nb, nvec, cnt3.data(), pcnt, st);
-        return *info = 0;
-    }
-    const bevec_call k{c, n, p, 0, schurindex, shifted, maxvec, left, orient};
-    // (16 bytes per element of T, Z, V and of the X planes)
-    const batch_list L[] = {{T, p, nn2, BATCH_IN}, {Z, p, nn2, BATCH_IN}, {V, nmat, vb, BATCH_OUT}};
-    auto body = [&](int q0, int gc, double* const* d) {
-        return zbevec_run(k, gc, d[0], d[1], alpha + 2 * (size_t)q0 * n, beta + (size_t)q0 * n,
-                          ascale ? ascale + (size_t)q0 * n : nullptr, select + (size_t)q0 * n, nvec + q0, d[2],
-                          cnt3.data() + 3 * (size_t)q0, st);
-    };
-    const size_t per = sizeof(double) * (2 * nn2 * p + vb * nmat + 2 * (size_t)p * n * mv);
-    *info = batch_staged(c, nb, per, L, nullptr, batch_no_extra, body);
-    if (*info != 0) return *info;
-    bevec_finish(nb, nvec, cnt3.data(), pcnt, st);
-    return *info = 0;
+    int mv = 0;
+    if (zbevec_head(c, nb, n, p, T, Z, alpha, beta, orient, schurindex, select, V, maxvec, nvec, st, mv, info)) return *info;
+    const bevec_call k{c, n, p, 0, schurindex, shifted, maxvec, orient == 'L', orient};
+    return *info = bevec_entry_host(k, nb, 2 * (size_t)n * n, T, Z, V, mv, nvec, pcnt, st,
+                                    [&](int q0, int gc, const double* dTg, const double* dZg, double* dVg, int32_t* cnt3) {
+        return zbevec_run(k, q0, gc, dTg, dZg, alpha, beta, ascale, select, nvec, dVg, cnt3, st);
+    });
 }
 
 }  // extern "C"

@@ -1,7 +1,8 @@
 // Host drivers of the complex SIGNED batched entries psd_z_gphessenberg_batch / psd_z_gpschur_batch /
 // psd_z_gpschur_batch_dev / psd_z_gpschur_hess_batch: nb ComplexF64 periodic problems of one shape (n, p) and one
 // signature S in one call — pschur!(A, S, lr) of generalized.jl:108-148 for each, the path behind gpschur(As, Bs).  Group
-// sizing, staging path and buffers are those of psd_batch_host.inl / psd_zbatch_host.inl.
+// sizing, staging path and buffers are those of psd_batch_host.inl; the workspace, the launch and read-back of the
+// iteration kernel, the fallback loop and the bodies of the pschur entries those of psd_zbatch_host.inl.
 //
 //   reduction    stage 1: psd_zgbhess1, one workgroup per problem, the whole batch in one launch; stage 2: psd_zgbqz with
 //                hessmode = 1, one wavefront per problem (psd_zgbqz.h)
@@ -10,7 +11,7 @@
 //
 // Above the order cap (zgb_nmax) the steps are those of the single call — zsghess_dev, zgrun_iteration —, problem by
 // problem on the slices of the batch buffer.  A batch of one goes through the same kernels as any other.  An all-true
-// (or NULL) signature is the business of psd_zbatch_host.inl: the pschur entries forward to it.
+// (or NULL) signature is the business of psd_zbatch_host.inl: the bodies of the pschur entries take its path.
 
 namespace {
 
@@ -20,13 +21,6 @@ namespace {
 // 65 x in wall time at n = 8 and 18 x at n = 128, the largest swept order (profiles/batch/README.md).  Orders above 128
 // have not been swept.
 int zgb_nmax(const psd_ctx* c) { return c->zb_nmax; }
-
-bool zgb_all_true(const uint8_t* S, int p) {
-    if (S)
-        for (int j = 0; j < p; ++j)
-            if (!S[j]) return false;
-    return true;
-}
 
 // the workspace of psd_zgbqz for nb problems (zb_work, psd_zbatch_host.inl) with the signature S (host, p flags) behind it
 using zgb_work = zb_work<psd_zgbqz_args>;
@@ -38,31 +32,18 @@ int zgb_work_alloc(psd_ctx* c, zgb_work& ws, int nb, int n, int p, int maxlog, c
     return 0;
 }
 
-// one launch of psd_zgbqz over nb problems; the states and per-problem codes (PSD_LIST_OVERFLOW, PSD_ZB_TICKCAP, level)
-// come back in hst / hinfo
-int zgb_launch(psd_ctx* c, zgb_work& ws, int nb, psd_z* dH, psd_z* dZ, int wantT, int wantZ, int maxitfac, int hessmode,
-               std::vector<psd_zgstate>& hst, std::vector<int>& hinfo) {
-    psd_zgbqz_args& A = ws.A;
-    const int n = A.n, p = A.p;
-    const int W = choose_window(p, 16);
-    if (W == 0) return PSD_INFO_NOTIMPL;
-    A.H = dH;
-    A.Z = wantZ ? dZ : nullptr;
-    A.wantT = wantT; A.wantZ = wantZ; A.W = W; A.maxitfac = maxitfac; A.hessmode = hessmode;
-    const int nbmin = (W - 3 > 0) ? ((W - 3 < 8) ? (W - 3) : 8) : 1;  // (the bound of zgiterate_dev's tick loop)
-    A.cap = (long long)maxitfac * n * ((long long)n / nbmin + 8) + 8LL * n + 1024 + (hessmode ? (long long)n * n : 0);
-    size_t lds = step_lds_bytes(p, W, 16);
-    if (psd_zgbqz_apply_lds_bytes() > lds) lds = psd_zgbqz_apply_lds_bytes();
-    PSD_CHECK(c->lds_limit(reinterpret_cast<const void*>(psd_zgbqz), lds));
-    PSD_LAUNCH(psd_zgbqz, psd_dim3(nb), PSD_STEP_NT, lds, c->stream, A);
-    hst.resize(nb);
-    hinfo.resize(nb);
-    PSD_CHECK(psd_rt_d2h(hst.data(), A.st, sizeof(psd_zgstate) * nb, c->stream));
-    PSD_CHECK(psd_rt_d2h(hinfo.data(), A.infos, sizeof(int) * nb, c->stream));
-    PSD_CHECK(psd_rt_sync(c->stream));
-    PSD_CHECK(psd_rt_last_error());
-    return 0;
-}
+// what psd_zgbqz asks of zb_launch
+struct zgbqz_signed {
+    using args_t = psd_zgbqz_args;
+    using state_t = psd_zgstate;
+    static constexpr int capk = 8;  // (the slack of zgiterate_dev's tick loop)
+    static size_t apply_lds(int) { return psd_zgbqz_apply_lds_bytes(); }
+    static void set_hessmode(args_t& A, int hessmode) { A.hessmode = hessmode; }
+    static const void* kernel() { return reinterpret_cast<const void*>(psd_zgbqz); }
+    static void launch(psd_ctx* c, int nb, size_t lds, const args_t& A) {
+        PSD_LAUNCH(psd_zgbqz, psd_dim3(nb), PSD_STEP_NT, lds, c->stream, A);
+    }
+};
 
 // _phessenberg!(A, S; wantQ) (generalized.jl:988-1082) for nb problems on the device: dA / dQ [nb][p][n][n] internal
 // order (dQ may be null), S (host, internal order, S[0] true).  infos (nb, may be null) receives a per-problem code of
@@ -95,7 +76,7 @@ int zgbhess_dev(psd_ctx* c, int nb, int n, int p, psd_z* dA, psd_z* dQ, const ui
     t.start(c->stream);
     std::vector<psd_zgstate> hst;
     std::vector<int> hinfo;
-    if ((rc = zgb_launch(c, ws, nb, dA, dQ, 1, dQ ? 1 : 0, 1, 1, hst, hinfo)) != 0) return rc;
+    if ((rc = zb_launch<zgbqz_signed>(c, ws, nb, dA, dQ, 1, dQ ? 1 : 0, 1, 1, hst, hinfo)) != 0) return rc;
     const double ms2 = t.stop(c->stream);
     s->ms_hess += ms1 + ms2;
     s->ms_formq += ms1;  // (stage 1 accumulates Q as it goes: the convention of zsghess_dev)
@@ -120,31 +101,21 @@ int zgbiterate_dev(psd_ctx* c, int nb, int n, int p, psd_z* dH, psd_z* dZ, const
         int rc = c->zreserve(n, p, false, maxlog);
         if (rc == 0) rc = c->zgreserve(n, p);
         if (rc != 0) return rc;
-        for (int q = 0; q < nb; ++q) {
-            psd_stats ps;
-            memset(&ps, 0, sizeof(ps));
-            rc = zgrun_iteration(c, n, p, dH + (size_t)q * p * nn, wantZ ? dZ + (size_t)q * p * nn : nullptr, S, wantT, wantZ,
-                                 maxitfac, alpha + 2 * (size_t)q * n, beta + (size_t)q * n, ascale + (size_t)q * n, &ps);
-            if (rc == PSD_INFO_RUNTIME + 0xfffc) rc = PSD_INFO_RUNTIME + 0xfffe;  // (the tick bound of the single call)
-            if (batch_fatal(rc) && rc != PSD_INFO_RUNTIME + 77 && rc != PSD_INFO_RUNTIME + 0xfffe) return rc;
-            infos[q] = rc;
-            batch_add_counts(s, ps);  // (not maxits: the single signed call keeps its train sweeps there)
-        }
-        s->window = W;
-        return 0;
+        // (the counts, not maxits: the single signed call keeps its train sweeps there)
+        return zb_single_loop(nb, W, infos, s, {PSD_INFO_RUNTIME + 77, PSD_INFO_RUNTIME + 0xfffe}, [&](int q, psd_stats* ps) {
+            const int e = zgrun_iteration(c, n, p, dH + (size_t)q * p * nn, wantZ ? dZ + (size_t)q * p * nn : nullptr, S, wantT,
+                                          wantZ, maxitfac, alpha + 2 * (size_t)q * n, beta + (size_t)q * n,
+                                          ascale + (size_t)q * n, ps);
+            return e == PSD_INFO_RUNTIME + 0xfffc ? PSD_INFO_RUNTIME + 0xfffe : e;  // (the tick bound of the single call)
+        });
     }
     zgb_work ws;
     int rc = zgb_work_alloc(c, ws, nb, n, p, maxlog, S);
     if (rc != 0) return rc;
     std::vector<psd_zgstate> hst;
     std::vector<int> hinfo;
-    if ((rc = zgb_launch(c, ws, nb, dH, dZ, wantT, wantZ, maxitfac, 0, hst, hinfo)) != 0) return rc;
-    std::vector<int> hsc((size_t)nb * n);
-    PSD_CHECK(psd_rt_d2h(alpha, ws.A.alpha, sizeof(psd_z) * (size_t)nb * n, c->stream));
-    PSD_CHECK(psd_rt_d2h(beta, ws.A.beta, sizeof(double) * (size_t)nb * n, c->stream));
-    PSD_CHECK(psd_rt_d2h(hsc.data(), ws.A.ascale, sizeof(int) * (size_t)nb * n, c->stream));
-    PSD_CHECK(psd_rt_sync(c->stream));
-    for (size_t e = 0; e < (size_t)nb * n; ++e) ascale[e] = hsc[e];
+    rc = zb_launch<zgbqz_signed>(c, ws, nb, dH, dZ, wantT, wantZ, maxitfac, 0, hst, hinfo, alpha, beta, ascale);
+    if (rc != 0) return rc;
     for (int q = 0; q < nb; ++q) {
         infos[q] = batch_info_code(hinfo[q]);
         zbatch_add_state(s, hst[q]);
@@ -215,91 +186,25 @@ int psd_z_gphessenberg_batch(psd_ctx* c, int nb, int n, int p, double* const* A,
     return *info = 0;
 }
 
+// (the bodies, which take the signature: psd_zbatch_host.inl)
 int psd_z_gpschur_batch_dev(psd_ctx* c, int nb, int n, int p, double* dA, const uint8_t* S, char orient, int wantT,
                             int wantZ, int maxitfac, double* dZ, double* alpha, double* beta, int32_t* ascale, int* infos,
                             int* schurindex, psd_stats* stats, int* info) {
-    batch_call<psd_stats> k(info, stats);
-    if ((*info = k.head(c, nb, n, p)) != 0) return *info;
-    if (!dA) return *info = -5;
-    if (orient != 'R' && orient != 'L') return *info = -6;  // PSD.jl:175-177
-    if (S && !S[(orient == 'L') ? p - 1 : 0]) return *info = -7;  // generalized.jl:140
-    if (maxitfac < 1) return *info = -9;
-    if (wantZ && !dZ) return *info = -10;
-    if (!alpha || !beta || !ascale) return *info = -11;
-    if (zgb_all_true(S, p))  // (the tuned all-true path, as psd_z_pschur keeps it)
-        return psd_z_pschur_batch_dev(c, nb, n, p, dA, orient, wantT, wantZ, maxitfac, dZ, alpha, beta, ascale, infos,
-                                      schurindex, stats, info);
-    int* pinfos = k.infos(infos, nb);
-    const int rc = zgpschur_batch_core(c, nb, n, p, reinterpret_cast<psd_z*>(dA), S, orient == 'L', wantT, wantZ, maxitfac,
-                                       reinterpret_cast<psd_z*>(dZ), alpha, beta, ascale, pinfos, k.s);
-    if (schurindex) *schurindex = (orient == 'L') ? p : 1;
-    return *info = (rc != 0) ? rc : batch_first_code(pinfos, nb);
+    return zb_pschur_batch_dev(c, nb, n, p, dA, S, orient, wantT, wantZ, maxitfac, dZ, alpha, beta, ascale, infos, schurindex,
+                               stats, info);
 }
 
 int psd_z_gpschur_batch(psd_ctx* c, int nb, int n, int p, double* const* A, const uint8_t* S, char orient, int wantT,
                         int wantZ, int maxitfac, double* const* Z, double* alpha, double* beta, int32_t* ascale, int* infos,
                         int* schurindex, psd_stats* stats, int* info) {
-    batch_call<psd_stats> k(info, stats);
-    if ((*info = k.head(c, nb, n, p)) != 0) return *info;
-    if (!A) return *info = -5;
-    if (orient != 'R' && orient != 'L') return *info = -6;
-    if (S && !S[(orient == 'L') ? p - 1 : 0]) return *info = -7;
-    if (maxitfac < 1) return *info = -9;
-    if (wantZ && !Z) return *info = -10;
-    if (!alpha || !beta || !ascale) return *info = -11;
-    if (zgb_all_true(S, p))
-        return psd_z_pschur_batch(c, nb, n, p, A, orient, wantT, wantZ, maxitfac, Z, alpha, beta, ascale, infos, schurindex,
-                                  stats, info);
-    const size_t nn2 = 2 * (size_t)n * n;
-    const batch_list L[] = {{A, p, nn2, BATCH_IN | BATCH_OUT}, {wantZ ? Z : nullptr, p, nn2, BATCH_OUT}};
-    int* pinfos = k.infos(infos, nb);
-    auto body = [&](int q0, int gc, double* const* d) {
-        psd_stats gs;
-        // complex rule: the core returns call-wide codes only and each of them ends the group loop; the per-problem
-        // codes wait in pinfos
-        if (int e = zgpschur_batch_core(c, gc, n, p, (psd_z*)d[0], S, orient == 'L', wantT, wantZ, maxitfac, (psd_z*)d[1],
-                                        alpha + 2 * (size_t)q0 * n, beta + (size_t)q0 * n, ascale + (size_t)q0 * n,
-                                        pinfos + q0, &gs))
-            return e;
-        batch_add_stats(k.s, gs, true);
-        return 0;
-    };
-    *info = batch_staged(c, nb, sizeof(double) * ((wantZ ? 2 : 1) * nn2 + 2 * (size_t)n) * p, L, k.s, batch_no_extra, body);
-    if (*info != 0) return *info;
-    if (schurindex) *schurindex = (orient == 'L') ? p : 1;
-    return *info = batch_first_code(pinfos, nb);
+    return zb_pschur_batch(c, nb, n, p, A, S, orient, wantT, wantZ, maxitfac, Z, alpha, beta, ascale, infos, schurindex, stats,
+                           info);
 }
 
 int psd_z_gpschur_hess_batch(psd_ctx* c, int nb, int n, int p, double* const* H, const uint8_t* S, double* const* Q,
                              int wantT, int wantZ, int maxitfac, double* alpha, double* beta, int32_t* ascale, int* infos,
                              psd_stats* stats, int* info) {
-    batch_call<psd_stats> k(info, stats);
-    if ((*info = k.head(c, nb, n, p)) != 0) return *info;
-    if (!H) return *info = -5;
-    if (wantZ && !Q) return *info = -6;
-    if (S && !S[0]) return *info = -7;
-    if (maxitfac < 1) return *info = -9;
-    if (!alpha || !beta || !ascale) return *info = -11;
-    if (zgb_all_true(S, p))
-        return psd_z_pschur_hess_batch(c, nb, n, p, H, Q, wantT, wantZ, maxitfac, alpha, beta, ascale, infos, stats, info);
-    if (c->shard_world > 1) return *info = PSD_INFO_NOTIMPL;
-    const size_t nn2 = 2 * (size_t)n * n;
-    const batch_list L[] = {{H, p, nn2, BATCH_IN | BATCH_OUT}, {wantZ ? Q : nullptr, p, nn2, BATCH_IN | BATCH_OUT}};
-    int* pinfos = k.infos(infos, nb);
-    Timer tk;
-    auto body = [&](int q0, int gc, double* const* d) {
-        tk.start(c->stream);
-        if (int e = zgbiterate_dev(c, gc, n, p, (psd_z*)d[0], (psd_z*)d[1], S, wantT, wantZ, maxitfac,
-                                   alpha + 2 * (size_t)q0 * n, beta + (size_t)q0 * n, ascale + (size_t)q0 * n, pinfos + q0, k.s))
-            return e;
-        k.s->ms_iter += tk.stop(c->stream);
-        return 0;
-    };
-    *info = batch_staged(c, nb, sizeof(double) * ((wantZ ? 2 : 1) * nn2 + 2 * (size_t)n) * p, L, k.s, batch_no_extra, body);
-    if (*info != 0) return *info;
-    k.s->ms_total = k.s->ms_iter;
-    return *info = batch_first_code(pinfos, nb);
+    return zb_pschur_hess_batch(c, nb, n, p, H, S, Q, wantT, wantZ, maxitfac, alpha, beta, ascale, infos, stats, info, -11);
 }
 
 }  // extern "C"
-

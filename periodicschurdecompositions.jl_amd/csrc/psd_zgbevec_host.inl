@@ -2,8 +2,7 @@
 // back-substitution, zero and infinite eigenvalues included — for nb signed ComplexF64 periodic Schur decompositions of
 // one shape and one signature, as psd_z_gpschur_batch / psd_z_gordschur_batch leave them.  Included at the end of
 // psd_engine.cpp behind psd_zbevec_host.inl, whose pieces it shares: bevec_checked, bevec_call, bevec_launch (with the
-// senses of the working factors), bevec_single_loop, bevec_dev_groups, bevec_finish, zbevec_tables, zbevec_count;
-// batch_staged.
+// senses of the working factors), bevec_single_loop, bevec_entry_dev, bevec_entry_host, zbevec_head, zbevec_tables.
 //
 // Nothing is read back before the solve: `select` is used as given, every selected row is one solve column, and the
 // kernel takes the scalars a_l from the diagonals of the factors.  Launches of a call up to the context's bev_nmax
@@ -73,19 +72,24 @@ void zgbevec_scalars(int nb, int n, int p, int maxvec, const uint8_t* select, Di
     }
 }
 
-// what both entries start with: the codes, the counts, the size query.  Returns true when the call is over (*info set)
-bool zgbevec_head(psd_ctx* c, int nb, int n, int p, const void* T, const void* Z, char orient, int schurindex,
-                  const uint8_t* select, const void* V, int maxvec, int* nvec, psd_bevec_stats* st, int& mv, int* info) {
-    const double none = 0.0;  // (there are no eigenvalue arguments: -6 is not used)
-    if ((*info = bevec_checked(c, nb, n, p, T, Z, &none, &none, orient, schurindex, select, nvec, st)) != 0 || nb == 0)
-        return true;
-    mv = zbevec_count(nb, n, select, nvec);
-    if (!V) return true;
-    if (mv > maxvec) {
-        *info = -10;
-        return true;
+// the same from the factors on the device: one gather (psd_zgbev_diag) and one read-back for the whole batch; no launch
+// when nothing is selected (mv == 0)
+int zgbevec_scalars_dev(psd_ctx* c, int nb, int n, int p, const double* dT, int maxvec, int mv, const uint8_t* select,
+                        double* a, psd_bevec_stats* st) {
+    const size_t tot = (size_t)nb * p * n;
+    std::vector<double> diag(mv > 0 ? 2 * tot : 0);
+    if (mv > 0) {
+        psd_batchbuf bdiag;
+        PSD_CHECK(bdiag.alloc(sizeof(double) * 2 * tot));
+        PSD_LAUNCH(psd_zgbev_diag, psd_dim3((int)((tot + PSD_BEV_NT - 1) / PSD_BEV_NT)), PSD_BEV_NT, 0, c->stream, dT, n,
+                   (size_t)nb * p, bdiag.d());
+        st->nlaunch += 1;
+        PSD_CHECK(psd_rt_d2h(diag.data(), bdiag.d(), sizeof(double) * 2 * tot, c->stream));
+        PSD_CHECK(psd_rt_sync(c->stream));
     }
-    return false;
+    zgbevec_scalars(nb, n, p, maxvec, select, [&](int q, int l, int i) { return diag.data() + 2 * (((size_t)q * p + l) * n + i); },
+                    a);
+    return 0;
 }
 
 }  // namespace
@@ -97,39 +101,16 @@ int psd_z_geigvecs_batch_dev(psd_ctx* c, int nb, int n, int p, const double* dT,
                              double* a, int* nvec, int32_t* pcnt, psd_bevec_stats* stats, int* info) {
     batch_call<psd_bevec_stats> entry(info, stats);
     psd_bevec_stats* st = entry.s;
+    const double none = 0.0;  // (there are no eigenvalue arguments: -6 is not used)
     int mv = 0;
-    if (zgbevec_head(c, nb, n, p, dT, dZ, orient, schurindex, select, dV, maxvec, nvec, st, mv, info)) return *info;
-    const size_t nn2 = 2 * (size_t)n * n;
+    if (zbevec_head(c, nb, n, p, dT, dZ, &none, &none, orient, schurindex, select, dV, maxvec, nvec, st, mv, info)) return *info;
+    if (a && (*info = zgbevec_scalars_dev(c, nb, n, p, dT, maxvec, mv, select, a, st)) != 0) return *info;
     const bool left = orient == 'L';
-    const int nmat = shifted ? p : 1;
-    std::vector<int32_t> cnt3(3 * (size_t)nb, 0);
-    if (mv > 0) {
-        if (a) {  // one gather and one read-back for the scalars of the whole batch
-            const size_t tot = (size_t)nb * p * n;
-            psd_batchbuf bdiag;
-            std::vector<double> diag(2 * tot);
-            PSD_CHECK(bdiag.alloc(sizeof(double) * 2 * tot));
-            PSD_LAUNCH(psd_zgbev_diag, psd_dim3((int)((tot + PSD_BEV_NT - 1) / PSD_BEV_NT)), PSD_BEV_NT, 0, c->stream, dT,
-                       n, (size_t)nb * p, bdiag.d());
-            st->nlaunch += 1;
-            PSD_CHECK(psd_rt_d2h(diag.data(), bdiag.d(), sizeof(double) * 2 * tot, c->stream));
-            PSD_CHECK(psd_rt_sync(c->stream));
-            zgbevec_scalars(nb, n, p, maxvec, select,
-                            [&](int q, int l, int i) { return diag.data() + 2 * (((size_t)q * p + l) * n + i); }, a);
-        }
-        const zgbevec_call g{{c, n, p, 0, schurindex, shifted, maxvec, left, orient}, S, zgbevec_sgn(p, S, left)};
-        *info = bevec_dev_groups(c, nb, sizeof(double) * 2 * (size_t)p * n * mv, [&](int q0, int gc) {
-            return zgbevec_run(g, gc, dT + (size_t)q0 * p * nn2, dZ + (size_t)q0 * p * nn2, nullptr, select + (size_t)q0 * n,
-                               nvec + q0, dV + 2 * (size_t)q0 * nmat * n * maxvec, cnt3.data() + 3 * (size_t)q0, st);
-        });
-        if (*info != 0) return *info;
-    } else {
-        if (a) memset(a, 0, sizeof(double) * 2 * (size_t)nb * maxvec * p);
-        PSD_CHECK(psd_rt_memset(dV, 0, sizeof(double) * 2 * (size_t)nb * nmat * n * maxvec, c->stream));
-        PSD_CHECK(psd_rt_sync(c->stream));
-    }
-    bevec_finish(nb, nvec, cnt3.data(), pcnt, st);
-    return *info = 0;
+    const zgbevec_call g{{c, n, p, 0, schurindex, shifted, maxvec, left, orient}, S, zgbevec_sgn(p, S, left)};
+    return *info = bevec_entry_dev(g.k, nb, 2 * (size_t)n * n, dT, dZ, dV, mv, nvec, pcnt, st,
+                                   [&](int q0, int gc, const double* dTg, const double* dZg, double* dVg, int32_t* cnt3) {
+        return zgbevec_run(g, gc, dTg, dZg, nullptr, select + (size_t)q0 * n, nvec + q0, dVg, cnt3, st);
+    });
 }
 
 int psd_z_geigvecs_batch(psd_ctx* c, int nb, int n, int p, double* const* T, double* const* Z, const uint8_t* S,
@@ -137,33 +118,18 @@ int psd_z_geigvecs_batch(psd_ctx* c, int nb, int n, int p, double* const* T, dou
                          double* a, int* nvec, int32_t* pcnt, psd_bevec_stats* stats, int* info) {
     batch_call<psd_bevec_stats> entry(info, stats);
     psd_bevec_stats* st = entry.s;
+    const double none = 0.0;
     int mv = 0;
-    if (zgbevec_head(c, nb, n, p, T, Z, orient, schurindex, select, V, maxvec, nvec, st, mv, info)) return *info;
-    const size_t nn2 = 2 * (size_t)n * n;
-    const bool left = orient == 'L';
-    const int nmat = shifted ? p : 1;
-    const size_t vb = 2 * (size_t)n * maxvec;
-    std::vector<int32_t> cnt3(3 * (size_t)nb, 0);
+    if (zbevec_head(c, nb, n, p, T, Z, &none, &none, orient, schurindex, select, V, maxvec, nvec, st, mv, info)) return *info;
     if (a)  // (the factors are on the host: no kernel)
         zgbevec_scalars(nb, n, p, maxvec, select,
                         [&](int q, int l, int i) { return T[(size_t)q * p + l] + 2 * ((size_t)i * n + i); }, a);
-    if (mv == 0 || maxvec == 0) {
-        for (size_t e = 0; e < (size_t)nb * nmat; ++e) memset(V[e], 0, sizeof(double) * vb);
-        bevec_finish(nb, nvec, cnt3.data(), pcnt, st);
-        return *info = 0;
-    }
+    const bool left = orient == 'L';
     const zgbevec_call g{{c, n, p, 0, schurindex, shifted, maxvec, left, orient}, S, zgbevec_sgn(p, S, left)};
-    // (16 bytes per element of T, Z, V and of the X planes)
-    const batch_list L[] = {{T, p, nn2, BATCH_IN}, {Z, p, nn2, BATCH_IN}, {V, nmat, vb, BATCH_OUT}};
-    auto body = [&](int q0, int gc, double* const* d) {
-        return zgbevec_run(g, gc, d[0], d[1], T + (size_t)q0 * p, select + (size_t)q0 * n, nvec + q0, d[2],
-                           cnt3.data() + 3 * (size_t)q0, st);
-    };
-    const size_t per = sizeof(double) * (2 * nn2 * p + vb * nmat + 2 * (size_t)p * n * mv);
-    *info = batch_staged(c, nb, per, L, nullptr, batch_no_extra, body);
-    if (*info != 0) return *info;
-    bevec_finish(nb, nvec, cnt3.data(), pcnt, st);
-    return *info = 0;
+    return *info = bevec_entry_host(g.k, nb, 2 * (size_t)n * n, T, Z, V, mv, nvec, pcnt, st,
+                                    [&](int q0, int gc, const double* dTg, const double* dZg, double* dVg, int32_t* cnt3) {
+        return zgbevec_run(g, gc, dTg, dZg, T + (size_t)q0 * p, select + (size_t)q0 * n, nvec + q0, dVg, cnt3, st);
+    });
 }
 
 }  // extern "C"
