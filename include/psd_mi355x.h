@@ -246,6 +246,37 @@ int psd_z_gpschur_hess_batch(psd_ctx* ctx, int nb, int n, int p, double* const* 
                              int wantT, int wantZ, int maxitfac, double* alpha, double* beta, int32_t* ascale, int* infos,
                              psd_stats* stats, int* info);
 
+/* ---- the same batch entries for Float64 with a signature -----------------------------------------------------------
+ * pschur!(A, S, lr) of rgeneralized.jl:3-45 (the MB03BD-type real periodic QZ) — pencils A - lambda B and generalized
+ * periodic products B_p^-1 A_p ... B_1^-1 A_1 with real data — for nb problems of one shape (n, p) and ONE signature S
+ * per call, without the detour through ComplexF64: the factor at schurindex comes out real quasi-triangular (a 2 x 2
+ * block per conjugate pair, a zero sub-diagonal wherever the eigenvalue is real), the others upper triangular, the Z_l
+ * real orthogonal, and the alpha of a 2 x 2 block are exact conjugates.  Argument layout (n * n doubles per matrix),
+ * info codes (-1 ... -11, as listed above), per-problem infos, return value and stats conventions are those of the four
+ * psd_z_g*_batch entries; alpha is nb * n complex pairs, beta and ascale nb * n, eigenvalue = alpha / beta * 2^ascale.
+ * stats: reserved = ncase2 + 1000 * ncase3, ndefl2 counts 2 x 2 blocks (of both kinds), nrqpass zero-shift passes, each
+ * summed over the problems.  One difference from the complex entries: a NULL or all-true S runs the SAME signed real
+ * kernels (as psd_d_gpschur does, and pschur!(A, S, lr) for real element types); it is not sent to psd_d_pschur_batch,
+ * whose outputs (wr, wi) have another form.  Stage 1 of the reduction runs one workgroup per problem, stage 2 and the
+ * iteration ONE WAVEFRONT PER PROBLEM (single-wave sweep, no trains), one launch each per group; nothing is shared
+ * between problems, so a result does not depend on its place in the batch.  Orders above 128 run psd_d_gpschur's
+ * reduction and iteration problem by problem on the batch buffer.  A period-sharded context: PSD_INFO_NOTIMPL. */
+int psd_d_gphessenberg_batch(psd_ctx* ctx, int nb, int n, int p, double* const* A, const uint8_t* S, double* const* Q,
+                             psd_stats* stats, int* info);
+int psd_d_gpschur_batch(psd_ctx* ctx, int nb, int n, int p, double* const* A, const uint8_t* S, char orient, int wantT,
+                        int wantZ, int maxitfac, double* const* Z, double* alpha, double* beta, int32_t* ascale, int* infos,
+                        int* schurindex, psd_stats* stats, int* info);
+/* Device-resident variant: dA, dZ device [nb][p][n][n] column-major real blocks in user order (dZ may be NULL when
+ * !wantZ), overwritten; S, alpha / beta / ascale / infos are host buffers. */
+int psd_d_gpschur_batch_dev(psd_ctx* ctx, int nb, int n, int p, double* dA, const uint8_t* S, char orient, int wantT,
+                            int wantZ, int maxitfac, double* dZ, double* alpha, double* beta, int32_t* ascale, int* infos,
+                            int* schurindex, psd_stats* stats, int* info);
+/* nb Hessenberg-triangular Float64 problems with the signature S (internal order, NULL: all true): pschur!(H1, Hs, S;
+ * wantT, wantZ, Q, maxitfac) for each, as psd_d_gpschur_hess; H / Q as psd_d_pschur_hess_batch. */
+int psd_d_gpschur_hess_batch(psd_ctx* ctx, int nb, int n, int p, double* const* H, const uint8_t* S, double* const* Q,
+                             int wantT, int wantZ, int maxitfac, double* alpha, double* beta, int32_t* ascale, int* infos,
+                             psd_stats* stats, int* info);
+
 /* Device-resident variant of psd_d_pschur: dA, dZ are device pointers to [p][n][n] blocks in user
  * order (dZ may be NULL when !wantZ).  wr/wi/sweeplog are host buffers. */
 int psd_d_pschur_dev(psd_ctx* ctx, int n, int p, double* dA, char orient, int wantT, int wantZ, int maxitfac,

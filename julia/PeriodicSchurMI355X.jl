@@ -265,14 +265,65 @@ end
 pschur_batch(problems::AbstractVector, S::AbstractVector{Bool}, lr::Symbol = :R; kwargs...) =
     pschur_batch!([Matrix{ComplexF64}[Matrix{ComplexF64}(a) for a in A] for A in problems], S, lr; kwargs...)
 
-# gpschur_batch(Aslist, Bslist) — gpschur(As, Bs) (generalized.jl:1191-1211) for many pairs of series of equal shape in ONE
-# call: the interleaving of gpschur per problem, then pschur_batch! with the common alternating signature
-function gpschur_batch(Aslist::AbstractVector, Bslist::AbstractVector; kwargs...)
+# pschur_batch!(problems::Vector{Vector{Matrix{Float64}}}, S, lr; wantZ, wantT, maxitfac, infos) — pschur!(A, S, lr) for
+# Float64 (rgeneralized.jl:3-45) for many small real problems of equal order and period and ONE signature S in ONE call
+# (psd_d_gpschur_batch): real quasi-triangular T at schurindex, orthogonal Z, conjugate pairs exact conjugates.  Works in
+# place; returns a Vector{GeneralizedPeriodicSchur}.  An all-true S runs the same signed kernels (as pschur!(A, S, lr) does
+# for real element types).  maxitfac defaults to the reference's 120 for Float64.  Failures and `infos` as the ComplexF64
+# method.  (Written by analogy with that method; not run yet.)
+function pschur_batch!(problems::Vector{Vector{Matrix{Float64}}}, S::AbstractVector{Bool}, lr::Symbol = :R;
+                       wantZ::Bool = true, wantT::Bool = true, maxitfac = 120,
+                       infos::Union{Nothing, Vector{Cint}} = nothing)
+    orient = PSD.char_lr(lr)
+    nb = length(problems)
+    nb == 0 && return GeneralizedPeriodicSchur[]
+    p = length(problems[1]); n = _check(problems[1])
+    for A in problems
+        (length(A) == p && _check(A) == n) || throw(DimensionMismatch("the problems of a batch must have equal order and period"))
+    end
+    length(S) == p || throw(DimensionMismatch("one sign per factor"))
+    (orient == 'L' ? S[p] : S[1]) || throw(ArgumentError("The leftmost entry in S must be true"))  # rgeneralized.jl:37
+    flat = reduce(vcat, problems)
+    Z = wantZ ? [Matrix{Float64}(undef, n, n) for _ in 1:(nb * p)] : Matrix{Float64}[]
+    α = zeros(ComplexF64, n, nb); β = zeros(Float64, n, nb); sc = zeros(Int32, n, nb)
+    codes = infos === nothing ? Vector{Cint}(undef, nb) : infos
+    length(codes) == nb || throw(DimensionMismatch("infos must have one entry per problem"))
+    si = Ref{Cint}(0); info = Ref{Cint}(0)
+    Ap = _ptrs(flat); Zp = _ptrs(Z); Sb = UInt8.(S)
+    GC.@preserve flat Z α β sc codes Sb begin
+        ccall((:psd_d_gpschur_batch, libpsd), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Ptr{Float64}}, Ptr{UInt8}, Cchar, Cint, Cint, Cint,
+               Ptr{Ptr{Float64}}, Ptr{ComplexF64}, Ptr{Float64}, Ptr{Int32}, Ptr{Cint}, Ref{Cint}, Ptr{Cvoid}, Ref{Cint}),
+              ctx().ptr, nb, n, p, Ap, Sb, orient, wantT, wantZ, maxitfac,
+              wantZ ? Zp : C_NULL, α, β, sc, codes, si, C_NULL, info)
+    end
+    (info[] < 0 || (info[] >= INFO_NOTIMPL && !(info[] in codes))) && _throw(info[])
+    js = Int(si[])
+    out = map(1:nb) do q
+        A = problems[q]
+        T1 = A[js]; Tv = [A[j] for j in 1:p if j != js]
+        Zq = wantZ ? Z[((q - 1) * p + 1):(q * p)] : [similar(T1, 0, 0)]
+        GeneralizedPeriodicSchur(collect(Bool, S), js, T1, Tv, Zq, α[:, q], β[:, q], Int.(sc[:, q]), orient)  # (β::Vector{Ty}, Ty real here: generalized.jl:44-58)
+    end
+    infos === nothing && foreach(_throw, codes)
+    out
+end
+
+# gpschur_batch(Aslist, Bslist; real = false) — gpschur(As, Bs) (generalized.jl:1191-1211) for many pairs of series of equal
+# shape in ONE call: the interleaving of gpschur per problem, then pschur_batch! with the common alternating signature.
+# real = true: every matrix must be real, and the interleaving goes to the Float64 method as it is instead of being cast
+# to ComplexF64 (a complex matrix is an ArgumentError then).
+function gpschur_batch(Aslist::AbstractVector, Bslist::AbstractVector; real::Bool = false, kwargs...)
     length(Aslist) == length(Bslist) || throw(DimensionMismatch("one Bs per As"))
     isempty(Aslist) && return GeneralizedPeriodicSchur[]
     args = [PSD._mkpsargs(collect(As), Bs) for (As, Bs) in zip(Aslist, Bslist)]
     Ss = args[1][2]
     all(a -> a[2] == Ss, args) || throw(DimensionMismatch("the problems of a batch must have equal order and period"))
+    if real
+        all(a -> all(c -> eltype(c) <: Real, a[1]), args) ||
+            throw(ArgumentError("gpschur_batch(real = true): the matrices must be real"))
+        return pschur_batch!([Matrix{Float64}[Matrix{Float64}(c) for c in a[1]] for a in args], collect(Bool, Ss); kwargs...)
+    end
     pschur_batch!([Matrix{ComplexF64}[Matrix{ComplexF64}(c) for c in a[1]] for a in args], collect(Bool, Ss); kwargs...)
 end
 

@@ -271,6 +271,9 @@ def _check_square(A):
 _Family = collections.namedtuple("_Family", "tag dtype wrong_exc wrong_text")
 _D = _Family("d", np.float64, NotImplementedPSD, "pschur_batch: Float64 only (ComplexF64 problems: zpschur_batch)")
 _Z = _Family("z", np.complex128, TypeError, "zpschur_batch: ComplexF64 only (use pschur_batch for Float64 problems)")
+# the Float64 SIGNED entries (psd_d_gp*_batch): the ABI prefix and dtype of _D, the scaled eigenvalues, the
+# GeneralizedPeriodicSchur results and the per-problem codes of the ComplexF64 entries
+_DG = _Family("d", np.float64, TypeError, "dgpschur_batch: Float64 only (ComplexF64 problems: zgpschur_batch)")
 
 
 _ORD_WRONG = {_D: "ordschur_batch: Float64 only (use ordschur_ per problem for ComplexF64)",
@@ -282,7 +285,7 @@ def _other_family(fam, cplx, every=False):
     """Whether matrices (`cplx`: which of them are complex) belong to the other family: a complex one among Float64;
     among ComplexF64 none complex, or with `every` not all (one complex matrix makes a problem complex: the in-place
     contract turns the real ones away afterwards)."""
-    return any(cplx) if fam is _D else not (all(cplx) if every else any(cplx))
+    return any(cplx) if fam.dtype is np.float64 else not (all(cplx) if every else any(cplx))
 
 
 def _eig_alloc(fam, shape, nan=False):
@@ -372,18 +375,19 @@ class Engine:
         lib.psd_d_checkpsd_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, u8p,
                                            C.c_char, C.c_int, C.c_double, C.c_int, dp, dp, dp, ip, ip]
         # the batch entries: one description per entry family, crossed with d / z (the eigenvalue arguments), plain /
-        # signed (the signature after the factors) and host / dev (how the matrices are passed)
+        # signed (the signature after the factors) and host / dev (how the matrices are passed).  The signed pschur
+        # entries of both types return scaled eigenvalues (alpha, beta, alphascale).
         sp, head = C.POINTER(Stats), [C.c_void_p, C.c_int, C.c_int, C.c_int]  # (head: ctx, nb, n, p)
         for t, eig in (("d", [dp, dp]), ("z", [dp, dp, i32p])):
             sigs = {f"psd_{t}_phessenberg_batch": head + [dpp, dp, sp, ip],
                     f"psd_{t}_gphessenberg_batch": head + [dpp, u8p, dpp, sp, ip]}
-            for g, sig in (("", []), ("g", [u8p])):
-                sigs[f"psd_{t}_{g}pschur_hess_batch"] = (head + [dpp] + sig + [dpp, C.c_int, C.c_int, C.c_int] + eig
+            for g, sig, ge in (("", [], eig), ("g", [u8p], [dp, dp, i32p])):
+                sigs[f"psd_{t}_{g}pschur_hess_batch"] = (head + [dpp] + sig + [dpp, C.c_int, C.c_int, C.c_int] + ge
                                                          + [ip, sp, ip])
             for dev, mats in (("", dpp), ("_dev", C.c_void_p)):
-                for g, sig in (("", []), ("g", [u8p])):
+                for g, sig, ge in (("", [], eig), ("g", [u8p], [dp, dp, i32p])):
                     sigs[f"psd_{t}_{g}pschur_batch{dev}"] = (head + [mats] + sig + [C.c_char, C.c_int, C.c_int, C.c_int,
-                                                                                     mats] + eig + [ip, ip, sp, ip])
+                                                                                     mats] + ge + [ip, ip, sp, ip])
                 for g, sig in (("", []), ("g", [u8p])):
                     sigs[f"psd_{t}_{g}ordschur_batch{dev}"] = (head + [mats, mats] + sig + [C.c_char, C.c_int, u8p, C.c_int]
                                                                + eig + [ip, ip, sp, ip])
@@ -991,7 +995,8 @@ class Engine:
                                   lambda: result(eig, si.value, st))
 
     def _pschur_batch_(self, fam, name, problems, S, lr, wantZ, wantT, maxitfac, infos_out):
-        """pschur_batch_ / zpschur_batch_ / zgpschur_batch_ (`S` None: all true, the entry without a signature)."""
+        """pschur_batch_ / zpschur_batch_ / zgpschur_batch_ / dgpschur_batch_ (`S` None: all true, the entry without a
+        signature)."""
         orient = char_lr(lr)
         if hasattr(problems, "data_ptr"):
             return self._pschur_batch_dev(fam, name, problems, S, orient, wantZ, wantT, maxitfac, infos_out)
@@ -1002,6 +1007,8 @@ class Engine:
             return []
         n, p, A = self._batch_factors(fam, problems)
         Sarr = None
+        if S is None and fam is _DG:  # (the real signed entries take every signature, the all-true one included)
+            S = [True] * p
         if S is not None:
             S, Sarr = self._zgbatch_sig(S, p, orient)
         self._as_work(A, fam.dtype)
@@ -1013,9 +1020,11 @@ class Engine:
     def _pschur_batch_dev(self, fam, name, dA, S, orient, wantZ, wantT, maxitfac, infos_out):
         import torch
 
-        wrong = fam.wrong_exc(fam.wrong_text if S is None else "zgpschur_batch: ComplexF64 only")
+        wrong = fam.wrong_exc(fam.wrong_text if S is None or fam is _DG else "zgpschur_batch: ComplexF64 only")
         nb, p, n = self._dev_batch(fam, name, wrong, dA)
         Sarr = None
+        if S is None and fam is _DG:
+            S = [True] * p
         if S is not None:
             S, Sarr = self._zgbatch_sig(S, p, orient)
         if nb == 0:
@@ -1029,8 +1038,9 @@ class Engine:
             fam, Sarr, True, nb, n, p, dT, dZ, orient, wantT, wantZ, maxitfac, infos_out,
             lambda eig, si, st: (dT.transpose(2, 3), (dZ.transpose(2, 3) if wantZ else None), _eig_values(eig), st))
 
-    def _pschur_hess_batch_(self, fam, problems, S, wrong, wantT, wantZ, maxitfac, infos_out):
-        """The three *_hess_batch_ entries on a non-empty batch (`S` None: no signature argument)."""
+    def _pschur_hess_batch_(self, fam, problems, S, wrong, wantT, wantZ, maxitfac, infos_out, general):
+        """The *_hess_batch_ entries on a non-empty batch (`S` None: no signature argument).  `general`: whether the
+        results are GeneralizedPeriodicSchur (the Float64 all-true entry returns PeriodicSchur)."""
         nb = len(problems)
         n, p, Hall, Qall = self._batch_hess(fam, problems, wantZ, wrong)
         sig = [] if S is None else [(C.c_uint8 * p)(*[1 if x else 0 for x in S])]
@@ -1040,7 +1050,7 @@ class Engine:
         fn(self.ctx, nb, n, p, self._ptrs(Hall), *sig, self._ptrs(Qall) if wantZ else None, int(wantT), int(wantZ),
            int(maxitfac), *self._evec_ptrs(eig), infos, C.byref(st), C.byref(info))
         return self._batch_finish(info.value, infos, infos_out, self._raise, fam is _D,
-                                  lambda: self._batch_results(fam is _Z, S, nb, p, Hall, Qall, eig, "R", 1, st))
+                                  lambda: self._batch_results(general, S, nb, p, Hall, Qall, eig, "R", 1, st))
 
     def pschur_hess_batch_(self, problems, wantT=True, wantZ=True, maxitfac=30, infos_out=None):
         """pschur!(H1, Hs; wantT, wantZ, Q, maxitfac) (src/PeriodicSchurDecompositions.jl:322-330) for a list of
@@ -1052,7 +1062,7 @@ class Engine:
         leaves it as it is)."""
         if len(problems) == 0:
             return []
-        return self._pschur_hess_batch_(_D, problems, None, None, wantT, wantZ, maxitfac, infos_out)
+        return self._pschur_hess_batch_(_D, problems, None, None, wantT, wantZ, maxitfac, infos_out, False)
 
     def phessenberg_batch_(self, problems):
         """phessenberg!(A) (src/PeriodicSchurDecompositions.jl:213-259) for a list of problems of equal shape in ONE call
@@ -1120,7 +1130,7 @@ class Engine:
                 infos_out[:] = []
             return []
         wrong = TypeError("zpschur_hess_batch_: ComplexF64 only (use pschur_hess_batch_ for Float64 problems)")
-        return self._pschur_hess_batch_(_Z, problems, None, wrong, wantT, wantZ, maxitfac, infos_out)
+        return self._pschur_hess_batch_(_Z, problems, None, wrong, wantT, wantZ, maxitfac, infos_out, True)
 
     # ---- ComplexF64 batch family with a signed signature (psd_z_gp*_batch): gpschur(As, Bs) for many small problems
     def _zgbatch_sig(self, S, p, orient):
@@ -1184,15 +1194,81 @@ class Engine:
         if not S[0]:
             raise ValueError("Signature entry S[1] must be true")  # src/generalized.jl:182
         wrong = TypeError("zgpschur_hess_batch_: ComplexF64 only")
-        return self._pschur_hess_batch_(_Z, problems, S, wrong, wantT, wantZ, maxitfac, infos_out)
+        return self._pschur_hess_batch_(_Z, problems, S, wrong, wantT, wantZ, maxitfac, infos_out, True)
 
-    def gpschur_batch(self, As_list, Bs_list, **kw):
+    # ---- Float64 batch family with a signature (psd_d_gp*_batch): pencils and generalized periodic products with real
+    # data; real quasi-triangular T_1, orthogonal Z, conjugate pairs as exact conjugates
+    def dgphessenberg_batch_(self, problems, S, wantQ=True):
+        """_phessenberg!(A, S; wantQ) for Float64 (src/generalized.jl:988-1082) for a list of problems of equal shape and
+        ONE signature in ONE call (psd_d_gphessenberg_batch): stage 1 one workgroup per problem, stage 2 one wavefront
+        per problem.  `problems`: list of lists of p writable Fortran-ordered float64 matrices, overwritten with the
+        Hessenberg / triangular factors.  `S` None: all true.  Returns a list of (H list, Q list) like gphessenberg_,
+        and the Stats of the call."""
+        nb = len(problems)
+        if nb == 0:
+            return [], Stats()
+        n, p, flat = self._batch_factors(_DG, problems)
+        self._as_work(flat, np.float64)
+        S, Sarr = self._zgbatch_sig([True] * p if S is None else S, p, "R")
+        Qall = [np.zeros((n, n), order="F") for _ in range(nb * p)] if wantQ else []
+        st = Stats()
+        info = C.c_int(0)
+        self.lib.psd_d_gphessenberg_batch(self.ctx, nb, n, p, self._ptrs(flat), Sarr, self._ptrs(Qall) if wantQ else None,
+                                          C.byref(st), C.byref(info))
+        self._raise(info.value)
+        return [(flat[q * p:(q + 1) * p], Qall[q * p:(q + 1) * p] if wantQ else []) for q in range(nb)], st
+
+    def dgpschur_batch_(self, problems, S, lr="R", wantZ=True, wantT=True, maxitfac=120, infos_out=None):
+        """pschur!(A::Vector{Matrix{Float64}}, S, lr; wantZ, wantT, maxitfac) (src/rgeneralized.jl:3-45) for many small
+        problems of equal shape and ONE signature `S` in ONE call (psd_d_gpschur_batch): the signed Hessenberg
+        reduction and the real signed periodic QZ iteration (after MB03BD), one workgroup / one wavefront per problem.
+        The default `maxitfac` is that of pschur_(..., S=...) for Float64.
+
+        `problems`: a list of lists of p writable Fortran-ordered float64 n x n matrices, overwritten with the T
+        factors; returns a list of GeneralizedPeriodicSchur with real Ts (the one at schurindex quasi-triangular) and
+        real orthogonal Z; the `values` of a 2 x 2 block are exact conjugates.  Or one torch float64 [nb, p, n, n]
+        device tensor (device-resident entry, psd_d_gpschur_batch_dev; the input is not modified): returns
+        (T, Z, values, stats).  `S` None or all true: the same signed kernels (as pschur_(..., S=...) — not the path of
+        pschur_batch_, whose results have another form).  A problem that fails to converge raises like the single
+        call, after all have run — the others are complete then.  `infos_out`: a list that receives the per-problem
+        info codes instead."""
+        return self._pschur_batch_(_DG, "dgpschur_batch", problems, S, lr, wantZ, wantT, maxitfac, infos_out)
+
+    def dgpschur_batch(self, problems, S, lr="R", **kw):
+        """Copying form of dgpschur_batch_: the factors are left untouched."""
+        if not hasattr(problems, "data_ptr"):
+            problems = self._batch_copies(_DG, _DG.wrong_exc(_DG.wrong_text), problems)
+        return self.dgpschur_batch_(problems, S, lr, **kw)
+
+    def dgpschur_hess_batch_(self, problems, S, wantT=True, wantZ=True, maxitfac=120, infos_out=None):
+        """pschur!(H1, Hs, S; wantT, wantZ, Q, maxitfac) for Float64 (src/rgeneralized.jl:49-80) for a list of
+        Hessenberg-triangular problems of equal shape and ONE signature in ONE call (psd_d_gpschur_hess_batch).
+        `problems`: list of (H1, Hs) or (H1, Hs, Q); matrices are overwritten.  `S` None: all true.  Returns a list of
+        GeneralizedPeriodicSchur, as gpschur_hess_ does; failures and `infos_out` as dgpschur_batch_."""
+        if len(problems) == 0:
+            if infos_out is not None:
+                infos_out[:] = []
+            return []
+        p = len(problems[0][1]) + 1
+        S = [True] * p if S is None else [bool(x) for x in S]
+        if len(S) != p:
+            raise DimensionMismatch("S must have one entry per factor")
+        if not S[0]:
+            raise ValueError("Signature entry S[1] must be true")  # src/rgeneralized.jl:73
+        wrong = TypeError("dgpschur_hess_batch_: Float64 only (ComplexF64 problems: zgpschur_hess_batch_)")
+        return self._pschur_hess_batch_(_DG, problems, S, wrong, wantT, wantZ, maxitfac, infos_out, True)
+
+    def gpschur_batch(self, As_list, Bs_list, real=False, **kw):
         """gpschur(As, Bs) (src/generalized.jl:1191-1211) for many pairs of series of equal shape in ONE call: the
         interleaving of `gpschur` per problem, then zgpschur_batch_ with the common signature (T, F, T, F, ...).
-        Returns a list of GeneralizedPeriodicSchur."""
+        Returns a list of GeneralizedPeriodicSchur.  `real`: all matrices must be real, and the interleaving goes to
+        dgpschur_batch_ as it is (real quasi-triangular T, orthogonal Z, exact conjugate pairs) instead of being cast to
+        ComplexF64; a complex matrix raises TypeError then."""
         if len(As_list) != len(Bs_list):
             raise DimensionMismatch("one Bs per As")
-        cz = lambda m: np.array(m, dtype=np.complex128, order="F", copy=True)  # noqa: E731
+        if real and any(np.iscomplexobj(m) for Ms in list(As_list) + list(Bs_list) for m in Ms):
+            raise TypeError("gpschur_batch(real=True): the matrices must be real (real=False takes complex ones)")
+        cz = lambda m: np.array(m, dtype=np.float64 if real else np.complex128, order="F", copy=True)  # noqa: E731
         problems = []
         for As, Bs in zip(As_list, Bs_list):
             ph = len(As)
@@ -1208,7 +1284,8 @@ class Engine:
         if not problems:
             return []
         # (pairs of another length make a problem of another period: turned away with those of another order)
-        return self.zgpschur_batch_(problems, [True, False] * len(As_list[0]), "R", **kw)
+        run = self.dgpschur_batch_ if real else self.zgpschur_batch_
+        return run(problems, [True, False] * len(As_list[0]), "R", **kw)
 
 
     def ordschur_(self, P, select, wantZ=True, Z=None):

@@ -28,6 +28,7 @@
 #include "psd_bord.h"
 #include "psd_zbqz.h"
 #include "psd_zgbqz.h"
+#include "psd_gbqz.h"
 #include "psd_zbord.h"
 #include "psd_zgbord.h"
 
@@ -295,6 +296,7 @@ struct psd_ctx {
     int shard_rank = 0, shard_world = 1;
     int batch_group = 0;  // PSD_BATCH_GROUP: most problems a host batch entry takes to the device at once (0: what fits)
     int bh_nmax = PSD_BH_NMAX;  // largest order of the one-workgroup-per-problem reduction (diagnostic build: PSD_BH_NMAX in the environment, for the sweep that sets the constant)
+    int gb_nmax = PSD_GB_NMAX;  // largest order of the real signed one-workgroup / one-wavefront-per-problem kernels (diagnostic build: PSD_GB_NMAX in the environment, for the sweep that sets the constant)
     int zb_nmax = PSD_ZB_NMAX;  // largest order of the complex one-workgroup / one-wavefront-per-problem kernels (diagnostic build: PSD_ZB_NMAX in the environment, for the sweep that sets the constant)
     int bev_nmax = PSD_BEV_NMAX;  // largest order of the batched eigenvector kernels (diagnostic build: PSD_BEV_NMAX in the environment, for the sweep that sets the constant)
     int bord_nmax = PSD_BORD_NMAX;  // largest order of the batched reordering kernel (PSD_BORD_NMAX in the environment lowers it: the tests reach the fallback with it)
@@ -1918,6 +1920,7 @@ int psd_create(psd_ctx** ctx, int device) {
     if (const char* e = psd_env("PSD_BATCH_GROUP")) c->batch_group = atoi(e) > 0 ? atoi(e) : 0;
     if (const char* e = psd_env_diag("PSD_BH_NMAX")) c->bh_nmax = (atoi(e) >= 1 && atoi(e) <= 2048) ? atoi(e) : PSD_BH_NMAX;
     if (const char* e = psd_env_diag("PSD_ZB_NMAX")) c->zb_nmax = (atoi(e) >= 1 && atoi(e) <= 2048) ? atoi(e) : PSD_ZB_NMAX;
+    if (const char* e = psd_env_diag("PSD_GB_NMAX")) c->gb_nmax = (atoi(e) >= 1 && atoi(e) <= 2048) ? atoi(e) : PSD_GB_NMAX;
     if (const char* e = psd_env_diag("PSD_BEV_NMAX")) c->bev_nmax = (atoi(e) >= 1 && atoi(e) <= 2048) ? atoi(e) : PSD_BEV_NMAX;
     if (const char* e = psd_env("PSD_BORD_NMAX")) c->bord_nmax = (atoi(e) >= 1 && atoi(e) < PSD_BORD_NMAX) ? atoi(e) : PSD_BORD_NMAX;
     if (const char* e = psd_env("PSD_BORD_W")) c->bord_w = (atoi(e) >= 1 && atoi(e) <= 32) ? atoi(e) : 0;  // (each kernel has its own least window: PSD_BORD_WMIN, PSD_ZBORD_WMIN)
@@ -3952,6 +3955,7 @@ extern "C" int psd_dbg_apply_bench(psd_ctx* c, int n, int p, int nwin, int W, in
 #include "psd_batch_host.inl"
 #include "psd_zbatch_host.inl"
 #include "psd_zgbatch_host.inl"
+#include "psd_gbatch_host.inl"
 #include "psd_bevec_host.inl"
 #include "psd_zbevec_host.inl"
 #include "psd_zgbevec_host.inl"

@@ -250,11 +250,12 @@ PSD_KERNEL psd_hess_next(psd_hess_args* G) {
 }
 
 // Q <- I for all p factors.  grid = (n, p)
-PSD_KERNEL psd_set_identity(double* Q, int n) {
-    const int c = PSD_BLOCK_X + 1, j = PSD_BLOCK_Y + 1;
+// (body: column c of factor j, both 1-based)
+PSD_D void psd_set_identity_body(double* Q, int n, int c, int j) {
     const psd_mat<double> M = psd_mat<double>{Q + (size_t)(j - 1) * n * n, n};
     PSD_PAR_FOR(r, n) { M(r + 1, c) = (r + 1 == c) ? 1.0 : 0.0; }
 }
+PSD_KERNEL psd_set_identity(double* Q, int n) { psd_set_identity_body(Q, n, PSD_BLOCK_X + 1, PSD_BLOCK_Y + 1); }
 
 // One step (reflector index i) of the backward accumulation Q_j = H_{j,1} ... H_{j,n-1}, all
 // factors at once (what Matrix(H.Q) / Matrix(QR.Q) produce, PSD.jl:136-143).  grid = (tiles, p).

@@ -2517,11 +2517,11 @@ PSD_D int psd_gtr_stage(const psd_gtr* gtr, int cnt, psd_gtr* ltr, int* flags) {
     return !flags[0] ? 1 : (!flags[1] ? -1 : 0);
 }
 
-PSD_D void psd_gq_apply_body(const psd_gparams& P, int n, int p, int role) {
+// (item: tile bx of factor l, 1-based, in one role — a block of psd_gq_apply's grid; psd_gbqz loops over them)
+PSD_D void psd_gq_apply_item(const psd_gparams& P, int n, int p, int role, int bx, int l) {
     PSD_LDS_DECL;
     const psd_gapply_desc d = *P.desc;
     if (!d.active) return;
-    const int l = PSD_BLOCK_Y + 1;
     const int own = (role == 0) ? psd_growner(P, l, p) : (role == 1) ? psd_gcowner(P, l, p) : l;
     const int cnt = P.cnt[own - 1] < PSD_GTR_CAP ? P.cnt[own - 1] : PSD_GTR_CAP;
     if (cnt <= 0) return;
@@ -2533,7 +2533,7 @@ PSD_D void psd_gq_apply_body(const psd_gparams& P, int n, int p, int role) {
     const psd_gtr* gtr = P.tr + (size_t)(own - 1) * PSD_GTR_CAP;
     const bool h1x = d.h1mode == 1 && l == 1;  // stage 2 of the signed Hessenberg reduction: H_1 outside the window
     if (role == 0) {
-        const int c0 = (h1x ? d.h1c0 : d.lc0) + PSD_BLOCK_X * T;
+        const int c0 = (h1x ? d.h1c0 : d.lc0) + bx * T;
         if (c0 > d.lc1) return;
         const int nc = (d.lc1 - c0 + 1 < T) ? (d.lc1 - c0 + 1) : T;
         if (h1x && c0 >= d.plo && c0 + nc - 1 <= d.phi) return;
@@ -2597,7 +2597,7 @@ PSD_D void psd_gq_apply_body(const psd_gparams& P, int n, int p, int role) {
         const bool h1r = h1x && role == 1;
         const int lo = (role == 1) ? (h1r ? 1 : d.rr0) : d.zr0;
         const int hi = (role == 1) ? (h1r ? n : d.rr1) : d.zr1;
-        const int r0 = lo + PSD_BLOCK_X * T;
+        const int r0 = lo + bx * T;
         if (r0 > hi) return;
         const int nr = (hi - r0 + 1 < T) ? (hi - r0 + 1) : T;
         double* base = (role == 1) ? P.H : P.Z;
@@ -2644,6 +2644,10 @@ PSD_D void psd_gq_apply_body(const psd_gparams& P, int n, int p, int role) {
     }
 }
 
+PSD_D void psd_gq_apply_body(const psd_gparams& P, int n, int p, int role) {
+    psd_gq_apply_item(P, n, p, role, PSD_BLOCK_X, PSD_BLOCK_Y + 1);
+}
+
 PSD_KERNEL_B(PSD_GAPPLY_NT) psd_gq_apply(psd_gparams P, int n, int p) { psd_gq_apply_body(P, n, p, PSD_BLOCK_Z); }
 
 // bulk updates of all cursors of a tick (as psd_rq_apply_train): pass 0 = rows and Z roles (grid.z = 2 M), pass 1 =
@@ -2661,12 +2665,12 @@ PSD_KERNEL_B(PSD_GAPPLY_NT) psd_gq_apply_train(psd_gparams P, int n, int p, int 
 
 // Deferred right side of H_1 after a zero-shift pass (rgeneralized.jl:312-320):
 // for j = djlo..djhi: rmul!(view(H1, drow0:(j+1), :), G_j').  One thread per row.
-PSD_KERNEL psd_gq_defer(psd_gparams P, int n) {
+PSD_D void psd_gq_defer_body(const psd_gparams& P, int n, int bx) {
     const psd_gapply_desc d = *P.desc;
     if (!d.active || d.defer_run != 1) return;
     const psd_mat<double> H1 = psd_mat<double>{P.H, n};
     const int NT = PSD_NTHREADS;
-    const int rbase = d.drow0 + PSD_BLOCK_X * NT;
+    const int rbase = d.drow0 + bx * NT;
     PSD_PAR_FOR(t, NT) {
         const int r = rbase + t;
         if (r <= d.djhi + 1 && d.djhi >= d.djlo) {
@@ -2682,9 +2686,10 @@ PSD_KERNEL psd_gq_defer(psd_gparams P, int n) {
         }
     }
 }
+PSD_KERNEL psd_gq_defer(psd_gparams P, int n) { psd_gq_defer_body(P, n, PSD_BLOCK_X); }
 
-PSD_KERNEL psd_gq_init(psd_gparams P, int n, int p, int wantT, int wantZ, int W, int maxitfac, int maxlog,
-                       int hessmode, int train_want, int train_oc) {
+PSD_D void psd_gq_init_body(const psd_gparams& P, int n, int p, int wantT, int wantZ, int W, int maxitfac, int maxlog,
+                            int hessmode, int train_want, int train_oc) {
     const psd_mat<double> H1 = psd_mat<double>{P.H, n};
     if (!hessmode) PSD_PAR_FOR(c, n) {
         for (int r = c + 3; r <= n; ++r) H1(r, c + 1) = 0.0;  // _gethess!
@@ -2724,14 +2729,18 @@ PSD_KERNEL psd_gq_init(psd_gparams P, int n, int p, int wantT, int wantZ, int W,
         P.desc->defer_run = 0;
     }
 }
+PSD_KERNEL psd_gq_init(psd_gparams P, int n, int p, int wantT, int wantZ, int W, int maxitfac, int maxlog,
+                       int hessmode, int train_want, int train_oc) {
+    psd_gq_init_body(P, n, p, wantT, wantZ, W, maxitfac, maxlog, hessmode, train_want, train_oc);
+}
 
 // ---- stage 1 helpers of the signed Hessenberg reduction (generalized.jl:1009-1028) -------------------------------------
 // RQ of A is taken as the QR of B = J A' J (reflection about the anti-diagonal), so the QR kernels of psd_hess.h serve
 // both signs; the neighbours that receive the orthogonal factor are flipped to the same index space and back.
+// (the bodies take the column the kernel's block index names, 1-based; psd_gbhess1 loops over it)
 // in place B(r, c) = A(n+1-c, n+1-r).  grid = n (columns)
-PSD_KERNEL psd_antitranspose(double* A, int n) {
+PSD_D void psd_antitranspose_body(double* A, int n, int c) {
     const psd_mat<double> M = psd_mat<double>{A, n};
-    const int c = PSD_BLOCK_X + 1;
     PSD_PAR_FOR(t, n) {
         const int r = t + 1;
         const int r2 = n + 1 - c, c2 = n + 1 - r;
@@ -2742,10 +2751,10 @@ PSD_KERNEL psd_antitranspose(double* A, int n) {
         }
     }
 }
+PSD_KERNEL psd_antitranspose(double* A, int n) { psd_antitranspose_body(A, n, PSD_BLOCK_X + 1); }
 // reverse the column order (rows == 0) or the row order (rows == 1).  grid = n
-PSD_KERNEL psd_flip(double* A, int n, int rows) {
+PSD_D void psd_flip_body(double* A, int n, int rows, int k) {
     const psd_mat<double> M = psd_mat<double>{A, n};
-    const int k = PSD_BLOCK_X + 1;
     if (rows == 0) {
         if (k > n / 2) return;
         PSD_PAR_FOR(t, n) {
@@ -2761,11 +2770,12 @@ PSD_KERNEL psd_flip(double* A, int n, int rows) {
         }
     }
 }
+PSD_KERNEL psd_flip(double* A, int n, int rows) { psd_flip_body(A, n, rows, PSD_BLOCK_X + 1); }
 // zero everything strictly below the diagonal.  grid = n
-PSD_KERNEL psd_tril_zero(double* A, int n) {
+PSD_D void psd_tril_zero_body(double* A, int n, int c) {
     const psd_mat<double> M = psd_mat<double>{A, n};
-    const int c = PSD_BLOCK_X + 1;
     PSD_PAR_FOR(t, n) {
         if (t + 1 > c) M(t + 1, c) = 0.0;
     }
 }
+PSD_KERNEL psd_tril_zero(double* A, int n) { psd_tril_zero_body(A, n, PSD_BLOCK_X + 1); }

@@ -12,10 +12,10 @@
 // Above PSD_ZB_NMAX the three steps are those of the single call — zhessenberg_dev, zformq_dev, ziterate_dev —, problem
 // by problem on the slices of the batch buffer.  A batch of one goes through the same kernels as any other.
 //
-// The signed driver (psd_zgbatch_host.inl) comes in behind this file and shares its workspace (zb_work), the launch and
-// read-back of the iteration kernel (zb_launch), the fallback loop above the cap (zb_single_loop) and the bodies of the
-// three kinds of entry with their argument codes (zb_pschur_batch_dev, zb_pschur_batch, zb_pschur_hess_batch), which take
-// the signature.
+// The signed drivers (psd_zgbatch_host.inl, and psd_gbatch_host.inl for Float64) come in behind this file and share its
+// workspace (zb_work), the launch and read-back of the iteration kernel (zb_launch), the fallback loop above the cap
+// (zb_single_loop) and the bodies of the three kinds of entry with their argument codes (zb_pschur_batch_dev,
+// zb_pschur_batch, zb_pschur_hess_batch), which take the signature and the family.
 
 namespace {
 
@@ -54,8 +54,9 @@ int zbformq_dev(psd_ctx* c, int nb, int n, int p, psd_z* dH, const psd_z* dtau, 
 }
 
 
-// Per-problem workspace of psd_zbqz / psd_zgbqz (Args: their argument struct) for nb problems, carved from one zeroed
-// allocation, every region 16-byte aligned; `extra` bytes follow the per-problem arrays (the signed kernel's signature).
+// Per-problem workspace of psd_zbqz / psd_zgbqz / psd_gbqz (Args: their argument struct, which names the types of the
+// state, the descriptor and the rotation records) for nb problems, carved from one zeroed allocation, every region
+// 16-byte aligned; `extra` bytes follow the per-problem arrays (the signed kernels' signature, the real kernel's xscr).
 // alloc fills the workspace pointers and n, p, maxlog of A.
 template <class Args>
 struct zb_work {
@@ -65,6 +66,7 @@ struct zb_work {
     int alloc(psd_ctx* c, int nb, int n, int p, int trcap, int maxlog, size_t extra_bytes = 0) {
         using State = typename std::remove_pointer<decltype(A.st)>::type;
         using Desc = typename std::remove_pointer<decltype(A.desc)>::type;
+        using Rot = typename std::remove_pointer<decltype(A.tr)>::type;
         size_t off = 0;
         auto carve = [&off](size_t bytes) {
             const size_t o = off;
@@ -72,8 +74,8 @@ struct zb_work {
             return o;
         };
         const size_t o_st = carve(sizeof(State) * nb), o_desc = carve(sizeof(Desc) * nb);
-        const size_t o_tr = carve(sizeof(psd_ztr) * (size_t)nb * p * trcap), o_cnt = carve(sizeof(int) * (size_t)nb * p);
-        const size_t o_dG = carve(sizeof(psd_ztr) * (size_t)nb * (n + 2)), o_alpha = carve(sizeof(psd_z) * (size_t)nb * n);
+        const size_t o_tr = carve(sizeof(Rot) * (size_t)nb * p * trcap), o_cnt = carve(sizeof(int) * (size_t)nb * p);
+        const size_t o_dG = carve(sizeof(Rot) * (size_t)nb * (n + 2)), o_alpha = carve(sizeof(psd_z) * (size_t)nb * n);
         const size_t o_beta = carve(sizeof(double) * (size_t)nb * n), o_asc = carve(sizeof(int) * (size_t)nb * n);
         const size_t o_log = carve(sizeof(int) * (size_t)nb * 3 * maxlog), o_info = carve(sizeof(int) * nb);
         const size_t o_extra = carve(extra_bytes);
@@ -82,9 +84,9 @@ struct zb_work {
         char* w = (char*)buf.ptr;
         A.st = (State*)(w + o_st);
         A.desc = (Desc*)(w + o_desc);
-        A.tr = (psd_ztr*)(w + o_tr);
+        A.tr = (Rot*)(w + o_tr);
         A.cnt = (int*)(w + o_cnt);
-        A.dG = (psd_ztr*)(w + o_dG);
+        A.dG = (Rot*)(w + o_dG);
         A.alpha = (psd_z*)(w + o_alpha);
         A.beta = (double*)(w + o_beta);
         A.ascale = (int*)(w + o_asc);
@@ -108,11 +110,14 @@ void zbatch_add_state(psd_stats* s, const State& st) {
     s->nlog += st.nlog;
 }
 
-// what psd_zbqz asks of zb_launch (the signed kernel: zgbqz_signed, psd_zgbatch_host.inl)
+// what psd_zbqz asks of zb_launch (the signed kernels: zgbqz_signed, psd_zgbatch_host.inl; gbqz_signed,
+// psd_gbatch_host.inl)
 struct zbqz_unsigned {
     using args_t = psd_zbqz_args;
     using state_t = psd_zstate;
-    static constexpr int capk = 4;  // (the slack of ziterate_dev's tick loop)
+    static constexpr int esize = 16;  // bytes of an element: the window choose_window / step_lds_bytes give
+    static constexpr int capk = 4;    // (the slack of ziterate_dev's tick loop)
+    static constexpr int capw = 3;    // (the positions it takes off the window for the shortest one)
     static size_t apply_lds(int W) { return psd_zbqz_apply_lds_bytes(W); }
     static void set_hessmode(args_t&, int) {}
     static const void* kernel() { return reinterpret_cast<const void*>(psd_zbqz); }
@@ -125,21 +130,21 @@ struct zbqz_unsigned {
 // and what the kernel left as per-problem codes (PSD_LIST_OVERFLOW, PSD_ZB_TICKCAP, level) in hst / hinfo, and with alpha
 // (nb * n complex pairs, host) the scaled eigenvalues in alpha, beta, ascale.  hessmode: stage 2 of the signed reduction.
 template <class K>
-int zb_launch(psd_ctx* c, zb_work<typename K::args_t>& ws, int nb, psd_z* dH, psd_z* dZ, int wantT, int wantZ, int maxitfac,
-              int hessmode, std::vector<typename K::state_t>& hst, std::vector<int>& hinfo, double* alpha = nullptr,
+int zb_launch(psd_ctx* c, zb_work<typename K::args_t>& ws, int nb, decltype(K::args_t::H) dH, decltype(K::args_t::H) dZ,
+              int wantT, int wantZ, int maxitfac, int hessmode, std::vector<typename K::state_t>& hst, std::vector<int>& hinfo, double* alpha = nullptr,
               double* beta = nullptr, int32_t* ascale = nullptr) {
     typename K::args_t& A = ws.A;
     const int n = A.n, p = A.p;
-    const int W = choose_window(p, 16);
+    const int W = choose_window(p, K::esize);
     if (W == 0) return PSD_INFO_NOTIMPL;
     A.H = dH;
     A.Z = wantZ ? dZ : nullptr;
     A.wantT = wantT; A.wantZ = wantZ; A.W = W; A.maxitfac = maxitfac;
     K::set_hessmode(A, hessmode);
-    const int nbmin = (W - 3 > 0) ? ((W - 3 < 8) ? (W - 3) : 8) : 1;  // (the bound of the single drivers' tick loops)
+    const int nbmin = (W - K::capw > 0) ? ((W - K::capw < 8) ? (W - K::capw) : 8) : 1;  // (the bound of the single drivers' tick loops)
     A.cap = (long long)maxitfac * n * ((long long)n / nbmin + K::capk) + (long long)K::capk * n + 1024 +
             (hessmode ? (long long)n * n : 0);
-    const size_t lds = std::max(step_lds_bytes(p, W, 16), K::apply_lds(W));
+    const size_t lds = std::max(step_lds_bytes(p, W, K::esize), K::apply_lds(W));
     PSD_CHECK(c->lds_limit(K::kernel(), lds));
     K::launch(c, nb, lds, A);
     const size_t nv = alpha ? (size_t)nb * n : 0;
@@ -266,42 +271,60 @@ bool zb_pschur_head(const batch_call<psd_stats>& k, psd_ctx* c, int nb, int n, i
     return *info != 0;
 }
 
+// What the three bodies below ask of a family F (zb_complex here; gb_real, psd_gbatch_host.inl): elem, the element type
+// (dpe doubles each); core, the whole path for a batch on the device in user order; iterate, the iteration alone.  The
+// complex family sends an all-true S to the tuned all-true kernels, the real one keeps it on the signed kernels (as
+// psd_d_gpschur's outputs have another form than psd_d_pschur_batch's).
+struct zb_complex {
+    using elem = psd_z;
+    static constexpr size_t dpe = 2;
+    static int core(psd_ctx* c, int nb, int n, int p, psd_z* dA, const uint8_t* S, bool left, int wantT, int wantZ, int maxitfac,
+                    psd_z* dZ, double* alpha, double* beta, int32_t* ascale, int* infos, psd_stats* s) {
+        return zgb_all_true(S, p)
+                   ? zpschur_batch_core(c, nb, n, p, dA, left, wantT, wantZ, maxitfac, dZ, alpha, beta, ascale, infos, s)
+                   : zgpschur_batch_core(c, nb, n, p, dA, S, left, wantT, wantZ, maxitfac, dZ, alpha, beta, ascale, infos, s);
+    }
+    static int iterate(psd_ctx* c, int nb, int n, int p, psd_z* dH, psd_z* dZ, const uint8_t* S, int wantT, int wantZ,
+                       int maxitfac, double* alpha, double* beta, int32_t* ascale, int* infos, psd_stats* s) {
+        return zgb_all_true(S, p) ? zbiterate_dev(c, nb, n, p, dH, dZ, wantT, wantZ, maxitfac, alpha, beta, ascale, infos, s)
+                                  : zgbiterate_dev(c, nb, n, p, dH, dZ, S, wantT, wantZ, maxitfac, alpha, beta, ascale, infos, s);
+    }
+};
+
 // The cores return call-wide codes only and each of them ends the call; the per-problem codes wait in the infos.
+template <class F = zb_complex>
 int zb_pschur_batch_dev(psd_ctx* c, int nb, int n, int p, double* dA, const uint8_t* S, char orient, int wantT, int wantZ,
                         int maxitfac, double* dZ, double* alpha, double* beta, int32_t* ascale, int* infos, int* schurindex,
                         psd_stats* stats, int* info) {
     batch_call<psd_stats> k(info, stats);
     if (zb_pschur_head(k, c, nb, n, p, dA, S, orient, maxitfac, wantZ, dZ, alpha, beta, ascale, info)) return *info;
     int* pinfos = k.infos(infos, nb);
-    psd_z* A = reinterpret_cast<psd_z*>(dA);
-    psd_z* Z = reinterpret_cast<psd_z*>(dZ);
+    typename F::elem* A = reinterpret_cast<typename F::elem*>(dA);
+    typename F::elem* Z = reinterpret_cast<typename F::elem*>(dZ);
     const bool left = orient == 'L';
-    const int rc = zgb_all_true(S, p)
-                       ? zpschur_batch_core(c, nb, n, p, A, left, wantT, wantZ, maxitfac, Z, alpha, beta, ascale, pinfos, k.s)
-                       : zgpschur_batch_core(c, nb, n, p, A, S, left, wantT, wantZ, maxitfac, Z, alpha, beta, ascale, pinfos, k.s);
+    const int rc = F::core(c, nb, n, p, A, S, left, wantT, wantZ, maxitfac, Z, alpha, beta, ascale, pinfos, k.s);
     if (schurindex) *schurindex = left ? p : 1;
     return *info = (rc != 0) ? rc : batch_first_code(pinfos, nb);
 }
 
+template <class F = zb_complex>
 int zb_pschur_batch(psd_ctx* c, int nb, int n, int p, double* const* A, const uint8_t* S, char orient, int wantT, int wantZ,
                     int maxitfac, double* const* Z, double* alpha, double* beta, int32_t* ascale, int* infos, int* schurindex,
                     psd_stats* stats, int* info) {
     batch_call<psd_stats> k(info, stats);
     if (zb_pschur_head(k, c, nb, n, p, A, S, orient, maxitfac, wantZ, Z, alpha, beta, ascale, info)) return *info;
-    const size_t nn2 = 2 * (size_t)n * n;  // doubles of one factor
+    const size_t nn2 = F::dpe * (size_t)n * n;  // doubles of one factor
     const batch_list L[] = {{A, p, nn2, BATCH_IN | BATCH_OUT}, {wantZ ? Z : nullptr, p, nn2, BATCH_OUT}};
     int* pinfos = k.infos(infos, nb);
-    const bool left = orient == 'L', plain = zgb_all_true(S, p);
+    const bool left = orient == 'L';
     auto body = [&](int q0, int gc, double* const* d) {
         psd_stats gs;
-        psd_z* dA = (psd_z*)d[0];
-        psd_z* dZ = (psd_z*)d[1];
+        typename F::elem* dA = (typename F::elem*)d[0];
+        typename F::elem* dZ = (typename F::elem*)d[1];
         double* al = alpha + 2 * (size_t)q0 * n;
         double* be = beta + (size_t)q0 * n;
         int32_t* sc = ascale + (size_t)q0 * n;
-        if (int e = plain ? zpschur_batch_core(c, gc, n, p, dA, left, wantT, wantZ, maxitfac, dZ, al, be, sc, pinfos + q0, &gs)
-                          : zgpschur_batch_core(c, gc, n, p, dA, S, left, wantT, wantZ, maxitfac, dZ, al, be, sc, pinfos + q0, &gs))
-            return e;
+        if (int e = F::core(c, gc, n, p, dA, S, left, wantT, wantZ, maxitfac, dZ, al, be, sc, pinfos + q0, &gs)) return e;
         batch_add_stats(k.s, gs, true);
         return 0;
     };
@@ -312,6 +335,7 @@ int zb_pschur_batch(psd_ctx* c, int nb, int n, int p, double* const* A, const ui
 }
 
 // noval: the code of missing eigenvalue arrays, which the two entries number differently
+template <class F = zb_complex>
 int zb_pschur_hess_batch(psd_ctx* c, int nb, int n, int p, double* const* H, const uint8_t* S, double* const* Q, int wantT,
                          int wantZ, int maxitfac, double* alpha, double* beta, int32_t* ascale, int* infos, psd_stats* stats,
                          int* info, int noval) {
@@ -323,21 +347,18 @@ int zb_pschur_hess_batch(psd_ctx* c, int nb, int n, int p, double* const* H, con
     if (maxitfac < 1) return *info = -9;
     if (!alpha || !beta || !ascale) return *info = noval;
     if (c->shard_world > 1) return *info = PSD_INFO_NOTIMPL;
-    const size_t nn2 = 2 * (size_t)n * n;
+    const size_t nn2 = F::dpe * (size_t)n * n;
     const batch_list L[] = {{H, p, nn2, BATCH_IN | BATCH_OUT}, {wantZ ? Q : nullptr, p, nn2, BATCH_IN | BATCH_OUT}};
     int* pinfos = k.infos(infos, nb);
-    const bool plain = zgb_all_true(S, p);
     Timer tk;
     auto body = [&](int q0, int gc, double* const* d) {
-        psd_z* dH = (psd_z*)d[0];
-        psd_z* dZ = (psd_z*)d[1];
+        typename F::elem* dH = (typename F::elem*)d[0];
+        typename F::elem* dZ = (typename F::elem*)d[1];
         double* al = alpha + 2 * (size_t)q0 * n;
         double* be = beta + (size_t)q0 * n;
         int32_t* sc = ascale + (size_t)q0 * n;
         tk.start(c->stream);
-        if (int e = plain ? zbiterate_dev(c, gc, n, p, dH, dZ, wantT, wantZ, maxitfac, al, be, sc, pinfos + q0, k.s)
-                          : zgbiterate_dev(c, gc, n, p, dH, dZ, S, wantT, wantZ, maxitfac, al, be, sc, pinfos + q0, k.s))
-            return e;
+        if (int e = F::iterate(c, gc, n, p, dH, dZ, S, wantT, wantZ, maxitfac, al, be, sc, pinfos + q0, k.s)) return e;
         k.s->ms_iter += tk.stop(c->stream);
         return 0;
     };

@@ -36,7 +36,9 @@ int zgb_work_alloc(psd_ctx* c, zgb_work& ws, int nb, int n, int p, int maxlog, c
 struct zgbqz_signed {
     using args_t = psd_zgbqz_args;
     using state_t = psd_zgstate;
+    static constexpr int esize = 16;
     static constexpr int capk = 8;  // (the slack of zgiterate_dev's tick loop)
+    static constexpr int capw = 3;
     static size_t apply_lds(int) { return psd_zgbqz_apply_lds_bytes(); }
     static void set_hessmode(args_t& A, int hessmode) { A.hessmode = hessmode; }
     static const void* kernel() { return reinterpret_cast<const void*>(psd_zgbqz); }

@@ -10,14 +10,19 @@
                     lifted (PSD_BH_NMAX in the environment), so that every order takes the batched kernel.
 
   --complex         the ComplexF64 family: Engine.zpschur_batch_ against the loop of Engine.pschur_ over the same complex
-                    problems, in the same process and run, nb = 256, p = 8 over the orders of --complex-orders: the
+                    problems, in the same process and run, nb = 256, p = 8 over the orders of --orders: the
                     measurement PSD_ZB_NMAX is set from (the largest order at which the batched call still wins).
 
   --signed          the signed ComplexF64 family: Engine.zgpschur_batch_ against the loop of Engine.pschur_(..., S=S) over
                     the same problems with the alternating signature (T, F, T, F, ...), nb = 256, p = 8 over the orders of
-                    --complex-orders: the measurement the order cap of the signed batch kernels is set from.  Loop and
+                    --orders: the measurement the order cap of the signed batch kernels is set from.  Loop and
                     batch alternate, --reps times each after one warm-up pair; the row carries every repetition and the
                     ratio of the fastest ones, and the largest eigenvalue difference between the two on the first problem.
+
+  --signed-real     the signed Float64 family: Engine.dgpschur_batch_ against the loop of Engine.pschur_(..., S=S) over the
+                    same real problems over the orders of --orders (nb = --nb, p = 8), otherwise as --signed (same
+                    process and run, alternating, repetition 0 the warm-up): the measurement the order cap of the real signed batch kernels (PSD_GB_NMAX) is set from.
+                    Each row also carries the spread of the repetitions of either side.
 
 One JSON line per shape on stdout; --json FILE collects them."""
 import argparse
@@ -76,7 +81,7 @@ def time_batch(eng, probs, lr, cplx=False):
     return best
 
 
-def time_signed(eng, probs, S, lr, reps):
+def time_signed(eng, probs, S, lr, reps, real=False):
     """Loop of single signed calls and the batched call, alternating; repetition 0 is the warm-up."""
     import psdtest as pt
 
@@ -93,7 +98,7 @@ def time_signed(eng, probs, S, lr, reps):
         loop = dict(wall_ms=1e3 * (time.perf_counter() - t0), ms_total=dev)
         Ws = copies(probs)
         t0 = time.perf_counter()
-        out = eng.zgpschur_batch_(Ws, S, lr)
+        out = eng.dgpschur_batch_(Ws, S, lr) if real else eng.zgpschur_batch_(Ws, S, lr)
         wall = 1e3 * (time.perf_counter() - t0)
         st = out[0].stats
         batch = dict(wall_ms=wall, ms_hess=st.ms_hess, ms_iter=st.ms_iter, ms_copy=st.ms_copy, ms_total=st.ms_total,
@@ -125,9 +130,12 @@ def main():
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--sweep-orders", default="32,64,96,128,192,256")
     ap.add_argument("--complex", dest="cplx", action="store_true")
-    ap.add_argument("--complex-orders", default="8,16,32,64,96,128")
-    ap.add_argument("--complex-nb", type=int, default=256)
+    ap.add_argument("--orders", "--complex-orders", dest="complex_orders", default="8,16,32,64,96,128",
+                    help="orders of --complex, --signed and --signed-real (p = 8)")
+    ap.add_argument("--nb", "--complex-nb", dest="complex_nb", type=int, default=256,
+                    help="problems per batch of --complex, --signed and --signed-real")
     ap.add_argument("--signed", action="store_true")
+    ap.add_argument("--signed-real", dest="signed_real", action="store_true")
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--lib", default=None, help="library to load instead of the package's (a build of another commit)")
     ap.add_argument("--json", default=None)
@@ -148,7 +156,7 @@ def main():
         for n in [int(x) for x in args.sweep_orders.split(",") if x]:
             rows.append(time_sweep(eng, 64, n, 8))
             print(json.dumps(rows[-1]), flush=True)
-    elif args.signed:
+    elif args.signed or args.signed_real:
         import numpy as np
 
         for n in [int(x) for x in args.complex_orders.split(",") if x]:
@@ -156,11 +164,14 @@ def main():
             S = [q % 2 == 0 for q in range(p)]
             if args.lr == "L":
                 S = S[::-1]
-            probs = factors(nb, n, p, np.complex128)
-            loops, batches, diff = time_signed(eng, probs, S, args.lr, args.reps)
-            row = dict(nb=nb, n=n, p=p, lr=args.lr, dtype="complex128", S="".join("T" if x else "F" for x in S),
+            dtype = np.float64 if args.signed_real else np.complex128
+            probs = factors(nb, n, p, dtype)
+            loops, batches, diff = time_signed(eng, probs, S, args.lr, args.reps, real=args.signed_real)
+            row = dict(nb=nb, n=n, p=p, lr=args.lr, dtype=np.dtype(dtype).name, S="".join("T" if x else "F" for x in S),
                        loop=loops, batch=batches, eig_diff_problem0=diff)
             row["wall_ratio"] = min(r["wall_ms"] for r in loops) / min(r["wall_ms"] for r in batches)
+            for side, runs in (("loop", loops), ("batch", batches)):  # (spread of the repetitions: max / min of the wall times)
+                row[side + "_spread"] = max(r["wall_ms"] for r in runs) / min(r["wall_ms"] for r in runs)
             row["device_ratio"] = min(r["ms_total"] for r in loops) / min(r["ms_total"] for r in batches)
             rows.append(row)
             print(json.dumps(row), flush=True)
