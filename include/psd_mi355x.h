@@ -877,6 +877,38 @@ int psd_z_gordschur_batch_dev(psd_ctx* ctx, int nb, int n, int p, void* dT, void
                               int schurindex, const uint8_t* select, int wantZ, double* alpha, double* beta,
                               int32_t* ascale, int* infos, int* nswaps, psd_stats* stats, int* info);
 
+/* ---- dgordschur_batch: reorder many small signed Float64 periodic Schur forms in one call --------------------------
+ * ordschur!(P::GeneralizedPeriodicSchur{Float64}, select) (rordschur.jl:3-132 with the signed block swaps of
+ * sylswap.jl:197-538) for nb real generalized decompositions of one shape (n, p) and ONE signature, as
+ * psd_d_gpschur_batch leaves them: quasi-triangular T at schurindex (1 or p), orthogonal Z, one orient for the whole
+ * batch; the conventions of psd_z_gordschur_batch.  S: host [p] flags in user order, or NULL (all true).  Up to order
+ * 128 one wavefront carries one problem through its whole reordering — the scan, window and swap bodies of the single
+ * driver and its off-window update with the sides the signature asks for — and a group is ONE launch of the swap kernel
+ * (psd_gbord) whatever nb is; above, or for a period whose narrowest window does not fit the LDS, the real signed single
+ * driver runs problem by problem on the slices of the batch buffers (every problem: unlike psd_d_gordschur, a problem
+ * with a purely real spectrum is not promoted to the complex kernel).  A problem's result does not depend on its place
+ * in the batch or on the grouping (bit for bit).  A NULL or all-true S stays on these kernels: the eigenvalues are
+ * always returned in the scaled form.  PSD_BATCH_GROUP, PSD_BORD_W (from 6) and PSD_BORD_NMAX act as for
+ * psd_d_ordschur_batch.
+ *
+ * T, Z: nb * p host matrices of n * n doubles, column-major; select: nb * n flags — one member of a conjugate pair takes
+ * its partner along; alpha: nb * n complex pairs (conjugate pairs as exact conjugates), beta, ascale: nb * n; infos,
+ * nswaps, stats and the per-problem codes (0, 3000, 2000 + row) as for psd_z_gordschur_batch; stats->window = W (at
+ * most 25).
+ * Returns the first non-zero per-problem code, or a call-wide one: -1 ctx NULL; -2 n < 1; -3 p < 1; -4 T NULL;
+ * -5 Z NULL with wantZ; -6 orient; -7 schurindex strictly inside the period; -8 select NULL; -9 alpha, beta or ascale
+ * NULL; -10 the entry of S that lands first in working order (that of the factor at schurindex) is false; -11 nb < 0;
+ * PSD_INFO_NOTIMPL on a period-sharded context; PSD_INFO_RUNTIME + k.  nb == 0 returns 0 and touches nothing. */
+int psd_d_gordschur_batch(psd_ctx* ctx, int nb, int n, int p, double* const* T, double* const* Z, const uint8_t* S,
+                          char orient, int schurindex, const uint8_t* select, int wantZ, double* alpha, double* beta,
+                          int32_t* ascale, int* infos, int* nswaps, psd_stats* stats, int* info);
+/* Device-resident variant: dT, dZ device [nb][p][n][n] column-major blocks of doubles in user order (what
+ * psd_d_gpschur_batch_dev leaves), reordered in place; S and the other arrays are host arrays.  The blocks are brought
+ * to the internal order and back on the device, as psd_d_ordschur_batch_dev does. */
+int psd_d_gordschur_batch_dev(psd_ctx* ctx, int nb, int n, int p, void* dT, void* dZ, const uint8_t* S, char orient,
+                              int schurindex, const uint8_t* select, int wantZ, double* alpha, double* beta,
+                              int32_t* ascale, int* infos, int* nswaps, psd_stats* stats, int* info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -462,6 +462,53 @@ function ordschur_batch!(problems::Vector{<:GeneralizedPeriodicSchur{ComplexF64}
     problems
 end
 
+# ordschur_batch!(problems, select; wantZ, infos) for signed Float64 problems — ordschur!(P::GeneralizedPeriodicSchur{Float64},
+# select; wantZ) (rordschur.jl:3-132 with the signed block swaps of sylswap.jl:197-538) for many small real decompositions of
+# equal order, period, orientation, schurindex (1 or p) and signature S in ONE call (psd_d_gordschur_batch), the follow-up
+# of pschur_batch!(problems, S, lr) on real problems.  One member of a conjugate pair takes its partner along.  Every
+# signature, the all-true one included, stays on the signed real kernels; everything else as in the ComplexF64 method.
+# NOT YET RUN: this method has not been executed.  It follows the signed ComplexF64 method above and the real branch of
+# ordschur!(P::GeneralizedPeriodicSchur, ...) line by line; the C entry it calls is tested through the Python binding.
+function ordschur_batch!(problems::Vector{<:GeneralizedPeriodicSchur{Float64}}, select::AbstractVector;
+                         wantZ::Bool = true, infos::Union{Nothing, Vector{Cint}} = nothing)
+    nb = length(problems)
+    nb == 0 && return problems
+    ps1 = problems[1]
+    p = ps1.period; n = size(ps1.T1, 1); js = ps1.schurindex; orient = ps1.orientation
+    (js == 1 || js == p) || throw(ArgumentError("only implemented for schurindex in (1,p)"))     # rordschur.jl:25
+    wantZ = wantZ && all(ps -> !isempty(ps.Z) && size(ps.Z[1], 1) == n, problems)
+    sel = zeros(UInt8, n, nb)
+    for (q, ps) in enumerate(problems)
+        (ps.period == p && size(ps.T1, 1) == n && ps.schurindex == js && ps.orientation == orient) ||
+            throw(DimensionMismatch("the problems of a batch must have equal order, period, orientation and schurindex"))
+        ps.S == ps1.S || throw(DimensionMismatch("the problems of a batch must have equal signatures S"))
+        sq = select[1] isa Bool ? select : select[q]
+        length(sq) == n || throw(DimensionMismatch("select must have one entry per eigenvalue"))
+        sel[:, q] .= UInt8.(sq)
+    end
+    ps1.S[js] || throw(ArgumentError("The entry of S at schurindex must be true"))                # generalized.jl:182
+    T = reduce(vcat, [_userT(ps) for ps in problems])
+    Z = wantZ ? reduce(vcat, [ps.Z for ps in problems]) : Matrix{Float64}[]
+    α = zeros(ComplexF64, n, nb); β = zeros(n, nb); sc = zeros(Int32, n, nb)
+    codes = infos === nothing ? Vector{Cint}(undef, nb) : infos
+    length(codes) == nb || throw(DimensionMismatch("infos must have one entry per problem"))
+    info = Ref{Cint}(0)
+    Tp = _ptrs(T); Zp = _ptrs(Z); Sb = UInt8.(ps1.S)
+    GC.@preserve T Z Sb sel α β sc codes begin
+        ccall((:psd_d_gordschur_batch, libpsd), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ptr{UInt8}, Cchar, Cint, Ptr{UInt8}, Cint,
+               Ptr{ComplexF64}, Ptr{Float64}, Ptr{Int32}, Ptr{Cint}, Ptr{Cint}, Ptr{Cvoid}, Ref{Cint}),
+              ctx().ptr, nb, n, p, Tp, wantZ ? Zp : C_NULL, Sb, orient, js, sel, wantZ, α, β, sc, codes, C_NULL, C_NULL, info)
+    end
+    (info[] < 0 || info[] >= INFO_NOTIMPL) && _throw(info[])                 # argument / runtime codes end the call
+    for (q, ps) in enumerate(problems)
+        codes[q] == 0 || continue
+        ps.α .= α[:, q]; ps.β .= β[:, q]; ps.αscale .= Int.(sc[:, q])                             # ordschur.jl:75-96
+    end
+    infos === nothing && foreach(_throw_ord, codes)
+    problems
+end
+
 # eigvecs_batch_device(problems, select; shifted) — no reference equivalent: eigvecs(ps, select; shifted) (vectors.jl:25-138)
 # by periodic back-substitution for many small Float64 decompositions of equal order, period, orientation and schurindex in
 # ONE call (psd_d_eigvecs_batch), the follow-up of pschur_batch!.  `select`: a Vector{Bool} used for every problem or one per

@@ -278,7 +278,8 @@ _DG = _Family("d", np.float64, TypeError, "dgpschur_batch: Float64 only (Complex
 
 _ORD_WRONG = {_D: "ordschur_batch: Float64 only (use ordschur_ per problem for ComplexF64)",
               _Z: "zordschur_batch: ComplexF64 only (Float64 problems: ordschur_batch)"}
-_GORD_WRONG = "zgordschur_batch: ComplexF64 only (use ordschur_ per problem for a signed Float64 decomposition)"
+_GORD_WRONG = {_Z: "zgordschur_batch: ComplexF64 only (Float64 problems: dgordschur_batch)",
+               _DG: "dgordschur_batch: Float64 only (ComplexF64 problems: zgordschur_batch)"}
 
 
 def _other_family(fam, cplx, every=False):
@@ -375,8 +376,8 @@ class Engine:
         lib.psd_d_checkpsd_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, u8p,
                                            C.c_char, C.c_int, C.c_double, C.c_int, dp, dp, dp, ip, ip]
         # the batch entries: one description per entry family, crossed with d / z (the eigenvalue arguments), plain /
-        # signed (the signature after the factors) and host / dev (how the matrices are passed).  The signed pschur
-        # entries of both types return scaled eigenvalues (alpha, beta, alphascale).
+        # signed (the signature after the factors) and host / dev (how the matrices are passed).  The signed pschur and
+        # ordschur entries of both types return scaled eigenvalues (alpha, beta, alphascale).
         sp, head = C.POINTER(Stats), [C.c_void_p, C.c_int, C.c_int, C.c_int]  # (head: ctx, nb, n, p)
         for t, eig in (("d", [dp, dp]), ("z", [dp, dp, i32p])):
             sigs = {f"psd_{t}_phessenberg_batch": head + [dpp, dp, sp, ip],
@@ -388,9 +389,8 @@ class Engine:
                 for g, sig, ge in (("", [], eig), ("g", [u8p], [dp, dp, i32p])):
                     sigs[f"psd_{t}_{g}pschur_batch{dev}"] = (head + [mats] + sig + [C.c_char, C.c_int, C.c_int, C.c_int,
                                                                                      mats] + ge + [ip, ip, sp, ip])
-                for g, sig in (("", []), ("g", [u8p])):
                     sigs[f"psd_{t}_{g}ordschur_batch{dev}"] = (head + [mats, mats] + sig + [C.c_char, C.c_int, u8p, C.c_int]
-                                                               + eig + [ip, ip, sp, ip])
+                                                               + ge + [ip, ip, sp, ip])
                 sigs[f"psd_{t}_eigvecs_batch{dev}"] = (head + [mats, mats] + eig + [C.c_char, C.c_int, u8p, C.c_int, mats,
                                                                                     C.c_int, ip, i32p,
                                                                                     C.POINTER(BevecStats), ip])
@@ -1449,7 +1449,7 @@ class Engine:
                 other = any(cT) if fam is _D else not any(cT + cZ)
                 mixed = any(cZ) if fam is _D else not all(cT + cZ)
             else:  # ordschur: real vectors beside complex factors are left to the in-place contract
-                other = any(cT + cZ) if fam is _D else not all(cT)
+                other = any(cT + cZ) if fam.dtype is np.float64 else not all(cT)
                 mixed = False
             if other:
                 raise wrong
@@ -1498,9 +1498,9 @@ class Engine:
         setattr(self, name + "_nswaps", nswaps)
 
     def _ordschur_batch_(self, fam, name, problems, args, wantZ, infos_out, lr, schurindex, signed=False, S=None):
-        """ordschur_batch_ / zordschur_batch_ / zgordschur_batch_ (`signed`: the entry with a signature, which the
-        problems carry; `S`: that of device tensors)."""
-        wrong = NotImplementedPSD(_GORD_WRONG if signed else _ORD_WRONG[fam])
+        """ordschur_batch_ / zordschur_batch_ / zgordschur_batch_ / dgordschur_batch_ (`signed`: the entry with a
+        signature, which the problems carry; `S`: that of device tensors)."""
+        wrong = NotImplementedPSD((_GORD_WRONG if signed else _ORD_WRONG)[fam])
         if hasattr(problems, "data_ptr"):
             if len(args) != 2:
                 raise TypeError(f"{name}_(T, Z, select, lr=..., schurindex=...)")
@@ -1535,7 +1535,7 @@ class Engine:
             for q, ps in enumerate(problems):
                 if infos[q] == 0:  # (a problem that failed keeps its old values)
                     ps.values = values[q].copy()  # (its own array, not a view that keeps the batch's alive)
-                    if fam is _Z and isinstance(ps, GeneralizedPeriodicSchur):  # (the real entry has no scaled form)
+                    if fam is not _D and isinstance(ps, GeneralizedPeriodicSchur):  # (the real unsigned entry has no scaled form)
                         ps.alpha, ps.beta, ps.alphascale = eig[0][q].copy(), eig[1][q].copy(), eig[2][q].copy()
                 ps.stats = Stats.from_buffer_copy(st)
                 ps.stats.nsweeps = nsw[q]
@@ -1570,7 +1570,7 @@ class Engine:
             lambda eig, infos, nsw, st: (dT.transpose(2, 3), (dZ.transpose(2, 3) if wantZ else Z), _eig_values(eig), st), S)
 
     def _ordschur_batch(self, fam, inplace, problems, args, kw, wrong=None):
-        """The copying forms of the three above."""
+        """The copying forms of the four entries."""
         if hasattr(problems, "data_ptr"):
             Z = args[0] if len(args) > 0 else None
             return inplace(problems.clone(), Z.clone() if Z is not None else None, *args[1:], **kw)
@@ -1655,7 +1655,34 @@ class Engine:
 
     def zgordschur_batch(self, problems, *args, **kw):
         """Copying form of zgordschur_batch_: the decompositions are left untouched (device tensors are copied too)."""
-        return self._ordschur_batch(_Z, self.zgordschur_batch_, problems, args, kw, _GORD_WRONG)
+        return self._ordschur_batch(_Z, self.zgordschur_batch_, problems, args, kw, _GORD_WRONG[_Z])
+
+    def dgordschur_batch_(self, problems, *args, wantZ=True, infos_out=None, lr="R", schurindex=1, S=None):
+        """LinearAlgebra.ordschur!(P::GeneralizedPeriodicSchur{Float64}, select; wantZ) (src/rordschur.jl:3-132 with the
+        signed block swaps of src/sylswap.jl:197-538) for MANY small real decompositions of one shape and ONE signature in
+        ONE call (psd_d_gordschur_batch): the follow-up of dgpschur_batch / gpschur_batch(..., real=True), the signed
+        counterpart of ordschur_batch_.  T stays real and quasi-triangular, Z orthogonal, conjugate pairs exact
+        conjugates.  Per problem the result contract is that of `ordschur_`; a problem's result does not depend on its
+        place in the batch.  An all-true signature stays on the signed kernels: the result is always in the scaled form.
+        Above the order cap the real signed single driver runs problem by problem — every problem, while `ordschur_`
+        sends a problem with a purely real spectrum through the complex kernel.
+
+        dgordschur_batch_(problems, select, wantZ=True, infos_out=None): `problems` a list of real
+        GeneralizedPeriodicSchur of equal order, period, orientation, schurindex (1 or p) and S, with writable
+        Fortran-ordered float64 factors; each is mutated (Ts, Z, values, alpha, beta, alphascale, stats) and the list
+        returned.  The `stats` of a problem are the call's, with `nsweeps` its own swap count; the call's own are left
+        in `self.dgordschur_batch_stats`, the swap counts in `self.dgordschur_batch_nswaps` ([nb]).
+        dgordschur_batch_(T, Z, select, S=..., lr=..., schurindex=..., wantZ=True, infos_out=None): the torch outputs
+        of the device-resident dgpschur_batch_ ([nb, p, n, n] float64 tensors; Z may be None with wantZ=False) and
+        the signature of that call; returns (T, Z, values, stats), in place or through a copy as ordschur_batch_ does.
+
+        `select` (one member of a conjugate pair takes its partner along), rejected swaps and `infos_out` as
+        ordschur_batch_."""
+        return self._ordschur_batch_(_DG, "dgordschur_batch", problems, args, wantZ, infos_out, lr, schurindex, True, S)
+
+    def dgordschur_batch(self, problems, *args, **kw):
+        """Copying form of dgordschur_batch_: the decompositions are left untouched (device tensors are copied too)."""
+        return self._ordschur_batch(_DG, self.dgordschur_batch_, problems, args, kw, _GORD_WRONG[_DG])
 
     def eigvecs(self, ps0, select, shifted=True, method="ordschur"):
         """LinearAlgebra.eigvecs(ps::PeriodicSchur, select; shifted) — src/vectors.jl:25-138: selected right

@@ -67,6 +67,13 @@ PSD_D psd_roparams psd_bord_params(const psd_bord_args& A, int q) {
 // restricted to the window's span plo..phi: a lane copies its strip to LDS, runs the owner's list over it — per element
 // the dot products of psd_rord_apply in the same order — and writes it back.  The items of all owners and roles are
 // dealt to the lanes together, L per pass (tile: L strips of at most W doubles, in the window area, which is free here).
+//
+// SIGNED (psd_gbord, psd_gbord.h): the side follows the signature as in psd_rord_apply — owner m acts on T_m from the
+// left only if S[m], otherwise from the right on its rows, and on T_{m-1} from the right only if S[m-1], otherwise from
+// the left on its columns.  Every factor T_f so gets one update of its columns lc0..lc1 and one of its rows rr0..rr1,
+// each by f or by its successor f+1 (cyclically); the items are dealt by factor: the columns of T_f (owner f if S[f],
+// else f+1), its rows (owner f+1 if S[f], else f), the rows of Z_f (owner f).
+template <bool SIGNED>
 PSD_D void psd_bord_apply(const psd_roparams& P, int n, int p, double* tile, int L) {
     const psd_apply_desc d = *P.desc;
     if (!d.active) return;
@@ -88,7 +95,7 @@ PSD_D void psd_bord_apply(const psd_roparams& P, int n, int p, double* tile, int
                     x = P.H + (size_t)(m - 1) * nn + (size_t)(d.lc0 + k - 1) * n + (d.plo - 1);
                     sx = 1;
                 } else if (k < nc + nr) {
-                    x = P.H + (size_t)(mm1 - 1) * nn + (size_t)(d.plo - 1) * n + (d.rr0 + (k - nc) - 1);
+                    x = P.H + (size_t)((SIGNED ? m : mm1) - 1) * nn + (size_t)(d.plo - 1) * n + (d.rr0 + (k - nc) - 1);
                     sx = (size_t)n;
                 } else {
                     x = P.Z + (size_t)(m - 1) * nn + (size_t)(d.plo - 1) * n + (d.zr0 + (k - nc - nr) - 1);
@@ -96,8 +103,12 @@ PSD_D void psd_bord_apply(const psd_roparams& P, int n, int p, double* tile, int
                 }
                 double* v = tile + t;
                 for (int r = 0; r < S; ++r) v[r * L] = x[r * sx];
-                const int cnt = P.cnt[m - 1] < PSD_RORD_CAP ? P.cnt[m - 1] : PSD_RORD_CAP;
-                const psd_tq* list = P.tq + (size_t)(m - 1) * PSD_RORD_CAP;
+                int own = m;  // whose list runs over the strip
+                if constexpr (SIGNED) {  // the columns of T_m: m if S[m], else its successor; the rows: the other one
+                    if (k < nc + nr && (k < nc) != psd_rosig(P, m)) own = (m == p) ? 1 : (m + 1);
+                }
+                const int cnt = P.cnt[own - 1] < PSD_RORD_CAP ? P.cnt[own - 1] : PSD_RORD_CAP;
+                const psd_tq* list = P.tq + (size_t)(own - 1) * PSD_RORD_CAP;
                 for (int e = 0; e < cnt; ++e) {
                     const psd_tq& tr = list[e];
                     const int r = tr.pos - d.plo, mm = tr.m;
@@ -116,14 +127,16 @@ PSD_D void psd_bord_apply(const psd_roparams& P, int n, int p, double* tile, int
     }
 }
 
-// grid = problems of the group, one wavefront each; LDS = rord_lds_bytes(p, W)
-PSD_KERNEL_B(PSD_STEP_NT) psd_bord(psd_bord_args A) {
+// One problem from the first scan to the last swap, by one wavefront; P: its parameters, the others the members of the
+// launch's psd_bord_args of these names, info: where the problem's code goes.  SIGNED: P.S
+// is the signature of the batch (psd_gbord.h), which the flags SL of the left-oriented sequence X_l = T_{sigma(l)} and
+// the sides of the off-window update follow as in psd_rord_step / psd_rord_apply; otherwise every flag is 1.
+template <bool SIGNED>
+PSD_D void psd_bord_body(const psd_roparams P, const int n, const int p, const int wantZ, const int W, const int maxwin,
+                         int* info) {
     PSD_LDS_DECL;
-    const int q = PSD_BLOCK_X;
-    const int n = A.n, p = A.p, W = A.W;
-    const psd_roparams P = psd_bord_params(A, q);
     psd_rostate st;
-    st.n = n; st.p = p; st.wantZ = A.wantZ; st.W = W;
+    st.n = n; st.p = p; st.wantZ = wantZ; st.W = W;
     st.phase = PSD_ROPH_SCAN; st.info = 0;
     st.j = 0; st.jdest = 0; st.pairskip = 0;
     st.here = 0; st.nbsrc = 1; st.splitsrc = 0; st.jtarget = 0; st.jsrc0 = 0; st.pend1x1 = 0;
@@ -138,13 +151,17 @@ PSD_KERNEL_B(PSD_STEP_NT) psd_bord(psd_bord_args A) {
     double* ws = flagbuf + 4;
     int* lcnt = (int*)(ws + 192 + psd_rord_tree_doubles(p));
     unsigned char* SL = (unsigned char*)(lcnt + p);
-    PSD_PAR_FOR(t, p) { SL[t] = 1; }
+    if constexpr (SIGNED) {
+        PSD_PAR_FOR(t, p) { SL[t] = psd_rosig(P, psd_ord_sigma(p, t + 1)) ? 1 : 0; }
+    } else {
+        PSD_PAR_FOR(t, p) { SL[t] = 1; }
+    }
     PSD_SYNC();
     const int L = (winb / (size_t)W < (size_t)PSD_STEP_NT) ? (int)(winb / (size_t)W) : PSD_STEP_NT;  // (>= W + 1)
     for (;;) {
         psd_rord_scan(P, st);
         if (st.phase != PSD_ROPH_MOVE) break;
-        if (st.nwindows >= A.maxwin) {
+        if (st.nwindows >= maxwin) {
             st.info = PSD_LIST_OVERFLOW;
             st.phase = PSD_ROPH_DONE;
             break;
@@ -160,14 +177,20 @@ PSD_KERNEL_B(PSD_STEP_NT) psd_bord(psd_bord_args A) {
             st.phase = PSD_ROPH_DONE;
             break;
         }
-        psd_bord_apply(P, n, p, ldsd, L);
+        psd_bord_apply<SIGNED>(P, n, p, ldsd, L);
         PSD_SYNC();
     }
     PSD_SYNC();
     PSD_ONE {
         *P.st = st;
-        A.infos[q] = st.info;
+        *info = st.info;
     }
+}
+
+// grid = problems of the group, one wavefront each; LDS = rord_lds_bytes(p, W)
+PSD_KERNEL_B(PSD_STEP_NT) psd_bord(psd_bord_args A) {
+    const int q = PSD_BLOCK_X;
+    psd_bord_body<false>(psd_bord_params(A, q), A.n, A.p, A.wantZ, A.W, A.maxwin, A.infos + q);
 }
 
 // psd_rord_values for a batch: grid = (ceil(n / 64), nb), 64 threads.  Problems with a non-zero info are skipped.

@@ -31,6 +31,7 @@
 #include "psd_gbqz.h"
 #include "psd_zbord.h"
 #include "psd_zgbord.h"
+#include "psd_gbord.h"
 
 #include "../../include/psd_mi355x.h"
 
@@ -3962,4 +3963,5 @@ extern "C" int psd_dbg_apply_bench(psd_ctx* c, int n, int p, int nwin, int W, in
 #include "psd_bord_host.inl"
 #include "psd_zbord_host.inl"
 #include "psd_zgbord_host.inl"
+#include "psd_gbord_host.inl"
 #include "psd_diag_scalar.inl"

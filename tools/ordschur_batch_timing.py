@@ -16,7 +16,11 @@ median modulus are selected per problem (the stable half of a Floquet spectrum),
   --signed          the signed ComplexF64 family on the same shapes: Engine.zgpschur_batch decomposes complex bench_factors
                     under the alternating signature (T, F, T, F, ...) — a pencil sequence —, one Engine.zgordschur_batch_
                     call (psd_z_gordschur_batch) against the loop of Engine.ordschur_ (psd_z_gordschur) over the same
-                    problems, and the device-resident entry.
+                    problems, and the device-resident entry;
+  --signed-real     the signed Float64 family (family "dg") on the same shapes: Engine.dgpschur_batch decomposes real
+                    bench_factors under the alternating signature, one Engine.dgordschur_batch_ call
+                    (psd_d_gordschur_batch) against the loop of Engine.ordschur_ (psd_d_gordschur) over the same problems,
+                    and the device-resident entry.
 
 The second of two runs of each is reported.  One JSON line per shape on stdout; --json FILE collects them."""
 import argparse
@@ -47,8 +51,8 @@ def clones(pss):
 
 
 def entry(eng, family):
-    """(the in-place batched method, the name of its stats attribute) of a family: "d", "z" or "zg"."""
-    name = {"d": "ordschur_batch", "z": "zordschur_batch", "zg": "zgordschur_batch"}[family]
+    """(the in-place batched method, the name of its stats attribute) of a family: "d", "z", "zg" or "dg"."""
+    name = {"d": "ordschur_batch", "z": "zordschur_batch", "zg": "zgordschur_batch", "dg": "dgordschur_batch"}[family]
     return getattr(eng, name + "_"), name + "_stats"
 
 
@@ -85,7 +89,7 @@ def time_dev(eng, pss, sels, lr, family="d"):
     import torch
 
     fn, stats = entry(eng, family)
-    kw = dict(S=pss[0].S) if family == "zg" else {}
+    kw = dict(S=pss[0].S) if family in ("zg", "dg") else {}
 
     T0 = torch.from_numpy(np.array([[np.array(t) for t in ps.Ts] for ps in pss])).cuda().transpose(2, 3).contiguous().transpose(2, 3)
     Z0 = torch.from_numpy(np.array([[np.array(z) for z in ps.Z] for ps in pss])).cuda().transpose(2, 3).contiguous().transpose(2, 3)
@@ -109,6 +113,8 @@ def main():
     ap.add_argument("--loop-only", action="store_true")
     ap.add_argument("--complex", dest="cplx", action="store_true")
     ap.add_argument("--signed", action="store_true", help="signed ComplexF64 problems, alternating signature")
+    ap.add_argument("--signed-real", dest="signed_real", action="store_true",
+                    help="signed Float64 problems, alternating signature")
     ap.add_argument("--lib", default=None, help="library to load instead of the package's (a build of another commit)")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
@@ -122,9 +128,13 @@ def main():
 
     eng = psd_amd.Engine(0, libpath=args.lib)
     rows = []
-    family = "zg" if args.signed else "z" if args.cplx else "d"
+    family = "dg" if args.signed_real else "zg" if args.signed else "z" if args.cplx else "d"
     for (nb, n, p) in parse_shapes(args.shapes):
-        if args.signed:
+        if args.signed_real:
+            S = [q % 2 == 0 for q in range(p)]
+            pss = eng.dgpschur_batch([pt.bench_factors(n, p, seed=9000 + q) for q in range(nb)],
+                                     S[::-1] if args.lr == "L" else S, args.lr)
+        elif args.signed:
             S = [q % 2 == 0 for q in range(p)]
             pss = eng.zgpschur_batch([pt.bench_factors(n, p, seed=9000 + q, dtype=np.complex128) for q in range(nb)],
                                      S[::-1] if args.lr == "L" else S, args.lr)
@@ -133,7 +143,8 @@ def main():
         else:
             pss = eng.pschur_batch([pt.bench_factors(n, p, seed=9000 + q) for q in range(nb)], args.lr)
         sels = np.array([np.abs(ps.values) <= np.sort(np.abs(ps.values))[n // 2] for ps in pss])
-        row = dict(nb=nb, n=n, p=p, lr=args.lr, dtype="float64" if family == "d" else "complex128", signed=args.signed,
+        row = dict(nb=nb, n=n, p=p, lr=args.lr, dtype="float64" if family in ("d", "dg") else "complex128", family=family,
+                   signed=args.signed or args.signed_real,
                    loop=time_loop(eng, pss, sels))
         if not args.loop_only:
             row["batch"] = time_batch(eng, pss, sels, family)
