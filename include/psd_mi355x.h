@@ -786,6 +786,44 @@ int psd_z_geigvecs_batch_dev(psd_ctx* ctx, int nb, int n, int p, const double* d
                              char orient, int schurindex, const uint8_t* select, int shifted, double* dV, int maxvec,
                              double* a, int* nvec, int32_t* pcnt, psd_bevec_stats* stats, int* info);
 
+/* ---- dgeigvecs_batch: eigenvectors of many small signed Float64 periodic Schur forms in one call -------------------
+ * psd_d_geigvecs for nb generalized decompositions of one shape (n, p) and ONE signature, as psd_d_gpschur_batch /
+ * psd_d_gordschur_batch leave them: Float64, one orient and schurindex (any in 1..p, the quasi-triangular factor) for the
+ * whole batch; the conventions of psd_z_geigvecs_batch, with real T and Z.  Per problem the result contract is that of
+ * psd_d_geigvecs: columns top to bottom, a conjugate pair two columns (the partner and its scalars the exact
+ * conjugates); a_l = T_l(k, k) on a 1x1 row, sqrt|det B_l| on a pair, times e^(+-i arg lambda) at schurindex;
+ * ||V_1(:, j)|| = 1 with the largest-modulus entry real and positive; a zero or infinite eigenvalue gives a valid finite
+ * column (counted, never NaN), pivots below smin are replaced (counted), columns past 2^500 are rescaled by a power of
+ * two (counted).  A problem's vectors and scalars do not depend on its place in the batch or on the grouping (bit for
+ * bit).  A NULL or all-true S runs this path too, not psd_d_eigvecs_batch.  Up to order 128 the whole back-substitution
+ * of a group is one launch (psd_gbev_solve: several columns per wavefront for p <= 32, 1x1 and 2x2 row blocks side by
+ * side, the scalars uploaded with the tables) and a group makes four launches with shifted and p > 1, three otherwise,
+ * whatever nb and n are; the device entry makes one more for the whole call, the gather of the diagonals, sub- and
+ * super-diagonals (it defines the row blocks and the scalars); none when nothing is selected (stats->nlaunch).  Above,
+ * psd_d_geigvecs_dev's driver runs problem by problem on the slices of the batch buffers.  PSD_BATCH_GROUP acts as for
+ * psd_d_eigvecs_batch.
+ *
+ * T, Z: nb * p pointers to n x n column-major real matrices (problem-major, user order).  S: host [p] flags in user
+ * order, or NULL (all true).  select: host [nb][n], completed in place to whole conjugate pairs per problem, as
+ * psd_d_eigvecs_batch does; nvec[q] counts the completed row q, and a problem whose row is all false costs nothing.
+ * V: nb * nmat pointers to n x maxvec interleaved complex matrices, laid out as for psd_d_eigvecs_batch (the columns at
+ * and beyond nvec[q] zero); V = NULL is a size query (select completed, nvec filled).  a: host [nb][maxvec][p] complex
+ * interleaved — per problem column-major p x maxvec with ld p, as psd_d_geigvecs lays it out, the columns at and beyond
+ * nvec[q] zero — or NULL.  pcnt: host [nb][3] or NULL: perturbed pivots, rescaled columns, columns with a zero or
+ * infinite eigenvalue per problem; stats->nzero is the sum of the third.
+ * info: as psd_z_geigvecs_batch (-6 not used, -10 maxvec below the largest nvec, -11 nb < 0, -12 nvec NULL,
+ * PSD_INFO_NOTIMPL on a period-sharded context).  nb == 0 returns 0 and touches nothing. */
+int psd_d_geigvecs_batch(psd_ctx* ctx, int nb, int n, int p, double* const* T, double* const* Z, const uint8_t* S,
+                         char orient, int schurindex, uint8_t* select, int shifted, double* const* V, int maxvec,
+                         double* a, int* nvec, int32_t* pcnt, psd_bevec_stats* stats, int* info);
+/* Device-resident variant: dT, dZ device [nb][p][n][n] column-major blocks in user order (what psd_d_gpschur_batch_dev /
+ * psd_d_gordschur_batch_dev leave), dV a device block [nb][nmat][maxvec][n] of interleaved complex values.  S, select, a,
+ * nvec and pcnt are host arrays.  One gather kernel and one read-back for the whole batch define the row blocks and the
+ * scalars (no separate sub-diagonal kernel). */
+int psd_d_geigvecs_batch_dev(psd_ctx* ctx, int nb, int n, int p, const double* dT, const double* dZ, const uint8_t* S,
+                             char orient, int schurindex, uint8_t* select, int shifted, double* dV, int maxvec,
+                             double* a, int* nvec, int32_t* pcnt, psd_bevec_stats* stats, int* info);
+
 /* ---- ordschur_batch: reorder many small periodic Schur forms in one call ------------------------------------------
  * psd_d_ordschur (rordschur.jl:3-132) for nb decompositions of one shape (n, p), as psd_d_pschur_batch leaves them:
  * Float64, all-true signature, one orient and schurindex (1 or p) for the whole batch.  Per problem the result contract

@@ -601,8 +601,14 @@ end
 # ordschur_batch!.  Returns, per problem, (Vs, a) as geigvecs_device does; `select` is used as given; a zero or infinite
 # eigenvalue gives a valid column.  (Like the rest of this file it has not been executed: no Julia toolchain; the tested
 # mirror is Engine.zgeigvecs_batch.)
-function geigvecs_batch_device(problems::Vector{<:GeneralizedPeriodicSchur{ComplexF64}}, select::AbstractVector;
-                               shifted::Bool = true)
+#
+# The method for GeneralizedPeriodicSchur{Float64} (psd_d_geigvecs_batch) is the follow-up of the real gpschur_batch and
+# ordschur_batch!: T and Z stay real, `select` is completed to whole conjugate pairs per problem, a pair gives two
+# columns (the partner and its scalars the exact conjugates).  The two entries take the same arguments, so both methods
+# are made from one text.  (Not executed either; the tested mirror is Engine.dgeigvecs_batch.)
+for (Tv, entry) in ((ComplexF64, :psd_z_geigvecs_batch), (Float64, :psd_d_geigvecs_batch))
+@eval function geigvecs_batch_device(problems::Vector{<:GeneralizedPeriodicSchur{$Tv}}, select::AbstractVector;
+                                     shifted::Bool = true)
     nb = length(problems)
     nb == 0 && return Tuple{Vector{Matrix{ComplexF64}}, Matrix{ComplexF64}}[]
     ps1 = problems[1]
@@ -624,12 +630,12 @@ function geigvecs_batch_device(problems::Vector{<:GeneralizedPeriodicSchur{Compl
     nvec = zeros(Cint, nb); info = Ref{Cint}(0)
     Tp = _ptrs(T); Zp = _ptrs(Z)
     nmat = shifted ? p : 1
-    call(Vp, maxvec, a) = ccall((:psd_z_geigvecs_batch, libpsd), Cint,
+    call(Vp, maxvec, a) = ccall(($(QuoteNode(entry)), libpsd), Cint,
         (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ptr{UInt8}, Cchar, Cint, Ptr{UInt8}, Cint,
          Ptr{Ptr{ComplexF64}}, Cint, Ptr{ComplexF64}, Ptr{Cint}, Ptr{Int32}, Ptr{Cvoid}, Ref{Cint}),
         ctx().ptr, nb, n, p, Tp, Zp, S, orient, js, sel, shifted, Vp, maxvec, a, nvec, C_NULL, C_NULL, info)
     GC.@preserve T Z S sel nvec begin
-        call(C_NULL, 0, C_NULL)                           # size query: nvec
+        call(C_NULL, 0, C_NULL)                           # size query: nvec (Float64: select completed)
         info[] != 0 && _throw(info[])
         maxvec = Int(maximum(nvec))
         V = [zeros(ComplexF64, n, maxvec) for _ in 1:(nb * nmat)]
@@ -641,6 +647,7 @@ function geigvecs_batch_device(problems::Vector{<:GeneralizedPeriodicSchur{Compl
         info[] != 0 && _throw(info[])
         return [([V[(q - 1) * nmat + l][:, 1:nvec[q]] for l in 1:nmat], a[:, 1:nvec[q], q]) for q in 1:nb]
     end
+end
 end
 
 # pschur!(A, lr; ...), ComplexF64 — PSD.jl:1106-1111 (the all-true signature of generalized.jl:108-137)

@@ -394,9 +394,9 @@ class Engine:
                 sigs[f"psd_{t}_eigvecs_batch{dev}"] = (head + [mats, mats] + eig + [C.c_char, C.c_int, u8p, C.c_int, mats,
                                                                                     C.c_int, ip, i32p,
                                                                                     C.POINTER(BevecStats), ip])
-                if t == "z":  # (no eigenvalue arguments: the signature, and the scalars a behind maxvec)
-                    sigs[f"psd_z_geigvecs_batch{dev}"] = (head + [mats, mats, u8p, C.c_char, C.c_int, u8p, C.c_int, mats,
-                                                                  C.c_int, dp, ip, i32p, C.POINTER(BevecStats), ip])
+                # (no eigenvalue arguments: the signature, and the scalars a behind maxvec)
+                sigs[f"psd_{t}_geigvecs_batch{dev}"] = (head + [mats, mats, u8p, C.c_char, C.c_int, u8p, C.c_int, mats,
+                                                                C.c_int, dp, ip, i32p, C.POINTER(BevecStats), ip])
             for nm, sig in sigs.items():
                 if hasattr(lib, nm):  # (tools load builds of earlier commits to time their single calls)
                     getattr(lib, nm).argtypes = sig
@@ -1446,8 +1446,8 @@ class Engine:
                 raise ValueError("eigvecs requires Schur vectors in the PSD")  # vectors.jl:30-32
             cT, cZ = [np.iscomplexobj(t) for t in ps.Ts], [np.iscomplexobj(z) for z in ps.Z]
             if needZ:  # eigvecs: factors and vectors of different kinds are the error of the single call
-                other = any(cT) if fam is _D else not any(cT + cZ)
-                mixed = any(cZ) if fam is _D else not all(cT + cZ)
+                other = any(cT) if fam.dtype is np.float64 else not any(cT + cZ)
+                mixed = any(cZ) if fam.dtype is np.float64 else not all(cT + cZ)
             else:  # ordschur: real vectors beside complex factors are left to the in-place contract
                 other = any(cT + cZ) if fam.dtype is np.float64 else not all(cT)
                 mixed = False
@@ -1896,16 +1896,17 @@ class Engine:
             self.eigvecs_batch_counts = cnts
         return nvec
 
-    def _geigvecs_batch_call(self, dev, nb, n, p, T, Z, S, orient, si, sel, shifted, V=None, maxvec=0):
-        """One call of psd_z_geigvecs_batch[_dev] on packed factors (T, Z, V: ctypes arguments; S: the signature, a list
-        of p flags).  Without V the size query; with V the stats and counters of the call are left in
-        self.eigvecs_batch_*.  Returns nvec and the scalars a [nb, maxvec, p] (None without V)."""
+    def _geigvecs_batch_call(self, fam, dev, nb, n, p, T, Z, S, orient, si, sel, shifted, V=None, maxvec=0):
+        """One call of psd_?_geigvecs_batch[_dev] on packed factors (T, Z, V: ctypes arguments; S: the signature, a list
+        of p flags).  Without V the size query (the Float64 entry completes `sel` to whole pairs); with V the stats and
+        counters of the call are left in self.eigvecs_batch_*.  Returns nvec and the scalars a [nb, maxvec, p] (None
+        without V)."""
         nvec = (C.c_int * nb)()
         cnts = np.zeros((nb, 3), dtype=np.int32)
         st = BevecStats()
         info = C.c_int(0)
         a = None if V is None else np.zeros((nb, maxvec, p), dtype=np.complex128)
-        fn = getattr(self.lib, f"psd_z_geigvecs_batch{'_dev' if dev else ''}")
+        fn = getattr(self.lib, f"psd_{fam.tag}_geigvecs_batch{'_dev' if dev else ''}")
         fn(self.ctx, nb, n, p, T, Z, (C.c_uint8 * p)(*[1 if x else 0 for x in S]), orient.encode(), int(si),
            sel.ctypes.data_as(C.POINTER(C.c_uint8)), int(bool(shifted)), V, maxvec,
            None if a is None else a.ctypes.data_as(C.POINTER(C.c_double)), nvec,
@@ -2015,6 +2016,60 @@ class Engine:
         wrong = TypeError("zeigvecs_batch: ComplexF64 only (Float64 problems: eigvecs_batch)")
         return self._eigvecs_batch(_Z, "zeigvecs_batch", wrong, problems, args, shifted, lr, schurindex)
 
+    def _geigvecs_batch(self, fam, name, wrong, problems, args, shifted, lr, schurindex, S):
+        """zgeigvecs_batch / dgeigvecs_batch."""
+        nmat_of = lambda p: p if shifted else 1  # noqa: E731
+        if hasattr(problems, "data_ptr"):
+            if len(args) != 2:
+                raise TypeError(f"{name}(T, Z, select, S=..., lr=..., schurindex=...)")
+            import torch
+
+            T, Z, select = problems, args[0], args[1]
+            if Z is None:
+                raise ValueError("geigvecs requires Schur vectors in the PSD")
+            nb, p, n = self._dev_batch(fam, name, wrong, T, Z, mixed=True)
+            S = [True] * p if S is None else [bool(x) for x in S]
+            if len(S) != p:
+                raise DimensionMismatch("length of S must match the period")
+            nmat = nmat_of(p)
+            if nb == 0:
+                self.eigvecs_batch_stats = BevecStats()
+                self.eigvecs_batch_counts = np.zeros((0, 3), dtype=np.int32)
+                return (torch.zeros((0, nmat, n, 0), dtype=torch.complex128, device=T.device),
+                        np.zeros((0, p, 0), dtype=np.complex128), np.zeros(0, dtype=np.int32))
+            sel = self._batch_select(select, nb, n)
+            dT, dZ = _dev_blocks(T, fam, "readonly"), _dev_blocks(Z, fam, "readonly")
+            call = (fam, True, nb, n, p, C.c_void_p(dT.data_ptr()), C.c_void_p(dZ.data_ptr()), S, char_lr(lr), schurindex,
+                    sel, shifted)
+            torch.cuda.synchronize(T.device)
+            maxvec = max(self._geigvecs_batch_call(*call)[0])
+            dV = torch.empty((nb, nmat, max(maxvec, 1), n), dtype=torch.complex128, device=T.device)
+            if maxvec == 0:
+                dV.zero_()
+            torch.cuda.synchronize(T.device)
+            nvec, a = self._geigvecs_batch_call(*call, C.c_void_p(dV.data_ptr()), max(maxvec, 1))
+            return (dV[:, :, :maxvec, :].transpose(2, 3), np.ascontiguousarray(a[:, :maxvec, :].transpose(0, 2, 1)),
+                    np.array(list(nvec), dtype=np.int32))
+        if len(args) != 1:
+            raise TypeError(f"{name}(problems, select, shifted=True)")
+        problems = list(problems)
+        nb = len(problems)
+        if nb == 0:
+            self.eigvecs_batch_stats = BevecStats()
+            self.eigvecs_batch_counts = np.zeros((0, 3), dtype=np.int32)
+            return []
+        n, p, orient, si, Ts, Zs, S = self._batch_decomps(fam, name, wrong, problems, needZ=True, work=False, signed=True)
+        if len(S) != p:
+            raise DimensionMismatch("length of S must match the period")
+        sel = self._batch_select(args[0], nb, n)
+        call = (fam, False, nb, n, p, self._ptrs(Ts), self._ptrs(Zs), S, orient, si, sel, shifted)
+        maxvec = max(self._geigvecs_batch_call(*call)[0])
+        nmat = nmat_of(p)
+        Vs = [np.zeros((n, maxvec), dtype=np.complex128, order="F") for _ in range(nb * nmat)]
+        nvec, a = self._geigvecs_batch_call(*call, self._ptrs(Vs), maxvec)
+        return [([np.asfortranarray(Vs[q * nmat + l][:, :nvec[q]]) for l in range(nmat)],
+                 np.asfortranarray(a[q, :nvec[q], :].T)) for q in range(nb)]
+
     def zgeigvecs_batch(self, problems, *args, shifted=True, lr="R", schurindex=1, S=None):
         """geigvecs(P, select; shifted) for MANY small signed ComplexF64 decompositions of one shape and ONE signature in
         ONE call (psd_z_geigvecs_batch): the follow-up of zgpschur_batch / gpschur_batch and zgordschur_batch_, the signed
@@ -2034,58 +2089,31 @@ class Engine:
         costs nothing and gets no columns.  Stats and counters (perturbed pivots, rescaled columns, columns with a zero
         or infinite eigenvalue) are left in `self.eigvecs_batch_stats` and `self.eigvecs_batch_counts`."""
         wrong = TypeError("zgeigvecs_batch: ComplexF64 only (use geigvecs per problem for a Float64 decomposition)")
-        nmat_of = lambda p: p if shifted else 1  # noqa: E731
-        if hasattr(problems, "data_ptr"):
-            if len(args) != 2:
-                raise TypeError("zgeigvecs_batch(T, Z, select, S=..., lr=..., schurindex=...)")
-            import torch
+        return self._geigvecs_batch(_Z, "zgeigvecs_batch", wrong, problems, args, shifted, lr, schurindex, S)
 
-            T, Z, select = problems, args[0], args[1]
-            if Z is None:
-                raise ValueError("geigvecs requires Schur vectors in the PSD")
-            nb, p, n = self._dev_batch(_Z, "zgeigvecs_batch", wrong, T, Z, mixed=True)
-            S = [True] * p if S is None else [bool(x) for x in S]
-            if len(S) != p:
-                raise DimensionMismatch("length of S must match the period")
-            nmat = nmat_of(p)
-            if nb == 0:
-                self.eigvecs_batch_stats = BevecStats()
-                self.eigvecs_batch_counts = np.zeros((0, 3), dtype=np.int32)
-                return (torch.zeros((0, nmat, n, 0), dtype=torch.complex128, device=T.device),
-                        np.zeros((0, p, 0), dtype=np.complex128), np.zeros(0, dtype=np.int32))
-            sel = self._batch_select(select, nb, n)
-            dT, dZ = _dev_blocks(T, _Z, "readonly"), _dev_blocks(Z, _Z, "readonly")
-            call = (True, nb, n, p, C.c_void_p(dT.data_ptr()), C.c_void_p(dZ.data_ptr()), S, char_lr(lr), schurindex, sel,
-                    shifted)
-            torch.cuda.synchronize(T.device)
-            maxvec = max(self._geigvecs_batch_call(*call)[0])
-            dV = torch.empty((nb, nmat, max(maxvec, 1), n), dtype=torch.complex128, device=T.device)
-            if maxvec == 0:
-                dV.zero_()
-            torch.cuda.synchronize(T.device)
-            nvec, a = self._geigvecs_batch_call(*call, C.c_void_p(dV.data_ptr()), max(maxvec, 1))
-            return (dV[:, :, :maxvec, :].transpose(2, 3), np.ascontiguousarray(a[:, :maxvec, :].transpose(0, 2, 1)),
-                    np.array(list(nvec), dtype=np.int32))
-        if len(args) != 1:
-            raise TypeError("zgeigvecs_batch(problems, select, shifted=True)")
-        problems = list(problems)
-        nb = len(problems)
-        if nb == 0:
-            self.eigvecs_batch_stats = BevecStats()
-            self.eigvecs_batch_counts = np.zeros((0, 3), dtype=np.int32)
-            return []
-        n, p, orient, si, Ts, Zs, S = self._batch_decomps(_Z, "zgeigvecs_batch", wrong, problems, needZ=True, work=False,
-                                                          signed=True)
-        if len(S) != p:
-            raise DimensionMismatch("length of S must match the period")
-        sel = self._batch_select(args[0], nb, n)
-        call = (False, nb, n, p, self._ptrs(Ts), self._ptrs(Zs), S, orient, si, sel, shifted)
-        maxvec = max(self._geigvecs_batch_call(*call)[0])
-        nmat = nmat_of(p)
-        Vs = [np.zeros((n, maxvec), dtype=np.complex128, order="F") for _ in range(nb * nmat)]
-        nvec, a = self._geigvecs_batch_call(*call, self._ptrs(Vs), maxvec)
-        return [([np.asfortranarray(Vs[q * nmat + l][:, :nvec[q]]) for l in range(nmat)],
-                 np.asfortranarray(a[q, :nvec[q], :].T)) for q in range(nb)]
+    def dgeigvecs_batch(self, problems, *args, shifted=True, lr="R", schurindex=1, S=None):
+        """geigvecs(P, select; shifted) for MANY small signed Float64 decompositions of one shape and ONE signature in
+        ONE call (psd_d_geigvecs_batch): the follow-up of dgpschur_batch / gpschur_batch(..., real=True) and
+        dgordschur_batch_, the real counterpart of zgeigvecs_batch.  T and Z stay real: the quasi-triangular factor keeps
+        its 2x2 blocks, a conjugate pair gives two columns (the partner and its scalars the exact conjugates).  Per
+        problem the result contract is that of `geigvecs` — a_l = T_l[k, k] on a 1x1 row, sqrt|det B_l| on a pair (times
+        e^(+-i arg lambda) at schurindex), a zero or infinite eigenvalue a valid finite column — and a problem's vectors
+        and scalars do not depend on its place in the batch.  An all-true signature runs this path too.
+
+        dgeigvecs_batch(problems, select, shifted=True): `problems` a list of real GeneralizedPeriodicSchur of equal
+        order, period, orientation, schurindex and S (real PeriodicSchur count as all true); returns a list of (Vs, a),
+        each what geigvecs(P, select) returns.
+        dgeigvecs_batch(T, Z, select, S=..., lr=..., schurindex=..., shifted=True): the torch outputs of the
+        device-resident dgpschur_batch_ / dgordschur_batch_ ([nb, p, n, n] float64 tensors) and the signature of that
+        call (None: all true); returns (V, a, nvec) shaped as zgeigvecs_batch returns them (V complex128
+        [nb, nmat, n, maxvec], a [nb, p, maxvec]); nvec counts completed pairs.
+
+        `select`: [nb][n] flags, or one [n] row used for every problem, completed to whole conjugate pairs per problem.
+        A problem whose row is all false costs nothing and gets no columns.  Stats and counters (perturbed pivots,
+        rescaled columns, columns with a zero or infinite eigenvalue) are left in `self.eigvecs_batch_stats` and
+        `self.eigvecs_batch_counts`."""
+        wrong = TypeError("dgeigvecs_batch: Float64 only (ComplexF64 problems: zgeigvecs_batch)")
+        return self._geigvecs_batch(_DG, "dgeigvecs_batch", wrong, problems, args, shifted, lr, schurindex, S)
 
 
     def geigvecs(self, P, select, shifted=True):

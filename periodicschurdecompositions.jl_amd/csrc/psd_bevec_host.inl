@@ -7,9 +7,9 @@
 // the other factors — four launches whatever nb and n are — and one read-back of the counters.  Orders above
 // PSD_BEV_NMAX run eigvecs_dev problem by problem on the slices of the batch buffers.
 //
-// The complex and signed drivers (psd_zbevec_host.inl, psd_zgbevec_host.inl) come in behind this file and share the
-// argument checks, the call description, bevec_launch, the single-path loop, the statistics and the bodies of the two
-// kinds of entry (bevec_entry_dev, bevec_entry_host).
+// The complex and signed drivers (psd_zbevec_host.inl, psd_zgbevec_host.inl, psd_gbevec_host.inl) come in behind this
+// file and share the argument checks, the call description, bevec_itab, bevec_launch, the single-path loop, the
+// statistics and the bodies of the two kinds of entry (bevec_entry_dev, bevec_entry_host).
 
 namespace {
 
@@ -43,9 +43,11 @@ struct bevec_call {
 
 // The device part of a group, for both families (CPLX: the kernels of psd_zbevec.h): the tables of gc problems (itab, dtab,
 // the units behind them) go up, then the solve, the back-transformation of V_1, its norms and phases, the other factors,
-// and one read-back of the counters into cnt3 [gc][3].  sgn (complex only): the senses of the working factors of a signed
-// batch — psd_zgbev_solve (psd_zgbevec.h) is the solve then, there are no doubles to upload (dtab is empty), and the third
-// counter is the columns with a zero scalar, from flags of their own behind the counters (no NaN columns)
+// and one read-back of the counters into cnt3 [gc][3].  sgn: the senses of the working factors of a signed batch.  Complex:
+// psd_zgbev_solve (psd_zgbevec.h) is the solve then, there are no doubles to upload (dtab is empty), and the third
+// counter is the columns with a zero scalar, from flags of their own behind the counters (no NaN columns).  Real:
+// psd_gbev_solve (psd_gbevec.h), dtab the scalars of the solve columns; the third counter stays zero here (the caller
+// counts the zero scalars on the host)
 template <bool CPLX>
 int bevec_launch(const bevec_call& k, int gc, const double* dT, const double* dZ, std::vector<int>& itab,
                  const std::vector<double>& dtab, const std::vector<int>& units, int nsm, double* dV, int32_t* cnt3,
@@ -61,7 +63,7 @@ int bevec_launch(const bevec_call& k, int gc, const double* dT, const double* dZ
     itab.insert(itab.end(), units.begin(), units.end());
     const size_t isgn = itab.size();
     if (sgn) itab.insert(itab.end(), sgn, sgn + p);
-    const size_t ncnt = 3 * (size_t)gc * n, nflag = sgn ? (size_t)gc * n : 0;
+    const size_t ncnt = 3 * (size_t)gc * n, nflag = sgn && CPLX ? (size_t)gc * n : 0;
     psd_batchbuf bI, bD, bX, bR, bS, bC;
     PSD_CHECK(bI.alloc(sizeof(int) * itab.size()));
     if (!dtab.empty()) PSD_CHECK(bD.alloc(sizeof(double) * dtab.size()));
@@ -78,7 +80,11 @@ int bevec_launch(const bevec_call& k, int gc, const double* dT, const double* dZ
     a.T = dT; a.itab = (const int*)bI.ptr; a.dtab = bD.d(); a.X = bX.d(); a.R = bR.d(); a.cnt = (int*)bC.ptr;
     a.n = n; a.p = p; a.nsm = nsm; a.nunits = nunits; a.gc = gc; a.six = k.six;
     const int C = 64 / psd_bev_lw(p);
-    if (sgn) {
+    if (sgn && !CPLX) {
+        psd_gbev_args ga;
+        ga.b = a; ga.sgn = (const int*)bI.ptr + isgn;
+        PSD_LAUNCH(psd_gbev_solve, psd_dim3((nunits + C - 1) / C), 64, PSD_GBEV_LDS, c->stream, ga);
+    } else if (sgn) {
         psd_zgbev_args ga;
         ga.b = a; ga.sgn = (const int*)bI.ptr + isgn; ga.zc = (int*)bC.ptr + ncnt;
         PSD_LAUNCH(psd_zgbev_solve, psd_dim3((nunits + C - 1) / C), 64, PSD_ZGBEV_LDS, c->stream, ga);
@@ -113,19 +119,21 @@ int bevec_launch(const bevec_call& k, int gc, const double* dT, const double* dZ
             const int* e = cnt.data() + 3 * ((size_t)q * n + j);
             cnt3[3 * q] += e[0];
             cnt3[3 * q + 1] += e[1] > 0;
-            cnt3[3 * q + 2] += sgn ? cnt[ncnt + (size_t)q * n + j] : e[2];
+            cnt3[3 * q + 2] += nflag ? cnt[ncnt + (size_t)q * n + j] : e[2];
         }
     return 0;
 }
 
-// gc problems resident on the device (dT, dZ [gc][p][n][n], dV [gc][nmat][maxvec][n] complex), their eigenvalues, completed
-// selections and row blocks; cnt3 [gc][3] receives the counters per problem
-int bevec_group(const bevec_call& k, int gc, const double* dT, const double* dZ, const double* wr, const double* wi,
-                const uint8_t* select, const int* bsz, double* dV, int32_t* cnt3, psd_bevec_stats* st) {
+// The integer tables of gc real problems from their completed selections and row blocks (itab, and the units): one solve
+// column per selected block.  col(q, ns, i): solve column ns of problem q stands on the block at row i (the doubles of the
+// family).  Returns the largest number of solve columns of a problem.
+template <class Col>
+int bevec_itab(const bevec_call& k, int gc, const uint8_t* select, const int* bsz, std::vector<int>& itab,
+               std::vector<int>& units, Col col) {
     const int n = k.n, p = k.p;
-    const int IS = psd_bev_istride(n), IH = psd_bev_ihead(p), DS = psd_bev_dstride(n);
-    std::vector<int> itab((size_t)IH + (size_t)gc * IS, 0), units;
-    std::vector<double> dtab((size_t)gc * DS, 0.0);
+    const int IS = psd_bev_istride(n), IH = psd_bev_ihead(p);
+    itab.assign((size_t)IH + (size_t)gc * IS, 0);
+    units.clear();
     for (int j = 0; j < p; ++j) {  // working form (left orientation), as eigvecs_dev
         itab[j] = k.left ? j : p - 1 - j;
         itab[p + j] = k.left ? j : (p - j) % p;
@@ -133,37 +141,51 @@ int bevec_group(const bevec_call& k, int gc, const double* dT, const double* dZ,
     int nsm = 0;
     for (int q = 0; q < gc; ++q) {
         int* tab = itab.data() + IH + (size_t)q * IS;
-        double* dt = dtab.data() + (size_t)q * DS;
         const int* b = bsz + (size_t)q * n;
         const uint8_t* s = select + (size_t)q * n;
         int ns = 0, nvec = 0, nblk = 0;
         for (int i = 0; i < n; i += b[i]) {
             ++nblk;
             if (!s[i]) continue;
-            const std::complex<double> l(wr[(size_t)q * n + i], wi[(size_t)q * n + i]), u = psd_ev_root(l, p);
             tab[n + ns] = i;
             tab[2 * n + ns] = b[i];
             tab[3 * n + ns] = i + b[i];
             tab[4 * n + ns] = nvec;
             tab[5 * n + ns] = b[i] == 2;
             tab[6 * n + ns] = nblk;
-            dt[2 * ns] = u.real();
-            dt[2 * ns + 1] = u.imag();
-            dt[2 * n + 2 * ns] = l.real();
-            dt[2 * n + 2 * ns + 1] = l.imag();
+            col(q, ns, i);
             units.push_back(q);
             units.push_back(ns);
             nvec += b[i];
             ++ns;
         }
-        for (int i = 0; i < n; ++i) {
-            tab[i] = b[i];
-            dt[4 * n + 2 * i] = wr[(size_t)q * n + i];
-            dt[4 * n + 2 * i + 1] = wi[(size_t)q * n + i];
-        }
+        for (int i = 0; i < n; ++i) tab[i] = b[i];
         tab[7 * n] = ns;
         nsm = ns > nsm ? ns : nsm;
     }
+    return nsm;
+}
+
+// gc problems resident on the device (dT, dZ [gc][p][n][n], dV [gc][nmat][maxvec][n] complex), their eigenvalues, completed
+// selections and row blocks; cnt3 [gc][3] receives the counters per problem
+int bevec_group(const bevec_call& k, int gc, const double* dT, const double* dZ, const double* wr, const double* wi,
+                const uint8_t* select, const int* bsz, double* dV, int32_t* cnt3, psd_bevec_stats* st) {
+    const int n = k.n, p = k.p, DS = psd_bev_dstride(n);
+    std::vector<int> itab, units;
+    std::vector<double> dtab((size_t)gc * DS, 0.0);
+    const int nsm = bevec_itab(k, gc, select, bsz, itab, units, [&](int q, int ns, int i) {
+        double* dt = dtab.data() + (size_t)q * DS;
+        const std::complex<double> l(wr[(size_t)q * n + i], wi[(size_t)q * n + i]), u = psd_ev_root(l, p);
+        dt[2 * ns] = u.real();
+        dt[2 * ns + 1] = u.imag();
+        dt[2 * n + 2 * ns] = l.real();
+        dt[2 * n + 2 * ns + 1] = l.imag();
+    });
+    for (int q = 0; q < gc; ++q)
+        for (int i = 0; i < n; ++i) {
+            dtab[(size_t)q * DS + 4 * n + 2 * i] = wr[(size_t)q * n + i];
+            dtab[(size_t)q * DS + 4 * n + 2 * i + 1] = wi[(size_t)q * n + i];
+        }
     return bevec_launch<false>(k, gc, dT, dZ, itab, dtab, units, nsm, dV, cnt3, st);
 }
 

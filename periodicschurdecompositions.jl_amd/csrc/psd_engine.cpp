@@ -25,6 +25,7 @@
 #include "psd_bevec.h"
 #include "psd_zbevec.h"
 #include "psd_zgbevec.h"
+#include "psd_gbevec.h"
 #include "psd_bord.h"
 #include "psd_zbqz.h"
 #include "psd_zgbqz.h"
@@ -3960,6 +3961,7 @@ extern "C" int psd_dbg_apply_bench(psd_ctx* c, int n, int p, int nwin, int W, in
 #include "psd_bevec_host.inl"
 #include "psd_zbevec_host.inl"
 #include "psd_zgbevec_host.inl"
+#include "psd_gbevec_host.inl"
 #include "psd_bord_host.inl"
 #include "psd_zbord_host.inl"
 #include "psd_zgbord_host.inl"

@@ -86,7 +86,8 @@ PSD_HD psd_gm<B> psd_gm_compose(const psd_gm<B>& m2, const psd_gm<B>& m1) {
 
 // What a map takes from its column beside the factors' entries — the scalar a_l, the sense of working factor l and the
 // update product r_l(row) — as the single path keeps them: a in the uploaded table, r in the GEMM's R buffer.  (The
-// batched path, psd_zgbevec.h, reads a from the factors and keeps r in LDS: its own source type.)
+// batched paths have source types of their own: psd_zgbevec.h reads a from the factors, psd_gbevec.h from its tables,
+// and both keep r in LDS.)
 template <bool CPLX>
 struct psd_gev_src {
     const psd_gev_args& g;
@@ -214,6 +215,22 @@ PSD_D void psd_gev_lane(const SRC& g, const psd_ev_col<CPLX>& col, const psd_gm<
     }
 }
 
+// y_0 of the own 2x2 block of a conjugate pair from the total map round the period (the last entry of the column's
+// forward scan): the null vector of C - A, (N01, -N00) or (N11, -N10), scaled to a largest entry in [1, 2)
+template <int B>
+PSD_HD void psd_gev_null(const psd_gm<B>& tot, psd_z y0[2]) {
+    psd_z N[2][2];
+    for (int q = 0; q < 2; ++q)
+        for (int k = 0; k < 2; ++k) N[q][k] = zsub(tot.A[q % B][k % B], q == k ? tot.c : zmk(0.0, 0.0));
+    const bool first = zabs2(N[0][1]) + zabs2(N[0][0]) >= zabs2(N[1][1]) + zabs2(N[1][0]);
+    y0[0] = first ? N[0][1] : N[1][1];
+    y0[1] = first ? zneg(N[0][0]) : zneg(N[1][0]);
+    if (ziszero(y0[0]) && ziszero(y0[1])) y0[0] = zmk(1.0, 0.0);
+    const double s = ldexp(1.0, -psd_gev_ilogb(zabs1(y0[0]) > zabs1(y0[1]) ? y0[0] : y0[1]));
+    y0[0] = zscal(s, y0[0]);
+    y0[1] = zscal(s, y0[1]);
+}
+
 #define PSD_GEV_LDS (4 * 64 * sizeof(psd_gm<2>) + 64 * sizeof(int))
 
 // One row block (i, B) of column col.j; rows >= i1 of the chunk are done.
@@ -262,19 +279,7 @@ PSD_D void psd_gev_row(const psd_gev_args& g, const psd_ev_col<CPLX>& col, char*
     const psd_gm<B>* inc = F + 64 * cur;
     const psd_gm<B>* suf = Sf + 64 * cur;
     psd_z y0[2] = {zmk(1.0, 0.0), zmk(0.0, 0.0)};
-    if (own && B == 2) {  // the null vector of C - A round the period: (N01, -N00) or (N11, -N10)
-        const psd_gm<B>& tot = inc[63];
-        psd_z N[2][2];
-        for (int q = 0; q < 2; ++q)
-            for (int k = 0; k < 2; ++k) N[q][k] = zsub(tot.A[q % B][k % B], q == k ? tot.c : zmk(0.0, 0.0));
-        const bool first = zabs2(N[0][1]) + zabs2(N[0][0]) >= zabs2(N[1][1]) + zabs2(N[1][0]);
-        y0[0] = first ? N[0][1] : N[1][1];
-        y0[1] = first ? zneg(N[0][0]) : zneg(N[1][0]);
-        if (ziszero(y0[0]) && ziszero(y0[1])) y0[0] = zmk(1.0, 0.0);
-        const double s = ldexp(1.0, -psd_gev_ilogb(zabs1(y0[0]) > zabs1(y0[1]) ? y0[0] : y0[1]));
-        y0[0] = zscal(s, y0[0]);
-        y0[1] = zscal(s, y0[1]);
-    }
+    if (own && B == 2) psd_gev_null(inc[63], y0);
     // the largest entry y_l(I) will have: a column growing past 2^PSD_EV_BIG is scaled down first
     PSD_PAR_FOR(t, 64) {
         int mx, np;

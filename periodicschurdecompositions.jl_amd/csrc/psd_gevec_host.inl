@@ -36,6 +36,65 @@ int gev_gather(psd_ctx* c, int n, int p, const double* dT, double* const* hT, st
     return 0;
 }
 
+// The scalars a_l (user order, au [p]) of the solve column whose own block is the b rows from k.  dg(l, i, q): T_l(i, i),
+// T_l(i + 1, i), T_l(i, i + 1) for q = 0, 1, 2; si: schurindex - 1; wmap, sgn: the working form.  A 1x1 block: the
+// diagonal entries; returns whether one of them is zero (a zero or infinite eigenvalue).  A pair: sqrt|det B_l|, times
+// e^(i arg lambda) at schurindex (e^(-i arg lambda) if that factor is inverted: the signed product is lambda).
+template <class DG>
+bool gev_scalars(int p, int si, const uint8_t* S, const int* wmap, const int* sgn, int k, int b, DG dg,
+                 std::complex<double>* au) {
+    using cd = std::complex<double>;
+    if (b == 1) {
+        bool z = false;
+        for (int l = 0; l < p; ++l) {
+            au[l] = dg(l, k, 0);
+            z = z || dg(l, k, 0) == 0.0;
+        }
+        return z;
+    }
+    auto blk = [&](int l, double B[2][2]) {
+        B[0][0] = dg(l, k, 0).real();
+        B[0][1] = dg(l, k, 2).real();
+        B[1][0] = l == si ? dg(l, k, 1).real() : 0.0;
+        B[1][1] = dg(l, k + 1, 0).real();
+    };
+    // lambda of the first member (positive imaginary part) from the working product, renormalised at each step
+    double M[2][2] = {{1.0, 0.0}, {0.0, 1.0}};
+    for (int w = 0; w < p; ++w) {
+        double B[2][2], F[2][2], R[2][2];
+        blk(wmap[w], B);
+        if (sgn[w]) {
+            memcpy(F, B, sizeof(F));
+        } else {
+            F[0][0] = B[1][1];
+            F[0][1] = -B[0][1];
+            F[1][0] = -B[1][0];
+            F[1][1] = B[0][0];  // adj(B), made a positive multiple of B^-1 (the argument of lambda is all we need)
+            const double d = B[0][0] * B[1][1] - B[0][1] * B[1][0];
+            if (d < 0)
+                for (auto& r : F)
+                    for (auto& v : r) v = -v;
+        }
+        double mx = 0.0;
+        for (int q = 0; q < 2; ++q)
+            for (int r = 0; r < 2; ++r) {
+                R[q][r] = F[q][0] * M[0][r] + F[q][1] * M[1][r];
+                mx = fmax(mx, fabs(R[q][r]));
+            }
+        for (int q = 0; q < 2; ++q)
+            for (int r = 0; r < 2; ++r) M[q][r] = mx > 0.0 ? R[q][r] / mx : R[q][r];
+    }
+    const double h = 0.5 * (M[0][0] + M[1][1]), det = M[0][0] * M[1][1] - M[0][1] * M[1][0];
+    const double th = atan2(sqrt(fmax(det - h * h, 0.0)), h);
+    for (int l = 0; l < p; ++l) {
+        double B[2][2];
+        blk(l, B);
+        const double r = sqrt(fabs(B[0][0] * B[1][1] - B[0][1] * B[1][0]));
+        au[l] = l == si ? std::polar(r, (S && !S[si]) ? -th : th) : cd(r, 0.0);
+    }
+    return false;
+}
+
 // dT, dZ: [p][n][n] device blocks in user order; hT: host copies of the factors, or nullptr (read from dT); S: NULL or
 // the user's signature; select completed in place; dV as eigvecs_dev; aout: p x maxvec complex (ld p), or nullptr.
 template <bool CPLX>
@@ -89,62 +148,11 @@ int geigvecs_dev(psd_ctx* c, int n, int p, const double* dT, double* const* hT, 
         bmap[j] = sgn[j] ? j : (j + 1) % p;  // an inverted factor's update reads X_{j+1}
     }
     const int six = left ? si : p - schurindex;
-    // the scalars a_l (user order) of every solve column; the pairs: sqrt|det B_l|, times e^(i arg lambda) at schurindex
-    // (e^(-i arg lambda) if that factor is inverted: the signed product is lambda)
+    // the scalars a_l (user order) of every solve column
     std::vector<cd> au((size_t)p * ns);
     int nzero = 0;
-    for (int j = 0; j < ns; ++j) {
-        const int k = k0[j];
-        if (m[j] == 1) {
-            bool z = false;
-            for (int l = 0; l < p; ++l) {
-                au[(size_t)j * p + l] = dg(l, k, 0);
-                z = z || dg(l, k, 0) == 0.0;
-            }
-            nzero += z;
-            continue;
-        }
-        auto blk = [&](int l, double B[2][2]) {
-            B[0][0] = dg(l, k, 0).real();
-            B[0][1] = dg(l, k, 2).real();
-            B[1][0] = l == si ? dg(l, k, 1).real() : 0.0;
-            B[1][1] = dg(l, k + 1, 0).real();
-        };
-        // lambda of the first member (positive imaginary part) from the working product, renormalised at each step
-        double M[2][2] = {{1.0, 0.0}, {0.0, 1.0}};
-        for (int w = 0; w < p; ++w) {
-            double B[2][2], F[2][2], R[2][2];
-            blk(wmap[w], B);
-            if (sgn[w]) {
-                memcpy(F, B, sizeof(F));
-            } else {
-                F[0][0] = B[1][1];
-                F[0][1] = -B[0][1];
-                F[1][0] = -B[1][0];
-                F[1][1] = B[0][0];  // adj(B), made a positive multiple of B^-1 (the argument of lambda is all we need)
-                const double d = B[0][0] * B[1][1] - B[0][1] * B[1][0];
-                if (d < 0)
-                    for (auto& r : F)
-                        for (auto& v : r) v = -v;
-            }
-            double mx = 0.0;
-            for (int q = 0; q < 2; ++q)
-                for (int r = 0; r < 2; ++r) {
-                    R[q][r] = F[q][0] * M[0][r] + F[q][1] * M[1][r];
-                    mx = fmax(mx, fabs(R[q][r]));
-                }
-            for (int q = 0; q < 2; ++q)
-                for (int r = 0; r < 2; ++r) M[q][r] = mx > 0.0 ? R[q][r] / mx : R[q][r];
-        }
-        const double h = 0.5 * (M[0][0] + M[1][1]), det = M[0][0] * M[1][1] - M[0][1] * M[1][0];
-        const double th = atan2(sqrt(fmax(det - h * h, 0.0)), h);
-        for (int l = 0; l < p; ++l) {
-            double B[2][2];
-            blk(l, B);
-            const double r = sqrt(fabs(B[0][0] * B[1][1] - B[0][1] * B[1][0]));
-            au[(size_t)j * p + l] = l == si ? std::polar(r, (S && !S[si]) ? -th : th) : cd(r, 0.0);
-        }
-    }
+    for (int j = 0; j < ns; ++j)
+        nzero += gev_scalars(p, si, S, wmap.data(), sgn.data(), k0[j], m[j], dg, au.data() + (size_t)j * p);
     if (aout)
         for (int j = 0; j < ns; ++j)
             for (int l = 0; l < p; ++l) {

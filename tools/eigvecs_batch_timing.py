@@ -16,6 +16,8 @@ device times and the launches of the stats, and the largest difference between t
   --signed   signed ComplexF64 problems (alternating signature): zgpschur_batch_, then Engine.zgeigvecs_batch
              (psd_z_geigvecs_batch_dev) against the loop of Engine.geigvecs_dev on the same device tensors; nb = 256,
              n in {8, 16, 32, 64}, p in {4, 16}; one warm-up, then the median of five alternating runs of each
+  --signed-real  the same for signed Float64 problems: dgpschur_batch_, then Engine.dgeigvecs_batch
+             (psd_d_geigvecs_batch_dev) against the loop of Engine.geigvecs_dev on the real T, Z; n up to 128
 
 Every shape runs in a process of its own under `timeout`; the tool stops at the first one that fails.  One JSON line per
 shape on stdout; --json FILE collects them."""
@@ -96,14 +98,15 @@ def run_one(nb, n, p, lr, sweep, cplx=False):
     print(json.dumps(row), flush=True)
 
 
-def signed_shapes():
-    return [(256, n, p) for n in (8, 16, 32, 64) for p in (4, 16)]
+def signed_shapes(real=False):
+    return [(256, n, p) for n in (8, 16, 32, 64) + ((128,) if real else ()) for p in (4, 16)]
 
 
-def run_signed(nb, n, p, lr, repeats=5):
+def run_signed(nb, n, p, lr, repeats=5, real=False):
     """--signed: zgpschur_batch_ with the alternating signature, then Engine.zgeigvecs_batch against the loop of
-    Engine.geigvecs_dev on the same device tensors.  One warm-up of each, then `repeats` timed runs of each, alternating;
-    the medians and the extremes are reported."""
+    Engine.geigvecs_dev on the same device tensors; --signed-real (`real`): dgpschur_batch_ and Engine.dgeigvecs_batch on
+    Float64 factors.  One warm-up of each, then `repeats` timed runs of each, alternating; the medians and the extremes
+    are reported."""
     import numpy as np
     import torch
 
@@ -113,22 +116,25 @@ def run_signed(nb, n, p, lr, repeats=5):
     eng = psd_amd.Engine(0)
     gen = torch.Generator(device="cuda")
     gen.manual_seed(9000 + n + 1000 * p)
-    A = torch.eye(n, dtype=torch.complex128, device="cuda") + 0.5 * torch.randn(
-        (nb, p, n, n), dtype=torch.complex128, device="cuda", generator=gen) / np.sqrt(n)
+    dt = torch.float64 if real else torch.complex128
+    A = torch.eye(n, dtype=dt, device="cuda") + 0.5 * torch.randn(
+        (nb, p, n, n), dtype=dt, device="cuda", generator=gen) / np.sqrt(n)
     S = [l % 2 == 0 for l in range(p)]
     infos = []
-    T, Z, values, _ = eng.zgpschur_batch_(A, S, lr, infos_out=infos)
+    T, Z, values, _ = (eng.dgpschur_batch_ if real else eng.zgpschur_batch_)(A, S, lr, infos_out=infos)
+    batched = eng.dgeigvecs_batch if real else eng.zgeigvecs_batch
     si = p if lr == "L" else 1
     select = np.ones((nb, n), dtype=bool)
     select[[q for q in range(nb) if infos[q] != 0]] = False  # (a problem that did not converge is skipped)
     Tc, Zc = T.transpose(2, 3), Z.transpose(2, 3)  # the [nb][p][n][n] column-major blocks, contiguous
     assert Tc.is_contiguous() and Zc.is_contiguous()
-    row = dict(nb=nb, n=n, p=p, lr=lr, nfailed=int(sum(1 for i in infos if i != 0)), signed=True, repeats=repeats)
+    row = dict(nb=nb, n=n, p=p, lr=lr, nfailed=int(sum(1 for i in infos if i != 0)), signed=True, real=bool(real),
+               repeats=repeats)
 
     def batch():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        out = eng.zgeigvecs_batch(T, Z, select, S=S, lr=lr, schurindex=si)
+        out = batched(T, Z, select, S=S, lr=lr, schurindex=si)
         torch.cuda.synchronize()
         return 1e3 * (time.perf_counter() - t0), out
 
@@ -151,7 +157,8 @@ def run_signed(nb, n, p, lr, repeats=5):
         tl.append(ms)
     row["batch"] = dict(wall_ms=float(np.median(tb)), wall_ms_min=min(tb), wall_ms_max=max(tb), ms_solve=st.ms_solve,
                         ms_backtransform=st.ms_backtransform, nlaunch=int(st.nlaunch), ngroups=int(st.ngroups),
-                        nvec=int(st.nvec_total), nzero=int(st.nzero), nperturbed=int(st.nperturbed))
+                        nvec=int(st.nvec_total), nzero=int(st.nzero), nperturbed=int(st.nperturbed),
+                        nrescaled=int(st.nrescaled))
     row["loop"] = dict(wall_ms=float(np.median(tl)), wall_ms_min=min(tl), wall_ms_max=max(tl))
     diff = adiff = 0.0
     for q in range(0, nb, max(1, nb // 8)):
@@ -174,20 +181,21 @@ def main():
     ap.add_argument("--sweep-orders", default="64,96,128,160,192,256")
     ap.add_argument("--complex", action="store_true", dest="cplx")
     ap.add_argument("--signed", action="store_true")
+    ap.add_argument("--signed-real", action="store_true", dest="signed_real")
     ap.add_argument("--timeout", type=int, default=240, help="seconds per shape")
     ap.add_argument("--json", default=None)
     ap.add_argument("--one", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
-    if args.one and args.signed:
-        run_signed(*parse_shapes(args.one)[0], args.lr)
+    if args.one and (args.signed or args.signed_real):
+        run_signed(*parse_shapes(args.one)[0], args.lr, real=args.signed_real)
         return 0
     if args.one:
         run_one(*parse_shapes(args.one)[0], args.lr, args.sweep, args.cplx)
         return 0
     if args.shapes:
         shapes = parse_shapes(args.shapes)
-    elif args.signed:
-        shapes = signed_shapes()
+    elif args.signed or args.signed_real:
+        shapes = signed_shapes(args.signed_real)
     elif args.sweep:
         shapes = [(64, int(x), 4) for x in args.sweep_orders.split(",") if x]
     else:
@@ -196,7 +204,8 @@ def main():
     for s in shapes:
         cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--one",
                "%dx%dx%d" % s, "--lr", args.lr] + (["--sweep"] if args.sweep else []) + (
-                   ["--complex"] if args.cplx else []) + (["--signed"] if args.signed else [])
+                   ["--complex"] if args.cplx else []) + (["--signed"] if args.signed else []) + (
+                       ["--signed-real"] if args.signed_real else [])
         pr = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
         sys.stdout.write(pr.stdout)
         sys.stdout.flush()
