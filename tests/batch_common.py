@@ -1,0 +1,114 @@
+"""What the case modules of the batched entries share: the family descriptor, the read-only input cache and a few
+helpers.
+
+A family is what Engine calls a family: Float64 (D), ComplexF64 (Z), signed ComplexF64 (ZG) and signed Float64 (DG).  A
+case is a plain function case_xxx(eng, fam, ...); the engine's method of a family is getattr(eng, fam.prefix + name), as
+Engine itself looks its entries up, and the C entry getattr(eng.lib, fam.csym + name).  A role module adds the lists that
+belong to its role (shapes, holes, seeds) to its own copies of the four descriptors with `with_`."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+
+import psdtest as pt
+
+
+class Family:
+    """A plain record: the fields given here, plus those a role module adds."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+    def with_(self, **fields):
+        return Family(**{**self.__dict__, **fields})
+
+    def __repr__(self):
+        return self.name
+
+    def method(self, eng, name):
+        return getattr(eng, self.prefix + name)
+
+    def entry(self, eng, name):
+        return getattr(eng.lib, self.csym + name)
+
+    def sargs(self, S):
+        """the signature as the positional argument the signed methods take after the problems; nothing otherwise"""
+        return (S,) if self.signed else ()
+
+
+# prefix: of the Engine methods; csym: of the C entries; maxitfac: the default of the entries; check: the checker of a
+# signed decomposition, check(A, S, ps, ...); cplx: ComplexF64 elements
+D = Family(name="D", prefix="", csym="psd_d_", dtype=np.float64, cplx=False, signed=False, maxitfac=30)
+Z = Family(name="Z", prefix="z", csym="psd_z_", dtype=np.complex128, cplx=True, signed=False, maxitfac=30)
+ZG = Family(name="ZG", prefix="zg", csym="psd_z_g", dtype=np.complex128, cplx=True, signed=True, maxitfac=30,
+            check=pt.gpschur_check)
+DG = Family(name="DG", prefix="dg", csym="psd_d_g", dtype=np.float64, cplx=False, signed=True, maxitfac=120,
+            check=pt.rgpschur_check)
+
+T, F = True, False
+SIG22 = tuple([T] + [bool((5 * q + 1) % 3) for q in range(1, 22)])
+SIG70 = tuple(q % 2 == 0 for q in range(70))
+
+
+def work(fam, A):
+    return [np.array(a, dtype=fam.dtype, order="F", copy=True) for a in A]
+
+
+def shape_id(s):
+    return "nb%d_n%d_p%d" % tuple(s[:3])
+
+
+def sig(shape, lr):
+    """the signature of a signed shape (nb, n, p, S for 'R'): reversed for 'L' (true entry last)"""
+    S = list(shape[3])
+    return S[::-1] if lr == "L" else S
+
+
+def sarr(S):
+    return (C.c_uint8 * len(S))(*[1 if x else 0 for x in S])
+
+
+def same_bits(a, b, p, what):
+    """T, Z, the values and — where both decompositions carry them — alpha, beta and the scaling, bit for bit"""
+    for name in ("alpha", "beta", "alphascale"):
+        if hasattr(a, name) and hasattr(b, name):
+            assert np.array_equal(getattr(a, name), getattr(b, name), equal_nan=name != "alphascale"), (what, name)
+    assert np.array_equal(a.values, b.values, equal_nan=True), what
+    for j in range(p):
+        assert np.array_equal(a.Ts[j], b.Ts[j]), (what, j)
+        if a.Z or b.Z:
+            assert np.array_equal(a.Z[j], b.Z[j]), (what, j)
+
+
+def cap(header, macro):
+    """An order cap as a kernel header under csrc/ defines it; None if the header has no such macro."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "periodicschurdecompositions.jl_amd", "csrc", header)) as fh:
+        m = re.search(r"^#define %s (\d+)" % macro, fh.read(), re.M)
+    return int(m.group(1)) if m else None
+
+
+# ------------------------------------------------------------------------------------------------
+# inputs: built once, shared among the cases, never written to
+_cache = {}
+
+
+def cached(key, make):
+    if key not in _cache:
+        _cache[key] = make()
+    return _cache[key]
+
+
+def _readonly(arrays):
+    for a in arrays:
+        a.setflags(write=False)
+
+
+def factors(dtype, seeds, n, p):
+    """pt.bench_factors(n, p, seed) for every seed, read-only"""
+    def make():
+        probs = [pt.bench_factors(n, p, seed=s, dtype=dtype) for s in seeds]
+        _readonly(a for A in probs for a in A)
+        return probs
+    return cached(("factors", np.dtype(dtype).char, tuple(seeds), n, p), make)

@@ -27,6 +27,7 @@ import pytest
 import gevec_cases as gc
 import psd_amd
 import psdtest as pt
+from zgbevec_cases import _lead, _represented, _same, _sarr, sig
 
 GATE = gc.GATE
 SEEDS = (5, 7, 9)
@@ -52,10 +53,6 @@ def is_sim(eng):
 def _figure(eng, name, v):
     key = ("sim" if is_sim(eng) else "gpu", name)
     FIGURES[key] = max(FIGURES.get(key, 0.0), float(v))
-
-
-def sig(p):
-    return gc.S_ALT(p) if p < 4 else gc.S_TFFT(p)
 
 
 def dgform(n, p, lr, seed, pairs=(), S=None, diag=None):
@@ -134,15 +131,6 @@ def check_batch(eng, probs, select, proto=True, vs_single=True):
     for q, (P, As) in enumerate(probs):
         check_problem(eng, P, As, out[q][0], out[q][1], sel[q], proto, vs_single)
     return out
-
-
-def _same(ra, rb):
-    """two results (Vs, a): the same bits"""
-    return len(ra[0]) == len(rb[0]) and all(np.array_equal(x, y) for x, y in zip(ra[0], rb[0])) and np.array_equal(ra[1], rb[1])
-
-
-def _sarr(P):
-    return (C.c_uint8 * len(P.Ts))(*[1 if x else 0 for x in gc._sgn(P)])
 
 
 def raw_host(eng, Ps, select, shifted=True, maxvec=None):
@@ -438,26 +426,8 @@ def case_launch_count(eng):
 
 # ------------------------------------------------------------------------------------------------
 # 11. pipeline
-def _represented(S, lr, Ts, Zs):
-    """the factors a decomposition represents (as gevec_cases.case_end_to_end builds them)"""
-    p = len(S)
-    As = []
-    for l in range(p):
-        ln = (l + 1) % p
-        fwd = bool(S[l]) == (lr == "L")
-        As.append(Zs[ln] @ Ts[l] @ Zs[l].conj().T if fwd else Zs[l] @ Ts[l] @ Zs[ln].conj().T)
-    return As
-
-
 def _pipeline_inputs(n, p, nb):
     return [pt.bench_factors(n, p, seed=191 + q) for q in range(nb)]
-
-
-def _lead(values):
-    """the eigenvalues inside the unit circle (whole conjugate pairs), and the leading rows they occupy after the
-    reordering"""
-    inside = np.abs(values) < 1
-    return inside, np.arange(len(values)) < inside.sum()
 
 
 def case_pipeline_host(eng, lr):

@@ -2,7 +2,7 @@
 small signed Float64 periodic Schur forms reordered in one call — the cases shared by the simulated tier
 (test_hostsim_dgordschur_batch.py) and the device tier (test_gpu_dgordschur_batch.py), the real counterparts of
 zgord_batch_cases and the signed counterparts of ord_batch_cases.  Inputs are dgpschur_batch results of the factors of
-dgbatch_cases (pt.bench_factors(n, p, seed=9000 + 131 q + 7 n + p)) with one signature per shape (reversed for 'L') and
+batch_cases.DG (pt.bench_factors(n, p, seed=9000 + 131 q + 7 n + p)) with one signature per shape (reversed for 'L') and
 the eigenvalues at or below the median modulus selected (row 2 alone for n = 2).  Random real factors give real
 eigenvalues and conjugate pairs side by side, so a batch contains the 1x1 and the 2x2 signed swaps; every problem of
 (4, 2, 2) has a real spectrum.  pt.oracle_gordschur accepts every swap of the first six problems of every shape
@@ -16,19 +16,20 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import dgbatch_cases as dg
+import batch_cases as bc
 import psd_amd
 import psdtest as pt
-from dgbatch_cases import _sig22, real_form
+from batch_cases import real_form
+from batch_common import SIG22, shape_id, sig
 from ord_batch_cases import median_select
-from zgord_batch_cases import gclone, oracle, raw
+from zgord_batch_cases import gclone, oracle, raw, select_for
 
 T, F = True, False
 
 # (nb, n, p, S for 'R') and what each covers; for 'L' the signature is reversed (true entry last)
 WINDOW_SHAPES = [
     (3, 48, 3, (T, F, T)),       # W = 25 < n: several windows, all off-window roles on both sides
-    (2, 40, 22, _sig22()),       # W = 24
+    (2, 40, 22, SIG22),          # W = 24
     (2, 30, 70, tuple(q % 2 == 0 for q in range(70))),  # W = 6: the per-factor scratch near the LDS limit
     (33, 12, 3, (T, F, T)),      # more problems than a 32-wide chunk, n < W
     (3, 5, 2, (T, F)),           # a pencil (problem 2 needs no swap in 'L')
@@ -45,13 +46,6 @@ CHAIN_SHAPE = (5, 12, 3, (T, F, T))
 NORACLE = 6  # the oracle runs on the first six problems of a shape
 
 _cache = {}
-
-
-def shape_id(s):
-    return "nb%d_n%d_p%d" % s[:3]
-
-
-sig = dg.sig
 
 
 def expected_window(n, p):
@@ -73,12 +67,6 @@ def _lds_bytes(p, w):
     return (b + 15) // 16 * 16
 
 
-def select_for(shape, lam):
-    if shape[1] == 2:  # (the median rule selects both rows of an order-2 problem: nothing would move)
-        return np.array([False, True])
-    return median_select(lam)
-
-
 def closed_select(lam0, select):
     """the selection closed under conjugation, as the device closes it"""
     closed = np.array(select, dtype=bool).copy()
@@ -93,7 +81,7 @@ def inputs(eng, shape, lr):
     differ in the knobs of the reordering only) and only cloned."""
     key = (eng.lib._name, shape, lr)
     if key not in _cache:
-        probs = dg.problems(shape)
+        probs = bc.problems(bc.DG, shape)
         ps0 = eng.dgpschur_batch(probs, sig(shape, lr), lr)
         sels = np.array([select_for(shape, ps.values) for ps in ps0])
         _cache[key] = (probs, ps0, sels)
@@ -287,7 +275,7 @@ def case_all_true(eng, shape=CHAIN_SHAPE):
     """A null or all-true S is accepted and stays on the signed kernels: the result is in the scaled form, with the swap
     counts of ordschur_batch_ on the same factors and its eigenvalues to 1e-9 * scale."""
     nb, n, p = shape[:3]
-    probs = dg.problems(shape)
+    probs = bc.problems(bc.DG, shape)
     for lr in "RL":
         ps0 = eng.dgpschur_batch(probs, None, lr)
         assert all(ps.S == [True] * p for ps in ps0)
@@ -445,13 +433,13 @@ def case_argument_codes(eng, shape=CHAIN_SHAPE):
 def case_python_errors(eng):
     nb, n, p, S = CHAIN_SHAPE
     probs, ps0, sels = inputs(eng, CHAIN_SHAPE, "R")
-    other = eng.pschur_(dg.work(pt.bench_factors(9, p, seed=3)), "R", S=list(S))
+    other = eng.pschur_(bc.work(bc.DG, pt.bench_factors(9, p, seed=3)), "R", S=list(S))
     with pytest.raises(psd_amd.DimensionMismatch):
         eng.dgordschur_batch([ps0[0], other], np.zeros(n, dtype=bool))  # unequal order
-    left = eng.pschur_(dg.work(pt.bench_factors(n, p, seed=4)), "L", S=list(S))
+    left = eng.pschur_(bc.work(bc.DG, pt.bench_factors(n, p, seed=4)), "L", S=list(S))
     with pytest.raises(psd_amd.DimensionMismatch):
         eng.dgordschur_batch([ps0[0], left], sels[:2])  # unequal orientation
-    otherS = eng.pschur_(dg.work(pt.bench_factors(n, p, seed=5)), "R", S=[True, True, False])
+    otherS = eng.pschur_(bc.work(bc.DG, pt.bench_factors(n, p, seed=5)), "R", S=[True, True, False])
     with pytest.raises(psd_amd.DimensionMismatch, match="signatures"):
         eng.dgordschur_batch([ps0[0], otherS], sels[:2])  # unequal S
     with pytest.raises(psd_amd.DimensionMismatch):
@@ -561,7 +549,7 @@ def case_device_chain(eng, lr, shape=CHAIN_SHAPE):
 
     nb, n, p = shape[:3]
     S = sig(shape, lr)
-    probs = dg.problems(shape)
+    probs = bc.problems(bc.DG, shape)
     si = p if lr == "L" else 1
     dA = torch.from_numpy(np.array([[np.array(a) for a in A] for A in probs])).cuda()
     T, Z, values, _ = eng.dgpschur_batch_(dA, S, lr)

@@ -11,6 +11,7 @@ import pytest
 
 import psd_amd
 import psdtest as pt
+from batch_common import shape_id  # noqa: F401 (used by the test files)
 from engine_cases import _clone
 
 # (nb, n, p): several windows at the widest W; narrow W from a large p (two of them); more problems than a 32-wide chunk
@@ -21,10 +22,6 @@ CAP_SHAPE = (2, 20, 3)
 CHAIN_SHAPE = (5, 12, 3)
 
 _cache = {}
-
-
-def shape_id(s):
-    return "nb%d_n%d_p%d" % s
 
 
 def factors(shape):

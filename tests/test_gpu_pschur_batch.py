@@ -1,67 +1,58 @@
 """GPU tier (MI355X): the batched entries — one workgroup per problem in the reduction (psd_bhess), one per (problem,
 factor) in the Q formation, the iteration 32 problems at a time — against the single calls on the same engine, the
 fallback above PSD_BH_NMAX, and the device-resident entry."""
-import os
-import re
-
 import pytest
 
 import batch_cases as bc
 import psd_amd
+from batch_common import cap
 
 pytestmark = pytest.mark.gpu
 
 
-def _bh_nmax():
-    """PSD_BH_NMAX as the kernel header defines it."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    with open(os.path.join(root, "periodicschurdecompositions.jl_amd", "csrc", "psd_bhess.h")) as fh:
-        return int(re.search(r"^#define PSD_BH_NMAX (\d+)", fh.read(), re.M).group(1))
-
-
-@pytest.mark.parametrize("shape", bc.HESS_SHAPES, ids=bc.shape_id)
+@pytest.mark.parametrize("shape", bc.D.hess_shapes, ids=bc.shape_id)
 def test_reduction_bit_for_bit(gpu_engine, shape):
     """p < 3: the single call is the one-launch-per-link form, whose bodies the batched kernel calls in the same order"""
-    bc.case_reduction_bits(gpu_engine, shape)
+    bc.case_reduction_bits(gpu_engine, bc.D, shape)
 
 
-@pytest.mark.parametrize("shape", bc.HESS_SHAPES_P3, ids=bc.shape_id)
+@pytest.mark.parametrize("shape", bc.D.hess_shapes_p3, ids=bc.shape_id)
 def test_reduction_against_lookahead_form(gpu_engine, shape):
     """p >= 3: the single call takes the look-ahead form and rounds differently"""
-    bc.case_reduction_close(gpu_engine, shape)
+    bc.case_reduction_close(gpu_engine, bc.D, shape)
 
 
 @pytest.mark.parametrize("lr", ["R", "L"])
-@pytest.mark.parametrize("shape", bc.FULL_SHAPES, ids=bc.shape_id)
+@pytest.mark.parametrize("shape", bc.D.shapes, ids=bc.shape_id)
 def test_full_decomposition(gpu_engine, shape, lr):
-    bc.case_full(gpu_engine, shape, lr)
+    bc.case_full_d(gpu_engine, shape, lr)
 
 
 def test_flags(gpu_engine):
-    bc.case_flags(gpu_engine)
+    bc.case_flags(gpu_engine, bc.D)
 
 
 def test_one_problem_fails(gpu_engine):
     """(the inputs are built for the simulation's single call; here the batch's own pattern and results are checked)"""
-    bc.case_one_fails(gpu_engine, single_pattern=False)
+    bc.case_one_fails(gpu_engine, bc.D)
 
 
 def test_argument_errors(gpu_engine):
-    bc.case_argument_errors(gpu_engine)
+    bc.case_argument_errors(gpu_engine, bc.D)
 
 
 @pytest.mark.parametrize("lr", ["R", "L"])
 def test_above_the_cap(gpu_engine, lr):
     """order PSD_BH_NMAX + 1: the multi-workgroup reduction and Q formation, problem by problem on the batch buffer"""
-    bc.case_full(gpu_engine, (2, _bh_nmax() + 1, 2), lr)
+    bc.case_full_d(gpu_engine, (2, cap("psd_bhess.h", "PSD_BH_NMAX") + 1, 2), lr)
 
 
 def test_device_resident(gpu_engine):
-    bc.case_device_resident(gpu_engine)
+    bc.case_device_resident(gpu_engine, bc.D)
 
 
 def test_argument_codes(gpu_engine):
-    bc.case_abi_codes(gpu_engine)
+    bc.case_abi_codes_d(gpu_engine)
 
 
 def test_groups(monkeypatch):
@@ -75,7 +66,7 @@ def test_groups(monkeypatch):
             monkeypatch.setenv(k, v)
         return psd_amd.Engine(device=0)
 
-    bc.case_groups(make)
+    bc.case_groups(make, bc.D)
 
 
 def test_empty_device_batch(gpu_engine):

@@ -1,13 +1,11 @@
 """GPU tier (MI355X): the ComplexF64 signed batched entries — one workgroup per problem in stage 1 of the signed
 Hessenberg reduction (psd_zgbhess1), one wavefront per problem in stage 2 and in the iteration (psd_zgbqz) — against the
 reference's checks and the CPU oracle, the fallback above the order cap, and the device-resident entry."""
-import os
-import re
-
 import pytest
 
+import batch_cases as gc
 import psd_amd
-import zgbatch_cases as gc
+from batch_common import cap
 
 pytestmark = pytest.mark.gpu
 
@@ -15,49 +13,47 @@ pytestmark = pytest.mark.gpu
 def _zgb_nmax():
     """The order cap of the signed batch kernels as the sources define it: PSD_ZGB_NMAX if the host driver has one,
     PSD_ZB_NMAX (the cap of the all-true path, reused) otherwise."""
-    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "periodicschurdecompositions.jl_amd", "csrc")
     for name, macro in (("psd_zgbqz.h", "PSD_ZGB_NMAX"), ("psd_zbhess.h", "PSD_ZB_NMAX")):
-        with open(os.path.join(csrc, name)) as fh:
-            m = re.search(r"^#define %s (\d+)" % macro, fh.read(), re.M)
-        if m:
-            return int(m.group(1))
+        nmax = cap(name, macro)
+        if nmax is not None:
+            return nmax
     raise AssertionError("no order cap found")
 
 
-@pytest.mark.parametrize("shape", gc.SHAPES, ids=gc.shape_id)
+@pytest.mark.parametrize("shape", gc.ZG.shapes, ids=gc.shape_id)
 def test_reduction(gpu_engine, shape):
-    gc.case_reduction(gpu_engine, shape)
+    gc.case_reduction(gpu_engine, gc.ZG, shape)
 
 
 @pytest.mark.parametrize("lr", ["R", "L"])
-@pytest.mark.parametrize("shape", gc.SHAPES, ids=gc.shape_id)
+@pytest.mark.parametrize("shape", gc.ZG.shapes, ids=gc.shape_id)
 def test_full_decomposition(gpu_engine, shape, lr):
-    gc.case_full(gpu_engine, shape, lr)
+    gc.case_full(gpu_engine, gc.ZG, shape, lr)
 
 
 def test_all_true_signature(gpu_engine):
-    gc.case_all_true(gpu_engine)
+    gc.case_all_true_zg(gpu_engine)
 
 
 def test_gpschur_batch(gpu_engine):
     gc.case_gpschur_batch(gpu_engine)
 
 
-@pytest.mark.parametrize("hole", gc.HOLES, ids=gc.hole_id)
+@pytest.mark.parametrize("hole", gc.ZG.holes, ids=gc.hole_id)
 def test_holes(gpu_engine, hole):
-    gc.case_holes(gpu_engine, hole)
+    gc.case_holes_zg(gpu_engine, hole)
 
 
 def test_one_problem_fails(gpu_engine):
-    gc.case_one_fails(gpu_engine)
+    gc.case_one_fails(gpu_engine, gc.ZG)
 
 
 def test_flags(gpu_engine):
-    gc.case_flags(gpu_engine)
+    gc.case_flags(gpu_engine, gc.ZG)
 
 
 def test_argument_errors(gpu_engine):
-    gc.case_argument_errors(gpu_engine)
+    gc.case_argument_errors(gpu_engine, gc.ZG)
 
 
 def test_groups(monkeypatch):
@@ -71,16 +67,16 @@ def test_groups(monkeypatch):
             monkeypatch.setenv(k, v)
         return psd_amd.Engine(device=0)
 
-    gc.case_groups(make)
+    gc.case_groups(make, gc.ZG)
 
 
 def test_device_resident(gpu_engine):
-    gc.case_device_resident(gpu_engine)
+    gc.case_device_resident(gpu_engine, gc.ZG)
 
 
 def test_above_the_cap(gpu_engine):
     """order cap + 1: the single call's signed reduction and iteration, problem by problem on the batch buffer"""
-    gc.case_above_cap(gpu_engine, _zgb_nmax() + 1)
+    gc.case_above_cap(gpu_engine, gc.ZG, _zgb_nmax() + 1)
 
 
 def test_empty_device_batch(gpu_engine):

@@ -9,32 +9,32 @@ import batch_cases as bc
 import psd_amd
 
 
-@pytest.mark.parametrize("shape", bc.HESS_SHAPES + bc.HESS_SHAPES_P3, ids=bc.shape_id)
+@pytest.mark.parametrize("shape", bc.D.hess_shapes + bc.D.hess_shapes_p3, ids=bc.shape_id)
 def test_reduction_bit_for_bit(sim_engine, shape):
-    bc.case_reduction_bits(sim_engine, shape)
+    bc.case_reduction_bits(sim_engine, bc.D, shape)
 
 
-@pytest.mark.parametrize("shape", bc.HESS_SHAPES_P3, ids=bc.shape_id)
+@pytest.mark.parametrize("shape", bc.D.hess_shapes_p3, ids=bc.shape_id)
 def test_reduction_factorization(sim_engine, shape):
-    bc.case_reduction_close(sim_engine, shape)
+    bc.case_reduction_close(sim_engine, bc.D, shape)
 
 
 @pytest.mark.parametrize("lr", ["R", "L"])
-@pytest.mark.parametrize("shape", bc.FULL_SHAPES, ids=bc.shape_id)
+@pytest.mark.parametrize("shape", bc.D.shapes, ids=bc.shape_id)
 def test_full_decomposition(sim_engine, shape, lr):
-    bc.case_full(sim_engine, shape, lr)
+    bc.case_full_d(sim_engine, shape, lr)
 
 
 def test_flags(sim_engine):
-    bc.case_flags(sim_engine)
+    bc.case_flags(sim_engine, bc.D)
 
 
 def test_one_problem_fails(sim_engine):
-    bc.case_one_fails(sim_engine)
+    bc.case_one_fails(sim_engine, bc.D, single_pattern=True)
 
 
 def test_argument_errors(sim_engine):
-    bc.case_argument_errors(sim_engine)
+    bc.case_argument_errors(sim_engine, bc.D)
 
 
 def test_device_entry_and_argument_codes(sim_engine):
@@ -42,7 +42,7 @@ def test_device_entry_and_argument_codes(sim_engine):
 
 
 def test_argument_codes(sim_engine):
-    bc.case_abi_codes(sim_engine)
+    bc.case_abi_codes_d(sim_engine)
 
 
 def test_groups(built, monkeypatch):
@@ -54,4 +54,4 @@ def test_groups(built, monkeypatch):
             monkeypatch.setenv(k, v)
         return psd_amd.Engine(libpath=lib)
 
-    bc.case_groups(make)
+    bc.case_groups(make, bc.D)

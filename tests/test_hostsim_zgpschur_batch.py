@@ -6,21 +6,21 @@ import os
 
 import pytest
 
+import batch_cases as gc
 import psd_amd
-import zgbatch_cases as gc
 
 LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostsim", "_build", "libpsd_hostsim.so")
 
 
-@pytest.mark.parametrize("shape", gc.SHAPES, ids=gc.shape_id)
+@pytest.mark.parametrize("shape", gc.ZG.shapes, ids=gc.shape_id)
 def test_reduction(sim_engine, shape):
-    gc.case_reduction(sim_engine, shape)
+    gc.case_reduction(sim_engine, gc.ZG, shape)
 
 
 @pytest.mark.parametrize("lr", ["R", "L"])
-@pytest.mark.parametrize("shape", gc.SHAPES, ids=gc.shape_id)
+@pytest.mark.parametrize("shape", gc.ZG.shapes, ids=gc.shape_id)
 def test_full_decomposition(sim_engine, shape, lr):
-    gc.case_full(sim_engine, shape, lr)
+    gc.case_full(sim_engine, gc.ZG, shape, lr)
 
 
 @pytest.fixture(scope="module")
@@ -31,45 +31,45 @@ def single_engine(built):
     return eng
 
 
-@pytest.mark.parametrize("shape", gc.SHAPES, ids=gc.shape_id)
+@pytest.mark.parametrize("shape", gc.ZG.shapes, ids=gc.shape_id)
 def test_reduction_bit_for_bit(sim_engine, single_engine, shape, monkeypatch):
     monkeypatch.setenv("PSD_HESS_SERIAL", "1")  # (read by the single call at every reduction)
-    gc.case_reduction_bits(sim_engine, single_engine, shape)
+    gc.case_reduction_bits(sim_engine, gc.ZG, shape, single_engine)
 
 
-@pytest.mark.parametrize("shape", gc.SHAPES, ids=gc.shape_id)
+@pytest.mark.parametrize("shape", gc.ZG.shapes, ids=gc.shape_id)
 def test_iteration_bit_for_bit(sim_engine, single_engine, shape, monkeypatch):
     monkeypatch.setenv("PSD_HESS_SERIAL", "1")
-    gc.case_iteration_bits(sim_engine, single_engine, shape)
+    gc.case_iteration_bits(sim_engine, gc.ZG, single_engine, shape)
 
 
 def test_all_true_signature(sim_engine):
-    gc.case_all_true(sim_engine)
+    gc.case_all_true_zg(sim_engine)
 
 
 def test_gpschur_batch(sim_engine):
     gc.case_gpschur_batch(sim_engine)
 
 
-@pytest.mark.parametrize("hole", gc.HOLES, ids=gc.hole_id)
+@pytest.mark.parametrize("hole", gc.ZG.holes, ids=gc.hole_id)
 def test_holes(sim_engine, hole):
-    gc.case_holes(sim_engine, hole)
+    gc.case_holes_zg(sim_engine, hole)
 
 
 def test_one_problem_fails(sim_engine):
-    gc.case_one_fails(sim_engine)
+    gc.case_one_fails(sim_engine, gc.ZG)
 
 
 def test_flags(sim_engine):
-    gc.case_flags(sim_engine)
+    gc.case_flags(sim_engine, gc.ZG)
 
 
 def test_argument_errors(sim_engine):
-    gc.case_argument_errors(sim_engine)
+    gc.case_argument_errors(sim_engine, gc.ZG)
 
 
 def test_argument_codes_and_device_entry(sim_engine):
-    gc.case_abi_codes(sim_engine)
+    gc.case_abi_codes(sim_engine, gc.ZG)
 
 
 def test_groups(built, monkeypatch):
@@ -80,4 +80,4 @@ def test_groups(built, monkeypatch):
             monkeypatch.setenv(k, v)
         return psd_amd.Engine(libpath=LIB)
 
-    gc.case_groups(make)
+    gc.case_groups(make, gc.ZG)

@@ -6,21 +6,21 @@ import os
 
 import pytest
 
+import batch_cases as zc
 import psd_amd
-import zbatch_cases as zc
 
 LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostsim", "_build", "libpsd_hostsim.so")
 
 
-@pytest.mark.parametrize("shape", zc.SHAPES, ids=zc.shape_id)
+@pytest.mark.parametrize("shape", zc.Z.shapes, ids=zc.shape_id)
 def test_reduction_bit_for_bit(sim_engine, shape):
-    zc.case_reduction_bits(sim_engine, shape)
+    zc.case_reduction_bits(sim_engine, zc.Z, shape)
 
 
 @pytest.mark.parametrize("lr", ["R", "L"])
-@pytest.mark.parametrize("shape", zc.SHAPES, ids=zc.shape_id)
+@pytest.mark.parametrize("shape", zc.Z.shapes, ids=zc.shape_id)
 def test_full_decomposition(sim_engine, shape, lr):
-    zc.case_full(sim_engine, shape, lr)
+    zc.case_full(sim_engine, zc.Z, shape, lr)
 
 
 @pytest.fixture(scope="module")
@@ -34,30 +34,30 @@ def onewave_engine(built):
         mp.undo()
 
 
-@pytest.mark.parametrize("shape", zc.SHAPES, ids=zc.shape_id)
+@pytest.mark.parametrize("shape", zc.Z.shapes, ids=zc.shape_id)
 def test_iteration_bit_for_bit(sim_engine, onewave_engine, shape):
-    zc.case_iteration_bits(sim_engine, onewave_engine, shape)
+    zc.case_iteration_bits(sim_engine, zc.Z, onewave_engine, shape)
 
 
-@pytest.mark.parametrize("hole", zc.HOLES, ids=lambda h: "n%d_p%d_f%d_i%d" % h)
+@pytest.mark.parametrize("hole", zc.Z.holes, ids=lambda h: "n%d_p%d_f%d_i%d" % h)
 def test_holes(sim_engine, hole):
-    zc.case_holes(sim_engine, hole)
+    zc.case_holes_z(sim_engine, hole)
 
 
 def test_one_problem_fails(sim_engine):
-    zc.case_one_fails(sim_engine)
+    zc.case_one_fails(sim_engine, zc.Z)
 
 
 def test_flags(sim_engine):
-    zc.case_flags(sim_engine)
+    zc.case_flags(sim_engine, zc.Z)
 
 
 def test_argument_errors(sim_engine):
-    zc.case_argument_errors(sim_engine)
+    zc.case_argument_errors(sim_engine, zc.Z)
 
 
 def test_argument_codes_and_device_entry(sim_engine):
-    zc.case_abi_codes(sim_engine)
+    zc.case_abi_codes(sim_engine, zc.Z)
 
 
 def test_groups(built, monkeypatch):
@@ -68,4 +68,4 @@ def test_groups(built, monkeypatch):
             monkeypatch.setenv(k, v)
         return psd_amd.Engine(libpath=LIB)
 
-    zc.case_groups(make)
+    zc.case_groups(make, zc.Z)

@@ -12,15 +12,15 @@ import pytest
 
 import psd_amd
 import psdtest as pt
-from zgbatch_cases import _sig22
-from zord_batch_cases import bits_differ, median_select
+from batch_common import SIG22, shape_id, sig
+from zord_batch_cases import bits_differ, median_select, select_for
 
 T, F = True, False
 
 # (nb, n, p, S for 'R') and what each covers; for 'L' the signature is reversed (true entry last)
 WINDOW_SHAPES = [
     (3, 48, 3, (T, F, T)),       # W = 32 < n: several windows, all three off-window roles
-    (2, 40, 22, _sig22()),       # W = 20
+    (2, 40, 22, SIG22),          # W = 20
     (2, 30, 70, tuple(q % 2 == 0 for q in range(70))),  # W = 10, window image near the LDS limit
     (33, 12, 3, (T, F, T)),      # more problems than a 32-wide chunk, n < W
     (3, 5, 2, (T, F)),           # a pencil
@@ -36,15 +36,6 @@ CHAIN_SHAPE = (5, 12, 3, (T, F, T))
 NORACLE = 6  # the oracle runs on the first six problems of a shape
 
 _cache = {}
-
-
-def shape_id(s):
-    return "nb%d_n%d_p%d" % s[:3]
-
-
-def sig(shape, lr):
-    S = list(shape[3])
-    return S[::-1] if lr == "L" else S
 
 
 def expected_window(n, p):
@@ -77,12 +68,6 @@ def factors(shape):
                 a.setflags(write=False)
         _cache[key] = probs
     return _cache[key]
-
-
-def select_for(shape, lam):
-    if shape[1] == 2:  # (the median rule selects both rows of an order-2 problem: nothing would move)
-        return np.array([False, True])
-    return median_select(lam)
 
 
 def inputs(eng, shape, lr):

@@ -11,7 +11,9 @@ import pytest
 
 import psd_amd
 import psdtest as pt
+from batch_common import shape_id
 from engine_cases import _clone
+from ord_batch_cases import median_select
 
 # (nb, n, p) and what each covers
 WINDOW_SHAPES = [
@@ -31,10 +33,6 @@ CHAIN_SHAPE = (5, 12, 3)
 _cache = {}
 
 
-def shape_id(s):
-    return "nb%d_n%d_p%d" % s
-
-
 def factors(shape):
     """The factors of a shape: built once, shared, never written to."""
     nb, n, p = shape
@@ -46,11 +44,6 @@ def factors(shape):
                 a.setflags(write=False)
         _cache[key] = probs
     return _cache[key]
-
-
-def median_select(lam):
-    n = len(lam)
-    return np.abs(lam) <= np.sort(np.abs(lam))[n // 2]
 
 
 def select_for(shape, lam):
