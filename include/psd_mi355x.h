@@ -390,6 +390,10 @@ int psd_z_checkpsd(psd_ctx* ctx, int n, int p, double* const* T, double* const* 
 int psd_d_checkpsd_dev(psd_ctx* ctx, int n, int p, const double* dT, const double* dZ, const double* dA,
                        const uint8_t* S, char orient, int schurindex, double thresh, int strict, double* err,
                        double* orth, double* tri, int* ok, int* info);
+/* The ComplexF64 twin of psd_d_checkpsd_dev: [p][n][n] blocks of interleaved (re, im) doubles, same codes. */
+int psd_z_checkpsd_dev(psd_ctx* ctx, int n, int p, const double* dT, const double* dZ, const double* dA,
+                       const uint8_t* S, char orient, int schurindex, double thresh, int strict, double* err,
+                       double* orth, double* tri, int* ok, int* info);
 
 /* ---- partial_pschur: periodic Krylov-Schur for dense factors — src/krylov.jl:446-798 (D. Kressner, Numer. Math. 2006) --
  * A `nev`-order partial periodic Schur decomposition of the product A_p ... A_2 A_1 in the LEFT orientation of the
@@ -946,6 +950,49 @@ int psd_d_gordschur_batch(psd_ctx* ctx, int nb, int n, int p, double* const* T, 
 int psd_d_gordschur_batch_dev(psd_ctx* ctx, int nb, int n, int p, void* dT, void* dZ, const uint8_t* S, char orient,
                               int schurindex, const uint8_t* select, int wantZ, double* alpha, double* beta,
                               int32_t* ascale, int* infos, int* nswaps, psd_stats* stats, int* info);
+
+/* ---- checkpsd_batch: verify many small periodic Schur forms in one call ---------------------------------------------
+ * checkpsd(P, As; thresh, strict) (diagnostics.jl:190-263) for nb decompositions of one shape (n, p), ONE signature, one
+ * orient and one schurindex, as the *_pschur_batch, *_ordschur_batch entries of every family leave them: two entries
+ * per element type, the signature an argument (NULL: all true).  Up to order 64 (PSD_BCK_NMAX) a group of problems is
+ * ONE launch — a workgroup per (problem, factor) forms || tril(T_l) ||_F, opnorm(A_l, 1), || Z_l Z_l' - I ||_F and
+ * || Z_a T_l Z_b' - A_l ||_F on the matrix cores, W = T_l Z_b' staying in LDS — and one read-back of four numbers per
+ * factor; every sum has a fixed order and there are no atomics, so up to that order a factor's numbers do not depend on
+ * nb, on the problem's place in the batch or on the grouping (bit for bit).  Above it the single verifier
+ * (psd_?_checkpsd_dev) runs problem by problem on the slices of the batch buffers, without that promise.  PSD_BATCH_GROUP
+ * acts as for the other batch entries; PSD_BCK_NMAX in the environment at psd_create may only lower the order.
+ *
+ * T, Z, A: nb * p host matrices of n * n elements, column-major, problem-major, USER order (T[q * p + schurindex - 1] is
+ * the quasi-triangular factor of problem q); they are only read.  S: host [p] flags in user order, or NULL.  err
+ * (required), orth, tri (each may be NULL): host [nb][p], as the single entry defines them; ok (may be NULL): host [nb],
+ * the reference's Bool per problem (tri <= (strict ? 0 : 10 eps n), orth <= 10 eps n, err <= thresh; a NaN fails).
+ * stats (may be NULL): nfail the problems with ok == 0; nlaunch == ngroups up to order 64.  A failed check is a verdict,
+ * not an error: the return value and *info are 0.
+ * Returns: -1 ctx NULL; -2 nb < 0; -3 n < 1; -4 p < 1; -5 T, Z or A NULL; -8 orient; -9 schurindex not in 1..p;
+ * -13 err NULL; PSD_INFO_NOTIMPL on a period-sharded context; PSD_INFO_RUNTIME + k.  nb == 0 returns 0 and touches
+ * nothing. */
+typedef struct psd_bcheck_stats {
+    int32_t nb;        /* problems of the call */
+    int32_t nfail;     /* problems whose verdict is false */
+    int32_t nlaunch;   /* kernel launches (one per group up to order 64) */
+    int32_t ngroups;   /* groups the batch went to the device in */
+    double ms_kernels; /* device time of the kernels and their read-back */
+    double ms_copy;    /* host entries: time of the uploads */
+} psd_bcheck_stats;
+int psd_d_checkpsd_batch(psd_ctx* ctx, int nb, int n, int p, double* const* T, double* const* Z, double* const* A,
+                         const uint8_t* S, char orient, int schurindex, double thresh, int strict, double* err,
+                         double* orth, double* tri, int32_t* ok, psd_bcheck_stats* stats, int* info);
+int psd_z_checkpsd_batch(psd_ctx* ctx, int nb, int n, int p, double* const* T, double* const* Z, double* const* A,
+                         const uint8_t* S, char orient, int schurindex, double thresh, int strict, double* err,
+                         double* orth, double* tri, int32_t* ok, psd_bcheck_stats* stats, int* info);
+/* Device-resident variants: dT, dZ, dA device [nb][p][n][n] column-major blocks in user order (what the
+ * psd_?_*pschur_batch_dev entries leave; psd_z_: interleaved), read only; S and the outputs are host arrays. */
+int psd_d_checkpsd_batch_dev(psd_ctx* ctx, int nb, int n, int p, const double* dT, const double* dZ, const double* dA,
+                             const uint8_t* S, char orient, int schurindex, double thresh, int strict, double* err,
+                             double* orth, double* tri, int32_t* ok, psd_bcheck_stats* stats, int* info);
+int psd_z_checkpsd_batch_dev(psd_ctx* ctx, int nb, int n, int p, const double* dT, const double* dZ, const double* dA,
+                             const uint8_t* S, char orient, int schurindex, double thresh, int strict, double* err,
+                             double* orth, double* tri, int32_t* ok, psd_bcheck_stats* stats, int* info);
 
 #ifdef __cplusplus
 }

@@ -24,7 +24,7 @@ import PeriodicSchurDecompositions: pschur!, pschur, phessenberg!, gpschur, Peri
 const PSD = PeriodicSchurDecompositions
 using ArnoldiMethod: ArnoldiMethod
 
-export set_train!, engine_version, pschur_batch!, pschur_batch, gpschur_batch, eigvecs_batch_device, geigvecs_batch_device, ordschur_batch!
+export set_train!, engine_version, pschur_batch!, pschur_batch, gpschur_batch, eigvecs_batch_device, geigvecs_batch_device, ordschur_batch!, checkpsd_batch
 
 const libpsd = get(ENV, "LIBPSD_MI355X", joinpath(@__DIR__, "..", "periodicschurdecompositions.jl_amd", "libpsd_mi355x.so"))
 
@@ -921,6 +921,54 @@ function checkpsd(P::PSD.AbstractPeriodicSchur{T}, Hs::AbstractVector{<:Abstract
         end
     end
     return ok[] != 0, err
+end
+
+# checkpsd_batch(Ps, Hss; thresh, strict): checkpsd for MANY small decompositions of one shape (order, period,
+# orientation, schurindex, signature) in ONE call (psd_d_checkpsd_batch / psd_z_checkpsd_batch): up to order 64 one
+# launch per group of problems, a workgroup per (problem, factor).  Hss[q] are the factors Ps[q] was computed from.
+# Returns (ok, err): the reference's Bool per problem and the p x nb matrix of the normalized factorization errors.
+# Nothing is warned about: ask checkpsd about a problem whose verdict is false.
+function checkpsd_batch(Ps::Vector{<:PSD.AbstractPeriodicSchur{T}}, Hss::AbstractVector; thresh = 100,
+                        strict = true) where {T <: BlasElt}
+    nb = length(Ps)
+    length(Hss) == nb || throw(DimensionMismatch("one vector of factors per decomposition"))
+    nb == 0 && return Bool[], zeros(Float64, 0, 0)
+    P1 = Ps[1]
+    p = P1.period; n = size(P1.T1, 1); js = P1.schurindex; orient = P1.orientation
+    sig(P) = P isa GeneralizedPeriodicSchur ? UInt8.(P.S) : fill(0x01, p)
+    S = sig(P1)
+    Ts = Matrix{T}[]; Zs = Matrix{T}[]; As = Matrix{T}[]
+    for (P, Hs) in zip(Ps, Hss)
+        P.period == length(Hs) || throw(DimensionMismatch("length of Hs vector must match period of P"))  # diagnostics.jl:194
+        for H in Hs
+            checksquare(H) == size(P.T1, 1) || throw(DimensionMismatch("size of Hs matrices must match P"))  # :197-202
+        end
+        (P.period == p && size(P.T1, 1) == n) ||
+            throw(DimensionMismatch("the problems of a batch must have equal order and period"))
+        (P.schurindex == js && P.orientation == orient && length(P.Z) == p) ||
+            throw(DimensionMismatch("the problems of a batch must have equal order, period, orientation and schurindex"))
+        sig(P) == S || throw(DimensionMismatch("the problems of a batch must have equal signatures S"))
+        append!(Ts, _dense(_userT(P))); append!(Zs, _dense(P.Z)); append!(As, _dense(Hs))
+    end
+    err = zeros(p, nb); ok = zeros(Int32, nb); info = Ref{Cint}(0)
+    Tp = _ptrs(Ts); Zp = _ptrs(Zs); Ap = _ptrs(As)
+    GC.@preserve Ts Zs As S err ok begin
+        # (the two entries have one argument list: ctx, nb, n, p, T, Z, A, S, orient, schurindex, thresh, strict, err, orth,
+        #  tri, ok, stats, info)
+        if T <: Real
+            ccall((:psd_d_checkpsd_batch, libpsd), Cint,
+                  (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ptr{UInt8}, Cchar,
+                   Cint, Cdouble, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Cvoid}, Ref{Cint}),
+                  ctx().ptr, nb, n, p, Tp, Zp, Ap, S, orient, js, thresh, strict, err, C_NULL, C_NULL, ok, C_NULL, info)
+        else
+            ccall((:psd_z_checkpsd_batch, libpsd), Cint,
+                  (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ptr{UInt8}, Cchar,
+                   Cint, Cdouble, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Cvoid}, Ref{Cint}),
+                  ctx().ptr, nb, n, p, Tp, Zp, Ap, S, orient, js, thresh, strict, err, C_NULL, C_NULL, ok, C_NULL, info)
+        end
+    end
+    _throw(info[])
+    return Bool[o != 0 for o in ok], err
 end
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -164,6 +164,17 @@ class BevecStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class BcheckStats(C.Structure):
+    """psd_bcheck_stats (include/psd_mi355x.h): counters, launches and device times of one checkpsd_batch call."""
+    _fields_ = [
+        ("nb", C.c_int32), ("nfail", C.c_int32), ("nlaunch", C.c_int32), ("ngroups", C.c_int32),
+        ("ms_kernels", C.c_double), ("ms_copy", C.c_double),
+    ]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class PKSFailure(Exception):
     """PKSFailure (src/krylov.jl:21-23): the Arnoldi re-initialisation failed."""
 
@@ -375,6 +386,8 @@ class Engine:
                                        C.c_double, C.c_int, dp, dp, dp, ip, ip]
         lib.psd_d_checkpsd_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, u8p,
                                            C.c_char, C.c_int, C.c_double, C.c_int, dp, dp, dp, ip, ip]
+        if hasattr(lib, "psd_z_checkpsd_dev"):  # (tools load builds of earlier commits)
+            lib.psd_z_checkpsd_dev.argtypes = lib.psd_d_checkpsd_dev.argtypes
         # the batch entries: one description per entry family, crossed with d / z (the eigenvalue arguments), plain /
         # signed (the signature after the factors) and host / dev (how the matrices are passed).  The signed pschur and
         # ordschur entries of both types return scaled eigenvalues (alpha, beta, alphascale).
@@ -397,6 +410,8 @@ class Engine:
                 # (no eigenvalue arguments: the signature, and the scalars a behind maxvec)
                 sigs[f"psd_{t}_geigvecs_batch{dev}"] = (head + [mats, mats, u8p, C.c_char, C.c_int, u8p, C.c_int, mats,
                                                                 C.c_int, dp, ip, i32p, C.POINTER(BevecStats), ip])
+                sigs[f"psd_{t}_checkpsd_batch{dev}"] = (head + [mats, mats, mats, u8p, C.c_char, C.c_int, C.c_double,
+                                                                C.c_int, dp, dp, dp, i32p, C.POINTER(BcheckStats), ip])
             for nm, sig in sigs.items():
                 if hasattr(lib, nm):  # (tools load builds of earlier commits to time their single calls)
                     getattr(lib, nm).argtypes = sig
@@ -2550,18 +2565,115 @@ class Engine:
             return bool(ok.value), err, orth, tri
         return bool(ok.value), err
 
-    def checkpsd_dev(self, dT_ptr, dZ_ptr, dA_ptr, n, p, lr="R", schurindex=1, thresh=100, strict=True, S=None):
-        """checkpsd on operands already resident in HBM ([p][n][n] Float64 blocks in user order)."""
+    def checkpsd_dev(self, dT_ptr, dZ_ptr, dA_ptr, n, p, lr="R", schurindex=1, thresh=100, strict=True, S=None,
+                     cplx=False):
+        """checkpsd on operands already resident in HBM ([p][n][n] Float64 blocks in user order; `cplx`: ComplexF64
+        blocks of interleaved (re, im) doubles, psd_z_checkpsd_dev)."""
         sig = (C.c_uint8 * p)(*[1 if x else 0 for x in S]) if S is not None else None
         err, orth, tri = np.zeros(p), np.zeros(p), np.zeros(p)
         ok, info = C.c_int(0), C.c_int(0)
         dp = C.POINTER(C.c_double)
-        self.lib.psd_d_checkpsd_dev(self.ctx, n, p, C.c_void_p(dT_ptr), C.c_void_p(dZ_ptr), C.c_void_p(dA_ptr), sig,
-                                    char_lr(lr).encode(), schurindex, float(thresh), int(strict),
-                                    err.ctypes.data_as(dp), orth.ctypes.data_as(dp), tri.ctypes.data_as(dp),
-                                    C.byref(ok), C.byref(info))
+        entry = self.lib.psd_z_checkpsd_dev if cplx else self.lib.psd_d_checkpsd_dev
+        entry(self.ctx, n, p, C.c_void_p(dT_ptr), C.c_void_p(dZ_ptr), C.c_void_p(dA_ptr), sig, char_lr(lr).encode(),
+              schurindex, float(thresh), int(strict), err.ctypes.data_as(dp), orth.ctypes.data_as(dp),
+              tri.ctypes.data_as(dp), C.byref(ok), C.byref(info))
         self._raise(info.value)
         return bool(ok.value), err, orth, tri
+
+    def _checkpsd_batch_call(self, cplx, dev, nb, n, p, T, Z, A, S, orient, si, thresh, strict, details):
+        """psd_?_checkpsd_batch[_dev] on packed factors (flat pointer lists, or with `dev` device blocks); the stats of
+        the call are left in `self.checkpsd_batch_stats`."""
+        if S is not None and len(S) != p:
+            raise DimensionMismatch("length of S must match the period")
+        sig = (C.c_uint8 * p)(*[1 if x else 0 for x in S]) if S is not None else None
+        err, orth, tri = np.zeros((nb, p)), np.zeros((nb, p)), np.zeros((nb, p))
+        ok = np.zeros(nb, dtype=np.int32)
+        st, info = BcheckStats(), C.c_int(0)
+        dp = C.POINTER(C.c_double)
+        entry = getattr(self.lib, f"psd_{'z' if cplx else 'd'}_checkpsd_batch{'_dev' if dev else ''}")
+        entry(self.ctx, nb, n, p, T, Z, A, sig, orient.encode(), si, float(thresh), int(strict), err.ctypes.data_as(dp),
+              orth.ctypes.data_as(dp), tri.ctypes.data_as(dp), ok.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(st),
+              C.byref(info))
+        self.checkpsd_batch_stats = st
+        self._raise(info.value)
+        return (ok != 0, err, orth, tri) if details else (ok != 0, err)
+
+    def checkpsd_batch(self, Ps, *args, thresh=100, strict=True, S=None, details=False, lr="R", schurindex=1):
+        """checkpsd(P, As; thresh, strict) — src/diagnostics.jl:190-263 — for MANY small decompositions of one shape in
+        ONE call (psd_?_checkpsd_batch): the follow-up of every *pschur_batch / *ordschur_batch.  Real or complex
+        follows the data; the signature is an argument, so the one method serves all four batch families.
+
+        checkpsd_batch(Ps, As_list, thresh=100, strict=True, S=None, details=False): `Ps` a list of PeriodicSchur /
+        GeneralizedPeriodicSchur of equal order, period, orientation, schurindex and signature (`S`: None takes that of
+        the decompositions), `As_list` the factors each was computed from.
+        checkpsd_batch(T, Z, A, lr=..., schurindex=..., S=...): three GPU tensors [nb, p, n, n] of one dtype (float64 or
+        complex128), the outputs of a device-resident *pschur_batch_ and the factors it started from; they are only
+        read, and tensors in the layout those entries return are not copied.
+
+        Returns (ok, err): ok a bool array [nb] (the reference's verdict per problem), err [nb, p]; with details=True
+        also orth and tri [nb, p].  Up to order 64 a problem's numbers do not depend on its place in the batch (bit for
+        bit).  The stats of the call are left in `self.checkpsd_batch_stats` (BcheckStats)."""
+        if hasattr(Ps, "data_ptr"):
+            if len(args) != 2:
+                raise TypeError("checkpsd_batch(T, Z, A, lr=..., schurindex=..., S=...)")
+            import torch
+
+            T, Z, A = Ps, args[0], args[1]
+            if any(x.dtype not in (torch.float64, torch.complex128) for x in (T, Z, A)):
+                raise TypeError("checkpsd_batch: float64 or complex128 tensors")
+            fam = _Z if T.is_complex() else _D
+            wrong = TypeError("checkpsd_batch: the tensors T, Z and A must be of one dtype")
+            nb, p, n = self._dev_batch(fam, "checkpsd_batch", wrong, T, Z, A)
+            if nb == 0:
+                self.checkpsd_batch_stats = BcheckStats()
+                empty = (np.zeros(0, dtype=bool),) + (np.zeros((0, p)),) * 3
+                return empty if details else empty[:2]
+            dT, dZ, dA = (_dev_blocks(x, fam, "readonly") for x in (T, Z, A))
+            torch.cuda.synchronize(T.device)
+            return self._checkpsd_batch_call(fam is _Z, True, nb, n, p, C.c_void_p(dT.data_ptr()),
+                                             C.c_void_p(dZ.data_ptr()), C.c_void_p(dA.data_ptr()), S, char_lr(lr),
+                                             schurindex, thresh, strict, details)
+        if len(args) != 1:
+            raise TypeError("checkpsd_batch(Ps, As_list, thresh=100, strict=True)")
+        Ps, As_list = list(Ps), [list(As) for As in args[0]]
+        nb = len(Ps)
+        if len(As_list) != nb:
+            raise DimensionMismatch("checkpsd_batch: one list of factors per decomposition")
+        if nb == 0:
+            self.checkpsd_batch_stats = BcheckStats()
+            empty = (np.zeros(0, dtype=bool),) + (np.zeros((0, 0)),) * 3
+            return empty if details else empty[:2]
+        shape = kind = sig0 = None
+        Tw, Zw, Aw = [], [], []
+        for P, As in zip(Ps, As_list):
+            p = len(As)
+            if P.period != p:
+                raise DimensionMismatch("length of Hs vector must match period of P")  # diagnostics.jl:194-196
+            n = P.Ts[0].shape[0]
+            if any(np.ndim(a) != 2 or a.shape != (n, n) for a in As):
+                raise DimensionMismatch("size of Hs matrices must match P")  # diagnostics.jl:197-202
+            if shape is None:
+                shape, orient, si = (n, p), P.orientation, P.schurindex
+            if (n, p) != shape:
+                raise DimensionMismatch("the problems of a batch must have equal order and period")
+            if (P.orientation, P.schurindex) != (orient, si) or len(P.Z) != p:
+                raise DimensionMismatch("the problems of a batch must have equal order, period, orientation and schurindex")
+            sig = [bool(x) for x in getattr(P, "S", [True] * p)]
+            sig0 = sig if sig0 is None else sig0
+            if sig != sig0:
+                raise DimensionMismatch("the problems of a batch must have equal signatures S")
+            cplx = self._is_complex(P.Ts) or self._is_complex(As) or self._is_complex(P.Z)
+            kind = cplx if kind is None else kind
+            if cplx != kind:
+                raise TypeError("checkpsd_batch: the problems of a batch must be all real or all complex")
+            Tw += list(P.Ts)
+            Zw += list(P.Z)
+            Aw += As
+        dt = np.complex128 if kind else np.float64
+        Tw, Zw, Aw = ([np.asfortranarray(x, dtype=dt) for x in M] for M in (Tw, Zw, Aw))
+        n, p = shape
+        return self._checkpsd_batch_call(kind, False, nb, n, p, self._ptrs(Tw), self._ptrs(Zw), self._ptrs(Aw),
+                                         sig0 if S is None else S, orient, si, thresh, strict, details)
 
     def pschur_dev(self, dA_ptr, n, p, lr="R", dZ_ptr=None, wantT=True, maxitfac=30):
         """Device-resident pschur!: dA_ptr / dZ_ptr are device addresses of [p][n][n] column-major blocks."""

@@ -13,6 +13,19 @@ struct psd_devbuf {
     double* d() const { return (double*)p; }
 };
 
+// The verdict on one factor from its norms (diagnostics.jl:236-262), for the single and the batched path alike: o =
+// ||Z Z' - I||_F, r = ||Z_a T Z_b' - A||_F, t = ||tril(T, .)||_F, anorm = opnorm(A, 1).  *e receives the normalized error.
+inline bool checkpsd_verdict(int n, double o, double r, double t, double anorm, double thresh, int strict, double* e) {
+    const double eps = PSD_DBL_EPS;
+    bool good = true;
+    const double cmp = strict ? 0.0 : 10.0 * eps * n;
+    if (t > cmp) good = false;
+    if (o > 10.0 * eps * n) good = false;
+    *e = r / eps / anorm;
+    if (!(*e <= thresh)) good = false;
+    return good;
+}
+
 // T, Z, A: [p][n][n] device blocks in USER order (ES doubles per element).  err[p] (host) receives the normalized
 // factorization errors, orth[p] / tri[p] (host, optional) the orthogonality and triangularity norms.
 template <bool CPLX>
@@ -59,17 +72,10 @@ int checkpsd_dev(psd_ctx* c, int n, int p, const double* dT, const double* dZ, c
     PSD_CHECK(psd_rt_d2h(acc.data(), dacc, sizeof(double) * 5 * (size_t)p, c->stream));
     PSD_CHECK(psd_rt_sync(c->stream));
     PSD_CHECK(psd_rt_last_error());
-    const double eps = PSD_DBL_EPS;
     bool good = true;
     for (int l = 0; l < p; ++l) {
         const double o = sqrt(acc[5 * l + 0]), r = sqrt(acc[5 * l + 1]), t = sqrt(acc[5 * l + 2]);
-        const double anorm = acc[5 * l + 3];
-        const double cmp = strict ? 0.0 : 10.0 * eps * n;
-        if (t > cmp) good = false;
-        if (o > 10.0 * eps * n) good = false;
-        const double e = r / eps / anorm;
-        if (!(e <= thresh)) good = false;
-        err[l] = e;
+        if (!checkpsd_verdict(n, o, r, t, acc[5 * l + 3], thresh, strict, &err[l])) good = false;
         if (orth) orth[l] = o;
         if (tri) tri[l] = t;
     }
@@ -126,7 +132,13 @@ int psd_z_checkpsd(psd_ctx* c, int n, int p, double* const* T, double* const* Z,
     return checkpsd_host<true>(c, n, p, T, Z, A, S, orient, schurindex, nullptr, thresh, strict, err, orth, tri, ok, info);
 }
 
-int psd_d_checkpsd_dev(psd_ctx* c, int n, int p, const double* dT, const double* dZ, const double* dA, const uint8_t* S,
+}  // extern "C"
+
+namespace {
+
+// the device entry of either element type: operands already in HBM
+template <bool CPLX>
+int checkpsd_dev_entry(psd_ctx* c, int n, int p, const double* dT, const double* dZ, const double* dA, const uint8_t* S,
                        char orient, int schurindex, double thresh, int strict, double* err, double* orth, double* tri,
                        int* ok, int* info) {
     int dummy;
@@ -137,7 +149,23 @@ int psd_d_checkpsd_dev(psd_ctx* c, int n, int p, const double* dT, const double*
     if (orient != 'R' && orient != 'L') return *info = -8;
     if (schurindex < 1 || schurindex > p) return *info = -9;
     if (!err) return *info = -12;
-    return *info = checkpsd_dev<false>(c, n, p, dT, dZ, dA, S, orient, schurindex, nullptr, thresh, strict, err, orth, tri, ok);
+    return *info = checkpsd_dev<CPLX>(c, n, p, dT, dZ, dA, S, orient, schurindex, nullptr, thresh, strict, err, orth, tri, ok);
+}
+
+}  // namespace
+
+extern "C" {
+
+int psd_d_checkpsd_dev(psd_ctx* c, int n, int p, const double* dT, const double* dZ, const double* dA, const uint8_t* S,
+                       char orient, int schurindex, double thresh, int strict, double* err, double* orth, double* tri,
+                       int* ok, int* info) {
+    return checkpsd_dev_entry<false>(c, n, p, dT, dZ, dA, S, orient, schurindex, thresh, strict, err, orth, tri, ok, info);
+}
+
+int psd_z_checkpsd_dev(psd_ctx* c, int n, int p, const double* dT, const double* dZ, const double* dA, const uint8_t* S,
+                       char orient, int schurindex, double thresh, int strict, double* err, double* orth, double* tri,
+                       int* ok, int* info) {
+    return checkpsd_dev_entry<true>(c, n, p, dT, dZ, dA, S, orient, schurindex, thresh, strict, err, orth, tri, ok, info);
 }
 
 }  // extern "C"

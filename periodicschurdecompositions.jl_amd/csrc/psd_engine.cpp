@@ -19,6 +19,7 @@
 #include "psd_grord.h"
 #include "psd_rhessx.h"
 #include "psd_check.h"
+#include "psd_bcheck.h"
 #include "psd_krylov.h"
 #include "psd_evec.h"
 #include "psd_gevec.h"
@@ -302,6 +303,7 @@ struct psd_ctx {
     int zb_nmax = PSD_ZB_NMAX;  // largest order of the complex one-workgroup / one-wavefront-per-problem kernels (diagnostic build: PSD_ZB_NMAX in the environment, for the sweep that sets the constant)
     int bev_nmax = PSD_BEV_NMAX;  // largest order of the batched eigenvector kernels (diagnostic build: PSD_BEV_NMAX in the environment, for the sweep that sets the constant)
     int bord_nmax = PSD_BORD_NMAX;  // largest order of the batched reordering kernel (PSD_BORD_NMAX in the environment lowers it: the tests reach the fallback with it)
+    int bck_nmax = PSD_BCK_NMAX;    // largest order of the batched verifier (PSD_BCK_NMAX in the environment lowers it: the tests reach the fallback with it)
     int bord_w = 0;                 // PSD_BORD_W: a narrower window of the batched reordering kernel (0: bord_window's own choice)
     void slice(int p, int& lo, int& hi) const {  // [lo, hi), 0-based internal factor index
         const int base = p / shard_world, rem = p % shard_world;
@@ -1925,6 +1927,7 @@ int psd_create(psd_ctx** ctx, int device) {
     if (const char* e = psd_env_diag("PSD_GB_NMAX")) c->gb_nmax = (atoi(e) >= 1 && atoi(e) <= 2048) ? atoi(e) : PSD_GB_NMAX;
     if (const char* e = psd_env_diag("PSD_BEV_NMAX")) c->bev_nmax = (atoi(e) >= 1 && atoi(e) <= 2048) ? atoi(e) : PSD_BEV_NMAX;
     if (const char* e = psd_env("PSD_BORD_NMAX")) c->bord_nmax = (atoi(e) >= 1 && atoi(e) < PSD_BORD_NMAX) ? atoi(e) : PSD_BORD_NMAX;
+    if (const char* e = psd_env("PSD_BCK_NMAX")) c->bck_nmax = (atoi(e) >= 1 && atoi(e) < PSD_BCK_NMAX) ? atoi(e) : PSD_BCK_NMAX;
     if (const char* e = psd_env("PSD_BORD_W")) c->bord_w = (atoi(e) >= 1 && atoi(e) <= 32) ? atoi(e) : 0;  // (each kernel has its own least window: PSD_BORD_WMIN, PSD_ZBORD_WMIN)
     if (const char* e = psd_env("PSD_BAND_HELPER")) c->band_helper = atoi(e);
     if (const char* e = psd_env_diag("PSD_TRAIN_LONG")) c->train_long = atoi(e);
@@ -3966,4 +3969,5 @@ extern "C" int psd_dbg_apply_bench(psd_ctx* c, int n, int p, int nwin, int W, in
 #include "psd_zbord_host.inl"
 #include "psd_zgbord_host.inl"
 #include "psd_gbord_host.inl"
+#include "psd_bcheck_host.inl"
 #include "psd_diag_scalar.inl"
