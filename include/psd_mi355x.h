@@ -754,6 +754,63 @@ int psd_z_eigvecs_batch_dev(psd_ctx* ctx, int nb, int n, int p, const double* dT
                             const uint8_t* select, int shifted, double* dV, int maxvec, int* nvec, int32_t* pcnt,
                             psd_bevec_stats* stats, int* info);
 
+/* ---- leigvecs_batch: LEFT eigenvectors of many small periodic Schur forms in one call ------------------------------
+ * The side = 'L' of xTREVC in periodic form, for the decompositions psd_d_eigvecs_batch / psd_z_eigvecs_batch take:
+ * W_1 .. W_p (or W_1 alone without shifted) with, mu_j being the principal p-th root of eigenvalue j exactly as the right
+ * entries take it and l + 1 cyclic,
+ *     orient 'L' (right vectors: A_l v_l = mu v_{l+1}):   w_{l+1}^H A_l = mu w_l^H
+ *     orient 'R' (right vectors: A_l v_{l+1} = mu v_l):   w_l^H A_l = mu w_{l+1}^H
+ * so that w_l is a left and v_l a right eigenvector of the same cyclic shift of the product, and w_l^H v_l is the same
+ * number for every l.  Column j of W belongs to the eigenvalue of column j of V.  Everything else is the right entry's
+ * contract, word for word: select completed to conjugate pairs (real), columns top to bottom, ||W_1(:, j)|| = 1 with
+ * the largest-modulus entry real and positive and the same factor on every W_l(:, j), the partner of a pair the exact
+ * conjugate, a zero eigenvalue a NaN column (counted), small pivots replaced by smin (counted), columns past 2^500
+ * rescaled by a power of two (counted), the inputs not modified, the padding columns written as zeros, V = NULL a size
+ * query, a problem's bits independent of its place in the batch and of the grouping.
+ *
+ * No second solver: the adjoints of the left relations are a periodic problem of the opposite orientation whose Schur
+ * form is T'_l = J T_l^H J, Z'_l = Z_l J (J the reversal permutation), eigenvalues conjugated and reversed, schurindex
+ * unchanged.  One launch writes T' and Z' of a group into workspace, the launches of the right entry run on them with
+ * the conjugates of the caller's roots, and one launch turns the columns into the caller's order: stats->nlaunch is the
+ * right call's count plus two, whatever nb and n are.  Above order 128 the single driver runs on the flipped slices.
+ * Arguments, info codes and stats: those of psd_d_eigvecs_batch[_dev] and psd_z_eigvecs_batch[_dev] respectively. */
+int psd_d_leigvecs_batch(psd_ctx* ctx, int nb, int n, int p, double* const* T, double* const* Z, const double* wr,
+                         const double* wi, char orient, int schurindex, uint8_t* select, int shifted, double* const* V,
+                         int maxvec, int* nvec, int32_t* pcnt, psd_bevec_stats* stats, int* info);
+int psd_d_leigvecs_batch_dev(psd_ctx* ctx, int nb, int n, int p, const double* dT, const double* dZ, const double* wr,
+                             const double* wi, char orient, int schurindex, uint8_t* select, int shifted, double* dV,
+                             int maxvec, int* nvec, int32_t* pcnt, psd_bevec_stats* stats, int* info);
+int psd_z_leigvecs_batch(psd_ctx* ctx, int nb, int n, int p, double* const* T, double* const* Z, const double* alpha,
+                         const double* beta, const int32_t* ascale, char orient, int schurindex, const uint8_t* select,
+                         int shifted, double* const* V, int maxvec, int* nvec, int32_t* pcnt, psd_bevec_stats* stats,
+                         int* info);
+int psd_z_leigvecs_batch_dev(psd_ctx* ctx, int nb, int n, int p, const double* dT, const double* dZ, const double* alpha,
+                             const double* beta, const int32_t* ascale, char orient, int schurindex,
+                             const uint8_t* select, int shifted, double* dV, int maxvec, int* nvec, int32_t* pcnt,
+                             psd_bevec_stats* stats, int* info);
+
+/* ---- eigcond_batch: reciprocal condition numbers of the eigenvalues, per factor -------------------------------------
+ * The S of xTRSNA in periodic form (for p = 1 exactly that), from the right and left vectors of EVERY factor as the
+ * eigenvector entries write them with shifted (nmat = p; complex interleaved for both families):
+ *     orient 'L':   s[l, j] = |w_l^H v_l| / (||w_{l+1}||_2 ||v_l||_2)
+ *     orient 'R':   s[l, j] = |w_l^H v_l| / (||w_l||_2 ||v_{l+1}||_2)
+ * To first order d lambda_j / lambda_j = (1 / mu_j) sum_l w_{l+1}^H dA_l v_l / (w_1^H v_1) for 'L' (for 'R' the sum runs
+ * over w_l^H dA_l v_{l+1}), hence |d lambda_j / lambda_j| <= sum_l ||dA_l||_2 / (|mu_j| s[l, j]).  A NaN column (a zero
+ * eigenvalue) gives NaN.  One wavefront per (problem, column), every sum in a fixed order, no atomics: s does not depend
+ * on the batch or the grouping, bit for bit.
+ *
+ * V, W: nb * p pointers to n x maxvec complex interleaved column-major blocks (problem-major).  nvec: host [nb], the
+ * columns of every problem.  s: host [nb][maxvec][p], out; the entries of the columns at and beyond nvec[q] are 0.
+ * info: 0; -1 ctx NULL; -2 n < 1; -3 p < 1; -4 V NULL; -5 W NULL; -7 orient; -10 maxvec < 1 or an nvec[q] outside
+ * 0..maxvec; -11 nb < 0; -12 nvec NULL; -13 s NULL; PSD_INFO_NOTIMPL on a period-sharded context; PSD_INFO_RUNTIME + k.
+ * nb == 0 returns 0 and touches nothing. */
+int psd_eigcond_batch(psd_ctx* ctx, int nb, int n, int p, double* const* V, double* const* W, char orient, int maxvec,
+                      const int* nvec, double* s, int* info);
+/* Device-resident variant: dV, dW device blocks [nb][p][maxvec][n] of interleaved complex values, as
+ * psd_?_eigvecs_batch_dev and psd_?_leigvecs_batch_dev leave them with shifted.  nvec and s are host arrays. */
+int psd_eigcond_batch_dev(psd_ctx* ctx, int nb, int n, int p, const double* dV, const double* dW, char orient,
+                          int maxvec, const int* nvec, double* s, int* info);
+
 /* ---- zgeigvecs_batch: eigenvectors of many small signed ComplexF64 periodic Schur forms in one call ----------------
  * psd_z_geigvecs (homogeneous back-substitution, the periodic form of xTGEVC) for nb generalized decompositions of one
  * shape (n, p) and ONE signature, as psd_z_gpschur_batch / psd_z_gordschur_batch leave them: ComplexF64, one orient and

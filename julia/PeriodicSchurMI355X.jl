@@ -24,7 +24,7 @@ import PeriodicSchurDecompositions: pschur!, pschur, phessenberg!, gpschur, Peri
 const PSD = PeriodicSchurDecompositions
 using ArnoldiMethod: ArnoldiMethod
 
-export set_train!, engine_version, pschur_batch!, pschur_batch, gpschur_batch, eigvecs_batch_device, geigvecs_batch_device, ordschur_batch!, checkpsd_batch
+export set_train!, engine_version, pschur_batch!, pschur_batch, gpschur_batch, eigvecs_batch_device, eigcond_batch, geigvecs_batch_device, ordschur_batch!, checkpsd_batch
 
 const libpsd = get(ENV, "LIBPSD_MI355X", joinpath(@__DIR__, "..", "periodicschurdecompositions.jl_amd", "libpsd_mi355x.so"))
 
@@ -515,9 +515,15 @@ end
 # problem; completed to conjugate pairs.  A problem whose flags are all false costs nothing and gets n x 0 matrices (skip
 # the problems whose pschur_batch! code was non-zero that way).  Returns, per problem, the p (shifted) or 1 matrices of
 # eigvecs_device.
-function eigvecs_batch_device(problems::Vector{<:PeriodicSchur{Float64}}, select::AbstractVector; shifted::Bool = true)
+# `side`: :R the right eigenvectors; :L the LEFT eigenvectors W in the same shapes (psd_d_leigvecs_batch: with mu the root of
+# the right vectors, w_{l+1}' A_l = mu w_l' for orientation 'L' and w_l' A_l = mu w_{l+1}' for 'R'; column j of W belongs to
+# the eigenvalue of column j of V and w_l' v_l does not depend on l); :B the pair (V, W).  (The `side` keyword is written by
+# analogy with Engine.eigvecs_batch(..., side=...), the tested mirror; not run.)
+function eigvecs_batch_device(problems::Vector{<:PeriodicSchur{Float64}}, select::AbstractVector; shifted::Bool = true,
+                              side::Symbol = :R)
+    side in (:R, :L, :B) || throw(ArgumentError("side must be :R, :L or :B"))
     nb = length(problems)
-    nb == 0 && return Vector{Matrix{ComplexF64}}[]
+    nb == 0 && return side == :B ? (Vector{Matrix{ComplexF64}}[], Vector{Matrix{ComplexF64}}[]) : Vector{Matrix{ComplexF64}}[]
     ps1 = problems[1]
     p = ps1.period; n = size(ps1.T1, 1); js = ps1.schurindex; orient = ps1.orientation
     (isempty(ps1.Z) || size(ps1.Z[1], 1) == 0) && throw(ArgumentError("eigvecs requires Schur vectors in the PSD"))
@@ -536,30 +542,40 @@ function eigvecs_batch_device(problems::Vector{<:PeriodicSchur{Float64}}, select
     nvec = zeros(Cint, nb); info = Ref{Cint}(0)
     Tp = _ptrs(T); Zp = _ptrs(Z)
     nmat = shifted ? p : 1
-    call(Vp, maxvec) = ccall((:psd_d_eigvecs_batch, libpsd), Cint,
+    call(Vp, maxvec, left) = left ?
+        ccall((:psd_d_leigvecs_batch, libpsd), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ptr{Float64}, Ptr{Float64}, Cchar, Cint,
+         Ptr{UInt8}, Cint, Ptr{Ptr{ComplexF64}}, Cint, Ptr{Cint}, Ptr{Int32}, Ptr{Cvoid}, Ref{Cint}),
+        ctx().ptr, nb, n, p, Tp, Zp, wr, wi, orient, js, sel, shifted, Vp, maxvec, nvec, C_NULL, C_NULL, info) :
+        ccall((:psd_d_eigvecs_batch, libpsd), Cint,
         (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ptr{Float64}, Ptr{Float64}, Cchar, Cint,
          Ptr{UInt8}, Cint, Ptr{Ptr{ComplexF64}}, Cint, Ptr{Cint}, Ptr{Int32}, Ptr{Cvoid}, Ref{Cint}),
         ctx().ptr, nb, n, p, Tp, Zp, wr, wi, orient, js, sel, shifted, Vp, maxvec, nvec, C_NULL, C_NULL, info)
     GC.@preserve T Z wr wi sel nvec begin
-        call(C_NULL, 0)                                   # size query: select completed, nvec
+        call(C_NULL, 0, false)                            # size query: select completed, nvec
         info[] != 0 && _throw(info[])
         maxvec = Int(maximum(nvec))
-        V = [zeros(ComplexF64, n, maxvec) for _ in 1:(nb * nmat)]
-        Vp = [pointer(v) for v in V]
-        GC.@preserve V Vp begin
-            call(Vp, maxvec)
+        out = map(side == :B ? (false, true) : (side == :L,)) do left
+            V = [zeros(ComplexF64, n, maxvec) for _ in 1:(nb * nmat)]
+            Vp = [pointer(v) for v in V]
+            GC.@preserve V Vp begin
+                call(Vp, maxvec, left)
+            end
+            info[] != 0 && _throw(info[])
+            [[V[(q - 1) * nmat + l][:, 1:nvec[q]] for l in 1:nmat] for q in 1:nb]
         end
-        info[] != 0 && _throw(info[])
-        return [[V[(q - 1) * nmat + l][:, 1:nvec[q]] for l in 1:nmat] for q in 1:nb]
+        return side == :B ? out : out[1]
     end
 end
 
 # eigvecs_batch_device for ComplexF64 decompositions (psd_z_eigvecs_batch), the follow-up of the complex pschur_batch!: the
 # contract above, except that `select` is used as given — a complex form has no conjugate pairs to complete.  The
-# eigenvalues go in as alpha = values, beta = 1, ascale = NULL.
-function eigvecs_batch_device(problems::Vector{<:PeriodicSchur{ComplexF64}}, select::AbstractVector; shifted::Bool = true)
+# eigenvalues go in as alpha = values, beta = 1, ascale = NULL.  `side` as above (psd_z_leigvecs_batch; not run).
+function eigvecs_batch_device(problems::Vector{<:PeriodicSchur{ComplexF64}}, select::AbstractVector; shifted::Bool = true,
+                              side::Symbol = :R)
+    side in (:R, :L, :B) || throw(ArgumentError("side must be :R, :L or :B"))
     nb = length(problems)
-    nb == 0 && return Vector{Matrix{ComplexF64}}[]
+    nb == 0 && return side == :B ? (Vector{Matrix{ComplexF64}}[], Vector{Matrix{ComplexF64}}[]) : Vector{Matrix{ComplexF64}}[]
     ps1 = problems[1]
     p = ps1.period; n = size(ps1.T1, 1); js = ps1.schurindex; orient = ps1.orientation
     (isempty(ps1.Z) || size(ps1.Z[1], 1) == 0) && throw(ArgumentError("eigvecs requires Schur vectors in the PSD"))
@@ -578,22 +594,60 @@ function eigvecs_batch_device(problems::Vector{<:PeriodicSchur{ComplexF64}}, sel
     nvec = zeros(Cint, nb); info = Ref{Cint}(0)
     Tp = _ptrs(T); Zp = _ptrs(Z)
     nmat = shifted ? p : 1
-    call(Vp, maxvec) = ccall((:psd_z_eigvecs_batch, libpsd), Cint,
+    call(Vp, maxvec, left) = left ?
+        ccall((:psd_z_leigvecs_batch, libpsd), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ptr{ComplexF64}, Ptr{Float64}, Ptr{Int32},
+         Cchar, Cint, Ptr{UInt8}, Cint, Ptr{Ptr{ComplexF64}}, Cint, Ptr{Cint}, Ptr{Int32}, Ptr{Cvoid}, Ref{Cint}),
+        ctx().ptr, nb, n, p, Tp, Zp, α, β, C_NULL, orient, js, sel, shifted, Vp, maxvec, nvec, C_NULL, C_NULL, info) :
+        ccall((:psd_z_eigvecs_batch, libpsd), Cint,
         (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ptr{ComplexF64}, Ptr{Float64}, Ptr{Int32},
          Cchar, Cint, Ptr{UInt8}, Cint, Ptr{Ptr{ComplexF64}}, Cint, Ptr{Cint}, Ptr{Int32}, Ptr{Cvoid}, Ref{Cint}),
         ctx().ptr, nb, n, p, Tp, Zp, α, β, C_NULL, orient, js, sel, shifted, Vp, maxvec, nvec, C_NULL, C_NULL, info)
     GC.@preserve T Z α β sel nvec begin
-        call(C_NULL, 0)                                   # size query: nvec
+        call(C_NULL, 0, false)                            # size query: nvec
         info[] != 0 && _throw(info[])
         maxvec = Int(maximum(nvec))
-        V = [zeros(ComplexF64, n, maxvec) for _ in 1:(nb * nmat)]
-        Vp = [pointer(v) for v in V]
-        GC.@preserve V Vp begin
-            call(Vp, maxvec)
+        out = map(side == :B ? (false, true) : (side == :L,)) do left
+            V = [zeros(ComplexF64, n, maxvec) for _ in 1:(nb * nmat)]
+            Vp = [pointer(v) for v in V]
+            GC.@preserve V Vp begin
+                call(Vp, maxvec, left)
+            end
+            info[] != 0 && _throw(info[])
+            [[V[(q - 1) * nmat + l][:, 1:nvec[q]] for l in 1:nmat] for q in 1:nb]
         end
-        info[] != 0 && _throw(info[])
-        return [[V[(q - 1) * nmat + l][:, 1:nvec[q]] for l in 1:nmat] for q in 1:nb]
+        return side == :B ? out : out[1]
     end
+end
+
+# eigcond_batch(problems, select) — no reference equivalent: the reciprocal condition numbers of the eigenvalues of many
+# small decompositions (Float64 or ComplexF64, as eigvecs_batch_device takes them) with respect to every factor, the S of
+# xTRSNA in periodic form (psd_eigcond_batch), with the right and left eigenvectors of every factor they are computed
+# from.  Returns (s, V, W): V, W as eigvecs_batch_device(problems, select; side = :B) returns them, s[q] a p x nvec_q
+# matrix, s[q][l, j] = |w_l' v_l| / (||w_{l+1}|| ||v_l||) for orientation 'L' and |w_l' v_l| / (||w_l|| ||v_{l+1}||) for 'R'
+# (l + 1 cyclic): to first order |dλ_j / λ_j| <= sum_l ||dA_l|| / (|μ_j| s[q][l, j]).  A zero eigenvalue gives NaN.
+# (Written by analogy with Engine.eigcond_batch, the tested mirror; not run.)
+function eigcond_batch(problems::Vector{<:PeriodicSchur}, select::AbstractVector)
+    V, W = eigvecs_batch_device(problems, select; shifted = true, side = :B)
+    nb = length(problems)
+    nb == 0 && return (Matrix{Float64}[], V, W)
+    ps1 = problems[1]
+    p = ps1.period; n = size(ps1.T1, 1)
+    nvec = Cint[size(V[q][1], 2) for q in 1:nb]
+    maxvec = Int(maximum(nvec))
+    maxvec == 0 && return ([zeros(Float64, p, 0) for _ in 1:nb], V, W)
+    pad(X) = [(B = zeros(ComplexF64, n, maxvec); B[:, 1:size(x, 2)] .= x; B) for Xq in X for x in Xq]
+    Vb = pad(V); Wb = pad(W)
+    Vp = [pointer(b) for b in Vb]; Wp = [pointer(b) for b in Wb]
+    s = zeros(Float64, p, maxvec, nb); info = Ref{Cint}(0)
+    GC.@preserve Vb Wb Vp Wp nvec s begin
+        ccall((:psd_eigcond_batch, libpsd), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Ptr{ComplexF64}}, Ptr{Ptr{ComplexF64}}, Cchar, Cint, Ptr{Cint}, Ptr{Float64},
+               Ref{Cint}),
+              ctx().ptr, nb, n, p, Vp, Wp, ps1.orientation, maxvec, nvec, s, info)
+    end
+    info[] != 0 && _throw(info[])
+    return ([s[:, 1:nvec[q], q] for q in 1:nb], V, W)
 end
 
 # geigvecs_batch_device(problems, select; shifted) — geigvecs_device for many small signed ComplexF64 decompositions of one

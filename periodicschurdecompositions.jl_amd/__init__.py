@@ -407,6 +407,8 @@ class Engine:
                 sigs[f"psd_{t}_eigvecs_batch{dev}"] = (head + [mats, mats] + eig + [C.c_char, C.c_int, u8p, C.c_int, mats,
                                                                                     C.c_int, ip, i32p,
                                                                                     C.POINTER(BevecStats), ip])
+                sigs[f"psd_{t}_leigvecs_batch{dev}"] = sigs[f"psd_{t}_eigvecs_batch{dev}"]  # (the left vectors)
+                sigs[f"psd_eigcond_batch{dev}"] = head + [mats, mats, C.c_char, C.c_int, ip, dp, ip]
                 # (no eigenvalue arguments: the signature, and the scalars a behind maxvec)
                 sigs[f"psd_{t}_geigvecs_batch{dev}"] = (head + [mats, mats, u8p, C.c_char, C.c_int, u8p, C.c_int, mats,
                                                                 C.c_int, dp, ip, i32p, C.POINTER(BevecStats), ip])
@@ -1893,15 +1895,15 @@ class Engine:
                              "(its length must correspond to the rank of the Schur space)")  # vectors.jl:34-36
         return np.ascontiguousarray(sel.astype(bool), dtype=np.uint8)
 
-    def _eigvecs_batch_call(self, fam, dev, nb, n, p, T, Z, ev, orient, si, sel, shifted, V=None, maxvec=0):
-        """One call of psd_?_eigvecs_batch[_dev] on packed factors (T, Z, V: ctypes arguments; ev: the eigenvalue
-        arguments).  Without V the size query (select completed); with V the stats and counters of the call are left in
-        self.eigvecs_batch_*.  Returns the vectors per problem, nvec."""
+    def _eigvecs_batch_call(self, fam, dev, nb, n, p, T, Z, ev, orient, si, sel, shifted, V=None, maxvec=0, left=False):
+        """One call of psd_?_eigvecs_batch[_dev] (left: psd_?_leigvecs_batch[_dev]) on packed factors (T, Z, V: ctypes
+        arguments; ev: the eigenvalue arguments).  Without V the size query (select completed); with V the stats and
+        counters of the call are left in self.eigvecs_batch_*.  Returns the vectors per problem, nvec."""
         nvec = (C.c_int * nb)()
         cnts = np.zeros((nb, 3), dtype=np.int32)
         st = BevecStats()
         info = C.c_int(0)
-        fn = getattr(self.lib, f"psd_{fam.tag}_eigvecs_batch{'_dev' if dev else ''}")
+        fn = getattr(self.lib, f"psd_{fam.tag}_{'l' if left else ''}eigvecs_batch{'_dev' if dev else ''}")
         fn(self.ctx, nb, n, p, T, Z, *self._evec_ptrs(ev), orient.encode(), int(si),
            sel.ctypes.data_as(C.POINTER(C.c_uint8)), int(bool(shifted)), V, maxvec, nvec,
            cnts.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(st), C.byref(info))
@@ -1932,22 +1934,39 @@ class Engine:
             self.eigvecs_batch_counts = cnts
         return nvec, a
 
-    def _eigvecs_batch(self, fam, name, wrong, problems, args, shifted, lr, schurindex):
+    @staticmethod
+    def _bevec_sides(side):
+        """the calls of side = "R" (right vectors), "L" (left) or "B" (both): whether each is the left entry"""
+        try:
+            return {"R": (False,), "L": (True,), "B": (False, True)}[side]
+        except (KeyError, TypeError):
+            raise ValueError(f'side must be "R", "L" or "B", not {side!r}') from None
+
+    def _eigvecs_batch(self, fam, name, wrong, problems, args, shifted, lr, schurindex, side="R"):
         """eigvecs_batch / zeigvecs_batch."""
+        sides = self._bevec_sides(side)
         if hasattr(problems, "data_ptr"):
             if len(args) != 3:
                 raise TypeError(f"{name}(T, Z, values, select, lr=..., schurindex=...)")
-            return self._eigvecs_batch_dev(fam, name, wrong, problems, args[0], args[1], args[2], lr, schurindex, shifted)
+            Vs, nvec = self._eigvecs_batch_dev(fam, name, wrong, problems, args[0], args[1], args[2], lr, schurindex,
+                                               shifted, sides)
+            return (*Vs, nvec)
         if len(args) != 1:
             raise TypeError(f"{name}(problems, select, shifted=True)")
-        problems = list(problems)
+        Vs, nvec, _, _ = self._eigvecs_batch_host(fam, name, wrong, list(problems), args[0], shifted, sides)
+        out = [[[np.asfortranarray(v[:, :nvec[q]]) for v in Vq] for q, Vq in enumerate(V)] for V in Vs]
+        return out[0] if len(sides) == 1 else tuple(out)
+
+    def _eigvecs_batch_host(self, fam, name, wrong, problems, select, shifted, sides):
+        """The list form of _eigvecs_batch and eigcond_batch: per side the blocks as the entry leaves them (per problem
+        nmat matrices n x maxvec), and nvec, n, maxvec."""
         nb = len(problems)
         if nb == 0:
             self.eigvecs_batch_stats = BevecStats()
             self.eigvecs_batch_counts = np.zeros((0, 3), dtype=np.int32)
-            return []
+            return [[] for _ in sides], [], 0, 0
         n, p, orient, si, Ts, Zs = self._batch_decomps(fam, name, wrong, problems, needZ=True, work=False)
-        sel = self._batch_select(args[0], nb, n)
+        sel = self._batch_select(select, nb, n)
         if fam is _D:
             vals = np.array([np.asarray(ps.values, dtype=np.complex128) for ps in problems])
             ev = [np.ascontiguousarray(vals.real), np.ascontiguousarray(vals.imag)]
@@ -1955,13 +1974,17 @@ class Engine:
             vals = [self._evec_values(ps, True) for ps in problems]
             ev = [np.ascontiguousarray(np.array([v[k] for v in vals])) for k in range(3)]
         call = (fam, False, nb, n, p, self._ptrs(Ts), self._ptrs(Zs), ev, orient, si, sel, shifted)
-        maxvec = max(self._eigvecs_batch_call(*call))
+        maxvec = max(self._eigvecs_batch_call(*call, left=sides[0]))
         nmat = p if shifted else 1
-        Vs = [np.zeros((n, maxvec), dtype=np.complex128, order="F") for _ in range(nb * nmat)]
-        nvec = self._eigvecs_batch_call(*call, self._ptrs(Vs), maxvec)
-        return [[np.asfortranarray(Vs[q * nmat + l][:, :nvec[q]]) for l in range(nmat)] for q in range(nb)]
+        out = []
+        for left in sides:
+            Vs = [np.zeros((n, maxvec), dtype=np.complex128, order="F") for _ in range(nb * nmat)]
+            nvec = self._eigvecs_batch_call(*call, self._ptrs(Vs), maxvec, left=left)
+            out.append([Vs[q * nmat:(q + 1) * nmat] for q in range(nb)])
+        return out, list(nvec), n, maxvec
 
-    def _eigvecs_batch_dev(self, fam, name, wrong, T, Z, values, select, lr, schurindex, shifted):
+    def _eigvecs_batch_dev(self, fam, name, wrong, T, Z, values, select, lr, schurindex, shifted, sides=(False,)):
+        """The device form: the blocks [nb, nmat, n, maxvec] of every side, and nvec."""
         import torch
 
         if Z is None:
@@ -1972,7 +1995,8 @@ class Engine:
         if nb == 0:
             self.eigvecs_batch_stats = BevecStats()
             self.eigvecs_batch_counts = np.zeros((0, 3), dtype=np.int32)
-            return torch.zeros((0, nmat, n, 0), dtype=torch.complex128, device=T.device), np.zeros(0, dtype=np.int32)
+            return ([torch.zeros((0, nmat, n, 0), dtype=torch.complex128, device=T.device) for _ in sides],
+                    np.zeros(0, dtype=np.int32))
         sel = self._batch_select(select, nb, n)
         vals = np.ascontiguousarray(values, dtype=np.complex128)
         if vals.shape != (nb, n):
@@ -1984,15 +2008,75 @@ class Engine:
         call = (fam, True, nb, n, p, C.c_void_p(dT.data_ptr()), C.c_void_p(dZ.data_ptr()), ev, orient, schurindex, sel,
                 shifted)
         torch.cuda.synchronize(T.device)
-        maxvec = max(self._eigvecs_batch_call(*call))
-        dV = torch.empty((nb, nmat, max(maxvec, 1), n), dtype=torch.complex128, device=T.device)
-        if maxvec == 0:
-            dV.zero_()
-        torch.cuda.synchronize(T.device)
-        nvec = self._eigvecs_batch_call(*call, C.c_void_p(dV.data_ptr()), max(maxvec, 1))
-        return dV[:, :, :maxvec, :].transpose(2, 3), np.array(list(nvec), dtype=np.int32)
+        maxvec = max(self._eigvecs_batch_call(*call, left=sides[0]))
+        out = []
+        for left in sides:
+            dV = torch.empty((nb, nmat, max(maxvec, 1), n), dtype=torch.complex128, device=T.device)
+            if maxvec == 0:
+                dV.zero_()
+            torch.cuda.synchronize(T.device)
+            nvec = self._eigvecs_batch_call(*call, C.c_void_p(dV.data_ptr()), max(maxvec, 1), left=left)
+            out.append(dV[:, :, :maxvec, :].transpose(2, 3))
+        return out, np.array(list(nvec), dtype=np.int32)
 
-    def eigvecs_batch(self, problems, *args, shifted=True, lr="R", schurindex=1):
+    def eigcond_batch(self, problems, *args, lr="R", schurindex=1):
+        """Reciprocal condition numbers of the eigenvalues of MANY small periodic Schur decompositions with respect to
+        every factor (psd_eigcond_batch: the periodic form of xTRSNA's S), with the right and left eigenvectors they are
+        computed from.  Float64 or ComplexF64, picked from the dtype; all-true signature.
+
+        eigcond_batch(problems, select): returns (s, V, W); V and W what eigvecs_batch(problems, select, side="B")
+        returns (every factor's vectors), s a list of [p, nvec_q] arrays.
+        eigcond_batch(T, Z, values, select, lr=..., schurindex=...): the device form; returns (s, V, W, nvec) with V, W
+        as the device form of eigvecs_batch returns them and s a host array [nb, p, maxvec] (zero at and beyond nvec[q]).
+
+        With mu_j the principal p-th root of eigenvalue j, v_l and w_l its right and left vectors (l + 1 cyclic):
+        lr "L": s[l, j] = |w_l' v_l| / (||w_{l+1}|| ||v_l||);  lr "R": s[l, j] = |w_l' v_l| / (||w_l|| ||v_{l+1}||).
+        To first order |d lambda_j / lambda_j| <= sum_l ||dA_l||_2 / (|mu_j| s[l, j]).  A zero eigenvalue gives NaN.
+        The stats of the eigenvector calls are left as by eigvecs_batch(..., side="B")."""
+        sides = (False, True)
+        if hasattr(problems, "data_ptr"):
+            if len(args) != 3:
+                raise TypeError("eigcond_batch(T, Z, values, select, lr=..., schurindex=...)")
+            fam = _Z if problems.is_complex() else _D
+            wrong = TypeError("eigcond_batch: T and Z must both be float64 or both complex128")
+            (V, W), nvec = self._eigvecs_batch_dev(fam, "eigcond_batch", wrong, problems, args[0], args[1], args[2], lr,
+                                                   schurindex, True, sides)
+            nb, p, n, maxvec = V.shape
+            s = np.zeros((nb, maxvec, p))
+            if nb > 0 and maxvec > 0:
+                # (the blocks behind the views: [nb][p][maxvec][n], contiguous)
+                dV, dW = V.transpose(2, 3), W.transpose(2, 3)
+                assert dV.is_contiguous() and dW.is_contiguous()
+                self._eigcond_call(True, nb, n, p, C.c_void_p(dV.data_ptr()), C.c_void_p(dW.data_ptr()), char_lr(lr),
+                                   maxvec, nvec, s)
+            return np.ascontiguousarray(s.transpose(0, 2, 1)), V, W, nvec
+        if len(args) != 1:
+            raise TypeError("eigcond_batch(problems, select)")
+        problems = list(problems)
+        fam = _Z if problems and len(problems[0].Ts) > 0 and np.iscomplexobj(problems[0].Ts[0]) else _D
+        wrong = TypeError("eigcond_batch: the problems of a batch must all be Float64 or all ComplexF64")
+        (V, W), nvec, n, maxvec = self._eigvecs_batch_host(fam, "eigcond_batch", wrong, problems, args[0], True, sides)
+        nb = len(problems)
+        if nb == 0:
+            return [], [], []
+        p = len(V[0])
+        s = np.zeros((nb, maxvec, p))
+        if maxvec > 0:
+            self._eigcond_call(False, nb, n, p, self._ptrs([v for Vq in V for v in Vq]),
+                               self._ptrs([w for Wq in W for w in Wq]), problems[0].orientation, maxvec, nvec, s)
+        trim = [[[np.asfortranarray(v[:, :nvec[q]]) for v in Xq] for q, Xq in enumerate(X)] for X in (V, W)]
+        return [np.ascontiguousarray(s[q, :nvec[q], :].T) for q in range(nb)], trim[0], trim[1]
+
+    def _eigcond_call(self, dev, nb, n, p, V, W, orient, maxvec, nvec, s):
+        """psd_eigcond_batch[_dev] on the blocks of both sides (V, W: ctypes arguments); s [nb][maxvec][p] is filled"""
+        info = C.c_int(0)
+        nv = (C.c_int * nb)(*[int(x) for x in nvec])
+        fn = getattr(self.lib, "psd_eigcond_batch_dev" if dev else "psd_eigcond_batch")
+        fn(self.ctx, nb, n, p, V, W, orient.encode(), maxvec, nv, s.ctypes.data_as(C.POINTER(C.c_double)),
+           C.byref(info))
+        self._raise(info.value)
+
+    def eigvecs_batch(self, problems, *args, shifted=True, lr="R", schurindex=1, side="R"):
         """eigvecs(ps, select; shifted) by periodic back-substitution for MANY small decompositions of one shape in ONE
         call (psd_d_eigvecs_batch): the follow-up of pschur_batch.  Float64, all-true signature.  Per problem the result
         contract is that of `_eigvecs_backsub`; a problem's vectors do not depend on its place in the batch.
@@ -2008,11 +2092,17 @@ class Engine:
         problem whose row is all false costs nothing and gets no columns: that is how to skip the problems whose
         pschur_batch info was non-zero.  The stats of the call are left in `self.eigvecs_batch_stats` (BevecStats), the
         per-problem counters (perturbed pivots, rescaled columns, zero eigenvalues) in `self.eigvecs_batch_counts`
-        ([nb, 3])."""
-        wrong = NotImplementedPSD("eigvecs_batch: Float64 only (ComplexF64 problems: zeigvecs_batch)")
-        return self._eigvecs_batch(_D, "eigvecs_batch", wrong, problems, args, shifted, lr, schurindex)
+        ([nb, 3]).
 
-    def zeigvecs_batch(self, problems, *args, shifted=True, lr="R", schurindex=1):
+        `side`: "R" the right eigenvectors (A_l v_l = mu v_{l+1} for lr "L", A_l v_{l+1} = mu v_l for lr "R"); "L" the
+        left eigenvectors W in the same shapes (psd_d_leigvecs_batch: w_{l+1}' A_l = mu w_l' for lr "L",
+        w_l' A_l = mu w_{l+1}' for lr "R", with the same root mu and the same contract otherwise; column j of W belongs
+        to the eigenvalue of column j of V, and w_l' v_l does not depend on l); "B" both: (V, W) for the list form,
+        (V, W, nvec) for the device form, the stats and counters those of the left call."""
+        wrong = NotImplementedPSD("eigvecs_batch: Float64 only (ComplexF64 problems: zeigvecs_batch)")
+        return self._eigvecs_batch(_D, "eigvecs_batch", wrong, problems, args, shifted, lr, schurindex, side)
+
+    def zeigvecs_batch(self, problems, *args, shifted=True, lr="R", schurindex=1, side="R"):
         """eigvecs(ps, select; shifted) by periodic back-substitution for MANY small ComplexF64 decompositions of one
         shape in ONE call (psd_z_eigvecs_batch): the follow-up of zpschur_batch, the complex counterpart of
         eigvecs_batch.  All-true signature.  Per problem the result contract is that of `_eigvecs_backsub`; a problem's
@@ -2027,9 +2117,10 @@ class Engine:
 
         `select`: [nb][n] flags, or one [n] row used for every problem, used as given.  A problem whose row is all false
         costs nothing and gets no columns.  Stats and counters are left in `self.eigvecs_batch_stats` and
-        `self.eigvecs_batch_counts`, as by eigvecs_batch."""
+        `self.eigvecs_batch_counts`, as by eigvecs_batch.  `side`: "R", "L" (psd_z_leigvecs_batch) or "B", as for
+        eigvecs_batch."""
         wrong = TypeError("zeigvecs_batch: ComplexF64 only (Float64 problems: eigvecs_batch)")
-        return self._eigvecs_batch(_Z, "zeigvecs_batch", wrong, problems, args, shifted, lr, schurindex)
+        return self._eigvecs_batch(_Z, "zeigvecs_batch", wrong, problems, args, shifted, lr, schurindex, side)
 
     def _geigvecs_batch(self, fam, name, wrong, problems, args, shifted, lr, schurindex, S):
         """zgeigvecs_batch / dgeigvecs_batch."""

@@ -10,6 +10,10 @@
 // The complex and signed drivers (psd_zbevec_host.inl, psd_zgbevec_host.inl, psd_gbevec_host.inl) come in behind this
 // file and share the argument checks, the call description, bevec_itab, bevec_launch, the single-path loop, the
 // statistics and the bodies of the two kinds of entry (bevec_entry_dev, bevec_entry_host).
+//
+// psd_d_leigvecs_batch / psd_d_leigvecs_batch_dev (the LEFT eigenvectors, psd_lbevec.h) are the same two bodies with
+// lside set: lbevec_run puts the flip-adjoint form of a group into workspace (one launch), the group run above works on
+// it with the tables of the flipped form (lbevec_rows, bevec_root), and one launch turns the columns round.
 
 namespace {
 
@@ -39,7 +43,39 @@ struct bevec_call {
     int n, p, six, schurindex, shifted, maxvec;
     bool left;
     char orient;
+    // a left-vector call (psd_lbevec.h): n, p, left, orient and six describe the FLIPPED form the solve runs on, the
+    // eigenvalues, selections and row blocks handed down are the caller's and are flipped where the tables are built
+    bool lconj = false;
 };
+
+// The flipped form of gc problems of a left-vector call: rows reversed, eigenvalues conjugated.  The roots follow in
+// bevec_root.
+struct lbevec_rows {
+    std::vector<double> wr, wi;
+    std::vector<uint8_t> select;
+    std::vector<int> bsz;
+    lbevec_rows(int gc, int n, const double* wr_, const double* wi_, const uint8_t* select_, const int* bsz_)
+        : wr((size_t)gc * n), wi((size_t)gc * n), select((size_t)gc * n), bsz(bsz_ ? (size_t)gc * n : 0) {
+        for (int q = 0; q < gc; ++q)
+            for (int i = 0; i < n; ++i) {
+                const size_t o = (size_t)q * n + i, f = (size_t)q * n + n - 1 - i;
+                wr[f] = wr_[o];
+                wi[f] = -wi_[o];
+                select[f] = select_[o];
+                if (bsz_ && bsz_[o] != 0) {  // (the block at rows i, i + b - 1 stands at rows n - i - b, ... of the flipped form)
+                    bsz[f - (bsz_[o] - 1)] = bsz_[o];
+                    if (bsz_[o] == 2) bsz[f] = 0;
+                }
+            }
+    }
+};
+
+// the root the solve divides by.  l: the eigenvalue of the form the solve runs on.  Of a flipped form it is
+// conj(psd_ev_root(caller's lambda)), NOT psd_ev_root(l): the two differ for a negative real lambda (psd_ev_root drops the
+// sign of a zero imaginary part), and the left vectors have to belong to the root the right vectors belong to
+std::complex<double> bevec_root(const bevec_call& k, std::complex<double> l) {
+    return k.lconj ? std::conj(psd_ev_root(std::conj(l), k.p)) : psd_ev_root(l, k.p);
+}
 
 // The device part of a group, for both families (CPLX: the kernels of psd_zbevec.h): the tables of gc problems (itab, dtab,
 // the units behind them) go up, then the solve, the back-transformation of V_1, its norms and phases, the other factors,
@@ -170,12 +206,12 @@ int bevec_itab(const bevec_call& k, int gc, const uint8_t* select, const int* bs
 // selections and row blocks; cnt3 [gc][3] receives the counters per problem
 int bevec_group(const bevec_call& k, int gc, const double* dT, const double* dZ, const double* wr, const double* wi,
                 const uint8_t* select, const int* bsz, double* dV, int32_t* cnt3, psd_bevec_stats* st) {
-    const int n = k.n, p = k.p, DS = psd_bev_dstride(n);
+    const int n = k.n, DS = psd_bev_dstride(n);
     std::vector<int> itab, units;
     std::vector<double> dtab((size_t)gc * DS, 0.0);
     const int nsm = bevec_itab(k, gc, select, bsz, itab, units, [&](int q, int ns, int i) {
         double* dt = dtab.data() + (size_t)q * DS;
-        const std::complex<double> l(wr[(size_t)q * n + i], wi[(size_t)q * n + i]), u = psd_ev_root(l, p);
+        const std::complex<double> l(wr[(size_t)q * n + i], wi[(size_t)q * n + i]), u = bevec_root(k, l);
         dt[2 * ns] = u.real();
         dt[2 * ns + 1] = u.imag();
         dt[2 * n + 2 * ns] = l.real();
@@ -230,7 +266,7 @@ int bevec_single(const bevec_call& k, int gc, const double* dT, const double* dZ
     const size_t bd = (CPLX ? 2 : 1) * (size_t)n * n;
     return bevec_single_loop(k, gc, select, nvec, dV, cnt3, st, [&](int q, uint8_t* sel, double* dVq, psd_evec_stats* es) {
         return eigvecs_dev<CPLX>(k.c, n, p, dT + (size_t)q * p * bd, dZ + (size_t)q * p * bd, lam + (size_t)q * n, k.orient,
-                                 k.schurindex, sel, k.shifted, dVq, nvec[q], es);
+                                 k.schurindex, sel, k.shifted, dVq, nvec[q], es, nullptr, k.lconj);
     });
 }
 
@@ -247,10 +283,51 @@ int bevec_dev_groups(psd_ctx* c, int nb, size_t per, Body body) {
 int bevec_run(const bevec_call& k, int gc, const double* dT, const double* dZ, const double* wr, const double* wi,
               const uint8_t* select, const int* bsz, const int* nvec, double* dV, int32_t* cnt3, psd_bevec_stats* st) {
     st->ngroups += 1;
+    std::optional<lbevec_rows> f;
+    if (k.lconj) {
+        f.emplace(gc, k.n, wr, wi, select, bsz);
+        wr = f->wr.data(); wi = f->wi.data(); select = f->select.data(); bsz = f->bsz.data();
+    }
     if (k.n <= k.c->bev_nmax) return bevec_group(k, gc, dT, dZ, wr, wi, select, bsz, dV, cnt3, st);
     std::vector<std::complex<double>> lam((size_t)gc * k.n);
     for (size_t e = 0; e < lam.size(); ++e) lam[e] = std::complex<double>(wr[e], wi[e]);
     return bevec_single<false>(k, gc, dT, dZ, lam.data(), select, nvec, dV, cnt3, st);
+}
+
+// A group of a left-vector call (CPLX: a complex form).  The flip-adjoint of dT and the reversed dZ go into workspace
+// (psd_lbev_flip: one launch), run(fT, fZ) is the family's group run on them into dV, and psd_lbev_reverse turns the
+// columns of dV into the caller's order (one launch): two launches more than the right call, whatever gc and n are.
+template <bool CPLX, class Run>
+int lbevec_run(const bevec_call& k, int gc, const double* dT, const double* dZ, double* dV, const int* nvec,
+               psd_bevec_stats* st, Run run) {
+    psd_ctx* c = k.c;
+    const int n = k.n, p = k.p, nmat = k.shifted ? p : 1;
+    const size_t tot = (CPLX ? 2 : 1) * (size_t)gc * p * n * n;
+    psd_batchbuf bF, bN;
+    PSD_CHECK(bF.alloc(sizeof(double) * 2 * tot));
+    PSD_CHECK(bN.alloc(sizeof(int) * gc));
+    PSD_CHECK(psd_rt_h2d(bN.ptr, nvec, sizeof(int) * gc, c->stream));
+    const int nt = (n + PSD_LBEV_TILE - 1) / PSD_LBEV_TILE;
+    const int tiles = nt * nt < PSD_LBEV_TILES_MAX ? nt * nt : PSD_LBEV_TILES_MAX;
+    Timer tflip, trev;
+    tflip.start(c->stream);
+    if (CPLX) PSD_LAUNCH(psd_zlbev_flip, psd_dim3(2 * gc * p, tiles), PSD_BEV_NT, PSD_LBEV_LDS(true), c->stream, dT, dZ, bF.d(), n, gc * p);
+    else PSD_LAUNCH(psd_lbev_flip, psd_dim3(2 * gc * p, tiles), PSD_BEV_NT, PSD_LBEV_LDS(false), c->stream, dT, dZ, bF.d(), n, gc * p);
+    st->nlaunch += 1;
+    st->ms_solve += tflip.stop(c->stream);
+    if (const int rc = run((const double*)bF.d(), (const double*)bF.d() + tot)) return rc;
+    int mv = 0;
+    for (int q = 0; q < gc; ++q) mv = nvec[q] > mv ? nvec[q] : mv;
+    const size_t pairs = (size_t)(mv / 2) * n;
+    const int rt = (int)((pairs + PSD_BEV_NT - 1) / PSD_BEV_NT);
+    trev.start(c->stream);
+    PSD_LAUNCH(psd_lbev_reverse, psd_dim3(gc * nmat, rt < 1 ? 1 : (rt < PSD_LBEV_TILES_MAX ? rt : PSD_LBEV_TILES_MAX)), PSD_BEV_NT, 0,
+               c->stream, dV, (const int*)bN.ptr, n, nmat, k.maxvec);
+    st->nlaunch += 1;
+    st->ms_backtransform += trev.stop(c->stream);
+    PSD_CHECK(psd_rt_sync(c->stream));
+    PSD_CHECK(psd_rt_last_error());
+    return 0;
 }
 
 int bevec_checked(psd_ctx* c, int nb, int n, int p, const void* T, const void* Z, const double* wr, const double* wi,
@@ -290,11 +367,12 @@ void bevec_finish(int nb, const int* nvec, const int32_t* cnt3, int32_t* pcnt, p
 template <class Run>
 int bevec_entry_dev(const bevec_call& k, int nb, size_t bd, const double* dT, const double* dZ, double* dV, int mv,
                     const int* nvec, int32_t* pcnt, psd_bevec_stats* st, Run run) {
+    const size_t flipped = k.lconj ? sizeof(double) * 2 * bd * k.p : 0;  // (the flipped copies of T and Z of a left call)
     psd_ctx* c = k.c;
     const int n = k.n, p = k.p, nmat = k.shifted ? p : 1;
     std::vector<int32_t> cnt3(3 * (size_t)nb, 0);
     if (mv > 0) {
-        const int rc = bevec_dev_groups(c, nb, sizeof(double) * 2 * (size_t)p * n * mv, [&](int q0, int gc) {
+        const int rc = bevec_dev_groups(c, nb, sizeof(double) * 2 * (size_t)p * n * mv + flipped, [&](int q0, int gc) {
             return run(q0, gc, dT + (size_t)q0 * p * bd, dZ + (size_t)q0 * p * bd, dV + 2 * (size_t)q0 * nmat * n * k.maxvec,
                        cnt3.data() + 3 * (size_t)q0);
         });
@@ -320,26 +398,25 @@ int bevec_entry_host(const bevec_call& k, int nb, size_t bd, double* const* T, d
     } else {
         const batch_list L[] = {{T, p, bd, BATCH_IN}, {Z, p, bd, BATCH_IN}, {V, nmat, vb, BATCH_OUT}};
         auto body = [&](int q0, int gc, double* const* d) { return run(q0, gc, d[0], d[1], d[2], cnt3.data() + 3 * (size_t)q0); };
-        const size_t per = sizeof(double) * (2 * bd * p + vb * nmat + 2 * (size_t)p * n * mv);
+        // (a left call holds the flipped copies of T and Z beside them)
+        const size_t per = sizeof(double) * ((k.lconj ? 4 : 2) * bd * p + vb * nmat + 2 * (size_t)p * n * mv);
         if (const int rc = batch_staged(k.c, nb, per, L, nullptr, batch_no_extra, body)) return rc;
     }
     bevec_finish(nb, nvec, cnt3.data(), pcnt, st);
     return 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-int psd_d_eigvecs_batch_dev(psd_ctx* c, int nb, int n, int p, const double* dT, const double* dZ, const double* wr,
-                            const double* wi, char orient, int schurindex, uint8_t* select, int shifted, double* dV,
-                            int maxvec, int* nvec, int32_t* pcnt, psd_bevec_stats* stats, int* info) {
+// The two real entries behind their names.  lside: the left vectors (psd_lbevec.h): the solve runs on the flipped form,
+// which has the opposite orientation and the same schurindex
+int bevec_d_dev(bool lside, psd_ctx* c, int nb, int n, int p, const double* dT, const double* dZ, const double* wr,
+                const double* wi, char orient, int schurindex, uint8_t* select, int shifted, double* dV, int maxvec,
+                int* nvec, int32_t* pcnt, psd_bevec_stats* stats, int* info) {
     batch_call<psd_bevec_stats> entry(info, stats);
     psd_bevec_stats* st = entry.s;
     if ((*info = bevec_checked(c, nb, n, p, dT, dZ, wr, wi, orient, schurindex, select, nvec, st)) != 0 || nb == 0)
         return *info;
     const size_t nn = (size_t)n * n, tot = (size_t)nb * n;
-    const bool left = orient == 'L';
+    const bool left = (orient == 'L') != lside;
     bool any = false;
     for (size_t e = 0; e < tot && !any; ++e) any = select[e] != 0;
     std::vector<double> sub;
@@ -360,23 +437,26 @@ int psd_d_eigvecs_batch_dev(psd_ctx* c, int nb, int n, int p, const double* dT, 
     if (!dV) return *info = 0;
     if (mv > maxvec) return *info = -10;
     // (a selected row is a column or two: mv > 0 exactly when anything is selected)
-    const bevec_call k{c, n, p, left ? schurindex - 1 : p - schurindex, schurindex, shifted, maxvec, left, orient};
+    const bevec_call k{c, n, p, left ? schurindex - 1 : p - schurindex, schurindex, shifted, maxvec, left, left ? 'L' : 'R', lside};
     return *info = bevec_entry_dev(k, nb, nn, dT, dZ, dV, mv, nvec, pcnt, st,
                                    [&](int q0, int gc, const double* dTg, const double* dZg, double* dVg, int32_t* cnt3) {
-        return bevec_run(k, gc, dTg, dZg, wr + (size_t)q0 * n, wi + (size_t)q0 * n, select + (size_t)q0 * n,
-                         bsz.data() + (size_t)q0 * n, nvec + q0, dVg, cnt3, st);
+        auto run = [&](const double* gT, const double* gZ) {
+            return bevec_run(k, gc, gT, gZ, wr + (size_t)q0 * n, wi + (size_t)q0 * n, select + (size_t)q0 * n,
+                             bsz.data() + (size_t)q0 * n, nvec + q0, dVg, cnt3, st);
+        };
+        return lside ? lbevec_run<false>(k, gc, dTg, dZg, dVg, nvec + q0, st, run) : run(dTg, dZg);
     });
 }
 
-int psd_d_eigvecs_batch(psd_ctx* c, int nb, int n, int p, double* const* T, double* const* Z, const double* wr,
-                        const double* wi, char orient, int schurindex, uint8_t* select, int shifted, double* const* V,
-                        int maxvec, int* nvec, int32_t* pcnt, psd_bevec_stats* stats, int* info) {
+int bevec_d_host(bool lside, psd_ctx* c, int nb, int n, int p, double* const* T, double* const* Z, const double* wr,
+                 const double* wi, char orient, int schurindex, uint8_t* select, int shifted, double* const* V, int maxvec,
+                 int* nvec, int32_t* pcnt, psd_bevec_stats* stats, int* info) {
     batch_call<psd_bevec_stats> entry(info, stats);
     psd_bevec_stats* st = entry.s;
     if ((*info = bevec_checked(c, nb, n, p, T, Z, wr, wi, orient, schurindex, select, nvec, st)) != 0 || nb == 0)
         return *info;
     const size_t nn = (size_t)n * n, tot = (size_t)nb * n;
-    const bool left = orient == 'L';
+    const bool left = (orient == 'L') != lside;
     std::vector<double> sub(tot, 0.0);  // (the factors are on the host: no kernel)
     for (int q = 0; q < nb; ++q) {
         const double* t = T[(size_t)q * p + schurindex - 1];
@@ -388,12 +468,47 @@ int psd_d_eigvecs_batch(psd_ctx* c, int nb, int n, int p, double* const* T, doub
     for (int q = 0; q < nb; ++q) mv = nvec[q] > mv ? nvec[q] : mv;
     if (!V) return *info = 0;
     if (mv > maxvec) return *info = -10;
-    const bevec_call k{c, n, p, left ? schurindex - 1 : p - schurindex, schurindex, shifted, maxvec, left, orient};
+    const bevec_call k{c, n, p, left ? schurindex - 1 : p - schurindex, schurindex, shifted, maxvec, left, left ? 'L' : 'R', lside};
     return *info = bevec_entry_host(k, nb, nn, T, Z, V, mv, nvec, pcnt, st,
                                     [&](int q0, int gc, const double* dTg, const double* dZg, double* dVg, int32_t* cnt3) {
-        return bevec_run(k, gc, dTg, dZg, wr + (size_t)q0 * n, wi + (size_t)q0 * n, select + (size_t)q0 * n,
-                         bsz.data() + (size_t)q0 * n, nvec + q0, dVg, cnt3, st);
+        auto run = [&](const double* gT, const double* gZ) {
+            return bevec_run(k, gc, gT, gZ, wr + (size_t)q0 * n, wi + (size_t)q0 * n, select + (size_t)q0 * n,
+                             bsz.data() + (size_t)q0 * n, nvec + q0, dVg, cnt3, st);
+        };
+        return lside ? lbevec_run<false>(k, gc, dTg, dZg, dVg, nvec + q0, st, run) : run(dTg, dZg);
     });
+}
+
+}  // namespace
+
+extern "C" {
+
+int psd_d_eigvecs_batch_dev(psd_ctx* c, int nb, int n, int p, const double* dT, const double* dZ, const double* wr,
+                            const double* wi, char orient, int schurindex, uint8_t* select, int shifted, double* dV,
+                            int maxvec, int* nvec, int32_t* pcnt, psd_bevec_stats* stats, int* info) {
+    return bevec_d_dev(false, c, nb, n, p, dT, dZ, wr, wi, orient, schurindex, select, shifted, dV, maxvec, nvec, pcnt, stats,
+                       info);
+}
+
+int psd_d_eigvecs_batch(psd_ctx* c, int nb, int n, int p, double* const* T, double* const* Z, const double* wr,
+                        const double* wi, char orient, int schurindex, uint8_t* select, int shifted, double* const* V,
+                        int maxvec, int* nvec, int32_t* pcnt, psd_bevec_stats* stats, int* info) {
+    return bevec_d_host(false, c, nb, n, p, T, Z, wr, wi, orient, schurindex, select, shifted, V, maxvec, nvec, pcnt, stats,
+                        info);
+}
+
+int psd_d_leigvecs_batch_dev(psd_ctx* c, int nb, int n, int p, const double* dT, const double* dZ, const double* wr,
+                             const double* wi, char orient, int schurindex, uint8_t* select, int shifted, double* dV,
+                             int maxvec, int* nvec, int32_t* pcnt, psd_bevec_stats* stats, int* info) {
+    return bevec_d_dev(true, c, nb, n, p, dT, dZ, wr, wi, orient, schurindex, select, shifted, dV, maxvec, nvec, pcnt, stats,
+                       info);
+}
+
+int psd_d_leigvecs_batch(psd_ctx* c, int nb, int n, int p, double* const* T, double* const* Z, const double* wr,
+                         const double* wi, char orient, int schurindex, uint8_t* select, int shifted, double* const* V,
+                         int maxvec, int* nvec, int32_t* pcnt, psd_bevec_stats* stats, int* info) {
+    return bevec_d_host(true, c, nb, n, p, T, Z, wr, wi, orient, schurindex, select, shifted, V, maxvec, nvec, pcnt, stats,
+                        info);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // Host side of libpsd_mi355x: launch sequencing and the C ABI (include/psd_mi355x.h).
 // Built by hipcc (-x hip, gfx950).  tests/hostsim builds the same file with g++ -DPSD_HOSTSIM as a
 // serial simulation for the CPU-only test tier; the package never loads that build.
+#include <algorithm>
 #include <atomic>
 #include "psd_hess.h"
 #include "psd_bhess.h"
@@ -27,6 +28,7 @@
 #include "psd_zbevec.h"
 #include "psd_zgbevec.h"
 #include "psd_gbevec.h"
+#include "psd_lbevec.h"
 #include "psd_bord.h"
 #include "psd_zbqz.h"
 #include "psd_zgbqz.h"
@@ -3965,6 +3967,7 @@ extern "C" int psd_dbg_apply_bench(psd_ctx* c, int n, int p, int nwin, int W, in
 #include "psd_zbevec_host.inl"
 #include "psd_zgbevec_host.inl"
 #include "psd_gbevec_host.inl"
+#include "psd_lbevec_host.inl"
 #include "psd_bord_host.inl"
 #include "psd_zbord_host.inl"
 #include "psd_zgbord_host.inl"

@@ -18,10 +18,12 @@ static std::complex<double> psd_ev_root(std::complex<double> lam, int p) {
 // dT, dZ: [p][n][n] device blocks in user order (E doubles per element); lam: host, the n eigenvalues; select: n flags,
 // completed to pairs in place; dV: nmat blocks of n x nvec (interleaved complex, column-major); dV == nullptr: only the
 // completion and stats->nvec (a size query).  hTsi: a host copy of the quasi-triangular factor, or nullptr (read from dT).
+// conjroot: the form is the flip-adjoint of a caller's (the left vectors of the batch entries, psd_lbevec.h) and lam the
+// conjugates of the caller's eigenvalues: the root is conj(psd_ev_root(conj lam)), the conjugate of the caller's root.
 template <bool CPLX>
 int eigvecs_dev(psd_ctx* c, int n, int p, const double* dT, const double* dZ, const std::complex<double>* lam,
                 char orient, int schurindex, uint8_t* select, int shifted, double* dV, int maxvec, psd_evec_stats* st,
-                const double* hTsi = nullptr) {
+                const double* hTsi = nullptr, bool conjroot = false) {
     constexpr int E = CPLX ? 2 : 1;
     const size_t nn = (size_t)n * n;
     const bool left = orient == 'L';
@@ -77,7 +79,8 @@ int eigvecs_dev(psd_ctx* c, int n, int p, const double* dT, const double* dZ, co
     const int six = left ? schurindex - 1 : p - schurindex;
     std::vector<double> mu(2 * ns), lamc(2 * ns), ev(2 * (size_t)n);
     for (int j = 0; j < ns; ++j) {
-        const std::complex<double> l = lam[k0[j]], u = psd_ev_root(l, p);
+        const std::complex<double> l = lam[k0[j]];
+        const std::complex<double> u = conjroot ? std::conj(psd_ev_root(std::conj(l), p)) : psd_ev_root(l, p);
         lamc[2 * j] = l.real();
         lamc[2 * j + 1] = l.imag();
         mu[2 * j] = u.real();

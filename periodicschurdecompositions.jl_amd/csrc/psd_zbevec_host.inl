@@ -9,6 +9,9 @@
 // psd_zbev_solve, psd_zbev_backtransform for V_1, psd_bev_norm, psd_zbev_backtransform for the other factors — four
 // launches with shifted and p > 1, three otherwise, whatever nb and n are — and one read-back of the counters.  Orders
 // above the context's bev_nmax (PSD_BEV_NMAX) run eigvecs_dev<true> problem by problem on the slices of the batch buffers.
+//
+// psd_z_leigvecs_batch / psd_z_leigvecs_batch_dev (the LEFT eigenvectors, psd_lbevec.h): the same bodies with lside set,
+// through lbevec_run of psd_bevec_host.inl; zbevec_run flips the eigenvalues and the selection of its group.
 
 namespace {
 
@@ -59,7 +62,7 @@ int zbevec_tables(const bevec_call& k, int gc, const std::complex<double>* lam, 
             tab[5 * n + ns] = 0;
             tab[6 * n + ns] = i + 1;
             if (l) {
-                const std::complex<double> u = psd_ev_root(l[i], p);
+                const std::complex<double> u = bevec_root(k, l[i]);
                 dt[2 * ns] = u.real();
                 dt[2 * ns + 1] = u.imag();
                 dt[2 * n + 2 * ns] = l[i].real();
@@ -92,9 +95,19 @@ int zbevec_run(const bevec_call& k, int q0, int gc, const double* dT, const doub
                psd_bevec_stats* st) {
     st->ngroups += 1;
     const size_t r0 = (size_t)q0 * k.n;
-    const auto lam = zbevec_values(gc, k.n, alpha + 2 * r0, beta + r0, ascale ? ascale + r0 : nullptr);
+    auto lam = zbevec_values(gc, k.n, alpha + 2 * r0, beta + r0, ascale ? ascale + r0 : nullptr);
     select += r0;
     nvec += q0;
+    std::vector<uint8_t> fsel;
+    if (k.lconj) {  // a left call: the rows of the flipped form (psd_lbevec.h), eigenvalues conjugated
+        fsel.resize((size_t)gc * k.n);
+        for (int q = 0; q < gc; ++q) {
+            std::reverse(lam.begin() + (size_t)q * k.n, lam.begin() + (size_t)(q + 1) * k.n);
+            for (int i = 0; i < k.n; ++i) fsel[(size_t)q * k.n + k.n - 1 - i] = select[(size_t)q * k.n + i];
+        }
+        for (auto& l : lam) l = std::conj(l);
+        select = fsel.data();
+    }
     if (k.n > k.c->bev_nmax) return bevec_single<true>(k, gc, dT, dZ, lam.data(), select, nvec, dV, cnt3, st);
     return zbevec_group(k, gc, dT, dZ, lam.data(), select, dV, cnt3, st);
 }
@@ -127,6 +140,44 @@ bool zbevec_head(psd_ctx* c, int nb, int n, int p, const void* T, const void* Z,
     return false;
 }
 
+// The two complex entries behind their names.  lside: the left vectors (psd_lbevec.h): the solve runs on the flipped
+// form, which has the opposite orientation and the same schurindex
+int zbevec_dev(bool lside, psd_ctx* c, int nb, int n, int p, const double* dT, const double* dZ, const double* alpha,
+               const double* beta, const int32_t* ascale, char orient, int schurindex, const uint8_t* select, int shifted,
+               double* dV, int maxvec, int* nvec, int32_t* pcnt, psd_bevec_stats* stats, int* info) {
+    batch_call<psd_bevec_stats> entry(info, stats);
+    psd_bevec_stats* st = entry.s;
+    int mv = 0;
+    if (zbevec_head(c, nb, n, p, dT, dZ, alpha, beta, orient, schurindex, select, dV, maxvec, nvec, st, mv, info)) return *info;
+    const bool left = (orient == 'L') != lside;
+    const bevec_call k{c, n, p, 0, schurindex, shifted, maxvec, left, left ? 'L' : 'R', lside};
+    return *info = bevec_entry_dev(k, nb, 2 * (size_t)n * n, dT, dZ, dV, mv, nvec, pcnt, st,
+                                   [&](int q0, int gc, const double* dTg, const double* dZg, double* dVg, int32_t* cnt3) {
+        auto run = [&](const double* gT, const double* gZ) {
+            return zbevec_run(k, q0, gc, gT, gZ, alpha, beta, ascale, select, nvec, dVg, cnt3, st);
+        };
+        return lside ? lbevec_run<true>(k, gc, dTg, dZg, dVg, nvec + q0, st, run) : run(dTg, dZg);
+    });
+}
+
+int zbevec_host(bool lside, psd_ctx* c, int nb, int n, int p, double* const* T, double* const* Z, const double* alpha,
+                const double* beta, const int32_t* ascale, char orient, int schurindex, const uint8_t* select, int shifted,
+                double* const* V, int maxvec, int* nvec, int32_t* pcnt, psd_bevec_stats* stats, int* info) {
+    batch_call<psd_bevec_stats> entry(info, stats);
+    psd_bevec_stats* st = entry.s;
+    int mv = 0;
+    if (zbevec_head(c, nb, n, p, T, Z, alpha, beta, orient, schurindex, select, V, maxvec, nvec, st, mv, info)) return *info;
+    const bool left = (orient == 'L') != lside;
+    const bevec_call k{c, n, p, 0, schurindex, shifted, maxvec, left, left ? 'L' : 'R', lside};
+    return *info = bevec_entry_host(k, nb, 2 * (size_t)n * n, T, Z, V, mv, nvec, pcnt, st,
+                                    [&](int q0, int gc, const double* dTg, const double* dZg, double* dVg, int32_t* cnt3) {
+        auto run = [&](const double* gT, const double* gZ) {
+            return zbevec_run(k, q0, gc, gT, gZ, alpha, beta, ascale, select, nvec, dVg, cnt3, st);
+        };
+        return lside ? lbevec_run<true>(k, gc, dTg, dZg, dVg, nvec + q0, st, run) : run(dTg, dZg);
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -135,30 +186,32 @@ int psd_z_eigvecs_batch_dev(psd_ctx* c, int nb, int n, int p, const double* dT, 
                             const double* beta, const int32_t* ascale, char orient, int schurindex, const uint8_t* select,
                             int shifted, double* dV, int maxvec, int* nvec, int32_t* pcnt, psd_bevec_stats* stats,
                             int* info) {
-    batch_call<psd_bevec_stats> entry(info, stats);
-    psd_bevec_stats* st = entry.s;
-    int mv = 0;
-    if (zbevec_head(c, nb, n, p, dT, dZ, alpha, beta, orient, schurindex, select, dV, maxvec, nvec, st, mv, info)) return *info;
-    const bevec_call k{c, n, p, 0, schurindex, shifted, maxvec, orient == 'L', orient};
-    return *info = bevec_entry_dev(k, nb, 2 * (size_t)n * n, dT, dZ, dV, mv, nvec, pcnt, st,
-                                   [&](int q0, int gc, const double* dTg, const double* dZg, double* dVg, int32_t* cnt3) {
-        return zbevec_run(k, q0, gc, dTg, dZg, alpha, beta, ascale, select, nvec, dVg, cnt3, st);
-    });
+    return zbevec_dev(false, c, nb, n, p, dT, dZ, alpha, beta, ascale, orient, schurindex, select, shifted, dV, maxvec, nvec,
+                      pcnt, stats, info);
 }
 
 int psd_z_eigvecs_batch(psd_ctx* c, int nb, int n, int p, double* const* T, double* const* Z, const double* alpha,
                         const double* beta, const int32_t* ascale, char orient, int schurindex, const uint8_t* select,
                         int shifted, double* const* V, int maxvec, int* nvec, int32_t* pcnt, psd_bevec_stats* stats,
                         int* info) {
-    batch_call<psd_bevec_stats> entry(info, stats);
-    psd_bevec_stats* st = entry.s;
-    int mv = 0;
-    if (zbevec_head(c, nb, n, p, T, Z, alpha, beta, orient, schurindex, select, V, maxvec, nvec, st, mv, info)) return *info;
-    const bevec_call k{c, n, p, 0, schurindex, shifted, maxvec, orient == 'L', orient};
-    return *info = bevec_entry_host(k, nb, 2 * (size_t)n * n, T, Z, V, mv, nvec, pcnt, st,
-                                    [&](int q0, int gc, const double* dTg, const double* dZg, double* dVg, int32_t* cnt3) {
-        return zbevec_run(k, q0, gc, dTg, dZg, alpha, beta, ascale, select, nvec, dVg, cnt3, st);
-    });
+    return zbevec_host(false, c, nb, n, p, T, Z, alpha, beta, ascale, orient, schurindex, select, shifted, V, maxvec, nvec,
+                       pcnt, stats, info);
+}
+
+int psd_z_leigvecs_batch_dev(psd_ctx* c, int nb, int n, int p, const double* dT, const double* dZ, const double* alpha,
+                             const double* beta, const int32_t* ascale, char orient, int schurindex, const uint8_t* select,
+                             int shifted, double* dV, int maxvec, int* nvec, int32_t* pcnt, psd_bevec_stats* stats,
+                             int* info) {
+    return zbevec_dev(true, c, nb, n, p, dT, dZ, alpha, beta, ascale, orient, schurindex, select, shifted, dV, maxvec, nvec,
+                      pcnt, stats, info);
+}
+
+int psd_z_leigvecs_batch(psd_ctx* c, int nb, int n, int p, double* const* T, double* const* Z, const double* alpha,
+                         const double* beta, const int32_t* ascale, char orient, int schurindex, const uint8_t* select,
+                         int shifted, double* const* V, int maxvec, int* nvec, int32_t* pcnt, psd_bevec_stats* stats,
+                         int* info) {
+    return zbevec_host(true, c, nb, n, p, T, Z, alpha, beta, ascale, orient, schurindex, select, shifted, V, maxvec, nvec,
+                       pcnt, stats, info);
 }
 
 }  // extern "C"

@@ -18,6 +18,10 @@ device times and the launches of the stats, and the largest difference between t
              n in {8, 16, 32, 64}, p in {4, 16}; one warm-up, then the median of five alternating runs of each
   --signed-real  the same for signed Float64 problems: dgpschur_batch_, then Engine.dgeigvecs_batch
              (psd_d_geigvecs_batch_dev) against the loop of Engine.geigvecs_dev on the real T, Z; n up to 128
+  --left     the left eigenvectors beside the right ones at the shapes of the default grid: Engine.eigvecs_batch (with
+             --complex: zeigvecs_batch) with side="L" (psd_?_leigvecs_batch_dev) against side="R" on the same device
+             tensors, and Engine.eigcond_batch (both calls and psd_bev_cond); one warm-up, then the median of five
+             alternating runs of each.  A record of what the flipped copies and the column reversal cost, not a gate
 
 Every shape runs in a process of its own under `timeout`; the tool stops at the first one that fails.  One JSON line per
 shape on stdout; --json FILE collects them."""
@@ -95,6 +99,66 @@ def run_one(nb, n, p, lr, sweep, cplx=False):
                 diff = max(diff, d if d == d else 0.0)  # (NaN columns of zero eigenvalues aside)
     row["max_abs_diff"] = diff
     row["wall_ratio"] = row["loop"]["wall_ms"] / row["batch"]["wall_ms"]
+    print(json.dumps(row), flush=True)
+
+
+def run_left(nb, n, p, lr, cplx=False, repeats=5):
+    """--left: side="R", side="L" and eigcond_batch on the output of the device-resident [z]pschur_batch_."""
+    import numpy as np
+    import torch
+
+    torch.cuda.init()
+    import psd_amd
+
+    eng = psd_amd.Engine(0)
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(9000 + n + 1000 * p)
+    dt = torch.complex128 if cplx else torch.float64
+    A = torch.eye(n, dtype=dt, device="cuda") + 0.5 * torch.randn(
+        (nb, p, n, n), dtype=dt, device="cuda", generator=gen) / np.sqrt(n)
+    infos = []
+    T, Z, values, _ = (eng.zpschur_batch_ if cplx else eng.pschur_batch_)(A, lr, infos_out=infos)
+    batched = eng.zeigvecs_batch if cplx else eng.eigvecs_batch
+    si = p if lr == "L" else 1
+    select = np.ones((nb, n), dtype=bool)
+    select[[q for q in range(nb) if infos[q] != 0]] = False  # (a problem that did not converge is skipped)
+    row = dict(nb=nb, n=n, p=p, lr=lr, nfailed=int(sum(1 for i in infos if i != 0)), left=True, complex=bool(cplx),
+               repeats=repeats)
+
+    def timed(call):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = call()
+        torch.cuda.synchronize()
+        st = eng.eigvecs_batch_stats
+        return 1e3 * (time.perf_counter() - t0), out, dict(ms_solve=st.ms_solve, ms_backtransform=st.ms_backtransform,
+                                                          nlaunch=int(st.nlaunch), ngroups=int(st.ngroups))
+
+    calls = dict(right=lambda: batched(T, Z, values, select, lr=lr, schurindex=si),
+                 left=lambda: batched(T, Z, values, select, lr=lr, schurindex=si, side="L"),
+                 cond=lambda: eng.eigcond_batch(T, Z, values, select, lr=lr, schurindex=si))
+    for call in calls.values():
+        timed(call)  # warm-up
+    ms = {k: [] for k in calls}
+    for _ in range(repeats):
+        for k, call in calls.items():
+            t, out, st = timed(call)
+            ms[k].append(t)
+            row[k] = st
+            if k == "cond":
+                s, V, W, nvec = out
+    for k in calls:
+        row[k].update(wall_ms=float(np.median(ms[k])), wall_ms_min=min(ms[k]), wall_ms_max=max(ms[k]))
+    # w_l' v_l over l: the largest relative spread over every eighth problem (NaN columns of zero eigenvalues aside)
+    spread = 0.0
+    for q in range(0, nb, max(1, nb // 8)):
+        d = (W[q, :, :, :nvec[q]].conj() * V[q, :, :, :nvec[q]]).sum(dim=1)
+        r = ((d - d[0]).abs() / d[0].abs()).max().item() if nvec[q] else 0.0
+        spread = max(spread, r if r == r else 0.0)
+    row["inner_product_spread"] = spread
+    sv = s[s > 0]
+    row["s_min"] = float(sv.min()) if sv.size else None
+    row["left_over_right"] = row["left"]["wall_ms"] / row["right"]["wall_ms"]
     print(json.dumps(row), flush=True)
 
 
@@ -182,12 +246,16 @@ def main():
     ap.add_argument("--complex", action="store_true", dest="cplx")
     ap.add_argument("--signed", action="store_true")
     ap.add_argument("--signed-real", action="store_true", dest="signed_real")
+    ap.add_argument("--left", action="store_true")
     ap.add_argument("--timeout", type=int, default=240, help="seconds per shape")
     ap.add_argument("--json", default=None)
     ap.add_argument("--one", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.one and (args.signed or args.signed_real):
         run_signed(*parse_shapes(args.one)[0], args.lr, real=args.signed_real)
+        return 0
+    if args.one and args.left:
+        run_left(*parse_shapes(args.one)[0], args.lr, args.cplx)
         return 0
     if args.one:
         run_one(*parse_shapes(args.one)[0], args.lr, args.sweep, args.cplx)
@@ -205,7 +273,7 @@ def main():
         cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--one",
                "%dx%dx%d" % s, "--lr", args.lr] + (["--sweep"] if args.sweep else []) + (
                    ["--complex"] if args.cplx else []) + (["--signed"] if args.signed else []) + (
-                       ["--signed-real"] if args.signed_real else [])
+                       ["--signed-real"] if args.signed_real else []) + (["--left"] if args.left else [])
         pr = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
         sys.stdout.write(pr.stdout)
         sys.stdout.flush()
