@@ -89,6 +89,25 @@ def cap(header, macro):
     return int(m.group(1)) if m else None
 
 
+def engine_maker(monkeypatch, knobs, new, made, default=None):
+    """make(env) of a test file's make_engine fixture: the engine created by new() with the variables of env set and every
+    other one of `knobs` cleared.  An engine is created once per env and kept in `made` — a dict of the test, or of the
+    file, whose engines then serve all its tests —; `default`, where given, is the engine of an empty env."""
+    def make(env):
+        if default is not None and not env:
+            return default
+        key = tuple(sorted(env.items()))
+        if key not in made:
+            for k in knobs:
+                monkeypatch.delenv(k, raising=False)
+            for k, v in env.items():
+                monkeypatch.setenv(k, v)
+            made[key] = new()
+        return made[key]
+
+    return make
+
+
 # ------------------------------------------------------------------------------------------------
 # inputs: built once, shared among the cases, never written to
 _cache = {}

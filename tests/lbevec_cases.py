@@ -17,10 +17,10 @@ import bevec_cases as bc
 import evec_cases as vc
 import psd_amd
 import psdtest as pt
-import zbevec_cases as zc
+from batch_common import cap
 
 _cache = {}
-SEEDS = bc.SEEDS
+SEEDS = bc.D.seeds
 
 
 def _shared(key, make):
@@ -198,26 +198,26 @@ def raw_host(eng, pss, select, shifted=True, maxvec=None, cplx=False):
 # ------------------------------------------------------------------------------------------------
 # 1. mixed batch
 def mixed_problems(cplx):
-    return zc.mixed_problems() if cplx else bc.mixed_problems()
+    return bc.mixed_problems(bc.Z) if cplx else bc.mixed_problems()
 
 
 def case_mixed(eng, cplx):
     probs = mixed_problems(cplx)
     pss = [ps for ps, _ in probs]
-    nvec0 = zc.MIXED_NVEC if cplx else bc.MIXED_NVEC
-    Vs, Ws = check_batch(eng, probs, bc.MIXED_SELECT, cplx)
+    nvec0 = bc.Z.mixed_nvec if cplx else bc.D.mixed_nvec
+    Vs, Ws = check_batch(eng, probs, bc.D.mixed_select, cplx)
     assert [W[0].shape[1] for W in Ws] == nvec0
-    right = _call(eng, cplx)(pss, bc.MIXED_SELECT)
+    right = _call(eng, cplx)(pss, bc.D.mixed_select)
     right_launches = eng.eigvecs_batch_stats.nlaunch
     assert all(_same(a, b) for a, b in zip(right, Vs))  # the right vectors of "B" are those of the right call
-    WL = _call(eng, cplx)(pss, bc.MIXED_SELECT, side="L")
+    WL = _call(eng, cplx)(pss, bc.D.mixed_select, side="L")
     assert eng.eigvecs_batch_stats.nlaunch == right_launches + 2
     assert all(_same(a, b) for a, b in zip(WL, Ws))
-    W1 = _call(eng, cplx)(pss, bc.MIXED_SELECT, side="L", shifted=False)
+    W1 = _call(eng, cplx)(pss, bc.D.mixed_select, side="L", shifted=False)
     for q in range(5):
         assert len(W1[q]) == 1 and np.array_equal(W1[q][0], Ws[q][0])  # bit-identical
     # the blocks as the ABI leaves them: n x maxvec, the columns at and beyond nvec exactly zero
-    info, W, nvec, cnts, st = raw_host(eng, pss, bc.MIXED_SELECT, cplx=cplx)
+    info, W, nvec, cnts, st = raw_host(eng, pss, bc.D.mixed_select, cplx=cplx)
     assert info == 0 and nvec == nvec0 and W.shape[2] == 7
     for q in range(5):
         for l in range(3):
@@ -287,7 +287,7 @@ def negative_problems(p, cplx):
     diag[1] = diag[1].copy()
     diag[1][2] = -1.3
     if cplx:
-        return _shared(("negz", p), lambda: [zc.zform(n, p, 7), vc.schur_form(n, p, diag, seed=5, cplx=True)])
+        return _shared(("negz", p), lambda: [bc.zform(n, p, 7), vc.schur_form(n, p, diag, seed=5, cplx=True)])
     return _shared(("neg", p), lambda: [bc.plain_form(n, p, 7, (4,)), vc.schur_form(n, p, diag, seed=5, pairs=(4,))])
 
 
@@ -383,7 +383,7 @@ def cap_form(n, p, diag, seed, pairs):
 
 def case_above_cap(eng):
     """the single path on the flipped slices, and its root: one negative diagonal entry"""
-    n, p = bc.bev_nmax() + 1, 2
+    n, p = cap(bc.D.cap_header, bc.D.cap_macro) + 1, 2
     rs = np.random.RandomState(13)
     diag = [np.linspace(0.6, 1.9, n) * (1 + 0.2 * rs.rand(n)) for _ in range(p)]
     diag[1][9] = -diag[1][9]
@@ -415,8 +415,8 @@ def case_cond_formula(eng, cplx):
     probs = mixed_problems(cplx)
     for pr in (probs, [as_right(x) for x in probs]):
         pss = [ps for ps, _ in pr]
-        s, Vs, Ws = eng.eigcond_batch(pss, bc.MIXED_SELECT)
-        both = _call(eng, cplx)(pss, bc.MIXED_SELECT, side="B")
+        s, Vs, Ws = eng.eigcond_batch(pss, bc.D.mixed_select)
+        both = _call(eng, cplx)(pss, bc.D.mixed_select, side="B")
         for q in range(5):
             assert _same(Vs[q], both[0][q]) and _same(Ws[q], both[1][q])
             ref = cond_formula(pss[q], Vs[q], Ws[q])
@@ -451,7 +451,7 @@ def case_cond_perturbation(eng, cplx):
     """(c) one factor perturbed by 1e-6 E: the eigenvalue shifts of the explicit product agree with the first-order
     formula d lambda = mu^(p-1) 1e-6 w_{l+1}' E v_l / (w_1' v_1) ('R': w_l' E v_{l+1}) to 1e-3 relative"""
     n, p = (6, 4) if cplx else (7, 3)
-    base = zc.zform(n, p, 7) if cplx else bc.mixed_problems()[2]  # (real: pairs at rows 2 and 5)
+    base = bc.zform(n, p, 7) if cplx else bc.mixed_problems()[2]  # (real: pairs at rows 2 and 5)
     for prob in (base, as_right(base)):
         ps, As = prob
         left = ps.orientation == "L"
@@ -504,7 +504,7 @@ def case_errors(eng, make_engine):
         with pytest.raises(ValueError, match="side"):
             eng.eigvecs_batch(pss, [True] * n, side=bad)
     with pytest.raises(ValueError, match="side"):
-        eng.zeigvecs_batch([ps for ps, _ in zc.mixed_problems()], [True] * n, side="left")
+        eng.zeigvecs_batch([ps for ps, _ in bc.mixed_problems(bc.Z)], [True] * n, side="left")
     g = psd_amd.GeneralizedPeriodicSchur([True, False, True], pss[0].Ts, pss[0].Z, np.array(pss[0].values), np.ones(n),
                                          np.zeros(n, dtype=np.int32), "L", p)
     with pytest.raises(psd_amd.NotImplementedPSD):
@@ -520,7 +520,7 @@ def case_errors(eng, make_engine):
     with pytest.raises(psd_amd.NotImplementedPSD):
         sharded.eigvecs_batch(pss, [True] * n, side="L")
     with pytest.raises(psd_amd.NotImplementedPSD):
-        sharded.zeigvecs_batch([ps for ps, _ in zc.mixed_problems()], [True] * n, side="B")
+        sharded.zeigvecs_batch([ps for ps, _ in bc.mixed_problems(bc.Z)], [True] * n, side="B")
     # an empty batch
     assert eng.eigvecs_batch([], [True] * n, side="L") == []
     assert eng.eigvecs_batch([], [True] * n, side="B") == ([], [])
@@ -529,10 +529,10 @@ def case_errors(eng, make_engine):
     s, Vs, Ws = eng.eigcond_batch(pss, np.zeros(n, dtype=bool))
     assert all(x.shape == (p, 0) for x in s) and all(W.shape == (n, 0) for Wq in Ws for W in Wq)
     assert eng.eigvecs_batch_stats.nlaunch == 0
-    info, W, nvec, _, _ = raw_host(eng, pss, bc.MIXED_SELECT, maxvec=6)  # problem 0 has 7 columns
-    assert info == -10 and nvec == bc.MIXED_NVEC
-    info, W, nvec, _, _ = raw_host(eng, [ps for ps, _ in zc.mixed_problems()], bc.MIXED_SELECT, maxvec=6, cplx=True)
-    assert info == -10 and nvec == zc.MIXED_NVEC
+    info, W, nvec, _, _ = raw_host(eng, pss, bc.D.mixed_select, maxvec=6)  # problem 0 has 7 columns
+    assert info == -10 and nvec == bc.D.mixed_nvec
+    info, W, nvec, _, _ = raw_host(eng, [ps for ps, _ in bc.mixed_problems(bc.Z)], bc.D.mixed_select, maxvec=6, cplx=True)
+    assert info == -10 and nvec == bc.Z.mixed_nvec
 
 
 def case_abi(eng, make_engine):
@@ -541,12 +541,12 @@ def case_abi(eng, make_engine):
     nb, n, p = 5, 7, 3
     dp, u8p, i32p = C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_int32)
     lib, ctx = eng.lib, eng.ctx
-    sel0 = np.ascontiguousarray(bc.MIXED_SELECT, dtype=np.uint8)
+    sel0 = np.ascontiguousarray(bc.D.mixed_select, dtype=np.uint8)
     blocks = {}
     for cplx in (False, True):
         pss = [ps for ps, _ in mixed_problems(cplx)]
-        nvec0 = zc.MIXED_NVEC if cplx else bc.MIXED_NVEC
-        host = _call(eng, cplx)(pss, bc.MIXED_SELECT, side="L")
+        nvec0 = bc.Z.mixed_nvec if cplx else bc.D.mixed_nvec
+        host = _call(eng, cplx)(pss, bc.D.mixed_select, side="L")
         dt = np.complex128 if cplx else np.float64
         dT = np.ascontiguousarray(np.array([pt.pack(ps.Ts, dt) for ps in pss]))
         dZ = np.ascontiguousarray(np.array([pt.pack(ps.Z, dt) for ps in pss]))
@@ -599,7 +599,7 @@ def case_abi(eng, make_engine):
         assert call(fdev, bT, bZ, V_=C.c_void_p(W.ctypes.data), mv=6) == -10
     # the condition numbers of the real batch: device blocks against host pointers
     pss = [ps for ps, _ in bc.mixed_problems()]
-    s0, Vs, Ws = eng.eigcond_batch(pss, bc.MIXED_SELECT)
+    s0, Vs, Ws = eng.eigcond_batch(pss, bc.D.mixed_select)
     W, nvec0 = blocks[False]
     V = np.zeros_like(W)
     for q in range(nb):

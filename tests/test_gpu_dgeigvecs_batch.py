@@ -1,90 +1,90 @@
 """GPU tier (MI355X): Engine.dgeigvecs_batch — the whole homogeneous back-substitution of a signed Float64 batch in one
 launch (psd_gbev_solve: several columns per wavefront, 1x1 and 2x2 row blocks side by side, forward and backward segmented
 scans), the back-transform and the normalisation — against the numpy prototype, the single geigvecs and the gates of the
-single-problem tests (dgbevec_cases.py), and the device-resident pipeline behind dgpschur_batch_ and dgordschur_batch_."""
+single-problem tests (bevec_cases.py), and the device-resident pipeline behind dgpschur_batch_ and dgordschur_batch_."""
 import pytest
 
-import dgbevec_cases as dg
+import bevec_cases as dg
 import psd_amd
 
 pytestmark = pytest.mark.gpu
 
 
 def test_mixed_batch(gpu_engine):
-    dg.case_mixed(gpu_engine)
+    dg.case_mixed(gpu_engine, dg.DG)
 
 
 def test_batch_independence_bits(gpu_engine, monkeypatch):
     monkeypatch.setenv("PSD_BATCH_GROUP", "3")
     grouped = psd_amd.Engine(device=0)
     monkeypatch.delenv("PSD_BATCH_GROUP")
-    dg.case_independence(gpu_engine, grouped)
+    dg.case_independence(gpu_engine, dg.DG, grouped)
 
 
 @pytest.mark.parametrize("lr", ["L", "R"])
-@pytest.mark.parametrize("shape", dg.LAYOUTS, ids=dg.layout_id)
+@pytest.mark.parametrize("shape", dg.DG.layouts, ids=dg.DG.layout_id)
 def test_lane_layouts(gpu_engine, shape, lr):
-    dg.case_layout(gpu_engine, shape, lr)
+    dg.case_layout(gpu_engine, dg.DG, shape, lr)
 
 
 @pytest.mark.parametrize("lr", ["L", "R"])
 def test_all_false_signature(gpu_engine, lr):
-    dg.case_all_false(gpu_engine, lr)
+    dg.case_all_false(gpu_engine, dg.DG, lr)
 
 
 @pytest.mark.parametrize("lr", ["L", "R"])
 def test_depth(gpu_engine, lr):
-    dg.case_depth(gpu_engine, lr)
+    dg.case_depth(gpu_engine, dg.DG, lr)
 
 
 @pytest.mark.parametrize("lr", ["L", "R"])
 @pytest.mark.parametrize("n", [128, 129])
 def test_cap(gpu_engine, n, lr):
-    dg.case_cap(gpu_engine, n, lr)
+    dg.case_cap(gpu_engine, dg.DG, n, lr)
 
 
 @pytest.mark.parametrize("lr", ["L", "R"])
 def test_zero_and_infinite_eigenvalues(gpu_engine, lr):
-    dg.case_zero_infinite(gpu_engine, lr)
+    dg.case_zero_infinite(gpu_engine, dg.DG, lr)
 
 
 def test_repeated_eigenvalue(gpu_engine):
-    dg.case_repeated(gpu_engine)
+    dg.case_repeated(gpu_engine, dg.DG)
 
 
 @pytest.mark.parametrize("lr", ["L", "R"])
 def test_rescaled_columns(gpu_engine, lr):
-    dg.case_rescale(gpu_engine, lr)
+    dg.case_rescale(gpu_engine, dg.DG, lr)
 
 
 def test_all_true_signature(gpu_engine):
-    dg.case_all_true(gpu_engine)
+    dg.case_all_true_dg(gpu_engine)
 
 
 def test_skipped_problems(gpu_engine):
-    dg.case_skipped(gpu_engine)
+    dg.case_skipped(gpu_engine, dg.DG)
 
 
 def test_launch_count(gpu_engine):
-    dg.case_launch_count(gpu_engine)
+    dg.case_launch_count(gpu_engine, dg.DG)
 
 
 @pytest.mark.parametrize("lr", ["R", "L"])
 def test_pipeline_device_resident(gpu_engine, lr):
-    dg.case_pipeline(gpu_engine, lr)
+    dg.case_pipeline_signed(gpu_engine, dg.DG, lr)
 
 
 @pytest.mark.parametrize("lr", ["R", "L"])
 def test_pipeline_host_forms(gpu_engine, lr):
-    dg.case_pipeline_host(gpu_engine, lr)
+    dg.case_pipeline_host(gpu_engine, dg.DG, lr)
 
 
 def test_gpschur_batch_end_to_end(gpu_engine):
-    dg.case_gpschur_batch(gpu_engine)
+    dg.case_gpschur_batch(gpu_engine, dg.DG)
 
 
 def test_errors(gpu_engine):
-    dg.case_errors(gpu_engine, lambda: psd_amd.Engine(device=0))
+    dg.case_errors(gpu_engine, dg.DG, lambda: psd_amd.Engine(device=0))
 
 
 def test_empty_device_batch(gpu_engine):

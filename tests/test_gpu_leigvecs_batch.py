@@ -28,7 +28,7 @@ def test_batch_independence_bits(gpu_engine, monkeypatch):
     lc.case_independence(gpu_engine, grouped)
 
 
-@pytest.mark.parametrize("shape", bc.LAYOUTS, ids=bc.layout_id)
+@pytest.mark.parametrize("shape", bc.D.layouts, ids=bc.D.layout_id)
 def test_factor_layouts(gpu_engine, shape):
     lc.case_layout(gpu_engine, shape)
 

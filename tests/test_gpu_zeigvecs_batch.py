@@ -1,66 +1,66 @@
 """GPU tier (MI355X): Engine.zeigvecs_batch — the whole back-substitution of a ComplexF64 batch in one launch
 (psd_zbev_solve: several columns per wavefront), the complex back-transform and the normalisation — against the numpy
-prototype and the gates of the single-problem tests (zbevec_cases.py), and the device-resident pipeline behind
+prototype and the gates of the single-problem tests (bevec_cases.py), and the device-resident pipeline behind
 zpschur_batch_."""
 import pytest
 
+import bevec_cases as zc
 import psd_amd
-import zbevec_cases as zc
 
 pytestmark = pytest.mark.gpu
 
 
 def test_mixed_batch(gpu_engine):
-    zc.case_mixed(gpu_engine)
+    zc.case_mixed(gpu_engine, zc.Z)
 
 
 def test_batch_independence_bits(gpu_engine, monkeypatch):
     monkeypatch.setenv("PSD_BATCH_GROUP", "3")
     grouped = psd_amd.Engine(device=0)
     monkeypatch.delenv("PSD_BATCH_GROUP")
-    zc.case_independence(gpu_engine, grouped)
+    zc.case_independence(gpu_engine, zc.Z, grouped)
 
 
-@pytest.mark.parametrize("shape", zc.LAYOUTS, ids=zc.layout_id)
+@pytest.mark.parametrize("shape", zc.Z.layouts, ids=zc.Z.layout_id)
 def test_factor_layouts(gpu_engine, shape):
-    zc.case_layout(gpu_engine, shape)
+    zc.case_layout(gpu_engine, zc.Z, shape)
 
 
 def test_depth(gpu_engine):
-    zc.case_depth(gpu_engine)
+    zc.case_depth(gpu_engine, zc.Z)
 
 
 def test_repeated_eigenvalues(gpu_engine):
-    zc.case_special_repeated(gpu_engine)
+    zc.case_special_repeated(gpu_engine, zc.Z)
 
 
 def test_zero_eigenvalue(gpu_engine):
-    zc.case_special_zero(gpu_engine)
+    zc.case_special_zero(gpu_engine, zc.Z)
 
 
 def test_rescaled_columns(gpu_engine):
-    zc.case_special_rescale(gpu_engine)
+    zc.case_special_rescale(gpu_engine, zc.Z)
 
 
 def test_skipped_problems(gpu_engine):
-    zc.case_skipped(gpu_engine)
+    zc.case_skipped(gpu_engine, zc.Z)
 
 
 def test_launch_count(gpu_engine):
-    zc.case_launch_count(gpu_engine)
+    zc.case_launch_count(gpu_engine, zc.Z)
 
 
 def test_above_the_cap(gpu_engine):
-    zc.case_above_cap(gpu_engine)
+    zc.case_above_cap(gpu_engine, zc.Z)
 
 
 @pytest.mark.parametrize("lr", ["R", "L"])
 def test_pipeline_device_resident(gpu_engine, lr):
-    zc.case_pipeline(gpu_engine, lr)
+    zc.case_pipeline(gpu_engine, zc.Z, lr)
 
 
 def test_errors(gpu_engine):
-    zc.case_errors(gpu_engine, lambda: psd_amd.Engine(device=0))
+    zc.case_errors(gpu_engine, zc.Z, lambda: psd_amd.Engine(device=0))
 
 
 def test_empty_device_batch(gpu_engine):

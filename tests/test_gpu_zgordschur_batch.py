@@ -4,8 +4,9 @@ entry on packed blocks for both alignments of each orientation, and the device-r
 zgordschur_batch_."""
 import pytest
 
+import batch_common as bcm
+import ord_batch_cases as gc
 import psd_amd
-import zgord_batch_cases as gc
 
 pytestmark = pytest.mark.gpu
 
@@ -15,89 +16,78 @@ _engines = {}
 
 @pytest.fixture
 def make_engine(gpu_engine, monkeypatch):
-    def make(env):
-        if not env:
-            return gpu_engine
-        key = tuple(sorted(env.items()))
-        if key not in _engines:  # (an engine with knobs is made once and shared by the tests of this file)
-            for k in KNOBS:
-                monkeypatch.delenv(k, raising=False)
-            for k, v in env.items():
-                monkeypatch.setenv(k, v)
-            _engines[key] = psd_amd.Engine(device=0)
-        return _engines[key]
-
-    return make
+    # (an engine with knobs is made once and shared by the tests of this file)
+    return bcm.engine_maker(monkeypatch, KNOBS, lambda: psd_amd.Engine(device=0), _engines, default=gpu_engine)
 
 
 @pytest.mark.parametrize("lr", ["R", "L"])
 def test_reference_shape(gpu_engine, lr):
-    gc.case_reference(gpu_engine, lr)
+    gc.case_reference(gpu_engine, gc.ZG, lr)
 
 
 @pytest.mark.parametrize("lr", ["R", "L"])
-@pytest.mark.parametrize("shape", gc.WINDOW_SHAPES, ids=gc.shape_id)
+@pytest.mark.parametrize("shape", gc.ZG.windows, ids=gc.shape_id)
 def test_windows(gpu_engine, shape, lr):
-    gc.case_windows(gpu_engine, shape, lr)
+    gc.case_windows(gpu_engine, gc.ZG, shape, lr)
 
 
 @pytest.mark.parametrize("lr", ["R", "L"])
 def test_windows_narrow(make_engine, lr):
-    gc.case_windows(make_engine({"PSD_BORD_W": "6"}), gc.NARROW_SHAPE, lr, expect_window=6)
+    gc.case_windows(make_engine({"PSD_BORD_W": "6"}), gc.ZG, gc.ZG.narrow, lr, expect_window=6)
 
 
 @pytest.mark.parametrize("lr", ["R", "L"])
-@pytest.mark.parametrize("shape", gc.WINDOW_SHAPES, ids=gc.shape_id)
+@pytest.mark.parametrize("shape", gc.ZG.windows, ids=gc.shape_id)
 def test_against_serial_single_driver(make_engine, shape, lr):
     # (1e-12 * scale: contraction may differ between the kernels; the count of differing bits is printed)
-    gc.case_against_serial(make_engine, shape, lr, exact=False)
+    gc.case_against_serial(make_engine, gc.ZG, shape, lr, exact=False)
 
 
-@pytest.mark.parametrize("shape", [gc.WINDOW_SHAPES[0], gc.WINDOW_SHAPES[3]], ids=gc.shape_id)
+@pytest.mark.parametrize("shape", [gc.ZG.windows[0], gc.ZG.windows[3]], ids=gc.shape_id)
 def test_independence(gpu_engine, shape):
-    gc.case_independence(gpu_engine, shape)
+    gc.case_independence(gpu_engine, gc.ZG, shape)
 
 
 def test_groups(make_engine):
-    gc.case_groups(make_engine)
+    gc.case_groups(make_engine, gc.ZG)
 
 
 def test_all_true_signature(gpu_engine):
-    gc.case_all_true(gpu_engine)
+    gc.case_all_true_zg(gpu_engine)
 
 
 def test_per_problem_selections(gpu_engine):
-    gc.case_selections(gpu_engine)
+    gc.case_selections(gpu_engine, gc.ZG)
 
 
 def test_one_problem_fails(gpu_engine):
-    gc.case_one_fails(gpu_engine)
+    gc.case_one_fails(gpu_engine, gc.ZG)
 
 
 def test_fallback_above_the_cap(make_engine):
-    gc.case_above_cap(make_engine)
+    gc.case_above_cap(make_engine, gc.ZG)
 
 
 def test_argument_codes(gpu_engine):
-    gc.case_argument_codes(gpu_engine)
+    gc.case_argument_codes(gpu_engine, gc.ZG)
 
 
 def test_python_errors(gpu_engine):
-    gc.case_python_errors(gpu_engine)
+    gc.case_python_errors(gpu_engine, gc.ZG)
 
 
 def test_device_entry_bits(gpu_engine):
-    gc.case_dev_abi(gpu_engine, device=True)
+    gc.case_dev_abi(gpu_engine, gc.ZG, device=True)
 
 
 def test_device_entry_bits_grouped(make_engine):
     # (5 problems in groups of 2, 2 and 1: the last group is a partial one)
-    gc.case_dev_abi(make_engine({"PSD_BATCH_GROUP": "2"}), launches=3, device=True)
+    gc.case_dev_abi(make_engine({"PSD_BATCH_GROUP": "2"}), gc.ZG, launches=3, device=True)
 
 
 @pytest.mark.parametrize("lr", ["R", "L"])
 def test_device_resident_chain(gpu_engine, lr):
-    gc.case_device_chain(gpu_engine, lr)
+    gc.case_device_chain(gpu_engine, gc.ZG, lr)
 
 
 def test_empty_device_batch(gpu_engine):

@@ -3,8 +3,9 @@ against the single calls on the same device and the oracle, the fallback above P
 blocks for all four alignments, and the device-resident chain zpschur_batch_ -> zordschur_batch_."""
 import pytest
 
+import batch_common as bcm
+import ord_batch_cases as zc
 import psd_amd
-import zord_batch_cases as zc
 
 pytestmark = pytest.mark.gpu
 
@@ -14,85 +15,74 @@ _engines = {}
 
 @pytest.fixture
 def make_engine(gpu_engine, monkeypatch):
-    def make(env):
-        if not env:
-            return gpu_engine
-        key = tuple(sorted(env.items()))
-        if key not in _engines:  # (an engine with knobs is made once and shared by the tests of this file)
-            for k in KNOBS:
-                monkeypatch.delenv(k, raising=False)
-            for k, v in env.items():
-                monkeypatch.setenv(k, v)
-            _engines[key] = psd_amd.Engine(device=0)
-        return _engines[key]
-
-    return make
+    # (an engine with knobs is made once and shared by the tests of this file)
+    return bcm.engine_maker(monkeypatch, KNOBS, lambda: psd_amd.Engine(device=0), _engines, default=gpu_engine)
 
 
 @pytest.mark.parametrize("lr", ["R", "L"])
 def test_reference_shape(gpu_engine, lr):
-    zc.case_reference(gpu_engine, lr)
+    zc.case_reference(gpu_engine, zc.Z, lr)
 
 
 @pytest.mark.parametrize("lr", ["R", "L"])
-@pytest.mark.parametrize("shape", zc.WINDOW_SHAPES, ids=zc.shape_id)
+@pytest.mark.parametrize("shape", zc.Z.windows, ids=zc.shape_id)
 def test_windows(gpu_engine, shape, lr):
-    zc.case_windows(gpu_engine, shape, lr)
+    zc.case_windows(gpu_engine, zc.Z, shape, lr)
 
 
 @pytest.mark.parametrize("lr", ["R", "L"])
 def test_windows_narrow(make_engine, lr):
-    zc.case_windows(make_engine({"PSD_BORD_W": "6"}), zc.NARROW_SHAPE, lr, expect_window=6)
+    zc.case_windows(make_engine({"PSD_BORD_W": "6"}), zc.Z, zc.Z.narrow, lr, expect_window=6)
 
 
 @pytest.mark.parametrize("lr", ["R", "L"])
-@pytest.mark.parametrize("shape", zc.WINDOW_SHAPES, ids=zc.shape_id)
+@pytest.mark.parametrize("shape", zc.Z.windows, ids=zc.shape_id)
 def test_against_serial_single_driver(make_engine, shape, lr):
     # (1e-12 * scale: contraction may differ between the kernels; the count of differing bits is printed)
-    zc.case_against_serial(make_engine, shape, lr, exact=False)
+    zc.case_against_serial(make_engine, zc.Z, shape, lr, exact=False)
 
 
-@pytest.mark.parametrize("shape", [zc.WINDOW_SHAPES[0], zc.WINDOW_SHAPES[3]], ids=zc.shape_id)
+@pytest.mark.parametrize("shape", [zc.Z.windows[0], zc.Z.windows[3]], ids=zc.shape_id)
 def test_independence(gpu_engine, shape):
-    zc.case_independence(gpu_engine, shape)
+    zc.case_independence(gpu_engine, zc.Z, shape)
 
 
 def test_groups(make_engine):
-    zc.case_groups(make_engine)
+    zc.case_groups(make_engine, zc.Z)
 
 
 def test_per_problem_selections(gpu_engine):
-    zc.case_selections(gpu_engine)
+    zc.case_selections(gpu_engine, zc.Z)
 
 
 def test_one_problem_fails(gpu_engine):
-    zc.case_one_fails(gpu_engine)
+    zc.case_one_fails(gpu_engine, zc.Z)
 
 
 def test_fallback_above_the_cap(make_engine):
-    zc.case_above_cap(make_engine)
+    zc.case_above_cap(make_engine, zc.Z)
 
 
 def test_argument_codes(gpu_engine):
-    zc.case_argument_codes(gpu_engine)
+    zc.case_argument_codes(gpu_engine, zc.Z)
 
 
 def test_python_errors(gpu_engine):
-    zc.case_python_errors(gpu_engine)
+    zc.case_python_errors(gpu_engine, zc.Z)
 
 
 def test_device_entry_bits(gpu_engine):
-    zc.case_dev_abi(gpu_engine, device=True)
+    zc.case_dev_abi(gpu_engine, zc.Z, device=True)
 
 
 def test_device_entry_bits_grouped(make_engine):
     # (5 problems in groups of 2, 2 and 1: the last group is a partial one)
-    zc.case_dev_abi(make_engine({"PSD_BATCH_GROUP": "2"}), launches=3, device=True)
+    zc.case_dev_abi(make_engine({"PSD_BATCH_GROUP": "2"}), zc.Z, launches=3, device=True)
 
 
 @pytest.mark.parametrize("lr", ["R", "L"])
 def test_device_resident_chain(gpu_engine, lr):
-    zc.case_device_chain(gpu_engine, lr)
+    zc.case_device_chain(gpu_engine, zc.Z, lr)
 
 
 def test_empty_device_batch(gpu_engine):

@@ -12,23 +12,23 @@ _LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostsim", "_bui
 
 
 def test_mixed_batch(sim_engine):
-    bc.case_mixed(sim_engine)
+    bc.case_mixed(sim_engine, bc.D)
 
 
 def test_batch_independence_bits(sim_engine, monkeypatch):
     monkeypatch.setenv("PSD_BATCH_GROUP", "3")
     grouped = psd_amd.Engine(libpath=_LIB)
     monkeypatch.delenv("PSD_BATCH_GROUP")
-    bc.case_independence(sim_engine, grouped)
+    bc.case_independence(sim_engine, bc.D, grouped)
 
 
-@pytest.mark.parametrize("shape", bc.LAYOUTS, ids=bc.layout_id)
+@pytest.mark.parametrize("shape", bc.D.layouts, ids=bc.D.layout_id)
 def test_factor_layouts(sim_engine, shape):
-    bc.case_layout(sim_engine, shape)
+    bc.case_layout(sim_engine, bc.D, shape)
 
 
 def test_depth(sim_engine):
-    bc.case_depth(sim_engine)
+    bc.case_depth(sim_engine, bc.D)
 
 
 def test_negative_eigenvalue_even_period(sim_engine):
@@ -36,32 +36,32 @@ def test_negative_eigenvalue_even_period(sim_engine):
 
 
 def test_repeated_eigenvalues(sim_engine):
-    bc.case_special_repeated(sim_engine)
+    bc.case_special_repeated(sim_engine, bc.D)
 
 
 def test_zero_eigenvalue(sim_engine):
-    bc.case_special_zero(sim_engine)
+    bc.case_special_zero(sim_engine, bc.D)
 
 
 def test_rescaled_columns(sim_engine):
-    bc.case_special_rescale(sim_engine)
+    bc.case_special_rescale(sim_engine, bc.D)
 
 
 def test_skipped_problems(sim_engine):
-    bc.case_skipped(sim_engine)
+    bc.case_skipped(sim_engine, bc.D)
 
 
 def test_launch_count(sim_engine):
-    bc.case_launch_count(sim_engine)
+    bc.case_launch_count(sim_engine, bc.D)
 
 
 def test_above_the_cap(sim_engine):
-    bc.case_above_cap(sim_engine)
+    bc.case_above_cap(sim_engine, bc.D)
 
 
 def test_errors(sim_engine):
-    bc.case_errors(sim_engine, lambda: psd_amd.Engine(libpath=_LIB))
+    bc.case_errors(sim_engine, bc.D, lambda: psd_amd.Engine(libpath=_LIB))
 
 
 def test_device_entry_and_argument_codes(sim_engine):
-    bc.case_dev_abi(sim_engine)
+    bc.case_dev_abi(sim_engine, bc.D)

@@ -29,7 +29,7 @@ def test_batch_independence_bits(sim_engine, monkeypatch):
     lc.case_independence(sim_engine, grouped)
 
 
-@pytest.mark.parametrize("shape", bc.LAYOUTS, ids=bc.layout_id)
+@pytest.mark.parametrize("shape", bc.D.layouts, ids=bc.D.layout_id)
 def test_factor_layouts(sim_engine, shape):
     lc.case_layout(sim_engine, shape)
 
