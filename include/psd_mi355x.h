@@ -1051,6 +1051,77 @@ int psd_z_checkpsd_batch_dev(psd_ctx* ctx, int nb, int n, int p, const double* d
                              const uint8_t* S, char orient, int schurindex, double thresh, int strict, double* err,
                              double* orth, double* tri, int32_t* ok, psd_bcheck_stats* stats, int* info);
 
+/* ---- psylv_batch, subcond_batch: periodic Sylvester solves and the condition of an invariant periodic subspace ------
+ * nb periodic Schur forms of one shape (n, p), one orient and one schurindex, all-true signature, as the *_pschur_batch
+ * and *_ordschur_batch entries leave them; problem q is split at m[q], 0 <= m[q] <= n, k = n - m[q], which must not cut a
+ * 2x2 block of the quasi-triangular factor: T_l = [T11_l T12_l; 0 T22_l].  With (a(l), b(l)) = (l + 1, l) cyclically for
+ * orient 'L' and (l, l + 1) for 'R' — the factors of the residual Z_a T_l Z_b' - A_l that checkpsd_batch forms — the
+ * periodic Sylvester operator on p stacked m x k blocks is
+ *     S(X)_l = T11_l X_b(l) - X_a(l) T22_l ,   l = 1..p.
+ *
+ * psd_?_psylv_batch solves S(X) = C (trans == 0) or S^H(Y) = C (trans != 0; the adjoint under the Frobenius inner product
+ * over the stacked blocks).  C: nb * p blocks in user order, problem-major, each of xb elements (xb >= m[q] (n - m[q]) for
+ * every q) of which block (q, l) uses the first m[q] (n - m[q]) as an m[q] x k matrix, column-major with leading dimension
+ * m[q]; the solution overwrites it.  from_t12 != 0: C is only written and the right-hand side is C_l = -T12_l.  Then
+ * T_l [X_b; I] = [X_a; I] T22_l: Y_l = Z_l [X_l; I] spans the complementary periodic invariant subspace.  There is NO
+ * scale factor (xTRSYL carries one): a nearly singular problem returns large or non-finite numbers, the latter with the
+ * code below.
+ *
+ * psd_?_subcond_batch is the periodic form of xTRSEN's two numbers for the leading m[q] eigenvalues:
+ *     s[q * p + l] = 1 / sqrt(1 + ||X_l||_F^2)   (X of from_t12: the reciprocal of the Frobenius bound on the norm of the
+ *                                                 spectral projector of factor l; at p = 1 xTRSEN's S),
+ *     sep[q]       = 1 / est,  est the estimate of || S^-1 ||_1 on the p m k stacked unknowns (blocks in user order, each
+ *                    column-major) by LAPACK's reverse-communication estimator xLACN2 (real variant for psd_d_, complex
+ *                    for psd_z_; iteration limit 5, the final alternating-sign vector); at p = 1 xTRSEN's SEP.
+ * X (may be NULL): receives the solution of from_t12, laid out as C above.  m[q] = 0 or n: s = 1, sep = +inf, X untouched,
+ * and the problem takes part in no launch.
+ *
+ * One launch solves a group of problems (one wavefront per problem, Bartels-Stewart over the common block partition, the
+ * small cyclic systems by the solvers of the reordering kernels); the condition entry launches per group one solve, one
+ * norm kernel and per estimator step one solve and one vector kernel — at most 1 + 11 solves.  Every sum has a fixed
+ * order: a problem's numbers do not depend on nb, on its place in the batch or on the grouping, bit for bit.
+ * PSD_BATCH_GROUP acts as for the other batch entries.  Orders above 128 (PSD_BSYL_NMAX; PSD_BSYL_NMAX in the environment
+ * at psd_create may only lower it) return PSD_INFO_NOTIMPL: the family has no single-problem path to fall back to.  So do
+ * periods whose small-block scratch does not fit the LDS (psd_z_: p > 19; psd_d_: p > 136).
+ *
+ * T: nb * p host matrices (psd_z_: interleaved complex), column-major, USER order, only read; the _dev variants take
+ * device [nb][p][n][n] blocks (what the *_pschur_batch_dev / *_ordschur_batch_dev entries leave) and device
+ * [nb][p][xb] blocks for C / X; m, s, sep, infos are host arrays.  infos[nb] (may be NULL): PSD_INFO_SINGULAR for a
+ * problem whose small solve was rejected (T11 and T22 share an eigenvalue of the product) or whose solution is not
+ * finite — its X is NaN, s = 0, sep = 0 — the others are complete; the return value is the first non-zero one.
+ * Returns: -1 ctx NULL; -2 nb < 0; -3 n < 1; -4 p < 1; -5 T NULL; -6 orient; -7 schurindex not in 1..p; -8 m NULL, an
+ * m[q] outside 0..n or inside a 2x2 block; -9 C NULL (subcond: s or sep NULL); -10 xb below the largest m[q] (n - m[q])
+ * (subcond: only with X); PSD_INFO_NOTIMPL above the cap and on a period-sharded context; PSD_INFO_RUNTIME + k.
+ * nb == 0 returns 0 and touches nothing. */
+typedef struct psd_bsylv_stats {
+    int32_t nb;         /* problems of the call */
+    int32_t ngroups;    /* groups the batch went to the device in */
+    int32_t nsolve;     /* launches of the solve kernel */
+    int32_t nnorms;     /* launches of the norm kernel */
+    int32_t nest_steps; /* launches of the estimator's vector kernel */
+    int32_t nest_iter;  /* most iterations the estimator took on a problem (<= 5) */
+    int32_t nsingular;  /* problems that ended with PSD_INFO_SINGULAR */
+    int32_t reserved;
+    double ms_kernels;  /* device time of the kernels and their read-backs */
+    double ms_copy;     /* host entries: time of the copies */
+} psd_bsylv_stats;
+int psd_d_psylv_batch(psd_ctx* ctx, int nb, int n, int p, double* const* T, char orient, int schurindex, const int* m,
+                      double* const* C, int64_t xb, int trans, int from_t12, int* infos, psd_bsylv_stats* stats, int* info);
+int psd_z_psylv_batch(psd_ctx* ctx, int nb, int n, int p, double* const* T, char orient, int schurindex, const int* m,
+                      double* const* C, int64_t xb, int trans, int from_t12, int* infos, psd_bsylv_stats* stats, int* info);
+int psd_d_psylv_batch_dev(psd_ctx* ctx, int nb, int n, int p, const double* dT, char orient, int schurindex, const int* m,
+                          double* dC, int64_t xb, int trans, int from_t12, int* infos, psd_bsylv_stats* stats, int* info);
+int psd_z_psylv_batch_dev(psd_ctx* ctx, int nb, int n, int p, const double* dT, char orient, int schurindex, const int* m,
+                          double* dC, int64_t xb, int trans, int from_t12, int* infos, psd_bsylv_stats* stats, int* info);
+int psd_d_subcond_batch(psd_ctx* ctx, int nb, int n, int p, double* const* T, char orient, int schurindex, const int* m,
+                        double* s, double* sep, double* const* X, int64_t xb, int* infos, psd_bsylv_stats* stats, int* info);
+int psd_z_subcond_batch(psd_ctx* ctx, int nb, int n, int p, double* const* T, char orient, int schurindex, const int* m,
+                        double* s, double* sep, double* const* X, int64_t xb, int* infos, psd_bsylv_stats* stats, int* info);
+int psd_d_subcond_batch_dev(psd_ctx* ctx, int nb, int n, int p, const double* dT, char orient, int schurindex, const int* m,
+                            double* s, double* sep, double* dX, int64_t xb, int* infos, psd_bsylv_stats* stats, int* info);
+int psd_z_subcond_batch_dev(psd_ctx* ctx, int nb, int n, int p, const double* dT, char orient, int schurindex, const int* m,
+                            double* s, double* sep, double* dX, int64_t xb, int* infos, psd_bsylv_stats* stats, int* info);
+
 #ifdef __cplusplus
 }
 #endif

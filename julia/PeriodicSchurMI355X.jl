@@ -24,7 +24,7 @@ import PeriodicSchurDecompositions: pschur!, pschur, phessenberg!, gpschur, Peri
 const PSD = PeriodicSchurDecompositions
 using ArnoldiMethod: ArnoldiMethod
 
-export set_train!, engine_version, pschur_batch!, pschur_batch, gpschur_batch, eigvecs_batch_device, eigcond_batch, geigvecs_batch_device, ordschur_batch!, checkpsd_batch
+export set_train!, engine_version, pschur_batch!, pschur_batch, gpschur_batch, eigvecs_batch_device, eigcond_batch, subspacecond_batch, psylvester_batch, geigvecs_batch_device, ordschur_batch!, checkpsd_batch
 
 const libpsd = get(ENV, "LIBPSD_MI355X", joinpath(@__DIR__, "..", "periodicschurdecompositions.jl_amd", "libpsd_mi355x.so"))
 
@@ -648,6 +648,88 @@ function eigcond_batch(problems::Vector{<:PeriodicSchur}, select::AbstractVector
     end
     info[] != 0 && _throw(info[])
     return ([s[:, 1:nvec[q], q] for q in 1:nb], V, W)
+end
+
+# subspacecond_batch(problems, m; want_x) and psylvester_batch(problems, m; C, trans) — no reference equivalent: the
+# periodic form of xTRSEN's S and SEP for the leading m eigenvalues of many small decompositions (Float64 or ComplexF64,
+# all-true signature; psd_?_subcond_batch), and the periodic Sylvester solve they are built on (psd_?_psylv_batch).
+# Problem q is split at m[q] (`m`: an Int or one per problem; not inside a 2 x 2 block), k = n - m:
+# T_l = [T11_l T12_l; 0 T22_l]; with (a, b) = (l + 1, l) cyclically for orientation 'L' and (l, l + 1) for 'R',
+#     S(X)_l = T11_l X_b - X_a T22_l.
+# psylvester_batch solves S(X) = C, or with trans = true the adjoint system S^H(Y) = C; C = nothing: C_l = -T12_l, and then
+# T_l [X_b; I] = [X_a; I] T22_l, so that Y_l = Z_l [X_l; I] spans the complementary periodic invariant subspace.  It
+# returns per problem the p matrices X_l (m x k).  subspacecond_batch returns (s, sep) — s a p x nb matrix,
+# s[l, q] = 1 / sqrt(1 + ||X_l||_F^2), sep[q] the reciprocal of LAPACK's xLACN2 estimate of ||S^-1||_1 on the p m k stacked
+# unknowns — and with want_x = true also X.  m = 0 or n: s = 1, sep = Inf.  A singular problem (T11 and T22 share an
+# eigenvalue of the product) gets X = NaN, s = 0, sep = 0, and its code (3000) is thrown after all have run unless `infos`
+# is given.  There is no scale factor (xTRSYL carries one) and no path above order 128 (NotImplemented).
+# (Written by analogy with Engine.subspacecond_batch / Engine.psylvester_batch, the tested mirrors; not run.)
+function _bsylv_inputs(problems::Vector{<:PeriodicSchur}, m)
+    nb = length(problems)
+    ps1 = problems[1]
+    p = ps1.period; n = size(ps1.T1, 1); js = ps1.schurindex; orient = ps1.orientation
+    for ps in problems
+        ps isa GeneralizedPeriodicSchur && !all(ps.S) &&
+            throw(PSD.NotImplemented("subspacecond_batch / psylvester_batch: signed GeneralizedPeriodicSchur"))
+        (ps.period == p && size(ps.T1, 1) == n && ps.schurindex == js && ps.orientation == orient) ||
+            throw(DimensionMismatch("the problems of a batch must have equal order, period, orientation and schurindex"))
+    end
+    mm = m isa Integer ? fill(Cint(m), nb) : Cint.(collect(m))
+    length(mm) == nb || throw(DimensionMismatch("m must be an Int or one Int per problem"))
+    # user order: T1 at schurindex, the others around it
+    T = reduce(vcat, [[j == js ? ps.T1 : ps.T[j < js ? j : j - 1] for j in 1:p] for ps in problems])
+    xb = max(1, maximum(Int(mq) * (n - Int(mq)) for mq in mm))
+    return nb, n, p, js, orient, mm, T, xb
+end
+_bsylv_blocks(bufs, mm, n, p, q) = [reshape(bufs[(q - 1) * p + l][1:(mm[q] * (n - mm[q]))], Int(mm[q]), n - Int(mm[q])) for l in 1:p]
+
+for (Tv, solve, cond) in ((Float64, :psd_d_psylv_batch, :psd_d_subcond_batch),
+                          (ComplexF64, :psd_z_psylv_batch, :psd_z_subcond_batch))
+@eval function psylvester_batch(problems::Vector{<:PeriodicSchur{$Tv}}, m; C = nothing, trans::Bool = false,
+                                infos::Union{Nothing, Vector{Cint}} = nothing)
+    isempty(problems) && return Vector{Matrix{$Tv}}[]
+    nb, n, p, js, orient, mm, T, xb = _bsylv_inputs(problems, m)
+    bufs = [zeros($Tv, xb) for _ in 1:(nb * p)]
+    if C !== nothing
+        for q in 1:nb, l in 1:p
+            size(C[q][l]) == (mm[q], n - mm[q]) || throw(DimensionMismatch("the right-hand sides of a problem are p matrices m x k"))
+            bufs[(q - 1) * p + l][1:length(C[q][l])] .= vec(C[q][l])
+        end
+    end
+    codes = infos === nothing ? zeros(Cint, nb) : infos
+    info = Ref{Cint}(0)
+    Tp = _ptrs(T); Xp = [pointer(b) for b in bufs]
+    GC.@preserve T bufs Xp mm codes begin
+        ccall(($(QuoteNode(solve)), libpsd), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Ptr{Float64}}, Cchar, Cint, Ptr{Cint}, Ptr{Ptr{$Tv}}, Int64, Cint, Cint,
+               Ptr{Cint}, Ptr{Cvoid}, Ref{Cint}),
+              ctx().ptr, nb, n, p, Tp, orient, js, mm, Xp, xb, trans, C === nothing, codes, C_NULL, info)
+    end
+    (info[] < 0 || info[] >= INFO_NOTIMPL) && _throw(info[])
+    out = [_bsylv_blocks(bufs, mm, n, p, q) for q in 1:nb]
+    infos === nothing && info[] != 0 && _throw_ord(info[])
+    return out
+end
+
+@eval function subspacecond_batch(problems::Vector{<:PeriodicSchur{$Tv}}, m; want_x::Bool = false,
+                                  infos::Union{Nothing, Vector{Cint}} = nothing)
+    isempty(problems) && return want_x ? (zeros(0, 0), Float64[], Vector{Matrix{$Tv}}[]) : (zeros(0, 0), Float64[])
+    nb, n, p, js, orient, mm, T, xb = _bsylv_inputs(problems, m)
+    bufs = want_x ? [zeros($Tv, xb) for _ in 1:(nb * p)] : Vector{$Tv}[]
+    s = zeros(Float64, p, nb); sep = zeros(Float64, nb)
+    codes = infos === nothing ? zeros(Cint, nb) : infos
+    info = Ref{Cint}(0)
+    Tp = _ptrs(T); Xp = [pointer(b) for b in bufs]
+    GC.@preserve T bufs Xp mm codes s sep begin
+        ccall(($(QuoteNode(cond)), libpsd), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Ptr{Float64}}, Cchar, Cint, Ptr{Cint}, Ptr{Float64}, Ptr{Float64},
+               Ptr{Ptr{$Tv}}, Int64, Ptr{Cint}, Ptr{Cvoid}, Ref{Cint}),
+              ctx().ptr, nb, n, p, Tp, orient, js, mm, s, sep, want_x ? pointer(Xp) : C_NULL, xb, codes, C_NULL, info)
+    end
+    (info[] < 0 || info[] >= INFO_NOTIMPL) && _throw(info[])
+    infos === nothing && info[] != 0 && _throw_ord(info[])
+    return want_x ? (s, sep, [_bsylv_blocks(bufs, mm, n, p, q) for q in 1:nb]) : (s, sep)
+end
 end
 
 # geigvecs_batch_device(problems, select; shifted) — geigvecs_device for many small signed ComplexF64 decompositions of one

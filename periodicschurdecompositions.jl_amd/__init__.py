@@ -175,6 +175,22 @@ class BcheckStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+_ct = C  # (psylvester_batch has an argument of the name C)
+
+
+class BsylvStats(C.Structure):
+    """psd_bsylv_stats (include/psd_mi355x.h): launches, estimator iterations and device times of one psylvester_batch
+    or subspacecond_batch call."""
+    _fields_ = [
+        ("nb", C.c_int32), ("ngroups", C.c_int32), ("nsolve", C.c_int32), ("nnorms", C.c_int32),
+        ("nest_steps", C.c_int32), ("nest_iter", C.c_int32), ("nsingular", C.c_int32), ("reserved", C.c_int32),
+        ("ms_kernels", C.c_double), ("ms_copy", C.c_double),
+    ]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class PKSFailure(Exception):
     """PKSFailure (src/krylov.jl:21-23): the Arnoldi re-initialisation failed."""
 
@@ -414,6 +430,11 @@ class Engine:
                                                                 C.c_int, dp, ip, i32p, C.POINTER(BevecStats), ip])
                 sigs[f"psd_{t}_checkpsd_batch{dev}"] = (head + [mats, mats, mats, u8p, C.c_char, C.c_int, C.c_double,
                                                                 C.c_int, dp, dp, dp, i32p, C.POINTER(BcheckStats), ip])
+                # (T, orient, schurindex, m, then C, xb, trans, from_t12 / s, sep, X, xb)
+                sigs[f"psd_{t}_psylv_batch{dev}"] = (head + [mats, C.c_char, C.c_int, ip, mats, C.c_int64, C.c_int, C.c_int,
+                                                             ip, C.POINTER(BsylvStats), ip])
+                sigs[f"psd_{t}_subcond_batch{dev}"] = (head + [mats, C.c_char, C.c_int, ip, dp, dp, mats, C.c_int64, ip,
+                                                               C.POINTER(BsylvStats), ip])
             for nm, sig in sigs.items():
                 if hasattr(lib, nm):  # (tools load builds of earlier commits to time their single calls)
                     getattr(lib, nm).argtypes = sig
@@ -2075,6 +2096,199 @@ class Engine:
         fn(self.ctx, nb, n, p, V, W, orient.encode(), maxvec, nv, s.ctypes.data_as(C.POINTER(C.c_double)),
            C.byref(info))
         self._raise(info.value)
+
+    # ---- periodic Sylvester solves and the condition of an invariant periodic subspace ----------------------------
+    def _bsylv_inputs(self, name, problems, m, lr, schurindex):
+        """What psylvester_batch and subspacecond_batch share: (fam, dev, nb, n, p, T argument, orient, schurindex, m
+        as int32 [nb], xb, keep-alive); `problems` a list of PeriodicSchur or a GPU tensor [nb, p, n, n]."""
+        wrong = TypeError(f"{name}: the problems of a batch must all be Float64 or all ComplexF64")
+        if hasattr(problems, "data_ptr"):
+            import torch
+
+            if problems.dtype not in (torch.float64, torch.complex128):
+                raise TypeError(f"{name}: a float64 or complex128 tensor")
+            fam = _Z if problems.is_complex() else _D
+            nb, p, n = self._dev_batch(fam, name, wrong, problems)
+            orient, si = char_lr(lr), int(schurindex)
+            keep = _dev_blocks(problems, fam, "readonly") if nb else problems
+            T = C.c_void_p(keep.data_ptr())
+            dev = True
+        else:
+            problems = list(problems)
+            nb = len(problems)
+            if nb == 0:
+                return None
+            fam = _Z if len(problems[0].Ts) > 0 and np.iscomplexobj(problems[0].Ts[0]) else _D
+            n, p, orient, si, keep = self._batch_decomps(fam, name, wrong, problems, needZ=False, work=False)
+            orient = char_lr(orient)
+            T = self._ptrs(keep)
+            dev = False
+        mm = np.asarray(m)
+        if mm.ndim == 0:
+            mm = np.full(nb, mm)
+        if mm.shape != (nb,) or not np.issubdtype(mm.dtype, np.integer):
+            raise DimensionMismatch(f"{name}: m must be an int or [nb] ints")
+        mm = np.ascontiguousarray(mm, dtype=np.int32)
+        xb = max(1, int(np.max(mm.astype(np.int64) * (n - mm)))) if nb else 1
+        return fam, dev, nb, n, p, T, orient, si, mm, xb, keep
+
+    @staticmethod
+    def _bsylv_blocks(buf, mm, n, q):
+        """the m x k matrices of problem q from its flat blocks"""
+        mq = int(mm[q])
+        return [np.asfortranarray(b[:mq * (n - mq)].reshape((mq, n - mq), order="F")) for b in buf]
+
+    def _bsylv_dev_x(self, X, mm, n):
+        """the device blocks [nb, p, xb] as the device forms return them: [nb, p, m, k] views for one common m"""
+        nb, p = X.shape[0], X.shape[1]
+        if nb > 0 and np.all(mm == mm[0]) and 0 < mm[0] < n:
+            mq = int(mm[0])
+            return X[:, :, :mq * (n - mq)].reshape(nb, p, n - mq, mq).transpose(2, 3)
+        return X
+
+    def psylvester_batch(self, problems, m, C=None, trans=False, lr="R", schurindex=1, infos_out=None):
+        """Periodic Sylvester solves on the off-diagonal block of MANY small periodic Schur forms of one shape in ONE
+        call (psd_?_psylv_batch).  Float64 or ComplexF64, picked from the dtype; all-true signature (a signed
+        GeneralizedPeriodicSchur: NotImplementedPSD).
+
+        Problem q is split at m[q] (`m`: an int or [nb] ints, 0 <= m <= n, not inside a 2x2 block), k = n - m:
+        T_l = [T11_l T12_l; 0 T22_l].  With (a, b) = (l + 1, l) cyclically for orientation "L" and (l, l + 1) for "R",
+            S(X)_l = T11_l X_b - X_a T22_l ,   l = 1..p,
+        and the call solves S(X) = C, or with trans=True S^H(Y) = C (the adjoint under the Frobenius inner product over
+        the stacked blocks).  C=None: C_l = -T12_l; the solution then block-diagonalises the form,
+        T_l [X_b; I] = [X_a; I] T22_l, so that Y_l = Z_l [X_l; I] spans the complementary periodic invariant
+        subspace (A_l Y_b = Y_a T22_l).  There is no scale factor (xTRSYL carries one), and no path above order 128 (NotImplementedPSD).
+
+        psylvester_batch(problems, m, C=None, trans=False): `problems` a list of PeriodicSchur, `C` per problem p
+        matrices m x k; returns per problem the p matrices X_l.
+        psylvester_batch(T, m, C=None, trans=False, lr=..., schurindex=...): T a GPU tensor [nb, p, n, n] as
+        pschur_batch_ / ordschur_batch_ return it (only read, not copied in that layout); C and the result GPU tensors
+        [nb, p, m, k] for one common m, otherwise [nb, p, xb] flat column-major blocks, xb = max m (n - m).  C is not
+        written.
+
+        A problem whose small solve is rejected (T11 and T22 share an eigenvalue of the product) or whose solution is
+        not finite has X = NaN; the others complete, and SingularException is raised afterwards, or the codes go to
+        `infos_out`.  A problem's result does not depend on its place in the batch, bit for bit.  Stats:
+        `self.psylvester_batch_stats` (BsylvStats)."""
+        name = "psylvester_batch"
+        inp = self._bsylv_inputs(name, problems, m, lr, schurindex)
+        self.psylvester_batch_stats = BsylvStats()
+        if inp is None:
+            if infos_out is not None:
+                infos_out[:] = []
+            return []
+        fam, dev, nb, n, p, T, orient, si, mm, xb, keep = inp
+        if dev:
+            import torch
+
+            dt = getattr(torch, np.dtype(fam.dtype).name)
+            X = torch.zeros((nb, p, xb), dtype=dt, device=problems.device)
+            if C is not None:
+                if C.dim() == 4:  # [nb, p, m, k] of one common m
+                    mq = int(mm[0]) if nb else 0
+                    if nb and (not np.all(mm == mq) or tuple(C.shape) != (nb, p, mq, n - mq)):
+                        raise DimensionMismatch(f"{name}: C must be [nb, p, m, k] (one common m) or [nb, p, xb]")
+                    X[:, :, :mq * (n - mq)] = C.to(dt).transpose(2, 3).reshape(nb, p, mq * (n - mq))
+                elif tuple(C.shape) == (nb, p, xb):
+                    X.copy_(C.to(dt))
+                else:
+                    raise DimensionMismatch(f"{name}: C must be [nb, p, m, k] (one common m) or [nb, p, xb]")
+            if nb == 0:
+                if infos_out is not None:
+                    infos_out[:] = []
+                return X
+            torch.cuda.synchronize(problems.device)
+            Xarg = _ct.c_void_p(X.data_ptr())
+        else:
+            bufs = [np.zeros(xb, dtype=fam.dtype) for _ in range(nb * p)]
+            if C is not None:
+                C = list(C)
+                if len(C) != nb:
+                    raise DimensionMismatch(f"{name}: one list of p right-hand sides per problem")
+                for q, Cq in enumerate(C):
+                    Cq = list(Cq)
+                    mq = int(mm[q])
+                    if len(Cq) != p or any(np.shape(c) != (mq, n - mq) for c in Cq):
+                        raise DimensionMismatch(f"{name}: the right-hand sides of a problem are p matrices m x k")
+                    if fam is _D and any(np.iscomplexobj(c) for c in Cq):
+                        raise TypeError(f"{name}: the problems of a batch must all be Float64 or all ComplexF64")
+                    for l, c in enumerate(Cq):
+                        bufs[q * p + l][:mq * (n - mq)] = np.asarray(c, dtype=fam.dtype).reshape(-1, order="F")
+            Xarg = self._ptrs(bufs)
+        infos, st, info = (_ct.c_int * nb)(), BsylvStats(), _ct.c_int(0)
+        fn = getattr(self.lib, f"psd_{fam.tag}_psylv_batch{'_dev' if dev else ''}")
+        fn(self.ctx, nb, n, p, T, orient.encode(), si, mm.ctypes.data_as(_ct.POINTER(_ct.c_int)), Xarg, xb, int(bool(trans)),
+           int(C is None), infos, _ct.byref(st), _ct.byref(info))
+        self.psylvester_batch_stats = st
+
+        def result():
+            if dev:
+                return self._bsylv_dev_x(X, mm, n)
+            return [self._bsylv_blocks(bufs[q * p:(q + 1) * p], mm, n, q) for q in range(nb)]
+
+        return self._batch_finish(info.value, infos, infos_out, self._raise_ord, True, result)
+
+    def subspacecond_batch(self, problems, m, want_x=False, lr="R", schurindex=1, infos_out=None):
+        """How well separated the leading invariant periodic subspace of MANY small periodic Schur forms is: the
+        periodic form of xTRSEN's S and SEP (psd_?_subcond_batch), the follow-up of ordschur_batch.  Float64 or
+        ComplexF64, picked from the dtype; all-true signature (a signed GeneralizedPeriodicSchur: NotImplementedPSD).
+
+        With the split m (an int or [nb] ints), the operator S and X the solution of S(X) = -T12 as in
+        `psylvester_batch`:
+            s[q, l] = 1 / sqrt(1 + ||X_l||_F^2): the reciprocal of the Frobenius bound on the norm of the spectral
+                      projector of factor l (p = 1: xTRSEN's S);
+            sep[q]  = 1 / est, est the estimate of ||S^-1||_1 on the p m k stacked unknowns (blocks in user order, each
+                      column-major) by LAPACK's xLACN2 — real variant for Float64, complex for ComplexF64, at most 5
+                      iterations and the final alternating-sign vector (p = 1: xTRSEN's SEP).
+        m = 0 or m = n: s = 1, sep = inf, X empty.  There is no scale factor, and no path above order 128
+        (NotImplementedPSD).
+
+        subspacecond_batch(problems, m, want_x=False) with a list of PeriodicSchur, or
+        subspacecond_batch(T, m, want_x=False, lr=..., schurindex=...) with a GPU tensor [nb, p, n, n] (only read):
+        returns (s, sep), numpy arrays [nb, p] and [nb], with want_x also X as `psylvester_batch` returns it.
+
+        A problem whose small solve is rejected or whose numbers are not finite gets s = 0, sep = 0, X = NaN; the others
+        complete, and SingularException is raised afterwards, or the codes go to `infos_out`.  A problem's numbers do
+        not depend on its place in the batch, bit for bit.  Stats: `self.subspacecond_batch_stats` (BsylvStats)."""
+        name = "subspacecond_batch"
+        inp = self._bsylv_inputs(name, problems, m, lr, schurindex)
+        self.subspacecond_batch_stats = BsylvStats()
+        if inp is None:
+            if infos_out is not None:
+                infos_out[:] = []
+            return (np.zeros((0, 0)), np.zeros(0), []) if want_x else (np.zeros((0, 0)), np.zeros(0))
+        fam, dev, nb, n, p, T, orient, si, mm, xb, keep = inp
+        s, sep = np.zeros((nb, p)), np.zeros(nb)
+        X = bufs = Xarg = None
+        if dev:
+            import torch
+
+            if want_x:
+                X = torch.zeros((nb, p, xb), dtype=getattr(torch, np.dtype(fam.dtype).name), device=problems.device)
+                Xarg = C.c_void_p(X.data_ptr())
+            if nb == 0:
+                if infos_out is not None:
+                    infos_out[:] = []
+                return (s, sep, X) if want_x else (s, sep)
+            torch.cuda.synchronize(problems.device)
+        elif want_x:
+            bufs = [np.zeros(xb, dtype=fam.dtype) for _ in range(nb * p)]
+            Xarg = self._ptrs(bufs)
+        infos, st, info = (C.c_int * nb)(), BsylvStats(), C.c_int(0)
+        dp = C.POINTER(C.c_double)
+        fn = getattr(self.lib, f"psd_{fam.tag}_subcond_batch{'_dev' if dev else ''}")
+        fn(self.ctx, nb, n, p, T, orient.encode(), si, mm.ctypes.data_as(C.POINTER(C.c_int)), s.ctypes.data_as(dp),
+           sep.ctypes.data_as(dp), Xarg, xb, infos, C.byref(st), C.byref(info))
+        self.subspacecond_batch_stats = st
+
+        def result():
+            if not want_x:
+                return s, sep
+            if dev:
+                return s, sep, self._bsylv_dev_x(X, mm, n)
+            return s, sep, [self._bsylv_blocks(bufs[q * p:(q + 1) * p], mm, n, q) for q in range(nb)]
+
+        return self._batch_finish(info.value, infos, infos_out, self._raise_ord, True, result)
 
     def eigvecs_batch(self, problems, *args, shifted=True, lr="R", schurindex=1, side="R"):
         """eigvecs(ps, select; shifted) by periodic back-substitution for MANY small decompositions of one shape in ONE

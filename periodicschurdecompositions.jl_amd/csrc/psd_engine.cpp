@@ -36,6 +36,7 @@
 #include "psd_zbord.h"
 #include "psd_zgbord.h"
 #include "psd_gbord.h"
+#include "psd_bsylv.h"
 
 #include "../../include/psd_mi355x.h"
 
@@ -306,6 +307,7 @@ struct psd_ctx {
     int bev_nmax = PSD_BEV_NMAX;  // largest order of the batched eigenvector kernels (diagnostic build: PSD_BEV_NMAX in the environment, for the sweep that sets the constant)
     int bord_nmax = PSD_BORD_NMAX;  // largest order of the batched reordering kernel (PSD_BORD_NMAX in the environment lowers it: the tests reach the fallback with it)
     int bck_nmax = PSD_BCK_NMAX;    // largest order of the batched verifier (PSD_BCK_NMAX in the environment lowers it: the tests reach the fallback with it)
+    int bsyl_nmax = PSD_BSYL_NMAX;  // largest order of the batched periodic Sylvester kernels (PSD_BSYL_NMAX in the environment lowers it: the tests reach the refusal with it; there is no path above it)
     int bord_w = 0;                 // PSD_BORD_W: a narrower window of the batched reordering kernel (0: bord_window's own choice)
     void slice(int p, int& lo, int& hi) const {  // [lo, hi), 0-based internal factor index
         const int base = p / shard_world, rem = p % shard_world;
@@ -1930,6 +1932,7 @@ int psd_create(psd_ctx** ctx, int device) {
     if (const char* e = psd_env_diag("PSD_BEV_NMAX")) c->bev_nmax = (atoi(e) >= 1 && atoi(e) <= 2048) ? atoi(e) : PSD_BEV_NMAX;
     if (const char* e = psd_env("PSD_BORD_NMAX")) c->bord_nmax = (atoi(e) >= 1 && atoi(e) < PSD_BORD_NMAX) ? atoi(e) : PSD_BORD_NMAX;
     if (const char* e = psd_env("PSD_BCK_NMAX")) c->bck_nmax = (atoi(e) >= 1 && atoi(e) < PSD_BCK_NMAX) ? atoi(e) : PSD_BCK_NMAX;
+    if (const char* e = psd_env("PSD_BSYL_NMAX")) c->bsyl_nmax = (atoi(e) >= 1 && atoi(e) < PSD_BSYL_NMAX) ? atoi(e) : PSD_BSYL_NMAX;
     if (const char* e = psd_env("PSD_BORD_W")) c->bord_w = (atoi(e) >= 1 && atoi(e) <= 32) ? atoi(e) : 0;  // (each kernel has its own least window: PSD_BORD_WMIN, PSD_ZBORD_WMIN)
     if (const char* e = psd_env("PSD_BAND_HELPER")) c->band_helper = atoi(e);
     if (const char* e = psd_env_diag("PSD_TRAIN_LONG")) c->train_long = atoi(e);
@@ -3973,4 +3976,5 @@ extern "C" int psd_dbg_apply_bench(psd_ctx* c, int n, int p, int nwin, int W, in
 #include "psd_zgbord_host.inl"
 #include "psd_gbord_host.inl"
 #include "psd_bcheck_host.inl"
+#include "psd_bsylv_host.inl"
 #include "psd_diag_scalar.inl"
