@@ -63,6 +63,7 @@ psd_simctx psd_sim;
         int _e = (int)(expr);                            \
         if (_e != 0) return PSD_INFO_RUNTIME + (_e & 0xffff); \
     } while (0)
+#define PSD_ALLOC(ptr, type, count) PSD_CHECK(psd_rt_malloc((void**)&ptr, sizeof(type) * (size_t)(count)))
 
 // Environment switches (INTEGRATION.md lists them).
 //  * psd_env(): selectors between code paths that ALL return a correct decomposition (the tests use them to reach every
@@ -464,14 +465,12 @@ struct psd_ctx {
     int zgreserve(int n, int p) {
         if (n <= zgcap_n && p <= zgcap_p) return 0;
         zgrelease();
-#define PSD_ALLOC(ptr, type, count) PSD_CHECK(psd_rt_malloc((void**)&ptr, sizeof(type) * (size_t)(count)))
         PSD_ALLOC(zgst, psd_zgstate, 1);
         PSD_ALLOC(zgdesc, psd_gapply_desc, 1);
         PSD_ALLOC(zgtr, psd_ztr, (size_t)p * PSD_GTR_CAP);
         PSD_ALLOC(zgdG, psd_ztr, n + 8);
         PSD_ALLOC(zgS, unsigned char, p + 16);
         PSD_ALLOC(zgcnt, int, p + 8);
-#undef PSD_ALLOC
         zgcap_n = n;
         zgcap_p = p;
         return 0;
@@ -488,7 +487,6 @@ struct psd_ctx {
     int greserve(int n, int p, int maxlog) {
         if (n <= gcap_n && p <= gcap_p && maxlog <= glogcap) return 0;
         grelease();
-#define PSD_ALLOC(ptr, type, count) PSD_CHECK(psd_rt_malloc((void**)&ptr, sizeof(type) * (size_t)(count)))
         PSD_ALLOC(gst, psd_gstate, 1);
         PSD_ALLOC(gdesc, psd_gapply_desc, 1);
         PSD_ALLOC(gtr, psd_gtr, (size_t)p * PSD_GTR_CAP);
@@ -500,7 +498,6 @@ struct psd_ctx {
         PSD_ALLOC(gascale, int, n + 8);
         PSD_ALLOC(gcnt, int, p + 8);
         PSD_ALLOC(glog, int, 3 * (size_t)maxlog + 8);
-#undef PSD_ALLOC
         gcap_n = n;
         gcap_p = p;
         glogcap = maxlog;
@@ -579,7 +576,6 @@ struct psd_ctx {
         const bool keep = mats || zcap_mats;
         zrelease();
         const size_t nn = (size_t)n * n;
-#define PSD_ALLOC(ptr, type, count) PSD_CHECK(psd_rt_malloc((void**)&ptr, sizeof(type) * (size_t)(count)))
         if (keep) {
             PSD_ALLOC(zH, psd_z, nn * p);
             PSD_ALLOC(zZ, psd_z, nn * p);
@@ -600,7 +596,6 @@ struct psd_ctx {
         PSD_ALLOC(oslots, psd_oslot, PSD_O_SLOTS);
         PSD_ALLOC(omb, psd_omb, 1);
         PSD_ALLOC(osel, unsigned char, n + 16);
-#undef PSD_ALLOC
         zcap_n = n;
         zcap_p = p;
         zcap_mats = keep;
@@ -613,7 +608,6 @@ struct psd_ctx {
         const bool keep_mats = mats || cap_mats;
         release();
         const size_t nn = (size_t)n * n;
-#define PSD_ALLOC(ptr, type, count) PSD_CHECK(psd_rt_malloc((void**)&ptr, sizeof(type) * (size_t)(count)))
         if (keep_mats) {
             PSD_ALLOC(dH, double, nn * p);
             PSD_ALLOC(dZ, double, nn * p);
@@ -634,7 +628,6 @@ struct psd_ctx {
         PSD_ALLOC(tr, psd_tr, (size_t)p * PSD_TR_CAP);
         PSD_ALLOC(cnt, int, p + 8);
         PSD_ALLOC(log, int, 3 * (size_t)maxlog + 8);
-#undef PSD_ALLOC
         cap_n = n;
         cap_p = p;
         cap_mats = keep_mats;
@@ -1196,6 +1189,90 @@ int launch_apply_wl(psd_ctx* c, psd_stream_t stream, const psd_rparams& Pq, int 
     return 0;
 }
 
+// The tick loop of the four iteration drivers.  tick(launched, sample) enqueues everything one tick launches and wraps its
+// chase launch in sample.around(); ticks go out in batches of 32, behind each batch the polled state of the device comes
+// to `host` (psd_poller; the serial simulation drains), and the loop ends when done(host) says so or, past `cap` ticks,
+// with the driver's runaway code.
+struct tick_totals {
+    long long launched = 0;
+    double sample_ms = 0.0;
+    int samples = 0;
+};
+// HIP events around the chase launch of every 16th tick of a profiled context (nothing in the serial simulation)
+struct tick_sample {
+#ifndef PSD_HOSTSIM
+    psd_stream_t stream = nullptr;
+    psd_poller::evlist* pend = nullptr;  // null: this tick is not sampled
+#endif
+    template <class Launch>
+    int around(Launch launch) const {
+#ifndef PSD_HOSTSIM
+        hipEvent_t ev0 = nullptr, ev1 = nullptr;
+        if (pend) {
+            (void)hipEventCreate(&ev0);
+            (void)hipEventCreate(&ev1);
+            (void)hipEventRecord(ev0, stream);
+        }
+#endif
+        if (int rc = launch()) return rc;
+#ifndef PSD_HOSTSIM
+        if (pend) {
+            (void)hipEventRecord(ev1, stream);
+            pend->emplace_back(ev0, ev1);
+        }
+#endif
+        return 0;
+    }
+};
+template <class Polled, class Tick, class Done>
+int tick_loop(psd_ctx* c, const Polled* dev, Polled& host, long long cap, int runaway_code, bool sampling, Tick tick,
+              Done done, tick_totals& out) {
+#ifndef PSD_HOSTSIM
+    psd_poller::evlist pend;
+    psd_poller poller(c, out.sample_ms, out.samples);
+#else
+    (void)sampling;
+#endif
+    for (;;) {
+        for (int b = 0; b < 32; ++b, ++out.launched) {
+            tick_sample sample;
+#ifndef PSD_HOSTSIM
+            if (sampling && c->profile && (out.launched & 15) == 0) sample = {c->stream, &pend};
+#endif
+            if (int rc = tick(out.launched, sample)) return rc;
+        }
+#ifdef PSD_HOSTSIM
+        PSD_CHECK(psd_rt_d2h(&host, dev, sizeof(host), c->stream));
+        PSD_CHECK(psd_rt_sync(c->stream));
+#else
+        PSD_CHECK(poller.poll(&host, dev, sizeof(host), pend));
+#endif
+        if (done(host)) break;
+        if (out.launched > cap) return PSD_INFO_RUNTIME + runaway_code;
+    }
+#ifndef PSD_HOSTSIM
+    PSD_CHECK(poller.finish(pend));
+#endif
+    return 0;
+}
+void stats_from_ticks(psd_stats* s, const tick_totals& t, int W) {
+    if (!s) return;
+    s->nlaunch_step = (int32_t)t.launched;
+    s->window = W;
+    s->step_kernel_ms_avg = t.samples ? t.sample_ms / t.samples : 0.0;
+    s->step_kernel_samples = t.samples;
+}
+
+// A copy of the parameter block of a driver that keeps two sets of descriptors, counts and lists (`slots` cursors each,
+// lists of `tr_cap` records per owner; ticks alternate between them) with the three moved to set `par`.
+template <class Params>
+Params parity_set(Params P, int par, int slots, int tr_cap, int p) {
+    P.desc += (size_t)par * slots;
+    P.cnt += (size_t)par * slots * (p + 8);
+    P.tr += (size_t)par * slots * p * tr_cap;
+    return P;
+}
+
 // PSD.jl:322-1096 on device.  dH: H_1 Hessenberg, H_j triangular; dZ: Q_j (or identity) or null.
 // nprob > 1 (batch, psd_d_pschur_hess_batch): dH / dZ hold nprob problems back to back, bws the per-problem band arrays
 // hdiag | hsub | hsup | Pd | Pe | Pf | wr | wi (nprob (n + 8) doubles each) and hnorms (nprob (p + 8)); pinfo_out: info per
@@ -1205,17 +1282,6 @@ int iterate_dev(psd_ctx* c, int n, int p, double* dH, double* dZ, int wantT, int
                 int* pinfo_out = nullptr) {
     const int W = choose_window(p, 8, true);
     if (W == 0) return PSD_INFO_NOTIMPL;
-#ifndef PSD_HOSTSIM
-    // Every way out (a failed runtime call or the runaway cap in the middle of the launch sequence included) first waits
-    // for the side streams: their launches read this call's lists and write the caller's factors and Schur vectors.
-    struct BulkStreams {
-        psd_ctx* c;
-        ~BulkStreams() {
-            if (c->stream2) (void)hipStreamSynchronize(c->stream2);
-            if (c->stream3) (void)hipStreamSynchronize(c->stream3);
-        }
-    } bulk_streams{c};
-#endif
     psd_rparams P;
     P.H = dH;
     P.Z = wantZ ? dZ : nullptr;
@@ -1263,14 +1329,16 @@ int iterate_dev(psd_ctx* c, int n, int p, double* dH, double* dZ, int wantT, int
     P.slerr = nullptr;
     const int c2waves = scan3 ? PSD_C3_WAVES : (P.c2off ? 2 : 1);
     (void)c2waves;
-    // Every way out of this function (the runaway cap, a failed runtime call) first waits for the second stream — its
-    // Schur-vector launches read the caller's dZ and the lists — and frees the tick log.
+    // Every way out of this function (a failed runtime call or the runaway cap in the middle of the launch sequence
+    // included) first waits for the side streams — their launches read this call's lists and write the caller's factors
+    // and Schur vectors — and frees the tick log.
     struct ExitGuard {
         psd_ctx* c;
         int** ticklog;
         ~ExitGuard() {
 #ifndef PSD_HOSTSIM
             if (c->stream2) (void)hipStreamSynchronize(c->stream2);
+            if (c->stream3) (void)hipStreamSynchronize(c->stream3);
 #endif
             if (*ticklog) {
                 psd_rt_free(*ticklog);
@@ -1365,7 +1433,6 @@ int iterate_dev(psd_ctx* c, int n, int p, double* dH, double* dZ, int wantT, int
                mb ? 1 : 0, mb ? c->cgap : 2, c->train_long, (c->train_wdiv > 0) ? c->train_wdiv : ((p >= 12 && p <= 32) ? 6 : ((p < 12 && n >= 512) ? 16 : 8)));
     const size_t lds_apply = apply_lds_bytes();
     const int tiles = (n + PSD_APPLY_NT - 1) / PSD_APPLY_NT;
-    const int batch = 32;
     int zlo0 = 0, zhi0 = p;
     c->slice(p, zlo0, zhi0);
     const int zlo1 = zlo0 + 1, zhi1 = zhi0;  // owners (1-based, inclusive) whose Z_m this context updates
@@ -1373,240 +1440,190 @@ int iterate_dev(psd_ctx* c, int n, int p, double* dH, double* dZ, int wantT, int
     memset(&hst, 0, sizeof(hst));
     psd_rglobal hgl;
     memset(&hgl, 0, sizeof(hgl));
-    long long launched = 0;
     // every window advances the chase by >= 1 position; generous cap against a runaway loop
     const long long cap = (long long)maxitfac * n * ((long long)n / 8 + 4) + 4LL * n + 1024;  // (trains run windows down to 8 positions)
-    double sample_ms = 0.0;
-    int samples = 0;
+    // ticks alternate between two sets of descriptors / counts / lists (multi-block mode)
+    auto pset = [&](int par) { return parity_set(P, par, PSD_SLOTS, PSD_TR_CAP, p); };
+    auto tick = [&](long long launched, const tick_sample& sample) -> int {
 #ifndef PSD_HOSTSIM
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pend;
-    psd_poller poller(c, sample_ms, samples);
+        if ((zdef || cdef) && launched >= 2) PSD_CHECK(hipStreamWaitEvent(c->stream, c->evF[(int)(launched & 1)], 0));
 #endif
-    for (;;) {
-        for (int b = 0; b < batch; ++b) {
-#ifndef PSD_HOSTSIM
-            if ((zdef || cdef) && launched >= 2) PSD_CHECK(hipStreamWaitEvent(c->stream, c->evF[(int)(launched & 1)], 0));
-#endif
-            P.tick = (int)launched;
-            // ticks alternate between two sets of descriptors / counts / lists (multi-block mode)
-            const int par = mb ? (int)(launched & 1) : 0;
-            psd_rparams Pq = P, Pprev = P;
-            if (mb) {
-                Pq.desc = P.desc + (size_t)par * PSD_SLOTS;
-                Pq.cnt = P.cnt + (size_t)par * PSD_SLOTS * (p + 8);
-                Pq.tr = P.tr + (size_t)par * PSD_SLOTS * p * PSD_TR_CAP;
-                Pprev.desc = P.desc + (size_t)(par ^ 1) * PSD_SLOTS;
-                Pprev.cnt = P.cnt + (size_t)(par ^ 1) * PSD_SLOTS * (p + 8);
-                Pprev.tr = P.tr + (size_t)(par ^ 1) * PSD_SLOTS * p * PSD_TR_CAP;
-            }
-            // (multi-block: in front of the chase launch the product bands of the wide decisions pending, spread over the chip)
-            // and the slot plan of the tick (last row of the grid; problems narrower than the band threshold launch that row alone)
-            if (mb) {
-                const bool bands = Pq.bandinfo && n >= PSD_DECIDE_YIELD;
-                PSD_LAUNCH(psd_rq_band, psd_dim3(bands ? (n + 63) / 64 : 1, bands ? PSD_SLOTS + 1 : 1), 64,
-                           sizeof(int) * PSD_PLAN_LDS_INTS, c->stream, Pq, n, p);
-            }
-#ifndef PSD_HOSTSIM
-            const bool sample = c->profile && ((launched & 15) == 0);  // HIP events around the chase launch alone
-            if (sample) {
-                (void)hipEventCreate(&ev0);
-                (void)hipEventCreate(&ev1);
-                (void)hipEventRecord(ev0, c->stream);
-            }
-#endif
+        P.tick = (int)launched;
+        const int par = mb ? (int)(launched & 1) : 0;
+        const psd_rparams Pq = pset(par);
+        // (multi-block: in front of the chase launch the product bands of the wide decisions pending, spread over the chip)
+        // and the slot plan of the tick (last row of the grid; problems narrower than the band threshold launch that row alone)
+        if (mb) {
+            const bool bands = Pq.bandinfo && n >= PSD_DECIDE_YIELD;
+            PSD_LAUNCH(psd_rq_band, psd_dim3(bands ? (n + 63) / 64 : 1, bands ? PSD_SLOTS + 1 : 1), 64,
+                       sizeof(int) * PSD_PLAN_LDS_INTS, c->stream, Pq, n, p);
+        }
+        const int rc = sample.around([&] {
             if (M == 1 && !mb)
                 PSD_LAUNCH2(psd_rq_step, psd_dim3(1), PSD_STEP_NT, c2waves, lds_step, c->stream, P);
             else if (mb)  // every slot of the scheduler in one launch
                 PSD_LAUNCH2(psd_rq_step_mb, psd_dim3(PSD_SLOTS, slG), PSD_STEP_NT, c2waves, lds_step, c->stream, Pq, p, p + 8);
             else  // every cursor of the tick in one launch, one workgroup each
                 PSD_LAUNCH2(psd_rq_step_train, psd_dim3(M), PSD_STEP_NT, c2waves, lds_step, c->stream, P, p, p + 8);
+            return 0;
+        });
+        if (rc) return rc;
+        if (rdef) {
+            // Both far parts of the H updates on stream2 (psd_rdefer_edge, psd_cdefer_edge), in the order rows, columns:
+            // the far columns of this tick's rows roles start as soon as the chases are done (evC) and run beside the
+            // near parts on this stream, the far rows of the column roles follow when those near parts are done (evE);
+            // the NEXT tick's near parts wait for both (evG).  The Schur vectors go to a stream of their own (stream3)
+            // so that they do not hold up the far H updates the next tick waits for.  The serial simulation runs both
+            // far parts at the latest point the streams allow, behind the next tick's chases.
+            const int wl_grid = c->apply_wl_grid;
 #ifndef PSD_HOSTSIM
-            if (sample) {
-                (void)hipEventRecord(ev1, c->stream);
-                pend.emplace_back(ev0, ev1);
-            }
+            PSD_CHECK(hipEventRecord(c->evC[par], c->stream));
 #endif
-            if (rdef) {
-                // Both far parts of the H updates on stream2 (psd_rdefer_edge, psd_cdefer_edge), in the order rows, columns:
-                // the far columns of this tick's rows roles start as soon as the chases are done (evC) and run beside the
-                // near parts on this stream, the far rows of the column roles follow when those near parts are done (evE);
-                // the NEXT tick's near parts wait for both (evG).  The Schur vectors go to a stream of their own (stream3)
-                // so that they do not hold up the far H updates the next tick waits for.  The serial simulation runs both
-                // far parts at the latest point the streams allow, behind the next tick's chases.
-                const int wl_grid = c->apply_wl_grid;
+            if (far_pending) {
 #ifndef PSD_HOSTSIM
-                PSD_CHECK(hipEventRecord(c->evC[par], c->stream));
-#endif
-                if (far_pending) {
-#ifndef PSD_HOSTSIM
-                    PSD_CHECK(hipStreamWaitEvent(c->stream, c->evG[par ^ 1], 0));
+                PSD_CHECK(hipStreamWaitEvent(c->stream, c->evG[par ^ 1], 0));
 #else
-                    PSD_CHECK(launch_apply_wl(c, c->stream, Pprev, n, p, 0, NSL, zlo1, zhi1, 8, W, wl_grid));
-                    PSD_CHECK(launch_apply_wl(c, c->stream, Pprev, n, p, 1, NSL, zlo1, zhi1, 6, W, wl_grid));
+                PSD_CHECK(launch_apply_wl(c, c->stream, pset(par ^ 1), n, p, 0, NSL, zlo1, zhi1, 8, W, wl_grid));
+                PSD_CHECK(launch_apply_wl(c, c->stream, pset(par ^ 1), n, p, 1, NSL, zlo1, zhi1, 6, W, wl_grid));
 #endif
-                    far_pending = false;
-                }
-                PSD_CHECK(launch_apply_wl(c, c->stream, Pq, n, p, 0, NSL, zlo1, zhi1, 7, W, wl_grid));
-                if (wantZ && !zdef) PSD_CHECK(launch_apply_wl(c, c->stream, Pq, n, p, 0, NSL, zlo1, zhi1, 4, W, wl_grid));
-                PSD_CHECK(launch_apply_wl(c, c->stream, Pq, n, p, 1, NSL, zlo1, zhi1, 5, W, wl_grid));
+                far_pending = false;
+            }
+            PSD_CHECK(launch_apply_wl(c, c->stream, Pq, n, p, 0, NSL, zlo1, zhi1, 7, W, wl_grid));
+            if (wantZ && !zdef) PSD_CHECK(launch_apply_wl(c, c->stream, Pq, n, p, 0, NSL, zlo1, zhi1, 4, W, wl_grid));
+            PSD_CHECK(launch_apply_wl(c, c->stream, Pq, n, p, 1, NSL, zlo1, zhi1, 5, W, wl_grid));
 #ifndef PSD_HOSTSIM
-                PSD_CHECK(hipEventRecord(c->evE[par], c->stream));
-                const int fgrid = c->far_grid > 0 ? c->far_grid : wl_grid;
-                PSD_CHECK(hipStreamWaitEvent(c->stream2, c->evC[par], 0));
-                PSD_CHECK(launch_apply_wl(c, c->stream2, Pq, n, p, 0, NSL, zlo1, zhi1, 8, W, fgrid));
-                PSD_CHECK(hipStreamWaitEvent(c->stream2, c->evE[par], 0));
+            PSD_CHECK(hipEventRecord(c->evE[par], c->stream));
+            const int fgrid = c->far_grid > 0 ? c->far_grid : wl_grid;
+            PSD_CHECK(hipStreamWaitEvent(c->stream2, c->evC[par], 0));
+            PSD_CHECK(launch_apply_wl(c, c->stream2, Pq, n, p, 0, NSL, zlo1, zhi1, 8, W, fgrid));
+            PSD_CHECK(hipStreamWaitEvent(c->stream2, c->evE[par], 0));
+            PSD_CHECK(launch_apply_wl(c, c->stream2, Pq, n, p, 1, NSL, zlo1, zhi1, 6, W, fgrid));
+            PSD_CHECK(hipEventRecord(c->evG[par], c->stream2));
+            if (zdef) {
+                hipStream_t zs = (c->zstream == 2) ? c->stream2 : c->stream3;  // (PSD_ZSTREAM=2: behind the far H updates on stream2)
+                if (zs != c->stream2) PSD_CHECK(hipStreamWaitEvent(zs, c->evC[par], 0));
+                PSD_CHECK(launch_apply_wl(c, zs, Pq, n, p, 0, NSL, zlo1, zhi1, 4, W, fgrid));
+                PSD_CHECK(hipEventRecord(c->evF[par], zs));
+            } else {
+                PSD_CHECK(hipEventRecord(c->evF[par], c->stream2));
+            }
+#else
+            if (zdef) PSD_CHECK(launch_apply_wl(c, c->stream, Pq, n, p, 0, NSL, zlo1, zhi1, 4, W, wl_grid));
+#endif
+            far_pending = true;
+        } else if (zdef || cdef) {
+            // Schur-vector updates one stream over (psd_rq_apply_wl modes 3 / 4): the Z launch of this tick starts on
+            // stream2 when the tick's H updates are done (evE) — beside the NEXT tick's chases, which leave most of the
+            // chip idle — and its lists must not be rewritten before it is done (evF, awaited in front of the chase
+            // that reuses this parity's lists, two ticks on).  The serial simulation runs the Z launch last.
+            // The far rows of the column roles (modes 5 / 6, psd_cdefer_edge) go the same way, in front of the Z launch:
+            // the next tick's rows roles cross them, so that launch waits for them (evG); nothing else reads them
+            // earlier.  The serial simulation runs them at the latest point the streams allow — behind the next
+            // tick's chases — which shows that no chase, band or decision depends on them.
+            const int wl_grid = c->apply_wl_grid;
+            const int hmode = cdef ? 5 : 3;
+            if (cdef && far_pending) {
+#ifndef PSD_HOSTSIM
+                PSD_CHECK(hipStreamWaitEvent(c->stream, c->evG[par ^ 1], 0));
+#else
+                PSD_CHECK(launch_apply_wl(c, c->stream, pset(par ^ 1), n, p, 1, NSL, zlo1, zhi1, 6, W, wl_grid));
+#endif
+                far_pending = false;
+            }
+            if (!zdef && wantZ) {  // (the Schur vectors stay on this stream)
+                PSD_CHECK(launch_apply_wl(c, c->stream, Pq, n, p, 0, NSL, zlo1, zhi1, 0, W, wl_grid));
+            } else {
+                PSD_CHECK(launch_apply_wl(c, c->stream, Pq, n, p, 0, NSL, zlo1, zhi1, 3, W, wl_grid));
+            }
+            PSD_CHECK(launch_apply_wl(c, c->stream, Pq, n, p, 1, NSL, zlo1, zhi1, hmode, W, wl_grid));
+#ifndef PSD_HOSTSIM
+            PSD_CHECK(hipEventRecord(c->evE[par], c->stream));
+            PSD_CHECK(hipStreamWaitEvent(c->stream2, c->evE[par], 0));
+            const int fgrid = c->far_grid > 0 ? c->far_grid : wl_grid;
+            if (cdef) {
                 PSD_CHECK(launch_apply_wl(c, c->stream2, Pq, n, p, 1, NSL, zlo1, zhi1, 6, W, fgrid));
                 PSD_CHECK(hipEventRecord(c->evG[par], c->stream2));
-                if (zdef) {
-                    hipStream_t zs = (c->zstream == 2) ? c->stream2 : c->stream3;  // (PSD_ZSTREAM=2: behind the far H updates on stream2)
-                    if (zs != c->stream2) PSD_CHECK(hipStreamWaitEvent(zs, c->evC[par], 0));
-                    PSD_CHECK(launch_apply_wl(c, zs, Pq, n, p, 0, NSL, zlo1, zhi1, 4, W, fgrid));
-                    PSD_CHECK(hipEventRecord(c->evF[par], zs));
-                } else {
-                    PSD_CHECK(hipEventRecord(c->evF[par], c->stream2));
-                }
-#else
-                if (zdef) PSD_CHECK(launch_apply_wl(c, c->stream, Pq, n, p, 0, NSL, zlo1, zhi1, 4, W, wl_grid));
-#endif
                 far_pending = true;
-            } else if (zdef || cdef) {
-                // Schur-vector updates one stream over (psd_rq_apply_wl modes 3 / 4): the Z launch of this tick starts on
-                // stream2 when the tick's H updates are done (evE) — beside the NEXT tick's chases, which leave most of the
-                // chip idle — and its lists must not be rewritten before it is done (evF, awaited in front of the chase
-                // that reuses this parity's lists, two ticks on).  The serial simulation runs the Z launch last.
-                // The far rows of the column roles (modes 5 / 6, psd_cdefer_edge) go the same way, in front of the Z launch:
-                // the next tick's rows roles cross them, so that launch waits for them (evG); nothing else reads them
-                // earlier.  The serial simulation runs them at the latest point the streams allow — behind the next
-                // tick's chases — which shows that no chase, band or decision depends on them.
-                const int wl_grid = c->apply_wl_grid;
-                const int hmode = cdef ? 5 : 3;
-                if (cdef && far_pending) {
-#ifndef PSD_HOSTSIM
-                    PSD_CHECK(hipStreamWaitEvent(c->stream, c->evG[par ^ 1], 0));
+            }
+            if (zdef) PSD_CHECK(launch_apply_wl(c, c->stream2, Pq, n, p, 0, NSL, zlo1, zhi1, 4, W, fgrid));
+            PSD_CHECK(hipEventRecord(c->evF[par], c->stream2));
 #else
-                    PSD_CHECK(launch_apply_wl(c, c->stream, Pprev, n, p, 1, NSL, zlo1, zhi1, 6, W, wl_grid));
+            if (cdef) far_pending = true;
+            if (zdef) PSD_CHECK(launch_apply_wl(c, c->stream, Pq, n, p, 0, NSL, zlo1, zhi1, 4, W, wl_grid));
 #endif
-                    far_pending = false;
-                }
-                if (!zdef && wantZ) {  // (the Schur vectors stay on this stream)
-                    PSD_CHECK(launch_apply_wl(c, c->stream, Pq, n, p, 0, NSL, zlo1, zhi1, 0, W, wl_grid));
-                } else {
-                    PSD_CHECK(launch_apply_wl(c, c->stream, Pq, n, p, 0, NSL, zlo1, zhi1, 3, W, wl_grid));
-                }
-                PSD_CHECK(launch_apply_wl(c, c->stream, Pq, n, p, 1, NSL, zlo1, zhi1, hmode, W, wl_grid));
-#ifndef PSD_HOSTSIM
-                PSD_CHECK(hipEventRecord(c->evE[par], c->stream));
-                PSD_CHECK(hipStreamWaitEvent(c->stream2, c->evE[par], 0));
-                const int fgrid = c->far_grid > 0 ? c->far_grid : wl_grid;
-                if (cdef) {
-                    PSD_CHECK(launch_apply_wl(c, c->stream2, Pq, n, p, 1, NSL, zlo1, zhi1, 6, W, fgrid));
-                    PSD_CHECK(hipEventRecord(c->evG[par], c->stream2));
-                    far_pending = true;
-                }
-                if (zdef) PSD_CHECK(launch_apply_wl(c, c->stream2, Pq, n, p, 0, NSL, zlo1, zhi1, 4, W, fgrid));
-                PSD_CHECK(hipEventRecord(c->evF[par], c->stream2));
-#else
-                if (cdef) far_pending = true;
-                if (zdef) PSD_CHECK(launch_apply_wl(c, c->stream, Pq, n, p, 0, NSL, zlo1, zhi1, 4, W, wl_grid));
-#endif
-            } else if (c->apply_worklist || c->shard_world > 1 || mb) {
-                // work-list form: one grid of single-wave workgroups loops over the items of the tick
-                const int wl_grid = c->apply_wl_grid;
-                if (c->apply_wl2 == 1 && W <= 17 && wantZ) {
-                    // (rows role and Schur vectors as separate launches: each on the form that is faster for it)
-                    PSD_CHECK(launch_apply_wl(c, c->stream, Pq, n, p, 0, NSL, zlo1, zhi1, 3, W, wl_grid));
-                    PSD_CHECK(launch_apply_wl(c, c->stream, Pq, n, p, 0, NSL, zlo1, zhi1, 4, W, wl_grid));
-                } else {
-                    PSD_CHECK(launch_apply_wl(c, c->stream, Pq, n, p, 0, NSL, zlo1, zhi1, 0, W, wl_grid));
-                }
-                PSD_CHECK(launch_apply_wl(c, c->stream, Pq, n, p, 1, NSL, zlo1, zhi1, 0, W, wl_grid));
-            } else if (M == 1) {
-                PSD_LAUNCH(psd_rq_apply, psd_dim3(tiles, p, 3), PSD_APPLY_NT, lds_apply, c->stream, P, n, p);
+        } else if (c->apply_worklist || c->shard_world > 1 || mb) {
+            // work-list form: one grid of single-wave workgroups loops over the items of the tick
+            const int wl_grid = c->apply_wl_grid;
+            if (c->apply_wl2 == 1 && W <= 17 && wantZ) {
+                // (rows role and Schur vectors as separate launches: each on the form that is faster for it)
+                PSD_CHECK(launch_apply_wl(c, c->stream, Pq, n, p, 0, NSL, zlo1, zhi1, 3, W, wl_grid));
+                PSD_CHECK(launch_apply_wl(c, c->stream, Pq, n, p, 0, NSL, zlo1, zhi1, 4, W, wl_grid));
             } else {
-                PSD_LAUNCH(psd_rq_apply_train, psd_dim3(tiles, p, 2 * M), PSD_APPLY_NT, lds_apply, c->stream, P, n, p, p + 8, 0);
-                PSD_LAUNCH(psd_rq_apply_train, psd_dim3(tiles, p, M), PSD_APPLY_NT, lds_apply, c->stream, P, n, p, p + 8, 1);
+                PSD_CHECK(launch_apply_wl(c, c->stream, Pq, n, p, 0, NSL, zlo1, zhi1, 0, W, wl_grid));
             }
-            ++launched;
+            PSD_CHECK(launch_apply_wl(c, c->stream, Pq, n, p, 1, NSL, zlo1, zhi1, 0, W, wl_grid));
+        } else if (M == 1) {
+            PSD_LAUNCH(psd_rq_apply, psd_dim3(tiles, p, 3), PSD_APPLY_NT, lds_apply, c->stream, P, n, p);
+        } else {
+            PSD_LAUNCH(psd_rq_apply_train, psd_dim3(tiles, p, 2 * M), PSD_APPLY_NT, lds_apply, c->stream, P, n, p, p + 8, 0);
+            PSD_LAUNCH(psd_rq_apply_train, psd_dim3(tiles, p, M), PSD_APPLY_NT, lds_apply, c->stream, P, n, p, p + 8, 1);
         }
-        if (mb) {
+        return 0;
+    };
+    tick_totals T;
+    const int rc = mb ? tick_loop(c, c->tgl, hgl, cap, 0xfffe, true, tick, [](const psd_rglobal& g) { return g.done != 0; }, T)
+                      : tick_loop(c, c->st, hst, cap, 0xfffe, true, tick, [](const psd_rstate& g) { return g.phase == PSD_PH_DONE; }, T);
 #ifdef PSD_HOSTSIM
-            PSD_CHECK(psd_rt_d2h(&hgl, c->tgl, sizeof(hgl), c->stream));
-            PSD_CHECK(psd_rt_sync(c->stream));
-#else
-            PSD_CHECK(poller.poll(&hgl, c->tgl, sizeof(hgl), pend));
-#endif
-            if (hgl.done) {
-                hst.phase = PSD_PH_DONE;
-                hst.info = hgl.info;
-                hst.niter = hgl.niter;
-                hst.maxits = hgl.maxits;
-                hst.nsweeps = hgl.nsweeps;
-                hst.nrqpass = hgl.nrqpass;
-                hst.ndefl1 = hgl.ndefl1;
-                hst.ndefl2 = hgl.ndefl2;
-                hst.nwindows = hgl.nwindows;
-                hst.nlog = hgl.nlog;
-                hst.ntrains = hgl.ntrains;
-                hst.ntrainsweeps = hgl.ntrainsweeps;
-                for (int q = 0; q < 6; ++q) hst.cyc[q] = hgl.cyc[q];
-                if (pinfo_out)  // (a call-wide abort — a list overflow — leaves the problems still active unfinished: say so)
-                    for (int q = 0; q < nprob; ++q)
-                        pinfo_out[q] = (hgl.abort && hgl.pinfo[q] == 0 && hgl.pactive[q] > 0) ? hgl.info : hgl.pinfo[q];
-                break;
-            }
-            if (launched > cap) {
-#ifdef PSD_HOSTSIM
-                fprintf(stderr, "mb runaway: launched %lld nactive %d nspawn %d nslotmax %d nsweeps %d\n", launched, hgl.nactive,
-                        hgl.nspawn, hgl.nslotmax, hgl.nsweeps);
-                for (int q = 0; q < PSD_SLOTS; ++q) {
-                    const psd_rstate& x = c->tcst[q];
-                    if (c->tslotw[q] != PSD_ROLE_FREE)
-                        fprintf(stderr, " slot %d role %d epoch %d phase %d cursor %d parent %d lo %d l %d i %d its %d train_n %d key %d kcur %d tick0 %d\n",
-                                q, c->tslotw[q], c->tslotw[PSD_SLOTS + q], x.phase, x.cursor, x.parent, x.lo, x.l, x.i, x.its,
-                                x.train_n, x.train_key, x.kcur, x.train_tick0);
-                    if (c->tslotw[q] == PSD_ROLE_LEADER && x.phase == PSD_PH_TWAIT)
-                        for (int b = 1; b < x.train_n; ++b)
-                            fprintf(stderr, "   cursor %d slot %d cdone %d (slot state: cursor %d parent %d key %d phase %d kcur %d i %d l %d tick0 %d)\n", b, x.cslots[b],
-                                    c->tslotw[2 * PSD_SLOTS + x.cslots[b]], c->tcst[x.cslots[b]].cursor, c->tcst[x.cslots[b]].parent,
-                                    c->tcst[x.cslots[b]].train_key, c->tcst[x.cslots[b]].phase, c->tcst[x.cslots[b]].kcur,
-                                    c->tcst[x.cslots[b]].i, c->tcst[x.cslots[b]].l, c->tcst[x.cslots[b]].train_tick0);
-                }
-#endif
-                *st_out = hst;
-                return PSD_INFO_RUNTIME + 0xfffe;
-            }
-            continue;
+    if (mb && rc == PSD_INFO_RUNTIME + 0xfffe) {
+        fprintf(stderr, "mb runaway: launched %lld nactive %d nspawn %d nslotmax %d nsweeps %d\n", T.launched, hgl.nactive,
+                hgl.nspawn, hgl.nslotmax, hgl.nsweeps);
+        for (int q = 0; q < PSD_SLOTS; ++q) {
+            const psd_rstate& x = c->tcst[q];
+            if (c->tslotw[q] != PSD_ROLE_FREE)
+                fprintf(stderr, " slot %d role %d epoch %d phase %d cursor %d parent %d lo %d l %d i %d its %d train_n %d key %d kcur %d tick0 %d\n",
+                        q, c->tslotw[q], c->tslotw[PSD_SLOTS + q], x.phase, x.cursor, x.parent, x.lo, x.l, x.i, x.its,
+                        x.train_n, x.train_key, x.kcur, x.train_tick0);
+            if (c->tslotw[q] == PSD_ROLE_LEADER && x.phase == PSD_PH_TWAIT)
+                for (int b = 1; b < x.train_n; ++b)
+                    fprintf(stderr, "   cursor %d slot %d cdone %d (slot state: cursor %d parent %d key %d phase %d kcur %d i %d l %d tick0 %d)\n", b, x.cslots[b],
+                            c->tslotw[2 * PSD_SLOTS + x.cslots[b]], c->tcst[x.cslots[b]].cursor, c->tcst[x.cslots[b]].parent,
+                            c->tcst[x.cslots[b]].train_key, c->tcst[x.cslots[b]].phase, c->tcst[x.cslots[b]].kcur,
+                            c->tcst[x.cslots[b]].i, c->tcst[x.cslots[b]].l, c->tcst[x.cslots[b]].train_tick0);
         }
-#ifdef PSD_HOSTSIM
-        PSD_CHECK(psd_rt_d2h(&hst, c->st, sizeof(hst), c->stream));
-        PSD_CHECK(psd_rt_sync(c->stream));
-#else
-        PSD_CHECK(poller.poll(&hst, c->st, sizeof(hst), pend));
+    }
 #endif
-        if (hst.phase == PSD_PH_DONE) break;
-        if (launched > cap) {
-            *st_out = hst;
-            return PSD_INFO_RUNTIME + 0xfffe;
-        }
+    if (rc) {
+        *st_out = hst;
+        return rc;
+    }
+    if (mb) {
+        hst.phase = PSD_PH_DONE;
+        hst.info = hgl.info;
+        hst.niter = hgl.niter;
+        hst.maxits = hgl.maxits;
+        hst.nsweeps = hgl.nsweeps;
+        hst.nrqpass = hgl.nrqpass;
+        hst.ndefl1 = hgl.ndefl1;
+        hst.ndefl2 = hgl.ndefl2;
+        hst.nwindows = hgl.nwindows;
+        hst.nlog = hgl.nlog;
+        hst.ntrains = hgl.ntrains;
+        hst.ntrainsweeps = hgl.ntrainsweeps;
+        for (int q = 0; q < 6; ++q) hst.cyc[q] = hgl.cyc[q];
+        if (pinfo_out)  // (a call-wide abort — a list overflow — leaves the problems still active unfinished: say so)
+            for (int q = 0; q < nprob; ++q)
+                pinfo_out[q] = (hgl.abort && hgl.pinfo[q] == 0 && hgl.pactive[q] > 0) ? hgl.info : hgl.pinfo[q];
     }
 #ifndef PSD_HOSTSIM
     if (zdef || cdef) PSD_CHECK(hipStreamSynchronize(c->stream2));
     if (rdef && zdef) PSD_CHECK(hipStreamSynchronize(c->stream3));
 #else
     if (cdef && far_pending) {  // (the last tick's far column roles: its parity is the one the last launch used)
-        psd_rparams Pl = P;
-        const int parl = (int)((launched - 1) & 1);
-        Pl.desc = P.desc + (size_t)parl * PSD_SLOTS;
-        Pl.cnt = P.cnt + (size_t)parl * PSD_SLOTS * (p + 8);
-        Pl.tr = P.tr + (size_t)parl * PSD_SLOTS * p * PSD_TR_CAP;
+        const psd_rparams Pl = pset((int)((T.launched - 1) & 1));
         if (rdef) PSD_CHECK(launch_apply_wl(c, c->stream, Pl, n, p, 0, NSL, zlo1, zhi1, 8, W, c->apply_wl_grid));
         PSD_CHECK(launch_apply_wl(c, c->stream, Pl, n, p, 1, NSL, zlo1, zhi1, 6, W, c->apply_wl_grid));
         far_pending = false;
     }
-#endif
-#ifndef PSD_HOSTSIM
-    PSD_CHECK(poller.finish(pend));
 #endif
     PSD_CHECK(psd_rt_last_error());
 #ifndef PSD_HOSTSIM
@@ -1633,17 +1650,12 @@ int iterate_dev(psd_ctx* c, int n, int p, double* dH, double* dZ, int wantT, int
             fprintf(stderr, "\n");
         }
         if (FILE* fh = fopen(ticklog_path, "w")) {
-            for (long long t = 0; t < launched && t < ticklog_cap; ++t) fprintf(fh, "%lld %d %d\n", t, tl[(size_t)t] >> 12, tl[(size_t)t] & 0xfff);
+            for (long long t = 0; t < T.launched && t < ticklog_cap; ++t) fprintf(fh, "%lld %d %d\n", t, tl[(size_t)t] >> 12, tl[(size_t)t] & 0xfff);
             fclose(fh);
         }
     }
     *st_out = hst;
-    if (stats) {
-        stats->nlaunch_step = (int32_t)launched;
-        stats->window = W;
-        stats->step_kernel_ms_avg = samples ? sample_ms / samples : 0.0;
-        stats->step_kernel_samples = samples;
-    }
+    stats_from_ticks(stats, T, W);
     return 0;
 }
 
@@ -2414,129 +2426,89 @@ int ziterate_dev(psd_ctx* c, int n, int p, psd_z* dH, psd_z* dZ, int wantT, int 
         return 0;
     };
     const int dtiles = (n + 255) / 256;
-    const int batch = 32;
     psd_zstate hst;
     memset(&hst, 0, sizeof(hst));
-    long long launched = 0;
     const int nbmin = (W - 3 > 0) ? ((W - 3 < 8) ? (W - 3) : 8) : 1;  // (trains run windows down to 8 positions)
     const long long cap = (long long)maxitfac * n * ((long long)n / nbmin + 4) + 4LL * n + 1024;
-    double sample_ms = 0.0;
-    int samples = 0;
+    // (zdef: ticks alternate between two sets of descriptors / counts / lists)
+    auto pset = [&](int par) { return parity_set(P, par, PSD_TRAIN_MAX, PSD_ZTR_CAP, p); };
+    auto tick = [&](long long launched, const tick_sample& sample) -> int {
+        P.tick = (int)launched;
+        const int par = zdef ? (int)(launched & 1) : 0;
+        const psd_zparams Pq = pset(par);
+        const int rc = sample.around([&]() -> int {  // (the sample starts in front of the wait for evF, not of the launch alone)
 #ifndef PSD_HOSTSIM
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pend;
-    psd_poller poller(c, sample_ms, samples);
+            if (zdef && launched >= 2) PSD_CHECK(hipStreamWaitEvent(c->stream, c->evF[par], 0));  // (the Z launch that read this parity's lists)
 #endif
-    for (;;) {
-        for (int b = 0; b < batch; ++b) {
-#ifndef PSD_HOSTSIM
-            const bool sample = c->profile && ((launched & 15) == 0);
-            if (sample) {
-                (void)hipEventCreate(&ev0);
-                (void)hipEventCreate(&ev1);
-                (void)hipEventRecord(ev0, c->stream);
-            }
-#endif
-            P.tick = (int)launched;
-            const int par = zdef ? (int)(launched & 1) : 0;
-            psd_zparams Pq = P, Pprev = P;
-            if (zdef) {
-#ifndef PSD_HOSTSIM
-                if (launched >= 2) PSD_CHECK(hipStreamWaitEvent(c->stream, c->evF[par], 0));  // (the Z launch that read this parity's lists)
-#endif
-                Pq.desc = P.desc + (size_t)par * PSD_TRAIN_MAX;
-                Pq.cnt = P.cnt + (size_t)par * PSD_TRAIN_MAX * (p + 8);
-                Pq.tr = P.tr + (size_t)par * PSD_TRAIN_MAX * p * PSD_ZTR_CAP;
-                Pprev.desc = P.desc + (size_t)(par ^ 1) * PSD_TRAIN_MAX;
-                Pprev.cnt = P.cnt + (size_t)(par ^ 1) * PSD_TRAIN_MAX * (p + 8);
-                Pprev.tr = P.tr + (size_t)(par ^ 1) * PSD_TRAIN_MAX * p * PSD_ZTR_CAP;
-            }
-            (void)Pprev;
             if (M == 1)
                 PSD_LAUNCH2(psd_zq_step, psd_dim3(1), PSD_STEP_NT, zwaves, lds_step, c->stream, P);
             else
                 PSD_LAUNCH2(psd_zq_step_train, psd_dim3(M, zslG), PSD_STEP_NT, zwaves, lds_step, c->stream, Pq, p, p + 8);
+            return 0;
+        });
+        if (rc) return rc;
+        if (M == 1) {
+            PSD_LAUNCH(psd_zq_apply, psd_dim3(tiles, p, 3), PSD_ZAPPLY_NT, lds_apply, c->stream, P, n, p);
+        } else if (zdef) {
+            // Schur-vector updates one stream over (as iterate_dev: nothing reads Z_m before the iteration ends and only
+            // owner m's lists touch it): they start when the tick's H updates are done and run beside the next tick's
+            // chases; the lists of a tick are double-buffered by parity, the chase that reuses a parity awaits evF.
+            // With zcdef the far rows of the sweep windows' column roles (psd_zapply_desc::rcut) go the same way, in
+            // front of the Z launch: the next tick's rows roles cross them, so those wait for them (evG); the last
+            // window of a sweep keeps its column role whole, so that the check in the next launch finds nothing under
+            // way.  The serial simulation runs them at the latest point the streams
+            // allow, behind the next tick's chases.
+            if (zcdef && far_pending) {
 #ifndef PSD_HOSTSIM
-            if (sample) {
-                (void)hipEventRecord(ev1, c->stream);
-                pend.emplace_back(ev0, ev1);
+                PSD_CHECK(hipStreamWaitEvent(c->stream, c->evG[par ^ 1], 0));
+#else
+                PSD_CHECK(zapply(c->stream, pset(par ^ 1), 5));
+#endif
+                far_pending = false;
             }
-#endif
-            if (M == 1) {
-                PSD_LAUNCH(psd_zq_apply, psd_dim3(tiles, p, 3), PSD_ZAPPLY_NT, lds_apply, c->stream, P, n, p);
-            } else if (zdef) {
-                // Schur-vector updates one stream over (as iterate_dev: nothing reads Z_m before the iteration ends and only
-                // owner m's lists touch it): they start when the tick's H updates are done and run beside the next tick's
-                // chases; the lists of a tick are double-buffered by parity, the chase that reuses a parity awaits evF.
-                // With zcdef the far rows of the sweep windows' column roles (psd_zapply_desc::rcut) go the same way, in
-                // front of the Z launch: the next tick's rows roles cross them, so those wait for them (evG); the last
-                // window of a sweep keeps its column role whole, so that the check in the next launch finds nothing under
-                // way.  The serial simulation runs them at the latest point the streams
-                // allow, behind the next tick's chases.
-                if (zcdef && far_pending) {
+            PSD_CHECK(zapply(c->stream, Pq, 2));
+            PSD_CHECK(zapply(c->stream, Pq, zcdef ? 4 : 1));
 #ifndef PSD_HOSTSIM
-                    PSD_CHECK(hipStreamWaitEvent(c->stream, c->evG[par ^ 1], 0));
-#else
-                    PSD_CHECK(zapply(c->stream, Pprev, 5));
-#endif
-                    far_pending = false;
-                }
-                PSD_CHECK(zapply(c->stream, Pq, 2));
-                PSD_CHECK(zapply(c->stream, Pq, zcdef ? 4 : 1));
-#ifndef PSD_HOSTSIM
-                PSD_CHECK(hipEventRecord(c->evE[par], c->stream));
-                PSD_CHECK(hipStreamWaitEvent(c->stream2, c->evE[par], 0));
-                if (zcdef) {
-                    PSD_CHECK(zapply(c->stream2, Pq, 5));
-                    PSD_CHECK(hipEventRecord(c->evG[par], c->stream2));
-                    far_pending = true;
-                }
-                PSD_CHECK(zapply(c->stream2, Pq, 3));
-                PSD_CHECK(hipEventRecord(c->evF[par], c->stream2));
-#else
-                if (zcdef) far_pending = true;
-                PSD_CHECK(zapply(c->stream, Pq, 3));
-#endif
-            } else if (c->apply_worklist) {
-                PSD_CHECK(zapply(c->stream, P, 2));
-                if (wantZ) PSD_CHECK(zapply(c->stream, P, 3));
-                PSD_CHECK(zapply(c->stream, P, 1));
-            } else {
-                PSD_LAUNCH(psd_zq_apply_train, psd_dim3(tiles, p, 2 * M), PSD_ZAPPLY_NT, lds_apply, c->stream, P, n, p, p + 8, 0);
-                PSD_LAUNCH(psd_zq_apply_train, psd_dim3(tiles, p, M), PSD_ZAPPLY_NT, lds_apply, c->stream, P, n, p, p + 8, 1);
+            PSD_CHECK(hipEventRecord(c->evE[par], c->stream));
+            PSD_CHECK(hipStreamWaitEvent(c->stream2, c->evE[par], 0));
+            if (zcdef) {
+                PSD_CHECK(zapply(c->stream2, Pq, 5));
+                PSD_CHECK(hipEventRecord(c->evG[par], c->stream2));
+                far_pending = true;
             }
-            PSD_LAUNCH(psd_zq_defer, psd_dim3(dtiles), 256, 0, c->stream, Pq, n);
-            ++launched;
-        }
-#ifdef PSD_HOSTSIM
-        PSD_CHECK(psd_rt_d2h(&hst, c->zst, sizeof(hst), c->stream));
-        PSD_CHECK(psd_rt_sync(c->stream));
+            PSD_CHECK(zapply(c->stream2, Pq, 3));
+            PSD_CHECK(hipEventRecord(c->evF[par], c->stream2));
 #else
-        PSD_CHECK(poller.poll(&hst, c->zst, sizeof(hst), pend));
+            if (zcdef) far_pending = true;
+            PSD_CHECK(zapply(c->stream, Pq, 3));
 #endif
-        if (hst.phase == PSD_ZPH_DONE) break;
-        if (launched > cap) {
-#ifndef PSD_HOSTSIM
-            if (zdef) (void)hipStreamSynchronize(c->stream2);
-#endif
-            *st_out = hst;
-            return PSD_INFO_RUNTIME + 0xfffe;
+        } else if (c->apply_worklist) {
+            PSD_CHECK(zapply(c->stream, P, 2));
+            if (wantZ) PSD_CHECK(zapply(c->stream, P, 3));
+            PSD_CHECK(zapply(c->stream, P, 1));
+        } else {
+            PSD_LAUNCH(psd_zq_apply_train, psd_dim3(tiles, p, 2 * M), PSD_ZAPPLY_NT, lds_apply, c->stream, P, n, p, p + 8, 0);
+            PSD_LAUNCH(psd_zq_apply_train, psd_dim3(tiles, p, M), PSD_ZAPPLY_NT, lds_apply, c->stream, P, n, p, p + 8, 1);
         }
+        PSD_LAUNCH(psd_zq_defer, psd_dim3(dtiles), 256, 0, c->stream, Pq, n);
+        return 0;
+    };
+    tick_totals T;
+    if (int rc = tick_loop(c, c->zst, hst, cap, 0xfffe, true, tick, [](const psd_zstate& g) { return g.phase == PSD_ZPH_DONE; }, T)) {
+#ifndef PSD_HOSTSIM
+        if (zdef) (void)hipStreamSynchronize(c->stream2);  // (its Z launches read this call's lists and write the caller's arrays)
+#endif
+        *st_out = hst;
+        return rc;
     }
 #ifdef PSD_HOSTSIM
     if (zcdef && far_pending) {  // (the last tick's far column roles: its parity is the one the last launch used)
-        psd_zparams Pl = P;
-        const int parl = (int)((launched - 1) & 1);
-        Pl.desc = P.desc + (size_t)parl * PSD_TRAIN_MAX;
-        Pl.cnt = P.cnt + (size_t)parl * PSD_TRAIN_MAX * (p + 8);
-        Pl.tr = P.tr + (size_t)parl * PSD_TRAIN_MAX * p * PSD_ZTR_CAP;
-        PSD_CHECK(zapply(c->stream, Pl, 5));
+        PSD_CHECK(zapply(c->stream, pset((int)((T.launched - 1) & 1)), 5));
         far_pending = false;
     }
 #endif
 #ifndef PSD_HOSTSIM
     if (zdef) PSD_CHECK(hipStreamSynchronize(c->stream2));  // (the phase pass below scales columns of Z)
-    PSD_CHECK(poller.finish(pend));
     if (zslG > 1) {  // (a sliced window whose hand-over never arrived: the results are void, say so)
         int serr = 0;
         PSD_CHECK(psd_rt_d2h(&serr, P.zslerr, sizeof(int), c->stream));
@@ -2553,12 +2525,7 @@ int ziterate_dev(psd_ctx* c, int n, int p, psd_z* dH, psd_z* dZ, int wantT, int 
     }
     PSD_CHECK(psd_rt_last_error());
     *st_out = hst;
-    if (stats) {
-        stats->nlaunch_step = (int32_t)launched;
-        stats->window = W;
-        stats->step_kernel_ms_avg = samples ? sample_ms / samples : 0.0;
-        stats->step_kernel_samples = samples;
-    }
+    stats_from_ticks(stats, T, W);
     return 0;
 }
 
@@ -2587,133 +2554,189 @@ int zrun_iteration(psd_ctx* c, int n, int p, psd_z* dH, psd_z* dZ, int wantT, in
 
 }  // namespace
 
+// =================================================================================================
+// signed (generalized) periodic QZ, real — rgeneralized.jl — and complex — generalized.jl
 namespace {
 
-int zgiterate_dev(psd_ctx* c, int n, int p, psd_z* dH, psd_z* dZ, const uint8_t* S, int wantT, int wantZ, int maxitfac,
-                  psd_zgstate* st_out, psd_stats* stats, int maxlog, int hessmode) {
-    const int W = choose_window(p, 16);
-    if (W == 0) return PSD_INFO_NOTIMPL;
-    std::vector<unsigned char> hS(p, 1);
-    for (int l = 0; l < p; ++l) hS[l] = (!S || S[l]) ? 1 : 0;
-    PSD_CHECK(psd_rt_h2d(c->zgS, hS.data(), (size_t)p, c->stream));
-    PSD_CHECK(psd_rt_sync(c->stream));
-    psd_zgparams P;
-    P.H = dH;
-    {
-        int zl = 0, zh = p;
-        c->slice(p, zl, zh);
-        P.zlo = zl + 1;
-        P.zhi = zh;
+// What the two signed engines differ in: the element, the device types, the workspaces of the context, the kernels,
+// and the constants of their drivers.
+struct signed_real {
+    typedef double T;
+    typedef psd_gstate State;
+    typedef psd_gparams Params;
+    static constexpr int ESIZE = 8, NBMIN_OFF = 5, TRAIN_CAP = PSD_TRAIN_MAX, RUNAWAY = 0xfffd, APPLY_NT = PSD_GAPPLY_NT;
+    static constexpr bool DIAG = true;        // HIP-event samples of the chase launch, the PSD_GDBG print
+    static constexpr bool PHASE = false;      // a phase pass behind the iteration
+    static constexpr double ROT0 = 2.0;       // bytes_sweeps: a sweep applies two rotations per (j, l)
+    static size_t lds_apply() { return PSD_GTR_LDS_BYTES + (size_t)32 * (PSD_GAPPLY_NT + 1) * sizeof(double); }
+    static size_t hess_lds_bytes(int p, int W) { return psd_ghess_lds_bytes(p, W); }
+    // workspaces: of the host entries (the engine's own come with reserve_engine), of the engine, of its trains
+    static int reserve(psd_ctx* c, int n, int p, int) { return c->reserve(n, p, true, 16); }
+    static int reserve_engine(psd_ctx* c, int n, int p, int maxlog) { return c->greserve(n, p, maxlog); }
+    static T* H(psd_ctx* c) { return c->dH; }
+    static T* Z(psd_ctx* c) { return c->dZ; }
+    static T* vbuf(psd_ctx* c) { return c->vbuf; }
+    static unsigned char* S(psd_ctx* c) { return c->gS; }
+    static void workspace(psd_ctx* c, Params& P) {
+        P.S = S(c);
+        P.st = c->gst;
+        P.desc = c->gdesc;
+        P.tr = c->gtr;
+        P.cnt = c->gcnt;
+        P.dG = c->gdG;
+        P.alpha = c->galpha;
+        P.beta = c->gbeta;
+        P.ascale = c->gascale;
+        P.log = c->glog;
+        P.xscr = c->gxscr;
     }
-    P.Z = wantZ ? dZ : nullptr;
-    P.S = c->zgS;
-    P.st = c->zgst;
-    P.desc = c->zgdesc;
-    P.tr = c->zgtr;
-    P.cnt = c->zgcnt;
-    P.dG = c->zgdG;
-    P.alpha = c->zalpha;
-    P.beta = c->zbeta;
-    P.ascale = c->zascale;
-    P.log = c->zlog;
-    const size_t lds_step = step_lds_bytes(p, W, 16);
-    PSD_CHECK(c->lds_limit(reinterpret_cast<const void*>(psd_zgq_step), lds_step));
-    // stage 2 of the signed Hessenberg reduction: pipeline over the factors (see giterate_dev)
-    const size_t lds_hess = psd_zghess_lds_bytes(p, W);
-    const int hess_links = psd_ghess_links(p), hess_waves = psd_ghess_waves(p);
-    const char* hserial = psd_env("PSD_HESS_SERIAL");
-    const bool hess_pipe = hessmode && lds_hess <= (size_t)160 * 1024 && !(hserial && hserial[0] == '1');
-    // (scan form of the stage-2 kernel, the default; PSD_HESS_SCAN=0: the pipeline of beats over the factors of round 2)
-    int hess_scan = 1;
-    if (const char* e = psd_env("PSD_HESS_SCAN")) hess_scan = atoi(e);
-    (void)hess_scan;
-    if (hess_pipe) PSD_CHECK(c->lds_limit(reinterpret_cast<const void*>(psd_zgq_hess_step), lds_hess));
-    // multishift trains (as giterate_dev)
-    const int tw = hessmode ? 0 : c->gtrain_m;
-    const int Mcap = (PSD_ZHQR_MAX < PSD_TRAIN_MAX) ? PSD_ZHQR_MAX : PSD_TRAIN_MAX;
-    const int M = (tw >= 2) ? ((tw > Mcap) ? Mcap : tw) : 1;
-    P.cst = nullptr;
-    P.cep = nullptr;
-    P.tshift = nullptr;
-    P.tick = 0;
-    if (M > 1 || tw == -2) {
-        PSD_CHECK(c->zgtreserve(p));
-        PSD_CHECK(psd_rt_memset(c->zgtcst, 0, sizeof(psd_zgstate) * PSD_TRAIN_MAX + sizeof(int) * (PSD_TRAIN_MAX + 8), c->stream));
-        PSD_CHECK(psd_rt_memset(c->zgtdesc, 0, sizeof(psd_gapply_desc) * PSD_TRAIN_MAX, c->stream));
+    static int train_workspace(psd_ctx* c, int p, Params& P, bool lists) {
+        if (int e = c->gtreserve(p)) return e;
+        P.cst = c->gtcst;
+        P.cep = (int*)(c->gtcst + PSD_TRAIN_MAX);
+        P.tshift = c->gtshift;
+        if (lists) {
+            P.desc = c->gtdesc;
+            P.cnt = c->gtcnt;
+            P.tr = c->gttr;
+        }
+        return 0;
+    }
+    static psd_gapply_desc* tdesc(psd_ctx* c) { return c->gtdesc; }
+    static const int* log(psd_ctx* c) { return c->glog; }
+    // scan form of the sweep windows (psd_gs3_run; PSD_GSCAN=0: the single-wave sweep): rotation tables and the helper
+    // wavefronts' command block behind everything the state machine uses.  Returns the wavefronts of a chase workgroup.
+    static int scan_sweep(Params& P, int p, int hessmode, size_t& lds_step) {
+        P.gcoff = P.gtaboff = 0;
+        int gscan = 1;
+        if (const char* e = psd_env("PSD_GSCAN")) gscan = atoi(e);
+        const size_t need = lds_step + (size_t)p * 8 * sizeof(double) + 128;
+        if (!gscan || hessmode || p < 2 || p > 64 || need > (size_t)160 * 1024) return 1;
+        P.gtaboff = (int)lds_step;
+        P.gcoff = (int)(lds_step + (size_t)p * 8 * sizeof(double));
+        lds_step = need;
+        return 4;
+    }
+    // the kernels; the stage-2 kernel of the signed Hessenberg reduction has two forms with their own arguments
+    static constexpr auto k_init = psd_gq_init;
+    static constexpr auto k_step = psd_gq_step;
+    static constexpr auto k_step_train = psd_gq_step_train;
+    static constexpr auto k_apply = psd_gq_apply;
+    static constexpr auto k_apply_train = psd_gq_apply_train;
+    static constexpr auto k_defer = psd_gq_defer;
+    static constexpr auto k_set_identity = psd_set_identity;
+    static constexpr auto k_antitranspose = psd_antitranspose;
+    static constexpr auto k_flip = psd_flip;
+    static constexpr auto k_tril_zero = psd_tril_zero;
+    static constexpr auto k_hess_refl = psd_hess_refl;
+    static constexpr auto k_hess_apply2 = psd_hess_apply2;
+    // (which form runs: the scan form, the default for p <= 64; PSD_HESS_SCAN=0: the pipeline of beats over the factors of round 2)
+    static int hess_prepare(psd_ctx* c, int p, size_t b, int& form) {  // (the runtime's code)
+        const char* e = psd_env("PSD_HESS_SCAN");
+        form = (!e || atoi(e)) && p <= 64;
+        if (int rc = c->lds_limit(reinterpret_cast<const void*>(psd_gq_hess_step), b)) return rc;
+        return c->lds_limit(reinterpret_cast<const void*>(psd_gq_hess_step_scan), b);
+    }
+    static void hess_step(psd_ctx* c, const Params& P, int form, int links, int waves, size_t lds) {
+        if (form)
+            PSD_LAUNCH(psd_gq_hess_step_scan, psd_dim3(1), 256, lds, c->stream, P, links);  // (scan form: four wavefronts, one per SIMD)
+        else
+            PSD_LAUNCH(psd_gq_hess_step, psd_dim3(1), 64 * waves, lds, c->stream, P, links, 0);
+    }
+    // rgeneralized.jl:21-34: an all-true signature takes the Householder phessenberg! and an explicit Q
+    static int householder(psd_ctx* c, int n, int p, int wantZ, psd_stats* s) {
+        Timer t;
+        t.start(c->stream);
+        if (int e = hessenberg_dev(c, n, p, c->dH, c->tau)) return e;
+        s->ms_hess = t.stop(c->stream);
+        if (wantZ) {
+            t.start(c->stream);
+            if (int e = formq_dev(c, n, p, c->dH, c->tau, c->dZ)) return e;
+            s->ms_formq = t.stop(c->stream);
+        }
+        PSD_LAUNCH(psd_triu, psd_dim3(n, p), 64, 0, c->stream, c->dH, n);
+        return 0;
+    }
+};
+// (shares zalpha / zbeta / zascale / zlog / zvbuf with the unsigned complex engine: zreserve)
+struct signed_cplx {
+    typedef psd_z T;
+    typedef psd_zgstate State;
+    typedef psd_zgparams Params;
+    static constexpr int ESIZE = 16, NBMIN_OFF = 3, TRAIN_CAP = (PSD_ZHQR_MAX < PSD_TRAIN_MAX) ? PSD_ZHQR_MAX : PSD_TRAIN_MAX,
+                         RUNAWAY = 0xfffc, APPLY_NT = PSD_ZAPPLY_NT;
+    static constexpr bool DIAG = false, PHASE = true;
+    static constexpr double ROT0 = 1.0;
+    static size_t lds_apply() { return sizeof(psd_ztr) * PSD_GTR_CAP + (size_t)32 * (PSD_ZAPPLY_NT + 1) * sizeof(psd_z); }
+    static size_t hess_lds_bytes(int p, int W) { return psd_zghess_lds_bytes(p, W); }
+    static int reserve(psd_ctx* c, int n, int p, int maxlog) {
+        if (int e = c->zreserve(n, p, true, maxlog)) return e;
+        return c->zgreserve(n, p);
+    }
+    static int reserve_engine(psd_ctx* c, int n, int p, int) { return c->zgreserve(n, p); }
+    static T* H(psd_ctx* c) { return c->zH; }
+    static T* Z(psd_ctx* c) { return c->zZ; }
+    static T* vbuf(psd_ctx* c) { return c->zvbuf; }
+    static unsigned char* S(psd_ctx* c) { return c->zgS; }
+    static void workspace(psd_ctx* c, Params& P) {
+        P.S = S(c);
+        P.st = c->zgst;
+        P.desc = c->zgdesc;
+        P.tr = c->zgtr;
+        P.cnt = c->zgcnt;
+        P.dG = c->zgdG;
+        P.alpha = c->zalpha;
+        P.beta = c->zbeta;
+        P.ascale = c->zascale;
+        P.log = c->zlog;
+    }
+    static int train_workspace(psd_ctx* c, int p, Params& P, bool lists) {
+        if (int e = c->zgtreserve(p)) return e;
         P.cst = c->zgtcst;
         P.cep = (int*)(c->zgtcst + PSD_TRAIN_MAX);
         P.tshift = c->zgtshift;
-        if (M > 1) {
+        if (lists) {
             P.desc = c->zgtdesc;
             P.cnt = c->zgtcnt;
             P.tr = c->zgttr;
-            PSD_CHECK(c->lds_limit(reinterpret_cast<const void*>(psd_zgq_step_train), lds_step));
         }
+        return 0;
     }
-    int train_oc = 50;
-    if (const char* e = psd_env_diag("PSD_TRAIN_OC")) train_oc = atoi(e);  // (tuning hook)
-    PSD_LAUNCH(psd_zgq_init, psd_dim3(1), 256, 0, c->stream, P, n, p, wantT, wantZ, W, maxitfac, maxlog, hessmode,
-               (tw == -2) ? -2 : M, train_oc);
-    const size_t lds_apply = sizeof(psd_ztr) * PSD_GTR_CAP + (size_t)32 * (PSD_ZAPPLY_NT + 1) * sizeof(psd_z);
-    const int tiles = (n + PSD_ZAPPLY_NT - 1) / PSD_ZAPPLY_NT;
-    const int dtiles = (n + 255) / 256;
-    const int batch = 32;
-    psd_zgstate hst;
-    memset(&hst, 0, sizeof(hst));
-    long long launched = 0;
-    const int nbmin = (W - 3 > 0) ? ((W - 3 < 8) ? (W - 3) : 8) : 1;  // (trains run windows down to 8 positions)
-    const long long cap = (long long)maxitfac * n * ((long long)n / nbmin + 8) + 8LL * n + 1024 + (hessmode ? (long long)n * n : 0);
-#ifndef PSD_HOSTSIM
-    double sample_ms = 0.0;
-    int samples = 0;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pend;
-    psd_poller poller(c, sample_ms, samples);
-#endif
-    for (;;) {
-        for (int b = 0; b < batch; ++b) {
-            P.tick = (int)launched;
-            if (hess_pipe)
-                PSD_LAUNCH(psd_zgq_hess_step, psd_dim3(1), 64 * hess_waves, lds_hess, c->stream, P, hess_links);
-            else if (M > 1)
-                PSD_LAUNCH(psd_zgq_step_train, psd_dim3(M), PSD_STEP_NT, lds_step, c->stream, P, p, p + 8);
-            else
-                PSD_LAUNCH(psd_zgq_step, psd_dim3(1), PSD_STEP_NT, lds_step, c->stream, P);
-            if (M > 1) {
-                PSD_LAUNCH(psd_zgq_apply_train, psd_dim3(tiles, p, 2 * M), PSD_ZAPPLY_NT, lds_apply, c->stream, P, n, p, p + 8, 0);
-                PSD_LAUNCH(psd_zgq_apply_train, psd_dim3(tiles, p, M), PSD_ZAPPLY_NT, lds_apply, c->stream, P, n, p, p + 8, 1);
-            } else {
-                PSD_LAUNCH(psd_zgq_apply, psd_dim3(tiles, p, 3), PSD_ZAPPLY_NT, lds_apply, c->stream, P, n, p);
-            }
-            if (!hess_pipe) PSD_LAUNCH(psd_zgq_defer, psd_dim3(dtiles), 256, 0, c->stream, P, n);
-            ++launched;
-        }
-#ifdef PSD_HOSTSIM
-        PSD_CHECK(psd_rt_d2h(&hst, c->zgst, sizeof(hst), c->stream));
-        PSD_CHECK(psd_rt_sync(c->stream));
-#else
-        PSD_CHECK(poller.poll(&hst, c->zgst, sizeof(hst), pend));
-#endif
-        if (hst.phase == PSD_GPH_DONE) break;
-        if (launched > cap) {
-            *st_out = hst;
-            return PSD_INFO_RUNTIME + 0xfffc;
-        }
+    static psd_gapply_desc* tdesc(psd_ctx* c) { return c->zgtdesc; }
+    static const int* log(psd_ctx*) { return nullptr; }  // (this engine hands no sweep log to the host)
+    static int scan_sweep(Params&, int, int, size_t&) { return 1; }
+    static constexpr auto k_init = psd_zgq_init;
+    static constexpr auto k_step = psd_zgq_step;
+    static constexpr auto k_step_train = psd_zgq_step_train;
+    static constexpr auto k_apply = psd_zgq_apply;
+    static constexpr auto k_apply_train = psd_zgq_apply_train;
+    static constexpr auto k_defer = psd_zgq_defer;
+    static constexpr auto k_phase = psd_zgq_phase;
+    static constexpr auto k_set_identity = psd_zset_identity;
+    static constexpr auto k_antitranspose = psd_zantitranspose;
+    static constexpr auto k_flip = psd_zflip;
+    static constexpr auto k_tril_zero = psd_ztril_zero;
+    static constexpr auto k_hess_refl = psd_zhess_refl;
+    static constexpr auto k_hess_apply2 = psd_zhess_apply2;
+    static int hess_prepare(psd_ctx* c, int, size_t b, int&) { return c->lds_limit(reinterpret_cast<const void*>(psd_zgq_hess_step), b); }
+    static void hess_step(psd_ctx* c, const Params& P, int, int links, int waves, size_t lds) {
+        PSD_LAUNCH(psd_zgq_hess_step, psd_dim3(1), 64 * waves, lds, c->stream, P, links);
     }
-#ifndef PSD_HOSTSIM
-    PSD_CHECK(poller.finish(pend));
-#endif
-    if (!hessmode && hst.info == 0 && wantT) {  // generalized.jl:860-908
-        for (int l = p; l >= 2; --l) PSD_LAUNCH(psd_zgq_phase, psd_dim3(n), 64, 64, c->stream, P, n, l, wantZ);
-    }
-    PSD_CHECK(psd_rt_last_error());
-    *st_out = hst;
-    if (stats) {
-        stats->nlaunch_step = (int32_t)launched;
-        stats->window = W;
-    }
-    return 0;
-}
+};
 
+void stats_from_state(psd_stats* s, const psd_gstate& st) {
+    if (!s) return;
+    s->niter = st.jiter;
+    s->nsweeps = st.nsweeps;
+    s->nrqpass = st.nzshift;
+    s->ndefl1 = st.nsplit;
+    s->ndefl2 = st.n2real + st.n2cplx;
+    s->nwindows = st.nwindows;
+    s->nlog = st.nlog;
+    s->reserved = st.ncase2 + 1000 * st.ncase3;
+    s->maxits = st.ntrainsweeps;  // (signed path: sweeps that ran inside multishift trains)
+    for (int q = 0; q < 6; ++q) s->step_cycles[q] = st.cyc[q];
+}
 void stats_from_state(psd_stats* s, const psd_zgstate& st) {
     if (!s) return;
     s->niter = st.jiter;
@@ -2727,95 +2750,223 @@ void stats_from_state(psd_stats* s, const psd_zgstate& st) {
     s->nlog = st.nlog;
 }
 
-// (the complex signed engine hands no sweep log to the host)
-int zgrun_iteration(psd_ctx* c, int n, int p, psd_z* dH, psd_z* dZ, const uint8_t* S, int wantT, int wantZ,
-                    int maxitfac, double* alpha, double* beta, int32_t* ascale, psd_stats* stats) {
-    const int maxlog = 2 * maxitfac * n + n + 16;
-    psd_zgstate st;
-    if (int rc = zgiterate_dev(c, n, p, dH, dZ, S, wantT, wantZ, maxitfac, &st, stats, maxlog, 0)) return rc;
-    stats_from_state(stats, st);
-    return iteration_tail(c, n, p, wantT, wantZ, st.nlog, st.info, maxlog,
-                          {c->zalpha, sizeof(psd_z), c->zbeta, c->zascale, alpha, beta, ascale}, {nullptr, 16.0, true, 1.0},
-                          stats, nullptr, 0);
+// The signed periodic QZ on device.  dH [p][n][n] (H_1 Hessenberg), dZ [p][n][n] or nullptr; S host signature (S[0] true)
+// hessmode: run stage 2 of the signed Hessenberg reduction instead of the QZ iteration (same step/apply machinery)
+template <class E>
+int signed_iterate(psd_ctx* c, int n, int p, typename E::T* dH, typename E::T* dZ, const uint8_t* S, int wantT, int wantZ,
+                   int maxitfac, typename E::State* st_out, psd_stats* stats, int maxlog, int hessmode) {
+    const int W = choose_window(p, E::ESIZE);
+    if (W == 0) return PSD_INFO_NOTIMPL;
+    typename E::Params P;
+    E::workspace(c, P);
+    std::vector<unsigned char> hS(p, 1);
+    for (int l = 0; l < p; ++l) hS[l] = (!S || S[l]) ? 1 : 0;
+    PSD_CHECK(psd_rt_h2d(E::S(c), hS.data(), (size_t)p, c->stream));
+    PSD_CHECK(psd_rt_sync(c->stream));
+    P.H = dH;
+    {
+        int zl = 0, zh = p;
+        c->slice(p, zl, zh);
+        P.zlo = zl + 1;
+        P.zhi = zh;
+    }
+    P.Z = wantZ ? dZ : nullptr;
+    size_t lds_step = step_lds_bytes(p, W, E::ESIZE);
+    const int waves = E::scan_sweep(P, p, hessmode, lds_step);
+    (void)waves;  // (the serial simulation launches one simulated wavefront)
+    PSD_CHECK(c->lds_limit(reinterpret_cast<const void*>(E::k_step), lds_step));
+    // stage 2 of the signed Hessenberg reduction runs as a pipeline over the factors (psd_gq_hess_step, psd_zgq_hess_step)
+    // when its LDS (window + mailboxes) fits; PSD_HESS_SERIAL=1 (test hook) keeps the single-wave chase
+    const size_t lds_hess = E::hess_lds_bytes(p, W);
+    const int hess_links = psd_ghess_links(p), hess_waves = psd_ghess_waves(p);
+    const char* hserial = psd_env("PSD_HESS_SERIAL");
+    const bool hess_pipe = hessmode && lds_hess <= (size_t)160 * 1024 && !(hserial && hserial[0] == '1');
+    int hess_form = 0;
+    if (hess_pipe) PSD_CHECK(E::hess_prepare(c, p, lds_hess, hess_form));
+    // multishift trains (as iterate_dev): M cursors, cursor 0 is the ordinary state machine
+    const int tw = hessmode ? 0 : c->gtrain_m;
+    const int M = (tw >= 2) ? ((tw > E::TRAIN_CAP) ? E::TRAIN_CAP : tw) : 1;
+    P.cst = nullptr;
+    P.cep = nullptr;
+    P.tshift = nullptr;
+    P.tick = 0;
+    if (M > 1 || tw == -2) {
+        PSD_CHECK(E::train_workspace(c, p, P, M > 1));
+        PSD_CHECK(psd_rt_memset(P.cst, 0, sizeof(typename E::State) * PSD_TRAIN_MAX + sizeof(int) * (PSD_TRAIN_MAX + 8), c->stream));
+        PSD_CHECK(psd_rt_memset(E::tdesc(c), 0, sizeof(psd_gapply_desc) * PSD_TRAIN_MAX, c->stream));
+        if (M > 1) PSD_CHECK(c->lds_limit(reinterpret_cast<const void*>(E::k_step_train), lds_step));
+    }
+    int train_oc = 50;  // (a position of a signed factor costs about 1 us, a tick's overhead about 50 us)
+    if (const char* e = psd_env_diag("PSD_TRAIN_OC")) train_oc = atoi(e);  // (tuning hook)
+    PSD_LAUNCH(E::k_init, psd_dim3(1), 256, 0, c->stream, P, n, p, wantT, wantZ, W, maxitfac, maxlog, hessmode,
+               (tw == -2) ? -2 : M, train_oc);
+    const size_t lds_apply = E::lds_apply();
+    const int tiles = (n + E::APPLY_NT - 1) / E::APPLY_NT;
+    const int dtiles = (n + 255) / 256;
+    typename E::State hst;
+    memset(&hst, 0, sizeof(hst));
+    const int nbmin = (W - E::NBMIN_OFF > 0) ? ((W - E::NBMIN_OFF < 8) ? (W - E::NBMIN_OFF) : 8) : 1;  // (trains run windows down to 8 positions)
+    const long long cap = (long long)maxitfac * n * ((long long)n / nbmin + 8) + 8LL * n + 1024 + (hessmode ? (long long)n * n : 0);
+    auto tick = [&](long long launched, const tick_sample& sample) -> int {
+        P.tick = (int)launched;
+        const int rc = sample.around([&] {
+            if (hess_pipe)
+                E::hess_step(c, P, hess_form, hess_links, hess_waves, lds_hess);
+            else if (M > 1)
+                PSD_LAUNCH2(E::k_step_train, psd_dim3(M), PSD_STEP_NT, waves, lds_step, c->stream, P, p, p + 8);
+            else
+                PSD_LAUNCH2(E::k_step, psd_dim3(1), PSD_STEP_NT, waves, lds_step, c->stream, P);
+            return 0;
+        });
+        if (rc) return rc;
+        if (M > 1) {
+            PSD_LAUNCH(E::k_apply_train, psd_dim3(tiles, p, 2 * M), E::APPLY_NT, lds_apply, c->stream, P, n, p, p + 8, 0);
+            PSD_LAUNCH(E::k_apply_train, psd_dim3(tiles, p, M), E::APPLY_NT, lds_apply, c->stream, P, n, p, p + 8, 1);
+        } else {
+            PSD_LAUNCH(E::k_apply, psd_dim3(tiles, p, 3), E::APPLY_NT, lds_apply, c->stream, P, n, p);
+        }
+        if (!hess_pipe) PSD_LAUNCH(E::k_defer, psd_dim3(dtiles), 256, 0, c->stream, P, n);
+        return 0;
+    };
+    tick_totals T;
+    if (int rc = tick_loop(c, P.st, hst, cap, E::RUNAWAY, E::DIAG, tick, [](const typename E::State& g) { return g.phase == PSD_GPH_DONE; }, T)) {
+        *st_out = hst;
+        return rc;
+    }
+    if constexpr (E::DIAG) {
+        if (psd_env_diag("PSD_GDBG")) {
+            fprintf(stderr, "psd signed check stages (cycles/calls: test 1, tests 2-3, start rotations, train shifts, explicit start, cursor states, 2x2 block, split):");
+            for (int q = 0; q < 8; ++q) fprintf(stderr, " %lld/%d", hst.dbg[q], hst.dbgn[q]);
+            fprintf(stderr, " | cyc decide %lld load %lld chase %lld store %lld total %lld\n", hst.cyc[0], hst.cyc[1], hst.cyc[2], hst.cyc[3], hst.cyc[4]);
+        }
+    }
+    if constexpr (E::PHASE) {
+        if (!hessmode && hst.info == 0 && wantT)  // generalized.jl:860-908
+            for (int l = p; l >= 2; --l) PSD_LAUNCH(E::k_phase, psd_dim3(n), 64, 64, c->stream, P, n, l, wantZ);
+    }
+    PSD_CHECK(psd_rt_last_error());
+    *st_out = hst;
+    stats_from_ticks(stats, T, W);
+    return 0;
 }
 
-// _phessenberg!(A, S; wantQ) for ComplexF64 on device — generalized.jl:988-1082
-int zsghess_dev(psd_ctx* c, int n, int p, psd_z* dA, psd_z* dQ, const uint8_t* S, psd_stats* stats) {
+// _phessenberg!(A, S; wantQ) on device — generalized.jl:988-1082.  dA [p][n][n] internal order, overwritten by
+// H_1 (Hessenberg), H_l (upper triangular); dQ [p][n][n] or nullptr.
+template <class E>
+int signed_hess(psd_ctx* c, int n, int p, typename E::T* dA, typename E::T* dQ, const uint8_t* S, psd_stats* stats) {
+    typedef typename E::T T;
     const size_t nn = (size_t)n * n;
     const size_t lds_refl = PSD_HESS_NT * 8;
-    const size_t lds_apply = (PSD_HESS_NT + (size_t)n + 8) * sizeof(psd_z);
+    const size_t lds_apply = (PSD_HESS_NT + (size_t)n + 8) * sizeof(T);
     auto sg = [&](int l) { return !S || S[l - 1]; };
-    if (dQ) PSD_LAUNCH(psd_zset_identity, psd_dim3(n, p), 64, 0, c->stream, dQ, n);
+    if (dQ) PSD_LAUNCH(E::k_set_identity, psd_dim3(n, p), 64, 0, c->stream, dQ, n);
     Timer t;
     t.start(c->stream);
-    for (int l = p; l >= 2; --l) {
-        psd_z* Al = dA + (size_t)(l - 1) * nn;
-        psd_z* Am = dA + (size_t)(l - 2) * nn;
-        psd_z* Ql = dQ ? dQ + (size_t)(l - 1) * nn : nullptr;
+    for (int l = p; l >= 2; --l) {  // stage 1 (:1009-1028)
+        T* Al = dA + (size_t)(l - 1) * nn;
+        T* Am = dA + (size_t)(l - 2) * nn;
+        T* Ql = dQ ? dQ + (size_t)(l - 1) * nn : nullptr;
         const bool rq = !sg(l);
-        const int mrows = sg(l - 1) ? 0 : 1;
+        const int mrows = sg(l - 1) ? 0 : 1;  // A_{l-1} takes U from the right (columns) or U' from the left (rows)
         if (rq) {
-            PSD_LAUNCH(psd_zantitranspose, psd_dim3(n), 256, 0, c->stream, Al, n);
-            PSD_LAUNCH(psd_zflip, psd_dim3(n), 256, 0, c->stream, Am, n, mrows);
-            if (Ql) PSD_LAUNCH(psd_zflip, psd_dim3(n), 256, 0, c->stream, Ql, n, 0);
+            PSD_LAUNCH(E::k_antitranspose, psd_dim3(n), 256, 0, c->stream, Al, n);
+            PSD_LAUNCH(E::k_flip, psd_dim3(n), 256, 0, c->stream, Am, n, mrows);
+            if (Ql) PSD_LAUNCH(E::k_flip, psd_dim3(n), 256, 0, c->stream, Ql, n, 0);
         }
         for (int i = 1; i <= n - 1; ++i) {
-            psd_z* vcur = c->zvbuf + (size_t)(i & 1) * (n + 8);
-            psd_z* vnext = (i < n - 1) ? (c->zvbuf + (size_t)((i + 1) & 1) * (n + 8)) : nullptr;
-            if (i == 1) PSD_LAUNCH(psd_zhess_refl, psd_dim3(1), PSD_HESS_NT, lds_refl, c->stream, Al, n, i, i, vcur, (psd_z*)nullptr);
-            const int nL = (n - i + 3) / 4;
+            // (reflector i: by its own launch for the first column, behind the panel update of link i - 1 otherwise)
+            T* vcur = E::vbuf(c) + (size_t)(i & 1) * (n + 8);
+            T* vnext = (i < n - 1) ? (E::vbuf(c) + (size_t)((i + 1) & 1) * (n + 8)) : nullptr;
+            if (i == 1) PSD_LAUNCH(E::k_hess_refl, psd_dim3(1), PSD_HESS_NT, lds_refl, c->stream, Al, n, i, i, vcur, (T*)nullptr);
+            const int nL = (n - i + 3) / 4;   // columns i+1..n of A_l
             const int nR = (n + PSD_HESS_RS - 1) / PSD_HESS_RS;
-            // one launch: A_l (+ Q_l) and the neighbour A_{l-1} (see sghess_dev)
+            // one launch: A_l (+ Q_l) and the neighbour A_{l-1} (different matrices, same reflector)
             const int g1 = nL + (Ql ? nR : 0);
             const int nLm = (n + 3) / 4;
             if (mrows == 0) {
-                PSD_LAUNCH(psd_zhess_apply2, psd_dim3(g1 + nR), PSD_HESS_NT, lds_apply, c->stream, Al, Ql, i + 1, nL, g1,
-                           (psd_z*)nullptr, Am, 1, 0, n, i, (const psd_z*)vcur, vnext);
+                PSD_LAUNCH(E::k_hess_apply2, psd_dim3(g1 + nR), PSD_HESS_NT, lds_apply, c->stream, Al, Ql, i + 1, nL, g1,
+                           (T*)nullptr, Am, 1, 0, n, i, (const T*)vcur, vnext);
             } else {
-                PSD_LAUNCH(psd_zhess_apply2, psd_dim3(g1 + nLm), PSD_HESS_NT, lds_apply, c->stream, Al, Ql, i + 1, nL, g1, Am,
-                           (psd_z*)nullptr, 1, nLm, n, i, (const psd_z*)vcur, vnext);
+                PSD_LAUNCH(E::k_hess_apply2, psd_dim3(g1 + nLm), PSD_HESS_NT, lds_apply, c->stream, Al, Ql, i + 1, nL, g1, Am,
+                           (T*)nullptr, 1, nLm, n, i, (const T*)vcur, vnext);
             }
         }
-        PSD_LAUNCH(psd_ztril_zero, psd_dim3(n), 256, 0, c->stream, Al, n);
+        PSD_LAUNCH(E::k_tril_zero, psd_dim3(n), 256, 0, c->stream, Al, n);
         if (rq) {
-            PSD_LAUNCH(psd_zantitranspose, psd_dim3(n), 256, 0, c->stream, Al, n);
-            PSD_LAUNCH(psd_zflip, psd_dim3(n), 256, 0, c->stream, Am, n, mrows);
-            if (Ql) PSD_LAUNCH(psd_zflip, psd_dim3(n), 256, 0, c->stream, Ql, n, 0);
+            PSD_LAUNCH(E::k_antitranspose, psd_dim3(n), 256, 0, c->stream, Al, n);
+            PSD_LAUNCH(E::k_flip, psd_dim3(n), 256, 0, c->stream, Am, n, mrows);
+            if (Ql) PSD_LAUNCH(E::k_flip, psd_dim3(n), 256, 0, c->stream, Ql, n, 0);
         }
     }
     const double ms1 = t.stop(c->stream);
     t.start(c->stream);
-    psd_zgstate st;
-    int rc = zgiterate_dev(c, n, p, dA, dQ, S, 1, dQ ? 1 : 0, 1, &st, nullptr, 16, 1);
+    // stage 2 (:1034-1079): same step/apply machinery as the QZ iteration
+    if (int rc = E::reserve_engine(c, n, p, 16)) return rc;
+    typename E::State st;
+    const int rc = signed_iterate<E>(c, n, p, dA, dQ, S, 1, dQ ? 1 : 0, 1, &st, nullptr, 16, 1);
     const double ms2 = t.stop(c->stream);
     if (stats) {
         stats->ms_hess = ms1 + ms2;
-        stats->ms_formq = ms1;
-        stats->bytes_hess = 2.0 * 16.0 * p * (double)n * n * n;
+        stats->ms_formq = ms1;  // stage 1 (QR/RQ sweeps incl. the accumulation of Q)
+        // SURVEY.md section 8(d): stage 2 moves about n^3 element pairs per factor incl. Q
+        stats->bytes_hess = 2.0 * E::ESIZE * p * (double)n * n * n;
     }
     return rc;
 }
 
-// pschur!(A, S, lr) for ComplexF64 with a signed S — generalized.jl:108-148: the signed Hessenberg reduction, then the
-// signed periodic QZ, in working order (the reversal of generalized.jl:910-927 for 'L', the identity for 'R')
-int zsigned_pschur_host(psd_ctx* c, int n, int p, double* const* A, const uint8_t* S, char orient, int wantT, int wantZ,
-                        int maxitfac, double* const* Z, double* alpha, double* beta, int32_t* ascale, int* schurindex,
-                        psd_stats* s) {
+// run the iteration, then the shared tail
+template <class E>
+int signed_run_iteration(psd_ctx* c, int n, int p, typename E::T* dH, typename E::T* dZ, const uint8_t* S, int wantT,
+                         int wantZ, int maxitfac, double* alpha, double* beta, int32_t* ascale, psd_stats* stats,
+                         int32_t* sweeplog, int64_t maxlog_user) {
+    const int maxlog = 2 * maxitfac * n + n + 16;
+    if (int e = E::reserve_engine(c, n, p, maxlog)) return e;
+    typename E::State st;
+    if (int rc = signed_iterate<E>(c, n, p, dH, dZ, S, wantT, wantZ, maxitfac, &st, stats, maxlog, 0)) return rc;
+    stats_from_state(stats, st);
+    typename E::Params P;  // (for the eigenvalue arrays of the engine)
+    E::workspace(c, P);
+    return iteration_tail(c, n, p, wantT, wantZ, st.nlog, st.info, maxlog, {P.alpha, sizeof(psd_z), P.beta, P.ascale, alpha, beta, ascale},
+                          {E::log(c), (double)E::ESIZE, true, E::ROT0}, stats, sweeplog, maxlog_user);
+}
+
+// (the names of the single call's steps in the batch drivers: psd_gbatch_host.inl, psd_zgbatch_host.inl)
+constexpr auto sghess_dev = signed_hess<signed_real>;
+constexpr auto zsghess_dev = signed_hess<signed_cplx>;
+constexpr auto grun_iteration = signed_run_iteration<signed_real>;
+int zgrun_iteration(psd_ctx* c, int n, int p, psd_z* dH, psd_z* dZ, const uint8_t* S, int wantT, int wantZ, int maxitfac,
+                    double* alpha, double* beta, int32_t* ascale, psd_stats* stats) {
+    return signed_run_iteration<signed_cplx>(c, n, p, dH, dZ, S, wantT, wantZ, maxitfac, alpha, beta, ascale, stats, nullptr, 0);
+}
+
+// pschur!(A, S, lr; wantZ, wantT) with a signed S behind the entry's argument checks — rgeneralized.jl:3-45,
+// generalized.jl:108-148: the signed Hessenberg reduction, then the signed periodic QZ, in working order (for 'L' the
+// reversal of rgeneralized.jl:1062-1071 / generalized.jl:910-927, schurindex p).  User-order in/out as psd_d_pschur.
+template <class E>
+int signed_pschur_host(psd_ctx* c, int n, int p, double* const* A, const uint8_t* S, char orient, int wantT, int wantZ,
+                       int maxitfac, double* const* Z, double* alpha, double* beta, int32_t* ascale, int* schurindex,
+                       psd_stats* s, double* ms_copy) {  // ms_copy: as staged takes it
     if (maxitfac < 1) return -9;
     const bool left = orient == 'L';
     signed_order o;
-    if (int e = signed_slots(orient, left ? p : 1, p, S, o)) return e;
-    if (int e = c->zreserve(n, p, true, 2 * maxitfac * n + n + 16)) return e;
-    if (int e = c->zgreserve(n, p)) return e;
-    staged g{A, c->zH, wantZ ? Z : nullptr, c->zZ, false, (size_t)n * n * 16, o.sA.data(), o.sZ.data()};
+    if (int e = signed_slots(orient, left ? p : 1, p, S, o)) return e;  // rgeneralized.jl:37
+    if (int e = E::reserve(c, n, p, 2 * maxitfac * n + n + 16)) return e;
+    typename E::T* const dH = E::H(c);
+    typename E::T* const dZ = wantZ ? E::Z(c) : nullptr;
+    staged g{A, dH, wantZ ? Z : nullptr, E::Z(c), false, (size_t)n * n * E::ESIZE, o.sA.data(), o.sZ.data(), ms_copy};
     return staged_call(c, p, g, [&]() -> int {
         Timer tt;
         tt.start(c->stream);
-        if (int e = zsghess_dev(c, n, p, c->zH, wantZ ? c->zZ : nullptr, o.S.data(), s)) return e;
+        int e;
+        if constexpr (std::is_same<E, signed_real>::value)  // (psd_z_pschur sends an all-true signature to the unsigned engine)
+            e = o.alltrue ? E::householder(c, n, p, wantZ, s) : signed_hess<E>(c, n, p, dH, dZ, o.S.data(), s);
+        else
+            e = signed_hess<E>(c, n, p, dH, dZ, o.S.data(), s);
+        if (e) return e;
         Timer ti;
         ti.start(c->stream);
-        const int rc = zgrun_iteration(c, n, p, c->zH, wantZ ? c->zZ : nullptr, o.S.data(), wantT, wantZ, maxitfac, alpha,
-                                       beta, ascale, s);
+        const int rc = signed_run_iteration<E>(c, n, p, dH, dZ, o.S.data(), wantT, wantZ, maxitfac, alpha, beta, ascale, s,
+                                               nullptr, 0);
         s->ms_iter = ti.stop(c->stream);
         s->ms_total = tt.stop(c->stream);
         if (schurindex) *schurindex = left ? p : 1;
@@ -2823,19 +2974,34 @@ int zsigned_pschur_host(psd_ctx* c, int n, int p, double* const* A, const uint8_
     });
 }
 
-// pschur!(H1, Hs, S; ...) for ComplexF64 with a signed S — generalized.jl:166-931
-int zsigned_hess_host(psd_ctx* c, int n, int p, double* const* H, const uint8_t* S, double* const* Q, int wantT,
-                      int wantZ, int maxitfac, double* alpha, double* beta, int32_t* ascale, psd_stats* s) {
-    if (int e = c->zreserve(n, p, true, 2 * maxitfac * n + n + 16)) return e;
-    if (int e = c->zgreserve(n, p)) return e;
-    staged g{H, c->zH, wantZ ? Q : nullptr, c->zZ, true, (size_t)n * n * 16};
+// pschur!(H1, Hs, S; ...) with a signed S behind the entry's argument checks — rgeneralized.jl:47-, generalized.jl:166-931
+template <class E>
+int signed_hess_host(psd_ctx* c, int n, int p, double* const* H, const uint8_t* S, double* const* Q, int wantT, int wantZ,
+                     int maxitfac, double* alpha, double* beta, int32_t* ascale, psd_stats* s, int32_t* sweeplog,
+                     int64_t maxlog) {
+    if (int e = E::reserve(c, n, p, 2 * maxitfac * n + n + 16)) return e;
+    staged g{H, E::H(c), wantZ ? Q : nullptr, E::Z(c), true, (size_t)n * n * E::ESIZE};
     return staged_call(c, p, g, [&] {
         Timer t;
         t.start(c->stream);
-        const int rc = zgrun_iteration(c, n, p, c->zH, wantZ ? c->zZ : nullptr, S, wantT, wantZ, maxitfac, alpha, beta,
-                                       ascale, s);
+        const int rc = signed_run_iteration<E>(c, n, p, E::H(c), wantZ ? E::Z(c) : nullptr, S, wantT, wantZ, maxitfac, alpha,
+                                               beta, ascale, s, sweeplog, maxlog);
         s->ms_iter = s->ms_total = t.stop(c->stream);
         return rc;
+    });
+}
+
+// _phessenberg!(A, S) — generalized.jl:988-1082.  A[l] overwritten by H_l, Q[l] = Qs[l].
+template <class E>
+int signed_phessenberg_host(psd_ctx* c, int n, int p, double* const* A, const uint8_t* S, double* const* Q, psd_stats* stats,
+                            int* info) {
+    return psd_entry(c, stats, info, [&](psd_stats* s) -> int {
+        if (int e = check_dims(n, p)) return e;
+        if (!A) return -4;
+        if (S && !S[0]) return -5;  // generalized.jl:990
+        if (int e = E::reserve(c, n, p, 16)) return e;
+        staged g{A, E::H(c), Q, E::Z(c), false, (size_t)n * n * E::ESIZE};
+        return staged_call(c, p, g, [&] { return signed_hess<E>(c, n, p, E::H(c), Q ? E::Z(c) : nullptr, S, s); });
     });
 }
 
@@ -2843,18 +3009,44 @@ int zsigned_hess_host(psd_ctx* c, int n, int p, double* const* H, const uint8_t*
 
 extern "C" {
 
-// _phessenberg!(A, S) for ComplexF64 — generalized.jl:988-1082
-int psd_z_gphessenberg(psd_ctx* c, int n, int p, double* const* A, const uint8_t* S, double* const* Q, psd_stats* stats,
+// _phessenberg!(A, S) for Float64
+int psd_d_gphessenberg(psd_ctx* c, int n, int p, double* const* A, const uint8_t* S, double* const* Q, psd_stats* stats,
                        int* info) {
+    return signed_phessenberg_host<signed_real>(c, n, p, A, S, Q, stats, info);
+}
+
+// pschur!(A, S, lr; wantZ, wantT) for Float64 — rgeneralized.jl:3-45
+int psd_d_gpschur(psd_ctx* c, int n, int p, double* const* A, const uint8_t* S, char orient, int wantT, int wantZ,
+                  int maxitfac, double* const* Z, double* alpha, double* beta, int32_t* ascale, int* schurindex,
+                  psd_stats* stats, int* info) {
     return psd_entry(c, stats, info, [&](psd_stats* s) -> int {
         if (int e = check_dims(n, p)) return e;
         if (!A) return -4;
-        if (S && !S[0]) return -5;
-        if (int e = c->zreserve(n, p, true, 16)) return e;
-        if (int e = c->zgreserve(n, p)) return e;
-        staged g{A, c->zH, Q, c->zZ, false, (size_t)n * n * 16};
-        return staged_call(c, p, g, [&] { return zsghess_dev(c, n, p, c->zH, Q ? c->zZ : nullptr, S, s); });
+        if (orient != 'R' && orient != 'L') return -6;
+        if (wantZ && !Z) return -10;
+        return signed_pschur_host<signed_real>(c, n, p, A, S, orient, wantT, wantZ, maxitfac, Z, alpha, beta, ascale,
+                                               schurindex, s, &s->ms_copy);
     });
+}
+
+int psd_d_gpschur_hess(psd_ctx* c, int n, int p, double* const* H, const uint8_t* S, double* const* Q, int wantT,
+                       int wantZ, int maxitfac, double* alpha, double* beta, int32_t* ascale, psd_stats* stats,
+                       int32_t* sweeplog, int64_t maxlog, int* info) {
+    return psd_entry(c, stats, info, [&](psd_stats* s) -> int {
+        if (int e = check_dims(n, p)) return e;
+        if (!H) return -4;
+        if (S && !S[0]) return -5;  // rgeneralized.jl:73
+        if (wantZ && !Q) return -6;
+        if (maxitfac < 1) return -9;
+        return signed_hess_host<signed_real>(c, n, p, H, S, Q, wantT, wantZ, maxitfac, alpha, beta, ascale, s, sweeplog,
+                                             maxlog);
+    });
+}
+
+// _phessenberg!(A, S) for ComplexF64
+int psd_z_gphessenberg(psd_ctx* c, int n, int p, double* const* A, const uint8_t* S, double* const* Q, psd_stats* stats,
+                       int* info) {
+    return signed_phessenberg_host<signed_cplx>(c, n, p, A, S, Q, stats, info);
 }
 
 int psd_z_phessenberg(psd_ctx* c, int n, int p, double* const* A, double* tau, psd_stats* stats, int* info) {
@@ -2909,8 +3101,8 @@ int psd_z_pschur(psd_ctx* c, int n, int p, double* const* A, const uint8_t* S, c
         if (S)
             for (int j = 0; j < p; ++j)
                 if (!S[j])  // signed case (generalized.jl:138-146)
-                    return zsigned_pschur_host(c, n, p, A, S, orient, wantT, wantZ, maxitfac, Z, alpha, beta, ascale,
-                                               schurindex, s);
+                    return signed_pschur_host<signed_cplx>(c, n, p, A, S, orient, wantT, wantZ, maxitfac, Z, alpha, beta,
+                                                           ascale, schurindex, s, nullptr);
         if (int e = c->zreserve(n, p, true, 2 * (maxitfac > 0 ? maxitfac : 1) * n + n + 16)) return e;
         staged g{A, c->zH, wantZ ? Z : nullptr, c->zZ, false, (size_t)n * n * 16};
         g.ms_copy = &s->ms_copy;
@@ -2935,7 +3127,8 @@ int psd_z_pschur_hess(psd_ctx* c, int n, int p, double* const* H, const uint8_t*
         }
         if (wantZ && !Q) return -6;
         if (maxitfac < 1) return -9;
-        if (signedS) return zsigned_hess_host(c, n, p, H, S, Q, wantT, wantZ, maxitfac, alpha, beta, ascale, s);
+        if (signedS)  // (the complex signed engine hands no sweep log to the host)
+            return signed_hess_host<signed_cplx>(c, n, p, H, S, Q, wantT, wantZ, maxitfac, alpha, beta, ascale, s, nullptr, 0);
         if (int e = c->zreserve(n, p, true, 2 * maxitfac * n + n + 16)) return e;
         staged g{H, c->zH, wantZ ? Q : nullptr, c->zZ, true, (size_t)n * n * 16};
         return staged_call(c, p, g, [&] {
@@ -3290,357 +3483,6 @@ int psd_d_ordschur(psd_ctx* c, int n, int p, double* const* T, double* const* Z,
         return staged_call(c, p, g, [&] {
             int code;  // (the reordering drivers also leave their code here)
             return rordschur_dev(c, n, p, c->dH, c->dZ, select, wantZ, wr, wi, s, &code);
-        });
-    });
-}
-
-}  // extern "C"
-
-
-// =================================================================================================
-// real generalized (signed) periodic QZ — rgeneralized.jl
-namespace {
-
-// dH [p][n][n] (H_1 Hessenberg), dZ [p][n][n] or nullptr; S host signature (S[0] true)
-// hessmode: run stage 2 of the signed Hessenberg reduction instead of the QZ iteration (same step/apply machinery)
-int giterate_dev(psd_ctx* c, int n, int p, double* dH, double* dZ, const uint8_t* S, int wantT, int wantZ, int maxitfac,
-                 psd_gstate* st_out, psd_stats* stats, int maxlog, int hessmode = 0) {
-    const int W = choose_window(p, 8);
-    if (W == 0) return PSD_INFO_NOTIMPL;
-    std::vector<unsigned char> hS(p, 1);
-    for (int l = 0; l < p; ++l) hS[l] = (!S || S[l]) ? 1 : 0;
-    PSD_CHECK(psd_rt_h2d(c->gS, hS.data(), (size_t)p, c->stream));
-    PSD_CHECK(psd_rt_sync(c->stream));
-    psd_gparams P;
-    P.H = dH;
-    {
-        int zl = 0, zh = p;
-        c->slice(p, zl, zh);
-        P.zlo = zl + 1;
-        P.zhi = zh;
-    }
-    P.Z = wantZ ? dZ : nullptr;
-    P.S = c->gS;
-    P.st = c->gst;
-    P.desc = c->gdesc;
-    P.tr = c->gtr;
-    P.cnt = c->gcnt;
-    P.dG = c->gdG;
-    P.alpha = c->galpha;
-    P.beta = c->gbeta;
-    P.ascale = c->gascale;
-    P.log = c->glog;
-    P.xscr = c->gxscr;
-    size_t lds_step = step_lds_bytes(p, W, 8);
-    // scan form of the sweep windows (psd_gs3_run; PSD_GSCAN=0: the single-wave sweep): rotation tables and the helper
-    // wavefronts' command block behind everything the state machine uses
-    P.gcoff = P.gtaboff = 0;
-    int gwaves = 1;
-    (void)gwaves;
-    {
-        int gscan = 1;
-        if (const char* e = psd_env("PSD_GSCAN")) gscan = atoi(e);
-        const size_t need = lds_step + (size_t)p * 8 * sizeof(double) + 128;
-        if (gscan && !hessmode && p >= 2 && p <= 64 && need <= (size_t)160 * 1024) {
-            P.gtaboff = (int)lds_step;
-            P.gcoff = (int)(lds_step + (size_t)p * 8 * sizeof(double));
-            lds_step = need;
-#ifndef PSD_HOSTSIM
-            gwaves = 4;
-#endif
-        }
-    }
-    PSD_CHECK(c->lds_limit(reinterpret_cast<const void*>(psd_gq_step), lds_step));
-    // stage 2 of the signed Hessenberg reduction runs as a pipeline over the factors (psd_gq_hess_step) when its LDS
-    // (window + mailboxes) fits; PSD_HESS_SERIAL=1 (test hook) keeps the single-wave chase
-    const size_t lds_hess = psd_ghess_lds_bytes(p, W);
-    const int hess_links = psd_ghess_links(p), hess_waves = psd_ghess_waves(p);
-    const char* hserial = psd_env("PSD_HESS_SERIAL");
-    const bool hess_pipe = hessmode && lds_hess <= (size_t)160 * 1024 && !(hserial && hserial[0] == '1');
-    // (scan form of the stage-2 kernel, the default; PSD_HESS_SCAN=0: the pipeline of beats over the factors of round 2)
-    int hess_scan = 1;
-    if (const char* e = psd_env("PSD_HESS_SCAN")) hess_scan = atoi(e);
-    if (hess_pipe) {
-        PSD_CHECK(c->lds_limit(reinterpret_cast<const void*>(psd_gq_hess_step), lds_hess));
-        PSD_CHECK(c->lds_limit(reinterpret_cast<const void*>(psd_gq_hess_step_scan), lds_hess));
-    }
-    // multishift trains (as iterate_dev): M cursors, cursor 0 is the ordinary state machine
-    const int tw = hessmode ? 0 : c->gtrain_m;
-    const int M = (tw >= 2) ? ((tw > PSD_TRAIN_MAX) ? PSD_TRAIN_MAX : tw) : 1;
-    P.cst = nullptr;
-    P.cep = nullptr;
-    P.tshift = nullptr;
-    P.tick = 0;
-    if (M > 1 || tw == -2) {
-        PSD_CHECK(c->gtreserve(p));
-        PSD_CHECK(psd_rt_memset(c->gtcst, 0, sizeof(psd_gstate) * PSD_TRAIN_MAX + sizeof(int) * (PSD_TRAIN_MAX + 8), c->stream));
-        PSD_CHECK(psd_rt_memset(c->gtdesc, 0, sizeof(psd_gapply_desc) * PSD_TRAIN_MAX, c->stream));
-        P.cst = c->gtcst;
-        P.cep = (int*)(c->gtcst + PSD_TRAIN_MAX);
-        P.tshift = c->gtshift;
-        if (M > 1) {
-            P.desc = c->gtdesc;
-            P.cnt = c->gtcnt;
-            P.tr = c->gttr;
-            PSD_CHECK(c->lds_limit(reinterpret_cast<const void*>(psd_gq_step_train), lds_step));
-        }
-    }
-    int train_oc = 50;  // (a position of a signed factor costs about 1 us, a tick's overhead about 50 us)
-    if (const char* e = psd_env_diag("PSD_TRAIN_OC")) train_oc = atoi(e);  // (tuning hook)
-    PSD_LAUNCH(psd_gq_init, psd_dim3(1), 256, 0, c->stream, P, n, p, wantT, wantZ, W, maxitfac, maxlog, hessmode,
-               (tw == -2) ? -2 : M, train_oc);
-    const size_t lds_apply = PSD_GTR_LDS_BYTES + (size_t)32 * (PSD_GAPPLY_NT + 1) * sizeof(double);
-    const int tiles = (n + PSD_GAPPLY_NT - 1) / PSD_GAPPLY_NT;
-    const int dtiles = (n + 255) / 256;
-    const int batch = 32;
-    psd_gstate hst;
-    memset(&hst, 0, sizeof(hst));
-    long long launched = 0;
-    const int nbmin = (W - 5 > 0) ? ((W - 5 < 8) ? (W - 5) : 8) : 1;  // (trains run windows down to 8 positions)
-    const long long cap = (long long)maxitfac * n * ((long long)n / nbmin + 8) + 8LL * n + 1024 + (hessmode ? (long long)n * n : 0);
-    double sample_ms = 0.0;
-    int samples = 0;
-#ifndef PSD_HOSTSIM
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pend;
-    psd_poller poller(c, sample_ms, samples);
-#endif
-    for (;;) {
-        for (int b = 0; b < batch; ++b) {
-#ifndef PSD_HOSTSIM
-            const bool sample = c->profile && ((launched & 15) == 0);
-            if (sample) {
-                (void)hipEventCreate(&ev0);
-                (void)hipEventCreate(&ev1);
-                (void)hipEventRecord(ev0, c->stream);
-            }
-#endif
-            P.tick = (int)launched;
-            if (hess_pipe && hess_scan && p <= 64)
-                PSD_LAUNCH(psd_gq_hess_step_scan, psd_dim3(1), 256, lds_hess, c->stream, P, hess_links);  // (scan form: four wavefronts, one per SIMD)
-            else if (hess_pipe)
-                PSD_LAUNCH(psd_gq_hess_step, psd_dim3(1), 64 * hess_waves, lds_hess, c->stream, P, hess_links, 0);
-            else if (M > 1)
-                PSD_LAUNCH2(psd_gq_step_train, psd_dim3(M), PSD_STEP_NT, gwaves, lds_step, c->stream, P, p, p + 8);
-            else
-                PSD_LAUNCH2(psd_gq_step, psd_dim3(1), PSD_STEP_NT, gwaves, lds_step, c->stream, P);
-#ifndef PSD_HOSTSIM
-            if (sample) {
-                (void)hipEventRecord(ev1, c->stream);
-                pend.emplace_back(ev0, ev1);
-            }
-#endif
-            if (M > 1) {
-                PSD_LAUNCH(psd_gq_apply_train, psd_dim3(tiles, p, 2 * M), PSD_GAPPLY_NT, lds_apply, c->stream, P, n, p, p + 8, 0);
-                PSD_LAUNCH(psd_gq_apply_train, psd_dim3(tiles, p, M), PSD_GAPPLY_NT, lds_apply, c->stream, P, n, p, p + 8, 1);
-            } else {
-                PSD_LAUNCH(psd_gq_apply, psd_dim3(tiles, p, 3), PSD_GAPPLY_NT, lds_apply, c->stream, P, n, p);
-            }
-            if (!hess_pipe) PSD_LAUNCH(psd_gq_defer, psd_dim3(dtiles), 256, 0, c->stream, P, n);
-            ++launched;
-        }
-#ifdef PSD_HOSTSIM
-        PSD_CHECK(psd_rt_d2h(&hst, c->gst, sizeof(hst), c->stream));
-        PSD_CHECK(psd_rt_sync(c->stream));
-#else
-        PSD_CHECK(poller.poll(&hst, c->gst, sizeof(hst), pend));
-#endif
-        if (hst.phase == PSD_GPH_DONE) break;
-        if (launched > cap) {
-            *st_out = hst;
-            return PSD_INFO_RUNTIME + 0xfffd;
-        }
-    }
-#ifndef PSD_HOSTSIM
-    PSD_CHECK(poller.finish(pend));
-#endif
-    if (psd_env_diag("PSD_GDBG")) {
-        fprintf(stderr, "psd signed check stages (cycles/calls: test 1, tests 2-3, start rotations, train shifts, explicit start, cursor states, 2x2 block, split):");
-        for (int q = 0; q < 8; ++q) fprintf(stderr, " %lld/%d", hst.dbg[q], hst.dbgn[q]);
-        fprintf(stderr, " | cyc decide %lld load %lld chase %lld store %lld total %lld\n", hst.cyc[0], hst.cyc[1], hst.cyc[2], hst.cyc[3], hst.cyc[4]);
-    }
-    PSD_CHECK(psd_rt_last_error());
-    *st_out = hst;
-    if (stats) {
-        stats->nlaunch_step = (int32_t)launched;
-        stats->window = W;
-        stats->step_kernel_ms_avg = samples ? sample_ms / samples : 0.0;
-        stats->step_kernel_samples = samples;
-    }
-    return 0;
-}
-
-void stats_from_state(psd_stats* s, const psd_gstate& st) {
-    if (!s) return;
-    s->niter = st.jiter;
-    s->nsweeps = st.nsweeps;
-    s->nrqpass = st.nzshift;
-    s->ndefl1 = st.nsplit;
-    s->ndefl2 = st.n2real + st.n2cplx;
-    s->nwindows = st.nwindows;
-    s->nlog = st.nlog;
-    s->reserved = st.ncase2 + 1000 * st.ncase3;
-    s->maxits = st.ntrainsweeps;  // (signed path: sweeps that ran inside multishift trains)
-    for (int q = 0; q < 6; ++q) s->step_cycles[q] = st.cyc[q];
-}
-
-// (bytes_sweeps: a sweep of the real signed engine applies two rotations per (j, l))
-int grun_iteration(psd_ctx* c, int n, int p, double* dH, double* dZ, const uint8_t* S, int wantT, int wantZ,
-                   int maxitfac, double* alpha, double* beta, int32_t* ascale, psd_stats* stats, int32_t* sweeplog,
-                   int64_t maxlog_user) {
-    const int maxlog = 2 * maxitfac * n + n + 16;
-    if (int e = c->greserve(n, p, maxlog)) return e;
-    psd_gstate st;
-    if (int rc = giterate_dev(c, n, p, dH, dZ, S, wantT, wantZ, maxitfac, &st, stats, maxlog)) return rc;
-    stats_from_state(stats, st);
-    return iteration_tail(c, n, p, wantT, wantZ, st.nlog, st.info, maxlog,
-                          {c->galpha, sizeof(psd_z), c->gbeta, c->gascale, alpha, beta, ascale}, {c->glog, 8.0, true, 2.0},
-                          stats, sweeplog, maxlog_user);
-}
-
-// _phessenberg!(A, S; wantQ) on device — generalized.jl:988-1082.  dA [p][n][n] internal order, overwritten by
-// H_1 (Hessenberg), H_l (upper triangular); dQ [p][n][n] or nullptr.
-int sghess_dev(psd_ctx* c, int n, int p, double* dA, double* dQ, const uint8_t* S, psd_stats* stats) {
-    const size_t nn = (size_t)n * n;
-    const size_t lds_refl = PSD_HESS_NT * 8;
-    const size_t lds_apply = (PSD_HESS_NT + (size_t)n + 8) * 8;
-    auto sg = [&](int l) { return !S || S[l - 1]; };
-    if (dQ) PSD_LAUNCH(psd_set_identity, psd_dim3(n, p), 64, 0, c->stream, dQ, n);
-    Timer t;
-    t.start(c->stream);
-    for (int l = p; l >= 2; --l) {  // stage 1 (:1009-1028)
-        double* Al = dA + (size_t)(l - 1) * nn;
-        double* Am = dA + (size_t)(l - 2) * nn;
-        double* Ql = dQ ? dQ + (size_t)(l - 1) * nn : nullptr;
-        const bool rq = !sg(l);
-        const int mrows = sg(l - 1) ? 0 : 1;  // A_{l-1} takes U from the right (columns) or U' from the left (rows)
-        if (rq) {
-            PSD_LAUNCH(psd_antitranspose, psd_dim3(n), 256, 0, c->stream, Al, n);
-            PSD_LAUNCH(psd_flip, psd_dim3(n), 256, 0, c->stream, Am, n, mrows);
-            if (Ql) PSD_LAUNCH(psd_flip, psd_dim3(n), 256, 0, c->stream, Ql, n, 0);
-        }
-        for (int i = 1; i <= n - 1; ++i) {
-            // (reflector i: by its own launch for the first column, behind the panel update of link i - 1 otherwise)
-            double* vcur = c->vbuf + (size_t)(i & 1) * (n + 8);
-            double* vnext = (i < n - 1) ? (c->vbuf + (size_t)((i + 1) & 1) * (n + 8)) : nullptr;
-            if (i == 1) PSD_LAUNCH(psd_hess_refl, psd_dim3(1), PSD_HESS_NT, lds_refl, c->stream, Al, n, i, i, vcur, (double*)nullptr);
-            const int nL = (n - i + 3) / 4;   // columns i+1..n of A_l
-            const int nR = (n + PSD_HESS_RS - 1) / PSD_HESS_RS;
-            // one launch: A_l (+ Q_l) and the neighbour A_{l-1} (different matrices, same reflector)
-            const int g1 = nL + (Ql ? nR : 0);
-            const int nLm = (n + 3) / 4;
-            if (mrows == 0) {
-                PSD_LAUNCH(psd_hess_apply2, psd_dim3(g1 + nR), PSD_HESS_NT, lds_apply, c->stream, Al, Ql, i + 1, nL, g1,
-                           (double*)nullptr, Am, 1, 0, n, i, (const double*)vcur, vnext);
-            } else {
-                PSD_LAUNCH(psd_hess_apply2, psd_dim3(g1 + nLm), PSD_HESS_NT, lds_apply, c->stream, Al, Ql, i + 1, nL, g1, Am,
-                           (double*)nullptr, 1, nLm, n, i, (const double*)vcur, vnext);
-            }
-        }
-        PSD_LAUNCH(psd_tril_zero, psd_dim3(n), 256, 0, c->stream, Al, n);
-        if (rq) {
-            PSD_LAUNCH(psd_antitranspose, psd_dim3(n), 256, 0, c->stream, Al, n);
-            PSD_LAUNCH(psd_flip, psd_dim3(n), 256, 0, c->stream, Am, n, mrows);
-            if (Ql) PSD_LAUNCH(psd_flip, psd_dim3(n), 256, 0, c->stream, Ql, n, 0);
-        }
-    }
-    const double ms1 = t.stop(c->stream);
-    t.start(c->stream);
-    // stage 2 (:1034-1079): same step/apply machinery as the QZ iteration
-    if (int rc = c->greserve(n, p, 16)) return rc;
-    psd_gstate st;
-    int rc = giterate_dev(c, n, p, dA, dQ, S, 1, dQ ? 1 : 0, 1, &st, nullptr, 16, 1);
-    const double ms2 = t.stop(c->stream);
-    if (stats) {
-        stats->ms_hess = ms1 + ms2;
-        stats->ms_formq = ms1;  // stage 1 (QR/RQ sweeps incl. the accumulation of Q)
-        // SURVEY.md section 8(d): stage 2 moves about n^3 element pairs per factor incl. Q
-        stats->bytes_hess = 2.0 * 8.0 * p * (double)n * n * n;
-    }
-    return rc;
-}
-
-}  // namespace
-
-extern "C" {
-
-// _phessenberg!(A, S) — generalized.jl:988-1082 (Float64).  A[l] overwritten by H_l, Q[l] = Qs[l].
-int psd_d_gphessenberg(psd_ctx* c, int n, int p, double* const* A, const uint8_t* S, double* const* Q, psd_stats* stats,
-                       int* info) {
-    return psd_entry(c, stats, info, [&](psd_stats* s) -> int {
-        if (int e = check_dims(n, p)) return e;
-        if (!A) return -4;
-        if (S && !S[0]) return -5;  // generalized.jl:990
-        if (int e = c->reserve(n, p, true, 16)) return e;
-        staged g{A, c->dH, Q, c->dZ, false, (size_t)n * n * 8};
-        return staged_call(c, p, g, [&] { return sghess_dev(c, n, p, c->dH, Q ? c->dZ : nullptr, S, s); });
-    });
-}
-
-// pschur!(A, S, lr; wantZ, wantT) for Float64 — rgeneralized.jl:3-45.  User-order in/out as psd_d_pschur; the working
-// order is the reversal of rgeneralized.jl:1062-1071 for 'L' (schurindex p).
-int psd_d_gpschur(psd_ctx* c, int n, int p, double* const* A, const uint8_t* S, char orient, int wantT, int wantZ,
-                  int maxitfac, double* const* Z, double* alpha, double* beta, int32_t* ascale, int* schurindex,
-                  psd_stats* stats, int* info) {
-    return psd_entry(c, stats, info, [&](psd_stats* s) -> int {
-        if (int e = check_dims(n, p)) return e;
-        if (!A) return -4;
-        if (orient != 'R' && orient != 'L') return -6;
-        if (wantZ && !Z) return -10;
-        if (maxitfac < 1) return -9;
-        const bool left = orient == 'L';
-        signed_order o;
-        if (int e = signed_slots(orient, left ? p : 1, p, S, o)) return e;  // rgeneralized.jl:37
-        if (int e = c->reserve(n, p, true, 16)) return e;
-        staged g{A, c->dH, wantZ ? Z : nullptr, c->dZ, false, (size_t)n * n * 8, o.sA.data(), o.sZ.data()};
-        g.ms_copy = &s->ms_copy;
-        return staged_call(c, p, g, [&]() -> int {
-            Timer tt;
-            tt.start(c->stream);
-            if (o.alltrue) {  // rgeneralized.jl:21-34: Householder phessenberg!, explicit Q
-                Timer t;
-                t.start(c->stream);
-                if (int e = hessenberg_dev(c, n, p, c->dH, c->tau)) return e;
-                s->ms_hess = t.stop(c->stream);
-                if (wantZ) {
-                    t.start(c->stream);
-                    if (int e = formq_dev(c, n, p, c->dH, c->tau, c->dZ)) return e;
-                    s->ms_formq = t.stop(c->stream);
-                }
-                PSD_LAUNCH(psd_triu, psd_dim3(n, p), 64, 0, c->stream, c->dH, n);
-            } else {
-                if (int e = sghess_dev(c, n, p, c->dH, wantZ ? c->dZ : nullptr, o.S.data(), s)) return e;
-            }
-            Timer ti;
-            ti.start(c->stream);
-            const int rc = grun_iteration(c, n, p, c->dH, wantZ ? c->dZ : nullptr, o.S.data(), wantT, wantZ, maxitfac, alpha,
-                                          beta, ascale, s, nullptr, 0);
-            s->ms_iter = ti.stop(c->stream);
-            s->ms_total = tt.stop(c->stream);
-            if (schurindex) *schurindex = left ? p : 1;
-            return rc;
-        });
-    });
-}
-
-int psd_d_gpschur_hess(psd_ctx* c, int n, int p, double* const* H, const uint8_t* S, double* const* Q, int wantT,
-                       int wantZ, int maxitfac, double* alpha, double* beta, int32_t* ascale, psd_stats* stats,
-                       int32_t* sweeplog, int64_t maxlog, int* info) {
-    return psd_entry(c, stats, info, [&](psd_stats* s) -> int {
-        if (int e = check_dims(n, p)) return e;
-        if (!H) return -4;
-        if (S && !S[0]) return -5;  // rgeneralized.jl:73
-        if (wantZ && !Q) return -6;
-        if (maxitfac < 1) return -9;
-        if (int e = c->reserve(n, p, true, 16)) return e;
-        staged g{H, c->dH, wantZ ? Q : nullptr, c->dZ, true, (size_t)n * n * 8};
-        return staged_call(c, p, g, [&] {
-            Timer t;
-            t.start(c->stream);
-            const int rc = grun_iteration(c, n, p, c->dH, wantZ ? c->dZ : nullptr, S, wantT, wantZ, maxitfac, alpha, beta,
-                                          ascale, s, sweeplog, maxlog);
-            s->ms_iter = s->ms_total = t.stop(c->stream);
-            return rc;
         });
     });
 }
