@@ -1081,7 +1081,8 @@ int psd_z_checkpsd_batch_dev(psd_ctx* ctx, int nb, int n, int p, const double* d
  * norm kernel and per estimator step one solve and one vector kernel — at most 1 + 11 solves.  Every sum has a fixed
  * order: a problem's numbers do not depend on nb, on its place in the batch or on the grouping, bit for bit.
  * PSD_BATCH_GROUP acts as for the other batch entries.  Orders above 128 (PSD_BSYL_NMAX; PSD_BSYL_NMAX in the environment
- * at psd_create may only lower it) return PSD_INFO_NOTIMPL: the family has no single-problem path to fall back to.  So do
+ * at psd_create may only lower it) return PSD_INFO_NOTIMPL: the batch entries do not fall back to the single-problem
+ * entries psd_?_psylv / psd_?_subcond below, which the caller uses above the cap.  So do
  * periods whose small-block scratch does not fit the LDS (psd_z_: p > 19; psd_d_: p > 136).
  *
  * T: nb * p host matrices (psd_z_: interleaved complex), column-major, USER order, only read; the _dev variants take
@@ -1121,6 +1122,60 @@ int psd_d_subcond_batch_dev(psd_ctx* ctx, int nb, int n, int p, const double* dT
                             double* s, double* sep, double* dX, int64_t xb, int* infos, psd_bsylv_stats* stats, int* info);
 int psd_z_subcond_batch_dev(psd_ctx* ctx, int nb, int n, int p, const double* dT, char orient, int schurindex, const int* m,
                             double* s, double* sep, double* dX, int64_t xb, int* infos, psd_bsylv_stats* stats, int* info);
+
+/* ---- psylv, subcond: the same for ONE periodic Schur form of any order ----------------------------------------------
+ * The single-problem entries of the family above, with its definitions, argument conventions and codes: S, trans,
+ * from_t12, s, sep (xLACN2 on the p m k stacked unknowns in user order), m = 0 or n (s = 1, sep = +inf, X untouched, no
+ * launch), no scale factor.  The arguments are those of the batch entries without nb, xb and infos: m is one int, and
+ * the p blocks of C / X are m x k, column-major, leading dimension m (the _dev variants: one device array [p][m k],
+ * dT [p][n][n]).  T is only read.
+ *
+ * The solve is a tiled Bartels-Stewart walk: the rows of T11 and the columns of T22 are cut at multiples of the tile
+ * width (a boundary that would cut a 2x2 block of the quasi-triangular factor moves by one), the tiles of one
+ * anti-diagonal are solved in one launch by the body of the batch kernel, one wavefront per tile, and before that their
+ * right-hand sides receive the sums over the tiles solved earlier from a matrix-core update kernel (left-looking, K
+ * ascending, every tile of C written by one workgroup once: for one tile width the result is the same bits on every
+ * run; another width may round differently).  With a tile at least max(m, k) wide the call is one tile, no update, and
+ * the arithmetic of the batch kernel.  The tile width is PSD_SYL_TILE of psd_sylv.h; PSD_SYL_TILE in the environment at
+ * psd_create sets another one in 2 ... 128 (anything else: the default).  Periods whose small-block scratch does not
+ * fit the LDS (psd_z_: p > 19; psd_d_: p > 136) and a period-sharded context return PSD_INFO_NOTIMPL.
+ *
+ * Returns: -1 ctx NULL; -3 n < 1; -4 p < 1; -5 T NULL; -6 orient; -7 schurindex not in 1..p; -8 m outside 0..n or inside
+ * a 2x2 block; -9 C NULL (subcond: s or sep NULL); PSD_INFO_SINGULAR where a small solve was rejected (T11 and T22 share
+ * an eigenvalue of the product) or the numbers are not finite — X is NaN, s = 0, sep = 0 —; PSD_INFO_NOTIMPL;
+ * PSD_INFO_RUNTIME + k. */
+typedef struct psd_sylv_stats {
+    int32_t tile;        /* tile width of the call */
+    int32_t ntiles;      /* tiles of X */
+    int32_t ndiag;       /* anti-diagonals of the tile walk */
+    int32_t nsolve;      /* launches of the tile solve kernel */
+    int32_t nupdate;     /* launches of the update kernel */
+    int32_t nnorms;      /* launches of the norm kernel */
+    int32_t nest_steps;  /* launches of the estimator's vector kernel */
+    int32_t nest_solves; /* applications of S^-1 or S^-H the estimator took (<= 11) */
+    int32_t nest_iter;   /* iterations of the estimator (<= 5) */
+    int32_t nsingular;   /* 1: the call ended with PSD_INFO_SINGULAR */
+    double ms_solve;     /* device time of the tile solve launches */
+    double ms_update;    /* device time of the update launches */
+    double ms_est;       /* subcond: device time of the norm and vector kernels and the read-backs between the steps */
+    double ms_copy;      /* host entries: time of the copies */
+} psd_sylv_stats;
+int psd_d_psylv(psd_ctx* ctx, int n, int p, double* const* T, char orient, int schurindex, int m, double* const* C,
+                int trans, int from_t12, psd_sylv_stats* stats, int* info);
+int psd_z_psylv(psd_ctx* ctx, int n, int p, double* const* T, char orient, int schurindex, int m, double* const* C,
+                int trans, int from_t12, psd_sylv_stats* stats, int* info);
+int psd_d_psylv_dev(psd_ctx* ctx, int n, int p, const double* dT, char orient, int schurindex, int m, double* dC, int trans,
+                    int from_t12, psd_sylv_stats* stats, int* info);
+int psd_z_psylv_dev(psd_ctx* ctx, int n, int p, const double* dT, char orient, int schurindex, int m, double* dC, int trans,
+                    int from_t12, psd_sylv_stats* stats, int* info);
+int psd_d_subcond(psd_ctx* ctx, int n, int p, double* const* T, char orient, int schurindex, int m, double* s, double* sep,
+                  double* const* X, psd_sylv_stats* stats, int* info);
+int psd_z_subcond(psd_ctx* ctx, int n, int p, double* const* T, char orient, int schurindex, int m, double* s, double* sep,
+                  double* const* X, psd_sylv_stats* stats, int* info);
+int psd_d_subcond_dev(psd_ctx* ctx, int n, int p, const double* dT, char orient, int schurindex, int m, double* s,
+                      double* sep, double* dX, psd_sylv_stats* stats, int* info);
+int psd_z_subcond_dev(psd_ctx* ctx, int n, int p, const double* dT, char orient, int schurindex, int m, double* s,
+                      double* sep, double* dX, psd_sylv_stats* stats, int* info);
 
 #ifdef __cplusplus
 }

@@ -24,7 +24,7 @@ import PeriodicSchurDecompositions: pschur!, pschur, phessenberg!, gpschur, Peri
 const PSD = PeriodicSchurDecompositions
 using ArnoldiMethod: ArnoldiMethod
 
-export set_train!, engine_version, pschur_batch!, pschur_batch, gpschur_batch, eigvecs_batch_device, eigcond_batch, subspacecond_batch, psylvester_batch, geigvecs_batch_device, ordschur_batch!, checkpsd_batch
+export set_train!, engine_version, pschur_batch!, pschur_batch, gpschur_batch, eigvecs_batch_device, eigcond_batch, subspacecond_batch, psylvester_batch, subspacecond, psylvester, geigvecs_batch_device, ordschur_batch!, checkpsd_batch
 
 const libpsd = get(ENV, "LIBPSD_MI355X", joinpath(@__DIR__, "..", "periodicschurdecompositions.jl_amd", "libpsd_mi355x.so"))
 
@@ -662,7 +662,7 @@ end
 # s[l, q] = 1 / sqrt(1 + ||X_l||_F^2), sep[q] the reciprocal of LAPACK's xLACN2 estimate of ||S^-1||_1 on the p m k stacked
 # unknowns — and with want_x = true also X.  m = 0 or n: s = 1, sep = Inf.  A singular problem (T11 and T22 share an
 # eigenvalue of the product) gets X = NaN, s = 0, sep = 0, and its code (3000) is thrown after all have run unless `infos`
-# is given.  There is no scale factor (xTRSYL carries one) and no path above order 128 (NotImplemented).
+# is given.  There is no scale factor (xTRSYL carries one); above order 128: NotImplemented (psylvester / subspacecond per problem).
 # (Written by analogy with Engine.subspacecond_batch / Engine.psylvester_batch, the tested mirrors; not run.)
 function _bsylv_inputs(problems::Vector{<:PeriodicSchur}, m)
     nb = length(problems)
@@ -729,6 +729,55 @@ end
     (info[] < 0 || info[] >= INFO_NOTIMPL) && _throw(info[])
     infos === nothing && info[] != 0 && _throw_ord(info[])
     return want_x ? (s, sep, [_bsylv_blocks(bufs, mm, n, p, q) for q in 1:nb]) : (s, sep)
+end
+end
+
+# psylvester(ps, m; C, trans) and subspacecond(ps, m; want_x) — the same for ONE decomposition of any order
+# (psd_?_psylv, psd_?_subcond): the definitions, conventions and codes of the batch methods above, whose kernel stops at
+# order 128; the solve is a tiled walk over anti-diagonals of X (tile width PSD_SYL_TILE in the environment, default 16).
+# psylvester returns the p matrices X_l (m x k); subspacecond returns (s, sep), s a vector of p numbers, and with
+# want_x = true also X.  A singular form: X = NaN, s = 0, sep = 0 and the code 3000 thrown.
+# (Written by analogy with Engine.psylvester / Engine.subspacecond, the tested mirrors; not run.)
+for (Tv, solve, cond) in ((Float64, :psd_d_psylv, :psd_d_subcond), (ComplexF64, :psd_z_psylv, :psd_z_subcond))
+@eval function psylvester(ps::PeriodicSchur{$Tv}, m::Integer; C = nothing, trans::Bool = false)
+    nb, n, p, js, orient, mm, T, xb = _bsylv_inputs([ps], m)
+    mq = Int(clamp(m, 0, n)); k = n - mq
+    bufs = [zeros($Tv, mq, k) for _ in 1:p]
+    if C !== nothing
+        (length(C) == p && all(size(c) == (mq, k) for c in C)) ||
+            throw(DimensionMismatch("the right-hand sides are p matrices m x k"))
+        for l in 1:p
+            bufs[l] .= C[l]
+        end
+    end
+    info = Ref{Cint}(0)
+    Tp = _ptrs(T); Xp = [pointer(b) for b in bufs]
+    GC.@preserve T bufs Xp begin
+        ccall(($(QuoteNode(solve)), libpsd), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Ptr{Ptr{Float64}}, Cchar, Cint, Cint, Ptr{Ptr{$Tv}}, Cint, Cint, Ptr{Cvoid}, Ref{Cint}),
+              ctx().ptr, n, p, Tp, orient, js, m, Xp, trans, C === nothing, C_NULL, info)
+    end
+    (info[] < 0 || info[] >= INFO_NOTIMPL) && _throw(info[])
+    info[] != 0 && _throw_ord(info[])
+    return bufs
+end
+
+@eval function subspacecond(ps::PeriodicSchur{$Tv}, m::Integer; want_x::Bool = false)
+    nb, n, p, js, orient, mm, T, xb = _bsylv_inputs([ps], m)
+    mq = Int(clamp(m, 0, n)); k = n - mq
+    bufs = want_x ? [zeros($Tv, mq, k) for _ in 1:p] : Matrix{$Tv}[]
+    s = zeros(Float64, p); sep = Ref{Float64}(0.0)
+    info = Ref{Cint}(0)
+    Tp = _ptrs(T); Xp = [pointer(b) for b in bufs]
+    GC.@preserve T bufs Xp s begin
+        ccall(($(QuoteNode(cond)), libpsd), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Ptr{Ptr{Float64}}, Cchar, Cint, Cint, Ptr{Float64}, Ref{Float64}, Ptr{Ptr{$Tv}},
+               Ptr{Cvoid}, Ref{Cint}),
+              ctx().ptr, n, p, Tp, orient, js, m, s, sep, want_x ? pointer(Xp) : C_NULL, C_NULL, info)
+    end
+    (info[] < 0 || info[] >= INFO_NOTIMPL) && _throw(info[])
+    info[] != 0 && _throw_ord(info[])
+    return want_x ? (s, sep[], bufs) : (s, sep[])
 end
 end
 

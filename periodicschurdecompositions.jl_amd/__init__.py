@@ -191,6 +191,20 @@ class BsylvStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class SylvStats(C.Structure):
+    """psd_sylv_stats (include/psd_mi355x.h): the tile walk, launches, estimator solves and device times of one
+    psylvester or subspacecond call."""
+    _fields_ = [
+        ("tile", C.c_int32), ("ntiles", C.c_int32), ("ndiag", C.c_int32), ("nsolve", C.c_int32), ("nupdate", C.c_int32),
+        ("nnorms", C.c_int32), ("nest_steps", C.c_int32), ("nest_solves", C.c_int32), ("nest_iter", C.c_int32),
+        ("nsingular", C.c_int32),
+        ("ms_solve", C.c_double), ("ms_update", C.c_double), ("ms_est", C.c_double), ("ms_copy", C.c_double),
+    ]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class PKSFailure(Exception):
     """PKSFailure (src/krylov.jl:21-23): the Arnoldi re-initialisation failed."""
 
@@ -435,6 +449,10 @@ class Engine:
                                                              ip, C.POINTER(BsylvStats), ip])
                 sigs[f"psd_{t}_subcond_batch{dev}"] = (head + [mats, C.c_char, C.c_int, ip, dp, dp, mats, C.c_int64, ip,
                                                                C.POINTER(BsylvStats), ip])
+                # (the single-problem entries: no nb, xb and infos, m one int)
+                one = [C.c_void_p, C.c_int, C.c_int, mats, C.c_char, C.c_int, C.c_int]
+                sigs[f"psd_{t}_psylv{dev}"] = one + [mats, C.c_int, C.c_int, C.POINTER(SylvStats), ip]
+                sigs[f"psd_{t}_subcond{dev}"] = one + [dp, dp, mats, C.POINTER(SylvStats), ip]
             for nm, sig in sigs.items():
                 if hasattr(lib, nm):  # (tools load builds of earlier commits to time their single calls)
                     getattr(lib, nm).argtypes = sig
@@ -2157,7 +2175,7 @@ class Engine:
         and the call solves S(X) = C, or with trans=True S^H(Y) = C (the adjoint under the Frobenius inner product over
         the stacked blocks).  C=None: C_l = -T12_l; the solution then block-diagonalises the form,
         T_l [X_b; I] = [X_a; I] T22_l, so that Y_l = Z_l [X_l; I] spans the complementary periodic invariant
-        subspace (A_l Y_b = Y_a T22_l).  There is no scale factor (xTRSYL carries one), and no path above order 128 (NotImplementedPSD).
+        subspace (A_l Y_b = Y_a T22_l).  There is no scale factor (xTRSYL carries one); above order 128: NotImplementedPSD (use `psylvester` per problem).
 
         psylvester_batch(problems, m, C=None, trans=False): `problems` a list of PeriodicSchur, `C` per problem p
         matrices m x k; returns per problem the p matrices X_l.
@@ -2240,8 +2258,8 @@ class Engine:
             sep[q]  = 1 / est, est the estimate of ||S^-1||_1 on the p m k stacked unknowns (blocks in user order, each
                       column-major) by LAPACK's xLACN2 — real variant for Float64, complex for ComplexF64, at most 5
                       iterations and the final alternating-sign vector (p = 1: xTRSEN's SEP).
-        m = 0 or m = n: s = 1, sep = inf, X empty.  There is no scale factor, and no path above order 128
-        (NotImplementedPSD).
+        m = 0 or m = n: s = 1, sep = inf, X empty.  There is no scale factor; above order 128: NotImplementedPSD (use
+        `subspacecond` per problem).
 
         subspacecond_batch(problems, m, want_x=False) with a list of PeriodicSchur, or
         subspacecond_batch(T, m, want_x=False, lr=..., schurindex=...) with a GPU tensor [nb, p, n, n] (only read):
@@ -2289,6 +2307,120 @@ class Engine:
             return s, sep, [self._bsylv_blocks(bufs[q * p:(q + 1) * p], mm, n, q) for q in range(nb)]
 
         return self._batch_finish(info.value, infos, infos_out, self._raise_ord, True, result)
+
+    # ---- the same for one form of any order ------------------------------------------------------------------------
+    def _sylv_inputs(self, name, P, m, lr, schurindex, dev):
+        """(fam, n, p, T argument, orient, schurindex, m, keep-alive) of a single-problem call: `P` a PeriodicSchur, or
+        with `dev` a GPU tensor [p, n, n]"""
+        if dev:
+            if not hasattr(P, "data_ptr") or P.dim() != 3:
+                raise DimensionMismatch(f"{name}: one [p, n, n] GPU tensor of square factors")
+            P = P.unsqueeze(0)
+        elif hasattr(P, "data_ptr"):
+            raise TypeError(f"{name}: a PeriodicSchur (GPU tensors: {name}_dev)")
+        if isinstance(m, bool) or not isinstance(m, (int, np.integer)):
+            raise DimensionMismatch(f"{name}: m must be an int")
+        fam, _, _, n, p, T, orient, si, mm, _, keep = self._bsylv_inputs(name, P if dev else [P], int(m), lr, schurindex)
+        return fam, n, p, T, orient, si, int(mm[0]), keep
+
+    def _sylv_finish(self, info, info_out, result):
+        """a fatal code raises; the singular code goes to the list `info_out` with the result (X = NaN, s = 0, sep = 0),
+        or raises, as the per-problem codes of the batch wrappers do"""
+        return self._batch_finish(info, [info if info == 3000 else 0], info_out, self._raise_ord, True, result)
+
+    def _psylvester(self, name, P, m, C, trans, lr, schurindex, dev, info_out):
+        fam, n, p, T, orient, si, m, keep = self._sylv_inputs(name, P, m, lr, schurindex, dev)
+        k = n - m if 0 <= m <= n else 0
+        mq = m if 0 <= m <= n else 0
+        if dev:
+            import torch
+
+            dt = getattr(torch, np.dtype(fam.dtype).name)
+            X = torch.zeros((p, k, mq), dtype=dt, device=P.device)  # (column-major m x k blocks)
+            if C is not None:
+                if not hasattr(C, "data_ptr") or tuple(C.shape) != (p, mq, k):
+                    raise DimensionMismatch(f"{name}: C must be a [p, m, k] GPU tensor")
+                X.copy_(C.to(dt).transpose(1, 2))
+            torch.cuda.synchronize(P.device)
+            Xarg = _ct.c_void_p(X.data_ptr())
+        else:
+            bufs = [np.zeros((mq, k), dtype=fam.dtype, order="F") for _ in range(p)]
+            if C is not None:
+                C = list(C)
+                if len(C) != p or any(np.shape(c) != (mq, k) for c in C):
+                    raise DimensionMismatch(f"{name}: the right-hand sides are p matrices m x k")
+                if fam is _D and any(np.iscomplexobj(c) for c in C):
+                    raise TypeError(f"{name}: complex right-hand sides for a Float64 form")
+                for b, c in zip(bufs, C):
+                    b[...] = c
+            Xarg = self._ptrs(bufs)
+        st, info = SylvStats(), _ct.c_int(0)
+        fn = getattr(self.lib, f"psd_{fam.tag}_psylv{'_dev' if dev else ''}")
+        fn(self.ctx, n, p, T, orient.encode(), si, m, Xarg, int(bool(trans)), int(C is None), _ct.byref(st),
+           _ct.byref(info))
+        self.psylvester_stats = st
+        return self._sylv_finish(info.value, info_out, lambda: X.transpose(1, 2) if dev else bufs)
+
+    def psylvester(self, P, m, C=None, trans=False, info_out=None):
+        """The periodic Sylvester solve of `psylvester_batch` for ONE PeriodicSchur of any order (psd_?_psylv): with
+        the split m, S(X)_l = T11_l X_b - X_a T22_l, solves S(X) = C, with trans=True S^H(Y) = C; C=None: C_l = -T12_l,
+        whose solution block-diagonalises the form.  Float64 or ComplexF64 from the dtype; a signed
+        GeneralizedPeriodicSchur: NotImplementedPSD.  `C`: p matrices m x k (not written); returns the p matrices X_l.
+
+        The solve is a tiled walk (tile width PSD_SYL_TILE, default 16): for one tile width the result is the same
+        bits on every run.  A form whose T11 and T22 share an eigenvalue of the product, or whose solution is not
+        finite: X = NaN and SingularException, or with a list `info_out` the code [3000] there.  Stats:
+        `self.psylvester_stats` (SylvStats)."""
+        return self._psylvester("psylvester", P, m, C, trans, "R", 1, False, info_out)
+
+    def psylvester_dev(self, T, m, C=None, trans=False, lr="R", schurindex=1, info_out=None):
+        """`psylvester` on a GPU tensor T [p, n, n] (only read); C and the result are GPU tensors [p, m, k]."""
+        return self._psylvester("psylvester_dev", T, m, C, trans, lr, schurindex, True, info_out)
+
+    def _subspacecond(self, name, P, m, want_x, lr, schurindex, dev, info_out):
+        fam, n, p, T, orient, si, m, keep = self._sylv_inputs(name, P, m, lr, schurindex, dev)
+        k = n - m if 0 <= m <= n else 0
+        mq = m if 0 <= m <= n else 0
+        s, sep = np.zeros(p), np.zeros(1)
+        X = bufs = Xarg = None
+        if dev and want_x:
+            import torch
+
+            X = torch.zeros((p, k, mq), dtype=getattr(torch, np.dtype(fam.dtype).name), device=P.device)
+            Xarg = C.c_void_p(X.data_ptr())
+        elif want_x:
+            bufs = [np.zeros((mq, k), dtype=fam.dtype, order="F") for _ in range(p)]
+            Xarg = self._ptrs(bufs)
+        if dev:
+            import torch
+
+            torch.cuda.synchronize(P.device)
+        st, info = SylvStats(), C.c_int(0)
+        dp = C.POINTER(C.c_double)
+        fn = getattr(self.lib, f"psd_{fam.tag}_subcond{'_dev' if dev else ''}")
+        fn(self.ctx, n, p, T, orient.encode(), si, m, s.ctypes.data_as(dp), sep.ctypes.data_as(dp), Xarg, C.byref(st),
+           C.byref(info))
+        self.subspacecond_stats = st
+
+        def result():
+            if not want_x:
+                return s, float(sep[0])
+            return s, float(sep[0]), (X.transpose(1, 2) if dev else bufs)
+
+        return self._sylv_finish(info.value, info_out, result)
+
+    def subspacecond(self, P, m, want_x=False, info_out=None):
+        """How well separated the leading invariant periodic subspace of ONE PeriodicSchur of any order is
+        (psd_?_subcond): s[l] = 1 / sqrt(1 + ||X_l||_F^2) and sep = 1 / est(||S^-1||_1) as `subspacecond_batch` defines
+        them, X the solution of S(X) = -T12.  m = 0 or m = n: s = 1, sep = inf, X empty.  Returns (s, sep), s a numpy
+        array [p] and sep a float, with want_x also the p matrices X_l.  A singular form: s = 0, sep = 0, X = NaN and
+        SingularException, or with a list `info_out` the code [3000] there.  Stats: `self.subspacecond_stats`
+        (SylvStats), the estimator's solves among them."""
+        return self._subspacecond("subspacecond", P, m, want_x, "R", 1, False, info_out)
+
+    def subspacecond_dev(self, T, m, want_x=False, lr="R", schurindex=1, info_out=None):
+        """`subspacecond` on a GPU tensor T [p, n, n] (only read); with want_x X is a GPU tensor [p, m, k]."""
+        return self._subspacecond("subspacecond_dev", T, m, want_x, lr, schurindex, True, info_out)
 
     def eigvecs_batch(self, problems, *args, shifted=True, lr="R", schurindex=1, side="R"):
         """eigvecs(ps, select; shifted) by periodic back-substitution for MANY small decompositions of one shape in ONE

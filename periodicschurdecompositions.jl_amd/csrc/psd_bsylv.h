@@ -1,5 +1,7 @@
 // Periodic Sylvester solves for many small periodic Schur forms, and what xTRSEN builds on them (the S and the SEP of an
 // invariant periodic subspace), for the batches of psd_bord.h / psd_zbord.h.  The host driver is psd_bsylv_host.inl.
+// The bodies of the solve take a row range of T11 and a column range of T22: the whole of X here, a tile of it in the
+// single-problem walk of psd_sylv.h.
 //
 // A periodic Schur form of order n and period p in USER order, split at m (k = n - m): T_l = [T11_l T12_l; 0 T22_l].  With
 // (a(l), b(l)) = (l + 1, l) for orientation 'L' and (l, l + 1) for 'R' (the factors of the residual Z_a T_l Z_b' - A_l), the
@@ -31,7 +33,7 @@
 #include "psd_rord.h"
 #include "psd_zord.h"
 
-#define PSD_BSYL_NMAX 128  // largest order of the family (there is no single-problem path above it)
+#define PSD_BSYL_NMAX 128  // largest order of the batch entries (above it: the tiled single-problem walk of psd_sylv.h)
 #define PSD_BSYL_ITMAX 5   // xLACN2's iteration limit
 
 struct psd_bsyl_args {
@@ -89,16 +91,19 @@ PSD_D void psd_bsyl_poison(double* X, size_t xb, int p, int mk) {
 PSD_D bool psd_bsyl_finite(double v) { return v - v == 0.0; }
 PSD_D bool psd_bsyl_same_product(double pa, double pb) { return pa == pb && psd_bsyl_finite(pa) && pa != 0.0; }
 
-PSD_D void psd_bsyl_solve_real(const psd_bsyl_args& g) {
+// The rows [r.i0, r.i1) of T11 and the columns [r.j0, r.j1) of T22 (local: column j of T22 is column m + j of T) of one
+// problem: the whole of X for the batch kernel, a tile of it for the tiled walk of psd_sylv.h, whose update kernel has
+// taken the sums over the tiles solved before into the right-hand side.  X has leading dimension m.
+struct psd_bsyl_range {
+    int i0, i1, j0, j1;
+};
+
+// false: the problem is singular (the caller leaves the code and the NaNs)
+PSD_D bool psd_bsyl_real_range(const double* T, double* X, size_t xb, int n, int p, int m, int qsub, bool left, bool trans,
+                               int fromT, const psd_bsyl_range rg) {
     PSD_LDS_DECL;
-    const int q = PSD_BLOCK_X, n = g.n, p = g.p;
-    if (!g.act[q]) return;
-    const int m = g.m[q], k = n - m;
-    if (m <= 0 || k <= 0) return;
-    const bool left = g.left != 0, trans = g.ptrans ? g.ptrans[q] == 2 : g.trans != 0;
-    const size_t nn = (size_t)n * n, xb = g.xb;
-    const double* T = g.T + (size_t)q * p * nn;
-    double* X = g.X + (size_t)q * p * xb;
+    const size_t nn = (size_t)n * n;
+    const int mt = rg.i1 - rg.i0, kt = rg.j1 - rg.j0;
     double* scr = (double*)psd_lds;
     double* wk = scr + (size_t)p * PSD_RORD_SCR;
     double* ws = wk + (size_t)p * 52;
@@ -106,48 +111,48 @@ PSD_D void psd_bsyl_solve_real(const psd_bsyl_args& g) {
     const int nred = 4 * p > 64 ? 4 * p : 64;
     double* flag = red + nred;  // the block's verdict (and a word of padding)
     unsigned char* SL = (unsigned char*)(flag + 2);
-    const double* Tq = T + (size_t)g.qsub * nn;
-    if (g.fromT) {
+    const double* Tq = T + (size_t)qsub * nn;
+    if (fromT) {
         for (int l = 0; l < p; ++l) {
-            PSD_PAR_FOR(t, m * k) {
-                const int i = t % m, j = t / m;
-                X[(size_t)l * xb + t] = -T[(size_t)l * nn + (size_t)(m + j) * n + i];
+            PSD_PAR_FOR(t, mt * kt) {
+                const int i = rg.i0 + t % mt, j = rg.j0 + t / mt;
+                X[(size_t)l * xb + (size_t)j * m + i] = -T[(size_t)l * nn + (size_t)(m + j) * n + i];
             }
         }
     }
     PSD_PAR_FOR(l, p) { SL[l] = left ? 1 : 0; }
     PSD_SYNC();
     // block rows of T11: bottom-up (S^H: top-down); i0 is the first row of the block, p1 its width
-    int inext = trans ? 0 : m - 1;
-    while (trans ? inext < m : inext >= 0) {
+    int inext = trans ? rg.i0 : rg.i1 - 1;
+    while (trans ? inext < rg.i1 : inext >= rg.i0) {
         int i0, p1;
         if (trans) {
             i0 = inext;
-            p1 = (i0 + 1 < m && Tq[(size_t)i0 * n + i0 + 1] != 0.0) ? 2 : 1;
+            p1 = (i0 + 1 < rg.i1 && Tq[(size_t)i0 * n + i0 + 1] != 0.0) ? 2 : 1;
             inext = i0 + p1;
         } else {
-            p1 = (inext > 0 && Tq[(size_t)(inext - 1) * n + inext] != 0.0) ? 2 : 1;
+            p1 = (inext > rg.i0 && Tq[(size_t)(inext - 1) * n + inext] != 0.0) ? 2 : 1;
             i0 = inext - p1 + 1;
             inext = i0 - 1;
         }
         // block columns of T22: left to right (S^H: right to left)
-        int jnext = trans ? k - 1 : 0;
-        while (trans ? jnext >= 0 : jnext < k) {
+        int jnext = trans ? rg.j1 - 1 : rg.j0;
+        while (trans ? jnext >= rg.j0 : jnext < rg.j1) {
             int j0, p2;
             if (trans) {
-                p2 = (jnext > 0 && Tq[(size_t)(m + jnext - 1) * n + m + jnext] != 0.0) ? 2 : 1;
+                p2 = (jnext > rg.j0 && Tq[(size_t)(m + jnext - 1) * n + m + jnext] != 0.0) ? 2 : 1;
                 j0 = jnext - p2 + 1;
                 jnext = j0 - 1;
             } else {
                 j0 = jnext;
-                p2 = (j0 + 1 < k && Tq[(size_t)(m + j0) * n + m + j0 + 1] != 0.0) ? 2 : 1;
+                p2 = (j0 + 1 < rg.j1 && Tq[(size_t)(m + j0) * n + m + j0 + 1] != 0.0) ? 2 : 1;
                 jnext = j0 + p2;
             }
             const int pp = p1 * p2, items = p * pp;
             const int nparts = items >= 64 ? 1 : 64 / items;
             // the sums of the right-hand sides: over the solved rows below (above) in column j, then over the solved
             // columns to the left (right) in row i; a lane takes every nparts-th term, ascending
-            const int la = trans ? i0 : m - (i0 + p1), lb = trans ? k - (j0 + p2) : j0;
+            const int la = trans ? i0 - rg.i0 : rg.i1 - (i0 + p1), lb = trans ? rg.j1 - (j0 + p2) : j0 - rg.j0;
             PSD_PAR_FOR(t, items * nparts) {
                 const int it = t / nparts, part = t - it * nparts, e = it / pp, ent = it - e * pp;
                 const int i = i0 + ent % p1, j = j0 + ent / p1;
@@ -159,11 +164,11 @@ PSD_D void psd_bsyl_solve_real(const psd_bsyl_args& g) {
                 double s = 0.0;
                 for (int u = part; u < la + lb; u += nparts) {
                     if (u < la) {
-                        const int r = trans ? u : i0 + p1 + u;
+                        const int r = trans ? rg.i0 + u : i0 + p1 + u;
                         const double a = trans ? A[(size_t)i * n + r] : A[(size_t)r * n + i];
                         s -= a * Xa[(size_t)j * m + r];
                     } else {
-                        const int r = trans ? j0 + p2 + (u - la) : u - la;
+                        const int r = trans ? j0 + p2 + (u - la) : rg.j0 + (u - la);
                         const double b = trans ? B[(size_t)(m + r) * n + m + j] : B[(size_t)(m + j) * n + m + r];
                         s += Xb[(size_t)r * m + i] * b;
                     }
@@ -214,33 +219,41 @@ PSD_D void psd_bsyl_solve_real(const psd_bsyl_args& g) {
                 X[(size_t)(left ? eq.ua : eq.ub) * xb + (size_t)(j0 + jj) * m + i0 + ii] = v;
             }
             PSD_SYNC();
-            if (flag[0] != 0.0) {
-                PSD_ONE { g.info[q] = PSD_INFO_SINGULAR; }
-                psd_bsyl_poison<false>(X, xb, p, m * k);
-                return;
-            }
+            if (flag[0] != 0.0) return false;
         }
     }
+    return true;
 }
 
-PSD_D void psd_bsyl_solve_cplx(const psd_bsyl_args& g) {
-    PSD_LDS_DECL;
+PSD_D void psd_bsyl_solve_real(const psd_bsyl_args& g) {
     const int q = PSD_BLOCK_X, n = g.n, p = g.p;
     if (!g.act[q]) return;
     const int m = g.m[q], k = n - m;
     if (m <= 0 || k <= 0) return;
     const bool left = g.left != 0, trans = g.ptrans ? g.ptrans[q] == 2 : g.trans != 0;
-    const size_t nn = (size_t)n * n, xb = g.xb;
-    const psd_z* T = (const psd_z*)g.T + (size_t)q * p * nn;
-    psd_z* X = (psd_z*)g.X + (size_t)q * p * xb;
+    double* X = g.X + (size_t)q * p * g.xb;
+    if (psd_bsyl_real_range(g.T + (size_t)q * p * n * n, X, g.xb, n, p, m, g.qsub, left, trans, g.fromT,
+                            psd_bsyl_range{0, m, 0, k}))
+        return;
+    PSD_ONE { g.info[q] = PSD_INFO_SINGULAR; }
+    psd_bsyl_poison<false>(X, g.xb, p, m * k);
+}
+
+PSD_D bool psd_bsyl_cplx_range(const double* Td, double* Xd, size_t xb, int n, int p, int m, bool left, bool trans, int fromT,
+                               const psd_bsyl_range rg) {
+    PSD_LDS_DECL;
+    const size_t nn = (size_t)n * n;
+    const int mt = rg.i1 - rg.i0, kt = rg.j1 - rg.j0;
+    const psd_z* T = (const psd_z*)Td;
+    psd_z* X = (psd_z*)Xd;
     const int lstride = 8 * p + 1;  // a lane's eight arrays of p (the odd stride spreads the lanes over the banks)
     psd_z* lanes = (psd_z*)psd_lds;
     double* flag = (double*)(lanes + (size_t)64 * lstride);
-    if (g.fromT) {
+    if (fromT) {
         for (int l = 0; l < p; ++l) {
-            PSD_PAR_FOR(t, m * k) {
-                const int i = t % m, j = t / m;
-                X[(size_t)l * xb + t] = zneg(T[(size_t)l * nn + (size_t)(m + j) * n + i]);
+            PSD_PAR_FOR(t, mt * kt) {
+                const int i = rg.i0 + t % mt, j = rg.j0 + t / mt;
+                X[(size_t)l * xb + (size_t)j * m + i] = zneg(T[(size_t)l * nn + (size_t)(m + j) * n + i]);
             }
         }
     }
@@ -248,11 +261,11 @@ PSD_D void psd_bsyl_solve_cplx(const psd_bsyl_args& g) {
     PSD_SYNC();
     // anti-diagonal d: the entries with ri + cj = d, ri counted from the bottom row and cj from the left column (S^H:
     // from the top row and the right column)
-    for (int d = 0; d <= m + k - 2; ++d) {
-        const int rlo = d - (k - 1) > 0 ? d - (k - 1) : 0, rhi = d < m - 1 ? d : m - 1;
+    for (int d = 0; d <= mt + kt - 2; ++d) {
+        const int rlo = d - (kt - 1) > 0 ? d - (kt - 1) : 0, rhi = d < mt - 1 ? d : mt - 1;
         PSD_PAR_FOR(t, rhi - rlo + 1) {
             const int ri = rlo + t, cj = d - ri;
-            const int i = trans ? ri : m - 1 - ri, j = trans ? k - 1 - cj : cj;
+            const int i = trans ? rg.i0 + ri : rg.i1 - 1 - ri, j = trans ? rg.j1 - 1 - cj : rg.j0 + cj;
             psd_z* w = lanes + (size_t)(t & 63) * lstride;
             psd_z *ca = w, *cb = w + p, *cc = w + 2 * p, *cx = w + 3 * p;
             psd_z pa = zmk(1.0, 0.0), pb = zmk(1.0, 0.0);  // (in the order of the factors, whatever the chain's is)
@@ -268,11 +281,11 @@ PSD_D void psd_bsyl_solve_cplx(const psd_bsyl_args& g) {
                 const psd_z* Xb = X + (size_t)eq.ub * xb;
                 psd_z s = X[(size_t)e * xb + (size_t)j * m + i];
                 if (!trans) {
-                    for (int r = i + 1; r < m; ++r) s = zsub(s, zmul(A[(size_t)r * n + i], Xa[(size_t)j * m + r]));
-                    for (int r = 0; r < j; ++r) s = zadd(s, zmul(Xb[(size_t)r * m + i], B[(size_t)(m + j) * n + m + r]));
+                    for (int r = i + 1; r < rg.i1; ++r) s = zsub(s, zmul(A[(size_t)r * n + i], Xa[(size_t)j * m + r]));
+                    for (int r = rg.j0; r < j; ++r) s = zadd(s, zmul(Xb[(size_t)r * m + i], B[(size_t)(m + j) * n + m + r]));
                 } else {
-                    for (int r = 0; r < i; ++r) s = zsub(s, zmul(zconj(A[(size_t)i * n + r]), Xa[(size_t)j * m + r]));
-                    for (int r = j + 1; r < k; ++r)
+                    for (int r = rg.i0; r < i; ++r) s = zsub(s, zmul(zconj(A[(size_t)i * n + r]), Xa[(size_t)j * m + r]));
+                    for (int r = j + 1; r < rg.j1; ++r)
                         s = zadd(s, zmul(Xb[(size_t)r * m + i], zconj(B[(size_t)(m + r) * n + m + j])));
                 }
                 psd_z a = A[(size_t)i * n + i], b = B[(size_t)(m + j) * n + m + j];
@@ -297,12 +310,22 @@ PSD_D void psd_bsyl_solve_cplx(const psd_bsyl_args& g) {
             }
         }
         PSD_SYNC();
-        if (flag[0] != 0.0) {
-            PSD_ONE { g.info[q] = PSD_INFO_SINGULAR; }
-            psd_bsyl_poison<true>((double*)X, xb, p, m * k);
-            return;
-        }
+        if (flag[0] != 0.0) return false;
     }
+    return true;
+}
+
+PSD_D void psd_bsyl_solve_cplx(const psd_bsyl_args& g) {
+    const int q = PSD_BLOCK_X, n = g.n, p = g.p;
+    if (!g.act[q]) return;
+    const int m = g.m[q], k = n - m;
+    if (m <= 0 || k <= 0) return;
+    const bool left = g.left != 0, trans = g.ptrans ? g.ptrans[q] == 2 : g.trans != 0;
+    double* X = g.X + (size_t)q * p * g.xb * 2;
+    if (psd_bsyl_cplx_range(g.T + (size_t)q * p * n * n * 2, X, g.xb, n, p, m, left, trans, g.fromT, psd_bsyl_range{0, m, 0, k}))
+        return;
+    PSD_ONE { g.info[q] = PSD_INFO_SINGULAR; }
+    psd_bsyl_poison<true>(X, g.xb, p, m * k);
 }
 
 template <bool CPLX>

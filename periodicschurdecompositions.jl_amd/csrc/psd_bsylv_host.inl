@@ -7,7 +7,8 @@
 // one solve and one psd_bsyl_est_step (at most 2 * PSD_BSYL_ITMAX + 1 solves: xLACN2 needs no more); after every step one
 // record per problem comes back, and the problems that are done leave the launches that follow.  A problem with m = 0 or
 // m = n takes part in no launch.  Orders above bsyl_nmax, and periods whose small-block scratch does not fit the LDS:
-// PSD_INFO_NOTIMPL — the family has no single-problem path.
+// PSD_INFO_NOTIMPL — the batch entries do not fall back to the single-problem path (psd_sylv_host.inl, included behind
+// this file, which shares the argument checks, the small arrays and the condition group below with it).
 
 namespace {
 
@@ -18,8 +19,9 @@ struct bsylv_call {
     size_t xb;  // elements of a block of X
 };
 
+// capped: the batch entries, which end at bsyl_nmax
 int bsylv_checked(const psd_ctx* c, bool cplx, int nb, int n, int p, const void* T, char orient, int schurindex,
-                  const int* m) {
+                  const int* m, bool capped = true) {
     if (!c) return -1;
     if (nb < 0) return -2;
     if (n < 1) return -3;
@@ -32,7 +34,7 @@ int bsylv_checked(const psd_ctx* c, bool cplx, int nb, int n, int p, const void*
     for (int q = 0; q < nb; ++q)
         if (m[q] < 0 || m[q] > n) return -8;
     if (c->shard_world > 1) return PSD_INFO_NOTIMPL;  // (as the other batch entries)
-    if (n > c->bsyl_nmax) return PSD_INFO_NOTIMPL;    // (no single-problem path to fall back to)
+    if (capped && n > c->bsyl_nmax) return PSD_INFO_NOTIMPL;  // (the batch entries keep their cap)
     if (psd_bsyl_lds_bytes(p, cplx) > (size_t)160 * 1024) return PSD_INFO_NOTIMPL;  // (the scratch of p factors: ComplexF64 p > 19, Float64 p > 136)
     return 0;
 }
@@ -143,10 +145,21 @@ struct bsylv_work {
     }
 };
 
-// subcond: gc problems on the device; dX [gc][p][xb] receives X (the caller's, or workspace); s [gc][p], sep [gc] host
-template <bool CPLX>
-int bsylv_cond_group(const bsylv_call& k, int gc, const double* dT, double* dX, bool want_x, const int* m, bsylv_work& w,
-                     double* s, double* sep, int* infos, psd_bsylv_stats* st) {
+// X of a problem = NaN
+int bsylv_fill_nan(psd_ctx* c, double* dX, size_t doubles) {
+    const std::vector<double> nans(doubles, NAN);
+    PSD_CHECK(psd_rt_h2d(dX, nans.data(), sizeof(double) * doubles, c->stream));
+    PSD_CHECK(psd_rt_sync(c->stream));
+    return 0;
+}
+
+// subcond: gc problems on the device; dX [gc][p][xb] receives X (the caller's, or workspace); s [gc][p], sep [gc] host.
+// solve(X, ptrans, fromT, rec) applies S^-1 or S^-H to the blocks X of the group in place: ptrans null: S^-1, otherwise
+// the device array of the problems' kase, of which rec holds the host's copy (the single-problem walk orders its
+// launches by it).
+template <bool CPLX, class Solve>
+int bsylv_cond_group(const bsylv_call& k, int gc, double* dX, bool want_x, const int* m, bsylv_work& w,
+                     double* s, double* sep, int* infos, psd_bsylv_stats* st, Solve solve) {
     psd_ctx* c = k.c;
     const int p = k.p;
     constexpr int E = CPLX ? 2 : 1;
@@ -165,7 +178,8 @@ int bsylv_cond_group(const bsylv_call& k, int gc, const double* dT, double* dX, 
     tk.start(c->stream);
     psd_batchbuf ds;
     PSD_CHECK(ds.alloc(sizeof(double) * (size_t)gc * p));
-    if (int e = bsylv_launch_solve<CPLX>(k, gc, dT, dX, sm, nullptr, 0, 1, st)) return e;
+    std::vector<psd_bsyl_est> rec(gc);
+    if (int e = solve(dX, (const int*)nullptr, 1, rec)) return e;
     psd_bsyl_norm_args ng;
     ng.X = dX; ng.m = sm.m; ng.act = sm.act; ng.s = ds.d(); ng.xb = k.xb; ng.n = k.n; ng.p = p;
     PSD_LAUNCH(psd_bsyl_norms<CPLX>, psd_dim3(gc * p), 64, PSD_BSYL_RED_LDS, c->stream, ng);
@@ -185,7 +199,6 @@ int bsylv_cond_group(const bsylv_call& k, int gc, const double* dT, double* dX, 
         }
     }
     // the estimator: x = 1 / N, then solve and step in turn until every problem is done
-    std::vector<psd_bsyl_est> rec(gc);
     std::vector<int> einfo(gc, 0);
     if (nact > 0) {
         PSD_CHECK(psd_rt_memset(sm.rec, 0, sizeof(psd_bsyl_est) * gc, c->stream));
@@ -198,7 +211,7 @@ int bsylv_cond_group(const bsylv_call& k, int gc, const double* dT, double* dX, 
         if (step > 2 * PSD_BSYL_ITMAX + 1) return PSD_INFO_RUNTIME + 78;  // (xLACN2 cannot take more solves)
         PSD_CHECK(psd_rt_h2d(sm.act, act.data(), sizeof(int) * gc, c->stream));
         if (step > 0)
-            if (int e = bsylv_launch_solve<CPLX>(k, gc, dT, w.e.d(), sm, sm.kase, 0, 0, st)) return e;
+            if (int e = solve(w.e.d(), (const int*)sm.kase, 0, rec)) return e;
         PSD_LAUNCH(psd_bsyl_est_step<CPLX>, psd_dim3(gc), 64, PSD_BSYL_EST_LDS, c->stream, eg);
         st->nest_steps += 1;
         PSD_CHECK(psd_rt_d2h(rec.data(), sm.rec, sizeof(psd_bsyl_est) * gc, c->stream));
@@ -223,20 +236,24 @@ int bsylv_cond_group(const bsylv_call& k, int gc, const double* dT, double* dX, 
         }
     }
     // a problem that ended with the singular code: s = 0, sep = 0, X = NaN
-    std::vector<double> nans;
     for (int q = 0; q < gc; ++q) {
         if (infos[q] == 0) continue;
         st->nsingular += 1;
         sep[q] = 0.0;
         for (int l = 0; l < p; ++l) s[(size_t)q * p + l] = 0.0;
-        if (want_x) {
-            nans.assign((size_t)E * k.xb * p, NAN);
-            PSD_CHECK(psd_rt_h2d(dX + (size_t)q * nans.size(), nans.data(), sizeof(double) * nans.size(), c->stream));
-            PSD_CHECK(psd_rt_sync(c->stream));
-        }
+        if (want_x)
+            if (int e = bsylv_fill_nan(c, dX + (size_t)q * E * k.xb * p, (size_t)E * k.xb * p)) return e;
     }
     st->ms_kernels += tk.stop(c->stream);
     return 0;
+}
+
+// the solve of the batch entries' condition group: one launch for the group
+template <bool CPLX>
+auto bsylv_batch_solver(const bsylv_call& k, int gc, const double* dT, const bsylv_small& sm, psd_bsylv_stats* st) {
+    return [=, &k, &sm](double* X, const int* ptrans, int fromT, const std::vector<psd_bsyl_est>&) {
+        return bsylv_launch_solve<CPLX>(k, gc, dT, X, sm, ptrans, 0, fromT, st);
+    };
 }
 
 template <bool CPLX>
@@ -310,8 +327,8 @@ int bsylv_cond_dev(psd_ctx* c, int nb, int n, int p, const double* dT, char orie
     *info = bevec_dev_groups(c, nb, sizeof(double) * 3 * cb + 64, [&](int q0, int gc) {
         bsylv_work w;
         PSD_CHECK(w.alloc<CPLX>(gc, p, (size_t)xb, !dX));
-        return bsylv_cond_group<CPLX>(k, gc, dT + q0 * tb, dX ? dX + q0 * cb : w.x.d(), dX != nullptr, m + q0, w,
-                                      s + (size_t)q0 * p, sep + q0, pinfos + q0, st);
+        return bsylv_cond_group<CPLX>(k, gc, dX ? dX + q0 * cb : w.x.d(), dX != nullptr, m + q0, w, s + (size_t)q0 * p,
+                                      sep + q0, pinfos + q0, st, bsylv_batch_solver<CPLX>(k, gc, dT + q0 * tb, w.sm, st));
     });
     return *info != 0 ? *info : (*info = batch_first_code(pinfos, nb));
 }
@@ -337,8 +354,8 @@ int bsylv_cond_host(psd_ctx* c, int nb, int n, int p, double* const* T, char ori
     *info = batch_staged(c, nb, sizeof(double) * (bd + 3 * cd) * p + 64, L, &copies,
                          [&](int g) { return psd_rt_code(w.alloc<CPLX>(g, p, (size_t)xb, !X)); },
                          [&](int q0, int gc, double* const* d) {
-        return bsylv_cond_group<CPLX>(k, gc, d[0], X ? d[1] : w.x.d(), X != nullptr, m + q0, w, s + (size_t)q0 * p, sep + q0,
-                                      pinfos + q0, st);
+        return bsylv_cond_group<CPLX>(k, gc, X ? d[1] : w.x.d(), X != nullptr, m + q0, w, s + (size_t)q0 * p, sep + q0,
+                                      pinfos + q0, st, bsylv_batch_solver<CPLX>(k, gc, d[0], w.sm, st));
     });
     st->ms_copy = copies.ms_copy;
     return *info != 0 ? *info : (*info = batch_first_code(pinfos, nb));

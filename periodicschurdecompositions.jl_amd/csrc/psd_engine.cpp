@@ -37,6 +37,7 @@
 #include "psd_zgbord.h"
 #include "psd_gbord.h"
 #include "psd_bsylv.h"
+#include "psd_sylv.h"
 
 #include "../../include/psd_mi355x.h"
 
@@ -308,7 +309,8 @@ struct psd_ctx {
     int bev_nmax = PSD_BEV_NMAX;  // largest order of the batched eigenvector kernels (diagnostic build: PSD_BEV_NMAX in the environment, for the sweep that sets the constant)
     int bord_nmax = PSD_BORD_NMAX;  // largest order of the batched reordering kernel (PSD_BORD_NMAX in the environment lowers it: the tests reach the fallback with it)
     int bck_nmax = PSD_BCK_NMAX;    // largest order of the batched verifier (PSD_BCK_NMAX in the environment lowers it: the tests reach the fallback with it)
-    int bsyl_nmax = PSD_BSYL_NMAX;  // largest order of the batched periodic Sylvester kernels (PSD_BSYL_NMAX in the environment lowers it: the tests reach the refusal with it; there is no path above it)
+    int bsyl_nmax = PSD_BSYL_NMAX;  // largest order of the batched periodic Sylvester kernels (PSD_BSYL_NMAX in the environment lowers it: the tests reach the refusal with it; the batch entries have no path above it)
+    int syl_tile = PSD_SYL_TILE;  // tile width of the single-problem periodic Sylvester walk (PSD_SYL_TILE in the environment, 2 ... 128; anything else: the default)
     int bord_w = 0;                 // PSD_BORD_W: a narrower window of the batched reordering kernel (0: bord_window's own choice)
     void slice(int p, int& lo, int& hi) const {  // [lo, hi), 0-based internal factor index
         const int base = p / shard_world, rem = p % shard_world;
@@ -1945,6 +1947,7 @@ int psd_create(psd_ctx** ctx, int device) {
     if (const char* e = psd_env("PSD_BORD_NMAX")) c->bord_nmax = (atoi(e) >= 1 && atoi(e) < PSD_BORD_NMAX) ? atoi(e) : PSD_BORD_NMAX;
     if (const char* e = psd_env("PSD_BCK_NMAX")) c->bck_nmax = (atoi(e) >= 1 && atoi(e) < PSD_BCK_NMAX) ? atoi(e) : PSD_BCK_NMAX;
     if (const char* e = psd_env("PSD_BSYL_NMAX")) c->bsyl_nmax = (atoi(e) >= 1 && atoi(e) < PSD_BSYL_NMAX) ? atoi(e) : PSD_BSYL_NMAX;
+    if (const char* e = psd_env("PSD_SYL_TILE")) c->syl_tile = (atoi(e) >= PSD_SYL_TILE_MIN && atoi(e) <= PSD_SYL_TILE_MAX) ? atoi(e) : PSD_SYL_TILE;
     if (const char* e = psd_env("PSD_BORD_W")) c->bord_w = (atoi(e) >= 1 && atoi(e) <= 32) ? atoi(e) : 0;  // (each kernel has its own least window: PSD_BORD_WMIN, PSD_ZBORD_WMIN)
     if (const char* e = psd_env("PSD_BAND_HELPER")) c->band_helper = atoi(e);
     if (const char* e = psd_env_diag("PSD_TRAIN_LONG")) c->train_long = atoi(e);
@@ -3819,4 +3822,5 @@ extern "C" int psd_dbg_apply_bench(psd_ctx* c, int n, int p, int nwin, int W, in
 #include "psd_gbord_host.inl"
 #include "psd_bcheck_host.inl"
 #include "psd_bsylv_host.inl"
+#include "psd_sylv_host.inl"
 #include "psd_diag_scalar.inl"
