@@ -1177,6 +1177,29 @@ int psd_d_subcond_dev(psd_ctx* ctx, int n, int p, const double* dT, char orient,
 int psd_z_subcond_dev(psd_ctx* ctx, int n, int p, const double* dT, char orient, int schurindex, int m, double* s,
                       double* sep, double* dX, psd_sylv_stats* stats, int* info);
 
+/* ---- diagnostic entry of the walk's update kernel ---------------------------------------------------------------------
+ * TEST PLUMBING like the diagnostic entries of the dense Krylov kernels above, without a Julia binding: ONE launch of
+ * psd_syl_update through the walk's own checks, partition and launch code, so that a test can compare the kernel with a
+ * high-precision reference at a chosen tile width and anti-diagonal.  T, orient, schurindex and m as psd_?_psylv; X: the
+ * p blocks m x k (in / out), every entry meaningful: the launch reads the tiles the walk would have solved before
+ * anti-diagonal d and adds the two sums of psd_sylv.h to the tiles of d (trans != 0: the sums of S^H; from_t12 != 0: the
+ * tiles of d start from -T12 and not from what X holds).  Nothing else of X is written, no tile is solved.
+ * tile: the tile width of this call, 2 ... 128 (the context's width and PSD_SYL_TILE are not consulted).
+ * d: 1 ... nI + nJ - 2 (anti-diagonal 0 has no update; the walk numbers them as psd_sylv.h says).
+ * geom (may be NULL): the partition and the grid; bounds (may be NULL): n + 2 ints, receives the row boundaries of T11
+ * rb[0 .. nI] = 0 ... m followed by the local column boundaries of T22 cb[0 .. nJ] = 0 ... k.
+ * info: the codes -1 ... -9 of psd_?_psylv; -10 tile outside 2 ... 128; -11 d outside 1 ... nI + nJ - 2 (geom is set,
+ * nothing is launched, X is untouched; m = 0 or n has no anti-diagonal); PSD_INFO_NOTIMPL; PSD_INFO_RUNTIME + k. */
+typedef struct psd_syl_geom {
+    int32_t nI, nJ;  /* tiles per column and per row of X */
+    int32_t nsb;     /* 32 x 32 sub-blocks per tile and dimension: ceil((tile + 1) / 32) */
+    int32_t ndtiles; /* tiles on anti-diagonal d: the grid is (ndtiles nsb nsb, p) */
+} psd_syl_geom;
+int psd_d_syl_update(psd_ctx* ctx, int n, int p, double* const* T, char orient, int schurindex, int m, double* const* X,
+                     int tile, int d, int trans, int from_t12, psd_syl_geom* geom, int32_t* bounds, int* info);
+int psd_z_syl_update(psd_ctx* ctx, int n, int p, double* const* T, char orient, int schurindex, int m, double* const* X,
+                     int tile, int d, int trans, int from_t12, psd_syl_geom* geom, int32_t* bounds, int* info);
+
 #ifdef __cplusplus
 }
 #endif

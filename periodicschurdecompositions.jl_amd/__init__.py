@@ -141,6 +141,14 @@ class KrylovGeom(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class SylGeom(C.Structure):
+    """psd_syl_geom (include/psd_mi355x.h): partition and grid of one update launch of the periodic Sylvester walk."""
+    _fields_ = [("nI", C.c_int32), ("nJ", C.c_int32), ("nsb", C.c_int32), ("ndtiles", C.c_int32)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class EvecStats(C.Structure):
     """psd_evec_stats (include/psd_mi355x.h): counters and device times of one eigvecs call by back-substitution."""
     _fields_ = [
@@ -453,6 +461,9 @@ class Engine:
                 one = [C.c_void_p, C.c_int, C.c_int, mats, C.c_char, C.c_int, C.c_int]
                 sigs[f"psd_{t}_psylv{dev}"] = one + [mats, C.c_int, C.c_int, C.POINTER(SylvStats), ip]
                 sigs[f"psd_{t}_subcond{dev}"] = one + [dp, dp, mats, C.POINTER(SylvStats), ip]
+            # (test plumbing: X, tile, d, trans, from_t12, geom, bounds)
+            sigs[f"psd_{t}_syl_update"] = ([C.c_void_p, C.c_int, C.c_int, dpp, C.c_char, C.c_int, C.c_int, dpp, C.c_int,
+                                            C.c_int, C.c_int, C.c_int, C.POINTER(SylGeom), C.POINTER(C.c_int32), ip])
             for nm, sig in sigs.items():
                 if hasattr(lib, nm):  # (tools load builds of earlier commits to time their single calls)
                     getattr(lib, nm).argtypes = sig
@@ -2421,6 +2432,33 @@ class Engine:
     def subspacecond_dev(self, T, m, want_x=False, lr="R", schurindex=1, info_out=None):
         """`subspacecond` on a GPU tensor T [p, n, n] (only read); with want_x X is a GPU tensor [p, m, k]."""
         return self._subspacecond("subspacecond_dev", T, m, want_x, lr, schurindex, True, info_out)
+
+    def syl_update(self, ps, m, X, tile, d, trans=False, from_t12=False):
+        """Test plumbing (psd_?_syl_update, include/psd_mi355x.h): ONE launch of the update kernel of the walk of
+        `psylvester`, at the tile width `tile` (2 ... 128, whatever the engine's own) on anti-diagonal `d` of the
+        partition of `ps` split at m.  `X`: p matrices m x k (not written), every entry meaningful.  Returns (Y, geom):
+        the p matrices after the launch and a dict with nI, nJ, nsb, ndtiles and the boundaries rb (rows of T11) and cb
+        (local columns of T22).  `d` outside 1 ... nI + nJ - 2: ValueError (argument 11), nothing is launched."""
+        name = "syl_update"
+        fam, n, p, T, orient, si, m, keep = self._sylv_inputs(name, ps, m, "R", 1, False)
+        if not 0 < m < n:
+            raise ValueError(f"{name}: a split 0 < m < n (m = 0 or n has no update)")
+        X = list(X)
+        if len(X) != p or any(np.shape(x) != (m, n - m) for x in X):
+            raise DimensionMismatch(f"{name}: X is p matrices m x k")
+        if fam is _D and any(np.iscomplexobj(x) for x in X):
+            raise TypeError(f"{name}: complex X for a Float64 form")
+        bufs = [np.array(x, dtype=fam.dtype, order="F") for x in X]
+        geom, info = SylGeom(), _ct.c_int(0)
+        bounds = np.zeros(n + 2, dtype=np.int32)
+        fn = getattr(self.lib, f"psd_{fam.tag}_syl_update")
+        fn(self.ctx, n, p, T, orient.encode(), si, m, self._ptrs(bufs), int(tile), int(d), int(bool(trans)),
+           int(bool(from_t12)), _ct.byref(geom), bounds.ctypes.data_as(_ct.POINTER(_ct.c_int32)), _ct.byref(info))
+        self._raise(info.value)
+        g = geom.asdict()
+        g["rb"] = [int(b) for b in bounds[:g["nI"] + 1]]
+        g["cb"] = [int(b) for b in bounds[g["nI"] + 1:g["nI"] + g["nJ"] + 2]]
+        return bufs, g
 
     def eigvecs_batch(self, problems, *args, shifted=True, lr="R", schurindex=1, side="R"):
         """eigvecs(ps, select; shifted) by periodic back-substitution for MANY small decompositions of one shape in ONE

@@ -89,12 +89,12 @@ struct sylv_plan {
 };
 
 // The partition of a form on the device; Float64: the sub-diagonal of the quasi-triangular factor comes back once, for
-// the split check (-8) and the boundaries
+// the split check (-8) and the boundaries; tile: the width of the call (0: the context's)
 template <bool CPLX>
 int sylv_prepare(sylv_plan& pl, psd_ctx* c, int n, int p, const double* dT, char orient, int schurindex, int m,
-                 psd_sylv_stats* st) {
+                 psd_sylv_stats* st, int tile = 0, std::vector<int>* bounds_out = nullptr) {
     pl.c = c; pl.n = n; pl.p = p; pl.m = m; pl.qsub = schurindex - 1; pl.left = orient == 'L'; pl.st = st;
-    const int t = c->syl_tile;
+    const int t = tile > 0 ? tile : c->syl_tile;
     st->tile = t;
     if (pl.trivial()) return 0;
     std::vector<double> sub;
@@ -115,6 +115,7 @@ int sylv_prepare(sylv_plan& pl, psd_ctx* c, int n, int p, const double* dT, char
     pl.nsb = (t + 1 + PSD_SYL_UB - 1) / PSD_SYL_UB;  // (a tile is at most t + 1 wide)
     std::vector<int> both(rb);
     both.insert(both.end(), cb.begin(), cb.end());
+    if (bounds_out) *bounds_out = both;
     PSD_CHECK(pl.bounds.alloc(sizeof(int) * both.size()));
     PSD_CHECK(psd_rt_h2d(pl.bounds.ptr, both.data(), sizeof(int) * both.size(), c->stream));
     PSD_CHECK(psd_rt_sync(c->stream));  // (the host vector goes away)
@@ -123,14 +124,26 @@ int sylv_prepare(sylv_plan& pl, psd_ctx* c, int n, int p, const double* dT, char
     return 0;
 }
 
+psd_syl_args sylv_args(const sylv_plan& pl, const double* dT, double* dX, int* dflag, int trans, int fromT, int d) {
+    psd_syl_args g;
+    g.T = dT; g.X = dX; g.rb = pl.rb(); g.cb = pl.cb(); g.flag = dflag;
+    g.n = pl.n; g.p = pl.p; g.m = pl.m; g.qsub = pl.qsub; g.left = pl.left; g.trans = trans; g.fromT = fromT;
+    g.nI = pl.nI; g.nJ = pl.nJ; g.d = d; g.nsb = pl.nsb;
+    return g;
+}
+
+// the update launch of anti-diagonal g.d >= 1 (the walk, and the diagnostic entry psd_?_syl_update)
+template <bool CPLX>
+void sylv_launch_update(const sylv_plan& pl, const psd_syl_args& g) {
+    const int nt = psd_syl_diag_tiles(pl.nI, pl.nJ, g.d);
+    PSD_LAUNCH(psd_syl_update<CPLX>, psd_dim3(nt * pl.nsb * pl.nsb, pl.p), PSD_SYL_NT, 0, pl.c->stream, g);
+}
+
 // X := S^-1 X (trans: S^-H X), with fromT of -T12, by the tiled walk; dflag: the singular word.  Nothing is read back.
 template <bool CPLX>
 int sylv_apply(sylv_plan& pl, const double* dT, double* dX, int* dflag, int trans, int fromT) {
     psd_ctx* c = pl.c;
-    psd_syl_args g;
-    g.T = dT; g.X = dX; g.rb = pl.rb(); g.cb = pl.cb(); g.flag = dflag;
-    g.n = pl.n; g.p = pl.p; g.m = pl.m; g.qsub = pl.qsub; g.left = pl.left; g.trans = trans; g.fromT = fromT;
-    g.nI = pl.nI; g.nJ = pl.nJ; g.d = 0; g.nsb = pl.nsb;
+    psd_syl_args g = sylv_args(pl, dT, dX, dflag, trans, fromT, 0);
     const size_t lds = psd_bsyl_lds_bytes(pl.p, CPLX);
     PSD_CHECK(c->lds_limit(reinterpret_cast<const void*>(psd_syl_solve<CPLX>), lds));
     pl.napply += 1;
@@ -140,7 +153,7 @@ int sylv_apply(sylv_plan& pl, const double* dT, double* dX, int* dflag, int tran
         g.d = d;
         if (d > 0) {  // (every tile behind the first anti-diagonal has a neighbour that is solved)
             g.fromT = fromT;
-            PSD_LAUNCH(psd_syl_update<CPLX>, psd_dim3(nt * pl.nsb * pl.nsb, pl.p), PSD_SYL_NT, 0, c->stream, g);
+            sylv_launch_update<CPLX>(pl, g);
             pl.st->nupdate += 1;
             pl.marks.mark(c->stream, sylv_marks::UPDATE);
         }
@@ -278,6 +291,43 @@ int sylv_cond_host(psd_ctx* c, int n, int p, double* const* T, char orient, int 
     return *info != 0 ? *info : (*info = code);
 }
 
+// ---- diagnostic entry of the update kernel (test plumbing; include/psd_mi355x.h) -------------------------------------
+// the checks and the partition of the walk at the width `tile`, then the update launch of anti-diagonal d alone, on host
+// blocks staged as those of psd_?_psylv
+template <bool CPLX>
+int sylv_update_host(psd_ctx* c, int n, int p, double* const* T, char orient, int schurindex, int m, double* const* X,
+                     int tile, int d, int trans, int from_t12, psd_syl_geom* geom, int32_t* bounds, int* info) {
+    batch_call<psd_sylv_stats> entry(info, nullptr);
+    if ((*info = sylv_head(c, CPLX, n, p, T, orient, schurindex, m)) != 0) return *info;
+    if (!X) return *info = -9;
+    if (tile < PSD_SYL_TILE_MIN || tile > PSD_SYL_TILE_MAX) return *info = -10;
+    constexpr int E = CPLX ? 2 : 1;
+    const size_t bd = (size_t)E * n * n, cd = (size_t)E * m * (n - m);
+    const batch_list L[] = {{T, p, bd, BATCH_IN}, {X, p, cd, BATCH_IN | BATCH_OUT}};
+    return *info = batch_staged(c, 1, sizeof(double) * (bd + cd) * p + 64, L, nullptr, batch_no_extra,
+                                [&](int, int, double* const* dv) {
+        sylv_plan pl;
+        std::vector<int> both;
+        if (int e = sylv_prepare<CPLX>(pl, c, n, p, dv[0], orient, schurindex, m, entry.s, tile, &both)) return e;
+        if (geom) {
+            geom->nI = pl.nI;
+            geom->nJ = pl.nJ;
+            geom->nsb = pl.nsb;
+            geom->ndtiles = 0;
+        }
+        if (d < 1 || d > pl.nI + pl.nJ - 2) return -11;  // (the trivial splits have no anti-diagonal at all)
+        if (geom) geom->ndtiles = psd_syl_diag_tiles(pl.nI, pl.nJ, d);
+        if (bounds) std::copy(both.begin(), both.end(), bounds);
+        bsylv_small sm;
+        PSD_CHECK(sm.alloc(1));
+        PSD_CHECK(psd_rt_memset(sm.info, 0, sizeof(int), c->stream));
+        sylv_launch_update<CPLX>(pl, sylv_args(pl, dv[0], dv[1], sm.info, trans != 0, from_t12 != 0, d));
+        PSD_CHECK(psd_rt_sync(c->stream));
+        PSD_CHECK(psd_rt_last_error());
+        return 0;
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -314,6 +364,15 @@ int psd_d_subcond_dev(psd_ctx* c, int n, int p, const double* dT, char orient, i
 int psd_z_subcond_dev(psd_ctx* c, int n, int p, const double* dT, char orient, int schurindex, int m, double* s, double* sep,
                       double* dX, psd_sylv_stats* stats, int* info) {
     return sylv_cond_dev<true>(c, n, p, dT, orient, schurindex, m, s, sep, dX, stats, info);
+}
+
+int psd_d_syl_update(psd_ctx* c, int n, int p, double* const* T, char orient, int schurindex, int m, double* const* X,
+                     int tile, int d, int trans, int from_t12, psd_syl_geom* geom, int32_t* bounds, int* info) {
+    return sylv_update_host<false>(c, n, p, T, orient, schurindex, m, X, tile, d, trans, from_t12, geom, bounds, info);
+}
+int psd_z_syl_update(psd_ctx* c, int n, int p, double* const* T, char orient, int schurindex, int m, double* const* X,
+                     int tile, int d, int trans, int from_t12, psd_syl_geom* geom, int32_t* bounds, int* info) {
+    return sylv_update_host<true>(c, n, p, T, orient, schurindex, m, X, tile, d, trans, from_t12, geom, bounds, info);
 }
 
 }  // extern "C"

@@ -14,7 +14,22 @@ checks both on the CPU).  The product diagonals come in groups, so that the spli
   d130b  the same seed and block: 127 in [1, 1.5], 3 in [8, 9]; 'L' m = 127, 'R' m = 3
   z20    ComplexF64 n = 20, p = 3, m = 10: the moduli of d20 times the phases of bevec_cases.zdiag
   z130   ComplexF64 n = 130, p = 2, m = 3: 3 in [1, 1.5], 124 in [2.1, 2.4], 3 in [3, 3.5]
-The n = 130 inputs are above the cap of the batch entries (128): psylvester_batch raises NotImplementedPSD on them."""
+The n = 130 inputs are above the cap of the batch entries (128): psylvester_batch raises NotImplementedPSD on them.
+Wide tiles (case_wide_tiles: the update kernel beyond one 16 x 16 fragment, `partition` restates the driver's boundaries):
+  d100   Float64 n = 100, p = 1, m = 50: 50 in [1, 1.5], 50 in [3, 3.5]; 2x2 blocks at rows 15, 31, 47 of T11 and at the
+         same local rows of T22 (65, 81, 97).  In 'L' the tiles are 17 | 16 | 16 | 1 wide at tile width 16 (three moved
+         boundaries: the second fragment row and column of a workgroup hold one row or column), 33 | 17 at 32 (a second
+         sub-block of one row, nsb = 2) and 49 | 1 at 48 (sub-blocks 32 + 17); 24 and 40 cut fragments inside
+  z100   ComplexF64, the same order, split and groups: no boundary moves, the widths 16 ... 48 are full fragments and
+         sub-blocks (48 = 32 + 16, 40 = 32 + 8, 24 = 16 + 8) with the ragged rest of 50
+  d133   Float64 n = 133, p = 2: 130 in [1, 1.5], 3 in [8, 9], a block at row 127; 'L' m = 130, 'R' m = 3.  At tile width
+         128 the boundary 128 of 'L' moves: tiles 129 | 1, above the cap of the batch kernel, nsb = 5, one update
+  the order-70 problems of bsylv_cases.PROBLEMS at tile widths 17, 24 and 32: 33 = 17 + 16 = 24 + 9 = 32 + 1 rows,
+         37 = 17 + 17 + 3 = 24 + 13 = 32 + 5 columns (d: the blocks at rows 10 and 40 move no boundary)
+Kernel cases (sylv_kernel_cases.py: one update launch against an extended-precision reference):
+  d140   Float64 n = 140, p = 2, m = 70: 2x2 blocks at rows 15, 31, 47, 63 of T11, the same local rows of T22, and at the
+         mirrored rows n - 2 - r, so that 'L' and the flip-adjoint 'R' both move the boundaries 16, 32, 48 and 64
+  z140   ComplexF64, the same order and split"""
 import numpy as np
 import pytest
 
@@ -45,6 +60,7 @@ def _zdiag(d, p, seed):
 
 
 TWO20 = ((10, 1.0, 1.5), (10, 3.0, 3.5))
+_PAIRS140 = (15, 31, 47, 63, 85, 101, 117, 133)
 # name: (ComplexF64, n, p, seed, pair rows, the groups of the product diagonals, m in 'L', m in 'R')
 INPUTS = {
     "d20": (False, 20, 3, 23, (3, 7, 13), TWO20, 10, 10),
@@ -55,10 +71,22 @@ INPUTS = {
     # residual only (the Kronecker matrix would have order 12800): GPU tier
     "d160": (False, 160, 2, 11, (30, 77, 120), ((80, 1.0, 1.5), (80, 3.0, 3.5)), 80, 80),
     "z160": (True, 160, 2, 11, (), ((80, 1.0, 1.5), (80, 3.0, 3.5)), 80, 80),
+    # wide tiles
+    "d100": (False, 100, 1, 17, (15, 31, 47, 65, 81, 97), ((50, 1.0, 1.5), (50, 3.0, 3.5)), 50, 50),
+    "z100": (True, 100, 1, 13, (), ((50, 1.0, 1.5), (50, 3.0, 3.5)), 50, 50),
+    "d133": (False, 133, 2, 7, (127,), ((130, 1.0, 1.5), (3, 8.0, 9.0)), 130, 3),
+    # one update launch (sylv_kernel_cases.py): no Kronecker reference
+    "d140": (False, 140, 2, 19, _PAIRS140 + tuple(sorted(138 - r for r in _PAIRS140)), ((70, 1.0, 1.5), (70, 3.0, 3.5)), 70, 70),
+    "z140": (True, 140, 2, 19, (), ((70, 1.0, 1.5), (70, 3.0, 3.5)), 70, 70),
 }
 SMALL = ("d20", "z20")
 BIG = ("d130a", "d130b", "z130")
 RESID = ("d160", "z160")
+WIDE = ("d100", "z100", "d133")
+WIDE_TILES = {"d100": (16, 24, 32, 40, 48), "z100": (16, 24, 32, 40, 48), "d133": (128,)}
+WIDE_BATCH = tuple(sc.IDS.index(i) for i in ("d_n70_p2_m33", "z_n70_p2_m33"))  # at the tile widths WIDE_BATCH_TILES
+WIDE_BATCH_TILES = (17, 24, 32)
+WIDTHS_L = {("d100", 16): [17, 16, 16, 1], ("d100", 32): [33, 17], ("d100", 48): [49, 1], ("d133", 128): [129, 1]}
 
 
 def problem(name, lr):
@@ -176,6 +204,49 @@ def case_small_tiles(eng, name, lr, tile):
     if tile == 4 and name == "d20":  # the boundaries 4 and 8 of T11 and the local 4 of T22 have moved
         assert st.ntiles == 9
     check_cond(eng, "tile %d %s %s" % (tile, name, lr), ps, m, ref)
+
+
+def bounds_of(length, t, sub, off):
+    """The driver's partition restated: boundaries at multiples of t; one that would cut a 2x2 block (sub[off + x - 1]
+    != 0) moves to x + 1, and is dropped if that is the end."""
+    b = [0]
+    for x in range(t, length, t):
+        y = x + 1 if sub is not None and sub[off + x - 1] != 0 else x
+        if y < length:
+            b.append(y)
+    return b + [length]
+
+
+def partition(ps, m, t):
+    """(rb, cb) of the form at tile width t: the rows of T11 and the local columns of T22, cut along the sub-diagonal of
+    the quasi-triangular factor"""
+    Tq = ps.Ts[ps.schurindex - 1]
+    sub = None if np.iscomplexobj(Tq) else np.diag(Tq, -1)
+    return bounds_of(m, t, sub, 0), bounds_of(Tq.shape[0] - m, t, sub, m)
+
+
+def case_wide_tiles(eng, key, lr, tile):
+    """eng: PSD_SYL_TILE=tile.  key: an input of WIDE, or an index of bsylv_cases.PROBLEMS (gates and seeds as
+    case_small_tiles and case_batch_problems have them).  The update kernel runs with tiles wider than one fragment; the
+    number of tiles is that of the restated partition."""
+    if isinstance(key, str):
+        (ps, As, m), ref, tag, seed, gate = problem(key, lr), reference(key, lr), key, 700, None
+    else:
+        (ps, As, m), ref, tag, seed, gate = sc.problem(key, lr), sc.reference(key, lr), sc.IDS[key], 800 + key, GATE
+    tag = "tile %d %s %s" % (tile, tag, lr)
+    rb, cb = partition(ps, m, tile)
+    widths = [b - a for a, b in zip(rb, rb[1:])]
+    print(tag, "tile rows", widths, "tile columns", [b - a for a, b in zip(cb, cb[1:])])
+    if lr == "L" and (key, tile) in WIDTHS_L:
+        assert widths == WIDTHS_L[(key, tile)], widths
+    check_solves(eng, tag, ps, m, ref, seed, ps.Ts[0].shape[0] * EPS if gate is None else gate)
+    check_cond(eng, tag, ps, m, ref)
+    for st in (eng.psylvester_stats, eng.subspacecond_stats):
+        assert st.tile == tile and st.ntiles == (len(rb) - 1) * (len(cb) - 1), (st.asdict(), rb, cb)
+    st = eng.psylvester_stats
+    assert st.nupdate == st.ndiag - 1 > 0 and st.nsolve == st.ndiag, st.asdict()
+    if key == "d133":
+        assert st.ntiles == 2 and st.nupdate == 1, st.asdict()
 
 
 def case_batch_problems(eng, k, lr):

@@ -50,6 +50,19 @@ def test_batch_problems_tile4(tiled, k, lr):
 
 
 @LR
+@pytest.mark.parametrize("name,tile", [(name, t) for name in yc.WIDE for t in yc.WIDE_TILES[name]])
+def test_wide_tiles(tiled, name, lr, tile):
+    yc.case_wide_tiles(tiled(tile), name, lr, tile)
+
+
+@LR
+@pytest.mark.parametrize("tile", yc.WIDE_BATCH_TILES)
+@pytest.mark.parametrize("k", yc.WIDE_BATCH, ids=[sc.IDS[k] for k in yc.WIDE_BATCH])
+def test_wide_tiles_batch_problems(tiled, k, lr, tile):
+    yc.case_wide_tiles(tiled(tile), k, lr, tile)
+
+
+@LR
 @pytest.mark.parametrize("name", yc.BIG)
 def test_above_batch_cap(tiled, name, lr):
     yc.case_above_cap(tiled(None), name, lr)
@@ -64,6 +77,12 @@ def test_one_tile_is_batch_kernel(tiled):
 @pytest.mark.parametrize("name", ["d130a", "z130"])
 def test_repeatable_bits_and_device_entry(tiled, name, lr):
     yc.case_device_equals_host(tiled(None), name, lr)
+
+
+@LR
+@pytest.mark.parametrize("name", ["d100", "z100"])
+def test_repeatable_bits_and_device_entry_tile48(tiled, name, lr):
+    yc.case_device_equals_host(tiled(48), name, lr)
 
 
 @LR

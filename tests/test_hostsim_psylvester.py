@@ -39,7 +39,7 @@ def tiled(monkeypatch):
 
 
 @LR
-@pytest.mark.parametrize("name", yc.SMALL + yc.BIG)
+@pytest.mark.parametrize("name", yc.SMALL + yc.BIG + yc.WIDE)
 def test_reference_inputs(name, lr):
     yc.case_reference_inputs(name, lr)
 
@@ -58,6 +58,19 @@ def test_batch_problems_tile4(tiled, k, lr):
 
 
 @LR
+@pytest.mark.parametrize("name,tile", [(name, t) for name in yc.WIDE for t in yc.WIDE_TILES[name]])
+def test_wide_tiles(tiled, name, lr, tile):
+    yc.case_wide_tiles(tiled(tile), name, lr, tile)
+
+
+@LR
+@pytest.mark.parametrize("tile", yc.WIDE_BATCH_TILES)
+@pytest.mark.parametrize("k", yc.WIDE_BATCH, ids=[sc.IDS[k] for k in yc.WIDE_BATCH])
+def test_wide_tiles_batch_problems(tiled, k, lr, tile):
+    yc.case_wide_tiles(tiled(tile), k, lr, tile)
+
+
+@LR
 @pytest.mark.parametrize("name", yc.BIG)
 def test_above_batch_cap(tiled, name, lr):
     yc.case_above_cap(tiled(None), name, lr)
@@ -71,6 +84,12 @@ def test_one_tile_is_batch_kernel_bits(tiled):
 @pytest.mark.parametrize("name", ["d130a", "z130"])
 def test_repeatable_bits(tiled, name, lr):
     yc.case_repeat(tiled(None), name, lr)
+
+
+@LR
+@pytest.mark.parametrize("name", ["d100", "z100"])
+def test_repeatable_bits_tile48(tiled, name, lr):
+    yc.case_repeat(tiled(48), name, lr)
 
 
 @pytest.mark.parametrize("name", yc.SMALL)
